@@ -10,15 +10,16 @@ A "step" is ONE fisheye key frame through the whole hot path (BASELINE.json conf
     + the D2H copy of every result (key points, descriptors, global descriptors, match lists, query result).
 The timed host loop is C++ (omni-swarm_amd/host/keyframe_pipeline.hpp, the flow of SwarmLoop::VIOKF_callback swarm_loop.cpp:140-170);
 Python prepares the synthetic inputs, starts the run and brackets it with barrier + synchronize.  EXACTLY --steps key frames are
-processed per timed region (a trailing partial micro-batch runs as its own smaller unit); when one region is shorter than --min-time
-it is repeated and the MEDIAN region is reported (`repeats`, `ms_per_step_minmax` say so).
+processed per timed region (a trailing partial micro-batch runs as its own smaller unit); by default ONE region is timed, after --warmup
+key frames; with --min-time, a region shorter than that is repeated and the MEDIAN region is reported (`repeats`, `ms_per_step_minmax` say so).
 
 One process per GPU.  N > 1 (launched by torch.distributed.run): key frames are data parallel, the global index is row-sharded across
 ranks and every micro-batch has one exchange (all_gather of the new rows, all_gather of per-shard top-k).
 
-Prints ONE JSON line on rank 0 (see the task contract) with the extra objects `roofline` (dominant kernel), `roofline_knn`,
-`roofline_knn_batched`, `loop_match`, `db100k` (the same loop against a 100k-key-frame = 400k-row database, fp16 and fp32 rows),
-`value_f32`, `python_host`, `parity` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run measures the headline only.  --full adds the extra objects `roofline`
+(dominant kernel), `roofline_knn`, `roofline_knn_batched`, `loop_match`, `db100k` (the same loop against a 100k-key-frame = 400k-row database,
+fp16 and fp32 rows), `value_f32`, `python_host`, `parity` and `cpu_baseline`.
+--dump-outputs DIR writes what the timed loop returned in its last timed region (loop candidates, hit count, database rows) as .npy files.
 """
 import argparse
 import json
@@ -117,7 +118,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--precision", choices=["f16", "f32", "split"], default="f16")
     ap.add_argument("--host", choices=["cpp", "python"], default="cpp", help="language of the timed host loop")
-    ap.add_argument("--min-time", type=float, default=1.0, help="repeat the timed region of --steps key frames until this many seconds were timed; the median region is reported")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the timed region of --steps key frames until this many seconds were timed; the median region is reported (default: the headline "
+                         "times exactly one region of --steps key frames; the --full legs keep their 1 s, at most 0.5 s per leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the comparison legs (long regions, geometry, Python host, f32, split, configs[4] shard, 100k-key-frame "
+                         "database), the rooflines and stage profiles, the p50 loop-match and batched-search measurements, the CPU baseline and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last timed region as DIR/<name>.npy (float64; the inputs are "
+                         "seeded, so two builds can be compared file by file; bench_outputs/ is git-ignored)")
     ap.add_argument("--db-keyframes", type=int, default=1000, help="key frames pre-loaded in the index (x4 rows) for the throughput loop")
     ap.add_argument("--match-db-rows", type=int, default=100_000, help="index rows for the p50 loop-match measurement (node total)")
     ap.add_argument("--pipelines", type=int, default=0,
@@ -245,8 +254,6 @@ def main():
         rem = steps % MB
         return (pinned_batch(1000 * rank + 8 * MB * POOL, rem), rem) if rem else (None, 0)
 
-    rowgen = RowFactory(7 + rank)
-
     def barrier(*syncs):
         for s in syncs:
             s()
@@ -278,11 +285,13 @@ def main():
 
     own = []                                                   # this rank's own seconds per region of the last timed_regions() call
 
-    def timed_regions(run, sync, steps, warmup, min_time, max_repeats=200):
-        """run(n_steps) processes exactly n_steps key frames.  Warm-up, then regions of `steps` key frames, each bracketed by barrier +
-        synchronize on both sides and reduced with MAX over ranks; repeated until min_time seconds are covered; returns the list."""
+    def timed_regions(run, sync, steps, warmup, min_time, max_repeats=200, prime=None):
+        """run(n_steps) processes exactly n_steps key frames.  Warm-up (+ prime(), untimed), then regions of `steps` key frames, each bracketed by
+        barrier + synchronize on both sides and reduced with MAX over ranks; repeated until min_time seconds are covered; returns the list."""
         if warmup > 0:
             run(warmup)
+        if prime is not None:
+            prime()
         dts = []
         own.clear()
         while True:
@@ -316,7 +325,11 @@ def main():
             out.append(img_cache[key])
         return out
 
-    def cpp_leg(precision, storage, db_rows, steps, warmup, min_time, geometry=False, ptrs=None, mb=None, pipelines=None):
+    def cpp_leg(precision, storage, db_rows, steps, warmup, min_time, geometry=False, ptrs=None, mb=None, pipelines=None, outputs=None, prime=False):
+        """outputs: a dict to receive what the last run() call returned to its caller (the last timed region).  prime: the warm-up also runs one
+        micro-batch on each unit in flight and then, untimed, a region of `steps` key frames when that is short (at most four rounds of the units),
+        else just its trailing partial micro-batch, so that a single timed region does not pay for a unit's first use (the --warmup key frames
+        alone may never reach some units, e.g. 5 key frames = one partial unit)"""
         mb = mb or MB
         # ONE configuration: the library's defaults, whatever --steps is (VERDICT r4 weak 3).  Units in flight: --pipelines, else 0 = the library's default
         # for the precision (KeyframePipeline::default_pipelines: 4 for fp16, 2 for the fp32-class modes); whether the units run oldest-first is the
@@ -345,10 +358,30 @@ def main():
                 pl.host_times(reset=True)
             state["calls"] += 1
             t = tail if n == steps else wtail
-            state["hits"] += pl.run(n, state["id"], ptrs, state["slot"], None if t is None else t.ctypes.data, True)
+            state["last_hits"] = pl.run(n, state["id"], ptrs, state["slot"], None if t is None else t.ctypes.data, True)
+            state["hits"] += state["last_hits"]
+            state["last_first_id"] = state["id"]
             state["id"] += n
             state["slot"] += n // mb
-        dts = timed_regions(run, pl.sync, steps, warmup, min_time)
+
+        def prime_units():
+            one_round = pl.units()[0] * mb                        # key frames: one micro-batch per unit in flight
+            for n in (one_round, steps if steps <= 4 * one_round else steps % mb):
+                if n:
+                    t = tail_for(n)[0] if mb == MB else None
+                    state["hits"] += pl.run(n, state["id"], ptrs, state["slot"], None if t is None else t.ctypes.data, True)
+                    state["id"] += n
+                    state["slot"] += n // mb
+            pl.sync()
+        dts = timed_regions(run, pl.sync, steps, warmup, min_time, prime=prime_units if prime else None)
+        if outputs is not None:
+            # candidates [i] = (new key frame, old key frame, direction_new, direction_old) found for the key frames of the last region, in the order the
+            # detector returned them; the last step = the region's last key frame
+            cand = pl.candidates()
+            cand = cand[cand[:, 0] >= state["last_first_id"]]
+            outputs["loop_candidates"] = cand.astype(np.float64).reshape(-1, 4)
+            outputs["loop_candidates_last_step"] = cand[cand[:, 0] == state["id"] - 1].astype(np.float64).reshape(-1, 4)
+            outputs["hits_and_db_rows"] = np.array([state["last_hits"], pl.db_rows], np.float64)
         out = summarize(dts, steps)
         lat = pl.latencies_ms()
         out.update(db_rows_start=db_rows, db_rows_end=int(pl.db_rows), loop_candidates_found=state["hits"])
@@ -413,6 +446,7 @@ def main():
 
         def finish(self, cam, step, mb):
             out = cam.fetch()
+            self.last_step = (out["images"][4 * (mb - 1):4 * mb], None)    # the micro-batch's last key frame (+ its query result below, N > 1)
             if os.environ.get("OMNI_BENCH_SKIP_DETECTOR") == "1":      # diagnostic only (host/index share of a step); never a reported number
                 return
             if world == 1:
@@ -431,6 +465,7 @@ def main():
                 else:
                     recs = self.det.on_images_recv_batch(frames, rows_dev=cam.vlad.dev_output())
                 self.hits += sum(int(r["old_msg_id"] != -1) for r in recs)
+                self.last_step = (self.last_step[0], recs[-1])
             else:
                 # the micro-batch's mb steps (each: add world*4 rows, query direction 1) in two collectives + one index sync
                 base = self.swarm.ntotal
@@ -439,6 +474,7 @@ def main():
                 else:
                     rows = np.stack([np.stack([i["image_desc"] for i in out["images"][4 * m:4 * m + 4]]) for m in range(mb)])
                     results = self.swarm.step_batch(rows, query_row=1, k=K_SEARCH)
+                self.last_step = (self.last_step[0], results[-1])
                 for m, (D, I) in enumerate(results):
                     nt = base + (m + 1) * world * 4                                 # ntotal as of this key frame's step
                     ok = (I[0] >= 0) & (I[0] <= nt - MATCH_INDEX_DIST) & (D[0] > QUERY_THRES)
@@ -498,30 +534,45 @@ def main():
             t = torch.tensor([ok], device=coll_dev)
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             cpp_host = bool(t.item() > 0.5)
+    head_min_time = 0.0 if args.min_time is None else args.min_time        # default: one region of exactly --steps key frames
+    leg_min_time = 1.0 if args.min_time is None else args.min_time         # the --full legs: min(this, 0.5) each
+    outputs = {}
     if cpp_host:
-        main_leg = cpp_leg(prec, capi.STORE_F32, 4 * args.db_keyframes, args.steps, args.warmup, args.min_time)
+        main_leg = cpp_leg(prec, capi.STORE_F32, 4 * args.db_keyframes, args.steps, args.warmup, head_min_time, outputs=outputs, prime=True)
         hits = main_leg["loop_candidates_found"]
     else:
         pyloop = PythonLoop(prec)
-        dts = timed_regions(pyloop.run, pyloop.sync, args.steps, args.warmup, args.min_time)
+        dts = timed_regions(pyloop.run, pyloop.sync, args.steps, args.warmup, head_min_time)
         main_leg = summarize(dts, args.steps)
         hits = pyloop.hits
+        images, result = pyloop.last_step                      # what the loop fetched for its last key frame
+        for d, im in enumerate(images):
+            for key in ("landmarks_2d", "feature_descriptor", "scores", "image_desc", "ids_up", "ids_down"):
+                outputs[f"last_step_dir{d}_{key}"] = np.asarray(im[key], np.float64)
+        if isinstance(result, dict):                          # N = 1: the detector's record of the key frame
+            outputs["last_step_detector"] = np.array([result["old_msg_id"], result["dir_new"], result["dir_old"]], np.float64)
+        elif result is not None:                              # N > 1: its query's top-k over the sharded database
+            outputs["last_step_query_D"], outputs["last_step_query_I"] = np.asarray(result[0], np.float64), np.asarray(result[1], np.float64)
     kfps = main_leg["value"]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
-    # ---- comparison legs (N = 1 only; bounded) ----------------------------------------------------------------------------------------
+    # ---- comparison legs (N = 1 only; bounded; --full) ----------------------------------------------------------------------------------
     python_host = value_f32 = value_parity = db100k = with_geometry = c5_shard = long_regions = None
-    if world == 1 and cpp_host and args.steps < 8 * MB and args.long_region_steps > 0:
+    if args.full and world == 1 and cpp_host and args.steps < 8 * MB and args.long_region_steps > 0:
         # a timed region shorter than the pipeline is deep (the driver's 20 key frames = 2.5 micro-batches) measures ramp-up and drain, not the rate: the
         # same loop over regions of 200 key frames, for the record (`value` above stays what was asked for)
         n = max(8 * MB, args.long_region_steps // MB * MB)
-        long_regions = cpp_leg(prec, capi.STORE_F32, 4 * args.db_keyframes, n, 4 * MB, min(args.min_time, 0.5))
+        long_regions = cpp_leg(prec, capi.STORE_F32, 4 * args.db_keyframes, n, 4 * MB, min(leg_min_time, 0.5))
         long_regions.update(steps=n, note=f"the headline loop timed over regions of {n} key frames instead of {args.steps}: {args.steps} key frames are "
                                           f"{args.steps / MB:.1f} micro-batches -- the first upload and the last unit's host work are exposed in every region; a "
                                           "running system never drains")
-    if world == 1:
+    if args.full and world == 1:
         if cpp_host and args.geometry_steps > 0:
             n = max(MB, args.geometry_steps // MB * MB)
-            with_geometry = cpp_leg(prec, capi.STORE_F32, 4 * args.db_keyframes, n, MB * (args.pipelines or 4), min(args.min_time, 0.5), geometry=True,
+            with_geometry = cpp_leg(prec, capi.STORE_F32, 4 * args.db_keyframes, n, MB * (args.pipelines or 4), min(leg_min_time, 0.5), geometry=True,
                                     ptrs=[a.ctypes.data for a in room_pool()])
             with_geometry.update(steps=n, note="same loop + the host geometry stage per candidate (lifting, up/down triangulation, BF + homography-RANSAC "
                                                "mask, PnP-RANSAC; f64, host) on key frames of a RENDERED scene (synth.room_keyframe: a stereo rig in textured "
@@ -529,7 +580,7 @@ def main():
         if cpp_host and args.python_steps > 0:
             pyloop = PythonLoop(prec)
             n = max(MB, args.python_steps // MB * MB)
-            python_host = summarize(timed_regions(pyloop.run, pyloop.sync, n, MB * (args.pipelines or 4), min(args.min_time, 0.5)), n)
+            python_host = summarize(timed_regions(pyloop.run, pyloop.sync, n, MB * (args.pipelines or 4), min(leg_min_time, 0.5)), n)
             python_host["steps"] = n
         if args.f32_steps > 0 and args.precision == "f16":
             n = max(MB, args.f32_steps // MB * MB)
@@ -541,7 +592,7 @@ def main():
             value_f32.update(steps=n, dtype="f32", note="OMNI_PREC_F32: exact-f32 MFMA network (key points identical to the fp32 oracle), same workload")
         if args.parity_steps > 0 and args.precision == "f16" and cpp_host:
             n = max(MB, args.parity_steps // MB * MB)
-            value_parity = cpp_leg(capi.PREC_SPLIT, capi.STORE_F32, 4 * args.db_keyframes, n, MB * (args.pipelines or 4), min(args.min_time, 0.5))
+            value_parity = cpp_leg(capi.PREC_SPLIT, capi.STORE_F32, 4 * args.db_keyframes, n, MB * (args.pipelines or 4), min(leg_min_time, 0.5))
             value_parity.update(steps=n, dtype="f16 x3 (split hi+lo operands, fp32-class)",
                                 note="OMNI_PREC_SPLIT: the SAME workload and host loop with SuperPoint's 3x3 convolutions on the fp16 matrix cores at fp32-class "
                                      "accuracy (every operand a (hi, lo) pair of halfs, three MFMA terms per product; heads in exact f32; MobileNetVLAD is "
@@ -552,9 +603,9 @@ def main():
             # MobileNetVLAD images per launch sequence), every micro-batch's 16 queries in ONE matrix-core pass over an fp16 shard
             c5_mb, c5_pipes = 16, 4
             n = c5_mb * c5_pipes * 2
-            c5_shard = cpp_leg(prec, capi.STORE_F16, args.c5_rows, n, c5_mb * c5_pipes, min(args.min_time, 0.5), mb=c5_mb, pipelines=c5_pipes)
+            c5_shard = cpp_leg(prec, capi.STORE_F16, args.c5_rows, n, c5_mb * c5_pipes, min(leg_min_time, 0.5), mb=c5_mb, pipelines=c5_pipes)
             if args.precision == "f16" and args.parity_steps > 0:
-                c5_split = cpp_leg(capi.PREC_SPLIT, capi.STORE_F16, args.c5_rows, n, c5_mb * c5_pipes, min(args.min_time, 0.5), mb=c5_mb, pipelines=c5_pipes)
+                c5_split = cpp_leg(capi.PREC_SPLIT, capi.STORE_F16, args.c5_rows, n, c5_mb * c5_pipes, min(leg_min_time, 0.5), mb=c5_mb, pipelines=c5_pipes)
                 c5_shard["split"] = {k: c5_split[k] for k in ("value", "ms_per_step", "repeats", "keyframe_latency_ms", "db_rows_end", "loop_candidates_found")}
                 c5_shard["split"]["dtype"] = "f16 x3 (split operands, fp32-class): the same leg in the mode that meets north_star's tolerance"
             c5_shard.update(steps=n, shard_rows=args.c5_rows, keyframes_per_microbatch=c5_mb, pipelines=c5_pipes,
@@ -565,183 +616,185 @@ def main():
             db100k = {"db_keyframes": args.big_db_keyframes, "db_rows": 4 * args.big_db_keyframes, "steps": n,
                       "note": "same key-frame loop, every key frame's query scans the whole database (one pass per micro-batch, per-query row limits)"}
             for name, st in (("f16_rows", capi.STORE_F16), ("f32_rows", capi.STORE_F32)):
-                db100k[name] = cpp_leg(prec, st, 4 * args.big_db_keyframes, n, MB * (args.pipelines or 4), min(args.min_time, 0.5))
+                db100k[name] = cpp_leg(prec, st, 4 * args.big_db_keyframes, n, MB * (args.pipelines or 4), min(leg_min_time, 0.5))
             if args.precision == "f16" and args.parity_steps > 0:
                 # north_star's "against a 100k-keyframe DB" in the mode that meets its tolerance: OMNI_PREC_SPLIT, exact fp32 rows
-                db100k["split_f32_rows"] = cpp_leg(capi.PREC_SPLIT, capi.STORE_F32, 4 * args.big_db_keyframes, n, MB * (args.pipelines or 2), min(args.min_time, 0.5))
+                db100k["split_f32_rows"] = cpp_leg(capi.PREC_SPLIT, capi.STORE_F32, 4 * args.big_db_keyframes, n, MB * (args.pipelines or 2), min(leg_min_time, 0.5))
                 db100k["split_f32_rows"]["dtype"] = "f16 x3 (split operands, fp32-class): key points identical to the fp32 oracle (parity_split)"
 
-    # ---- roofline of the dominant kernel (conv1b + pool, 43 % of the FLOPs): HIP events on the kernel's own stream --
-    # same launch shape as in the timed loop: one micro-batch = 8 * MB images per launch (HIP events between the stages, on the
-    # kernels' own stream); stage times are then quoted per key frame (8 images)
-    n_img = KF_IMAGES * MB
-    if pyloop is not None:
-        prof_sp = pyloop.cams[0].sp
-    else:
-        prof_sp = capi.SuperPoint(ictx, sp_w, comp, mean, W, H, THRES, MAXN, prec, n_img)
-    pool_dev = ictx.to_device(pool[0])
-    prof = prof_sp.profile(pool_dev, W, n_img, reps=21)
-    conv_ms = sum(p["ms"] for p in prof if p["stage"].startswith("conv")) / MB
-    sp_ms = sum(p["ms"] for p in prof) / MB
-    peak = PEAK_F32_TFLOPS if args.precision == "f32" else PEAK_F16_TFLOPS
-    left_out_flop = sum(p["flops_per_image"] * p["tiles_left_out"] for p in prof)       # per image, by the library's own plan
-
-    def conv1b_roofline(stages, precision):
-        """`frac` = FLOP the launch EXECUTED / its HIP-event time / peak: the tiles that ran (a fisheye-masked pass leaves the constant region of the mask
-        out of the tile walk) x 3 MFMA terms per product in OMNI_PREC_SPLIT; the layer's algorithmic FLOP / time is kept as frac_algorithmic."""
-        c1b = next(p for p in stages if p["stage"].startswith("conv1b"))
-        alg = c1b["flops_per_image"] * n_img
-        split = precision == "split"
-        wino = split and (capi.config_value("OMNI_SPLIT_WINO") & 1) != 0      # conv1b as the Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip): 16 products per 2 x 2 outputs, not 36
-        # OMNI_PREC_SPLIT executes three fp16 MFMA terms per product; the Winograd form has 16 / 36 of the direct form's products: 4/3 of the algorithmic FLOP
-        terms = (3.0 * 16.0 / 36.0 if wino else 3.0) if split else 1.0
-        executed = terms * alg * (1.0 - c1b["tiles_left_out"])
-        t = c1b["ms"] * 1e-3
-        pk = PEAK_F32_TFLOPS if precision == "f32" else PEAK_F16_TFLOPS
-        trace = rocprof_trace(("conv3x3_wino_kernelILb1ELb0ELb1" if wino else "conv3x3_split_kernelILb0ELb1ELb0ELb0ELb1") if split else "conv3x3_c64_pp_kernelILb1ELi0ELb1")
-        return {"bound": "mfma",
-                "kernel": ("conv3x3_wino_kernel<POOL, FUSE1A> = conv1a (built tile by tile from the u8 image, on the matrix cores) + conv1b 3x3 64->64 as Winograd F(2x2,3x3) + ReLU + maxpool2 "
-                           "with split (hi, lo) fp16 operands: 16 x 3 MFMA terms per 2 x 2 outputs and input channel (the direct form: 36 x 3) -- `frac` counts the MFMA FLOP the "
-                           "kernel executes (4/3 of the layer's algorithmic FLOP), `frac_algorithmic` the layer's own FLOP: the fraction that says how fast the LAYER runs; "
-                           "FLOP counted for conv1b only" if wino else
-                           "conv3x3_split_kernel<cin 64, POOL, FUSE1A> = conv1a (built tile by tile from the u8 image, on the matrix cores) + conv1b 3x3 64->64 + ReLU + maxpool2 with split "
-                           "(hi, lo) fp16 operands: three MFMA terms per product; FLOP counted for conv1b only" if split else
-                           "conv3x3_c64_pp_kernel<POOL, FUSE1A> = conv1a (u8 -> 64 ch, on the matrix cores) + conv1b 3x3 64->64 + ReLU + maxpool2 in one launch; "
-                           "FLOP counted for conv1b only"),
-                "achieved": round(executed / t / 1e12, 1), "peak": pk, "unit": "TFLOP/s", "frac": round(executed / t / 1e12 / pk, 4),
-                "definition": "achieved = MFMA FLOP of the tiles the launch ran / HIP-event time between the stage markers on the kernel's own stream",
-                "flop_executed_per_launch": executed, "launch_ms": round(c1b["ms"], 4), "images_per_launch": n_img, "tiles_left_out": round(c1b["tiles_left_out"], 4),
-                "flop_algorithmic_per_launch": alg, "achieved_algorithmic": round(alg / t / 1e12, 1), "frac_algorithmic": round(alg / t / 1e12 / pk, 4),
-                "rocprof_trace": trace,
-                "rocprof_trace_note": "median launch duration of the same kernel under rocprofv3 --kernel-trace (committed summary); frac recomputed from it = "
-                                      + (str(round(executed / (trace["median_us"] * 1e-6) / 1e12 / pk, 4)) if trace else "n/a: no trace committed yet"),
-                **(traffic_fields("conv3x3_wino_kernel<POOL,FUSE1A> (conv1b)" if wino else "conv3x3_split_kernel<cin64,POOL,FUSE1A> (conv1b)", True, n_img) if split else
-                   traffic_fields("conv3x3_c64_pp_kernel<POOL,FUSE1A>", precision == "f16", n_img))}
-
-    roofline = conv1b_roofline(prof, args.precision)
-    if args.precision != "f32" and rank == 0:
-        # what THIS board's fp16 matrix cores sustain (omni_ctx_mfma_ceiling: back-to-back MFMAs on every SIMD, ~0.1 s): `peak` is the guide's figure at the
-        # 2.4 GHz engine clock; saturated matrix cores run at the clock the power budget leaves (profiles/r05u_mfma_ceiling_probe.log: ~1.95 GHz, 2.0 PFLOP/s)
-        try:
-            cal = ictx.mfma_ceiling(100.0)
-            roofline["measured_ceiling"] = {"tflops": round(cal["tflops"], 1), "sclk_ghz": round(cal["sclk_ghz"], 3), "frac_of_peak": round(cal["tflops"] / PEAK_F16_TFLOPS, 4),
-                                            "frac_of_measured_ceiling": round(roofline["achieved"] / cal["tflops"], 4) if cal["tflops"] > 0 else None,
-                                            "definition": "v_mfma_f32_32x32x16_f16 back to back on every SIMD of this GPU for ~0.1 s, no memory traffic: TFLOP/s by HIP events, "
-                                                          "shader clock by s_memtime against s_memrealtime; extra information -- `frac` stays against `peak`"}
-        except Exception as e:                                    # noqa: BLE001
-            roofline["measured_ceiling"] = {"error": str(e)}
-    try:
-        _vl = capi.MobileNetVLAD(ictx, vl_w, vl_specs, *vl_shape, W, H, 1)
-        vlad_left_out = [round(f, 4) for f in _vl.mask_skip_layers()]
-        _vl.close()
-    except Exception as e:                                        # noqa: BLE001
-        vlad_left_out = str(e)
-    roofline.update({
-        "mask_skip": {"note": "stage times with the fisheye mask on, as the key-frame pipeline runs the network (loop_cam.cpp:536-539): the tiles whose whole "
-                              "receptive field lies in the blanked rows hold one constant vector per layer, written once, and are left out of the tile walk "
-                              "(bit-identical: tests/test_gpu_mask_skip.py; OMNI_SP_MASK_SKIP=0 / OMNI_SP_MASK_SKIP_SPLIT=0 = the dense pass)",
-                      "tiles_left_out": {p["stage"]: round(p["tiles_left_out"], 4) for p in prof if p["tiles_left_out"] > 0},
-                      "mobilenetvlad_tiles_left_out": vlad_left_out,
-                      "mobilenetvlad_note": "the same for MobileNetVLAD (the frame is blanked before both networks, loop_cam.cpp:536-539, 556-558): stem + block 0, blocks 1, 2, ... "
-                                            "(csrc/vlad.hip, omni_vlad::MaskSkip; OMNI_VLAD_MASK_SKIP=0 = the dense pass; tests/test_gpu_vlad_detector.py)"},
-        "conv_stack_tflops": round(mfma_terms_of(args.precision) * sp_flop_executed(args.precision, MAXN, True, left_out_flop) * KF_IMAGES / (conv_ms * 1e-3) / 1e12, 1),
-        "conv_stack_note": "MFMA FLOP executed by the stages named conv* (fp16 path: without convDa / convDb, which run only at the cells around the key points "
-                           "inside the post-processing stage; split: x 3 terms of the direct form for every layer -- the layers OMNI_SPLIT_WINO runs as Winograd kernels execute 4/3 -- so this is a rate of useful work) / their time",
-        "stages_ms_per_keyframe": {p["stage"]: round(p["ms"] / MB, 4) for p in prof}, "superpoint_ms_per_keyframe": round(sp_ms, 3)})
-    # the same kernel figure for the precision that meets north_star's tolerance (value_parity's conv1b), in the default run
-    roofline_parity = None
-    if args.precision == "f16" and args.parity_steps > 0 and world == 1:
-        sp_split = capi.SuperPoint(ictx, sp_w, comp, mean, W, H, THRES, MAXN, capi.PREC_SPLIT, n_img)
-        prof_s = sp_split.profile(pool_dev, W, n_img, reps=11)
-        sp_split.close()
-        roofline_parity = conv1b_roofline(prof_s, "split")
-        roofline_parity.update({"stages_ms_per_keyframe": {p["stage"]: round(p["ms"] / MB, 4) for p in prof_s},
-                                "superpoint_ms_per_keyframe": round(sum(p["ms"] for p in prof_s) / MB, 3),
-                                "tiles_left_out_by_stage": {p["stage"]: round(p["tiles_left_out"], 4) for p in prof_s if p["tiles_left_out"] > 0}})
-        mc = roofline.get("measured_ceiling") or {}
-        if mc.get("tflops"):
-            roofline_parity["measured_ceiling"] = {"tflops": mc["tflops"], "sclk_ghz": mc["sclk_ghz"], "frac_of_measured_ceiling": round(roofline_parity["achieved"] / mc["tflops"], 4),
-                                                   "definition": "see roofline.measured_ceiling"}
-    ictx.free(pool_dev)
-
-    # ---- p50 loop-match latency on big DBs (node total rows, sharded when N > 1): 100k rows and 100k key frames = 400k rows ----------
-    def p50_leg(total_rows):
-        rows_here = total_rows // world
-        midx = capi.IndexFlatIP(ictx, 4096, capi.STORE_F32, rows_here)
-        gen = RowFactory(11 + rank)
-        if world == 1:
-            for s in range(0, rows_here, 32768):
-                midx.add(gen.rows(min(32768, rows_here - s)))
-        mq = RowFactory(99).rows(1)
-        native_p50 = world > 1 and cpp_host
-        if world > 1 and not native_p50:
-            big = shard.ShardedIndex(midx, rank, world, dist, coll_dev)
-            for s in range(0, rows_here, 32768):
-                midx.add(gen.rows(min(32768, rows_here - s)))
-            search = lambda: big.search(mq, K_SEARCH)
-        elif world > 1:
-            big = capi.Shard(ictx, midx, rank, world, shard_uid())
-            for s in range(0, rows_here, 32768):
-                big.local.add(gen.rows(min(32768, rows_here - s)))
-            search = lambda: big.search(mq, K_SEARCH)
+    roofline = roofline_parity = roofline_knn = loop_match = batched = cpu = parity = parity_split = None
+    if args.full:
+        # ---- roofline of the dominant kernel (conv1b + pool, 43 % of the FLOPs): HIP events on the kernel's own stream --
+        # same launch shape as in the timed loop: one micro-batch = 8 * MB images per launch (HIP events between the stages, on the
+        # kernels' own stream); stage times are then quoted per key frame (8 images)
+        n_img = KF_IMAGES * MB
+        if pyloop is not None:
+            prof_sp = pyloop.cams[0].sp
         else:
-            search = lambda: midx.search(mq, K_SEARCH)
-        lat, scan = [], []
-        for i in range(60):
-            if dist is not None:
-                dist.barrier()
-            t = time.perf_counter()
-            search()
-            lat.append((time.perf_counter() - t) * 1e3)
-            scan.append(midx.last_scan_ms())
-        p50 = reduce_max(float(np.median(lat[10:])))
-        scan_ms = float(np.median(scan[10:]))
-        if world > 1 and native_p50:
-            big.close()
-        midx.close()
-        return p50, scan_ms, rows_here
+            prof_sp = capi.SuperPoint(ictx, sp_w, comp, mean, W, H, THRES, MAXN, prec, n_img)
+        pool_dev = ictx.to_device(pool[0])
+        prof = prof_sp.profile(pool_dev, W, n_img, reps=21)
+        conv_ms = sum(p["ms"] for p in prof if p["stage"].startswith("conv")) / MB
+        sp_ms = sum(p["ms"] for p in prof) / MB
+        peak = PEAK_F32_TFLOPS if args.precision == "f32" else PEAK_F16_TFLOPS
+        left_out_flop = sum(p["flops_per_image"] * p["tiles_left_out"] for p in prof)       # per image, by the library's own plan
 
-    p50, scan_ms, rows_here = p50_leg(args.match_db_rows)
-    gbs = rows_here * 4096 * 4 / (scan_ms * 1e-3) / 1e9
-    roofline_knn = {"bound": "hbm", "kernel": "ip_scan_kernel<float,1>", "achieved": round(gbs, 0), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": round(gbs / PEAK_HBM_GBS, 4),
-                    **traffic_fields(f"ip_scan_kernel<float,1>@{rows_here}"), "bytes_per_launch": rows_here * 16384,
-                    "launch_ms": round(scan_ms, 4), "rows_per_gpu": rows_here}
-    loop_match = {"p50_ms": round(p50, 4), "db_rows_node": args.match_db_rows, "db_rows_per_gpu": rows_here, "k": K_SEARCH,
-                  "includes": "H2D query, scan, top-k, D2H result" + (", all_gather + merge" if world > 1 else "")}
-    if args.match_db_rows != 400_000:
-        p50b, scan_b, rows_b = p50_leg(400_000)
-        loop_match["db_100k_keyframes"] = {"p50_ms": round(p50b, 4), "db_rows_node": 400_000, "db_rows_per_gpu": rows_b, "scan_ms": round(scan_b, 4),
-                                           "scan_gbs": round(rows_b * 16384 / (scan_b * 1e-3) / 1e9, 0)}
+        def conv1b_roofline(stages, precision):
+            """`frac` = FLOP the launch EXECUTED / its HIP-event time / peak: the tiles that ran (a fisheye-masked pass leaves the constant region of the mask
+            out of the tile walk) x 3 MFMA terms per product in OMNI_PREC_SPLIT; the layer's algorithmic FLOP / time is kept as frac_algorithmic."""
+            c1b = next(p for p in stages if p["stage"].startswith("conv1b"))
+            alg = c1b["flops_per_image"] * n_img
+            split = precision == "split"
+            wino = split and (capi.config_value("OMNI_SPLIT_WINO") & 1) != 0      # conv1b as the Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip): 16 products per 2 x 2 outputs, not 36
+            # OMNI_PREC_SPLIT executes three fp16 MFMA terms per product; the Winograd form has 16 / 36 of the direct form's products: 4/3 of the algorithmic FLOP
+            terms = (3.0 * 16.0 / 36.0 if wino else 3.0) if split else 1.0
+            executed = terms * alg * (1.0 - c1b["tiles_left_out"])
+            t = c1b["ms"] * 1e-3
+            pk = PEAK_F32_TFLOPS if precision == "f32" else PEAK_F16_TFLOPS
+            trace = rocprof_trace(("conv3x3_wino_kernelILb1ELb0ELb1" if wino else "conv3x3_split_kernelILb0ELb1ELb0ELb0ELb1") if split else "conv3x3_c64_pp_kernelILb1ELi0ELb1")
+            return {"bound": "mfma",
+                    "kernel": ("conv3x3_wino_kernel<POOL, FUSE1A> = conv1a (built tile by tile from the u8 image, on the matrix cores) + conv1b 3x3 64->64 as Winograd F(2x2,3x3) + ReLU + maxpool2 "
+                               "with split (hi, lo) fp16 operands: 16 x 3 MFMA terms per 2 x 2 outputs and input channel (the direct form: 36 x 3) -- `frac` counts the MFMA FLOP the "
+                               "kernel executes (4/3 of the layer's algorithmic FLOP), `frac_algorithmic` the layer's own FLOP: the fraction that says how fast the LAYER runs; "
+                               "FLOP counted for conv1b only" if wino else
+                               "conv3x3_split_kernel<cin 64, POOL, FUSE1A> = conv1a (built tile by tile from the u8 image, on the matrix cores) + conv1b 3x3 64->64 + ReLU + maxpool2 with split "
+                               "(hi, lo) fp16 operands: three MFMA terms per product; FLOP counted for conv1b only" if split else
+                               "conv3x3_c64_pp_kernel<POOL, FUSE1A> = conv1a (u8 -> 64 ch, on the matrix cores) + conv1b 3x3 64->64 + ReLU + maxpool2 in one launch; "
+                               "FLOP counted for conv1b only"),
+                    "achieved": round(executed / t / 1e12, 1), "peak": pk, "unit": "TFLOP/s", "frac": round(executed / t / 1e12 / pk, 4),
+                    "definition": "achieved = MFMA FLOP of the tiles the launch ran / HIP-event time between the stage markers on the kernel's own stream",
+                    "flop_executed_per_launch": executed, "launch_ms": round(c1b["ms"], 4), "images_per_launch": n_img, "tiles_left_out": round(c1b["tiles_left_out"], 4),
+                    "flop_algorithmic_per_launch": alg, "achieved_algorithmic": round(alg / t / 1e12, 1), "frac_algorithmic": round(alg / t / 1e12 / pk, 4),
+                    "rocprof_trace": trace,
+                    "rocprof_trace_note": "median launch duration of the same kernel under rocprofv3 --kernel-trace (committed summary); frac recomputed from it = "
+                                          + (str(round(executed / (trace["median_us"] * 1e-6) / 1e12 / pk, 4)) if trace else "n/a: no trace committed yet"),
+                    **(traffic_fields("conv3x3_wino_kernel<POOL,FUSE1A> (conv1b)" if wino else "conv3x3_split_kernel<cin64,POOL,FUSE1A> (conv1b)", True, n_img) if split else
+                       traffic_fields("conv3x3_c64_pp_kernel<POOL,FUSE1A>", precision == "f16", n_img))}
 
-    # ---- BASELINE config 5 per-GPU shard: 64 concurrent queries against 1 M key frames / 8 GPUs = 125 000 fp16 rows --------------
-    batched = None
-    if args.batched_rows > 0:
-        bidx = capi.IndexFlatIP(ictx, 4096, capi.STORE_F16, args.batched_rows)
-        gen = RowFactory(13 + rank)
-        for s in range(0, args.batched_rows, 32768):
-            bidx.add(gen.rows(min(32768, args.batched_rows - s)))
-        bq = RowFactory(98).rows(64)
-        blat, bscan = [], []
-        for i in range(30):
-            t = time.perf_counter()
-            bidx.search(bq, K_SEARCH)
-            blat.append((time.perf_counter() - t) * 1e3)
-            bscan.append(bidx.last_scan_ms())
-        b_ms, b_p50 = float(np.median(bscan[8:])), float(np.median(blat[8:]))
-        b_bytes = args.batched_rows * (4096 * 2 + 64 * 8)            # every fp16 row read once + one 64-bit key per (query, row)
-        batched = {"bound": "hbm", "kernel": "ip_scan_mq_kernel (64 queries, fp16 rows, v_mfma_f32_16x16x32_f16)",
-                   "achieved": round(b_bytes / (b_ms * 1e-3) / 1e9, 0), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                   "frac": round(b_bytes / (b_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), **traffic_fields("ip_scan_mq_kernel", args.batched_rows == 125_000),
-                   "bytes_per_launch": b_bytes, "launch_ms": round(b_ms, 4), "rows_per_gpu": args.batched_rows, "queries": 64,
-                   "search_p50_ms": round(b_p50, 4), "queries_per_s": round(64 / (b_p50 * 1e-3), 0)}
-        bidx.close()
+        roofline = conv1b_roofline(prof, args.precision)
+        if args.precision != "f32" and rank == 0:
+            # what THIS board's fp16 matrix cores sustain (omni_ctx_mfma_ceiling: back-to-back MFMAs on every SIMD, ~0.1 s): `peak` is the guide's figure at the
+            # 2.4 GHz engine clock; saturated matrix cores run at the clock the power budget leaves (profiles/r05u_mfma_ceiling_probe.log: ~1.95 GHz, 2.0 PFLOP/s)
+            try:
+                cal = ictx.mfma_ceiling(100.0)
+                roofline["measured_ceiling"] = {"tflops": round(cal["tflops"], 1), "sclk_ghz": round(cal["sclk_ghz"], 3), "frac_of_peak": round(cal["tflops"] / PEAK_F16_TFLOPS, 4),
+                                                "frac_of_measured_ceiling": round(roofline["achieved"] / cal["tflops"], 4) if cal["tflops"] > 0 else None,
+                                                "definition": "v_mfma_f32_32x32x16_f16 back to back on every SIMD of this GPU for ~0.1 s, no memory traffic: TFLOP/s by HIP events, "
+                                                              "shader clock by s_memtime against s_memrealtime; extra information -- `frac` stays against `peak`"}
+            except Exception as e:                                    # noqa: BLE001
+                roofline["measured_ceiling"] = {"error": str(e)}
+        try:
+            _vl = capi.MobileNetVLAD(ictx, vl_w, vl_specs, *vl_shape, W, H, 1)
+            vlad_left_out = [round(f, 4) for f in _vl.mask_skip_layers()]
+            _vl.close()
+        except Exception as e:                                        # noqa: BLE001
+            vlad_left_out = str(e)
+        roofline.update({
+            "mask_skip": {"note": "stage times with the fisheye mask on, as the key-frame pipeline runs the network (loop_cam.cpp:536-539): the tiles whose whole "
+                                  "receptive field lies in the blanked rows hold one constant vector per layer, written once, and are left out of the tile walk "
+                                  "(bit-identical: tests/test_gpu_mask_skip.py; OMNI_SP_MASK_SKIP=0 / OMNI_SP_MASK_SKIP_SPLIT=0 = the dense pass)",
+                          "tiles_left_out": {p["stage"]: round(p["tiles_left_out"], 4) for p in prof if p["tiles_left_out"] > 0},
+                          "mobilenetvlad_tiles_left_out": vlad_left_out,
+                          "mobilenetvlad_note": "the same for MobileNetVLAD (the frame is blanked before both networks, loop_cam.cpp:536-539, 556-558): stem + block 0, blocks 1, 2, ... "
+                                                "(csrc/vlad.hip, omni_vlad::MaskSkip; OMNI_VLAD_MASK_SKIP=0 = the dense pass; tests/test_gpu_vlad_detector.py)"},
+            "conv_stack_tflops": round(mfma_terms_of(args.precision) * sp_flop_executed(args.precision, MAXN, True, left_out_flop) * KF_IMAGES / (conv_ms * 1e-3) / 1e12, 1),
+            "conv_stack_note": "MFMA FLOP executed by the stages named conv* (fp16 path: without convDa / convDb, which run only at the cells around the key points "
+                               "inside the post-processing stage; split: x 3 terms of the direct form for every layer -- the layers OMNI_SPLIT_WINO runs as Winograd kernels execute 4/3 -- so this is a rate of useful work) / their time",
+            "stages_ms_per_keyframe": {p["stage"]: round(p["ms"] / MB, 4) for p in prof}, "superpoint_ms_per_keyframe": round(sp_ms, 3)})
+        # the same kernel figure for the precision that meets north_star's tolerance (value_parity's conv1b), in the default run
+        roofline_parity = None
+        if args.precision == "f16" and args.parity_steps > 0 and world == 1:
+            sp_split = capi.SuperPoint(ictx, sp_w, comp, mean, W, H, THRES, MAXN, capi.PREC_SPLIT, n_img)
+            prof_s = sp_split.profile(pool_dev, W, n_img, reps=11)
+            sp_split.close()
+            roofline_parity = conv1b_roofline(prof_s, "split")
+            roofline_parity.update({"stages_ms_per_keyframe": {p["stage"]: round(p["ms"] / MB, 4) for p in prof_s},
+                                    "superpoint_ms_per_keyframe": round(sum(p["ms"] for p in prof_s) / MB, 3),
+                                    "tiles_left_out_by_stage": {p["stage"]: round(p["tiles_left_out"], 4) for p in prof_s if p["tiles_left_out"] > 0}})
+            mc = roofline.get("measured_ceiling") or {}
+            if mc.get("tflops"):
+                roofline_parity["measured_ceiling"] = {"tflops": mc["tflops"], "sclk_ghz": mc["sclk_ghz"], "frac_of_measured_ceiling": round(roofline_parity["achieved"] / mc["tflops"], 4),
+                                                       "definition": "see roofline.measured_ceiling"}
+        ictx.free(pool_dev)
 
-    # ---- CPU baseline: the reference's PyTorch-CPU SuperPoint path + oracle post-processing, same host; and, with the oracle's outputs
-    # of that sample at hand, how far the GPU path at the benchmarked precision is from them (`parity`) -------------------------------
-    cpu = parity = parity_split = None
-    if rank == 0 and not args.no_cpu_baseline:
-        cpu, parity, parity_split = cpu_baseline(args.cpu_keyframes, W, H, THRES, MAXN, comp, mean, sp_w, vl_w, vl_specs, vl_shape, capi, ictx, prec)
+        # ---- p50 loop-match latency on big DBs (node total rows, sharded when N > 1): 100k rows and 100k key frames = 400k rows ----------
+        def p50_leg(total_rows):
+            rows_here = total_rows // world
+            midx = capi.IndexFlatIP(ictx, 4096, capi.STORE_F32, rows_here)
+            gen = RowFactory(11 + rank)
+            if world == 1:
+                for s in range(0, rows_here, 32768):
+                    midx.add(gen.rows(min(32768, rows_here - s)))
+            mq = RowFactory(99).rows(1)
+            native_p50 = world > 1 and cpp_host
+            if world > 1 and not native_p50:
+                big = shard.ShardedIndex(midx, rank, world, dist, coll_dev)
+                for s in range(0, rows_here, 32768):
+                    midx.add(gen.rows(min(32768, rows_here - s)))
+                search = lambda: big.search(mq, K_SEARCH)
+            elif world > 1:
+                big = capi.Shard(ictx, midx, rank, world, shard_uid())
+                for s in range(0, rows_here, 32768):
+                    big.local.add(gen.rows(min(32768, rows_here - s)))
+                search = lambda: big.search(mq, K_SEARCH)
+            else:
+                search = lambda: midx.search(mq, K_SEARCH)
+            lat, scan = [], []
+            for i in range(60):
+                if dist is not None:
+                    dist.barrier()
+                t = time.perf_counter()
+                search()
+                lat.append((time.perf_counter() - t) * 1e3)
+                scan.append(midx.last_scan_ms())
+            p50 = reduce_max(float(np.median(lat[10:])))
+            scan_ms = float(np.median(scan[10:]))
+            if world > 1 and native_p50:
+                big.close()
+            midx.close()
+            return p50, scan_ms, rows_here
+
+        p50, scan_ms, rows_here = p50_leg(args.match_db_rows)
+        gbs = rows_here * 4096 * 4 / (scan_ms * 1e-3) / 1e9
+        roofline_knn = {"bound": "hbm", "kernel": "ip_scan_kernel<float,1>", "achieved": round(gbs, 0), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": round(gbs / PEAK_HBM_GBS, 4),
+                        **traffic_fields(f"ip_scan_kernel<float,1>@{rows_here}"), "bytes_per_launch": rows_here * 16384,
+                        "launch_ms": round(scan_ms, 4), "rows_per_gpu": rows_here}
+        loop_match = {"p50_ms": round(p50, 4), "db_rows_node": args.match_db_rows, "db_rows_per_gpu": rows_here, "k": K_SEARCH,
+                      "includes": "H2D query, scan, top-k, D2H result" + (", all_gather + merge" if world > 1 else "")}
+        if args.match_db_rows != 400_000:
+            p50b, scan_b, rows_b = p50_leg(400_000)
+            loop_match["db_100k_keyframes"] = {"p50_ms": round(p50b, 4), "db_rows_node": 400_000, "db_rows_per_gpu": rows_b, "scan_ms": round(scan_b, 4),
+                                               "scan_gbs": round(rows_b * 16384 / (scan_b * 1e-3) / 1e9, 0)}
+
+        # ---- BASELINE config 5 per-GPU shard: 64 concurrent queries against 1 M key frames / 8 GPUs = 125 000 fp16 rows --------------
+        batched = None
+        if args.batched_rows > 0:
+            bidx = capi.IndexFlatIP(ictx, 4096, capi.STORE_F16, args.batched_rows)
+            gen = RowFactory(13 + rank)
+            for s in range(0, args.batched_rows, 32768):
+                bidx.add(gen.rows(min(32768, args.batched_rows - s)))
+            bq = RowFactory(98).rows(64)
+            blat, bscan = [], []
+            for i in range(30):
+                t = time.perf_counter()
+                bidx.search(bq, K_SEARCH)
+                blat.append((time.perf_counter() - t) * 1e3)
+                bscan.append(bidx.last_scan_ms())
+            b_ms, b_p50 = float(np.median(bscan[8:])), float(np.median(blat[8:]))
+            b_bytes = args.batched_rows * (4096 * 2 + 64 * 8)            # every fp16 row read once + one 64-bit key per (query, row)
+            batched = {"bound": "hbm", "kernel": "ip_scan_mq_kernel (64 queries, fp16 rows, v_mfma_f32_16x16x32_f16)",
+                       "achieved": round(b_bytes / (b_ms * 1e-3) / 1e9, 0), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                       "frac": round(b_bytes / (b_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), **traffic_fields("ip_scan_mq_kernel", args.batched_rows == 125_000),
+                       "bytes_per_launch": b_bytes, "launch_ms": round(b_ms, 4), "rows_per_gpu": args.batched_rows, "queries": 64,
+                       "search_p50_ms": round(b_p50, 4), "queries_per_s": round(64 / (b_p50 * 1e-3), 0)}
+            bidx.close()
+
+        # ---- CPU baseline: the reference's PyTorch-CPU SuperPoint path + oracle post-processing, same host; and, with the oracle's outputs
+        # of that sample at hand, how far the GPU path at the benchmarked precision is from them (`parity`) -------------------------------
+        cpu = parity = parity_split = None
+        if rank == 0 and not args.no_cpu_baseline:
+            cpu, parity, parity_split = cpu_baseline(args.cpu_keyframes, W, H, THRES, MAXN, comp, mean, sp_w, vl_w, vl_specs, vl_shape, capi, ictx, prec)
 
     librccl = None
     rccl_mapped = None
@@ -770,19 +823,11 @@ def main():
         line = {
             "metric": "keyframes/sec (4x fisheye 600x480) + p50 loop-match ms @ 100k-frame DB",
             "value": kfps, "unit": "keyframes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            # the honesty gate: is `value` a number INSIDE north_star's tolerance (key-point indices bit-exact, descriptors / VLAD vectors
-            # within 1e-3)?  fp16 -- the reference's own engine precision (launch/realsense.launch:10-11) -- is not; the mode that is runs at
-            # `value_within_north_star_tolerance` (= value_parity.value, OMNI_PREC_SPLIT, same workload and host loop, same run)
-            "within_north_star_tolerance": None if headline_gate is None else headline_gate["within_north_star_tolerance"],
-            "parity_gate": {"headline": headline_gate, "value_parity": split_gate},
-            "value_within_north_star_tolerance": (kfps if (headline_gate or {}).get("within_north_star_tolerance") else
-                                                  (value_parity or {}).get("value") if (split_gate or {}).get("within_north_star_tolerance") else None),
             "ms_per_step": main_leg["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": {"f16": "f16", "f32": "f32", "split": "f16 x3 (split operands)"}[args.precision], "data": "synthetic",
             "repeats": main_leg["repeats"], "ms_per_step_minmax": main_leg["ms_per_step_minmax"],
             "keyframe_latency_ms": main_leg.get("keyframe_latency_ms"),
             "host_ms_per_microbatch": main_leg.get("host_ms_per_microbatch"),
-            "value_long_regions": long_regions,
             "config": {"workload": "configs[1]: reference-faithful fisheye key frame = upload of 8 images + 8 SuperPoint + 4 MobileNetVLAD(assumed arch) "
                                    "images 600x480 + 4 up/down BF matches + <=4 index inserts + top-k query + results to host; "
                                    f"{args.db_keyframes}-keyframe DB ({4 * args.db_keyframes} rows); seeded synthetic weights",
@@ -793,17 +838,28 @@ def main():
                        "parallelism": f"dp{world} keyframes + {world}-way row-sharded index" if world > 1 else "single GPU",
                        "device": info["name"], "n_cu": info["n_cu"]},
             "loop_candidates_found": hits,
-            "gflop_per_keyframe_superpoint": round(sp_flop_executed(args.precision, MAXN, False, left_out_flop) * KF_IMAGES / 1e9, 1),
             "gflop_per_keyframe_superpoint_dense": round(SP_FLOP_PER_IMAGE * KF_IMAGES / 1e9, 1),
-            "achieved_tflops_end_to_end": round(kfps * sp_flop_executed(args.precision, MAXN, False, left_out_flop) * KF_IMAGES / 1e12 / world, 1),
             "rccl_ranks": world if (world > 1 and cpp_host) else (1 if world == 1 else 0), "librccl": librccl, "librccl_mapped_in_process": rccl_mapped,
             "torch_distributed_backend": (dist.get_backend() if dist is not None else None),
             "per_rank_keyframes_per_s": main_leg.get("per_rank_keyframes_per_s"), "db_rows_per_gpu": main_leg.get("db_rows_per_gpu"),
             "all_gather_us_p50": main_leg.get("all_gather_us_p50"),
-            "roofline": roofline, "roofline_parity": roofline_parity, "roofline_knn": roofline_knn, "roofline_knn_batched": batched, "loop_match": loop_match,
-            "db100k": db100k, "with_geometry": with_geometry, "value_f32": value_f32, "value_parity": value_parity, "c5_shard": c5_shard,
-            "python_host": python_host, "parity": parity, "parity_split": parity_split, "cpu_baseline": cpu,
         }
+        if args.full:
+            line.update({
+                # the honesty gate: is `value` a number INSIDE north_star's tolerance (key-point indices bit-exact, descriptors / VLAD vectors
+                # within 1e-3)?  fp16 -- the reference's own engine precision (launch/realsense.launch:10-11) -- is not; the mode that is runs at
+                # `value_within_north_star_tolerance` (= value_parity.value, OMNI_PREC_SPLIT, same workload and host loop, same run)
+                "within_north_star_tolerance": None if headline_gate is None else headline_gate["within_north_star_tolerance"],
+                "parity_gate": {"headline": headline_gate, "value_parity": split_gate},
+                "value_within_north_star_tolerance": (kfps if (headline_gate or {}).get("within_north_star_tolerance") else
+                                                      (value_parity or {}).get("value") if (split_gate or {}).get("within_north_star_tolerance") else None),
+                "value_long_regions": long_regions,
+                "gflop_per_keyframe_superpoint": round(sp_flop_executed(args.precision, MAXN, False, left_out_flop) * KF_IMAGES / 1e9, 1),
+                "achieved_tflops_end_to_end": round(kfps * sp_flop_executed(args.precision, MAXN, False, left_out_flop) * KF_IMAGES / 1e12 / world, 1),
+                "roofline": roofline, "roofline_parity": roofline_parity, "roofline_knn": roofline_knn, "roofline_knn_batched": batched, "loop_match": loop_match,
+                "db100k": db100k, "with_geometry": with_geometry, "value_f32": value_f32, "value_parity": value_parity, "c5_shard": c5_shard,
+                "python_host": python_host, "parity": parity, "parity_split": parity_split, "cpu_baseline": cpu,
+            })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -1,8 +1,12 @@
 """Worker of tests/test_gpu_shard_rccl.py: one rank of an omni_shard group (RCCL inside libomni_hip.so, no torch).
-usage: shard_rccl_worker.py rank world device id_file out_npz seed"""
+usage: shard_rccl_worker.py rank world device id_file out_npz seed
+rank and out_npz may be comma-separated lists of the same length: the process then runs those ranks, one thread each (every thread its own
+context and shard), so that a large group on one GPU needs fewer processes with the device open."""
 import os
 import sys
+import threading
 import time
+import traceback
 
 import numpy as np
 
@@ -14,8 +18,7 @@ omni_loader.load()
 from omni_swarm_amd import capi, shard  # noqa: E402
 
 
-def main():
-    rank, world, device, id_file, out, seed = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5], int(sys.argv[6])
+def run_rank(rank, world, device, id_file, out, seed):
     ctx = capi.Context(device)
     if rank == 0:
         uid = capi.shard_unique_id()
@@ -47,6 +50,29 @@ def main():
     Ds, Is = sw.search(q, k)
     np.savez(out, D=np.stack(res_D), I=np.stack(res_I), Ds=Ds, Is=Is, ntotal=sw.ntotal, librccl=capi.shard_library_path())
     sw.close()
+
+
+def main():
+    ranks, world, device, id_file, outs, seed = sys.argv[1].split(","), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5].split(","), int(sys.argv[6])
+    assert len(ranks) == len(outs), (ranks, outs)
+    if len(ranks) == 1:
+        run_rank(int(ranks[0]), world, device, id_file, outs[0], seed)
+        return
+    failed = []
+
+    def body(rank, out):
+        try:
+            run_rank(rank, world, device, id_file, out, seed)
+        except BaseException:                               # noqa: BLE001 -- reported below, the process exits non-zero
+            traceback.print_exc()
+            failed.append(rank)
+    threads = [threading.Thread(target=body, args=(int(r), o)) for r, o in zip(ranks, outs)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if failed:
+        raise SystemExit(f"ranks {sorted(failed)} failed")
 
 
 if __name__ == "__main__":

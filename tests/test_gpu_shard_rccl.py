@@ -54,13 +54,21 @@ def stub_env():
     return dict(os.environ, OMNI_RCCL_LIB=STUB)
 
 
+# worker processes with GPU 0 open at once, next to this one: ranks beyond that share a process, one thread each (shard_rccl_worker.py)
+MAX_WORKERS_ON_ONE_GPU = 4
+
+
 def run_world(world, tmp_path, seed, worker="shard_rccl_worker.py", env=None, one_gpu_per_rank=False):
     id_file = str(tmp_path / f"uid{world}{'m' if one_gpu_per_rank else ''}")
+    outs = [str(tmp_path / f"w{world}_r{r}{'m' if one_gpu_per_rank else ''}.npz") for r in range(world)]
+    n_procs = world if one_gpu_per_rank else min(world, MAX_WORKERS_ON_ONE_GPU)
+    groups = [list(range(world))[i::n_procs] for i in range(n_procs)]
+    assert worker == "shard_rccl_worker.py" or all(len(g) == 1 for g in groups), "only shard_rccl_worker.py runs several ranks per process"
     procs = []
-    for r in range(world):
-        out = str(tmp_path / f"w{world}_r{r}{'m' if one_gpu_per_rank else ''}.npz")
-        procs.append((subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", worker), str(r), str(world), str(r if one_gpu_per_rank else 0), id_file, out, str(seed)],
-                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env), out))
+    for g in groups:
+        procs.append((subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", worker), ",".join(map(str, g)), str(world),
+                                        str(g[0] if one_gpu_per_rank else 0), id_file, ",".join(outs[r] for r in g), str(seed)],
+                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env), g))
     logs = []
     for p, _ in procs:
         try:
@@ -69,7 +77,8 @@ def run_world(world, tmp_path, seed, worker="shard_rccl_worker.py", env=None, on
             for q, _ in procs:
                 q.kill()
             raise
-    return [(p.returncode, out) for p, out in procs], logs
+    rc = {r: p.returncode for p, g in procs for r in g}
+    return [(rc[r], outs[r]) for r in range(world)], logs
 
 
 def check_against_oracle(world, res, logs):
@@ -85,7 +94,8 @@ def check_against_oracle(world, res, logs):
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_multi_rank_exchange_on_one_gpu_equals_unsharded_oracle(world, tmp_path):
-    """omni_shard_* with world ranks as world processes on GPU 0 (stub collective): ids, scores, add-before-query order, ntotal == the oracle."""
+    """omni_shard_* with world ranks on GPU 0 (stub collective; at most MAX_WORKERS_ON_ONE_GPU processes, ranks beyond that as threads): ids, scores,
+    add-before-query order, ntotal == the oracle."""
     res, logs = run_world(world, tmp_path, seed=100 + world, env=stub_env())
     check_against_oracle(world, res, logs)
 

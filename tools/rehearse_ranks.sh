@@ -6,7 +6,7 @@ set -u
 N=${1:-8}; OUTF=${2:-gpurun_out/rehearsal.json}; shift; shift
 make -s -C tests/stub_rccl
 OMNI_BENCH_ONE_GPU=1 OMNI_RCCL_LIB=$PWD/tests/stub_rccl/libstub_rccl.so HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --steps 16 --warmup 8 --min-time 0 --match-db-rows 80000 --batched-rows 0 --no-cpu-baseline "$@" > $OUTF 2> ${OUTF%.json}.err
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $N --steps 16 --warmup 8 --min-time 0 --match-db-rows 80000 --batched-rows 0 --no-cpu-baseline "$@" > $OUTF 2> ${OUTF%.json}.err
 echo "rehearsal rc=$?"
 python - <<PY
 import json
