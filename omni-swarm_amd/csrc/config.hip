@@ -12,9 +12,7 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
     // ---- SuperPoint ---------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_CONV_V1", 0, 0, 3, CFG_VARIANT, "fp16 3x3 layers: 0 = production (conv1a fused into the ping-pong conv1b, register-stationary cin=128); 1 = generic kernel, 2 = persistent LDS-DMA kernel, "
                                            "3 = ping-pong without the conv1a fusion -- 1-3 exist only in the test build of the library (lib_test/)"},
-    {"OMNI_CONV_RS", 2, 0, 2, CFG_VARIANT, "cin=128 fp16 layers: 2 = the register-stationary kernel with its epilogue and DMA inside the MFMA stream (3 / 4-row tiles), 1 = the 6-row-tile "
-                                          "register-stationary kernel of rounds 1-5, 0 = generic kernel"},
-    {"OMNI_RS_TRN", -1, -1, 1, CFG_VARIANT, "register-stationary kernel: tile orientation, -1 = the one with fewer tiles, 0 = plain, 1 = transposed"},
+    {"OMNI_RS_TRN", -1, -1, 1, CFG_VARIANT, "register-stationary kernel of the unpooled cin=128 fp16 layers: tile orientation, -1 = the one with fewer tiles, 0 = plain, 1 = transposed"},
     {"OMNI_DET16", 1, 0, 1, CFG_VARIANT, "detector head of the fp16 and OMNI_PREC_SPLIT paths on v_mfma_f32_32x32x16_f16 with split (hi, lo) operands (0: the exact-f32 MFMA kernel)"},
     {"OMNI_SP_SPARSE_DESC", 1, 0, 1, CFG_VARIANT, "convDb + descriptor norm only at the cells around the key points (0: dense descriptor map)"},
     {"OMNI_SP_SPARSE_DA", 1, 0, 1, CFG_VARIANT, "convDa only at those cells too (fp16 and OMNI_PREC_SPLIT; 0: dense convDa)"},
@@ -109,7 +107,7 @@ int config_resolve(Config* out) {
 // config_process()[...] call sites and asserts that they are exactly this list, so it cannot drift from them unnoticed.
 static bool is_process_wide(int i) {
     switch (i) {
-        case CFG_CONV_RS: case CFG_CONV_XCD: case CFG_INDEX_CERT_FAIL: case CFG_INDEX_MIRROR: case CFG_INDEX_MIRROR_MIN_ROWS: case CFG_MQ_ROT:
+        case CFG_CONV_XCD: case CFG_INDEX_CERT_FAIL: case CFG_INDEX_MIRROR: case CFG_INDEX_MIRROR_MIN_ROWS: case CFG_MQ_ROT:
         case CFG_PP_DBG: case CFG_PP_TRACE: case CFG_RS_TRACE: case CFG_RS_TRN: case CFG_SCAN_ROWS_MIN: case CFG_SPLIT_DBG: case CFG_SPLIT_TRACE: case CFG_SPLIT_TRN: case CFG_WINO_TRACE: case CFG_ROCTX:
         case CFG_VLAD_BIG: case CFG_VLAD_SB_DBG: case CFG_VLAD_SB_LDSPAD: case CFG_VLAD_SB_TRACE:
             return true;

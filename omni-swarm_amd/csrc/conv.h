@@ -10,6 +10,7 @@
 //   OMNI_PREC_F32: v_mfma_f32_32x32x2_f32 (exact f32, an fmaf chain), fp32 activations/weights: the parity mode.
 #pragma once
 #include "common.h"
+#include "tile_walk.h"
 
 namespace omni {
 
@@ -17,8 +18,7 @@ namespace omni {
 #define CONV_TW 32         // output tile cols  (2 fragments x 16)
 #define RS_TH 6            // the register-stationary cin = 128 kernel's output tile (plain orientation): 6 rows x 32 columns
 #define RS_TW 32
-int conv_rs_pool_tile_rows();   // rows of the pooled cin = 128 fp16 layer's tile grid (ConvArgs::skip_* of conv3b): 4 (OMNI_CONV_RS=2) or RS_TH
-struct RsSkip { int act, n_above, n_upto, y0, y1, x0, w, bw, xcd /* OMNI_CONV_XCD: xcd_block_id() */; };      // conv3x3_c128_rs_kernel: the tiles of an image that run (ConvArgs::skip_*)
+int conv_rs_pool_tile_rows();   // rows of the pooled cin = 128 fp16 layer's tile grid (ConvArgs::skip_* of conv3b): RS_TH
 #define CONV_COUT_TILE 64  // output channels per workgroup (2 fragments x 32)
 #define CONV_CIN_CHUNK 64  // input channels staged per pass
 
@@ -45,8 +45,8 @@ struct ConvArgs {
     int variant = 0;       // test hook (OMNI_CONV_V1): 0 = best kernel per layer, 1 = generic kernel everywhere, 2 = v2 persistent kernel,
                            // 3 = v3 ping-pong kernel without the conv1a fusion
     // Tile rectangle [skip_ty0, skip_ty1) x [skip_tx0, skip_tx1) of the CONV_TH x CONV_TW output-tile grid of every image whose results ALREADY
-    // stand in `out` (the caller filled them: see superpoint.hip, "constant region of the fisheye mask"): the persistent cin = 64 fp16 kernel
-    // leaves those tiles out of its tile walk; every other kernel ignores the hint and recomputes them (same values).  Empty = nothing to skip.
+    // stand in `out` (the caller filled them: see superpoint.hip, "constant region of the fisheye mask"): the persistent kernels leave those tiles
+    // out of their tile walk (tile_walk.h); every other kernel ignores the hint and recomputes them (same values).  Empty = nothing to skip.
     int skip_ty0 = 0, skip_ty1 = 0, skip_tx0 = 0, skip_tx1 = 0;
 };
 int conv_mfma(hipStream_t stream, int precision, const ConvArgs& a);

@@ -566,12 +566,8 @@ struct Fuse1aArgs {
     const uint32_t* lut_hl;       // [256] half(x) | half(x - half(x)) << 16,  x = float(i) * float(1 / 255.0)
     unsigned long long* trace;    // OMNI_PP_TRACE=1: s_memtime stamps of workgroup 0 (debug only), else nullptr
     const char* zero_page;        // OMNI_ZERO_PAGE_BYTES of zeros: DMA source of the halo pixels outside the image (set by the launcher)
-    uint32_t magic_tpi, magic_tx; // ceil(2^32 / act_per_img), ceil(2^32 / tiles_x) (set by the launcher)
-    // ConvArgs::skip_*: the tile walk of an image = the tile rows above the rectangle (n_above tiles), the tiles left and right of it in its
-    // rows (skip_bw per row, up to n_upto), the tile rows below it; no rectangle: n_above = n_upto = act_per_img = tiles_per_img
-    int act_per_img, n_above, n_upto, skip_y0, skip_y1, skip_x0, skip_w, skip_bw;
-    uint32_t magic_bw;            // ceil(2^32 / skip_bw)
-    int xcd;                      // OMNI_CONV_XCD: xcd_block_id() (set by the launcher)
+    uint32_t magic_tpi;           // tile_walk_magic(walk.act) (set by the launcher)
+    TileWalk walk;                // the tiles of an image that run (ConvArgs::skip_*; set by the launcher)
 };
 
 template <bool POOL, int ABL, bool FUSE1A>
@@ -585,9 +581,9 @@ conv3x3_c64_pp_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ ou
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wl = wave & 3;
     const int n = lane & 31, hh = lane >> 5;
-    const int bid = xcd_block_id(fz.xcd);
+    const int bid = xcd_block_id(fz.walk.xcd);
     const int ct = bid % n_ct, wg = bid / n_ct, nwg = gridDim.x / n_ct;
-    const int total = batch * fz.act_per_img;
+    const int total = batch * fz.walk.act;
     const int n_mine = wg < total ? (total - wg + nwg - 1) / nwg : 0;      // tiles of this workgroup: t_k = wg + k * nwg
 
     {   // weights for this cout tile: 9 taps x 8 KB, fragment order (see pack_weights)
@@ -608,23 +604,13 @@ conv3x3_c64_pp_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ ou
         }
     const uint32_t a_base0 = lds0 + lane * 16, a_base1 = a_base0 + 18 * 2048;
 
-    // t / tiles_per_img and r / tiles_x by multiply-high with ceil(2^32 / d) (exact while t * d < 2^32: the launcher checks): the service phase
+    // t / tiles_per_img and the decode by multiply-high with ceil(2^32 / d) (exact while t * d < 2^32: the launcher checks): the service phase
     // calls this three times per tile, next to a partner wave that leaves it few issue slots -- two hardware-less integer divisions each were
     // ~200 instructions per phase
     auto tile_origin = [&](int t, int& b, int& ty0, int& tx0) {
-        b = fz.magic_tpi ? (int)__umulhi((uint32_t)t, fz.magic_tpi) : t;             // magic 0 = divisor 1 (2^32 does not fit)
-        int r = t - b * fz.act_per_img, ry, rx;
-        if (r < fz.n_above || r >= fz.n_upto) {                                      // full tile rows above / below the skipped rectangle
-            int base = 0;
-            if (r >= fz.n_upto) { r -= fz.n_upto; base = fz.skip_y1; }
-            ry = fz.magic_tx ? (int)__umulhi((uint32_t)r, fz.magic_tx) : r;
-            rx = r - ry * tiles_x; ry += base;
-        } else {                                                                     // its rows: the tiles left and right of it
-            r -= fz.n_above;
-            const int q = fz.magic_bw ? (int)__umulhi((uint32_t)r, fz.magic_bw) : r;
-            const int c = r - q * fz.skip_bw;
-            ry = fz.skip_y0 + q; rx = c < fz.skip_x0 ? c : c + fz.skip_w;
-        }
+        b = tile_walk_div(t, fz.magic_tpi);
+        int ry, rx;
+        tile_walk_rc(fz.walk, tiles_x, t - b * fz.walk.act, ry, rx);
         ty0 = ry * CONV_TH; tx0 = rx * CONV_TW;
     };
     // per-lane source offsets (bytes, relative to the halo origin) of this wave's 11 DMA instructions, valid for interior tiles
@@ -947,27 +933,14 @@ static int launch_conv_pp_abl(hipStream_t st, const ConvArgs& a, int n_cu, int d
     OMNI_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes));
     const int tiles_x = cdiv(a.W, CONV_TW), tiles_y = cdiv(a.H, CONV_TH), n_ct = a.cout / 64;
     Fuse1aArgs fzz = fz;
-    // the tile walk of one image, without the rectangle the caller already holds (ConvArgs::skip_*)
-    const bool skip = a.skip_ty1 > a.skip_ty0 && a.skip_tx1 > a.skip_tx0;
-    OMNI_REQUIRE(!skip || (a.skip_ty0 >= 0 && a.skip_ty1 <= tiles_y && a.skip_tx0 >= 0 && a.skip_tx1 <= tiles_x), OMNI_ERR_INVALID, "conv: skip rectangle outside the tile grid");
-    fzz.skip_y0 = skip ? a.skip_ty0 : 0; fzz.skip_y1 = skip ? a.skip_ty1 : 0; fzz.skip_x0 = skip ? a.skip_tx0 : 0; fzz.skip_w = skip ? a.skip_tx1 - a.skip_tx0 : 0;
-    fzz.skip_bw = tiles_x - fzz.skip_w;
-    fzz.act_per_img = tiles_x * tiles_y - (fzz.skip_y1 - fzz.skip_y0) * fzz.skip_w;
-    fzz.n_above = skip ? fzz.skip_y0 * tiles_x : fzz.act_per_img;
-    fzz.n_upto = fzz.n_above + (fzz.skip_y1 - fzz.skip_y0) * fzz.skip_bw;
-    OMNI_REQUIRE(fzz.act_per_img > 0, OMNI_ERR_INVALID, "conv: the skip rectangle covers the whole image");
-    const int total = a.batch * fzz.act_per_img;
-    int per_ct = n_cu / n_ct;
-    if (per_ct < 1) per_ct = 1;
-    if (per_ct > cdiv(total, 2)) per_ct = cdiv(total, 2);      // at least two tiles per workgroup: one per wave group
+    if (int rc = tile_walk_plan(fzz.walk, "conv", tiles_x, tiles_y, a.skip_ty0, a.skip_ty1, a.skip_tx0, a.skip_tx1)) return rc;
+    fzz.walk.xcd = config_process()[CFG_CONV_XCD];
+    const int total = a.batch * fzz.walk.act;
+    const int per_ct = tile_walk_grid(n_cu, n_ct, cdiv(total, 2));      // at least two tiles per workgroup: one per wave group
     OMNI_REQUIRE(a.zero_page, OMNI_ERR_INVALID, "conv: ConvArgs.zero_page is not set");
     fzz.zero_page = reinterpret_cast<const char*>(a.zero_page);
     OMNI_REQUIRE((int64_t)total * (tiles_x * tiles_y) < (1ll << 32), OMNI_ERR_INVALID, "conv: too many tiles for the multiply-high division");
-    auto magic = [](int d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; };      // 0 = divisor 1 (2^32 does not fit)
-    fzz.magic_tpi = magic(fzz.act_per_img);
-    fzz.magic_tx = magic(tiles_x);
-    fzz.magic_bw = magic(fzz.skip_bw);
-    fzz.xcd = config_process()[CFG_CONV_XCD];
+    fzz.magic_tpi = tile_walk_magic(fzz.walk.act);
     // OMNI_PP_TRACE=1 (debug): s_memtime stamps of workgroup 0's phases 2-5 for the layers without the conv1a fusion (conv1ab_fused prints its own)
     static const bool want_trace = config_process()[CFG_PP_TRACE] != 0;
     static unsigned long long* trace_dev = nullptr;
@@ -1024,7 +997,6 @@ __device__ __forceinline__ void spl2_for_each(F&& f) {
     if constexpr (J < N) { f(std::integral_constant<int, J>{}); spl2_for_each<J + 1, N>(f); }
 }
 #define CSP_KP 8                                  // key points per tile of the sparse descriptor kernels (32 corner cells)
-bool conv_rs_transposed(int H, int W);
 // (RS_TH x RS_TW = 6 x 32: conv.h)
 #define RS_ITH (RS_TH + 2)
 #define RS_ITW (RS_TW + 2)
@@ -1061,17 +1033,13 @@ __device__ __forceinline__ void rs_steps(uint32_t row_base, int n, int hh, const
     }
 }
 
-// TRN: transposed tiles -- the 32-pixel fragments run along y, the six fragment rows along x (the LDS image, the k order and every MFMA are
-// those of the plain kernel; only the pixel <-> address maps differ).  A 60x75 layer is 2 x 13 tiles of 32x6 instead of 3 x 10 of 6x32:
-// 0.90 instead of 0.78 of the computed pixels are real (the 75-pixel rows wasted 22 % of every 32-pixel fragment).  Same products, summed
-// tap-column-major instead of tap-row-major (fp32 accumulation order): equal to the plain kernel to fp32 rounding, batch-independent as before.
-template <bool POOL, bool TRN = false>
+// Since v5 (below) took over the unpooled layers, v4 runs the pooled conv3b only: the 2x2 max-pool is fused into its epilogue.
 __global__ void __launch_bounds__(256, 1)
 conv3x3_c128_rs_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ out, const _Float16* __restrict__ wp,
                        const float* __restrict__ bias, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu,
                        const char* __restrict__ zero_page /* OMNI_ZERO_PAGE_BYTES of zeros: DMA source of the halo pixels outside the image */,
                        unsigned long long* trace /* OMNI_RS_TRACE=1: s_memtime stamps of workgroup 0 (debug only), else nullptr */,
-                       RsSkip sk /* ConvArgs::skip_* in this kernel's tile grid (plain tiles only): the tiles that run */) {
+                       TileWalk wk /* ConvArgs::skip_* in this kernel's tile grid: the tiles that run */) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem_raw;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1079,9 +1047,9 @@ conv3x3_c128_rs_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ o
     const int n = lane & 31, hh = lane >> 5;
     const bool tr = trace != nullptr && blockIdx.x == 0 && tid == 0;
     int tk = 0;
-    const int bid = xcd_block_id(sk.xcd);
+    const int bid = xcd_block_id(wk.xcd);
     const int cg = bid % n_cg, wg = bid / n_cg, nwg = gridDim.x / n_cg;
-    const int tiles_per_img = sk.act;              // (the tiles that run: all of them unless a rectangle is left out)
+    const int tiles_per_img = wk.act;              // (the tiles that run: all of them unless a rectangle is left out)
     const int total = batch * tiles_per_img;
     const int g32 = cg * 4 + wave;                 // this wave's group of 32 output channels
 
@@ -1091,29 +1059,19 @@ conv3x3_c128_rs_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ o
         const _Float16* wbase = wp + (int64_t)(g32 >> 1) * 2 * 9 * 4096 + (g32 & 1) * 512 + lane * 8;
 #pragma unroll
         for (int s2 = 0; s2 < 72; ++s2) {
-            const int tk = s2 >> 3, ch = (s2 >> 2) & 1, kg4 = s2 & 3;
-            const int tap = TRN ? (tk % 3) * 3 + tk / 3 : tk;          // transposed tiles: the kernel's (row, column) shifts are the image's (column, row)
+            const int tap = s2 >> 3, ch = (s2 >> 2) & 1, kg4 = s2 & 3;
             wreg[s2] = *reinterpret_cast<const half8_t*>(wbase + ((ch * 9 + tap) * 4 + kg4) * 1024);
         }
     }
     float* const bias_lds = reinterpret_cast<float*>(smem_raw + 2 * RS_BUF_BYTES);
     if (tid < 128) bias_lds[tid] = bias[cg * 128 + tid];
 
-    // tile t = (image, index r among the image's tiles that run): the tile rows above the rectangle, the tiles left and right of it in its own rows,
-    // the tile rows below (tests/test_mask_skip_cpu.py walks this arithmetic over every rectangle of several grids)
+    // tile t = (image, index r among the image's tiles that run: tile_walk.h)
     auto tile_origin = [&](int t, int& b, int& ty0, int& tx0) {
         b = t / tiles_per_img;
-        int r = t - b * tiles_per_img, ry, rx;
-        if (r < sk.n_above || r >= sk.n_upto) {
-            int base = 0;
-            if (r >= sk.n_upto) { r -= sk.n_upto; base = sk.y1; }
-            ry = r / tiles_x; rx = r - ry * tiles_x; ry += base;
-        } else {
-            r -= sk.n_above;
-            const int q = r / sk.bw, c = r - q * sk.bw;
-            ry = sk.y0 + q; rx = c < sk.x0 ? c : c + sk.w;
-        }
-        ty0 = ry * (TRN ? RS_TW : RS_TH); tx0 = rx * (TRN ? RS_TH : RS_TW);
+        int ry, rx;
+        tile_walk_rc<false>(wk, tiles_x, t - b * tiles_per_img, ry, rx);
+        ty0 = ry * RS_TH; tx0 = rx * RS_TW;
     };
     // DMA: 68 wave-instructions of 1 KiB per tile, wave w issues pieces 17 w .. 17 w + 16 into buffer `which`.  Buffer-addressed: the
     // descriptor is the image, so halo rows above / below it are out of range (the offset wraps negative or passes the image's bytes) and
@@ -1126,8 +1084,7 @@ conv3x3_c128_rs_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ o
     for (int j = 0; j < 17; ++j) {
         const int idx = (wave * 17 + j) * 64 + lane;
         const int pix = idx >> 4, phys = idx & 15;
-        const int iv = pix / RS_ITW, iu = pix - iv * RS_ITW;
-        const int iy = TRN ? iu : iv, ix = TRN ? iv : iu;
+        const int iy = pix / RS_ITW, ix = pix - iy * RS_ITW;
         goff[j] = (uint32_t)((iy * W + ix) * 256 + ((phys ^ (pix & 15)) << 4));
         hx[j / 5] |= (uint32_t)ix << (6 * (j % 5));
     }
@@ -1177,36 +1134,24 @@ conv3x3_c128_rs_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ o
         rs_steps<0>(row_base, n, hh, wreg, acc, fb, issue_piece);
         if (tr && tk < 8) trace[tk * 8 + 2] = __builtin_amdgcn_s_memtime();
 
-        {   // epilogue: (2x2 max-pool) + bias + ReLU, 16-byte NHWC stores
+        {   // epilogue: 2x2 max-pool + bias + ReLU, 16-byte NHWC stores
             int b, ty0, tx0;
             tile_origin(t, b, ty0, tx0);
             const int ox = tx0 + n;
             float4 bs[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) bs[g] = *reinterpret_cast<const float4*>(bias_lds + wave * 32 + 8 * g + 4 * hh);
-            if constexpr (POOL) {
 #pragma unroll
-                for (int f2 = 0; f2 < RS_TH / 2; ++f2) {
-                    const int oy = ty0 + 2 * f2;
-                    float v[16];
+            for (int f2 = 0; f2 < RS_TH / 2; ++f2) {
+                const int oy = ty0 + 2 * f2;
+                float v[16];
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const float q = vmax_med3(acc[2 * f2][i], acc[2 * f2 + 1][i]);
-                        v[i] = vmax_med3(q, dpp_swap_pairs(q));
-                    }
-                    _Float16* o = out + (((int64_t)b * (H >> 1) + (oy >> 1)) * (W >> 1) + (ox >> 1)) * cout + g32 * 32;
-                    store_frag16<false>(v, bs, o, hh, relu, (oy < H) && (ox < W) && !(n & 1));
+                for (int i = 0; i < 16; ++i) {
+                    const float q = vmax_med3(acc[2 * f2][i], acc[2 * f2 + 1][i]);
+                    v[i] = vmax_med3(q, dpp_swap_pairs(q));
                 }
-            } else {
-#pragma unroll
-                for (int f = 0; f < RS_TH; ++f) {
-                    const int oy = TRN ? ty0 + n : ty0 + f, oxx = TRN ? tx0 + f : ox;
-                    float v[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) v[i] = acc[f][i];
-                    _Float16* o = out + (((int64_t)b * H + oy) * W + oxx) * cout + g32 * 32;
-                    store_frag16<false>(v, bs, o, hh, relu, (oy < H) && (oxx < W));
-                }
+                _Float16* o = out + (((int64_t)b * (H >> 1) + (oy >> 1)) * (W >> 1) + (ox >> 1)) * cout + g32 * 32;
+                store_frag16<false>(v, bs, o, hh, relu, (oy < H) && (ox < W) && !(n & 1));
             }
         }
         if (tr && tk < 8) trace[tk * 8 + 3] = __builtin_amdgcn_s_memtime();
@@ -1217,30 +1162,15 @@ conv3x3_c128_rs_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ o
     }
 }
 
-template <bool POOL, bool TRN = false>
 static int launch_conv_rs(hipStream_t st, const ConvArgs& a, int n_cu) {
-    if constexpr (!POOL && !TRN) {
-        // the tile orientation with fewer tiles (OMNI_RS_TRN=0/1 forces one: A/B hook; results do not depend on it)
-        if (conv_rs_transposed(a.H, a.W)) return launch_conv_rs<false, true>(st, a, n_cu);
-    }
-    auto kfn = conv3x3_c128_rs_kernel<POOL, TRN>;
+    auto kfn = conv3x3_c128_rs_kernel;
     OMNI_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_SMEM));
-    const int tiles_x = cdiv(a.W, TRN ? RS_TH : RS_TW), tiles_y = cdiv(a.H, TRN ? RS_TW : RS_TH), n_cg = a.cout / 128;
-    // the tiles of an image that run: all of them, or all but the rectangle the caller already holds (ConvArgs::skip_*, in THIS kernel's 6 x 32 tile grid)
-    const bool skip = !TRN && a.skip_ty1 > a.skip_ty0 && a.skip_tx1 > a.skip_tx0;
-    OMNI_REQUIRE(!skip || (a.skip_ty0 >= 0 && a.skip_ty1 <= tiles_y && a.skip_tx0 >= 0 && a.skip_tx1 <= tiles_x), OMNI_ERR_INVALID, "conv_rs: skip rectangle outside the tile grid");
-    RsSkip sk;
-    sk.y0 = skip ? a.skip_ty0 : 0; sk.y1 = skip ? a.skip_ty1 : 0; sk.x0 = skip ? a.skip_tx0 : 0; sk.w = skip ? a.skip_tx1 - a.skip_tx0 : 0;
-    sk.bw = tiles_x - sk.w;
-    sk.act = tiles_x * tiles_y - (sk.y1 - sk.y0) * sk.w;
-    sk.n_above = skip ? sk.y0 * tiles_x : sk.act;
-    sk.n_upto = sk.n_above + (sk.y1 - sk.y0) * sk.bw;
-    OMNI_REQUIRE(sk.act > 0 && sk.bw > 0, OMNI_ERR_INVALID, "conv_rs: the skip rectangle covers whole tile rows");
-    sk.xcd = config_process()[CFG_CONV_XCD];
-    const int total = a.batch * sk.act;
-    int per_cg = n_cu / n_cg;
-    if (per_cg < 1) per_cg = 1;
-    if (per_cg > total) per_cg = total;
+    const int tiles_x = cdiv(a.W, RS_TW), tiles_y = cdiv(a.H, RS_TH), n_cg = a.cout / 128;
+    TileWalk wk;      // the tiles of an image that run, in THIS kernel's 6 x 32 tile grid
+    if (int rc = tile_walk_plan(wk, "conv_rs", tiles_x, tiles_y, a.skip_ty0, a.skip_ty1, a.skip_tx0, a.skip_tx1)) return rc;
+    wk.xcd = config_process()[CFG_CONV_XCD];
+    const int total = a.batch * wk.act;
+    const int per_cg = tile_walk_grid(n_cu, n_cg, total);
     OMNI_REQUIRE(a.zero_page, OMNI_ERR_INVALID, "conv: ConvArgs.zero_page is not set");
     const char* zero_page = reinterpret_cast<const char*>(a.zero_page);
     static const bool want_trace = config_process()[CFG_RS_TRACE] != 0;
@@ -1251,7 +1181,7 @@ static int launch_conv_rs(hipStream_t st, const ConvArgs& a, int n_cu) {
     }
     hipLaunchKernelGGL(kfn, dim3(per_cg * n_cg), dim3(256), RS_SMEM, st, reinterpret_cast<const _Float16*>(a.in),
                        reinterpret_cast<_Float16*>(a.out), reinterpret_cast<const _Float16*>(a.w_packed), a.bias, a.H, a.W, a.cout, n_cg,
-                       tiles_x, tiles_y, a.batch, a.relu ? 1 : 0, zero_page, want_trace ? trace_dev : nullptr, sk);
+                       tiles_x, tiles_y, a.batch, a.relu ? 1 : 0, zero_page, want_trace ? trace_dev : nullptr, wk);
     OMNI_LAUNCH_CHECK();
     if (want_trace) {
         unsigned long long h[64];
@@ -1260,8 +1190,8 @@ static int launch_conv_rs(hipStream_t st, const ConvArgs& a, int n_cu) {
         static int launches = 0;
         if (launches++ / 4 == 5)                                 // the sixth forward pass: conv3b, conv4a, conv4b, heads
             for (int k = 0; k < 8; ++k)
-                fprintf(stderr, "rs trace H=%d W=%d cout=%d pool=%d tile %llu (ty %llu tx %llu): issue %llu mfma %llu epilogue %llu wait %llu zerofix+barrier %llu | total %llu\n",
-                        a.H, a.W, a.cout, (int)POOL, h[k * 8 + 6], (h[k * 8 + 6] % (tiles_x * tiles_y)) / tiles_x, (h[k * 8 + 6] % (tiles_x * tiles_y)) % tiles_x,
+                fprintf(stderr, "rs trace H=%d W=%d cout=%d tile %llu (ty %llu tx %llu): issue %llu mfma %llu epilogue %llu wait %llu zerofix+barrier %llu | total %llu\n",
+                        a.H, a.W, a.cout, h[k * 8 + 6], (h[k * 8 + 6] % (tiles_x * tiles_y)) / tiles_x, (h[k * 8 + 6] % (tiles_x * tiles_y)) % tiles_x,
                         h[k * 8 + 1] - h[k * 8], h[k * 8 + 2] - h[k * 8 + 1], h[k * 8 + 3] - h[k * 8 + 2], h[k * 8 + 4] - h[k * 8 + 3],
                         h[k * 8 + 5] - h[k * 8 + 4], h[k * 8 + 5] - h[k * 8]);
     }
@@ -1281,7 +1211,10 @@ static int launch_conv_rs(hipStream_t st, const ConvArgs& a, int n_cu) {
 //   * stores are raw-buffer stores whose offset is out of range for lanes with nothing to store (no exec branch in the stream); issued in the
 //     first half of the stream, they have retired when the tile's closing s_waitcnt vmcnt(0) comes.
 // Same weights, same LDS image, same order of summation per output pixel (tap column outer, tap row, 16-channel group inner) as v4: bit-identical
-// results (tests/test_gpu_superpoint.py::test_f16_persistent_kernels_are_bit_identical_to_generic_kernel).  OMNI_CONV_RS=1 keeps v4.
+// results (tests/test_gpu_superpoint.py::test_f16_persistent_kernels_are_bit_identical_to_generic_kernel).
+// TRN: transposed tiles -- the 32-pixel fragments run along y, the fragment rows along x (the LDS image, the k order and every MFMA are those of
+// the plain kernel; only the pixel <-> address maps differ).  Same products, summed tap-column-major instead of tap-row-major (fp32 accumulation
+// order): equal to the plain kernel to fp32 rounding, batch-independent as before.  rs2_transposed() picks the orientation for a layer shape.
 // ---------------------------------------------------------------------------------------------------------------
 #define RS2_RING 3
 template <int TH> struct Rs2Cfg {
@@ -1330,7 +1263,7 @@ __device__ __forceinline__ void rs2_steps(uint32_t row_base, int n, int hh, cons
 template <bool POOL, bool TRN = false>
 __global__ void __launch_bounds__(256, 1)
 conv3x3_c128_rs2_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ out, const _Float16* __restrict__ wp,
-                        const float* __restrict__ bias, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu, RsSkip sk) {
+                        const float* __restrict__ bias, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu, TileWalk wk) {
     constexpr int TH = POOL ? 4 : 3;
     using C = Rs2Cfg<TH>;
     constexpr int ITH = C::ITH, PPW = C::PPW, NPIECES = C::NPIECES;
@@ -1340,9 +1273,9 @@ conv3x3_c128_rs2_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31, hh = lane >> 5;
-    const int bid = xcd_block_id(sk.xcd);
+    const int bid = xcd_block_id(wk.xcd);
     const int cg = bid % n_cg, wg = bid / n_cg, nwg = gridDim.x / n_cg;
-    const int tiles_per_img = sk.act;
+    const int tiles_per_img = wk.act;
     const int total = batch * tiles_per_img;
     const int g32 = cg * 4 + wave;
 
@@ -1361,16 +1294,8 @@ conv3x3_c128_rs2_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ 
 
     auto tile_origin = [&](int t, int& b, int& ty0, int& tx0) {
         b = t / tiles_per_img;
-        int r = t - b * tiles_per_img, ry, rx;
-        if (r < sk.n_above || r >= sk.n_upto) {
-            int base = 0;
-            if (r >= sk.n_upto) { r -= sk.n_upto; base = sk.y1; }
-            ry = r / tiles_x; rx = r - ry * tiles_x; ry += base;
-        } else {
-            r -= sk.n_above;
-            const int q = r / sk.bw, c = r - q * sk.bw;
-            ry = sk.y0 + q; rx = c < sk.x0 ? c : c + sk.w;
-        }
+        int ry, rx;
+        tile_walk_rc<false>(wk, tiles_x, t - b * tiles_per_img, ry, rx);
         ty0 = ry * (TRN ? RS_TW : TH); tx0 = rx * (TRN ? TH : RS_TW);
     };
     uint32_t goff[PPW];                       // byte offset of this lane's chunk of piece j relative to the halo origin
@@ -1505,48 +1430,35 @@ conv3x3_c128_rs2_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ 
     spl2_for_each<0, NPARTS>(epi_part);                           // the last tile's
 }
 
-template <bool POOL, bool TRN = false>
+// the tile orientation of v5's unpooled layer: the one with fewer 3 x 32 tiles (OMNI_RS_TRN=0/1 forces one: A/B hook).  It fixes the order the
+// taps are summed in: the dense layer (launch_conv_rs2's TRN) and its sparse form (conv_c128_sparse) both take it from here
+static bool rs2_transposed(int H, int W) {
+    static const int force = config_process()[CFG_RS_TRN];
+    const int plain = cdiv(W, RS_TW) * cdiv(H, 3), trn = cdiv(W, 3) * cdiv(H, RS_TW);
+    return force == 1 || (force < 0 && trn < plain);
+}
+template <bool POOL, bool TRN>
 static int launch_conv_rs2(hipStream_t st, const ConvArgs& a, int n_cu) {
     constexpr int TH = POOL ? 4 : 3;
-    if constexpr (!POOL && !TRN) {
-        static const int force = config_process()[CFG_RS_TRN];
-        const int plain = cdiv(a.W, RS_TW) * cdiv(a.H, TH), trn = cdiv(a.W, TH) * cdiv(a.H, RS_TW);
-        if (force == 1 || (force < 0 && trn < plain)) return launch_conv_rs2<false, true>(st, a, n_cu);
-    }
     OMNI_REQUIRE(a.relu, OMNI_ERR_INVALID, "conv_rs2: instantiated with the ReLU in its epilogue (every cin = 128 layer of the graph has one)");
     auto kfn = conv3x3_c128_rs2_kernel<POOL, TRN>;
     static DynSmemState smem_state;
     OMNI_HIP_TRY(ensure_dyn_smem(smem_state, (const void*)kfn, Rs2Cfg<TH>::smem()));
     const int tiles_x = cdiv(a.W, TRN ? TH : RS_TW), tiles_y = cdiv(a.H, TRN ? RS_TW : TH), n_cg = a.cout / 128;
-    const bool skip = !TRN && a.skip_ty1 > a.skip_ty0 && a.skip_tx1 > a.skip_tx0;
-    OMNI_REQUIRE(!skip || (a.skip_ty0 >= 0 && a.skip_ty1 <= tiles_y && a.skip_tx0 >= 0 && a.skip_tx1 <= tiles_x), OMNI_ERR_INVALID, "conv_rs2: skip rectangle outside the tile grid");
     OMNI_REQUIRE((int64_t)a.H * a.W * 256 < (1ll << 31) && (int64_t)a.H * a.W * a.cout * 2 < (1ll << 31), OMNI_ERR_INVALID, "conv_rs2: image too large for 32-bit offsets");
-    RsSkip sk;
-    sk.y0 = skip ? a.skip_ty0 : 0; sk.y1 = skip ? a.skip_ty1 : 0; sk.x0 = skip ? a.skip_tx0 : 0; sk.w = skip ? a.skip_tx1 - a.skip_tx0 : 0;
-    sk.bw = tiles_x - sk.w;
-    sk.act = tiles_x * tiles_y - (sk.y1 - sk.y0) * sk.w;
-    sk.n_above = skip ? sk.y0 * tiles_x : sk.act;
-    sk.n_upto = sk.n_above + (sk.y1 - sk.y0) * sk.bw;
-    OMNI_REQUIRE(sk.act > 0 && sk.bw > 0, OMNI_ERR_INVALID, "conv_rs2: the skip rectangle covers whole tile rows");
-    sk.xcd = config_process()[CFG_CONV_XCD];
-    const int total = a.batch * sk.act;
-    int per_cg = n_cu / n_cg;
-    if (per_cg < 1) per_cg = 1;
-    if (per_cg > total) per_cg = total;
+    TileWalk wk;      // (a transposed-tile launch recomputes a rectangle it is offered: same values)
+    if (int rc = TRN ? tile_walk_plan(wk, "conv_rs2", tiles_x, tiles_y, 0, 0, 0, 0)
+                     : tile_walk_plan(wk, "conv_rs2", tiles_x, tiles_y, a.skip_ty0, a.skip_ty1, a.skip_tx0, a.skip_tx1)) return rc;
+    wk.xcd = config_process()[CFG_CONV_XCD];
+    const int total = a.batch * wk.act;
+    const int per_cg = tile_walk_grid(n_cu, n_cg, total);
     hipLaunchKernelGGL(kfn, dim3(per_cg * n_cg), dim3(256), Rs2Cfg<TH>::smem(), st, reinterpret_cast<const _Float16*>(a.in), reinterpret_cast<_Float16*>(a.out),
-                       reinterpret_cast<const _Float16*>(a.w_packed), a.bias, a.H, a.W, a.cout, n_cg, tiles_x, tiles_y, a.batch, a.relu ? 1 : 0, sk);
+                       reinterpret_cast<const _Float16*>(a.w_packed), a.bias, a.H, a.W, a.cout, n_cg, tiles_x, tiles_y, a.batch, a.relu ? 1 : 0, wk);
     OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 // rows of the pooled cin = 128 fp16 layer's tile (the grid ConvArgs::skip_* is given in)
-int conv_rs_pool_tile_rows() { return RS_TH; }                  // (the pooled layer runs on v4 in every configuration)
-
-// the tile orientation launch_conv_rs picks for a non-pooled H x W layer (it fixes the order the taps are summed in)
-bool conv_rs_transposed(int H, int W) {
-    static const int force = config_process()[CFG_RS_TRN];
-    const int plain = cdiv(W, RS_TW) * cdiv(H, RS_TH), trn = cdiv(W, RS_TH) * cdiv(H, RS_TW);
-    return force == 1 || (force < 0 && trn < plain);
-}
+int conv_rs_pool_tile_rows() { return RS_TH; }                  // (the pooled layer runs on v4)
 
 // ---------------------------------------------------------------------------------------------------------------
 // 3x3 conv, 128 input channels, ONLY at the coarse cells around the key points (convDa, superpoint.ipynb:183: its output is read by
@@ -1692,7 +1604,7 @@ int conv_c128_sparse(hipStream_t st, const omni_ctx* ctx, const void* in_f16, co
     int pairs = cus / 2;                                                 // two workgroups (channel halves) per tile stream
     if (pairs > n_tiles) pairs = n_tiles;
     if (pairs < 1) pairs = 1;
-    const bool trn = conv_rs_transposed(Hc, Wc);
+    const bool trn = rs2_transposed(Hc, Wc);          // the dense layer's orientation: the same order of summation
     OMNI_REQUIRE(ctx->zero_page, OMNI_ERR_INVALID, "conv_c128_sparse: the context has no zero block");
     auto launch = [&](auto kfn) -> int {
         static DynSmemState attr;
@@ -1820,15 +1732,13 @@ int conv_mfma(hipStream_t st, int precision, const ConvArgs& a) {
 #endif
         return a.pool ? launch_conv_pp<true>(st, a, a.n_cu) : launch_conv_pp<false>(st, a, a.n_cu);
     }
-    static const bool no_rs = config_process()[CFG_CONV_RS] == 0;     // A/B hook
     if (precision == OMNI_PREC_F16 && a.ksize == 3 && a.cin == 128 && a.cout % 128 == 0 && !a.out_f32 && (a.in_cstride == 0 || a.in_cstride == 128) &&
-        a.n_cu > 0 && a.zero_page && a.variant == 0 && !no_rs && (!a.pool || a.H % 2 == 0))
+        a.n_cu > 0 && a.zero_page && a.variant == 0 && (!a.pool || a.H % 2 == 0))
     {
-        static const int rs_ver = config_process()[CFG_CONV_RS];
         // v5 for the unpooled layers (conv4a, conv4b, convPa|convDa); the pooled conv3b stays on v4: its v5 form (4-row tiles) measured the same time and sits at
         // the register limit (13 registers of scratch)
-        if (rs_ver >= 2 && a.relu && !a.pool) return launch_conv_rs2<false>(st, a, a.n_cu);
-        return a.pool ? launch_conv_rs<true>(st, a, a.n_cu) : launch_conv_rs<false>(st, a, a.n_cu);
+        if (a.pool) return launch_conv_rs(st, a, a.n_cu);
+        return rs2_transposed(a.H, a.W) ? launch_conv_rs2<false, true>(st, a, a.n_cu) : launch_conv_rs2<false, false>(st, a, a.n_cu);
     }
     if (precision == OMNI_PREC_F16) {
 #ifdef OMNI_TEST_VARIANTS              // the generic kernel on the fp16 3x3 layers (OMNI_CONV_V1=1): the other bit-identity reference of the test build

@@ -174,9 +174,6 @@ __device__ __forceinline__ void spl_prime(uint32_t row_base, int n_eff, int hh, 
 // the pair's stores go with its second slice.  Every lane runs every slice (the swap is a cross-lane operation); pred guards the stores.
 struct SplPacked { uint4 a, b; };
 struct SplTileIx { int b, r, ty, tx; };                               // image, index among the image's tiles that run, tile row, tile column
-// ConvArgs::skip_* for this kernel's tile grid: the tiles of an image that run = the tile rows above the rectangle (n_above tiles), the tiles
-// left and right of it in its own rows (bw per row, up to n_upto), the tile rows below; no rectangle: n_above = n_upto = act = tiles_x * tiles_y
-struct SplSkip { int act, n_above, n_upto, y0, y1, x0, w, bw; uint32_t magic_tx, magic_bw; int xcd /* OMNI_CONV_XCD: xcd_block_id() */; };
 struct SplOrg { __amdgpu_buffer_rsrc_t r; uint32_t soff; };           // a halo tile's DMA source: the image's frame + the scalar offset of the halo origin
 typedef float spl_f4 __attribute__((ext_vector_type(4)));
 template <bool C128, bool POOL>
@@ -444,7 +441,8 @@ void conv1a_split_pack_fused(const float* w /*[64][9]*/, const float* bias /*[64
 template <bool C128, bool POOL, bool OUT_F32, bool TRN = false, bool FUSE1A = false, bool FZMIX = true>
 __global__ void __launch_bounds__(256, 1)
 conv3x3_split_kernel(const char* __restrict__ in, void* __restrict__ out, const _Float16* __restrict__ wp, const float* __restrict__ bias,
-                     float inv, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu, SplSkip sk,
+                     float inv, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu,
+                     TileWalk wk /* ConvArgs::skip_* in this kernel's tile grid: the tiles that run */,
                      int dbg /* OMNI_SPLIT_DBG (timing experiments, WRONG results): 1 = no stores, 2 = every DMA reads tile 0 */,
                      unsigned long long* trace /* OMNI_SPLIT_TRACE=1: s_memtime stamps of workgroup 0, waves 0 and 3 (debug only), else nullptr */,
                      SplFuse fz /* FUSE1A: the u8 image the halo tiles are built from (`in` is unused) */) {
@@ -459,9 +457,9 @@ conv3x3_split_kernel(const char* __restrict__ in, void* __restrict__ out, const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int co = wave & 1, part = wave >> 1;
     const int n = lane & 31, hh = lane >> 5;
-    const int bid = xcd_block_id(sk.xcd);
+    const int bid = xcd_block_id(wk.xcd);
     const int cg = bid % n_cg, wg = bid / n_cg, nwg = gridDim.x / n_cg;
-    const int tiles_per_img = sk.act;                       // (the tiles that run)
+    const int tiles_per_img = wk.act;                       // (the tiles that run)
     const int total = batch * tiles_per_img;
     const int g32 = cg * 2 + co;
 
@@ -486,24 +484,16 @@ conv3x3_split_kernel(const char* __restrict__ in, void* __restrict__ out, const 
     }
 
     // tile t = (image b, tile r of the image's tiles that run); a workgroup walks t = wg, wg + nwg, ...: (b, r) advance by a carry, (tile row,
-    // tile column) come from r by multiply-high divisions (scalar: a dozen SALU instructions per tile)
+    // tile column) come from r by multiply-high divisions (tile_walk.h; scalar: a dozen SALU instructions per tile)
     // (the transposed cin = 128 tiles -- 32 rows tall -- never fit a rectangle: their walk stays on carries alone, r unused)
     const int step_b = nwg / tiles_per_img, step_r = nwg - step_b * tiles_per_img;
     const int step_y = step_r / tiles_x, step_x = step_r - step_y * tiles_x;
     auto decode = [&](SplTileIx& q) {
-        int r = q.r, ty, tx;                                            // (locals, assigned to q once: stores in both branches send the struct to scratch)
+        int ty, tx;                                                     // (locals, assigned to q once: stores in both branches send the struct to scratch)
         if constexpr (TRN) {
-            ty = r / tiles_x; tx = r - ty * tiles_x;
-        } else if (r < sk.n_above || r >= sk.n_upto) {                  // full tile rows above / below the rectangle
-            int base = 0;
-            if (r >= sk.n_upto) { r -= sk.n_upto; base = sk.y1; }
-            const int ry = sk.magic_tx ? (int)__umulhi((uint32_t)r, sk.magic_tx) : r;      // magic 0 = divisor 1
-            tx = r - ry * tiles_x; ty = ry + base;
-        } else {                                                        // its rows: the tiles left and right of it
-            r -= sk.n_above;
-            const int qy = sk.magic_bw ? (int)__umulhi((uint32_t)r, sk.magic_bw) : r;
-            const int c = r - qy * sk.bw;
-            ty = sk.y0 + qy; tx = c < sk.x0 ? c : c + sk.w;
+            ty = q.r / tiles_x; tx = q.r - ty * tiles_x;
+        } else {
+            tile_walk_rc(wk, tiles_x, q.r, ty, tx);
         }
         q.ty = ty; q.tx = tx;
     };
@@ -943,36 +933,28 @@ conv3x3_split_kernel(const char* __restrict__ in, void* __restrict__ out, const 
     spl_epi_all<0, C128, POOL, OUT_F32>(e, bs, inv, relu, hh, part);       // the last tile's
 }
 
+// the tile orientation of the unpooled cin = 128 layers: the one with fewer 2 x 32 tiles (OMNI_SPLIT_TRN=0/1 forces one: A/B hook).  It fixes the
+// order the taps are summed in: the dense layer (launch_split's TRN) and its sparse form (conv_split_c128_sparse) both take it from here
+static bool split_c128_transposed(int H, int W) {
+    static const int force = config_process()[CFG_SPLIT_TRN];
+    const int plain = cdiv(W, 32) * cdiv(H, 2), trn = cdiv(H, 32) * cdiv(W, 2);
+    return force == 1 || (force < 0 && trn < plain);
+}
+
 template <bool C128, bool POOL, bool OUT_F32, bool TRN = false, bool FUSE1A = false, bool FZMIX = true>
 static int launch_split(hipStream_t st, const ConvArgs& a, const SplFuse& fz = SplFuse{}) {
-    if constexpr (C128 && !POOL && !TRN) {
-        // the tile orientation with fewer tiles (OMNI_SPLIT_TRN=0/1 forces one: A/B hook; it fixes the order the taps are summed in)
-        static const int force = config_process()[CFG_SPLIT_TRN];
-        const int plain = cdiv(a.W, 32) * cdiv(a.H, 2), trn = cdiv(a.H, 32) * cdiv(a.W, 2);
-        if (force == 1 || (force < 0 && trn < plain)) return launch_split<C128, POOL, OUT_F32, true>(st, a);
-    }
     auto kfn = conv3x3_split_kernel<C128, POOL, OUT_F32, TRN, FUSE1A, FZMIX>;
     static DynSmemState smem_state;
     OMNI_HIP_TRY(ensure_dyn_smem(smem_state, (const void*)kfn, SPL_SMEM));
     constexpr int TH = C128 ? 2 : 4;
     const int tiles_x = cdiv(a.W, TRN ? TH : 32), tiles_y = cdiv(a.H, TRN ? 32 : TH), n_cg = a.cout / 64;
-    // the tiles of an image that run: all of them, or all but the rectangle the caller already holds (ConvArgs::skip_*, in THIS kernel's tile grid)
-    const bool skip = !TRN && a.skip_ty1 > a.skip_ty0 && a.skip_tx1 > a.skip_tx0;       // (a transposed-tile launch recomputes a rectangle it is offered: same values)
-    OMNI_REQUIRE(!skip || (a.skip_ty0 >= 0 && a.skip_ty1 <= tiles_y && a.skip_tx0 >= 0 && a.skip_tx1 <= tiles_x), OMNI_ERR_INVALID, "conv_split: skip rectangle outside the tile grid");
-    SplSkip sk;
-    sk.y0 = skip ? a.skip_ty0 : 0; sk.y1 = skip ? a.skip_ty1 : 0; sk.x0 = skip ? a.skip_tx0 : 0; sk.w = skip ? a.skip_tx1 - a.skip_tx0 : 0;
-    sk.bw = tiles_x - sk.w;
-    sk.act = tiles_x * tiles_y - (sk.y1 - sk.y0) * sk.w;
-    sk.n_above = skip ? sk.y0 * tiles_x : sk.act;
-    sk.n_upto = sk.n_above + (sk.y1 - sk.y0) * sk.bw;
-    OMNI_REQUIRE(sk.act > 0, OMNI_ERR_INVALID, "conv_split: the skip rectangle covers the whole image");
-    auto magic = [](int d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; };      // exact for n * d < 2^32; 0 = divisor 1
-    sk.magic_tx = magic(tiles_x); sk.magic_bw = magic(sk.bw);
-    sk.xcd = config_process()[CFG_CONV_XCD];
-    const int total = a.batch * sk.act;
-    int per_cg = a.n_cu / n_cg;
-    if (per_cg < 1) per_cg = 1;
-    if (per_cg > total) per_cg = total;
+    // the tiles of an image that run, in THIS kernel's tile grid (a transposed-tile launch recomputes a rectangle it is offered: same values)
+    TileWalk wk;
+    if (int rc = TRN ? tile_walk_plan(wk, "conv_split", tiles_x, tiles_y, 0, 0, 0, 0)
+                     : tile_walk_plan(wk, "conv_split", tiles_x, tiles_y, a.skip_ty0, a.skip_ty1, a.skip_tx0, a.skip_tx1)) return rc;
+    wk.xcd = config_process()[CFG_CONV_XCD];
+    const int total = a.batch * wk.act;
+    const int per_cg = tile_walk_grid(a.n_cu, n_cg, total);
     const float inv = a.out_f32 ? a.split_inv / SPL_ACT_SCALE : a.split_inv;
     static const bool want_trace = config_process()[CFG_SPLIT_TRACE] != 0;
     static const int dbg = config_process()[CFG_SPLIT_DBG];
@@ -983,7 +965,7 @@ static int launch_split(hipStream_t st, const ConvArgs& a, const SplFuse& fz = S
     }
     hipLaunchKernelGGL(kfn, dim3(per_cg * n_cg), dim3(256), SPL_SMEM, st, reinterpret_cast<const char*>(a.in), a.out,
                        reinterpret_cast<const _Float16*>(a.w_packed), a.bias, inv, a.H, a.W, a.cout, n_cg, tiles_x, tiles_y, a.batch, a.relu ? 1 : 0,
-                       sk, dbg, want_trace ? trace_dev : nullptr, fz);
+                       wk, dbg, want_trace ? trace_dev : nullptr, fz);
     OMNI_LAUNCH_CHECK();
     if (want_trace) {
         unsigned long long h[128];
@@ -1024,6 +1006,8 @@ int conv_split(hipStream_t st, const ConvArgs& a) {
         return a.out_f32 ? launch_split<false, false, true>(st, a) : launch_split<false, false, false>(st, a);
     }
     if (a.pool) return launch_split<true, true, false>(st, a);
+    if (split_c128_transposed(a.H, a.W))
+        return a.out_f32 ? launch_split<true, false, true, true>(st, a) : launch_split<true, false, false, true>(st, a);
     return a.out_f32 ? launch_split<true, false, true>(st, a) : launch_split<true, false, false>(st, a);
 }
 
@@ -1229,10 +1213,7 @@ int conv_split_c128_sparse(hipStream_t st, const omni_ctx* ctx, const void* a4b,
     if (groups > n_tiles) groups = n_tiles;
     if (groups < 1) groups = 1;
     OMNI_REQUIRE((int64_t)batch * split_frame_h(Hc) * split_frame_w(Wc) * 512 < (1ll << 40), OMNI_ERR_INVALID, "conv_split_c128_sparse: map too large");
-    // the orientation launch_split picks for the dense layer of this shape (it fixes the order the taps are summed in)
-    static const int force = config_process()[CFG_SPLIT_TRN];
-    const int plain = cdiv(Wc, 32) * cdiv(Hc, 2), trn = cdiv(Hc, 32) * cdiv(Wc, 2);
-    const bool use_trn = force == 1 || (force < 0 && trn < plain);
+    const bool use_trn = split_c128_transposed(Hc, Wc);      // the dense layer's orientation: the same order of summation
     const float inv = split_inv / SPL_ACT_SCALE;
     auto launch = [&](auto kfn) -> int {
         static DynSmemState attr;

@@ -92,8 +92,6 @@ float conv_pack_weights_wino(const float* w, int cin, int cout, uint16_t* out) {
     return ldexpf(1.f, -k);
 }
 
-// the tiles of an image that run (ConvArgs::skip_*), as SplSkip of conv_split.hip: the 4 x 32 tile grid is the direct kernel's
-struct WnSkip { int act, n_above, n_upto, y0, y1, x0, w, bw; uint32_t magic_tx, magic_bw; int xcd; };
 struct WnTileIx { int b, r, ty, tx; };
 struct WnFuse {
     const uint8_t* gray = nullptr; int gstride = 0, mask_r0 = 0, mask_r1 = 0;
@@ -133,16 +131,17 @@ __device__ __forceinline__ void wn_split8(const wn_f4& a, const wn_f4& b, half8_
 template <bool POOL, bool OUT_SPLIT, bool FUSE1A>
 __global__ void __launch_bounds__(256, 1)
 conv3x3_wino_kernel(const char* __restrict__ in, char* __restrict__ out, const _Float16* __restrict__ wp, const float* __restrict__ bias,
-                    float inv, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu, WnSkip sk, WnFuse fz,
+                    float inv, int H, int W, int cout, int n_cg, int tiles_x, int tiles_y, int batch, int relu,
+                    TileWalk wk /* ConvArgs::skip_* in the direct kernel's 4 x 32 tile grid: the tiles that run */, WnFuse fz,
                     unsigned long long* trace /* OMNI_WINO_TRACE=1: s_memtime stamps of workgroup 0, waves 0 and 3 (debug), else nullptr */) {
     extern __shared__ __attribute__((aligned(256))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();      // (wn_lds_ld / wn_lds_st address LDS from 0)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // = i, the row of the transformed patch this wave owns
     const int n = lane & 31, hh = lane >> 5, trow = n >> 4, tcol = n & 15;
-    const int bid = xcd_block_id(sk.xcd);
+    const int bid = xcd_block_id(wk.xcd);
     const int cg = bid % n_cg, wg = bid / n_cg, nwg = gridDim.x / n_cg;
-    const int tiles_per_img = sk.act;
+    const int tiles_per_img = wk.act;
     const int total = batch * tiles_per_img;
     // row i of B^T: W = d[ra] + beta d[rb]
     const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
@@ -172,18 +171,8 @@ conv3x3_wino_kernel(const char* __restrict__ in, char* __restrict__ out, const _
     // ---- the tile walk (conv_split.hip's) ----------------------------------------------------------------------------------------------------
     const int step_b = nwg / tiles_per_img, step_r = nwg - step_b * tiles_per_img;
     auto decode = [&](WnTileIx& q) {
-        int r = q.r, ty, tx;
-        if (r < sk.n_above || r >= sk.n_upto) {
-            int base = 0;
-            if (r >= sk.n_upto) { r -= sk.n_upto; base = sk.y1; }
-            const int ry = sk.magic_tx ? (int)__umulhi((uint32_t)r, sk.magic_tx) : r;
-            tx = r - ry * tiles_x; ty = ry + base;
-        } else {
-            r -= sk.n_above;
-            const int qy = sk.magic_bw ? (int)__umulhi((uint32_t)r, sk.magic_bw) : r;
-            const int c = r - qy * sk.bw;
-            ty = sk.y0 + qy; tx = c < sk.x0 ? c : c + sk.w;
-        }
+        int ty, tx;
+        tile_walk_rc(wk, tiles_x, q.r, ty, tx);
         q.ty = ty; q.tx = tx;
     };
     auto advance = [&](WnTileIx& q) {
@@ -667,22 +656,11 @@ static int launch_wino(hipStream_t st, const ConvArgs& a, const WnFuse& fz) {
     static DynSmemState smem_state;
     OMNI_HIP_TRY(ensure_dyn_smem(smem_state, (const void*)kfn, WN_SMEM));
     const int tiles_x = cdiv(a.W, 32), tiles_y = cdiv(a.H, 4), n_cg = a.cout / 64;
-    const bool skip = a.skip_ty1 > a.skip_ty0 && a.skip_tx1 > a.skip_tx0;
-    OMNI_REQUIRE(!skip || (a.skip_ty0 >= 0 && a.skip_ty1 <= tiles_y && a.skip_tx0 >= 0 && a.skip_tx1 <= tiles_x), OMNI_ERR_INVALID, "conv_wino: skip rectangle outside the tile grid");
-    WnSkip sk;
-    sk.y0 = skip ? a.skip_ty0 : 0; sk.y1 = skip ? a.skip_ty1 : 0; sk.x0 = skip ? a.skip_tx0 : 0; sk.w = skip ? a.skip_tx1 - a.skip_tx0 : 0;
-    sk.bw = tiles_x - sk.w;
-    sk.act = tiles_x * tiles_y - (sk.y1 - sk.y0) * sk.w;
-    sk.n_above = skip ? sk.y0 * tiles_x : sk.act;
-    sk.n_upto = sk.n_above + (sk.y1 - sk.y0) * sk.bw;
-    OMNI_REQUIRE(sk.act > 0, OMNI_ERR_INVALID, "conv_wino: the skip rectangle covers the whole image");
-    auto magic = [](int d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; };
-    sk.magic_tx = magic(tiles_x); sk.magic_bw = magic(sk.bw);
-    sk.xcd = config_process()[CFG_CONV_XCD];
-    const int total = a.batch * sk.act;
-    int per_cg = a.n_cu / n_cg;
-    if (per_cg < 1) per_cg = 1;
-    if (per_cg > total) per_cg = total;
+    TileWalk wk;
+    if (int rc = tile_walk_plan(wk, "conv_wino", tiles_x, tiles_y, a.skip_ty0, a.skip_ty1, a.skip_tx0, a.skip_tx1)) return rc;
+    wk.xcd = config_process()[CFG_CONV_XCD];
+    const int total = a.batch * wk.act;
+    const int per_cg = tile_walk_grid(a.n_cu, n_cg, total);
     static const bool want_trace = config_process()[CFG_WINO_TRACE] != 0;
     static unsigned long long* trace_dev = nullptr;
     if (want_trace) {
@@ -690,7 +668,7 @@ static int launch_wino(hipStream_t st, const ConvArgs& a, const WnFuse& fz) {
         OMNI_HIP_TRY(hipMemsetAsync(trace_dev, 0, 256 * 8, st));
     }
     hipLaunchKernelGGL(kfn, dim3(per_cg * n_cg), dim3(256), WN_SMEM, st, reinterpret_cast<const char*>(a.in), reinterpret_cast<char*>(a.out),
-                       reinterpret_cast<const _Float16*>(a.w_packed), a.bias, a.split_inv, a.H, a.W, a.cout, n_cg, tiles_x, tiles_y, a.batch, a.relu ? 1 : 0, sk, fz,
+                       reinterpret_cast<const _Float16*>(a.w_packed), a.bias, a.split_inv, a.H, a.W, a.cout, n_cg, tiles_x, tiles_y, a.batch, a.relu ? 1 : 0, wk, fz,
                        want_trace ? trace_dev : nullptr);
     OMNI_LAUNCH_CHECK();
     if (want_trace) {

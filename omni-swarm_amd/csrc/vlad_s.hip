@@ -118,17 +118,11 @@ vlad_sblock_kernel(VladSBlockArgs a) {
         toy = tty * TH; tox = (ttr - tty * tiles_x) * 8;
     };
     // the t-th tile that RUNS -> its number in the full grid (the band of the fisheye mask's constant region is not walked: VladSBlockArgs::sk_*)
-    const int act_total = a.sk_act * a.batch;
+    const int act_total = a.walk.act * a.batch;
     auto full_tile = [&](int t) -> int {
-        if (a.sk_y1 <= a.sk_y0) return t;
-        const int tb = sb_div(t, a.m_act), r = t - tb * a.sk_act;
-        int ttr;
-        if (r < a.sk_above) ttr = r;
-        else if (r < a.sk_upto) {
-            const int q = r - a.sk_above, ry = sb_div(q, a.m_bw), c = q - ry * a.sk_bw;
-            ttr = (a.sk_y0 + ry) * tiles_x + (c < a.sk_x0 ? c : c + a.sk_w);
-        } else ttr = r - a.sk_upto + a.sk_y1 * tiles_x;
-        return tb * tiles_img + ttr;
+        if (a.walk.y1 <= a.walk.y0) return t;
+        const int tb = sb_div(t, a.m_act);
+        return tb * tiles_img + tile_walk_index(a.walk, tiles_x, t - tb * a.walk.act);
     };
     // input region of a tile: thread = (region pixel, half of its channels); fetched into registers one tile ahead
     const int xhf = tid & 1;
@@ -446,11 +440,9 @@ static int launch_sb(hipStream_t st, const VladSBlockArgs& a) {
     OMNI_HIP_TRY(ensure_dyn_smem(attr, (const void*)kfn, smem));
     // persistent workgroups: as many as fit the CUs' LDS at once, each walking tiles blockIdx.x, + gridDim.x, ... with the next tile's input in flight
     const int tiles_x = cdiv(a.Wo, 8), tiles_y = cdiv(a.Ho, C::TH);
-    const bool skip = a.sk_y1 > a.sk_y0 && a.sk_w > 0;
-    OMNI_REQUIRE(!skip || (a.sk_y0 >= 0 && a.sk_y1 <= tiles_y && a.sk_x0 >= 0 && a.sk_x0 + a.sk_w <= tiles_x), OMNI_ERR_INVALID, "vlad_sblock: skip rectangle outside the tile grid");
-    const int act_img = tiles_x * tiles_y - (skip ? (a.sk_y1 - a.sk_y0) * a.sk_w : 0);
-    OMNI_REQUIRE(act_img > 0, OMNI_ERR_INVALID, "vlad_sblock: the skip rectangle covers the whole map");
-    const int tiles = act_img * a.batch;                          // the tiles that run
+    VladSBlockArgs at = a;
+    if (int rc = tile_walk_plan(at.walk, "vlad_sblock", tiles_x, tiles_y, a.sk_y0, a.sk_y1, a.sk_x0, a.sk_x0 + a.sk_w)) return rc;
+    const int tiles = at.walk.act * a.batch;                      // the tiles that run
     OMNI_REQUIRE((int64_t)a.batch * a.Hi * a.Wi * a.cin < (1ll << 31) && (int64_t)a.batch * a.Ho * a.Wo * a.cout < (1ll << 31) && tiles < (1 << 20),
                  OMNI_ERR_CAPACITY, "vlad_sblock: tensor beyond 32-bit element offsets");
     // how many of these workgroups a CU really holds: the runtime knows (registers AND LDS AND wave slots).  Rounds 2-4 estimated it from the LDS alone
@@ -471,21 +463,12 @@ static int launch_sb(hipStream_t st, const VladSBlockArgs& a) {
     const int grid = (!persist || tiles < cap) ? tiles : (int)cap;
     static const bool want_trace = config_process()[CFG_VLAD_SB_TRACE] != 0;
     static unsigned long long* trace_dev = nullptr;
-    VladSBlockArgs at = a;
     at.trace = nullptr;
     static const int dbg = config_process()[CFG_VLAD_SB_DBG];
     at.dbg = dbg;
-    {   // sb_div()'s reciprocals
-        const unsigned d_img = (unsigned)(cdiv(a.Wo, 8) * cdiv(a.Ho, C::TH)), d_tx = (unsigned)cdiv(a.Wo, 8);
-        at.m_img = d_img > 1 ? (unsigned)(((1ull << 32) + d_img - 1) / d_img) : 0u;
-        at.m_tx = d_tx > 1 ? (unsigned)(((1ull << 32) + d_tx - 1) / d_tx) : 0u;
-        if (!skip) { at.sk_y0 = at.sk_y1 = at.sk_x0 = at.sk_w = 0; }
-        at.sk_bw = tiles_x - at.sk_w; at.sk_act = act_img;
-        at.sk_above = skip ? at.sk_y0 * tiles_x : act_img;
-        at.sk_upto = at.sk_above + (at.sk_y1 - at.sk_y0) * at.sk_bw;
-        at.m_act = act_img > 1 ? (unsigned)(((1ull << 32) + (unsigned)act_img - 1) / (unsigned)act_img) : 0u;
-        at.m_bw = at.sk_bw > 1 ? (unsigned)(((1ull << 32) + (unsigned)at.sk_bw - 1) / (unsigned)at.sk_bw) : 0u;
-    }
+    at.m_img = tile_walk_magic(tiles_x * tiles_y);                // sb_div()'s reciprocals
+    at.m_tx = tile_walk_magic(tiles_x);
+    at.m_act = tile_walk_magic(at.walk.act);
     if (want_trace) {
         if (!trace_dev) OMNI_HIP_TRY(hipMalloc((void**)&trace_dev, 8 * 16 * 8));
         OMNI_HIP_TRY(hipMemsetAsync(trace_dev, 0, 8 * 16 * 8, st));

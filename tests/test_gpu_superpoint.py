@@ -172,8 +172,9 @@ def test_f16_sparse_descriptors_are_bit_identical_to_the_dense_map_path(omni, ct
     key points (partial key-point tiles), several images per launch; omni_sp_get_dense after a sparse pass == the dense pass's map."""
     weights = S.synth_weights(0)
     comp, mean = synth.pca()
+    # 128 x 264 (16 x 33 coarse cells): the dense convDa runs on transposed 3-row tiles there, which the sparse kernel must follow (rs2_transposed)
     for (h, w, nb, thr, maxn, pca) in ((480, 600, 3, 0.015, 200, True), (96, 128, 2, 0.015, 37, False), (104, 136, 1, 0.2, 200, True),
-                                       (64, 96, 2, 0.001, 1000, True), (64, 96, 2, 0.999, 50, True)):      # the last one: no key point at all
+                                       (128, 264, 2, 0.015, 200, True), (64, 96, 2, 0.001, 1000, True), (64, 96, 2, 0.999, 50, True)):      # the last one: no key point at all
         imgs = np.stack([synth.image_u8(310 + i, h, w, n_shapes=60) for i in range(nb)])
         res = {}
         for flag, (desc_flag, da_flag) in {"sparse": ("1", "1"), "sparse_db_only": ("1", "0"), "dense": ("0", "0")}.items():

@@ -1,99 +1,74 @@
-"""CPU checks around the constant region of the fisheye mask (csrc/superpoint.hip sp_plan_mask_skip, csrc/conv.hip tile_origin; the GPU side is
-tests/test_gpu_mask_skip.py): the integer arithmetic of the tile walk -- the decode of a tile number into (image, tile row, tile column) over the
-tiles that run, by multiply-high divisions -- enumerates every tile outside the rectangle exactly once, for every rectangle of several grids; the
-plan bench.py mirrors for its FLOP accounting gives the rectangles worked out by hand for 600 x 480 (docs/history/rounds_2_to_5.md, round 3)."""
-import importlib.util
+"""CPU checks around the constant region of the fisheye mask (csrc/superpoint.hip sp_plan_mask_skip, csrc/tile_walk.h; the GPU side is
+tests/test_gpu_mask_skip.py): the tile walk the persistent kernels share -- the decode of a tile's number among the tiles that run into (tile row,
+tile column) by multiply-high or hardware division, and into its number in the full grid -- enumerates every tile outside the rectangle exactly
+once, for every rectangle of several grids (the header itself, compiled with g++ into tests/cpp/tile_walk_pin.cpp); the plan bench.py mirrors for
+its FLOP accounting gives the rectangles worked out by hand for 600 x 480 (docs/history/rounds_2_to_5.md, round 3)."""
 import os
+import subprocess
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _magic(d):
-    return ((1 << 32) + d - 1) // d if d > 1 else 0          # ceil(2^32 / d); 0 = divisor 1 (2^32 does not fit 32 bits)
+@pytest.fixture(scope="module")
+def pin(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("tile_walk") / "tile_walk_pin")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "cpp", "tile_walk_pin.cpp")])
+    return exe
 
 
-def _umulhi(a, b):
-    return (a * b) >> 32
+def _walks(pin, tiles_x, tiles_y, batch, rects):
+    """tile_walk_pin over rectangles (ty0, ty1, tx0, tx1): per rectangle None (refused) or an [n][3] array of full-grid tile numbers in walk order
+    (multiply-high (row, column), hardware-division (row, column), index form)"""
+    args = [str(v) for r in rects for v in r]
+    raw = np.frombuffer(subprocess.run([pin, str(tiles_x), str(tiles_y), str(batch)] + args, capture_output=True, check=True).stdout, np.uint16)
+    out, i = [], 0
+    for _ in rects:
+        n = int(raw[i]); i += 1
+        if n == 65535:
+            out.append(None)
+            continue
+        out.append(raw[i:i + 3 * n].reshape(n, 3).astype(np.int64)); i += 3 * n
+    assert i == len(raw)
+    return out
 
 
-def _walk(tiles_x, tiles_y, sy0, sy1, sx0, sx1, batch):
-    """conv.hip: launch_conv_pp_abl (the parameters) + tile_origin (the decode), in Python integers"""
-    skip = sy1 > sy0 and sx1 > sx0
-    y0, y1, x0, w = (sy0, sy1, sx0, sx1 - sx0) if skip else (0, 0, 0, 0)
-    bw = tiles_x - w
-    act = tiles_x * tiles_y - (y1 - y0) * w
-    n_above = y0 * tiles_x if skip else act
-    n_upto = n_above + (y1 - y0) * bw
-    m_tpi, m_tx, m_bw = _magic(act), _magic(tiles_x), _magic(bw)
-    assert batch * act * tiles_x * tiles_y < 1 << 32             # the launcher's exactness condition
-    out = []
-    for t in range(batch * act):
-        b = _umulhi(t, m_tpi) if m_tpi else t
-        r = t - b * act
-        if r < n_above or r >= n_upto:
-            base = 0
-            if r >= n_upto:
-                r, base = r - n_upto, y1
-            ry = _umulhi(r, m_tx) if m_tx else r
-            rx, ry = r - ry * tiles_x, ry + base
-        else:
-            r -= n_above
-            q = _umulhi(r, m_bw) if m_bw else r
-            c = r - q * bw
-            ry, rx = y0 + q, (c if c < x0 else c + w)
-        out.append((b, ry, rx))
-    return out, (y0, y1, x0, x0 + w, skip)
+def _expected(tiles_x, tiles_y, batch, ty0, ty1, tx0, tx1):
+    b, y, x = np.meshgrid(np.arange(batch), np.arange(tiles_y), np.arange(tiles_x), indexing="ij")
+    skip = ty1 > ty0 and tx1 > tx0
+    keep = ~(skip & (y >= ty0) & (y < ty1) & (x >= tx0) & (x < tx1))
+    return (b * tiles_x * tiles_y + y * tiles_x + x)[keep]                # row-major, image by image
 
 
-def test_tile_walk_enumerates_the_tiles_outside_the_rectangle_once():
+def test_tile_walk_enumerates_the_tiles_outside_the_rectangle_once(pin):
+    """the (tile row, tile column) form of the five persistent conv kernels, both divisions; rectangles up to the full width of the grid (bw = 0)"""
+    full_width = 0
     for tx, ty in [(19, 60), (10, 30), (5, 15), (1, 1), (2, 3), (3, 8)]:
         rects = [(0, 0, 0, 0)] + [(a, b, c, d) for a in range(ty) for b in range(a + 1, ty + 1) for c in range(tx) for d in range(c + 1, tx + 1)
                                   if (b - a) * (d - c) < tx * ty and (ty <= 20 or (a % 7 == 4 and b % 5 == 4))]
-        for sy0, sy1, sx0, sx1 in rects:
-            seen, (y0, y1, x0, x1, skip) = _walk(tx, ty, sy0, sy1, sx0, sx1, 2)
-            want = [(b, y, x) for b in range(2) for y in range(ty) for x in range(tx) if not (skip and y0 <= y < y1 and x0 <= x < x1)]
-            assert sorted(seen) == want and len(set(seen)) == len(seen), (tx, ty, sy0, sy1, sx0, sx1)
+        for rect, seen in zip(rects, _walks(pin, tx, ty, 2, rects)):
+            want = _expected(tx, ty, 2, *rect)
+            assert seen is not None, (tx, ty, rect)
+            for form in (0, 1):
+                assert np.array_equal(np.sort(seen[:, form]), want) and len(np.unique(seen[:, form])) == len(want), (tx, ty, rect, form)
+            full_width += rect[3] - rect[2] == tx
+    assert full_width > 100
+    # refused: outside the grid, the whole image
+    assert _walks(pin, 5, 3, 1, [(0, 4, 0, 1), (0, 1, 4, 6), (-1, 1, 0, 1), (0, 3, 0, 5)]) == [None] * 4
 
 
-def _walk_vlad(tiles_x, tiles_y, sy0, sy1, sx0, sw, batch):
-    """vlad_s.hip: launch_sb (the parameters) + full_tile (the t-th tile that runs -> its number in the full grid), in Python integers"""
-    skip = sy1 > sy0 and sw > 0
-    y0, y1, x0, w = (sy0, sy1, sx0, sw) if skip else (0, 0, 0, 0)
-    tiles_img = tiles_x * tiles_y
-    act = tiles_img - (y1 - y0) * w
-    bw = tiles_x - w
-    above = y0 * tiles_x if skip else act
-    upto = above + (y1 - y0) * bw
-    m_act, m_bw = _magic(act), _magic(bw)
-    out = []
-    for t in range(batch * act):
-        if y1 <= y0:
-            out.append(t)
-            continue
-        tb = _umulhi(t, m_act) if m_act else t
-        r = t - tb * act
-        if r < above:
-            ttr = r
-        elif r < upto:
-            q = r - above
-            ry = _umulhi(q, m_bw) if m_bw else q
-            c = q - ry * bw
-            ttr = (y0 + ry) * tiles_x + (c if c < x0 else c + w)
-        else:
-            ttr = r - upto + y1 * tiles_x
-        out.append(tb * tiles_img + ttr)
-    return out, (y0, y1, x0, x0 + w, skip)
-
-
-def test_mobilenetvlad_tile_walk_enumerates_the_tiles_outside_the_rectangle_once():
-    """the persistent block kernel of MobileNetVLAD under the fisheye mask (round 6): rectangles up to the full width of the grid (no tile left in a band row)"""
+def test_mobilenetvlad_tile_walk_enumerates_the_tiles_outside_the_rectangle_once(pin):
+    """the index form of the persistent block kernel of MobileNetVLAD under the fisheye mask (round 6): rectangles up to the full width of the grid
+    (no tile left in a band row)"""
     for tx, ty in [(19, 30), (10, 15), (5, 8), (1, 2), (3, 4)]:
         rects = [(0, 0, 0, 0)] + [(a, b, c, d - c) for a in range(ty) for b in range(a + 1, ty + 1) for c in range(tx) for d in range(c + 1, tx + 1)
                                   if (b - a) * (d - c) < tx * ty and (ty <= 8 or (a % 5 == 3 and b % 4 == 1))]
-        for sy0, sy1, sx0, sw in rects:
-            seen, (y0, y1, x0, x1, skip) = _walk_vlad(tx, ty, sy0, sy1, sx0, sw, 3)
-            want = [b * tx * ty + y * tx + x for b in range(3) for y in range(ty) for x in range(tx) if not (skip and y0 <= y < y1 and x0 <= x < x1)]
-            assert seen == want, (tx, ty, sy0, sy1, sx0, sw)              # (in order: the walk is monotonic)
+        walks = _walks(pin, tx, ty, 3, [(a, b, c, c + w) for a, b, c, w in rects])
+        for (sy0, sy1, sx0, sw), seen in zip(rects, walks):
+            want = _expected(tx, ty, 3, sy0, sy1, sx0, sx0 + sw)
+            assert seen is not None and np.array_equal(seen[:, 2], want), (tx, ty, sy0, sy1, sx0, sw)      # (in order: the walk is monotonic)
 
 
 def test_plan_for_600x480_is_the_one_worked_out_by_hand():
