@@ -367,10 +367,12 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
 
 static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, bool with_events, bool run_post);
 // One dense pass over an all-zero image with the mask on; every planned layer's constant is read from the middle of its rectangle and written
-// into that rectangle of every image slot of the layer's activation buffer.
-static int sp_calibrate_mask_skip(omni_sp* s, int stride) {
+// into that rectangle of every image slot of the layer's activation buffer.  The calibration pass takes the same conv1a form as the pass it
+// serves (fuse1a): an unfused pass whose image only missed the fusion through its pointer (stride % 4 == 0) calibrates on the zero image one
+// byte past its start, so that conv1a's own rectangle (OMNI_PREC_SPLIT) is filled and the constants come from the same kernels.
+static int sp_calibrate_mask_skip(omni_sp* s, int stride, bool fuse1a) {
     hipStream_t st = s->ctx->stream;
-    const size_t need = (size_t)stride * s->H;
+    const size_t need = (size_t)stride * s->H + 4;
     if (s->zero_gray_bytes < need) {
         if (s->zero_gray) (void)hipFree(s->zero_gray);
         s->zero_gray = nullptr; s->zero_gray_bytes = 0;
@@ -379,7 +381,8 @@ static int sp_calibrate_mask_skip(omni_sp* s, int stride) {
         OMNI_HIP_TRY(hipMemsetAsync(s->zero_gray, 0, need, st));
     }
     s->mask_skip_calibrating = true;
-    int rc = sp_forward(s, s->zero_gray, stride, 1, 1, false, false);
+    const int off = (!fuse1a && stride % 4 == 0) ? 1 : 0;
+    int rc = sp_forward(s, s->zero_gray + off, stride, 1, 1, false, false);
     s->mask_skip_calibrating = false;
     if (rc) return rc;
     s->mask_skip_cal_fused = s->fuse1a;
@@ -417,7 +420,7 @@ static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch
     const bool use_skip = s->mask_skip && fisheye_mask && (fuse1a || P == OMNI_PREC_SPLIT) && !s->mask_skip_calibrating;
     if (!use_skip && !s->mask_skip_calibrating) s->mask_skip_ready = false;          // this pass overwrites the filled rectangles
     if (use_skip && s->mask_skip_ready && s->mask_skip_cal_fused != fuse1a) s->mask_skip_ready = false;      // (conv1a's own rectangle is only filled by an unfused calibration)
-    if (use_skip && !s->mask_skip_ready && (rc = sp_calibrate_mask_skip(s, stride))) return rc;
+    if (use_skip && !s->mask_skip_ready && (rc = sp_calibrate_mask_skip(s, stride, fuse1a))) return rc;
     auto mark = [&]() -> int { if (with_events) OMNI_HIP_TRY(hipEventRecord(s->ev[stage], st)); ++stage; return OMNI_OK; };
     // OMNI_PREC_SPLIT: which of the cin = 64 layers run as Winograd kernels in THIS pass, and the frame format between them
     const bool w1b = P == OMNI_PREC_SPLIT && (s->wino & 1) && fuse1a, w2a = P == OMNI_PREC_SPLIT && (s->wino & 2) != 0, w2b = P == OMNI_PREC_SPLIT && (s->wino & 4) != 0,
