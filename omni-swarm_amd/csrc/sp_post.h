@@ -4,6 +4,7 @@
 //   computeDescriptors    swarm_loop/src/superpoint_tensorrt.cpp:192-230
 #pragma once
 #include "common.h"
+#include "sp_plan.h"
 
 namespace omni {
 
@@ -33,28 +34,25 @@ struct SpPostBuffers {      // all device pointers, sized for max_batch images
     const float* pca_mean;  // [256]
 };
 
-// descriptors sampled without the dense map (fp16 path): convDb + L2 norm only at the cells around the key points (conv.h: convdb_sparse_sample)
+// How sp_postprocess gets its descriptors: `mode` (the pass's descriptor tail, sp_plan.h) picks the path, the pointers are operands only.  The two
+// dense modes sample the finished map desc_nhwc; the sparse ones run convDb + L2 norm only at the <= 4 * max_num coarse cells the sampler reads --
+// bit-identical to the dense map + sp_sample_kernel (a 1x1 conv and the per-cell norm do not look at neighbours).
 struct SpSparseDesc {
+    SpDescTail mode = SP_DESC_DENSE_GENERIC;
+    bool split_db = false;          // SP_DESC_SPARSE_DA_SPLIT: convdb_l2norm_split (false: the exact-f32 convolution + l2norm_channels)
     const omni_ctx* ctx = nullptr;
-    const void* in_f16 = nullptr;   // cDa: NHWC fp16, already offset to the 256 input channels; null = sample the dense map instead
+    const void* cda = nullptr;      // cDa inside the heads buffer (fp16 / fp32 NHWC, pixel stride in_cstride elements): SP_DESC_SPARSE_F16, SP_DESC_GATHER_F32
     int in_cstride = 0;
-    const void* wfrag = nullptr;    // convdb_pack_weights
-    const float* bias = nullptr;
-    // convDa itself only around the key points (conv_c128_sparse): a4b -> da_compact [B][max_num][4][256] fp16, which then replaces in_f16
-    const void* a4b = nullptr;      // [B][Hc][Wc][128] fp16; null = in_f16 is the dense cDa map
-    const void* da_w = nullptr; const float* da_bias = nullptr; int da_g32_first = 0;
-    void* da_compact = nullptr;
-    // fp32 variant (OMNI_PREC_F32 / OMNI_PREC_SPLIT): convDb + L2 norm in exact f32 only at the <= 4 * max_num cells the sampler reads.
-    // cda_f32: the heads layer's cDa half, NHWC fp32 with pixel stride in_cstride floats; wdb_f32: conv_pack_weights_f32 of convDb; cx / cy:
-    // scratch [ceil8(batch * max_num * 4)][256] fp32 each.  Bit-identical to the dense map + sp_sample_kernel (a 1x1 conv and the per-cell norm
-    // do not look at neighbours).
-    const float* cda_f32 = nullptr; const void* wdb_f32 = nullptr; float* cx = nullptr; float* cy = nullptr;
+    const float* bias = nullptr;    // convDb's
+    const void* wfrag = nullptr;    // convdb_pack_weights (fp16 modes)
+    const void* wdb_f32 = nullptr;  // conv_pack_weights_f32 of convDb (the exact-f32 convolution)
+    const void* wdb_hi = nullptr; const void* wdb_lo = nullptr;      // convdb_pack_weights_split
+    // convDa itself only around the key points (conv_c128_sparse -> da_compact / conv_split_c128_sparse -> cx): a4b = conv4b's output (fp16 NHWC / split-64
+    // frames), da_w / da_bias / da_inv = the fused heads layer's packed weights, bias and split_inv, of which convDa is the 32-channel groups from da_g32_first
+    const void* a4b = nullptr; const void* da_w = nullptr; const float* da_bias = nullptr; int da_g32_first = 0; float da_inv = 0.f;
+    void* da_compact = nullptr;     // [B][max_num][4][256] fp16
+    float* cx = nullptr; float* cy = nullptr;       // fp32 modes: the cDa rows / their convDb + norm, [ceil8(batch * max_num * 4)][256] each
     int n_cu = 0; const void* zero_page = nullptr;
-    // OMNI_PREC_SPLIT: convDa itself only at those cells (conv_split_c128_sparse) -- a4b_split: conv4b's split-64 frames; the rows land in cx directly
-    // (cda_f32 is then not read); da_w / da_bias / da_g32_first as above, da_inv = the fused heads layer's split_inv
-    const void* a4b_split = nullptr; float da_inv = 0.f;
-    // ... and convDb + the norm over those rows with split operands too (convdb_l2norm_split; null = the exact-f32 convolution + l2norm_channels)
-    const void* wdb_hi = nullptr; const void* wdb_lo = nullptr;
     // the detector head already thresholded the map (conv.h DetCand): SpPostBuffers::cand_bits is filled; sp_mask_kernel compacts it into the candidate
     // lists and makes the window masks of the candidates only -- sp_cand_kernel, which re-reads the whole heat map through LDS tiles, is not launched
     bool cand_fused = false;
@@ -63,7 +61,7 @@ struct SpSparseDesc {
     bool cand_from_list = false;
 };
 
-// semi: [B][H][W] f32 probability map; desc_nhwc: [B][H/8][W/8][256] f32 (channel-normalised coarse descriptors; unused when sparse.in_f16 is set)
+// semi: [B][H][W] f32 probability map; desc_nhwc: [B][H/8][W/8][256] f32 (channel-normalised coarse descriptors; read by the two dense modes only)
 int sp_postprocess(hipStream_t stream, const SpPostParams& p, const SpPostBuffers& b, const float* semi,
                    const float* desc_nhwc, int batch, const SpSparseDesc& sparse = SpSparseDesc{});
 

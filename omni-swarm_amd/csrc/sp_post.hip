@@ -647,32 +647,32 @@ int sp_postprocess(hipStream_t stream, const SpPostParams& p, const SpPostBuffer
     hipLaunchKernelGGL(sp_nms_kernel, dim3(batch), dim3(NMS_THREADS), smem, stream, semi, p.width, p.height, p.max_num, b.cand,
                        b.cand_masks, b.counters, b.surv_keys, b.kps_xy, b.scores, b.n_kps, state_words, smem_main);
     OMNI_LAUNCH_CHECK();
-    if (sparse.a4b) {
-        int rc = conv_c128_sparse(stream, sparse.ctx, sparse.a4b, sparse.da_w, sparse.da_bias, p.height / 8, p.width / 8, sparse.da_g32_first, p.width, p.height,
-                                  p.max_num, b.kps_xy, b.n_kps, sparse.da_compact, 256, batch);
-        if (rc) return rc;
-        rc = convdb_sparse_sample(stream, sparse.ctx, sparse.da_compact, 256, sparse.wfrag, sparse.bias, p.width, p.height, p.max_num, b.kps_xy, b.n_kps,
-                                  b.raw_desc, batch, true);
-        if (rc) return rc;
-    } else if (sparse.in_f16) {
-        int rc = convdb_sparse_sample(stream, sparse.ctx, sparse.in_f16, sparse.in_cstride, sparse.wfrag, sparse.bias, p.width, p.height, p.max_num,
-                                      b.kps_xy, b.n_kps, b.raw_desc, batch, false);
-        if (rc) return rc;
-    } else if (sparse.cda_f32 || sparse.a4b_split) {
+    const bool split_da = sparse.mode == SP_DESC_SPARSE_DA_SPLIT;
+    int rc;
+    switch (sparse.mode) {
+    case SP_DESC_SPARSE_DA_F16:
+        if ((rc = conv_c128_sparse(stream, sparse.ctx, sparse.a4b, sparse.da_w, sparse.da_bias, p.height / 8, p.width / 8, sparse.da_g32_first, p.width, p.height,
+                                   p.max_num, b.kps_xy, b.n_kps, sparse.da_compact, 256, batch))) return rc;
+        if ((rc = convdb_sparse_sample(stream, sparse.ctx, sparse.da_compact, 256, sparse.wfrag, sparse.bias, p.width, p.height, p.max_num, b.kps_xy, b.n_kps,
+                                       b.raw_desc, batch, true))) return rc;
+        break;
+    case SP_DESC_SPARSE_F16:
+        if ((rc = convdb_sparse_sample(stream, sparse.ctx, sparse.cda, sparse.in_cstride, sparse.wfrag, sparse.bias, p.width, p.height, p.max_num,
+                                       b.kps_xy, b.n_kps, b.raw_desc, batch, false))) return rc;
+        break;
+    case SP_DESC_GATHER_F32: case SP_DESC_SPARSE_DA_SPLIT: {
         // exact-f32 descriptor head only where the sampler reads: gather the cells -> the SAME 1x1 convolution kernel and per-cell norm the dense
         // map uses, on [8][N / 8] pixels instead of [batch][Hc][Wc] -> sample the compact rows
         const int64_t n_rows = (((int64_t)batch * p.max_num * 4) + 7) & ~(int64_t)7;
-        if (sparse.a4b_split) {
-            int rc = conv_split_c128_sparse(stream, sparse.ctx, sparse.a4b_split, sparse.da_w, sparse.da_bias, sparse.da_inv, p.height / 8, p.width / 8,
-                                            sparse.da_g32_first, p.width, p.height, p.max_num, b.kps_xy, b.n_kps, sparse.cx, batch);
-            if (rc) return rc;
+        if (split_da) {
+            if ((rc = conv_split_c128_sparse(stream, sparse.ctx, sparse.a4b, sparse.da_w, sparse.da_bias, sparse.da_inv, p.height / 8, p.width / 8,
+                                             sparse.da_g32_first, p.width, p.height, p.max_num, b.kps_xy, b.n_kps, sparse.cx, batch))) return rc;
         } else {
-            hipLaunchKernelGGL(sp_gather_cells_kernel, dim3(p.max_num, batch), dim3(256), 0, stream, sparse.cda_f32, sparse.in_cstride, p.width, p.height, p.max_num,
-                               b.kps_xy, b.n_kps, sparse.cx);
+            hipLaunchKernelGGL(sp_gather_cells_kernel, dim3(p.max_num, batch), dim3(256), 0, stream, reinterpret_cast<const float*>(sparse.cda), sparse.in_cstride,
+                               p.width, p.height, p.max_num, b.kps_xy, b.n_kps, sparse.cx);
             OMNI_LAUNCH_CHECK();
         }
-        int rc;
-        if (sparse.a4b_split && sparse.wdb_hi) {
+        if (split_da && sparse.split_db) {
             if ((rc = convdb_l2norm_split(stream, sparse.ctx, sparse.cx, 256, sparse.wdb_hi, sparse.wdb_lo, sparse.bias, sparse.cy, n_rows))) return rc;
         } else {
             ConvArgs a;
@@ -684,10 +684,13 @@ int sp_postprocess(hipStream_t stream, const SpPostParams& p, const SpPostBuffer
         hipLaunchKernelGGL(sp_sample_compact_kernel, dim3(p.max_num, batch), dim3(256), 0, stream, sparse.cy, p.width, p.height, p.max_num, b.kps_xy, b.n_kps,
                            b.raw_desc);
         OMNI_LAUNCH_CHECK();
-    } else {
+        break;
+    }
+    case SP_DESC_DENSE_GENERIC: case SP_DESC_DENSE_F16:
         hipLaunchKernelGGL(sp_sample_kernel, dim3(cdiv(p.max_num, SAMPLE_KPB), batch), dim3(256), 0, stream, desc_nhwc, p.width, p.height,
                            p.max_num, b.kps_xy, b.n_kps, b.raw_desc);
         OMNI_LAUNCH_CHECK();
+        break;
     }
     hipLaunchKernelGGL(sp_chan_sumsq_kernel, dim3(NORM_SEGS, batch), dim3(256), 0, stream, p.max_num, b.n_kps, b.raw_desc, b.norm_partial);
     OMNI_LAUNCH_CHECK();

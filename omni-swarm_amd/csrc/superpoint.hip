@@ -4,21 +4,27 @@
 //
 // HBM layout per handle (sized for max_batch images, all NHWC, element type = precision):
 //   a1a [B][H][W][64]   a1b [B][H/2][W/2][64]   a2a  a2b [B][H/4][W/4][64]   a3a [..][128]  a3b [B][H/8][W/8][128]
-//   a4a a4b [..][128]   heads [B][Hc][Wc][512] (cPa | cDa, one fused N=512 conv)   draw [B][Hc][Wc][256] fp32
+//   a4a a4b [..][128]   heads [B][Hc][Wc][512] (cPa | cDa, one fused N=512 conv; fp32 under OMNI_PREC_SPLIT)   draw [B][Hc][Wc][256] fp32
 //   semi [B][H][W] fp32
+//   headsP [B][Hc][Wc][256] cPa alone, for the passes that run convDa only at the key points' cells (fp16; OMNI_PREC_SPLIT: fp32)
+//   da_compact [B][max_num][4][256] fp16 (fp16 path) / cx32, cy32 [ceil8(B * max_num * 4)][256] fp32 (fp32, split): cDa at the four coarse cells around
+//   every key point, and (cy32) convDb + norm of those rows
+// OMNI_PREC_SPLIT keeps every activation map in a zero frame (conv.h: split-64, or raw-32 between two Winograd layers).
+// Which kernels a pass runs on these buffers is decided by sp_plan_pass (sp_plan.h), nowhere else.
 #include <algorithm>
 #include <vector>
 
 #include "config.h"
 #include "conv.h"
+#include "sp_plan.h"
 #include "sp_post.h"
 
 namespace {
-struct LayerDef { const char* name; int cin, cout, ks; };
+struct LayerDef { const char* name; int cin, cout, ks, div; bool pool; };     // div: the layer's INPUT map is H / div x W / div; pool: 2x2 max-pool behind it
 const LayerDef kLayers[OMNI_SP_NUM_LAYERS] = {
-    {"conv1a", 1, 64, 3},  {"conv1b", 64, 64, 3},   {"conv2a", 64, 64, 3},   {"conv2b", 64, 64, 3},
-    {"conv3a", 64, 128, 3}, {"conv3b", 128, 128, 3}, {"conv4a", 128, 128, 3}, {"conv4b", 128, 128, 3},
-    {"convPa", 128, 256, 3}, {"convPb", 256, 65, 1}, {"convDa", 128, 256, 3}, {"convDb", 256, 256, 1}};
+    {"conv1a", 1, 64, 3, 1, false},    {"conv1b", 64, 64, 3, 1, true},     {"conv2a", 64, 64, 3, 2, false},    {"conv2b", 64, 64, 3, 2, true},
+    {"conv3a", 64, 128, 3, 4, false},  {"conv3b", 128, 128, 3, 4, true},   {"conv4a", 128, 128, 3, 8, false},  {"conv4b", 128, 128, 3, 8, false},
+    {"convPa", 128, 256, 3, 8, false}, {"convPb", 256, 65, 1, 8, false},   {"convDa", 128, 256, 3, 8, false},  {"convDb", 256, 256, 1, 8, false}};
 enum { L1A = 0, L1B, L2A, L2B, L3A, L3B, L4A, L4B, LPA, LPB, LDA, LDB };
 // profiling stages
 enum { ST_CONV1A = 0, ST_CONV1B, ST_CONV2A, ST_CONV2B, ST_CONV3A, ST_CONV3B, ST_CONV4A, ST_CONV4B, ST_HEADS_A,
@@ -28,9 +34,33 @@ const char* kStageNames[OMNI_SP_NUM_STAGES] = {
     "convPb+softmax+d2s", "convDb+l2norm", "nms+topk+describe", "", "", "", ""};
 }  // namespace
 
+// Every device allocation of a handle: what alloc() handed out is what omni_sp_destroy frees -- no list to keep next to the struct's pointers
+struct SpDevMem {
+    std::vector<void*> ptrs;
+    template <typename T>
+    int alloc(T** p, size_t bytes, hipStream_t st = nullptr, bool zero = false) {
+        void* q = nullptr;
+        OMNI_HIP_TRY(hipMalloc(&q, bytes));
+        ptrs.push_back(q);
+        *p = static_cast<T*>(q);
+        if (zero) OMNI_HIP_TRY(hipMemsetAsync(q, 0, bytes, st));
+        return OMNI_OK;
+    }
+    void release(void* one, bool all) {
+        for (void*& q : ptrs)
+            if (q && (all || q == one)) { (void)hipFree(q); q = nullptr; }
+    }
+    void release_one(void* p) { release(p, false); }        // a lazy buffer that has to grow (null: nothing)
+    void release_all() { release(nullptr, true); ptrs.clear(); }
+};
+
 struct omni_sp {
     omni_ctx* ctx = nullptr;
     omni::Config cfg;                        // the switches as they stood when the handle was created (config.h)
+    omni::SpHandleFacts facts;               // ... and what sp_plan_pass reads of them (sp_plan.h)
+    omni::SpPassPlan last;                   // the plan of the last forward pass: what it left in the buffers (sp_make_dense, omni_sp_debug_layer)
+    omni::SpMaskSkipState skip_state = omni::SP_SKIP_STALE;
+    SpDevMem mem;
     int W = 0, H = 0, Hc = 0, Wc = 0, max_num = 0, max_batch = 0, precision = 0, pca_dim = 0, desc_dim = 256;
     float thres = 0.f;
     size_t esz = 4;
@@ -43,35 +73,21 @@ struct omni_sp {
     float* wPbT = nullptr;                   // [256][65]
     float *wPbA = nullptr, *wPbDust = nullptr; // convPb in MFMA A-fragment order + the dustbin row
     void* wPbA16 = nullptr;                    // convPb as split-fp16 A fragments (detector_head_mfma16_kernel); OMNI_DET16=0 keeps the f32 MFMA head
-    bool det16 = true;
-    bool fused_cand = true;                  // getKeyPoints' threshold inside the detector head's epilogue (OMNI_SP_FUSED_CAND)
-    // fp16 path: descriptors are computed only at the four coarse cells around each key point (convdb_sparse_sample) and the dense map `draw`
-    // is produced on demand (omni_sp_get_dense) -- OMNI_SP_SPARSE_DESC=0 keeps the dense map in every forward pass (A/B, parity tests)
-    bool sparse_desc = true;
-    bool sparse_da = true;                   // ... and convDa itself only there too (conv_c128_sparse); OMNI_SP_SPARSE_DA=0: convDa stays dense
-    void* headsP = nullptr;                  // [B][Hc][Wc][256] cPa alone (sparse_da passes)
-    bool heads_full = true;                  // `heads` holds the fused layer of the last pass (false: OMNI_PREC_SPLIT ran cPa alone + convDa at the key points)
+    void* headsP = nullptr;                  // [B][Hc][Wc][256] cPa alone (passes with convDa at the key points only)
     void* da_compact = nullptr;              // [B][max_num][4][256] fp16: cDa at the corner cells of the key points
     float *cx32 = nullptr, *cy32 = nullptr;  // fp32 paths: the gathered cDa rows / their convDb + norm, [ceil8(B * max_num * 4)][256] each
-    bool dense_valid = false, dense_possible = false;   // `draw` holds / `heads` can still produce the dense map of the last forward pass
-    int last_batch = 0;
+    int last_batch = 0;                      // images of the last forward pass (0: none yet -- nothing to make a dense map from)
     void* wDbFrag = nullptr;                    // convDb as register-resident fp16 A fragments (fused convDb + L2 norm, fp16 path)
     void* wDbFragHi = nullptr; void* wDbFragLo = nullptr;      // OMNI_PREC_SPLIT: the same as (hi, lo) pairs (convdb_l2norm_split); OMNI_SP_SPLIT_DB=0: exact-f32 convDb
     float* bias_heads = nullptr;             // [512]
     float* lut = nullptr;
     uint16_t* w1a_frag = nullptr;            // conv1a split-fp16 A fragments (fused conv1a+conv1b, fp16 path)
     uint32_t* lut_hl = nullptr;              // u8 -> (half hi, half lo) table
-    bool fuse1a = false;
-    bool split_fuse1a = false;               // OMNI_PREC_SPLIT: conv1a is built inside conv1b's kernel (OMNI_SPLIT_FUSE1A=0: the separate conv1a_split pass)
-    // OMNI_PREC_SPLIT, Winograd F(2x2,3x3) kernels (conv_wino.hip) for the cin = 64 layers: bit 0 = conv1b (needs the conv1a fusion), 1 = conv2a, 2 = conv2b, 3 = conv3a (64 -> 128: two output-channel groups)
-    // (OMNI_SPLIT_WINO).  Between two Winograd layers the activation frame is raw-32 instead of split-64 (same geometry, same bytes): raw_1b / raw_2a say
-    // what the LAST pass left in a1b / a2a; a_tmp: the converted input of a Winograd layer behind a direct one (mixed configurations only)
-    int wino = 0;
+    // OMNI_PREC_SPLIT, Winograd F(2x2,3x3) kernels (conv_wino.hip) for the cin = 64 layers named by facts.wino: their weights; a_tmp: the converted
+    // input of a Winograd layer behind a direct one (mixed configurations only, allocated by the first pass that needs it)
     void* wpk_w[OMNI_SP_NUM_LAYERS] = {};
     float winv_w[OMNI_SP_NUM_LAYERS] = {};
-    bool raw_1b = false, raw_2a = false, raw_2b = false;
     void* a_tmp = nullptr;
-    bool mask_skip_cal_fused = false;        // ... and which of the two the mask's constant region was calibrated with
     float* pca_compT = nullptr;
     float* pca_mean = nullptr;
     // activations
@@ -85,14 +101,13 @@ struct omni_sp {
     hipEvent_t ev[OMNI_SP_NUM_STAGES + 1] = {};
     hipEvent_t ev_convs = nullptr;           // recorded behind the last CU-filling kernel of a pass (the detector head): what omni_cam_order_after waits for
     bool perf = false, perf_valid = false;    // omni_sp_set_perf: every pass records its stage events (omni_sp_last_stage_ms)
-    int conv_variant = 0;                    // OMNI_CONV_V1=1: generic conv kernel everywhere, 2: v2 persistent kernel (A/B and debugging)
     // The constant region of the fisheye mask (fp16 path; OMNI_SP_MASK_SKIP=0 switches it off).  LoopCam blanks rows [3H/4, 3H/4 + H/4) of every image before the
     // network sees it (loop_cam.cpp:536-539): a few pixels inside that band -- one per 3x3 convolution, doubling with every pool -- every
     // activation is ONE vector per layer, whatever the image (its whole receptive field is zeros; the arithmetic of a pixel does not depend on
     // where it is).  The vectors are read once from a pass over an all-zero image (sp_calibrate_mask_skip) and written once into the rectangle
     // of CONV_TH x CONV_TW tiles that lies inside the region, in every image slot of the activation buffers; the persistent cin = 64 kernel then
     // leaves those tiles out of its walk (ConvArgs::skip_*).  Results are bit-identical to the dense pass (tests/test_gpu_mask_skip.py).  A pass
-    // without the mask (or on another path) overwrites the rectangles: the next masked pass calibrates again.
+    // without the mask (or on another path) overwrites the rectangles: the next masked pass calibrates again (skip_state, sp_mask_skip_step).
     struct MaskSkip {
         int ty0 = 0, ty1 = 0, tx0 = 0, tx1 = 0;      // tile rectangle in the layer's conv-output tile grid (before the pool)
         int oy0 = 0, oy1 = 0, ox0 = 0, ox1 = 0;      // the same rectangle in the layer's output map (after the pool)
@@ -104,16 +119,17 @@ struct omni_sp {
         double frac = 0.0;                           // the rectangle's share of the layer's tiles (omni_sp_stage_tiles_left_out)
     };
     MaskSkip mskip[6];                       // conv1a (OMNI_PREC_SPLIT, unfused, only), conv1b (+pool), conv2a, conv2b (+pool), conv3a, conv3b (+pool; OMNI_PREC_SPLIT only)
-    bool mask_skip = false, mask_skip_ready = false, mask_skip_calibrating = false;
-    uint8_t* zero_gray = nullptr;
+    uint8_t* zero_gray = nullptr;            // the calibration's all-zero image (grows with the largest stride seen)
     size_t zero_gray_bytes = 0;
     std::mutex mu;
 };
 
 namespace omni {
 
-static int dev_upload(void** dst, const void* src, size_t bytes, hipStream_t st) {
-    OMNI_HIP_TRY(hipMalloc(dst, bytes));
+template <typename T>
+static int dev_upload(omni_sp* s, T** dst, const void* src, size_t bytes) {
+    hipStream_t st = s->ctx->stream;
+    if (int rc = s->mem.alloc(dst, bytes)) return rc;
     OMNI_HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st));
     OMNI_HIP_TRY(hipStreamSynchronize(st));
     return OMNI_OK;
@@ -157,9 +173,9 @@ static void sp_mask_skip_rects(int H, int W, bool split, omni_sp::MaskSkip (&ks)
 }
 
 static int sp_plan_mask_skip(omni_sp* s) {
-    s->mask_skip = false;
+    s->facts.mask_skip = false;
     const bool split = s->precision == OMNI_PREC_SPLIT;
-    if (s->conv_variant != 0 || s->precision == OMNI_PREC_F32) return OMNI_OK;
+    if (s->facts.conv_variant != 0 || s->precision == OMNI_PREC_F32) return OMNI_OK;
     if (!s->cfg[split ? CFG_SP_MASK_SKIP_SPLIT : CFG_SP_MASK_SKIP]) return OMNI_OK;       // = 0: the dense pass (A/B, tests)
     sp_mask_skip_rects(s->H, s->W, split, s->mskip);
     void** maps[6] = {&s->a1a, &s->a1b, &s->a2a, &s->a2b, &s->a3a, &s->a3b};
@@ -176,11 +192,25 @@ static int sp_plan_mask_skip(omni_sp* s) {
             k.pix_bytes = k.oc * 2; k.row_bytes = (int64_t)k.ow * k.pix_bytes; k.img_bytes = k.row_bytes * k.oh; k.org_bytes = 0;
         }
         if (k.ty1 > k.ty0) {
-            OMNI_HIP_TRY(hipMalloc(&k.vec, (size_t)k.pix_bytes * 4));                // (x 4: conv2a as a Winograd layer keeps one vector per position in the 2 x 2 tile)
-            s->mask_skip = true;
+            if (int rc = s->mem.alloc(&k.vec, (size_t)k.pix_bytes * 4)) return rc;   // (x 4: conv2a as a Winograd layer keeps one vector per position in the 2 x 2 tile)
+            s->facts.mask_skip = true;
         }
     }
     return OMNI_OK;
+}
+
+// what sp_plan_pass reads of the handle: the switches of config.h as they stand now (mask_skip: sp_plan_mask_skip, at the end of sp_init)
+static void sp_set_facts(omni_sp* s) {
+    SpHandleFacts& f = s->facts;
+    f.precision = s->precision; f.H = s->H; f.W = s->W;
+    f.conv_variant = s->cfg[CFG_CONV_V1];
+    f.det16 = s->cfg[CFG_DET16] != 0;
+    f.fused_cand = s->cfg[CFG_SP_FUSED_CAND] != 0;
+    f.sparse_desc = s->cfg[CFG_SP_SPARSE_DESC] != 0;
+    f.sparse_da = s->cfg[CFG_SP_SPARSE_DA] != 0;
+    f.split_fuse1a = s->cfg[CFG_SPLIT_FUSE1A] != 0;
+    f.split_db = s->cfg[CFG_SP_SPLIT_DB] != 0;
+    f.wino = sp_wino_layers(s->precision, s->cfg[CFG_SPLIT_WINO], s->H, s->W, f.split_fuse1a);
 }
 
 static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, const float* pca_mean) {
@@ -188,69 +218,52 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
     int rc;
     // biases, conv1a, convPb (fp32 always)
     for (int l = 0; l < OMNI_SP_NUM_LAYERS; ++l)
-        if ((rc = dev_upload((void**)&s->bias[l], w->bias[l], (size_t)kLayers[l].cout * 4, st))) return rc;
-    if ((rc = dev_upload((void**)&s->w1a, w->weight[L1A], 64 * 9 * 4, st))) return rc;
+        if ((rc = dev_upload(s, &s->bias[l], w->bias[l], (size_t)kLayers[l].cout * 4))) return rc;
+    if ((rc = dev_upload(s, &s->w1a, w->weight[L1A], 64 * 9 * 4))) return rc;
     {
         std::vector<float> t(256 * 65);
         for (int c = 0; c < 65; ++c)
             for (int k = 0; k < 256; ++k) t[(size_t)k * 65 + c] = w->weight[LPB][(size_t)c * 256 + k];
-        if ((rc = dev_upload((void**)&s->wPbT, t.data(), t.size() * 4, st))) return rc;
+        if ((rc = dev_upload(s, &s->wPbT, t.data(), t.size() * 4))) return rc;
         std::vector<float> wa(16384), wdst(256);
         detector_pack_weights(t.data(), wa.data(), wdst.data());
-        if ((rc = dev_upload((void**)&s->wPbA, wa.data(), wa.size() * 4, st))) return rc;
-        if ((rc = dev_upload((void**)&s->wPbDust, wdst.data(), wdst.size() * 4, st))) return rc;
+        if ((rc = dev_upload(s, &s->wPbA, wa.data(), wa.size() * 4))) return rc;
+        if ((rc = dev_upload(s, &s->wPbDust, wdst.data(), wdst.size() * 4))) return rc;
         std::vector<uint16_t> w16(2 * 2 * 16 * 64 * 8);
         detector_pack_weights16(t.data(), w16.data());
-        if ((rc = dev_upload(&s->wPbA16, w16.data(), w16.size() * 2, st))) return rc;
-        s->det16 = s->cfg[CFG_DET16] != 0;
-        s->fused_cand = s->cfg[CFG_SP_FUSED_CAND] != 0;
-        s->sparse_desc = s->cfg[CFG_SP_SPARSE_DESC] != 0;
-        s->sparse_da = s->sparse_desc && s->cfg[CFG_SP_SPARSE_DA] != 0;
+        if ((rc = dev_upload(s, &s->wPbA16, w16.data(), w16.size() * 2))) return rc;
     }
     {
         std::vector<float> bh(512);
         memcpy(bh.data(), w->bias[LPA], 256 * 4);
         memcpy(bh.data() + 256, w->bias[LDA], 256 * 4);
-        if ((rc = dev_upload((void**)&s->bias_heads, bh.data(), 512 * 4, st))) return rc;
+        if ((rc = dev_upload(s, &s->bias_heads, bh.data(), 512 * 4))) return rc;
     }
     {   // cv::Mat::convertTo(CV_32F, 1/255.0) (superpoint_tensorrt.cpp:127): OpenCV 3.4 scales 8-bit sources in float (cvt_32f): float(u8) * float(1/255.0)
         float lut[256];
         const volatile float alpha = (float)(1.0 / 255.0);                    // (volatile: one fp32 multiply, no contraction / folding in double)
         for (int i = 0; i < 256; ++i) lut[i] = (float)i * alpha;
-        if ((rc = dev_upload((void**)&s->lut, lut, sizeof(lut), st))) return rc;
+        if ((rc = dev_upload(s, &s->lut, lut, sizeof(lut)))) return rc;
     }
     if (s->precision == OMNI_PREC_F16) {
         std::vector<uint16_t> db(65536);
         convdb_pack_weights(w->weight[LDB], db.data());
-        if ((rc = dev_upload(&s->wDbFrag, db.data(), db.size() * 2, st))) return rc;
+        if ((rc = dev_upload(s, &s->wDbFrag, db.data(), db.size() * 2))) return rc;
     }
-    if (s->precision == OMNI_PREC_SPLIT && s->cfg[CFG_SP_SPLIT_DB] != 0) {
+    if (s->precision == OMNI_PREC_SPLIT && s->facts.split_db) {
         std::vector<uint16_t> hi(65536), lo(65536);
         convdb_pack_weights_split(w->weight[LDB], hi.data(), lo.data());
-        if ((rc = dev_upload(&s->wDbFragHi, hi.data(), hi.size() * 2, st))) return rc;
-        if ((rc = dev_upload(&s->wDbFragLo, lo.data(), lo.size() * 2, st))) return rc;
+        if ((rc = dev_upload(s, &s->wDbFragHi, hi.data(), hi.size() * 2))) return rc;
+        if ((rc = dev_upload(s, &s->wDbFragLo, lo.data(), lo.size() * 2))) return rc;
     }
-    if (s->precision == OMNI_PREC_SPLIT) {     // conv1a inside conv1b's kernel (conv1ab_split_fused): its weights x the activation scale, the u8 table
+    if (s->precision != OMNI_PREC_F32) {       // conv1a inside conv1b's kernel: its A fragments (OMNI_PREC_SPLIT: x the activation scale) and the u8 -> (hi, lo) table
+        const bool split = s->precision == OMNI_PREC_SPLIT, from_bytes = !split && s->cfg[CFG_PP_U8];      // fp16: operands straight from the bytes, no table (lut_hl stays null)
         std::vector<uint16_t> fr(2048);
-        conv1a_split_pack_fused(w->weight[L1A], w->bias[L1A], fr.data());
-        if ((rc = dev_upload((void**)&s->w1a_frag, fr.data(), fr.size() * 2, st))) return rc;
+        (split ? conv1a_split_pack_fused : from_bytes ? conv1a_pack_u8_weights : conv1a_pack_split_weights)(w->weight[L1A], w->bias[L1A], fr.data());
+        if ((rc = dev_upload(s, &s->w1a_frag, fr.data(), fr.size() * 2))) return rc;
         uint32_t lh[256];
         conv1a_make_split_lut(lh);
-        if ((rc = dev_upload((void**)&s->lut_hl, lh, sizeof(lh), st))) return rc;
-        s->split_fuse1a = s->cfg[CFG_SPLIT_FUSE1A] != 0;
-    }
-    if (s->precision == OMNI_PREC_F16) {
-        std::vector<uint16_t> fr(2048);
-        if (s->cfg[CFG_PP_U8]) {              // operands straight from the bytes: no table (lut_hl stays null)
-            conv1a_pack_u8_weights(w->weight[L1A], w->bias[L1A], fr.data());
-            if ((rc = dev_upload((void**)&s->w1a_frag, fr.data(), fr.size() * 2, st))) return rc;
-        } else {
-            conv1a_pack_split_weights(w->weight[L1A], w->bias[L1A], fr.data());
-            if ((rc = dev_upload((void**)&s->w1a_frag, fr.data(), fr.size() * 2, st))) return rc;
-            uint32_t lh[256];
-            conv1a_make_split_lut(lh);
-            if ((rc = dev_upload((void**)&s->lut_hl, lh, sizeof(lh), st))) return rc;
-        }
+        if (!from_bytes && (rc = dev_upload(s, &s->lut_hl, lh, sizeof(lh)))) return rc;
     }
     // packed MFMA weights
     auto pack_upload = [&](int l, const float* w_oihw, int cin, int cout, int ks) -> int {
@@ -258,16 +271,16 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
         if (s->precision == OMNI_PREC_SPLIT && ks == 3) {
             std::vector<uint16_t> p(n * 2);
             s->winv[l] = conv_pack_weights_split(w_oihw, cin, cout, p.data());
-            return dev_upload(&s->wpk[l], p.data(), n * 4, st);
+            return dev_upload(s, &s->wpk[l], p.data(), n * 4);
         }
         if (s->precision == OMNI_PREC_F16) {
             std::vector<__half> p(n);
             conv_pack_weights_f16(w_oihw, cin, cout, ks, p.data());
-            return dev_upload(&s->wpk[l], p.data(), n * 2, st);
+            return dev_upload(s, &s->wpk[l], p.data(), n * 2);
         }
         std::vector<float> p(n);
         conv_pack_weights_f32(w_oihw, cin, cout, ks, p.data());
-        return dev_upload(&s->wpk[l], p.data(), n * 4, st);
+        return dev_upload(s, &s->wpk[l], p.data(), n * 4);
     };
     for (int l : {L1B, L2A, L2B, L3A, L3B, L4A, L4B, LDB})
         if ((rc = pack_upload(l, w->weight[l], kLayers[l].cin, kLayers[l].cout, kLayers[l].ks))) return rc;
@@ -279,16 +292,12 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
         if ((rc = pack_upload(LPA, wh.data(), 128, 512, 3))) return rc;
     }
     if (s->precision == OMNI_PREC_SPLIT) {
-        s->wino = s->cfg[CFG_SPLIT_WINO];
-        if (s->H % 8 != 0 || s->W % 8 != 0) s->wino &= 7;                         // conv3a: even H / 4, W / 4 (F(2x2,3x3) tiles)
-        if (s->H % 4 != 0 || s->W % 4 != 0) s->wino &= 1;                         // conv2a / conv2b: even H / 2, W / 2
-        if (s->H % 2 != 0 || s->W % 2 != 0 || !s->split_fuse1a) s->wino &= ~1;
         for (int l : {L1B, L2A, L2B, L3A}) {
-            if (!(s->wino & (l == L1B ? 1 : l == L2A ? 2 : l == L2B ? 4 : 8))) continue;
+            if (!(s->facts.wino & (l == L1B ? 1 : l == L2A ? 2 : l == L2B ? 4 : 8))) continue;
             const int co = kLayers[l].cout;
             std::vector<uint16_t> p((size_t)64 * co * 16 * 2);
             s->winv_w[l] = conv_pack_weights_wino(w->weight[l], 64, co, p.data());
-            if ((rc = dev_upload(&s->wpk_w[l], p.data(), p.size() * 2, st))) return rc;
+            if ((rc = dev_upload(s, &s->wpk_w[l], p.data(), p.size() * 2))) return rc;
         }
     }
     if (s->precision == OMNI_PREC_SPLIT) {
@@ -296,15 +305,15 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
         for (int l : {L1B, L2A, L2B, L3A, L3B, L4A, L4B}) {
             std::vector<float> b(kLayers[l].cout);
             for (int c = 0; c < kLayers[l].cout; ++c) b[c] = S * w->bias[l][c];
-            if ((rc = dev_upload((void**)&s->bias_s[l], b.data(), b.size() * 4, st))) return rc;
+            if ((rc = dev_upload(s, &s->bias_s[l], b.data(), b.size() * 4))) return rc;
         }
     }
     if (pca_comp) {
         std::vector<float> t((size_t)256 * s->pca_dim);
         for (int j = 0; j < s->pca_dim; ++j)
             for (int c = 0; c < 256; ++c) t[(size_t)c * s->pca_dim + j] = pca_comp[(size_t)j * 256 + c];
-        if ((rc = dev_upload((void**)&s->pca_compT, t.data(), t.size() * 4, st))) return rc;
-        if ((rc = dev_upload((void**)&s->pca_mean, pca_mean, 256 * 4, st))) return rc;
+        if ((rc = dev_upload(s, &s->pca_compT, t.data(), t.size() * 4))) return rc;
+        if ((rc = dev_upload(s, &s->pca_mean, pca_mean, 256 * 4))) return rc;
     }
     // activations
     const size_t B = s->max_batch, H = s->H, W = s->W, e = s->esz;
@@ -314,49 +323,39 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
         const Act acts[] = {{&s->a1a, H, W, 64},         {&s->a1b, H / 2, W / 2, 64},  {&s->a2a, H / 2, W / 2, 64},  {&s->a2b, H / 4, W / 4, 64},
                             {&s->a3a, H / 4, W / 4, 128}, {&s->a3b, H / 8, W / 8, 128}, {&s->a4a, H / 8, W / 8, 128}, {&s->a4b, H / 8, W / 8, 128}};
         for (const Act& a : acts) {
-            if (s->precision == OMNI_PREC_SPLIT) {
-                const size_t bytes = B * split_frame_bytes((int)a.h, (int)a.w, (int)a.c);
-                OMNI_HIP_TRY(hipMalloc(a.p, bytes));
-                OMNI_HIP_TRY(hipMemsetAsync(*a.p, 0, bytes, st));
-            } else {
-                OMNI_HIP_TRY(hipMalloc(a.p, B * a.h * a.w * a.c * e));
-            }
+            const bool framed = s->precision == OMNI_PREC_SPLIT;
+            if ((rc = s->mem.alloc(a.p, framed ? B * split_frame_bytes((int)a.h, (int)a.w, (int)a.c) : B * a.h * a.w * a.c * e, st, framed))) return rc;
         }
         OMNI_HIP_TRY(hipStreamSynchronize(st));
     }
-    OMNI_HIP_TRY(hipMalloc(&s->heads, B * (H / 8) * (W / 8) * 512 * e));
+    if ((rc = s->mem.alloc(&s->heads, B * (H / 8) * (W / 8) * 512 * e))) return rc;
     if (s->precision == OMNI_PREC_F16) {
-        OMNI_HIP_TRY(hipMalloc(&s->headsP, B * (H / 8) * (W / 8) * 256 * e));
-        OMNI_HIP_TRY(hipMalloc(&s->da_compact, B * (size_t)s->max_num * 4 * 256 * 2));
+        if ((rc = s->mem.alloc(&s->headsP, B * (H / 8) * (W / 8) * 256 * e))) return rc;
+        if ((rc = s->mem.alloc(&s->da_compact, B * (size_t)s->max_num * 4 * 256 * 2))) return rc;
     }
     if (s->precision != OMNI_PREC_F16) {
         const size_t rows = ((B * (size_t)s->max_num * 4) + 7) & ~(size_t)7;
-        OMNI_HIP_TRY(hipMalloc((void**)&s->cx32, rows * 256 * 4));
-        OMNI_HIP_TRY(hipMalloc((void**)&s->cy32, rows * 256 * 4));
-        OMNI_HIP_TRY(hipMemsetAsync(s->cx32, 0, rows * 256 * 4, st));          // rows of key points that do not exist are never written (and never read back)
+        if ((rc = s->mem.alloc(&s->cx32, rows * 256 * 4, st, true))) return rc;      // rows of key points that do not exist are never written (and never read back)
+        if ((rc = s->mem.alloc(&s->cy32, rows * 256 * 4))) return rc;
         OMNI_HIP_TRY(hipStreamSynchronize(st));
     }
-    if (s->precision == OMNI_PREC_SPLIT) OMNI_HIP_TRY(hipMalloc(&s->headsP, B * (H / 8) * (W / 8) * 256 * 4));     // cPa alone, fp32 (sparse convDa passes)
-    OMNI_HIP_TRY(hipMalloc((void**)&s->draw, B * (H / 8) * (W / 8) * 256 * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->semi, B * H * W * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->gray_stage, B * H * W));
-    // post-processing buffers
+    if (s->precision == OMNI_PREC_SPLIT && (rc = s->mem.alloc(&s->headsP, B * (H / 8) * (W / 8) * 256 * 4))) return rc;     // cPa alone, fp32 (sparse convDa passes)
+    if ((rc = s->mem.alloc(&s->draw, B * (H / 8) * (W / 8) * 256 * 4))) return rc;
+    if ((rc = s->mem.alloc(&s->semi, B * H * W * 4))) return rc;
+    if ((rc = s->mem.alloc(&s->gray_stage, B * H * W))) return rc;
+    // post-processing buffers (the results zeroed once: the slots of key points that do not exist)
     const size_t hw = H * W, M = s->max_num;
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.cand, B * hw * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.cand_masks, B * hw * 16));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.counters, B * 4 * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.surv_keys, B * hw * 8));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.raw_desc, B * M * 256 * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.norm_partial, B * 8 * 256 * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.kps_xy, B * M * 2 * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.scores, B * M * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.n_kps, B * 4));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.desc_out, B * M * s->desc_dim * 4));
-    OMNI_HIP_TRY(hipMemsetAsync(s->pb.n_kps, 0, B * 4, st));
-    OMNI_HIP_TRY(hipMemsetAsync(s->pb.kps_xy, 0, B * M * 2 * 4, st));
-    OMNI_HIP_TRY(hipMemsetAsync(s->pb.desc_out, 0, B * M * s->desc_dim * 4, st));
-    OMNI_HIP_TRY(hipMemsetAsync(s->pb.scores, 0, B * M * 4, st));
-    OMNI_HIP_TRY(hipMalloc((void**)&s->pb.cand_bits, B * (H / 8) * (W / 8) * 2 * 4));
+    if ((rc = s->mem.alloc(&s->pb.cand, B * hw * 4))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.cand_masks, B * hw * 16))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.counters, B * 4 * 4))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.surv_keys, B * hw * 8))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.raw_desc, B * M * 256 * 4))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.norm_partial, B * 8 * 256 * 4))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.kps_xy, B * M * 2 * 4, st, true))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.scores, B * M * 4, st, true))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.n_kps, B * 4, st, true))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.desc_out, B * M * s->desc_dim * 4, st, true))) return rc;
+    if ((rc = s->mem.alloc(&s->pb.cand_bits, B * (H / 8) * (W / 8) * 2 * 4))) return rc;
     s->pb.pca_compT = s->pca_compT;
     s->pb.pca_mean = s->pca_mean;
     for (int i = 0; i <= OMNI_SP_NUM_STAGES; ++i) OMNI_HIP_TRY(hipEventCreate(&s->ev[i]));
@@ -365,30 +364,82 @@ static int sp_init(omni_sp* s, const omni_sp_weights* w, const float* pca_comp, 
     return sp_plan_mask_skip(s);
 }
 
-static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, bool with_events, bool run_post);
+// ---- one way to make a layer call ---------------------------------------------------------------------------------------------------------------
+static int tails_prec(const SpPassPlan& p) { return p.tails_f32 ? OMNI_PREC_F32 : OMNI_PREC_F16; }     // the heads layer's output type: OMNI_PREC_SPLIT hands its tails fp32
+
+enum SpKernelFamily { SP_K_DIRECT, SP_K_WINO };      // conv_mfma / conv_split and the kernels fused around them; conv_wino.hip
+// The ConvArgs of layer l of this handle, for every call site.  Shape, pool and ReLU are the layer's (kLayers); cout = 256 runs the heads layer for
+// cPa alone.  n_cu, zero_page and variant are set for every layer.  (The call sites used to differ in them; no difference was ever read: conv_mfma
+// looks at the three for 3x3 layers only -- the 1x1 convDb runs the generic kernel whatever they say -- and conv_split, conv_wino and the fused
+// conv1a + conv1b launchers read neither `variant` nor, conv1ab_fused apart, which needs it, `zero_page`.)
+static ConvArgs sp_layer_args(const omni_sp* s, const SpPassPlan& p, int l, SpKernelFamily fam, const void* in, void* out, int batch, int cout = 0) {
+    const LayerDef& d = kLayers[l];
+    const bool split = s->precision == OMNI_PREC_SPLIT, wino = fam == SP_K_WINO;
+    ConvArgs a;
+    a.in = in; a.out = out; a.batch = batch; a.H = s->H / d.div; a.W = s->W / d.div; a.cin = d.cin; a.cout = cout ? cout : d.cout; a.ksize = d.ks;
+    a.relu = l != LDB; a.pool = d.pool;
+    a.out_f32 = l == LDB || (l == LPA && split);               // the descriptor map; OMNI_PREC_SPLIT: the heads layer's output, true values
+    if (l == LDB) a.in_cstride = 512;                          // cDa: channels [256, 512) of the fused heads buffer
+    a.w_packed = wino ? s->wpk_w[l] : s->wpk[l];
+    a.split_inv = wino ? s->winv_w[l] : s->winv[l];            // (0 outside OMNI_PREC_SPLIT)
+    a.bias = l == LPA ? s->bias_heads : (split && !a.out_f32) ? s->bias_s[l] : s->bias[l];       // the scaled bias goes with scaled (split-64 / raw-32) outputs
+    a.n_cu = s->ctx->prop.multiProcessorCount; a.zero_page = s->ctx->zero_page; a.variant = s->facts.conv_variant;
+    const int i = l == L1B ? 1 : l == L2A ? 2 : l == L2B ? 3 : l == L3A ? 4 : l == L3B ? 5 : -1;
+    if (p.use_skip && i >= 0) { a.skip_ty0 = s->mskip[i].ty0; a.skip_ty1 = s->mskip[i].ty1; a.skip_tx0 = s->mskip[i].tx0; a.skip_tx1 = s->mskip[i].tx1; }
+    return a;
+}
+// layer l on the precision's direct kernels (convDb: the tails' precision)
+static int sp_conv(omni_sp* s, const SpPassPlan& p, int l, const void* in, void* out, int batch, int cout = 0) {
+    const ConvArgs a = sp_layer_args(s, p, l, SP_K_DIRECT, in, out, batch, cout);
+    if (l == LDB) return conv_mfma(s->ctx->stream, tails_prec(p), a);
+    return s->precision == OMNI_PREC_SPLIT ? conv_split(s->ctx->stream, a) : conv_mfma(s->ctx->stream, s->precision, a);
+}
+// convPa | convDa fused over every cell into `heads`, or (cpa_only) convPa alone into headsP: the detector branch needs cPa everywhere, cDa (output
+// channels 256-511 of the fused layer) is only read around the key points
+static int sp_heads_layer(omni_sp* s, const SpPassPlan& p, int batch, bool cpa_only) {
+    return sp_conv(s, p, LPA, s->a4b, cpa_only ? s->headsP : s->heads, batch, cpa_only ? 256 : 512);
+}
+static const void* sp_cda(const omni_sp* s) { return (const char*)s->heads + (size_t)256 * s->esz; }      // cDa inside `heads`: pixel stride 512
+// the dense descriptor map, fp16: convDb + descriptor L2 norm in one HBM pass
+static int sp_desc_dense_f16(omni_sp* s, int batch) {
+    return convdb_l2norm(s->ctx->stream, s->ctx, sp_cda(s), 512, s->wDbFrag, s->bias[LDB], s->draw, (int64_t)batch * s->Hc * s->Wc);
+}
+// ... every other path: the generic 1x1 convolution, then the norm in place
+static int sp_desc_dense_generic(omni_sp* s, const SpPassPlan& p, int batch) {
+    if (int rc = sp_conv(s, p, LDB, sp_cda(s), s->draw, batch)) return rc;
+    return l2norm_channels(s->ctx->stream, s->draw, (int64_t)batch * s->Hc * s->Wc);
+}
+// the operands of every descriptor tail that runs inside the post-processing; p.desc says which of them are read
+static SpSparseDesc sp_sparse_desc(const omni_sp* s, const SpPassPlan& p) {
+    SpSparseDesc sd;
+    sd.mode = p.desc; sd.split_db = p.desc_split_db; sd.cand_fused = p.cand_fused;
+    sd.ctx = s->ctx; sd.cda = sp_cda(s); sd.in_cstride = 512; sd.bias = s->bias[LDB];
+    sd.wfrag = s->wDbFrag; sd.wdb_hi = s->wDbFragHi; sd.wdb_lo = s->wDbFragLo; sd.wdb_f32 = s->wpk[LDB];
+    sd.a4b = s->a4b; sd.da_w = s->wpk[LPA]; sd.da_bias = s->bias_heads; sd.da_g32_first = 8; sd.da_inv = s->winv[LPA]; sd.da_compact = s->da_compact;
+    sd.cx = s->cx32; sd.cy = s->cy32; sd.n_cu = s->ctx->prop.multiProcessorCount; sd.zero_page = s->ctx->zero_page;
+    return sd;
+}
+
+static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, bool with_events, bool run_post, bool calibrating = false);
 // One dense pass over an all-zero image with the mask on; every planned layer's constant is read from the middle of its rectangle and written
-// into that rectangle of every image slot of the layer's activation buffer.  The calibration pass takes the same conv1a form as the pass it
-// serves (fuse1a): an unfused pass whose image only missed the fusion through its pointer (stride % 4 == 0) calibrates on the zero image one
-// byte past its start, so that conv1a's own rectangle (OMNI_PREC_SPLIT) is filled and the constants come from the same kernels.
-static int sp_calibrate_mask_skip(omni_sp* s, int stride, bool fuse1a) {
+// into that rectangle of every image slot of the layer's activation buffer.  The pass starts zero_image_offset bytes into the zero image
+// (sp_mask_skip_step: so that it takes the conv1a form of the pass it serves, conv1a's own rectangle (OMNI_PREC_SPLIT) is filled when that pass
+// skips it, and the constants come from the same kernels).
+static int sp_calibrate_mask_skip(omni_sp* s, int stride, int zero_image_offset) {
     hipStream_t st = s->ctx->stream;
+    int rc;
     const size_t need = (size_t)stride * s->H + 4;
     if (s->zero_gray_bytes < need) {
-        if (s->zero_gray) (void)hipFree(s->zero_gray);
+        s->mem.release_one(s->zero_gray);
         s->zero_gray = nullptr; s->zero_gray_bytes = 0;
-        OMNI_HIP_TRY(hipMalloc((void**)&s->zero_gray, need));
+        if ((rc = s->mem.alloc(&s->zero_gray, need, st, true))) return rc;
         s->zero_gray_bytes = need;
-        OMNI_HIP_TRY(hipMemsetAsync(s->zero_gray, 0, need, st));
     }
-    s->mask_skip_calibrating = true;
-    const int off = (!fuse1a && stride % 4 == 0) ? 1 : 0;
-    int rc = sp_forward(s, s->zero_gray + off, stride, 1, 1, false, false);
-    s->mask_skip_calibrating = false;
-    if (rc) return rc;
-    s->mask_skip_cal_fused = s->fuse1a;
+    if ((rc = sp_forward(s, s->zero_gray + zero_image_offset, stride, 1, 1, false, false, true))) return rc;
+    const SpPassPlan& cal = s->last;       // the calibration pass's own plan
     for (const omni_sp::MaskSkip& k : s->mskip) {
-        if (k.ty1 <= k.ty0 || (k.map == &s->a1a && s->fuse1a)) continue;
-        if (s->precision == OMNI_PREC_SPLIT && ((k.map == &s->a2a && (s->wino & 2)) || (k.map == &s->a3a && (s->wino & 8)))) {     // an unpooled Winograd layer: constant per position in the 2 x 2 output tile
+        if (k.ty1 <= k.ty0 || (k.map == &s->a1a && cal.conv1a == SP_1A_FUSED)) continue;
+        if ((k.map == &s->a2a && cal.conv2a.wino) || (k.map == &s->a3a && cal.conv3a.wino)) {     // an unpooled Winograd layer: constant per position in the 2 x 2 output tile
             if ((rc = conv_read_pixels2x2_bytes(st, *k.map, k.row_bytes, k.org_bytes, k.pix_bytes, ((k.oy0 + k.oy1) / 2) & ~1, ((k.ox0 + k.ox1) / 2) & ~1, k.vec))) return rc;
             if ((rc = conv_fill_rect2x2_bytes(st, *k.map, s->max_batch, k.img_bytes, k.row_bytes, k.org_bytes, k.pix_bytes, k.oy0, k.oy1, k.ox0, k.ox1, k.vec))) return rc;
             continue;
@@ -396,7 +447,6 @@ static int sp_calibrate_mask_skip(omni_sp* s, int stride, bool fuse1a) {
         if ((rc = conv_read_pixel_bytes(st, *k.map, k.row_bytes, k.org_bytes, k.pix_bytes, (k.oy0 + k.oy1) / 2, (k.ox0 + k.ox1) / 2, k.vec))) return rc;
         if ((rc = conv_fill_rect_bytes(st, *k.map, s->max_batch, k.img_bytes, k.row_bytes, k.org_bytes, k.pix_bytes, k.oy0, k.oy1, k.ox0, k.ox1, k.vec))) return rc;
     }
-    s->mask_skip_ready = true;
     return OMNI_OK;
 }
 
@@ -406,184 +456,91 @@ static SpPostParams post_params(const omni_sp* s) {
     return p;
 }
 
-// Enqueue the whole network + post-processing for `batch` HBM-resident images.  ev != nullptr records an event before
+// Enqueue the whole network + post-processing for `batch` HBM-resident images, as sp_plan_pass lays it out.  with_events records an event before
 // every stage (profiling only).
-static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, bool with_events,
-                      bool run_post) {
+static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, bool with_events, bool run_post, bool calibrating) {
     hipStream_t st = s->ctx->stream;
-    const int H = s->H, W = s->W, P = s->precision;
+    const int H = s->H, W = s->W, n_cu = s->ctx->prop.multiProcessorCount;
     int rc, stage = 0;
     if ((rc = s->ctx->ensure_zero_page())) return rc;
-    const bool aligned4 = stride % 4 == 0 && ((uintptr_t)gray_dev & 3) == 0;
-    const bool fuse1a = ((P == OMNI_PREC_F16 && s->conv_variant == 0) || (P == OMNI_PREC_SPLIT && s->split_fuse1a)) && aligned4;   // else: separate conv1a
-    // the constant region of the fisheye mask (omni_sp::MaskSkip): only on the production path (conv1a fused into conv1b)
-    const bool use_skip = s->mask_skip && fisheye_mask && (fuse1a || P == OMNI_PREC_SPLIT) && !s->mask_skip_calibrating;
-    if (!use_skip && !s->mask_skip_calibrating) s->mask_skip_ready = false;          // this pass overwrites the filled rectangles
-    if (use_skip && s->mask_skip_ready && s->mask_skip_cal_fused != fuse1a) s->mask_skip_ready = false;      // (conv1a's own rectangle is only filled by an unfused calibration)
-    if (use_skip && !s->mask_skip_ready && (rc = sp_calibrate_mask_skip(s, stride, fuse1a))) return rc;
+    SpPassInputs in;
+    in.aligned4 = stride % 4 == 0 && ((uintptr_t)gray_dev & 3) == 0; in.fisheye_mask = fisheye_mask != 0; in.run_post = run_post; in.calibrating = calibrating;
+    const SpPassPlan p = sp_plan_pass(s->facts, in);
+    const SpMaskSkipStep step = sp_mask_skip_step(s->skip_state, p, stride);
+    if (step.calibrate) {
+        s->skip_state = SP_SKIP_STALE;
+        if ((rc = sp_calibrate_mask_skip(s, stride, step.zero_image_offset))) return rc;
+    }
+    s->skip_state = step.after;
+    s->last = p; s->last_batch = batch;
     auto mark = [&]() -> int { if (with_events) OMNI_HIP_TRY(hipEventRecord(s->ev[stage], st)); ++stage; return OMNI_OK; };
-    // OMNI_PREC_SPLIT: which of the cin = 64 layers run as Winograd kernels in THIS pass, and the frame format between them
-    const bool w1b = P == OMNI_PREC_SPLIT && (s->wino & 1) && fuse1a, w2a = P == OMNI_PREC_SPLIT && (s->wino & 2) != 0, w2b = P == OMNI_PREC_SPLIT && (s->wino & 4) != 0,
-               w3a = P == OMNI_PREC_SPLIT && (s->wino & 8) != 0;
-    auto skip_of = [&](int l, ConvArgs& a) {
-        const int i = l == L1B ? 1 : l == L2A ? 2 : l == L2B ? 3 : l == L3A ? 4 : l == L3B ? 5 : -1;
-        if (use_skip && i >= 0) { a.skip_ty0 = s->mskip[i].ty0; a.skip_ty1 = s->mskip[i].ty1; a.skip_tx0 = s->mskip[i].tx0; a.skip_tx1 = s->mskip[i].tx1; }
-    };
-    auto conv = [&](int l, const void* in, void* out, const float* bias, int h, int w, int cin, int cout, int ks, bool relu,
-                    bool pool, bool out_f32) -> int {
-        ConvArgs a;
-        a.in = in; a.out = out; a.w_packed = s->wpk[l]; a.bias = bias; a.batch = batch; a.H = h; a.W = w; a.cin = cin;
-        a.cout = cout; a.ksize = ks; a.relu = relu; a.pool = pool; a.out_f32 = out_f32;
-        a.n_cu = s->ctx->prop.multiProcessorCount; a.zero_page = s->ctx->zero_page; a.variant = s->conv_variant;
-        skip_of(l, a);
-        if (P == OMNI_PREC_SPLIT) {     // split-64 activations in and (unless out_f32) out; the scaled bias goes with scaled outputs
-            a.split_inv = s->winv[l];
-            if (!out_f32) a.bias = s->bias_s[l];
-            return conv_split(st, a);
-        }
-        return conv_mfma(st, P, a);
-    };
-    const int PH = P == OMNI_PREC_SPLIT ? OMNI_PREC_F32 : P;      // the heads' tails: OMNI_PREC_SPLIT hands them fp32 activations
     if ((rc = mark())) return rc;
-    s->fuse1a = fuse1a;
-    if (P == OMNI_PREC_SPLIT && !fuse1a) { if ((rc = conv1a_split(st, gray_dev, stride, batch, H, W, fisheye_mask, s->w1a, s->bias[L1A], s->lut, s->a1a, use_skip ? s->mskip[0].ty0 : 0, use_skip ? s->mskip[0].ty1 : 0))) return rc; }
-    else if (!s->fuse1a) { if ((rc = conv1a_direct(st, P, gray_dev, stride, batch, H, W, fisheye_mask, s->w1a, s->bias[L1A], s->lut, s->a1a))) return rc; }
-    if ((rc = mark())) return rc;
-    if (s->fuse1a) {   // conv1a is computed inside conv1b's kernel: the conv1a activation tensor is never materialised
-        ConvArgs a;
-        a.in = nullptr; a.out = s->a1b; a.w_packed = s->wpk[L1B]; a.bias = s->bias[L1B]; a.batch = batch; a.H = H; a.W = W; a.cin = 64;
-        a.cout = 64; a.ksize = 3; a.relu = true; a.pool = true; a.out_f32 = false; a.n_cu = s->ctx->prop.multiProcessorCount; a.zero_page = s->ctx->zero_page;
-        skip_of(L1B, a);
-        if (P == OMNI_PREC_SPLIT && w1b) {
-            a.w_packed = s->wpk_w[L1B]; a.split_inv = s->winv_w[L1B]; a.bias = s->bias_s[L1B];
-            if ((rc = conv1ab_wino_fused(st, a, gray_dev, stride, fisheye_mask, s->w1a_frag, s->lut_hl, /*out_split=*/!w2a))) return rc;
-        } else if (P == OMNI_PREC_SPLIT) {
-            a.split_inv = s->winv[L1B]; a.bias = s->bias_s[L1B];
-            if ((rc = conv1ab_split_fused(st, a, gray_dev, stride, fisheye_mask, s->w1a_frag, s->lut_hl))) return rc;
-        } else if ((rc = conv1ab_fused(st, a, gray_dev, stride, fisheye_mask, reinterpret_cast<const _Float16*>(s->w1a_frag), s->bias[L1A], s->lut_hl))) return rc;
-    } else if ((rc = conv(L1B, s->a1a, s->a1b, s->bias[L1B], H, W, 64, 64, 3, true, true, false))) return rc;
-    if ((rc = mark())) return rc;
-    // a Winograd layer: raw-32 input (converted into a_tmp when the layer before it wrote split-64: mixed configurations), raw-32 or split-64 output
-    auto wino_layer = [&](int l, const void* in, bool in_raw, void* out, int h, int w, bool pool, bool out_split) -> int {
-        if (!in_raw) {
-            if (!s->a_tmp) OMNI_HIP_TRY(hipMalloc(&s->a_tmp, (size_t)s->max_batch * split_frame_bytes(H / 2, W / 2, 64)));
-            if ((rc = split_to_raw32(st, in, s->a_tmp, batch, 64, h, w))) return rc;
+    switch (p.conv1a) {
+        case SP_1A_FUSED: break;           // computed inside conv1b's kernel: the conv1a activation tensor is never materialised
+        case SP_1A_SPLIT: rc = conv1a_split(st, gray_dev, stride, batch, H, W, fisheye_mask, s->w1a, s->bias[L1A], s->lut, s->a1a, p.use_skip ? s->mskip[0].ty0 : 0, p.use_skip ? s->mskip[0].ty1 : 0); break;
+        case SP_1A_DIRECT: rc = conv1a_direct(st, s->precision, gray_dev, stride, batch, H, W, fisheye_mask, s->w1a, s->bias[L1A], s->lut, s->a1a); break;
+    }
+    if (rc || (rc = mark())) return rc;
+    if (p.conv1b == SP_1B_CONV) rc = sp_conv(s, p, L1B, s->a1a, s->a1b, batch);
+    else {
+        const ConvArgs a = sp_layer_args(s, p, L1B, p.conv1b == SP_1B_FUSED_WINO ? SP_K_WINO : SP_K_DIRECT, nullptr, s->a1b, batch);
+        if (p.conv1b == SP_1B_FUSED_WINO) rc = conv1ab_wino_fused(st, a, gray_dev, stride, fisheye_mask, s->w1a_frag, s->lut_hl, /*out_split=*/!p.raw_1b);
+        else if (p.conv1b == SP_1B_FUSED_SPLIT) rc = conv1ab_split_fused(st, a, gray_dev, stride, fisheye_mask, s->w1a_frag, s->lut_hl);
+        else rc = conv1ab_fused(st, a, gray_dev, stride, fisheye_mask, reinterpret_cast<const _Float16*>(s->w1a_frag), s->bias[L1A], s->lut_hl);
+    }
+    if (rc || (rc = mark())) return rc;
+    // conv2a, conv2b, conv3a: the direct kernel, or a Winograd layer: raw-32 input (converted into a_tmp when the layer before it wrote split-64: mixed
+    // configurations), raw-32 or split-64 output
+    auto c64 = [&](int l, const SpC64Plan& c, const void* in, void* out) -> int {
+        if (!c.wino) return sp_conv(s, p, l, in, out, batch);
+        if (c.convert_in) {
+            if (!s->a_tmp && (rc = s->mem.alloc(&s->a_tmp, (size_t)s->max_batch * split_frame_bytes(H / 2, W / 2, 64)))) return rc;
+            if ((rc = split_to_raw32(st, in, s->a_tmp, batch, 64, H / kLayers[l].div, W / kLayers[l].div))) return rc;
             in = s->a_tmp;
         }
-        ConvArgs a;
-        a.in = in; a.out = out; a.w_packed = s->wpk_w[l]; a.bias = s->bias_s[l]; a.batch = batch; a.H = h; a.W = w; a.cin = 64; a.cout = kLayers[l].cout; a.ksize = 3;
-        a.relu = true; a.pool = pool; a.out_f32 = false; a.n_cu = s->ctx->prop.multiProcessorCount; a.split_inv = s->winv_w[l];
-        skip_of(l, a);
-        return conv_wino(st, a, out_split);
+        return conv_wino(st, sp_layer_args(s, p, l, SP_K_WINO, in, out, batch), /*out_split=*/!c.out_raw32);
     };
-    const bool raw_1b = w1b && w2a, raw_2a = w2a && w2b, raw_2b = w2b && w3a;
-    if (P == OMNI_PREC_SPLIT) { s->raw_1b = raw_1b; s->raw_2a = raw_2a; s->raw_2b = raw_2b; }
-    if (w2a) { if ((rc = wino_layer(L2A, s->a1b, raw_1b, s->a2a, H / 2, W / 2, false, !w2b))) return rc; }
-    else if ((rc = conv(L2A, s->a1b, s->a2a, s->bias[L2A], H / 2, W / 2, 64, 64, 3, true, false, false))) return rc;
-    if ((rc = mark())) return rc;
-    if (w2b) { if ((rc = wino_layer(L2B, s->a2a, raw_2a, s->a2b, H / 2, W / 2, true, !w3a))) return rc; }
-    else if ((rc = conv(L2B, s->a2a, s->a2b, s->bias[L2B], H / 2, W / 2, 64, 64, 3, true, true, false))) return rc;
-    if ((rc = mark())) return rc;
-    if (w3a) { if ((rc = wino_layer(L3A, s->a2b, raw_2b, s->a3a, H / 4, W / 4, false, true))) return rc; }
-    else if ((rc = conv(L3A, s->a2b, s->a3a, s->bias[L3A], H / 4, W / 4, 64, 128, 3, true, false, false))) return rc;
-    if ((rc = mark())) return rc;
-    if ((rc = conv(L3B, s->a3a, s->a3b, s->bias[L3B], H / 4, W / 4, 128, 128, 3, true, true, false))) return rc;
-    if ((rc = mark())) return rc;
-    if ((rc = conv(L4A, s->a3b, s->a4a, s->bias[L4A], H / 8, W / 8, 128, 128, 3, true, false, false))) return rc;
-    if ((rc = mark())) return rc;
-    if ((rc = conv(L4B, s->a4a, s->a4b, s->bias[L4B], H / 8, W / 8, 128, 128, 3, true, false, false))) return rc;
-    if ((rc = mark())) return rc;
-    const bool sparse = s->precision == OMNI_PREC_F16 && s->conv_variant == 0 && s->sparse_desc && run_post;
-    // fp32 / split paths: the exact-f32 convDb + norm likewise only at the cells around the key points (sp_post.hip), the dense map on demand
-    const bool sparse32 = s->precision != OMNI_PREC_F16 && s->conv_variant == 0 && s->sparse_desc && run_post && s->cx32;
-    const bool sparse_da32 = sparse32 && P == OMNI_PREC_SPLIT && s->sparse_da && s->headsP;      // convDa itself at those cells only (conv_split_c128_sparse)
-    const bool sparse_da = (sparse && s->sparse_da && s->headsP) || sparse_da32;
-    // the detector branch needs cPa everywhere; cDa (output channels 256-511 of the fused heads layer) is only read around the key points
-    const void* cpa = sparse_da ? s->headsP : s->heads;
-    const int cpa_stride = sparse_da ? 256 : 512;
-    if (sparse_da) { if ((rc = conv(LPA, s->a4b, s->headsP, s->bias_heads, H / 8, W / 8, 128, 256, 3, true, false, P == OMNI_PREC_SPLIT))) return rc; }
-    else if ((rc = conv(LPA, s->a4b, s->heads, s->bias_heads, H / 8, W / 8, 128, 512, 3, true, false, P == OMNI_PREC_SPLIT))) return rc;
-    if ((rc = mark())) return rc;
+    if ((rc = c64(L2A, p.conv2a, s->a1b, s->a2a)) || (rc = mark())) return rc;
+    if ((rc = c64(L2B, p.conv2b, s->a2a, s->a2b)) || (rc = mark())) return rc;
+    if ((rc = c64(L3A, p.conv3a, s->a2b, s->a3a)) || (rc = mark())) return rc;
+    if ((rc = sp_conv(s, p, L3B, s->a3a, s->a3b, batch)) || (rc = mark())) return rc;
+    if ((rc = sp_conv(s, p, L4A, s->a3b, s->a4a, batch)) || (rc = mark())) return rc;
+    if ((rc = sp_conv(s, p, L4B, s->a4a, s->a4b, batch)) || (rc = mark())) return rc;
+    if ((rc = sp_heads_layer(s, p, batch, p.heads_sparse_da)) || (rc = mark())) return rc;
     // the head thresholds its own output into the candidate lists when the post-processing follows (superpoint_tensorrt.cpp:167-173 inside the epilogue)
     DetCand dc;
-    const bool cand_fused = run_post && s->fused_cand && s->conv_variant != 1;
-    if (cand_fused) { dc.thres = s->thres; dc.bits = s->pb.cand_bits; }
-    if (s->conv_variant == 1) { if ((rc = detector_head(st, PH, s->heads, 512, 0, batch, s->Hc, s->Wc, s->wPbT, s->bias[LPB], s->semi))) return rc; }
-    else if ((P == OMNI_PREC_F16 || P == OMNI_PREC_SPLIT) && s->det16) {
-        // fp16: exact operands, split weights; OMNI_PREC_SPLIT: the heads layer's fp32 output split on the fly as well (three terms: fp32-class logits)
-        if ((rc = detector_head_mfma16(st, P == OMNI_PREC_F16 ? OMNI_PREC_F16 : OMNI_PREC_F32, cpa, cpa_stride, 0, batch, s->Hc, s->Wc, s->wPbA16, s->wPbDust, s->bias[LPB], s->semi,
-                                       s->ctx->prop.multiProcessorCount, dc))) return rc;
-    } else if ((rc = detector_head_mfma(st, PH, cpa, cpa_stride, 0, batch, s->Hc, s->Wc, s->wPbA, s->wPbDust, s->bias[LPB], s->semi,
-                                        s->ctx->prop.multiProcessorCount, dc))) return rc;
-    if ((rc = mark())) return rc;
+    if (p.cand_fused) { dc.thres = s->thres; dc.bits = s->pb.cand_bits; }
+    const void* cpa = p.heads_sparse_da ? s->headsP : s->heads;
+    const int cpa_stride = p.heads_sparse_da ? 256 : 512, PH = tails_prec(p);
+    switch (p.det) {
+        case SP_DET_VALU: rc = detector_head(st, PH, cpa, cpa_stride, 0, batch, s->Hc, s->Wc, s->wPbT, s->bias[LPB], s->semi); break;
+        // fp16: exact operands, split weights; split precision: the heads layer's fp32 output split on the fly as well (three terms: fp32-class logits)
+        case SP_DET_MFMA16_F16: case SP_DET_MFMA16_F32:
+            rc = detector_head_mfma16(st, PH, cpa, cpa_stride, 0, batch, s->Hc, s->Wc, s->wPbA16, s->wPbDust, s->bias[LPB], s->semi, n_cu, dc); break;
+        case SP_DET_MFMA_F32: rc = detector_head_mfma(st, PH, cpa, cpa_stride, 0, batch, s->Hc, s->Wc, s->wPbA, s->wPbDust, s->bias[LPB], s->semi, n_cu, dc); break;
+    }
+    if (rc || (rc = mark())) return rc;
     OMNI_HIP_TRY(hipEventRecord(s->ev_convs, st));        // the convolution stack and the detector head are enqueued: what follows are small grids
-    s->dense_valid = !sparse && !sparse32; s->dense_possible = true; s->last_batch = batch;
-    s->heads_full = !sparse_da32;
-    if (sparse || sparse32) {
-        // nothing here: convDb runs inside the post-processing, at the key points only
-    } else if (s->precision == OMNI_PREC_F16 && s->conv_variant == 0) {
-        // convDb + descriptor L2 norm in one HBM pass (channels [256,512) = cDa of the fused heads buffer, pixel stride 512)
-        if ((rc = convdb_l2norm(st, s->ctx, (const char*)s->heads + (size_t)256 * s->esz, 512, s->wDbFrag, s->bias[LDB], s->draw,
-                                (int64_t)batch * s->Hc * s->Wc))) return rc;
-    } else {
-        // convDb reads channels [256,512) (cDa) of the fused heads buffer: input pointer offset by 256 channels,
-        // pixel stride 512
-        ConvArgs a;
-        a.in = (const char*)s->heads + (size_t)256 * s->esz; a.out = s->draw; a.w_packed = s->wpk[LDB]; a.bias = s->bias[LDB];
-        a.batch = batch; a.H = s->Hc; a.W = s->Wc; a.cin = 256; a.cout = 256; a.ksize = 1; a.relu = false; a.pool = false;
-        a.out_f32 = true; a.in_cstride = 512;
-        if ((rc = conv_mfma(st, PH, a))) return rc;
-        if ((rc = l2norm_channels(st, s->draw, (int64_t)batch * s->Hc * s->Wc))) return rc;
-    }
-    if ((rc = mark())) return rc;
-    if (run_post) {
-        SpSparseDesc sd;
-        if (sparse) { sd.ctx = s->ctx; sd.in_f16 = (const char*)s->heads + (size_t)256 * s->esz; sd.in_cstride = 512; sd.wfrag = s->wDbFrag; sd.bias = s->bias[LDB]; }
-        if (sparse_da32) { sd.ctx = s->ctx; sd.a4b_split = s->a4b; sd.da_w = s->wpk[LPA]; sd.da_bias = s->bias_heads; sd.da_g32_first = 8; sd.da_inv = s->winv[LPA];
-                           sd.wdb_hi = s->wDbFragHi; sd.wdb_lo = s->wDbFragLo; }
-        else if (sparse_da) { sd.a4b = s->a4b; sd.da_w = s->wpk[LPA]; sd.da_bias = s->bias_heads; sd.da_g32_first = 8; sd.da_compact = s->da_compact; }
-        if (sparse32) {
-            sd.cda_f32 = reinterpret_cast<const float*>(s->heads) + 256; sd.in_cstride = 512; sd.wdb_f32 = s->wpk[LDB]; sd.bias = s->bias[LDB];
-            sd.cx = s->cx32; sd.cy = s->cy32; sd.n_cu = s->ctx->prop.multiProcessorCount; sd.zero_page = s->ctx->zero_page;
-        }
-        sd.cand_fused = cand_fused;
-        if ((rc = sp_postprocess(st, post_params(s), s->pb, s->semi, s->draw, batch, sd))) return rc;
-    }
-    if ((rc = mark())) return rc;
-    return OMNI_OK;
+    if (p.desc == SP_DESC_DENSE_F16) rc = sp_desc_dense_f16(s, batch);
+    else if (p.desc == SP_DESC_DENSE_GENERIC) rc = sp_desc_dense_generic(s, p, batch);
+    // (every other tail: convDb runs inside the post-processing, at the key points only)
+    if (rc || (rc = mark())) return rc;
+    if (p.run_post && (rc = sp_postprocess(st, post_params(s), s->pb, s->semi, s->draw, batch, sp_sparse_desc(s, p)))) return rc;
+    return mark();
 }
 
 // the dense head activations and descriptor map of the LAST forward pass, when it sampled its descriptors sparsely: the fused heads layer over
-// every cell (conv4b's output is still in HBM) + convDb + L2 norm
+// every cell (conv4b's output is still in HBM) + convDb + L2 norm.  fp16 runs the fused layer whatever the pass left in `heads`; fp32 / split only
+// where the pass ran cPa alone
 static int sp_make_dense(omni_sp* s) {
-    hipStream_t st = s->ctx->stream;
+    SpPassPlan& p = s->last;
     int rc;
-    if (s->precision != OMNI_PREC_F16) {       // the heads layer's fp32 output is still in HBM: dense convDb + norm from it
-        if (!s->heads_full) {                  // (OMNI_PREC_SPLIT with convDa at the key points only: the fused layer over every cell first)
-            ConvArgs h;
-            h.in = s->a4b; h.out = s->heads; h.w_packed = s->wpk[LPA]; h.bias = s->bias_heads; h.batch = s->last_batch; h.H = s->Hc; h.W = s->Wc; h.cin = 128;
-            h.cout = 512; h.ksize = 3; h.relu = true; h.pool = false; h.out_f32 = true; h.split_inv = s->winv[LPA];
-            h.n_cu = s->ctx->prop.multiProcessorCount; h.zero_page = s->ctx->zero_page; h.variant = s->conv_variant;
-            if ((rc = conv_split(st, h))) return rc;
-            s->heads_full = true;
-        }
-        ConvArgs a;
-        a.in = (const char*)s->heads + (size_t)256 * 4; a.out = s->draw; a.w_packed = s->wpk[LDB]; a.bias = s->bias[LDB];
-        a.batch = s->last_batch; a.H = s->Hc; a.W = s->Wc; a.cin = 256; a.cout = 256; a.ksize = 1; a.relu = false; a.pool = false;
-        a.out_f32 = true; a.in_cstride = 512;
-        if ((rc = conv_mfma(st, OMNI_PREC_F32, a))) return rc;
-        if ((rc = l2norm_channels(st, s->draw, (int64_t)s->last_batch * s->Hc * s->Wc))) return rc;
-        s->dense_valid = true;
-        return OMNI_OK;
+    if (!p.tails_f32 || !p.heads_full) {
+        if ((rc = sp_heads_layer(s, p, s->last_batch, false))) return rc;
+        p.heads_full = true;
     }
-    ConvArgs a;
-    a.in = s->a4b; a.out = s->heads; a.w_packed = s->wpk[LPA]; a.bias = s->bias_heads; a.batch = s->last_batch; a.H = s->Hc; a.W = s->Wc; a.cin = 128;
-    a.cout = 512; a.ksize = 3; a.relu = true; a.pool = false; a.out_f32 = false;
-    a.n_cu = s->ctx->prop.multiProcessorCount; a.zero_page = s->ctx->zero_page; a.variant = s->conv_variant;
-    if ((rc = conv_mfma(st, s->precision, a))) return rc;
-    if ((rc = convdb_l2norm(st, s->ctx, (const char*)s->heads + (size_t)256 * s->esz, 512, s->wDbFrag, s->bias[LDB], s->draw,
-                            (int64_t)s->last_batch * s->Hc * s->Wc))) return rc;
-    s->dense_valid = true;
+    if ((rc = p.tails_f32 ? sp_desc_dense_generic(s, p, s->last_batch) : sp_desc_dense_f16(s, s->last_batch))) return rc;
+    p.dense_valid = true;
     return OMNI_OK;
 }
 
@@ -643,10 +600,10 @@ omni_sp* omni_sp_create(omni_ctx* ctx, const omni_sp_weights* w, const float* pc
     s->max_batch = max_batch; s->precision = precision; s->esz = precision == OMNI_PREC_F16 ? 2 : 4;
     s->pca_dim = pca_comp ? pca_dim : 0; s->desc_dim = pca_comp ? pca_dim : 256;
     if (omni::config_resolve(&s->cfg) != OMNI_OK) { delete s; return nullptr; }
-    s->conv_variant = s->cfg[omni::CFG_CONV_V1];
+    omni::sp_set_facts(s);
 #ifndef OMNI_TEST_VARIANTS
-    if (s->conv_variant != 0) {
-        omni::set_error("OMNI_CONV_V1=%d: the reference variants of the fp16 convolutions are only built into the test library (omni-swarm_amd/lib_test/, make -C omni-swarm_amd test-variants)", s->conv_variant);
+    if (s->facts.conv_variant != 0) {
+        omni::set_error("OMNI_CONV_V1=%d: the reference variants of the fp16 convolutions are only built into the test library (omni-swarm_amd/lib_test/, make -C omni-swarm_amd test-variants)", s->facts.conv_variant);
         delete s;
         return nullptr;
     }
@@ -659,14 +616,7 @@ void omni_sp_destroy(omni_sp* s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    if (s->a_tmp) (void)hipFree(s->a_tmp);
-    for (int l = 0; l < OMNI_SP_NUM_LAYERS; ++l) { if (s->wpk_w[l]) (void)hipFree(s->wpk_w[l]); if (s->wpk[l]) (void)hipFree(s->wpk[l]); if (s->bias[l]) (void)hipFree(s->bias[l]); if (s->bias_s[l]) (void)hipFree(s->bias_s[l]); }
-    void* ptrs[] = {s->wPbA16, s->wDbFragHi, s->wDbFragLo, s->w1a, s->w1a_frag, s->lut_hl, s->wPbT, s->wPbA, s->wPbDust, s->wDbFrag, s->bias_heads, s->lut, s->pca_compT, s->pca_mean, s->a1a, s->a1b, s->a2a, s->a2b, s->a3a, s->a3b,
-                    s->a4a, s->a4b, s->heads, s->headsP, s->da_compact, s->cx32, s->cy32, s->draw, s->semi, s->gray_stage, s->pb.cand, s->pb.cand_bits, s->pb.cand_masks, s->pb.counters, s->pb.surv_keys,
-                    s->pb.raw_desc, s->pb.norm_partial, s->pb.kps_xy, s->pb.scores, s->pb.n_kps, s->pb.desc_out};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (s->zero_gray) (void)hipFree(s->zero_gray);
-    for (auto& k : s->mskip) if (k.vec) (void)hipFree(k.vec);
+    s->mem.release_all();
     s->hstage.release(); s->dense_tmp.release();
     for (auto& e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->ev_convs) (void)hipEventDestroy(s->ev_convs);
@@ -734,9 +684,9 @@ int omni_sp_get_dense(omni_sp* s, int batch, float* semi_host, float* desc_host)
     int rc;
     if (semi_host) OMNI_HIP_TRY(hipMemcpyAsync(semi_host, s->semi, (size_t)batch * s->H * s->W * 4, hipMemcpyDeviceToHost, st));
     if (desc_host) {
-        if (!s->dense_valid) {
+        if (!s->last.dense_valid) {
             // the last forward pass sampled its descriptors without the dense map: produce it now from the head activations still in HBM
-            OMNI_REQUIRE(s->dense_possible && batch <= s->last_batch, OMNI_ERR_INVALID, "no forward pass of >= %d images to take the dense descriptors from", batch);
+            OMNI_REQUIRE(batch <= s->last_batch, OMNI_ERR_INVALID, "no forward pass of >= %d images to take the dense descriptors from", batch);
             if ((rc = omni::sp_make_dense(s))) return rc;
         }
         const size_t n = (size_t)batch * 256 * s->Hc * s->Wc;
@@ -761,9 +711,9 @@ int omni_sp_postprocess_dense(omni_sp* s, const float* semi_host, const float* d
     OMNI_HIP_TRY(hipMemcpyAsync(s->semi, semi_host, (size_t)batch * s->H * s->W * 4, hipMemcpyHostToDevice, st));
     OMNI_HIP_TRY(hipMemcpyAsync(s->dense_tmp.p, desc_host, n * 4, hipMemcpyHostToDevice, st));
     if ((rc = omni::nchw_to_nhwc(st, s->dense_tmp.as<float>(), s->draw, batch, 256, s->Hc * s->Wc))) return rc;
-    s->dense_valid = true; s->dense_possible = false; s->last_batch = batch;          // `draw` / `semi` now hold the caller's maps
+    s->last.dense_valid = true; s->last_batch = batch;          // `draw` / `semi` now hold the caller's maps
     omni::SpSparseDesc sd;
-    sd.cand_from_list = s->fused_cand;       // threshold + window masks as the pipeline makes them (OMNI_SP_FUSED_CAND=0: sp_cand_kernel)
+    sd.cand_from_list = s->facts.fused_cand;       // threshold + window masks as the pipeline makes them (OMNI_SP_FUSED_CAND=0: sp_cand_kernel)
     if ((rc = omni::sp_postprocess(st, omni::post_params(s), s->pb, s->semi, s->draw, batch, sd))) return rc;
     return omni::sp_fetch_locked(s, batch, kps_xy, n_kps, desc, scores);
 }
@@ -779,9 +729,9 @@ int omni_sp_debug_layer(omni_sp* s, const char* name, int batch, float* out_nchw
                        {"desc", s->draw, 256, 8, OMNI_PREC_F32}};
     for (const Ent& e : tab) {
         if (strcmp(e.n, name) != 0) continue;
-        if (e.p == s->a1a && s->fuse1a) { omni::set_error("conv1a is fused into conv1b on this path and not materialised (OMNI_CONV_V1=3 keeps it)"); return OMNI_ERR_INVALID; }
-        if ((e.p == s->heads || e.p == s->draw) && !s->dense_valid) {
-            OMNI_REQUIRE(s->dense_possible && batch <= s->last_batch, OMNI_ERR_INVALID, "no forward pass of >= %d images to take layer %s from", batch, name);
+        if (e.p == s->a1a && s->last.conv1a == omni::SP_1A_FUSED) { omni::set_error("conv1a is fused into conv1b on this path and not materialised (OMNI_CONV_V1=3 keeps it)"); return OMNI_ERR_INVALID; }
+        if ((e.p == s->heads || e.p == s->draw) && !s->last.dense_valid) {
+            OMNI_REQUIRE(batch <= s->last_batch, OMNI_ERR_INVALID, "no forward pass of >= %d images to take layer %s from", batch, name);
             std::lock_guard<std::mutex> lk(s->mu);
             (void)hipSetDevice(s->ctx->device);
             int rc = omni::sp_make_dense(s);
@@ -797,7 +747,7 @@ int omni_sp_debug_layer(omni_sp* s, const char* name, int batch, float* out_nchw
         const size_t n = (size_t)batch * e.c * h * w;
         int rc;
         if ((rc = s->dense_tmp.ensure(n * 4))) return rc;
-        if (e.prec == OMNI_PREC_SPLIT && ((e.p == s->a1b && s->raw_1b) || (e.p == s->a2a && s->raw_2a) || (e.p == s->a2b && s->raw_2b))) {      // a raw-32 frame between two Winograd layers
+        if (e.prec == OMNI_PREC_SPLIT && ((e.p == s->a1b && s->last.raw_1b) || (e.p == s->a2a && s->last.conv2a.out_raw32) || (e.p == s->a2b && s->last.conv2b.out_raw32))) {      // a raw-32 frame between two Winograd layers
             if ((rc = omni::raw32_to_nchw_f32(s->ctx->stream, e.p, s->dense_tmp.as<float>(), batch, e.c, h, w))) return rc;
         } else if (e.prec == OMNI_PREC_SPLIT) { if ((rc = omni::split_to_nchw_f32(s->ctx->stream, e.p, s->dense_tmp.as<float>(), batch, e.c, h, w))) return rc; }
         else if ((rc = omni::nhwc_any_to_nchw_f32(s->ctx->stream, e.prec, e.p, s->dense_tmp.as<float>(), batch, e.c, h * w))) return rc;
@@ -842,7 +792,7 @@ int omni_sp_mask_skip_plan(int width, int height, int precision, int layer, int*
 }
 
 double omni_sp_stage_tiles_left_out(const omni_sp* s, int stage) {
-    if (!s || !s->mask_skip) return 0.0;
+    if (!s || !s->facts.mask_skip) return 0.0;
     const int i = stage == ST_CONV1A ? 0 : stage == ST_CONV1B ? 1 : stage == ST_CONV2A ? 2 : stage == ST_CONV2B ? 3 : stage == ST_CONV3A ? 4 : stage == ST_CONV3B ? 5 : -1;
     return i < 0 ? 0.0 : s->mskip[i].frac;
 }
