@@ -378,6 +378,22 @@ int       omni_cam_enqueue_host(omni_cam* cam, const uint8_t* gray_host, int str
  * cameras' likewise (n_down = 0 for a mono handle); the totals must be the unit's active size (omni_cam_set_active).  One asynchronous copy per part. */
 int       omni_cam_enqueue_host_parts(omni_cam* cam, const uint8_t* const* up, const int* up_images, int n_up, const uint8_t* const* down, const int* down_images,
                                       int n_down, int width, int height, int fisheye_mask);
+/* A unit of RAW fisheye frames: the flattening (FisheyeUndist::undist_all_cuda in front of LoopCam::on_flattened_images) runs inside the unit.  n_keyframes frames
+ * of the up camera and as many of the down camera (u8, src_stride; frame i at + i * src_stride * source height), `up` / `down` = the two cameras' maps.  Views
+ * [first_view, n_views) of every frame become the unit's directions (first_view = 1 for the reference's rig: LoopCam never reads the top view 0, loop_cam.h:64-73),
+ * in the order of omni_cam_enqueue_dev: [up: frame 0's views, frame 1's, ... | down: the same].  n_keyframes * (n_views - first_view) must be the unit's active size
+ * (omni_cam_set_active) and every such view of both objects of the networks' size; stereo handles only.  fisheye_mask != 0: the rows omni_fisheye_mask_rows names
+ * are written as zeros without being computed (both networks blank them anyway).  Bytes = omni_flatten_enqueue_dev's.  Asynchronous, no host synchronisation; the
+ * remap runs on the unit's SuperPoint stream, so keep `up` and `down` alive until omni_cam_wait.
+ * _host: the frames in (pinned) host memory, untouched until omni_cam_wait returns: one asynchronous upload per camera into a staging buffer owned by the handle. */
+int       omni_cam_enqueue_fisheye_dev(omni_cam* cam, omni_flatten* up, omni_flatten* down, const uint8_t* up_dev, const uint8_t* down_dev, int src_stride,
+                                       int n_keyframes, int first_view, int fisheye_mask);
+int       omni_cam_enqueue_fisheye_host(omni_cam* cam, omni_flatten* up, omni_flatten* down, const uint8_t* up_host, const uint8_t* down_host, int src_stride,
+                                        int n_keyframes, int first_view, int fisheye_mask);
+/* The first `bytes` of the handle's own input block -- the images the last omni_cam_enqueue_host / _host_parts / _fisheye_* unit fed to the networks, [image][H][W],
+ * before the networks' own masking -- copied to out_host (blocking; for tests and for `show`-style debugging, loop_cam.cpp:471-515).  OMNI_ERR_INVALID while a unit
+ * is pending, or when the last unit read a caller's buffer through omni_cam_enqueue_dev. */
+int       omni_cam_get_input(omni_cam* cam, uint8_t* out_host, int64_t bytes);
 int       omni_cam_wait(omni_cam* cam, omni_cam_result* out);
 /* A unit smaller than the handle was created for (a partly filled micro-batch of key frames that must not wait any longer): the next enqueues read
  * cams * n_dirs images -- the up cameras' first, the down cameras' right behind them -- and every array of omni_cam_result has that leading dimension.

@@ -35,7 +35,7 @@ SYMBOLS = [
     "omni_index_destroy", "omni_index_add", "omni_index_add_dev", "omni_index_ntotal", "omni_index_dim", "omni_index_reset", "omni_index_truncate", "omni_index_cert_stats",
     "omni_index_search", "omni_index_search_dev", "omni_index_search_prefix_dev", "omni_index_search_batch_prefix_dev", "omni_index_set_shard", "omni_topk_merge", "omni_index_last_scan_ms",
     "omni_index_save", "omni_index_load",
-    "omni_trace_push", "omni_trace_pop", "omni_sp_set_perf", "omni_sp_last_stage_ms", "omni_bf_match", "omni_bf_match_multi", "omni_bf_match_batched_dev", "omni_config_count", "omni_config_describe", "omni_config_value", "omni_config_is_process_wide", "omni_cam_create", "omni_cam_create_mono", "omni_cam_destroy", "omni_cam_enqueue_dev", "omni_cam_enqueue_host", "omni_cam_enqueue_host_parts", "omni_cam_wait", "omni_cam_order_after", "omni_cam_set_active", "omni_cam_ready",
+    "omni_trace_push", "omni_trace_pop", "omni_sp_set_perf", "omni_sp_last_stage_ms", "omni_bf_match", "omni_bf_match_multi", "omni_bf_match_batched_dev", "omni_config_count", "omni_config_describe", "omni_config_value", "omni_config_is_process_wide", "omni_cam_create", "omni_cam_create_mono", "omni_cam_destroy", "omni_cam_enqueue_dev", "omni_cam_enqueue_host", "omni_cam_enqueue_host_parts", "omni_cam_enqueue_fisheye_dev", "omni_cam_enqueue_fisheye_host", "omni_cam_get_input", "omni_cam_wait", "omni_cam_order_after", "omni_cam_set_active", "omni_cam_ready",
     "omni_shard_unique_id", "omni_shard_library_path", "omni_shard_create", "omni_shard_destroy", "omni_shard_ntotal", "omni_shard_preload_local", "omni_shard_step_batch_dev", "omni_shard_step_enqueue", "omni_shard_rows_consumed", "omni_shard_step_wait", "omni_shard_last_exchange_us",
     "omni_shard_search", "omni_flatten_create", "omni_flatten_destroy", "omni_flatten_out_bytes", "omni_flatten_enqueue_dev",
 ]
@@ -168,6 +168,9 @@ def lib():
     sig("omni_trace_pop", None, [])
     sig("omni_cam_enqueue_host", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int])
     sig("omni_cam_enqueue_host_parts", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int])
+    sig("omni_cam_enqueue_fisheye_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int])
+    sig("omni_cam_enqueue_fisheye_host", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int])
+    sig("omni_cam_get_input", C.c_int, [_vp, _vp, C.c_int64])
     sig("omni_cam_wait", C.c_int, [_vp, C.POINTER(_CamResult)])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
@@ -843,6 +846,24 @@ class Cam:
         assert gray_host.dtype == np.uint8 and gray_host.ndim == 3 and gray_host.shape[0] == self.cams * self.n_active and gray_host.flags.c_contiguous
         _check(lib().omni_cam_enqueue_host(self.h, gray_host.ctypes.data_as(_vp), gray_host.shape[2], gray_host.shape[2], gray_host.shape[1],
                                            int(fisheye_mask)))
+
+    def enqueue_fisheye_dev(self, up: "Flatten", down: "Flatten", up_dev: int, down_dev: int, src_stride: int, n_keyframes: int, first_view: int = 1,
+                            fisheye_mask: bool = True):
+        """raw fisheye frames in HBM, n_keyframes per camera: flattened inside the unit into views first_view.. of `up` / `down` (omni_cam_enqueue_fisheye_dev)"""
+        _check(lib().omni_cam_enqueue_fisheye_dev(self.h, up.h, down.h, up_dev, down_dev, src_stride, n_keyframes, first_view, int(fisheye_mask)))
+
+    def enqueue_fisheye_host(self, up: "Flatten", down: "Flatten", up_host: np.ndarray, down_host: np.ndarray, first_view: int = 1, fisheye_mask: bool = True):
+        """up_host / down_host [n_keyframes][src_h][src_w] u8, ideally pinned (Context.host_alloc); must stay untouched until wait() returns."""
+        for a in (up_host, down_host):
+            assert a.dtype == np.uint8 and a.ndim == 3 and a.flags.c_contiguous and a.shape[0] == up_host.shape[0]
+        _check(lib().omni_cam_enqueue_fisheye_host(self.h, up.h, down.h, up_host.ctypes.data_as(_vp), down_host.ctypes.data_as(_vp), up_host.shape[2],
+                                                   up_host.shape[0], first_view, int(fisheye_mask)))
+
+    def get_input(self) -> np.ndarray:
+        """[cams * n_active][H][W] u8: the handle's own input block as the last enqueue_host / enqueue_fisheye_* unit left it (not after enqueue_dev)"""
+        out = np.empty((self.cams * self.n_active, self.sp.H, self.sp.W), np.uint8)
+        _check(lib().omni_cam_get_input(self.h, out.ctypes.data_as(_vp), out.nbytes))
+        return out
 
     def set_active(self, n_dirs: int):
         """a unit of fewer directions than the handle was created for: the next enqueues read cams * n_dirs images (up cameras first, down right behind)"""

@@ -26,6 +26,9 @@ struct omni_cam {
     hipEvent_t e1 = nullptr, e2 = nullptr, e_up = nullptr;
     uint8_t* d_gray = nullptr;        // staging for omni_cam_enqueue_host: the key frame's images, rows packed to `width`
     size_t d_gray_bytes = 0;
+    size_t input_bytes = 0;           // what the last unit read from d_gray (0: it read a caller's buffer): omni_cam_get_input
+    uint8_t* d_raw = nullptr;         // staging for omni_cam_enqueue_fisheye_host: the raw frames of the up cameras, then of the down cameras
+    size_t d_raw_bytes = 0;
     bool pending = false;
     std::mutex mu;
 };
@@ -86,7 +89,7 @@ void omni_cam_destroy(omni_cam* c) {
     (void)hipSetDevice(c->c1->device);
     (void)hipStreamSynchronize(c->c1->stream);
     (void)hipStreamSynchronize(c->c2->stream);
-    void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray};
+    void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->host) (void)hipHostFree(c->host);
     if (c->e1) (void)hipEventDestroy(c->e1);
@@ -96,6 +99,18 @@ void omni_cam_destroy(omni_cam* c) {
 }
 
 static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, int fisheye_mask);
+
+// a staging buffer of the handle (d_gray, d_raw) that holds `need` bytes: grown behind whatever the unit's two streams still read from the old one
+static int cam_staging(omni_cam* c, uint8_t*& buf, size_t& have, size_t need) {
+    if (have >= need) return OMNI_OK;
+    (void)hipStreamSynchronize(c->c1->stream);
+    (void)hipStreamSynchronize(c->c2->stream);
+    if (buf) (void)hipFree(buf);
+    buf = nullptr; have = 0;
+    OMNI_HIP_TRY(hipMalloc((void**)&buf, need));
+    have = need;
+    return OMNI_OK;
+}
 
 int omni_cam_enqueue_dev(omni_cam* c, const uint8_t* gray_dev, int stride, int fisheye_mask) {
     omni::TraceRange trace_range("omni_cam_enqueue_dev");
@@ -113,15 +128,8 @@ int omni_cam_enqueue_host(omni_cam* c, const uint8_t* gray_host, int stride, int
     OMNI_REQUIRE(width == c->W && height == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_host: images are %dx%d but the networks were created for %dx%d", width, height, c->W, c->H);
     std::lock_guard<std::mutex> lk(c->mu);
     (void)hipSetDevice(c->c1->device);
-    const size_t need = (size_t)c->cams * c->n * width * height;
-    if (c->d_gray_bytes < need) {
-        (void)hipStreamSynchronize(c->c1->stream);
-        (void)hipStreamSynchronize(c->c2->stream);
-        if (c->d_gray) (void)hipFree(c->d_gray);
-        c->d_gray = nullptr; c->d_gray_bytes = 0;
-        OMNI_HIP_TRY(hipMalloc((void**)&c->d_gray, need));
-        c->d_gray_bytes = need;
-    }
+    int rc;
+    if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, (size_t)c->cams * c->n * width * height))) return rc;
     // the reference uploads one image per engine call and blocks (tensorrt_generic.cpp:58-75); here the key frame's 2n images go up as one
     // asynchronous copy on the SuperPoint stream (pinned source: the copy engine runs it next to the other pipelines' kernels) and the
     // MobileNetVLAD stream waits for it on the device
@@ -152,18 +160,12 @@ int omni_cam_enqueue_host_parts(omni_cam* c, const uint8_t* const* up, const int
     int nu = 0, nd = 0;
     for (int i = 0; i < n_up; ++i) { OMNI_REQUIRE(up[i] && up_images[i] > 0, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: empty part"); nu += up_images[i]; }
     for (int i = 0; i < n_down; ++i) { OMNI_REQUIRE(down[i] && down_images[i] > 0, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: empty part"); nd += down_images[i]; }
+    std::lock_guard<std::mutex> lk(c->mu);                 // (before c->n is read: omni_cam_set_active writes it under this lock)
     OMNI_REQUIRE(nu == c->n && nd == (c->cams - 1) * c->n, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: %d + %d images for a unit of %d x %d", nu, nd, c->cams, c->n);
-    std::lock_guard<std::mutex> lk(c->mu);
     (void)hipSetDevice(c->c1->device);
-    const size_t img = (size_t)width * height, need = (size_t)c->cams * c->n * img;
-    if (c->d_gray_bytes < need) {
-        (void)hipStreamSynchronize(c->c1->stream);
-        (void)hipStreamSynchronize(c->c2->stream);
-        if (c->d_gray) (void)hipFree(c->d_gray);
-        c->d_gray = nullptr; c->d_gray_bytes = 0;
-        OMNI_HIP_TRY(hipMalloc((void**)&c->d_gray, need));
-        c->d_gray_bytes = need;
-    }
+    const size_t img = (size_t)width * height;
+    int rc;
+    if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, (size_t)c->cams * c->n * img))) return rc;
     size_t at = 0;
     for (int i = 0; i < n_up; ++i) { OMNI_HIP_TRY(hipMemcpyAsync(c->d_gray + at, up[i], up_images[i] * img, hipMemcpyHostToDevice, c->c1->stream)); at += up_images[i] * img; }
     OMNI_HIP_TRY(hipEventRecord(c->e_up, c->c1->stream));
@@ -172,9 +174,86 @@ int omni_cam_enqueue_host_parts(omni_cam* c, const uint8_t* const* up, const int
     return cam_enqueue_locked(c, c->d_gray, width, fisheye_mask);
 }
 
+// A key frame's two RAW fisheye frames instead of its flattened views: the remap (flatten.hip) runs inside the unit, on the SuperPoint stream, and writes the
+// unit's own input block.  n_keyframes up frames and as many down frames (u8, src_stride, frame i at + i * src_stride * source height); `up` / `down` hold the
+// two cameras' maps, of which views [first_view, n_views) are the unit's directions: n_keyframes * (n_views - first_view) = the unit's active size, each view of
+// the networks' size.  The maps are read on the unit's streams, never on the flatten objects' own: keep both objects alive until omni_cam_wait.
+static int cam_fisheye_check(omni_cam* c, const omni_flatten* up, const omni_flatten* down, int src_stride, int n_keyframes, int first_view, int* dirs) {
+    OMNI_REQUIRE(c->cams == 2, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye: a mono handle has no up / down camera pair");
+    OMNI_REQUIRE(n_keyframes >= 1 && first_view >= 0 && first_view < up->n_views && up->n_views == down->n_views, OMNI_ERR_INVALID,
+                 "omni_cam_enqueue_fisheye: %d key frames, first view %d of %d (up) / %d (down)", n_keyframes, first_view, up->n_views, down->n_views);
+    *dirs = up->n_views - first_view;
+    OMNI_REQUIRE((int64_t)n_keyframes * *dirs == c->n, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye: %d key frames x %d directions for a unit of %d (omni_cam_set_active)",
+                 n_keyframes, *dirs, c->n);
+    for (const omni_flatten* f : {up, down}) {
+        OMNI_REQUIRE(f->ctx->device == c->c1->device, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye: maps on device %d, the unit on device %d", f->ctx->device, c->c1->device);
+        OMNI_REQUIRE(src_stride >= f->src_w, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye: stride %d for frames %d wide", src_stride, f->src_w);
+        for (int v = first_view; v < f->n_views; ++v)
+            OMNI_REQUIRE(f->vw[v] == c->W && f->vh[v] == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye: view %d is %dx%d but the networks were created for %dx%d", v,
+                         f->vw[v], f->vh[v], c->W, c->H);
+    }
+    return OMNI_OK;
+}
+
+// up camera first and MobileNetVLAD behind it, then the down camera: the overlap omni_cam_enqueue_host arranges for its two uploads.  *_host != nullptr: the raw
+// frames go up first, one asynchronous copy per camera in front of its remap
+static int cam_fisheye_locked(omni_cam* c, omni_flatten* up, omni_flatten* down, const uint8_t* up_dev, const uint8_t* down_dev, const uint8_t* up_host,
+                              const uint8_t* down_host, int src_stride, int n_keyframes, int first_view, int fisheye_mask) {
+    int rc, dirs = 0;
+    if ((rc = cam_fisheye_check(c, up, down, src_stride, n_keyframes, first_view, &dirs))) return rc;
+    (void)hipSetDevice(c->c1->device);
+    const size_t half = (size_t)c->n * c->W * c->H;
+    if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, 2 * half))) return rc;
+    auto raw_bytes = [&](const omni_flatten* f) { return ((size_t)n_keyframes * f->src_h - 1) * src_stride + f->src_w; };      // (the last row may end at its width)
+    const size_t down_at = (raw_bytes(up) + 255) & ~(size_t)255;
+    if (up_host) {
+        if ((rc = cam_staging(c, c->d_raw, c->d_raw_bytes, down_at + raw_bytes(down)))) return rc;
+        up_dev = c->d_raw; down_dev = c->d_raw + down_at;
+    }
+    hipStream_t s1 = c->c1->stream;
+    if (up_host) OMNI_HIP_TRY(hipMemcpyAsync(c->d_raw, up_host, raw_bytes(up), hipMemcpyHostToDevice, s1));
+    if ((rc = omni::flatten_unit_launch(up, s1, up_dev, src_stride, n_keyframes, first_view, dirs, c->W, c->H, fisheye_mask, c->d_gray))) return rc;
+    OMNI_HIP_TRY(hipEventRecord(c->e_up, s1));
+    OMNI_HIP_TRY(hipStreamWaitEvent(c->c2->stream, c->e_up, 0));
+    if (down_host) OMNI_HIP_TRY(hipMemcpyAsync(c->d_raw + down_at, down_host, raw_bytes(down), hipMemcpyHostToDevice, s1));
+    if ((rc = omni::flatten_unit_launch(down, s1, down_dev, src_stride, n_keyframes, first_view, dirs, c->W, c->H, fisheye_mask, c->d_gray + half))) return rc;
+    return cam_enqueue_locked(c, c->d_gray, c->W, fisheye_mask);
+}
+
+int omni_cam_enqueue_fisheye_dev(omni_cam* c, omni_flatten* up, omni_flatten* down, const uint8_t* up_dev, const uint8_t* down_dev, int src_stride, int n_keyframes,
+                                 int first_view, int fisheye_mask) {
+    OMNI_REQUIRE(c && up && down && up_dev && down_dev, OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("omni_cam_enqueue_fisheye_dev (flatten + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return cam_fisheye_locked(c, up, down, up_dev, down_dev, nullptr, nullptr, src_stride, n_keyframes, first_view, fisheye_mask);
+}
+
+int omni_cam_enqueue_fisheye_host(omni_cam* c, omni_flatten* up, omni_flatten* down, const uint8_t* up_host, const uint8_t* down_host, int src_stride, int n_keyframes,
+                                  int first_view, int fisheye_mask) {
+    OMNI_REQUIRE(c && up && down && up_host && down_host, OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("omni_cam_enqueue_fisheye_host (upload + flatten + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return cam_fisheye_locked(c, up, down, nullptr, nullptr, up_host, down_host, src_stride, n_keyframes, first_view, fisheye_mask);
+}
+
+// the handle's own input block as the last unit's networks read it (the fisheye mask is applied inside the networks, not here: a unit of flattened views shows
+// them as uploaded, a unit of raw frames as flatten_unit_kernel wrote them)
+int omni_cam_get_input(omni_cam* c, uint8_t* out_host, int64_t bytes) {
+    OMNI_REQUIRE(c && out_host && bytes > 0, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_get_input with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->input_bytes > 0, OMNI_ERR_INVALID, "omni_cam_get_input: the last unit read the caller's buffer, not the handle's");
+    OMNI_REQUIRE((size_t)bytes <= c->input_bytes, OMNI_ERR_INVALID, "omni_cam_get_input: %lld bytes of an input block of %zu", (long long)bytes, c->input_bytes);
+    (void)hipSetDevice(c->c1->device);
+    OMNI_HIP_TRY(hipMemcpyAsync(out_host, c->d_gray, (size_t)bytes, hipMemcpyDeviceToHost, c->c1->stream));
+    OMNI_HIP_TRY(hipStreamSynchronize(c->c1->stream));
+    return OMNI_OK;
+}
+
 static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, int fisheye_mask) {
     const int n = c->n, M = c->M, D = c->D, ni = c->cams * c->n;
     int rc;
+    c->input_bytes = gray_dev == c->d_gray ? (size_t)ni * c->W * c->H : 0;
     // images 0..n-1 = "up" (main) camera of each direction, n..2n-1 = "down" camera (loop_cam.cpp:350-351)
     if ((rc = omni_sp_enqueue_dev(c->sp, gray_dev, stride, ni, fisheye_mask))) return rc;
     if ((rc = omni_vlad_enqueue_dev(c->vlad, gray_dev, stride, n, fisheye_mask))) return rc;       // main camera only (:553-556)

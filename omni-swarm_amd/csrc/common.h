@@ -133,6 +133,27 @@ struct omni_ctx {
     }
 };
 
+// omni_flatten (flatten.hip): a fisheye camera's undistortion maps in HBM, immutable after creation.  cam.hip reads the view table to check a raw key
+// frame against its unit and hands the maps to flatten_unit_launch
+struct omni_flatten {
+    omni_ctx* ctx = nullptr;
+    int src_w = 0, src_h = 0, n_views = 0;
+    std::vector<int> vw, vh;
+    std::vector<int64_t> out_off;          // byte offset of view v inside one image's output block
+    int64_t out_bytes = 0;                 // per source image
+    float* maps = nullptr;                 // all views back to back, [h][w][2]; every view starts on a 16-byte boundary
+    int* meta = nullptr;                   // per view: w, h, map offset (in float2), out offset
+    std::mutex mu;
+};
+
+namespace omni {
+// flatten.hip: remaps n_images raw fisheye frames of ONE camera (u8, src_stride) into views [first_view, first_view + dirs) of f, all width x height, written
+// as [image][view][row][x] with packed rows at out_dev -- a key-frame unit's input block for that camera.  fisheye_mask != 0: the rows
+// omni_fisheye_mask_rows names are written as zeros.  Asynchronous on `stream`; the caller has checked the view sizes.
+int flatten_unit_launch(const omni_flatten* f, hipStream_t stream, const uint8_t* src_dev, int src_stride, int n_images, int first_view, int dirs, int width,
+                        int height, int fisheye_mask, uint8_t* out_dev);
+}  // namespace omni
+
 // ---- 64-bit sortable keys -------------------------------------------------------------------------------------
 // key = (orderable(score) << 32) | (0xFFFFFFFF - id): descending key order == (score desc, id asc).
 __host__ __device__ static inline uint32_t omni_f32_orderable(float f) {

@@ -73,6 +73,16 @@ class LoopCam:
                            "ids_up": r["match_up"][d, :k].copy(), "ids_down": r["match_down"][d, :k].copy(), "direction": d})
         return {"images": images, "landmark_num": int(sum(i["landmark_num"] for i in images))}
 
+    def on_fisheye_images(self, up_raw: np.ndarray, down_raw: np.ndarray, undist_up, undist_down) -> dict:
+        """The blocking call from the two RAW fisheye frames [src_h][src_w] uint8 of a key frame: undist_up / undist_down are the cameras'
+        flatten.FisheyeUndist (or capi.Flatten) objects, whose last views -- as many as the unit has directions: 1..4 of five, the top view
+        is never read (loop_cam.h:64-73) -- are flattened inside the unit (omni_cam_enqueue_fisheye_host).  Returns what
+        on_flattened_images returns for the same views."""
+        fl = [getattr(u, "flatten", u) for u in (undist_up, undist_down)]
+        raw = [np.ascontiguousarray(r, np.uint8)[None] for r in (up_raw, down_raw)]
+        self.cam.enqueue_fisheye_host(fl[0], fl[1], raw[0], raw[1], len(fl[0].shapes) - self.cam.n_active, self.fisheye)
+        return self.fetch()
+
     def on_flattened_images(self, up: np.ndarray, down: np.ndarray) -> dict:
         """Host-pointer convenience (the reference's blocking call): up/down [n_dirs][H][W] uint8."""
         g = np.ascontiguousarray(np.concatenate([up, down]), np.uint8)

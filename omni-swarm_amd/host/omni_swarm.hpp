@@ -313,6 +313,16 @@ public:
     void enqueue_dev(const uint8_t* gray_dev, int stride, bool fisheye_mask = true) {      // images already in HBM
         check(omni_cam_enqueue_dev(h_, gray_dev, stride, fisheye_mask ? 1 : 0), "omni_cam_enqueue_dev");
     }
+    // the key frames' RAW fisheye frames (n_keyframes per camera, u8, src_stride) instead of their flattened views: views first_view.. of the two cameras' maps
+    // are made inside the unit (omni_cam_enqueue_fisheye_*); n_keyframes * (views - first_view) = the unit's directions.  up / down outlive wait().
+    void enqueue_fisheye_host(omni_flatten* up, omni_flatten* down, const uint8_t* up_host, const uint8_t* down_host, int src_stride, int n_keyframes,
+                              int first_view = 1, bool fisheye_mask = true) {
+        check(omni_cam_enqueue_fisheye_host(h_, up, down, up_host, down_host, src_stride, n_keyframes, first_view, fisheye_mask ? 1 : 0), "omni_cam_enqueue_fisheye_host");
+    }
+    void enqueue_fisheye_dev(omni_flatten* up, omni_flatten* down, const uint8_t* up_dev, const uint8_t* down_dev, int src_stride, int n_keyframes,
+                             int first_view = 1, bool fisheye_mask = true) {
+        check(omni_cam_enqueue_fisheye_dev(h_, up, down, up_dev, down_dev, src_stride, n_keyframes, first_view, fisheye_mask ? 1 : 0), "omni_cam_enqueue_fisheye_dev");
+    }
     // the next enqueue on this object starts behind the convolution stack of `earlier`'s last one (omni_cam_order_after)
     void order_after(LoopCamHIP& earlier, int streams) { check(omni_cam_order_after(h_, earlier.h_, streams), "omni_cam_order_after"); }
     // a unit of fewer directions than this object was created for (omni_cam_set_active): the next enqueues read cams * n_dirs images
