@@ -87,6 +87,27 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// Every device allocation of a handle (omni_sp, omni_vlad): what alloc() handed out is what the handle's destroy frees -- also after a creation that
+// failed half way -- with no list to keep next to the struct's pointers
+struct DevMem {
+    std::vector<void*> ptrs;
+    template <typename T>
+    int alloc(T** p, size_t bytes, hipStream_t st = nullptr, bool zero = false) {
+        void* q = nullptr;
+        OMNI_HIP_TRY(hipMalloc(&q, bytes));
+        ptrs.push_back(q);
+        *p = static_cast<T*>(q);
+        if (zero) OMNI_HIP_TRY(hipMemsetAsync(q, 0, bytes, st));
+        return OMNI_OK;
+    }
+    void release(void* one, bool all) {
+        for (void*& q : ptrs)
+            if (q && (all || q == one)) { (void)hipFree(q); q = nullptr; }
+    }
+    void release_one(void* p) { release(p, false); }        // a lazy buffer that has to grow (null: nothing)
+    void release_all() { release(nullptr, true); ptrs.clear(); }
+};
+
 // Pinned host staging buffer.
 struct HostBuf {
     void* p = nullptr;

@@ -34,33 +34,13 @@ const char* kStageNames[OMNI_SP_NUM_STAGES] = {
     "convPb+softmax+d2s", "convDb+l2norm", "nms+topk+describe", "", "", "", ""};
 }  // namespace
 
-// Every device allocation of a handle: what alloc() handed out is what omni_sp_destroy frees -- no list to keep next to the struct's pointers
-struct SpDevMem {
-    std::vector<void*> ptrs;
-    template <typename T>
-    int alloc(T** p, size_t bytes, hipStream_t st = nullptr, bool zero = false) {
-        void* q = nullptr;
-        OMNI_HIP_TRY(hipMalloc(&q, bytes));
-        ptrs.push_back(q);
-        *p = static_cast<T*>(q);
-        if (zero) OMNI_HIP_TRY(hipMemsetAsync(q, 0, bytes, st));
-        return OMNI_OK;
-    }
-    void release(void* one, bool all) {
-        for (void*& q : ptrs)
-            if (q && (all || q == one)) { (void)hipFree(q); q = nullptr; }
-    }
-    void release_one(void* p) { release(p, false); }        // a lazy buffer that has to grow (null: nothing)
-    void release_all() { release(nullptr, true); ptrs.clear(); }
-};
-
 struct omni_sp {
     omni_ctx* ctx = nullptr;
     omni::Config cfg;                        // the switches as they stood when the handle was created (config.h)
     omni::SpHandleFacts facts;               // ... and what sp_plan_pass reads of them (sp_plan.h)
     omni::SpPassPlan last;                   // the plan of the last forward pass: what it left in the buffers (sp_make_dense, omni_sp_debug_layer)
     omni::SpMaskSkipState skip_state = omni::SP_SKIP_STALE;
-    SpDevMem mem;
+    omni::DevMem mem;                        // every device allocation of the handle (common.h)
     int W = 0, H = 0, Hc = 0, Wc = 0, max_num = 0, max_batch = 0, precision = 0, pca_dim = 0, desc_dim = 256;
     float thres = 0.f;
     size_t esz = 4;

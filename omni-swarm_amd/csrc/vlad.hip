@@ -6,12 +6,17 @@
 // table arrives through omni_vlad_weights so the real graph can be swapped in; oracle/mobilenetvlad_ref.py states the
 // assumed one: (x-128)/128 tiled to 3 ch, MobileNetV2(0.35) to 112 ch at stride 32, NetVLAD K=32, FC->4096, L2.
 //
-// The net is ~0.34 GMAC/image (1.4 % of SuperPoint) so it is written as plain fp32 NHWC kernels: an LDS-tiled
-// pointwise (1x1) conv, a depthwise 3x3, a stem conv, the NetVLAD aggregation and an HBM-bound FC that reads the
-// 58.7 MB weight matrix once per batch.
+// The net is ~0.34 GMAC/image (1.4 % of SuperPoint) and latency-bound, so it is a few launches: stem + block 0 in one kernel (vlad_stem_b0_kernel), every
+// other inverted-residual block as ONE launch on the fp16 matrix cores with split operands, fp32-class results (vlad_sblock_kernel, vlad_s.hip; with plain
+// fp16 operands after omni_vlad_set_precision(OMNI_PREC_F16): vlad_hblock_kernel, vlad_h.hip), the NetVLAD soft-assign and aggregation, and the FC on the
+// matrix cores in exact f32, HBM-bound on its 58.7 MB weight matrix, read once per 32 images (vlad_fc_mfma_kernel).  The exact-f32 kernels of this file
+// (vlad_block_kernel on the VALU, vlad_mblock_kernel and vlad_pw_mfma on the f32 matrix cores, the layer-by-layer kernels) are the fallback for layer
+// tables vlad_sblock_supported() rejects and the A/B reference (docs/kernels.md).
+// Which of them a pass runs is decided by vlad_make_plan and vlad_pass_skip (vlad_plan.h), nowhere else.
 #include "config.h"
 #include "common.h"
 #include "vlad_h.h"
+#include "vlad_plan.h"
 #include "conv.h"          // conv_read_pixel_bytes / conv_fill_rect_bytes (the constant region of the fisheye mask)
 
 struct VladLayerDev { int kind, cin, cout, stride, hin, win, hout, wout; float* w; float* b; };
@@ -29,42 +34,34 @@ struct VladFusedBlock {      // one inverted-residual block = [expand] + depthwi
 
 struct omni_vlad {
     omni_ctx* ctx = nullptr;
-    omni::Config cfg;                         // the switches as they stood when the handle was created (config.h)
-    bool sblock = true;                       // blocks with an sblob run on vlad_sblock_kernel (OMNI_VLAD_SBLOCK=0 disables: A/B and parity tests)
-    int prec = OMNI_PREC_F32;                 // OMNI_PREC_F16: blocks with an hblob run on vlad_hblock_kernel (omni_vlad_set_precision)
-    bool fused = false;                       // every block has a fused kernel (OMNI_VLAD_UNFUSED=1 forces the layer-by-layer path)
-    bool mfma_late = true;                    // low-resolution blocks on the f32-MFMA pointwise path (OMNI_VLAD_MFMA=0 disables)
-    int mblock_max_px = 0;                    // blocks whose INPUT has at most this many pixels per image run on vlad_mblock_kernel (OMNI_VLAD_MBLOCK_PX)
-    int mfma_max_px = 2048;                   // ... = blocks whose input has at most this many pixels per image (OMNI_VLAD_MFMA_PX)
+    omni::VladHandleFacts facts;              // the switches as they stood when the handle was created (config.h) and the sizes: what the plan reads
+    std::vector<omni::VladBlockFacts> bfacts; // ... and of `blocks`, one each
+    int prec = OMNI_PREC_F32;                 // omni_vlad_set_precision
+    omni::VladPlan plan;                      // which kernels a pass at `prec` runs (vlad_plan.h)
+    omni::DevMem mem;                         // every device allocation of the handle
     std::vector<VladFusedBlock> blocks;
     int W = 0, H = 0, max_batch = 0, K = 0, Dm = 0, out_dim = 0, hf = 0, wf = 0;
     std::vector<VladLayerDev> layers;
     float *assign_wT = nullptr, *assign_b = nullptr, *clusters = nullptr, *fc_w = nullptr, *fc_b = nullptr;
-    float* mb_partial = nullptr; size_t mb_partial_bytes = 0; int mb_cpw = 1;   // hidden-layer split of vlad_mblock_kernel
+    float* mb_partial = nullptr; size_t mb_partial_bytes = 0;   // hidden-layer split of vlad_mblock_kernel
     float *fc_wp = nullptr, *fc_part = nullptr;   // FC weights in MFMA B-operand order + K-split partial tiles (vlad_fc_mfma_kernel); null: VALU path
-    bool fc_mfma = false;
     float *buf[3] = {nullptr, nullptr, nullptr};   // rotating activation buffers
     size_t buf_elems = 0;
     float *assign = nullptr, *vlad = nullptr, *out = nullptr;
     uint8_t* gray_stage = nullptr;
     omni::HostBuf hstage;
-    // The constant region of the fisheye mask (round 6; the SuperPoint side: superpoint.hip, omni_sp::MaskSkip).  LoopCam blanks the bottom quarter of the
-    // frame BEFORE both networks run (loop_cam.cpp:536-539, 556-558): inside the band, one 3x3 tap in from its borders per convolution, the output of the
-    // stem and of every block is one constant vector.  A planned layer writes into a buffer of its own (mskip[k].buf: the rotating buffers are shared between
+    // The constant region of the fisheye mask (round 6; the SuperPoint side: superpoint.hip, omni_sp::MaskSkip).  The rectangles and the rule of which pass
+    // uses them are vlad_plan.h's (VladPlan::skip, vlad_pass_skip).  A planned layer writes into a buffer of its own (the rotating buffers are shared between
     // layers) whose rectangle is filled once, from a dense pass over a blank masked frame (vlad_calibrate_mask_skip), and the tiles inside the rectangle are
-    // left out of the tile walk: bit-identical to the dense pass (tests/test_gpu_vlad_detector.py).  mskip[0] = stem + block 0, mskip[k] = block k.
+    // left out of the tile walk: bit-identical to the dense pass (tests/test_gpu_vlad_detector.py).  mskip[k] goes with plan.skip[k].
     struct MaskSkip {
-        int ty0 = 0, ty1 = 0, tx0 = 0, tx1 = 0;       // tile rectangle in the layer's output tile grid
-        int oy0 = 0, oy1 = 0, ox0 = 0, ox1 = 0;       // the same in output pixels
-        int oh = 0, ow = 0, oc = 0;
         float* buf = nullptr;                         // [max_batch][oh][ow][oc]
         void* vec = nullptr;                          // [oc] the constant
-        double frac = 0.0;                            // the rectangle's share of the layer's tiles
     };
     std::vector<MaskSkip> mskip;
     bool mask_skip_ready = false;
-    uint8_t* zero_gray = nullptr;
-    std::mutex mu;
+    uint8_t* zero_gray = nullptr;             // the calibration's blank frame (allocated by the first masked pass that skips)
+    mutable std::mutex mu;
 };
 
 namespace omni {
@@ -1015,9 +1012,11 @@ vlad_fc_finish_kernel(const float* __restrict__ part, const float* __restrict__ 
     for (int j = threadIdx.x; j < n_out; j += 256) out[(int64_t)b * n_out + j] = out[(int64_t)b * n_out + j] / nrm;
 }
 
-static int upload(float** dst, const float* src, size_t n, hipStream_t st) {
-    OMNI_HIP_TRY(hipMalloc((void**)dst, n * 4));
-    OMNI_HIP_TRY(hipMemcpyAsync(*dst, src, n * 4, hipMemcpyHostToDevice, st));
+template <typename T>
+static int upload(omni_vlad* v, T** dst, const void* src, size_t bytes) {
+    hipStream_t st = v->ctx->stream;
+    if (int rc = v->mem.alloc(dst, bytes)) return rc;
+    OMNI_HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st));
     OMNI_HIP_TRY(hipStreamSynchronize(st));
     return OMNI_OK;
 }
@@ -1066,8 +1065,7 @@ static int vlad_backbone_unfused(omni_vlad* v, const uint8_t* gray_dev, int stri
 // A workgroup = 16x8 output pixels: the 37x21 input patch is normalised into LDS once ((x - 128) / 128, zero padding applied AFTER
 // normalisation, fisheye rows read as 0), the stem is evaluated on the 18x10 halo region (zero outside the stem map = the depthwise
 // conv's padding), then depthwise and projection -- the same FMA order as vlad_stem4_kernel / vlad_block_kernel: bit-identical.
-#define SB_TW 16
-#define SB_TH 8
+// (SB_TW x SB_TH output pixels: vlad_plan.h)
 __global__ void __launch_bounds__(256)
 vlad_stem_b0_kernel(const uint8_t* __restrict__ gray, int stride, int H, int W, int mask0, int mask1, int Ho, int Wo,
                     const float* __restrict__ ws /*[16][9]*/, const float* __restrict__ bs, const float* __restrict__ wd_t /*[9][16]*/,
@@ -1162,95 +1160,97 @@ vlad_stem_b0_kernel(const uint8_t* __restrict__ gray, int stride, int H, int W, 
     }
 }
 
-// stem + one fused kernel per inverted-residual block (v->blocks, built at create time)
-// skip_mode: 0 = the rotating buffers, every tile; 1 = the planned layers write into their own buffers, every tile (the calibration pass); 2 = ... and leave
-// the tiles of their constant rectangles out.  *out_ptr = the backbone's output.
-static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, int skip_mode, const float** out_ptr) {
+// Low-resolution block: expand / project as f32-MFMA pointwise GEMMs, depthwise in between (three launches; the fused VALU kernel has too few workgroups
+// at these sizes and is latency-bound).  `out` also holds the expanded map on the way, `tmp` the depthwise output.
+static int vlad_block_mfma3(hipStream_t st, const VladFusedBlock& B, const float* in, float* out, float* tmp, int batch) {
+    const int64_t Pin = (int64_t)batch * B.hin * B.win, Pout = (int64_t)batch * B.hout * B.wout, total = Pout * (B.hid / 4);
+    int rc;
+    if ((rc = vlad_pw_mfma(st, in, Pin, B.cin, B.hid, B.we_t, B.be, nullptr, 1, out))) return rc;
+    hipLaunchKernelGGL(vlad_dw_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, out, B.hin, B.win, B.hid, B.hout, B.wout, B.stride, B.wd_t, B.bd,
+                       tmp, total);
+    OMNI_LAUNCH_CHECK();
+    return vlad_pw_mfma(st, tmp, Pout, B.hid, B.cout, B.wp_t, B.bp, B.res ? in : nullptr, 0, out);
+}
+
+// the fields every block kernel's argument struct shares, from the block
+template <typename Args>
+static Args vlad_block_args(const VladFusedBlock& B, const float* in, float* out, int batch) {
+    Args a{};
+    a.in = in; a.out = out; a.bp = B.bp;
+    a.Hi = B.hin; a.Wi = B.win; a.Ho = B.hout; a.Wo = B.wout; a.hid = B.hid; a.cout = B.cout; a.res = B.res; a.batch = batch;
+    return a;
+}
+
+// stem + one fused kernel per inverted-residual block (v->blocks, built at create time), each as v->plan says.  The layers `ps` names write into their
+// own buffers instead of the next rotating one and may leave their rectangle of the mask's constant region out.  *out_ptr = the backbone's output.
+static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, const VladPassSkip& ps, const float** out_ptr) {
     hipStream_t st = v->ctx->stream;
+    const VladPlan& plan = v->plan;
     const int H = v->H, W = v->W;
-    const float* in_over = nullptr;          // the previous layer wrote into a buffer of its own: this layer's input (instead of buf[cur])
     int m0, m1;
     omni_fisheye_mask_rows(H, fisheye_mask, &m0, &m1);
     const VladLayerDev& S = v->layers[0];
-    int cur = 0, rc;
+    int cur = 0, rc;                         // buf[cur]: the rotating buffer written last
+    auto own = [&](size_t k) { return (int)k < ps.n_own; };
+    auto left_out = [&](size_t k) { return own(k) && ps.leave_out ? plan.skip[k] : VladSkipRect{}; };      // (an empty rectangle: every tile runs)
+    const float* in = v->buf[0];             // the current layer's input
     size_t first = 0;
-    const bool stem_fuse = v->cfg[omni::CFG_VLAD_STEM_FUSE] != 0;           // 0: stem and block 0 as two kernels (A/B and parity tests)
-    const VladFusedBlock* B0 = v->blocks.empty() ? nullptr : &v->blocks[0];
-    if (stem_fuse && B0 && S.cout == 16 && S.stride == 2 && !B0->expand && !B0->res && B0->cin == 16 && B0->hid == 16 && B0->cout == 8 &&
-        B0->stride == 1) {
+    if (plan.stem == VLAD_STEM_B0) {
         // stem + block 0 in one kernel: the 16-channel stem map never reaches HBM
-        hipLaunchKernelGGL(vlad_stem_b0_kernel, dim3(cdiv(B0->wout, SB_TW) * cdiv(B0->hout, SB_TH), batch), dim3(256), 0, st, gray_dev, stride, H,
-                           W, m0, m1, S.hout, S.wout, S.w, S.b, B0->wd_t, B0->bd, B0->wp_t, B0->bp, skip_mode ? v->mskip[0].buf : v->buf[1],
-                           skip_mode == 2 ? v->mskip[0].ty0 : 0, skip_mode == 2 ? v->mskip[0].ty1 : 0, v->mskip.empty() ? 0 : v->mskip[0].tx0, v->mskip.empty() ? 0 : v->mskip[0].tx1);
-        OMNI_LAUNCH_CHECK();
-        cur = 1; first = 1;
-        if (skip_mode) in_over = v->mskip[0].buf;
+        const VladFusedBlock& B0 = v->blocks[0];
+        const VladSkipRect k = left_out(0);
+        float* const out = own(0) ? v->mskip[0].buf : v->buf[1];
+        hipLaunchKernelGGL(vlad_stem_b0_kernel, dim3(cdiv(B0.wout, SB_TW) * cdiv(B0.hout, SB_TH), batch), dim3(256), 0, st, gray_dev, stride, H, W, m0, m1,
+                           S.hout, S.wout, S.w, S.b, B0.wd_t, B0.bd, B0.wp_t, B0.bp, out, k.ty0, k.ty1, k.tx0, k.tx1);
+        cur = 1; first = 1; in = out;
     } else {
         hipLaunchKernelGGL(vlad_stem4_kernel, dim3(cdiv(S.hout * S.wout * (S.cout / 4), 256), batch), dim3(256), 0, st, gray_dev, stride, H, W, m0,
                            m1, S.hout, S.wout, S.cout, S.stride, S.w, S.b, v->buf[0]);
-        OMNI_LAUNCH_CHECK();
     }
+    OMNI_LAUNCH_CHECK();
     for (size_t bi = first; bi < v->blocks.size(); ++bi) {
         const VladFusedBlock& B = v->blocks[bi];
-        const int64_t Pin = (int64_t)batch * B.hin * B.win, Pout = (int64_t)batch * B.hout * B.wout;
-        const float* const in = in_over ? in_over : v->buf[cur];
-        in_over = nullptr;
-        if (v->prec == OMNI_PREC_F16 && B.hblob) {
-            VladHBlockArgs ha;
-            ha.in = in; ha.out = v->buf[(cur + 1) % 3]; ha.blob = B.hblob; ha.bp = B.bp;
-            ha.Hi = B.hin; ha.Wi = B.win; ha.Ho = B.hout; ha.Wo = B.wout; ha.cin = B.cin; ha.hid = B.hid; ha.cout = B.cout; ha.res = B.res; ha.batch = batch;
-            if ((rc = launch_vlad_hblock(st, ha, B.stride))) return rc;
-            cur = (cur + 1) % 3;
-            continue;
+        const int next = (cur + 1) % 3;
+        float* const out = own(bi) ? v->mskip[bi].buf : v->buf[next];
+        switch (plan.blocks[bi]) {
+        case VB_HBLOCK: {
+            VladHBlockArgs a = vlad_block_args<VladHBlockArgs>(B, in, out, batch);
+            a.blob = B.hblob; a.cin = B.cin;
+            if ((rc = launch_vlad_hblock(st, a, B.stride))) return rc;
+            break;
         }
-        if (v->sblock && B.sblob) {
-            VladSBlockArgs sa;
-            const bool own = skip_mode && bi < v->mskip.size();          // a planned layer: its own output buffer (the ring is not advanced)
-            sa.in = in; sa.out = own ? v->mskip[bi].buf : v->buf[(cur + 1) % 3]; sa.blob = B.sblob; sa.bp = B.bp;
-            if (own && skip_mode == 2) { sa.sk_y0 = v->mskip[bi].ty0; sa.sk_y1 = v->mskip[bi].ty1; sa.sk_x0 = v->mskip[bi].tx0; sa.sk_w = v->mskip[bi].tx1 - v->mskip[bi].tx0; }
-            sa.Hi = B.hin; sa.Wi = B.win; sa.Ho = B.hout; sa.Wo = B.wout; sa.cin = B.cin; sa.hid = B.hid; sa.cout = B.cout; sa.res = B.res; sa.batch = batch;
-            sa.n_cu = v->ctx->prop.multiProcessorCount > 0 ? v->ctx->prop.multiProcessorCount : 256; sa.trace = nullptr; sa.dbg = 0;
-            sa.persist = v->cfg[omni::CFG_VLAD_SB_PERSIST];
-            if ((rc = launch_vlad_sblock(st, sa, B.stride))) return rc;
-            if (own) in_over = v->mskip[bi].buf;
-            else cur = (cur + 1) % 3;
-            continue;
+        case VB_SBLOCK: {
+            VladSBlockArgs a = vlad_block_args<VladSBlockArgs>(B, in, out, batch);
+            const VladSkipRect k = left_out(bi);
+            a.blob = B.sblob; a.cin = B.cin;
+            a.sk_y0 = k.ty0; a.sk_y1 = k.ty1; a.sk_x0 = k.tx0; a.sk_w = k.tx1 - k.tx0;
+            a.n_cu = v->ctx->prop.multiProcessorCount > 0 ? v->ctx->prop.multiProcessorCount : 256; a.trace = nullptr; a.dbg = 0;
+            a.persist = v->facts.sb_persist;
+            if ((rc = launch_vlad_sblock(st, a, B.stride))) return rc;
+            break;
         }
-        if (B.mblob && B.hin * B.win <= v->mblock_max_px) {                  // per-image size: batch-independent numerics
-            VladMBlockArgs m;
-            m.in = in; m.out = v->buf[(cur + 1) % 3]; m.blob = B.mblob; m.bp = B.bp;
-            m.Hi = B.hin; m.Wi = B.win; m.Ho = B.hout; m.Wo = B.wout; m.cin = B.cin; m.hid = B.hid; m.cout = B.cout; m.cop = B.cop;
-            m.stride = B.stride; m.res = B.res; m.batch = batch;
-            const int n_chunks = (B.hid + 31) / 32, tiles = cdiv(B.wout, 8) * cdiv(B.hout, 8) * batch;
-            m.cpw = v->mb_cpw > 0 ? v->mb_cpw : n_chunks; m.n_groups = cdiv(n_chunks, m.cpw);
-            if ((size_t)tiles * m.n_groups * 64 * B.cop * 4 > v->mb_partial_bytes) { m.cpw = n_chunks; m.n_groups = 1; }      // scratch too small: no split
-            m.partial = v->mb_partial;
-            if ((rc = launch_vlad_mblock(st, m))) return rc;
-            cur = (cur + 1) % 3;
-            continue;
+        case VB_MBLOCK: {
+            VladMBlockArgs a = vlad_block_args<VladMBlockArgs>(B, in, out, batch);
+            const VladMBlockSplit split = vlad_mblock_split(v->facts, v->bfacts[bi], batch, v->mb_partial_bytes);
+            a.blob = B.mblob; a.cin = B.cin; a.cop = B.cop; a.stride = B.stride;
+            a.cpw = split.cpw; a.n_groups = split.n_groups; a.partial = v->mb_partial;
+            if ((rc = launch_vlad_mblock(st, a))) return rc;
+            break;
         }
-        if (B.expand && B.cin % 8 == 0 && B.hid % 8 == 0 && B.hin * B.win <= v->mfma_max_px && v->mfma_late) {     // per-image size: batch-independent numerics
-            // low-resolution block: expand / project as f32-MFMA pointwise GEMMs, depthwise in between (three launches; the fused
-            // VALU kernel has too few workgroups at these sizes and is latency-bound)
-            const int e = (cur + 1) % 3, d = (cur + 2) % 3;
-            if ((rc = vlad_pw_mfma(st, in, Pin, B.cin, B.hid, B.we_t, B.be, nullptr, 1, v->buf[e]))) return rc;
-            const int64_t total = Pout * (B.hid / 4);
-            hipLaunchKernelGGL(vlad_dw_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, v->buf[e], B.hin, B.win, B.hid, B.hout, B.wout,
-                               B.stride, B.wd_t, B.bd, v->buf[d], total);
-            OMNI_LAUNCH_CHECK();
-            if ((rc = vlad_pw_mfma(st, v->buf[d], Pout, B.hid, B.cout, B.wp_t, B.bp, B.res ? in : nullptr, 0, v->buf[e]))) return rc;
-            cur = e;
-            continue;
+        case VB_PW_MFMA3:
+            if ((rc = vlad_block_mfma3(st, B, in, out, v->buf[(cur + 2) % 3], batch))) return rc;
+            break;
+        case VB_VALU: {
+            VladBlockArgs a = vlad_block_args<VladBlockArgs>(B, in, out, batch);
+            a.blob = B.blob; a.stride = B.stride; a.expand = B.expand;
+            if ((rc = vlad_block(st, B.cin, a))) return rc;
+            break;
         }
-        VladBlockArgs a;
-        a.in = in; a.out = v->buf[(cur + 1) % 3];
-        a.blob = B.blob; a.bp = B.bp;
-        a.Hi = B.hin; a.Wi = B.win; a.Ho = B.hout; a.Wo = B.wout; a.hid = B.hid; a.cout = B.cout; a.stride = B.stride;
-        a.expand = B.expand; a.res = B.res; a.batch = batch;
-        if ((rc = vlad_block(st, B.cin, a))) return rc;
-        cur = (cur + 1) % 3;
+        }
+        if (!own(bi)) cur = next;
+        in = out;
     }
-    *out_ptr = in_over ? in_over : v->buf[cur];
+    *out_ptr = in;
     return OMNI_OK;
 }
 
@@ -1258,77 +1258,72 @@ static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride
 // rectangle and written into that rectangle of every image slot.  Passes without the mask use the rotating buffers: the rectangles stay valid.
 static int vlad_calibrate_mask_skip(omni_vlad* v) {
     hipStream_t st = v->ctx->stream;
-    if (!v->zero_gray) {
-        OMNI_HIP_TRY(hipMalloc((void**)&v->zero_gray, (size_t)v->W * v->H));
-        OMNI_HIP_TRY(hipMemsetAsync(v->zero_gray, 0, (size_t)v->W * v->H, st));
-    }
-    const float* unused;
     int rc;
-    if ((rc = vlad_backbone_fused(v, v->zero_gray, v->W, 1, 1, 1, &unused))) return rc;
-    for (const omni_vlad::MaskSkip& k : v->mskip) {
+    if (!v->zero_gray && (rc = v->mem.alloc(&v->zero_gray, (size_t)v->W * v->H, st, true))) return rc;
+    const float* unused;
+    if ((rc = vlad_backbone_fused(v, v->zero_gray, v->W, 1, 1, vlad_pass_skip(v->plan, v->prec, true, true), &unused))) return rc;
+    for (size_t i = 0; i < v->mskip.size(); ++i) {
+        const VladSkipRect& k = v->plan.skip[i];
+        const omni_vlad::MaskSkip& m = v->mskip[i];
         const int pix = k.oc * 4;
         const int64_t row = (int64_t)k.ow * pix, img = row * k.oh;
-        if ((rc = conv_read_pixel_bytes(st, k.buf, row, 0, pix, (k.oy0 + k.oy1) / 2, (k.ox0 + k.ox1) / 2, k.vec))) return rc;
-        if ((rc = conv_fill_rect_bytes(st, k.buf, v->max_batch, img, row, 0, pix, k.oy0, k.oy1, k.ox0, k.ox1, k.vec))) return rc;
+        if ((rc = conv_read_pixel_bytes(st, m.buf, row, 0, pix, (k.oy0 + k.oy1) / 2, (k.ox0 + k.ox1) / 2, m.vec))) return rc;
+        if ((rc = conv_fill_rect_bytes(st, m.buf, v->max_batch, img, row, 0, pix, k.oy0, k.oy1, k.ox0, k.ox1, m.vec))) return rc;
     }
     v->mask_skip_ready = true;
     return OMNI_OK;
 }
 
-// Where the stem's / the blocks' outputs are constant under the fisheye mask, and the tile rectangles inside (omni_vlad::MaskSkip): integer arithmetic on
-// (H, W), the layers' strides and the kernels' tile shapes (vlad_stem_b0_kernel: SB_TH x SB_TW; vlad_sblock_kernel: 8 x 8 at stride 1, 4 rows x 8 at stride 2).
-// A 3x3 convolution with padding 1 at stride s reads input rows s r - 1 .. s r + 1: the zero padding is not the constant.
-static void vlad_plan_mask_skip(omni_vlad* v) {
-    v->mskip.clear();
-    if (!v->fused || !v->sblock || !v->cfg[omni::CFG_VLAD_MASK_SKIP] || !v->cfg[omni::CFG_VLAD_STEM_FUSE] || v->blocks.empty()) return;
-    const VladLayerDev& S = v->layers[0];
-    const VladFusedBlock& B0 = v->blocks[0];
-    if (!(S.cout == 16 && S.stride == 2 && !B0.expand && !B0.res && B0.cin == 16 && B0.hid == 16 && B0.cout == 8 && B0.stride == 1)) return;      // (vlad_stem_b0_kernel's shape)
-    int m0, m1;
-    omni_fisheye_mask_rows(v->H, 1, &m0, &m1);
-    int a = m0, b = m1 - 1, c = 0, d = v->W - 1;                 // constant rows [a, b] x columns [c, d] (inclusive) of the current map
-    auto conv3 = [&](int stride) {                               // through a 3x3 convolution, padding 1
-        if (stride == 2) { a = (a + 2) / 2; b = (b - 1) >> 1; c = (c + 2) / 2; d = (d - 1) >> 1; }      // rows 2r - 1 .. 2r + 1 inside [a, b]
-        else { a += 1; b -= 1; c += 1; d -= 1; }
-    };
-    auto plan = [&](int th, int tw, int oh, int ow, int oc) -> bool {
-        omni_vlad::MaskSkip k;
-        if (b < a || d < c) return false;
-        k.ty0 = (a + th - 1) / th; k.ty1 = (b + 1) / th; k.tx0 = (c + tw - 1) / tw; k.tx1 = (d + 1) / tw;
-        if (k.ty1 <= k.ty0 || k.tx1 <= k.tx0) return false;
-        k.oy0 = k.ty0 * th; k.oy1 = k.ty1 * th; k.ox0 = k.tx0 * tw; k.ox1 = k.tx1 * tw;
-        k.oh = oh; k.ow = ow; k.oc = oc;
-        k.frac = (double)(k.ty1 - k.ty0) * (k.tx1 - k.tx0) / ((double)cdiv(oh, th) * cdiv(ow, tw));
-        v->mskip.push_back(k);
-        return true;
-    };
-    conv3(2);                                                    // the stem
-    conv3(1);                                                    // block 0's depthwise convolution (its projection is 1x1)
-    if (!plan(SB_TH, SB_TW, B0.hout, B0.wout, B0.cout)) return;
-    for (size_t bi = 1; bi < v->blocks.size(); ++bi) {
-        const VladFusedBlock& B = v->blocks[bi];
-        if (!B.sblob || (B.cout * 4) % 16 != 0) break;
-        conv3(B.stride);                                         // (expand and projection are 1x1; the residual adds two constants)
-        if (!plan(B.stride == 1 ? 8 : 4, 8, B.hout, B.wout, B.cout)) break;
+// FC + L2 norm: v->vlad [batch][K * Dm] -> v->out [batch][out_dim], in the form the plan names
+static int vlad_fc(omni_vlad* v, int batch) {
+    hipStream_t st = v->ctx->stream;
+    const VladPlan& plan = v->plan;
+    const int n_in = v->K * v->Dm;
+    const int fc_batch = plan.fc == VLAD_FC_MFMA ? 32 : FC_MAXB;            // images per FC launch
+    for (int b0 = 0; b0 < batch; b0 += fc_batch) {
+        const int nb = batch - b0 < fc_batch ? batch - b0 : fc_batch;
+        const float* const x = v->vlad + (int64_t)b0 * n_in;
+        float* const y = v->out + (int64_t)b0 * v->out_dim;
+        const size_t smem = (size_t)nb * n_in * 4;                          // (the VALU kernels keep their images in LDS)
+        switch (plan.fc) {
+        case VLAD_FC_MFMA:
+            hipLaunchKernelGGL(vlad_fc_mfma_kernel, dim3(v->out_dim / 32, FCM_KY), dim3(256), 0, st, x, nb, n_in, v->fc_wp, v->out_dim, v->fc_part);
+            OMNI_LAUNCH_CHECK();
+            hipLaunchKernelGGL(vlad_fc_finish_kernel, dim3(nb), dim3(256), 0, st, v->fc_part, v->fc_b, v->out_dim, y);
+            break;
+        case VLAD_FC4:
+            OMNI_HIP_TRY(hipFuncSetAttribute((const void*)vlad_fc4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            hipLaunchKernelGGL(vlad_fc4_kernel, dim3(cdiv(v->out_dim, 16)), dim3(256), smem, st, x, nb, n_in, v->fc_w, v->fc_b, v->out_dim, y);
+            break;
+        case VLAD_FC_VALU:
+            OMNI_HIP_TRY(hipFuncSetAttribute((const void*)vlad_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            hipLaunchKernelGGL(vlad_fc_kernel, dim3(cdiv(v->out_dim, 4)), dim3(256), smem, st, x, nb, n_in, v->fc_w, v->fc_b, v->out_dim, y);
+            break;
+        }
+        OMNI_LAUNCH_CHECK();
     }
+    if (plan.fc == VLAD_FC_MFMA) return OMNI_OK;                            // (vlad_fc_finish_kernel normalises)
+    hipLaunchKernelGGL(l2norm_rows_kernel, dim3(batch), dim3(256), 0, st, v->out, v->out_dim);
+    OMNI_LAUNCH_CHECK();
+    return OMNI_OK;
 }
 
 static int vlad_forward(omni_vlad* v, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask) {
     hipStream_t st = v->ctx->stream;
+    const VladPlan& plan = v->plan;
     int cur = 0, rc;
     const float* feat = nullptr;             // the backbone's output map
-    if (v->fused) {
-        // the mask's constant region (omni_vlad::MaskSkip): only the split block kernels know the shortened tile walk
-        const bool skip = fisheye_mask && !v->mskip.empty() && v->sblock && v->prec != OMNI_PREC_F16;
-        if (skip && !v->mask_skip_ready && (rc = vlad_calibrate_mask_skip(v))) return rc;
-        if ((rc = vlad_backbone_fused(v, gray_dev, stride, batch, fisheye_mask, skip ? 2 : 0, &feat))) return rc;
+    if (plan.fused) {
+        const VladPassSkip ps = vlad_pass_skip(plan, v->prec, fisheye_mask != 0, false);
+        if (ps.leave_out && !v->mask_skip_ready && (rc = vlad_calibrate_mask_skip(v))) return rc;
+        if ((rc = vlad_backbone_fused(v, gray_dev, stride, batch, fisheye_mask, ps, &feat))) return rc;
     } else {
         if ((rc = vlad_backbone_unfused(v, gray_dev, stride, batch, fisheye_mask, &cur))) return rc;
         feat = v->buf[cur];
     }
-    const int n_pos = v->hf * v->wf;
+    const int n_pos = v->hf * v->wf, n_in = v->K * v->Dm;
     const int64_t n_all = (int64_t)batch * n_pos;
-    if (v->fused && v->K <= 32) {
+    if (plan.head == VLAD_ASSIGN2_AGG8) {
         const size_t smem = ((size_t)v->Dm * v->K + 8 * v->Dm) * 4;
         hipLaunchKernelGGL(vlad_assign2_kernel, dim3((unsigned)cdiv64(n_all, 8)), dim3(256), smem, st, feat, n_all, v->Dm, v->K,
                            v->assign_wT, v->assign_b, v->assign);
@@ -1343,36 +1338,96 @@ static int vlad_forward(omni_vlad* v, const uint8_t* gray_dev, int stride, int b
                            v->vlad);
     }
     OMNI_LAUNCH_CHECK();
-    const int n_in = v->K * v->Dm;
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3(batch), dim3(256), 0, st, v->vlad, n_in);
     OMNI_LAUNCH_CHECK();
-    if (v->fc_mfma) {
-        for (int b0 = 0; b0 < batch; b0 += 32) {
-            const int nb = batch - b0 < 32 ? batch - b0 : 32;
-            hipLaunchKernelGGL(vlad_fc_mfma_kernel, dim3(v->out_dim / 32, FCM_KY), dim3(256), 0, st, v->vlad + (int64_t)b0 * n_in, nb, n_in, v->fc_wp,
-                               v->out_dim, v->fc_part);
-            OMNI_LAUNCH_CHECK();
-            hipLaunchKernelGGL(vlad_fc_finish_kernel, dim3(nb), dim3(256), 0, st, v->fc_part, v->fc_b, v->out_dim, v->out + (int64_t)b0 * v->out_dim);
-            OMNI_LAUNCH_CHECK();
-        }
-        return OMNI_OK;
+    return vlad_fc(v, batch);
+}
+
+// A block's weights per 32-channel chunk of the hidden layer, [We cin x 32 | be 32 | Wd 9 x 32 | bd 32 | Wp 32 x cols] zero padded, from the host copies of
+// the layer weights (OIHW; Le = null: no expansion).  cols = cout (VladBlockArgs) or the padded cop (VladMBlockArgs).
+static std::vector<float> vlad_pack_chunks(const VladFusedBlock& B, const omni_vlad_layer* Le, const omni_vlad_layer& Ld, const omni_vlad_layer& Lp, int cols) {
+    const int n_chunks = (B.hid + 31) / 32, blob = 32 * (B.cin + 11 + cols);
+    std::vector<float> pk((size_t)n_chunks * blob, 0.f);
+    for (int ch = 0; ch < B.hid; ++ch) {
+        float* q = pk.data() + (size_t)(ch / 32) * blob;
+        const int c = ch % 32;
+        if (Le) { for (int k = 0; k < B.cin; ++k) q[k * 32 + c] = Le->weight[(size_t)ch * B.cin + k]; q[B.cin * 32 + c] = Le->bias[ch]; }
+        for (int t = 0; t < 9; ++t) q[(B.cin + 1) * 32 + t * 32 + c] = Ld.weight[(size_t)ch * 9 + t];
+        q[(B.cin + 10) * 32 + c] = Ld.bias[ch];
+        for (int co = 0; co < B.cout; ++co) q[(B.cin + 11) * 32 + c * cols + co] = Lp.weight[(size_t)co * B.hid + ch];
     }
-    for (int b0 = 0; b0 < batch; b0 += FC_MAXB) {
-        const int nb = batch - b0 < FC_MAXB ? batch - b0 : FC_MAXB;
-        const size_t smem = (size_t)nb * n_in * 4;
-        if (v->fused) {
-            OMNI_HIP_TRY(hipFuncSetAttribute((const void*)vlad_fc4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            hipLaunchKernelGGL(vlad_fc4_kernel, dim3(cdiv(v->out_dim, 16)), dim3(256), smem, st, v->vlad + (int64_t)b0 * n_in, nb, n_in, v->fc_w,
-                               v->fc_b, v->out_dim, v->out + (int64_t)b0 * v->out_dim);
-        } else {
-            OMNI_HIP_TRY(hipFuncSetAttribute((const void*)vlad_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            hipLaunchKernelGGL(vlad_fc_kernel, dim3(cdiv(v->out_dim, 4)), dim3(256), smem, st, v->vlad + (int64_t)b0 * n_in, nb, n_in, v->fc_w,
-                               v->fc_b, v->out_dim, v->out + (int64_t)b0 * v->out_dim);
-        }
-        OMNI_LAUNCH_CHECK();
+    return pk;
+}
+
+// every packed form of a block that exists for its shape, uploaded (the fp32 VALU form always; the others need the expansion)
+static int vlad_upload_block(omni_vlad* v, VladFusedBlock& B, const omni_vlad_layer* Le, const omni_vlad_layer& Ld, const omni_vlad_layer& Lp) {
+    int rc;
+    const std::vector<float> pk = vlad_pack_chunks(B, Le, Ld, Lp, B.cout);
+    if ((rc = upload(v, &B.blob, pk.data(), pk.size() * 4))) return rc;
+    B.cop = vlad_mblock_cop(B.cout);
+    if (Le && B.cin % 4 == 0 && B.cop <= 128 && vlad_mblock_smem(B.cin, B.cop, B.stride) <= 160 * 1024) {
+        const std::vector<float> mk = vlad_pack_chunks(B, Le, Ld, Lp, B.cop);
+        if ((rc = upload(v, &B.mblob, mk.data(), mk.size() * 4))) return rc;
     }
-    hipLaunchKernelGGL(l2norm_rows_kernel, dim3(batch), dim3(256), 0, st, v->out, v->out_dim);
-    OMNI_LAUNCH_CHECK();
+    if (Le && vlad_sblock_supported(B.cin, B.hid, B.cout, B.stride)) {
+        std::vector<char> sk(vlad_sblock_blob_bytes(B.cin, B.hid, B.cout));
+        vlad_sblock_pack(B.cin, B.hid, B.cout, Le->weight, Le->bias, Ld.weight, Ld.bias, Lp.weight, sk.data());
+        if ((rc = upload(v, &B.sblob, sk.data(), sk.size()))) return rc;
+    }
+    if (Le && vlad_hblock_supported(B.cin, B.hid, B.cout, B.stride)) {
+        std::vector<char> hk(vlad_hblock_blob_bytes(B.cin, B.hid, B.cout));
+        vlad_hblock_pack(B.cin, B.hid, B.cout, Le->weight, Le->bias, Ld.weight, Ld.bias, Lp.weight, hk.data());
+        if ((rc = upload(v, &B.hblob, hk.data(), hk.size()))) return rc;
+    }
+    return OMNI_OK;
+}
+
+static VladBlockFacts vlad_block_facts(const VladFusedBlock& B) {
+    VladBlockFacts f;
+    f.cin = B.cin; f.hid = B.hid; f.cout = B.cout; f.stride = B.stride; f.expand = B.expand; f.res = B.res;
+    f.px = B.hin * B.win; f.hout = B.hout; f.wout = B.wout;
+    f.blob = B.blob != nullptr; f.mblob = B.mblob != nullptr; f.hblob = B.hblob != nullptr; f.sblob = B.sblob != nullptr;
+    return f;
+}
+
+static void vlad_replan(omni_vlad* v) {
+    VladStemFacts stem;
+    stem.cout = v->layers[0].cout; stem.stride = v->layers[0].stride;
+    v->plan = vlad_make_plan(v->facts, stem, v->bfacts, v->prec);
+}
+
+// the NetVLAD head's weights, the scratch and the activations of a handle whose layers are uploaded and whose blocks are grouped
+static int vlad_create_head(omni_vlad* v, const omni_vlad_weights* w) {
+    static_assert(VLAD_FC_MFMA_K == 4 * 2 * FCM_KY * 4, "vlad_plan.h states vlad_fc_mfma_kernel's K split");
+    int rc;
+    const size_t n_in = (size_t)v->K * v->Dm, B = (size_t)v->max_batch;
+    std::vector<float> awT((size_t)v->Dm * v->K);
+    for (int k = 0; k < v->K; ++k) for (int d = 0; d < v->Dm; ++d) awT[(size_t)d * v->K + k] = w->assign_w[(size_t)k * v->Dm + d];
+    if ((rc = upload(v, &v->assign_wT, awT.data(), awT.size() * 4)) || (rc = upload(v, &v->assign_b, w->assign_b, (size_t)v->K * 4)) ||
+        (rc = upload(v, &v->clusters, w->clusters, n_in * 4)) || (rc = upload(v, &v->fc_w, w->fc_w, n_in * v->out_dim * 4)) ||
+        (rc = upload(v, &v->fc_b, w->fc_b, (size_t)v->out_dim * 4))) return rc;
+    if (v->plan.fc == VLAD_FC_MFMA) {   // FC on the matrix cores: W [out][n_in] -> [out / 32][n_in / 4][32 rows][4] (vlad_fc_mfma_kernel)
+        const size_t groups = n_in / 4;
+        std::vector<float> pk(n_in * (size_t)v->out_dim);
+        for (int j = 0; j < v->out_dim; ++j)
+            for (size_t g = 0; g < groups; ++g)
+                memcpy(&pk[(((size_t)(j / 32) * groups + g) * 32 + (j % 32)) * 4], &w->fc_w[(size_t)j * n_in + g * 4], 16);
+        if ((rc = upload(v, &v->fc_wp, pk.data(), pk.size() * 4)) || (rc = v->mem.alloc(&v->fc_part, (size_t)FCM_KY * 32 * v->out_dim * 4))) return rc;
+    }
+    // scratch of vlad_mblock_kernel's hidden-layer split (measured: splitting does not pay -- same total issue-bound work + a reduce launch per block)
+    if (const size_t need = vlad_mblock_scratch_bytes(v->facts, v->bfacts, v->max_batch)) {
+        if ((rc = v->mem.alloc(&v->mb_partial, need))) return rc;
+        v->mb_partial_bytes = need;
+    }
+    for (int i = 0; i < 3; ++i)
+        if ((rc = v->mem.alloc(&v->buf[i], v->buf_elems * 4))) return rc;
+    v->mskip.resize(v->plan.skip.size());
+    for (size_t i = 0; i < v->mskip.size(); ++i) {
+        const VladSkipRect& k = v->plan.skip[i];
+        if ((rc = v->mem.alloc(&v->mskip[i].buf, B * k.oh * k.ow * k.oc * 4)) || (rc = v->mem.alloc(&v->mskip[i].vec, (size_t)k.oc * 4))) return rc;
+    }
+    if ((rc = v->mem.alloc(&v->assign, B * v->hf * v->wf * v->K * 4)) || (rc = v->mem.alloc(&v->vlad, B * n_in * 4)) ||
+        (rc = v->mem.alloc(&v->out, B * v->out_dim * 4)) || (rc = v->mem.alloc(&v->gray_stage, B * v->W * v->H))) return rc;
     return OMNI_OK;
 }
 
@@ -1389,10 +1444,16 @@ omni_vlad* omni_vlad_create(omni_ctx* ctx, const omni_vlad_weights* w, int width
         return nullptr;
     }
     (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
+    omni::Config cfg;
+    if (omni::config_resolve(&cfg) != OMNI_OK) return nullptr;
     omni_vlad* v = new omni_vlad();
-    if (omni::config_resolve(&v->cfg) != OMNI_OK) { delete v; return nullptr; }
     v->ctx = ctx; v->W = width; v->H = height; v->max_batch = max_batch; v->K = w->n_clusters; v->Dm = w->feat_dim; v->out_dim = w->out_dim;
+    omni::VladHandleFacts& f = v->facts;
+    f.unfused = cfg[omni::CFG_VLAD_UNFUSED] != 0; f.sblock = cfg[omni::CFG_VLAD_SBLOCK] != 0; f.stem_fuse = cfg[omni::CFG_VLAD_STEM_FUSE] != 0;
+    f.mfma = cfg[omni::CFG_VLAD_MFMA] != 0; f.mblock_px = cfg[omni::CFG_VLAD_MBLOCK_PX]; f.mfma_px = cfg[omni::CFG_VLAD_MFMA_PX];
+    f.fc_mfma = cfg[omni::CFG_VLAD_FC_MFMA] != 0; f.mask_skip = cfg[omni::CFG_VLAD_MASK_SKIP] != 0; f.sb_persist = cfg[omni::CFG_VLAD_SB_PERSIST];
+    f.mblock_cpw = cfg[omni::CFG_VLAD_MBLOCK_CPW];
+    f.K = v->K; f.Dm = v->Dm; f.out_dim = v->out_dim; f.H = height; f.W = width;
     int h = height, wd = width, c = 0;
     size_t max_elems = 0;
     bool ok = true;
@@ -1417,7 +1478,7 @@ omni_vlad* omni_vlad_create(omni_ctx* ctx, const omni_vlad_weights* w, int width
             tmp.resize((size_t)L.cout * L.cin);
             for (int co = 0; co < L.cout; ++co) for (int ci = 0; ci < L.cin; ++ci) tmp[(size_t)ci * L.cout + co] = L.weight[(size_t)co * L.cin + ci];
         }
-        if (omni::upload(&d.w, tmp.data(), tmp.size(), st) || omni::upload(&d.b, L.bias, L.cout, st)) { ok = false; break; }
+        if (omni::upload(v, &d.w, tmp.data(), tmp.size() * 4) || omni::upload(v, &d.b, L.bias, (size_t)L.cout * 4)) { ok = false; break; }
         v->layers.push_back(d);
         h = d.hout; wd = d.wout; c = L.cout;
         const size_t e = (size_t)h * wd * c;
@@ -1438,118 +1499,20 @@ omni_vlad* omni_vlad_create(omni_ctx* ctx, const omni_vlad_weights* w, int width
                 (dwl.stride != 1 && dwl.stride != 2)) { fusable = false; break; }
             B.cin = e ? e->cin : dwl.cin; B.hid = dwl.cin; B.cout = pl.cout; B.stride = dwl.stride; B.expand = e ? 1 : 0;
             B.res = pl.kind == OMNI_VLAD_PW_LINEAR_RES; B.hin = dwl.hin; B.win = dwl.win; B.hout = dwl.hout; B.wout = dwl.wout;
-            B.bp = pl.b; B.blob = nullptr;
+            B.bp = pl.b;
             B.we_t = e ? e->w : nullptr; B.be = e ? e->b : nullptr; B.wd_t = dwl.w; B.bd = dwl.b; B.wp_t = pl.w;
             if (!omni::vlad_block_supported(B.cin, B.cout) || B.cout % 4 || (B.res && (B.stride != 1 || B.cin != B.cout)) || (!e && B.hid > 32)) { fusable = false; break; }
-            {   // pack the block's weights per 32-channel chunk of the hidden layer (host copies of the layer weights, OIHW)
-                const omni_vlad_layer* Le = e ? &w->layers[i - 1] : nullptr;
-                const omni_vlad_layer& Ld = w->layers[i];
-                const omni_vlad_layer& Lp = w->layers[i + 1];
-                const int n_chunks = (B.hid + 31) / 32, blob = 32 * (B.cin + 11 + B.cout);
-                std::vector<float> pk((size_t)n_chunks * blob, 0.f);
-                for (int ch = 0; ch < B.hid; ++ch) {
-                    float* q = pk.data() + (size_t)(ch / 32) * blob;
-                    const int c = ch % 32;
-                    if (Le) { for (int k = 0; k < B.cin; ++k) q[k * 32 + c] = Le->weight[(size_t)ch * B.cin + k]; q[B.cin * 32 + c] = Le->bias[ch]; }
-                    for (int t = 0; t < 9; ++t) q[(B.cin + 1) * 32 + t * 32 + c] = Ld.weight[(size_t)ch * 9 + t];
-                    q[(B.cin + 10) * 32 + c] = Ld.bias[ch];
-                    for (int co = 0; co < B.cout; ++co) q[(B.cin + 11) * 32 + c * B.cout + co] = Lp.weight[(size_t)co * B.hid + ch];
-                }
-                if (omni::upload(&B.blob, pk.data(), pk.size(), st)) { fusable = false; ok = false; break; }
-                B.mblob = nullptr; B.cop = ((B.cout + 31) / 32) * 32;
-                if (Le && B.cin % 4 == 0 && B.cop <= 128 && omni::vlad_mblock_smem(B.cin, B.cop, B.stride) <= 160 * 1024) {
-                    const int mb = 32 * (B.cin + 11 + B.cop);
-                    std::vector<float> mk((size_t)n_chunks * mb, 0.f);
-                    for (int ch = 0; ch < B.hid; ++ch) {
-                        float* q = mk.data() + (size_t)(ch / 32) * mb;
-                        const int c = ch % 32;
-                        for (int k = 0; k < B.cin; ++k) q[k * 32 + c] = Le->weight[(size_t)ch * B.cin + k];
-                        q[B.cin * 32 + c] = Le->bias[ch];
-                        for (int t = 0; t < 9; ++t) q[(B.cin + 1) * 32 + t * 32 + c] = Ld.weight[(size_t)ch * 9 + t];
-                        q[(B.cin + 10) * 32 + c] = Ld.bias[ch];
-                        for (int co = 0; co < B.cout; ++co) q[(B.cin + 11) * 32 + c * B.cop + co] = Lp.weight[(size_t)co * B.hid + ch];
-                    }
-                    if (omni::upload(&B.mblob, mk.data(), mk.size(), st)) { fusable = false; ok = false; break; }
-                }
-                B.sblob = nullptr;
-                if (Le && omni::vlad_sblock_supported(B.cin, B.hid, B.cout, B.stride)) {
-                    std::vector<char> sk(omni::vlad_sblock_blob_bytes(B.cin, B.hid, B.cout));
-                    omni::vlad_sblock_pack(B.cin, B.hid, B.cout, Le->weight, Le->bias, Ld.weight, Ld.bias, Lp.weight, sk.data());
-                    if (hipMalloc(&B.sblob, sk.size()) != hipSuccess || hipMemcpy(B.sblob, sk.data(), sk.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                        omni::set_error("device allocation failed"); fusable = false; ok = false; break;
-                    }
-                }
-                B.hblob = nullptr;
-                if (Le && omni::vlad_hblock_supported(B.cin, B.hid, B.cout, B.stride)) {
-                    std::vector<char> hk(omni::vlad_hblock_blob_bytes(B.cin, B.hid, B.cout));
-                    omni::vlad_hblock_pack(B.cin, B.hid, B.cout, Le->weight, Le->bias, Ld.weight, Ld.bias, Lp.weight, hk.data());
-                    if (hipMalloc(&B.hblob, hk.size()) != hipSuccess || hipMemcpy(B.hblob, hk.data(), hk.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                        omni::set_error("device allocation failed"); fusable = false; ok = false; break;
-                    }
-                }
-            }
+            if (omni::vlad_upload_block(v, B, e ? &w->layers[i - 1] : nullptr, w->layers[i], w->layers[i + 1])) { fusable = false; ok = false; break; }
             v->blocks.push_back(B);
+            v->bfacts.push_back(omni::vlad_block_facts(B));
             i += 2;
         }
-        v->fused = fusable && !v->cfg[omni::CFG_VLAD_UNFUSED];
-        v->mfma_late = v->cfg[omni::CFG_VLAD_MFMA] != 0;
-        // fused matrix-core block kernel for blocks whose input has at most this many pixels per image (0 disables).  Measured at 32 images
-        // (profiles/r02_vlad32_*): the ten 38x30 / 19x15 blocks take 451 us on it vs 502 us as three launches each; on the 75x60 ... 300x240
-        // blocks it is slower than the fp32-VALU fused kernel (one 8x8 tile per workgroup keeps 47-108 KB of LDS: 1-2 workgroups per CU
-        // and every phase of a chunk is a dependent chain behind a barrier -- waves wait 50 % of their life, MFMA-busy 14-18 %).  A
-        // split-fp16 variant (v_mfma_f32_32x32x16_f16, hi/lo operands: 5x less matrix time) measured SLOWER still (60 us per block): the
-        // matrix pipe is not what bounds these blocks, the per-workgroup latency chain is.
-        v->sblock = v->cfg[omni::CFG_VLAD_SBLOCK] != 0;
-        v->mblock_max_px = v->cfg[omni::CFG_VLAD_MBLOCK_PX];
-        if (v->cfg[omni::CFG_VLAD_MFMA_PX] > 0) v->mfma_max_px = v->cfg[omni::CFG_VLAD_MFMA_PX];
+        f.fusable = fusable;
     }
     if (ok) {
         v->hf = h; v->wf = wd; v->buf_elems = max_elems * max_batch;
-        std::vector<float> awT((size_t)v->Dm * v->K);
-        for (int k = 0; k < v->K; ++k) for (int d = 0; d < v->Dm; ++d) awT[(size_t)d * v->K + k] = w->assign_w[(size_t)k * v->Dm + d];
-        const size_t n_in = (size_t)v->K * v->Dm;
-        ok = !omni::upload(&v->assign_wT, awT.data(), awT.size(), st) && !omni::upload(&v->assign_b, w->assign_b, v->K, st) &&
-             !omni::upload(&v->clusters, w->clusters, n_in, st) && !omni::upload(&v->fc_w, w->fc_w, n_in * v->out_dim, st) &&
-             !omni::upload(&v->fc_b, w->fc_b, v->out_dim, st);
-        {   // FC on the matrix cores: W [out][n_in] -> [out / 32][n_in / 4][32 rows][4] (vlad_fc_mfma_kernel); OMNI_VLAD_FC_MFMA=0 keeps the VALU kernel
-            const bool want = v->cfg[omni::CFG_VLAD_FC_MFMA] != 0 && v->fused;
-            if (ok && want && v->out_dim % 32 == 0 && n_in % (4 * 2 * FCM_KY * 4) == 0) {
-                const size_t groups = n_in / 4;
-                std::vector<float> pk(n_in * (size_t)v->out_dim);
-                for (int j = 0; j < v->out_dim; ++j)
-                    for (size_t g = 0; g < groups; ++g)
-                        memcpy(&pk[(((size_t)(j / 32) * groups + g) * 32 + (j % 32)) * 4], &w->fc_w[(size_t)j * n_in + g * 4], 16);
-                ok = !omni::upload(&v->fc_wp, pk.data(), pk.size(), st) && hipMalloc((void**)&v->fc_part, (size_t)FCM_KY * 32 * v->out_dim * 4) == hipSuccess;
-                v->fc_mfma = ok;
-            }
-        }
-        {   // scratch of the hidden-layer split (OMNI_VLAD_MBLOCK_CPW = chunks per workgroup; 0 = no split)
-            v->mb_cpw = v->cfg[omni::CFG_VLAD_MBLOCK_CPW];             // measured: splitting does not pay (same total issue-bound work + a reduce launch per block)
-            size_t need = 0, max_tiles = 0;
-            for (auto& B : v->blocks) {
-                if (!B.mblob || B.hin * B.win > v->mblock_max_px) continue;
-                const size_t tiles = (size_t)omni::cdiv(B.wout, 8) * omni::cdiv(B.hout, 8) * max_batch;
-                const int n_chunks = (B.hid + 31) / 32, cpw = v->mb_cpw > 0 ? v->mb_cpw : n_chunks;
-                need = std::max(need, tiles * omni::cdiv(n_chunks, cpw) * 64 * B.cop * 4);
-                max_tiles = std::max(max_tiles, tiles);
-            }
-            if (ok && need && need <= ((size_t)1 << 30)) {
-                (void)max_tiles;
-                ok = hipMalloc((void**)&v->mb_partial, need) == hipSuccess;
-                v->mb_partial_bytes = ok ? need : 0;
-            }
-        }
-        for (int i = 0; i < 3 && ok; ++i) ok = hipMalloc((void**)&v->buf[i], v->buf_elems * 4) == hipSuccess;
-        if (ok) {
-            omni::vlad_plan_mask_skip(v);
-            for (auto& k : v->mskip)
-                ok = ok && hipMalloc((void**)&k.buf, (size_t)max_batch * k.oh * k.ow * k.oc * 4) == hipSuccess && hipMalloc(&k.vec, (size_t)k.oc * 4) == hipSuccess;
-        }
-        ok = ok && hipMalloc((void**)&v->assign, (size_t)max_batch * h * wd * v->K * 4) == hipSuccess &&
-             hipMalloc((void**)&v->vlad, (size_t)max_batch * n_in * 4) == hipSuccess &&
-             hipMalloc((void**)&v->out, (size_t)max_batch * v->out_dim * 4) == hipSuccess &&
-             hipMalloc((void**)&v->gray_stage, (size_t)max_batch * width * height) == hipSuccess;
-        if (!ok && !*omni_last_error()) omni::set_error("device allocation failed");
+        omni::vlad_replan(v);
+        ok = omni::vlad_create_head(v, w) == OMNI_OK;
     }
     if (!ok) { omni_vlad_destroy(v); return nullptr; }
     return v;
@@ -1559,12 +1522,7 @@ void omni_vlad_destroy(omni_vlad* v) {
     if (!v) return;
     (void)hipSetDevice(v->ctx->device);
     (void)hipStreamSynchronize(v->ctx->stream);
-    for (auto& L : v->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); }
-    for (auto& B : v->blocks) { if (B.blob) (void)hipFree(B.blob); if (B.mblob) (void)hipFree(B.mblob); if (B.hblob) (void)hipFree(B.hblob); if (B.sblob) (void)hipFree(B.sblob); }
-    void* ptrs[] = {v->mb_partial, v->fc_wp, v->fc_part, v->assign_wT, v->assign_b, v->clusters, v->fc_w, v->fc_b, v->buf[0], v->buf[1], v->buf[2], v->assign, v->vlad, v->out, v->gray_stage};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& k : v->mskip) { if (k.buf) (void)hipFree(k.buf); if (k.vec) (void)hipFree(k.vec); }
-    if (v->zero_gray) (void)hipFree(v->zero_gray);
+    v->mem.release_all();
     v->hstage.release();
     delete v;
 }
@@ -1582,14 +1540,15 @@ int64_t omni_vlad_pack_block(int cin, int hid, int cout, int stride, const float
 int omni_vlad_set_precision(omni_vlad* v, int precision) {
     OMNI_REQUIRE(v, OMNI_ERR_INVALID, "null handle");
     OMNI_REQUIRE(precision == OMNI_PREC_F32 || precision == OMNI_PREC_F16, OMNI_ERR_INVALID, "precision %d", precision);
+    std::lock_guard<std::mutex> lk(v->mu);
     if (precision == OMNI_PREC_F16) {
-        OMNI_REQUIRE(v->fused, OMNI_ERR_INVALID, "OMNI_PREC_F16 needs the fused block path (layer table not groupable into inverted-residual blocks)");
+        OMNI_REQUIRE(v->plan.fused, OMNI_ERR_INVALID, "OMNI_PREC_F16 needs the fused block path (layer table not groupable into inverted-residual blocks)");
         int n = 0;
-        for (auto& B : v->blocks) n += B.hblob != nullptr;
+        for (auto& B : v->bfacts) n += B.hblob;
         OMNI_REQUIRE(n > 0, OMNI_ERR_INVALID, "OMNI_PREC_F16: no block of this layer table has an fp16 kernel");
     }
-    std::lock_guard<std::mutex> lk(v->mu);
     v->prec = precision;
+    omni::vlad_replan(v);
     return OMNI_OK;
 }
 
@@ -1619,8 +1578,9 @@ int omni_vlad_fetch(omni_vlad* v, int batch, float* out) {
 
 int omni_vlad_mask_skip_layers(const omni_vlad* v, double* frac, int max_layers) {
     if (!v) return 0;
-    const int n = (int)v->mskip.size();
-    for (int i = 0; i < n && i < max_layers && frac; ++i) frac[i] = v->mskip[i].frac;
+    std::lock_guard<std::mutex> lk(v->mu);                  // (omni_vlad_set_precision makes the plan again)
+    const int n = v->plan.n_skip();
+    for (int i = 0; i < n && i < max_layers && frac; ++i) frac[i] = v->plan.skip[i].frac;
     return n;
 }
 

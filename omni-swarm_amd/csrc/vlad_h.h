@@ -32,7 +32,7 @@ struct VladSBlockArgs {
     unsigned m_img, m_tx;            // ceil(2^32 / tiles per image), ceil(2^32 / tiles per row): set by the launcher
     int dbg;                         // OMNI_VLAD_SB_DBG (timing ablations only, WRONG results): bit 0 no result stores, bit 1 no input prefetch
     unsigned long long* trace;       // OMNI_VLAD_SB_TRACE=1: s_memtime stamps of workgroup 0 (debug only), else nullptr
-    // the constant region of the fisheye mask (vlad.hip, vlad_plan_mask_skip): tile rows [sk_y0, sk_y1) x tile columns [sk_x0, sk_x0 + sk_w) hold one
+    // the constant region of the fisheye mask (vlad_plan.h, vlad_plan_mask_rects): tile rows [sk_y0, sk_y1) x tile columns [sk_x0, sk_x0 + sk_w) hold one
     // constant vector, written once, and are left out of the tile walk (sk_y1 <= sk_y0: every tile runs)
     int sk_y0 = 0, sk_y1 = 0, sk_x0 = 0, sk_w = 0;
     TileWalk walk{};                 // the tiles of an image that run (set by the launcher)

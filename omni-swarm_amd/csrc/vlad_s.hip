@@ -19,6 +19,7 @@
 #include "config.h"
 #include "common.h"
 #include "vlad_h.h"
+#include "vlad_plan.h"   // the tile shape, which the constant-region arithmetic of the plan reads too
 
 namespace omni {
 
@@ -41,7 +42,8 @@ template <int STRIDE, int CIN, int NT>
 struct SBlockCfg {
     static constexpr int S1 = (2 * CIN + 2 + 15) / 16, S2 = (CIN + 15) / 16;        // k-steps: [x_hi | x_lo | 1 1] and x_hi again (for We_lo)
     static constexpr int XS = S1 * 32 + 16;
-    static constexpr int TH = STRIDE == 1 ? 8 : 4, OPX = 8 * TH, NTN = OPX / 32;
+    static constexpr int TH = vlad_sblock_th(STRIDE), OPX = 8 * TH, NTN = OPX / 32;
+    static_assert(VLAD_SBLOCK_TW == 8, "the tiles of vlad_sblock_kernel are 8 pixels wide");
     static constexpr int RWX = 7 * STRIDE + 3, RHY = (TH - 1) * STRIDE + 3, R = RWX * RHY, RT = (R + 31) / 32, RP = RT * 32;
     // one wave per 32-pixel region tile -- but never more than FOUR waves: at the ~210-250 registers these kernels need, a SIMD holds two waves, a CU
     // eight; a five-wave workgroup (the stride-2 region: 17 x 9 = 153 pixels = 5 tiles) then fits ONCE per CU where a four-wave one fits twice
