@@ -67,6 +67,7 @@ typedef struct omni_index omni_index;
 typedef struct omni_cam omni_cam;
 typedef struct omni_shard omni_shard;
 typedef struct omni_flatten omni_flatten;
+typedef struct omni_resize omni_resize;
 
 int         omni_abi_version(void);
 const char* omni_last_error(void);
@@ -341,6 +342,18 @@ void          omni_flatten_destroy(omni_flatten* f);
 int64_t       omni_flatten_out_bytes(const omni_flatten* f);       /* bytes of all views of ONE source image */
 int           omni_flatten_enqueue_dev(omni_flatten* f, const uint8_t* src_dev, int src_stride, int batch, uint8_t* out_dev);   /* asynchronous */
 
+/* ---- camera-size frames -> network-size images: the cv::resize(input, _input, cv::Size(width, height)) of both reference engines (superpoint_tensorrt.cpp:123-125,
+ * mobilenetvlad_tensorrt.cpp:6-8; INTER_LINEAR on CV_8UC1), on the GPU.  The arithmetic is a fixed integer spec restated from OpenCV 3.4's own resize
+ * (csrc/resize_plan.h; OpenCV is un-vendored: parity unpinned): equal sizes copy, an exact 2x reduction on both axes is the rounded 2 x 2 mean (OpenCV's switch to
+ * INTER_AREA), anything else two-tap linear with 11-bit coefficients.  The object holds the tables of ONE source size -> destination size in HBM.  Source at
+ * least 2 wide, destination width a multiple of 4 (there is no tail path; the networks take multiples of 8), every side <= 32768.
+ * omni_resize_enqueue_dev: `batch` frames (u8, src_stride, frame i at + i * src_stride * src_height) -> images of dst_width x dst_height written back to back,
+ * rows packed, at out_dev (4-byte aligned) -- ready for omni_sp_enqueue_dev / omni_cam_enqueue_dev.  Asynchronous on the object's context. */
+omni_resize* omni_resize_create(omni_ctx* ctx, int src_width, int src_height, int dst_width, int dst_height);
+void         omni_resize_destroy(omni_resize* r);
+int          omni_resize_mode(const omni_resize* r);              /* 0 copy, 1 area 2x, 2 linear; -1 for NULL */
+int          omni_resize_enqueue_dev(omni_resize* r, const uint8_t* src_dev, int src_stride, int batch, uint8_t* out_dev);
+
 /* ---- key-frame frontend: the device work of LoopCam::on_flattened_images (swarm_loop/src/loop_cam.cpp:178-229;
  * generate_stereo_image_descriptor :341-523, extractor_img_desc_deepnet :525-585, match_HFNet_local_features :141-174)
  * as one asynchronous unit: SuperPoint on the 2*n_dirs images (up cameras first, then down), MobileNetVLAD on the n_dirs
@@ -390,7 +403,19 @@ int       omni_cam_enqueue_fisheye_dev(omni_cam* cam, omni_flatten* up, omni_fla
                                        int n_keyframes, int first_view, int fisheye_mask);
 int       omni_cam_enqueue_fisheye_host(omni_cam* cam, omni_flatten* up, omni_flatten* down, const uint8_t* up_host, const uint8_t* down_host, int src_stride,
                                         int n_keyframes, int first_view, int fisheye_mask);
-/* The first `bytes` of the handle's own input block -- the images the last omni_cam_enqueue_host / _host_parts / _fisheye_* unit fed to the networks, [image][H][W],
+/* A unit of RAW stereo-pinhole frames (CameraConfig::STEREO_PINHOLE: generate_stereo_image_descriptor for one direction, loop_cam.cpp:189-196; the left and right
+ * cameras take the roles of up and down): n_keyframes left frames and as many right frames of the CAMERA's size (u8, src_stride; frame i at + i * src_stride *
+ * source height); the resize to the networks' size (`resize`, above) runs inside the unit, on its SuperPoint stream, MobileNetVLAD starts behind the left camera,
+ * and no rows are blanked (:536 masks STEREO_FISHEYE only).  With one direction the unit's active size counts key frames: n_keyframes must equal it
+ * (omni_cam_set_active).  Refused before anything is enqueued: a mono handle, a resize object whose destination is not the networks' size or that lives on
+ * another device, src_stride below the source width, a unit in flight.  Keep `resize` alive until omni_cam_wait.
+ * _host: the frames in (pinned) host memory, untouched until omni_cam_wait returns: one asynchronous upload per camera into a staging buffer owned by the handle.
+ * _host_parts: each camera's frames as the concatenation of parts (part i: *_images[i] frames), as omni_cam_enqueue_host_parts. */
+int       omni_cam_enqueue_raw_dev(omni_cam* cam, omni_resize* resize, const uint8_t* left_dev, const uint8_t* right_dev, int src_stride, int n_keyframes);
+int       omni_cam_enqueue_raw_host(omni_cam* cam, omni_resize* resize, const uint8_t* left_host, const uint8_t* right_host, int src_stride, int n_keyframes);
+int       omni_cam_enqueue_raw_host_parts(omni_cam* cam, omni_resize* resize, const uint8_t* const* left, const int* left_images, int n_left,
+                                          const uint8_t* const* right, const int* right_images, int n_right, int src_stride);
+/* The first `bytes` of the handle's own input block -- the images the last omni_cam_enqueue_host / _host_parts / _fisheye_* / _raw_* unit fed to the networks, [image][H][W],
  * before the networks' own masking -- copied to out_host (blocking; for tests and for `show`-style debugging, loop_cam.cpp:471-515).  OMNI_ERR_INVALID while a unit
  * is pending, or when the last unit read a caller's buffer through omni_cam_enqueue_dev. */
 int       omni_cam_get_input(omni_cam* cam, uint8_t* out_host, int64_t bytes);

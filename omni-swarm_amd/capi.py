@@ -38,6 +38,7 @@ SYMBOLS = [
     "omni_trace_push", "omni_trace_pop", "omni_sp_set_perf", "omni_sp_last_stage_ms", "omni_bf_match", "omni_bf_match_multi", "omni_bf_match_batched_dev", "omni_config_count", "omni_config_describe", "omni_config_value", "omni_config_is_process_wide", "omni_cam_create", "omni_cam_create_mono", "omni_cam_destroy", "omni_cam_enqueue_dev", "omni_cam_enqueue_host", "omni_cam_enqueue_host_parts", "omni_cam_enqueue_fisheye_dev", "omni_cam_enqueue_fisheye_host", "omni_cam_get_input", "omni_cam_wait", "omni_cam_order_after", "omni_cam_set_active", "omni_cam_ready",
     "omni_shard_unique_id", "omni_shard_library_path", "omni_shard_create", "omni_shard_destroy", "omni_shard_ntotal", "omni_shard_preload_local", "omni_shard_step_batch_dev", "omni_shard_step_enqueue", "omni_shard_rows_consumed", "omni_shard_step_wait", "omni_shard_last_exchange_us",
     "omni_shard_search", "omni_flatten_create", "omni_flatten_destroy", "omni_flatten_out_bytes", "omni_flatten_enqueue_dev",
+    "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
 ]
 
 
@@ -171,6 +172,9 @@ def lib():
     sig("omni_cam_enqueue_fisheye_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int])
     sig("omni_cam_enqueue_fisheye_host", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int])
     sig("omni_cam_get_input", C.c_int, [_vp, _vp, C.c_int64])
+    sig("omni_cam_enqueue_raw_dev", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int])
+    sig("omni_cam_enqueue_raw_host", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int])
+    sig("omni_cam_enqueue_raw_host_parts", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int])
     sig("omni_cam_wait", C.c_int, [_vp, C.POINTER(_CamResult)])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
@@ -179,6 +183,10 @@ def lib():
     sig("omni_flatten_destroy", None, [_vp])
     sig("omni_flatten_out_bytes", C.c_int64, [_vp])
     sig("omni_flatten_enqueue_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp])
+    sig("omni_resize_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int])
+    sig("omni_resize_destroy", None, [_vp])
+    sig("omni_resize_mode", C.c_int, [_vp])
+    sig("omni_resize_enqueue_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp])
     sig("omni_config_count", C.c_int, [])
     sig("omni_config_describe", C.c_int, [C.c_int, C.POINTER(C.c_char_p), _ip, _ip, _ip, _ip, C.POINTER(C.c_char_p)])
     sig("omni_config_value", C.c_int, [C.c_char_p, _ip])
@@ -661,6 +669,56 @@ class Flatten:
         return res
 
 
+class Resize:
+    """omni_resize: camera-size frames -> network-size images, the cv::resize(INTER_LINEAR) both reference engines run in front of their networks, as the fixed
+    integer spec of csrc/resize_plan.h (mode: RESIZE_COPY / RESIZE_AREA2 / RESIZE_LINEAR).  One object per source size -> destination size."""
+
+    def __init__(self, ctx: Context, src_width: int, src_height: int, dst_width: int, dst_height: int):
+        self.ctx = ctx
+        self.src_w, self.src_h, self.dst_w, self.dst_h = src_width, src_height, dst_width, dst_height
+        self.h = lib().omni_resize_create(ctx.h, src_width, src_height, dst_width, dst_height)
+        if not self.h:
+            raise OmniError(f"omni_resize_create failed: {lib().omni_last_error().decode()}")
+        ctx._adopt(self)
+        self.mode = lib().omni_resize_mode(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().omni_resize_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def enqueue_dev(self, src_dev: int, src_stride: int, batch: int, out_dev: int):
+        _check(lib().omni_resize_enqueue_dev(self.h, src_dev, src_stride, batch, out_dev))
+
+    def __call__(self, frames_u8: np.ndarray, src_stride: int = 0) -> np.ndarray:
+        """[h,w] or [B,h,w] uint8 -> [B][dst_h][dst_w] (host convenience: upload, resize, download).  src_stride > w: the rows are laid out with that pitch
+        on the device (the padding bytes are 0xA5: a kernel that read them would show it)."""
+        g = np.ascontiguousarray(frames_u8, np.uint8)
+        if g.ndim == 2:
+            g = g[None]
+        assert g.shape[1:] == (self.src_h, self.src_w)
+        stride = src_stride or self.src_w
+        if stride != self.src_w:
+            padded = np.full((g.shape[0], self.src_h, stride), 0xA5, np.uint8)
+            padded[:, :, :self.src_w] = g
+            g = padded
+        src = self.ctx.to_device(g)
+        out = self.ctx.alloc(g.shape[0] * self.dst_h * self.dst_w)
+        try:
+            self.enqueue_dev(src, stride, g.shape[0], out)
+            return self.ctx.from_device(out, (g.shape[0], self.dst_h, self.dst_w), np.uint8)
+        finally:
+            self.ctx.free(src)
+            self.ctx.free(out)
+
+
+RESIZE_COPY, RESIZE_AREA2, RESIZE_LINEAR = 0, 1, 2
 SHARD_ID_BYTES = 128
 
 
@@ -859,8 +917,28 @@ class Cam:
         _check(lib().omni_cam_enqueue_fisheye_host(self.h, up.h, down.h, up_host.ctypes.data_as(_vp), down_host.ctypes.data_as(_vp), up_host.shape[2],
                                                    up_host.shape[0], first_view, int(fisheye_mask)))
 
+    def enqueue_raw_dev(self, resize: "Resize", left_dev: int, right_dev: int, src_stride: int, n_keyframes: int):
+        """raw stereo-pinhole frames in HBM, n_keyframes per camera, of the camera's size: resized inside the unit (omni_cam_enqueue_raw_dev)"""
+        _check(lib().omni_cam_enqueue_raw_dev(self.h, resize.h, left_dev, right_dev, src_stride, n_keyframes))
+
+    def enqueue_raw_host(self, resize: "Resize", left_host: np.ndarray, right_host: np.ndarray):
+        """left_host / right_host [n_keyframes][src_h][src_stride] u8, ideally pinned (Context.host_alloc); must stay untouched until wait() returns."""
+        for a in (left_host, right_host):
+            assert a.dtype == np.uint8 and a.ndim == 3 and a.flags.c_contiguous and a.shape == left_host.shape and a.shape[1] == resize.src_h
+        _check(lib().omni_cam_enqueue_raw_host(self.h, resize.h, left_host.ctypes.data_as(_vp), right_host.ctypes.data_as(_vp), left_host.shape[2], left_host.shape[0]))
+
+    def enqueue_raw_host_parts(self, resize: "Resize", left_parts, right_parts):
+        """the same from lists of [k_i][src_h][src_w] arrays per camera (omni_cam_enqueue_raw_host_parts)"""
+        def pack(parts):
+            for a in parts:
+                assert a.dtype == np.uint8 and a.ndim == 3 and a.flags.c_contiguous and a.shape[1:] == (resize.src_h, resize.src_w)
+            return (_vp * len(parts))(*[a.ctypes.data for a in parts]), (C.c_int * len(parts))(*[a.shape[0] for a in parts]), len(parts)
+        lp, ln, nl = pack(left_parts)
+        rp, rn, nr = pack(right_parts)
+        _check(lib().omni_cam_enqueue_raw_host_parts(self.h, resize.h, lp, ln, nl, rp, rn, nr, resize.src_w))
+
     def get_input(self) -> np.ndarray:
-        """[cams * n_active][H][W] u8: the handle's own input block as the last enqueue_host / enqueue_fisheye_* unit left it (not after enqueue_dev)"""
+        """[cams * n_active][H][W] u8: the handle's own input block as the last enqueue_host / enqueue_fisheye_* / enqueue_raw_* unit left it (not after enqueue_dev)"""
         out = np.empty((self.cams * self.n_active, self.sp.H, self.sp.W), np.uint8)
         _check(lib().omni_cam_get_input(self.h, out.ctypes.data_as(_vp), out.nbytes))
         return out

@@ -27,7 +27,7 @@ struct omni_cam {
     uint8_t* d_gray = nullptr;        // staging for omni_cam_enqueue_host: the key frame's images, rows packed to `width`
     size_t d_gray_bytes = 0;
     size_t input_bytes = 0;           // what the last unit read from d_gray (0: it read a caller's buffer): omni_cam_get_input
-    uint8_t* d_raw = nullptr;         // staging for omni_cam_enqueue_fisheye_host: the raw frames of the up cameras, then of the down cameras
+    uint8_t* d_raw = nullptr;         // staging for omni_cam_enqueue_fisheye_host / _raw_host: the raw frames of the up (left) cameras, then of the down (right) cameras
     size_t d_raw_bytes = 0;
     bool pending = false;
     std::mutex mu;
@@ -234,6 +234,82 @@ int omni_cam_enqueue_fisheye_host(omni_cam* c, omni_flatten* up, omni_flatten* d
     omni::TraceRange trace_range("omni_cam_enqueue_fisheye_host (upload + flatten + unit)");
     std::lock_guard<std::mutex> lk(c->mu);
     return cam_fisheye_locked(c, up, down, nullptr, nullptr, up_host, down_host, src_stride, n_keyframes, first_view, fisheye_mask);
+}
+
+// A key frame's two RAW stereo-pinhole frames (CameraConfig::STEREO_PINHOLE: generate_stereo_image_descriptor for ONE direction, loop_cam.cpp:189-196) of the
+// camera's size instead of network-size images: the resize both reference engines run on the host in front of their networks (resize.hip) runs inside the unit,
+// on the SuperPoint stream, and writes the unit's own input block.  With one direction the unit's active size counts key frames: n_keyframes left frames (the
+// "up" role) and as many right frames.  The tables are read on the unit's streams, never on the resize object's own: keep it alive until omni_cam_wait.
+static int cam_raw_check(omni_cam* c, const omni_resize* r, int src_stride, int n_keyframes) {
+    OMNI_REQUIRE(c->cams == 2, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: a mono handle has no left / right camera pair");
+    OMNI_REQUIRE(r->dst_w == c->W && r->dst_h == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: the resize object makes %dx%d images but the networks were created for %dx%d",
+                 r->dst_w, r->dst_h, c->W, c->H);
+    OMNI_REQUIRE(r->ctx->device == c->c1->device, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: resize tables on device %d, the unit on device %d", r->ctx->device, c->c1->device);
+    OMNI_REQUIRE(n_keyframes == c->n, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: %d key frames for a unit of %d (omni_cam_set_active)", n_keyframes, c->n);
+    OMNI_REQUIRE(src_stride >= r->src_w, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: stride %d for frames %d wide", src_stride, r->src_w);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_enqueue_raw with a unit in flight (omni_cam_wait first)");
+    return OMNI_OK;
+}
+
+// left camera first and MobileNetVLAD behind it, then the right camera: the order of cam_fisheye_locked.  n_left > 0: the frames are in host memory, each camera's
+// n_keyframes frames the concatenation of its parts (part i: images[i] frames, src_stride); they go up into d_raw, one asynchronous copy per part, in front of
+// the camera's resize
+static int cam_raw_locked(omni_cam* c, omni_resize* r, const uint8_t* left_dev, const uint8_t* right_dev, const uint8_t* const* left, const int* left_images, int n_left,
+                          const uint8_t* const* right, const int* right_images, int n_right, int src_stride, int n_keyframes) {
+    int rc;
+    if ((rc = cam_raw_check(c, r, src_stride, n_keyframes))) return rc;
+    (void)hipSetDevice(c->c1->device);
+    const size_t half = (size_t)c->n * c->W * c->H, frame = (size_t)src_stride * r->src_h;
+    auto raw_bytes = [&](int frames) { return ((size_t)frames * r->src_h - 1) * src_stride + r->src_w; };      // (the last row may end at its width)
+    if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, 2 * half))) return rc;
+    const size_t right_at = (raw_bytes(n_keyframes) + 255) & ~(size_t)255;
+    if (n_left) {
+        if ((rc = cam_staging(c, c->d_raw, c->d_raw_bytes, right_at + raw_bytes(n_keyframes)))) return rc;
+        left_dev = c->d_raw; right_dev = c->d_raw + right_at;
+    }
+    hipStream_t s1 = c->c1->stream;
+    auto upload = [&](uint8_t* dst, const uint8_t* const* parts, const int* images, int n_parts) -> hipError_t {
+        for (int i = 0, at = 0; i < n_parts; at += images[i], ++i) {
+            const hipError_t e = hipMemcpyAsync(dst + at * frame, parts[i], raw_bytes(images[i]), hipMemcpyHostToDevice, s1);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    OMNI_HIP_TRY(upload(c->d_raw, left, left_images, n_left));
+    if ((rc = omni::resize_unit_launch(r, s1, left_dev, src_stride, n_keyframes, c->d_gray))) return rc;
+    OMNI_HIP_TRY(hipEventRecord(c->e_up, s1));
+    OMNI_HIP_TRY(hipStreamWaitEvent(c->c2->stream, c->e_up, 0));
+    OMNI_HIP_TRY(upload(c->d_raw + right_at, right, right_images, n_right));
+    if ((rc = omni::resize_unit_launch(r, s1, right_dev, src_stride, n_keyframes, c->d_gray + half))) return rc;
+    return cam_enqueue_locked(c, c->d_gray, c->W, 0);                         // loop_cam.cpp:536 blanks rows for STEREO_FISHEYE only
+}
+
+int omni_cam_enqueue_raw_dev(omni_cam* c, omni_resize* r, const uint8_t* left_dev, const uint8_t* right_dev, int src_stride, int n_keyframes) {
+    OMNI_REQUIRE(c && r && left_dev && right_dev, OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("omni_cam_enqueue_raw_dev (resize + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return cam_raw_locked(c, r, left_dev, right_dev, nullptr, nullptr, 0, nullptr, nullptr, 0, src_stride, n_keyframes);
+}
+
+int omni_cam_enqueue_raw_host(omni_cam* c, omni_resize* r, const uint8_t* left_host, const uint8_t* right_host, int src_stride, int n_keyframes) {
+    OMNI_REQUIRE(c && r && left_host && right_host, OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("omni_cam_enqueue_raw_host (upload + resize + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return cam_raw_locked(c, r, nullptr, nullptr, &left_host, &n_keyframes, 1, &right_host, &n_keyframes, 1, src_stride, n_keyframes);
+}
+
+// the same from segments of host memory (what KeyframePipeline::run needs to cut units of its choice out of blocks laid out for another unit size, as
+// omni_cam_enqueue_host_parts): the totals of both cameras' parts are the unit's active size
+int omni_cam_enqueue_raw_host_parts(omni_cam* c, omni_resize* r, const uint8_t* const* left, const int* left_images, int n_left, const uint8_t* const* right,
+                                    const int* right_images, int n_right, int src_stride) {
+    OMNI_REQUIRE(c && r && left && left_images && right && right_images && n_left > 0 && n_right > 0, OMNI_ERR_INVALID, "null argument");
+    int nl = 0, nr = 0;
+    for (int i = 0; i < n_left; ++i) { OMNI_REQUIRE(left[i] && left_images[i] > 0, OMNI_ERR_INVALID, "omni_cam_enqueue_raw_host_parts: empty part"); nl += left_images[i]; }
+    for (int i = 0; i < n_right; ++i) { OMNI_REQUIRE(right[i] && right_images[i] > 0, OMNI_ERR_INVALID, "omni_cam_enqueue_raw_host_parts: empty part"); nr += right_images[i]; }
+    OMNI_REQUIRE(nl == nr, OMNI_ERR_INVALID, "omni_cam_enqueue_raw_host_parts: %d left frames, %d right frames", nl, nr);
+    omni::TraceRange trace_range("omni_cam_enqueue_raw_host_parts (upload + resize + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return cam_raw_locked(c, r, nullptr, nullptr, left, left_images, n_left, right, right_images, n_right, src_stride, nl);
 }
 
 // the handle's own input block as the last unit's networks read it (the fisheye mask is applied inside the networks, not here: a unit of flattened views shows

@@ -175,6 +175,23 @@ int flatten_unit_launch(const omni_flatten* f, hipStream_t stream, const uint8_t
                         int height, int fisheye_mask, uint8_t* out_dev);
 }  // namespace omni
 
+// omni_resize (resize.hip): the four tables of one source size -> destination size (resize_plan.h) in HBM, immutable after creation.  cam.hip reads the sizes
+// to check a unit of raw stereo frames and hands the object to resize_unit_launch
+struct omni_resize {
+    omni_ctx* ctx = nullptr;
+    int mode = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0;
+    uint8_t* tables = nullptr;             // one allocation: xofs int32 [W] | ialpha int16 [W][2] | yofs int32 [H] | ibeta int16 [H][2], each part on 16 bytes
+    const int32_t *xofs = nullptr, *yofs = nullptr;
+    const int16_t *ialpha = nullptr, *ibeta = nullptr;
+    std::mutex mu;
+};
+
+namespace omni {
+// resize.hip: n_images frames (u8, src_stride, frame i at + i * src_stride * source height) -> n_images images of the object's destination size, rows packed,
+// back to back at out_dev (4-byte aligned).  Asynchronous on `stream`, which need not be the object's own.
+int resize_unit_launch(const omni_resize* r, hipStream_t stream, const uint8_t* src_dev, int src_stride, int n_images, uint8_t* out_dev);
+}  // namespace omni
+
 // ---- 64-bit sortable keys -------------------------------------------------------------------------------------
 // key = (orderable(score) << 32) | (0xFFFFFFFF - id): descending key order == (score desc, id asc).
 __host__ __device__ static inline uint32_t omni_f32_orderable(float f) {

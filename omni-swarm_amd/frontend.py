@@ -83,6 +83,16 @@ class LoopCam:
         self.cam.enqueue_fisheye_host(fl[0], fl[1], raw[0], raw[1], len(fl[0].shapes) - self.cam.n_active, self.fisheye)
         return self.fetch()
 
+    def on_stereo_images(self, left_raw: np.ndarray, right_raw: np.ndarray, resize: capi.Resize) -> dict:
+        """The blocking call for a STEREO_PINHOLE key frame (generate_stereo_image_descriptor for one direction, loop_cam.cpp:189-196): the two RAW frames
+        [src_h][src_w] uint8 of the camera's size -- or [k][src_h][src_w] for the k key frames of the unit's active size -- are resized to the networks' size
+        inside the unit (omni_cam_enqueue_raw_host), left = up, right = down, no rows blanked.  Returns what on_flattened_images returns for the resized images
+        on a LoopCam made with fisheye=False."""
+        raw = [np.ascontiguousarray(r, np.uint8) for r in (left_raw, right_raw)]
+        raw = [r[None] if r.ndim == 2 else r for r in raw]
+        self.cam.enqueue_raw_host(resize, raw[0], raw[1])
+        return self.fetch()
+
     def on_flattened_images(self, up: np.ndarray, down: np.ndarray) -> dict:
         """Host-pointer convenience (the reference's blocking call): up/down [n_dirs][H][W] uint8."""
         g = np.ascontiguousarray(np.concatenate([up, down]), np.uint8)

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "fisheye_flatten.hpp"
+#include "host_capi_types.hpp"
 #include "keyframe_pipeline.hpp"
 #include "loop_net_wire.hpp"
 #include "swarm_loop_params.hpp"
@@ -16,7 +17,6 @@ thread_local std::string g_err;
 
 extern "C" {
 
-struct omni_pipeline { omni::KeyframePipeline* p; };
 
 const char* omni_pipeline_last_error(void) { return g_err.c_str(); }
 
@@ -255,7 +255,9 @@ omni_pipeline* omni_pipeline_create_from_launch(int device, const char* launch_x
         }
         const omni::SwarmLoopParams p = omni::SwarmLoopParams::from_launch(launch_xml, node_name ? node_name : "swarm_loop", av);
         if (p.camera_configuration != 1 && p.camera_configuration != 2)
-            throw std::runtime_error("camera_configuration " + std::to_string(p.camera_configuration) + ": STEREO_FISHEYE (1) and PINHOLE_DEPTH (2) are built");
+            throw std::runtime_error("camera_configuration " + std::to_string(p.camera_configuration) + ": a launch file configures STEREO_FISHEYE (1) and PINHOLE_DEPTH (2); "
+                                     "STEREO_PINHOLE (0) needs what no launch file of the node carries -- the camera's frame size and the rig's two extrinsics: "
+                                     "omni_pipeline_create_stereo_pinhole (omni_host_stereo.h)");
         omni::KeyframePipeline::Config c;
         p.to_pipeline_config(c);
         c.device = device; c.sp_weights = sp_weights; c.vlad_weights = vlad_weights; c.precision = precision; c.microbatch = microbatch; c.pipelines = pipelines;

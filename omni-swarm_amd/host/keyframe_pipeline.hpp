@@ -85,14 +85,36 @@ public:
         // (2) max_wait_ms: a partly filled micro-batch older than this is sent as it is by the next push_keyframe() or poll() (< 0: never -- only flush()).
         bool dispatch_when_idle = true;
         double max_wait_ms = 50.0;
-        bool mono() const { return camera_configuration == 2; }
-        int dirs() const { return mono() ? 1 : 4; }
+        // STEREO_PINHOLE = 0 (loop_cam.cpp:189-196: generate_stereo_image_descriptor for ONE direction): a key frame is a left and a right image, the left camera in
+        // the role of the up camera (both networks) and the right one in the role of the down camera (SuperPoint, stereo match), not blanked, MAX_DIRS = 1, the
+        // query image is direction 0.  src_width x src_height > 0: the frames arrive at the CAMERA's size and are resized to width x height inside the unit
+        // (omni_cam_enqueue_raw_*: the cv::resize of superpoint_tensorrt.cpp:123-125 on the GPU); 0: they have the networks' size already.  Key points stay in
+        // network-image coordinates and are lifted as they are (loop_cam.cpp:558-569): fx fy cx cy are those of the width x height image.
+        int src_width = 0, src_height = 0;
+        // body -> camera of the two cameras (xyz + quaternion wxyz; swarm_loop.cpp:294-306 body_T_cam0 / body_T_cam1).  Defaults: the forward camera of
+        // PINHOLE_DEPTH, and the same displaced by stereo_baseline along its own x axis (to its right)
+        bool have_stereo_extrinsics = false;
+        double left_extrinsic[7] = {0, 0, 0, 1, 0, 0, 0}, right_extrinsic[7] = {0, 0, 0, 1, 0, 0, 0};
+        // what the camera configuration decides, one question each
+        bool stereo() const { return camera_configuration != 2; }      // two cameras per direction: up / down (left / right), stereo match, triangulated landmarks
+        int dirs() const { return camera_configuration == 1 ? 4 : 1; }
+        bool masked() const { return camera_configuration == 1; }       // loop_cam.cpp:536 blanks rows for STEREO_FISHEYE only; its query image is direction 1
+        bool raw() const { return camera_configuration == 0 && src_width > 0; }
+        int in_width() const { return raw() ? src_width : width; }      // the size of the images a caller hands over
+        int in_height() const { return raw() ? src_height : height; }
     };
 
     // units in flight when the caller does not say: fp16's small-grid tails (NMS, sampling, matcher, MobileNetVLAD's last blocks) are filled by the next
     // units' kernels, so four pay; the fp32-class modes are CU-filling convolutions end to end and gain nothing beyond two
     static int default_pipelines(int precision) { return precision == OMNI_PREC_F16 ? 4 : 2; }
-    static Config resolved(Config c) { if (c.pipelines <= 0) c.pipelines = default_pipelines(c.precision); return c; }
+    static Config resolved(Config c) {
+        if (c.camera_configuration < 0 || c.camera_configuration > 2)
+            throw std::runtime_error("KeyframePipeline: camera_configuration must be 0 (STEREO_PINHOLE), 1 (STEREO_FISHEYE) or 2 (PINHOLE_DEPTH)");
+        if ((c.src_width > 0) != (c.src_height > 0) || (c.src_width > 0 && c.camera_configuration != 0))
+            throw std::runtime_error("KeyframePipeline: src_width x src_height (frames resized inside the unit) belongs to camera_configuration 0 (STEREO_PINHOLE), both or neither");
+        if (c.pipelines <= 0) c.pipelines = default_pipelines(c.precision);
+        return c;
+    }
     int pipelines() const { return cfg_.pipelines; }
 
     explicit KeyframePipeline(const Config& c0) : KeyframePipeline(resolved(c0), 0) {}
@@ -100,8 +122,7 @@ private:
     KeyframePipeline(const Config& c, int) : cfg_(c), index_ctx_(c.device, true), det_(index_ctx_, c.self_id, c.storage) {
         det_.INNER_PRODUCT_THRES = c.inner_product_thres; det_.INIT_MODE_PRODUCT_THRES = c.init_mode_product_thres;
         det_.MATCH_INDEX_DIST = c.match_index_dist; det_.MIN_LOOP_NUM = c.min_loop_num; det_.MIN_DIRECTION_LOOP = c.min_direction_loop;
-        if (c.camera_configuration != 1 && c.camera_configuration != 2) throw std::runtime_error("KeyframePipeline: camera_configuration must be 1 (STEREO_FISHEYE) or 2 (PINHOLE_DEPTH)");
-        det_.stereo_fisheye = !c.mono();
+        det_.stereo_fisheye = c.masked();
         geo_.MAX_DIRS = c.dirs();
         for (int p = 0; p < c.pipelines; ++p) lanes_.push_back(std::make_unique<Lane>(c, c.microbatch));
         if (c.geometry) {
@@ -265,12 +286,16 @@ public:
     // extrinsics of the virtual pinhole views of the stacked fisheye pair: direction d looks along the body x axis rotated by 90 deg * d,
     // the up / down cameras sit +- baseline/2 along body z (camera axes: x right, y down, z forward)
     geom::Pose view_extrinsic(int direction, bool up) const {
-        if (cfg_.mono()) {                                  // the one forward-looking camera, at the body origin
+        if (cfg_.camera_configuration == 0 && cfg_.have_stereo_extrinsics) {      // the rig's own (set_stereo_extrinsics): left = up, right = down
+            const double* e = up ? cfg_.left_extrinsic : cfg_.right_extrinsic;
+            return {{e[0], e[1], e[2]}, {e[3], e[4], e[5], e[6]}};
+        }
+        if (cfg_.dirs() == 1) {                             // the one forward-looking camera, at the body origin; STEREO_PINHOLE's right camera stereo_baseline to its right
             geom::Mat3 R;
             R.m[0][0] = 0;  R.m[0][1] = 0;  R.m[0][2] = 1;
             R.m[1][0] = -1; R.m[1][1] = 0;  R.m[1][2] = 0;
             R.m[2][0] = 0;  R.m[2][1] = -1; R.m[2][2] = 0;
-            return {{0, 0, 0}, geom::quat_from_R(R)};
+            return {{0, (up || !cfg_.stereo()) ? 0.0 : -cfg_.stereo_baseline, 0}, geom::quat_from_R(R)};      // (the camera's x axis is the body's -y)
         }
         const double yaw = M_PI / 2 * direction, c = std::cos(yaw), s = std::sin(yaw);
         geom::Mat3 R;            // Rz(yaw) * [[0,0,1],[-1,0,0],[0,-1,0]]
@@ -278,6 +303,17 @@ public:
         R.m[1][0] = -c; R.m[1][1] = 0;  R.m[1][2] = s;
         R.m[2][0] = 0;  R.m[2][1] = -1; R.m[2][2] = 0;
         return {{0, 0, (up ? 0.5 : -0.5) * cfg_.stereo_baseline}, geom::quat_from_R(R)};
+    }
+
+    // STEREO_PINHOLE: the rig's two extrinsics (body -> camera, xyz + quaternion wxyz; swarm_loop.cpp:294-306) instead of the defaults.  Every key frame's
+    // messages carry them, so they are fixed before the first key frame
+    void set_stereo_extrinsics(const double* left7, const double* right7) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (cfg_.camera_configuration != 0) throw std::runtime_error("set_stereo_extrinsics: camera_configuration is not 0 (STEREO_PINHOLE)");
+        if (first_keyframe_seen_) throw std::runtime_error("set_stereo_extrinsics after the first key frame");
+        if (!left7 || !right7) throw std::invalid_argument("set_stereo_extrinsics: null argument");
+        std::copy(left7, left7 + 7, cfg_.left_extrinsic); std::copy(right7, right7 + 7, cfg_.right_extrinsic);
+        cfg_.have_stereo_extrinsics = true;
     }
 
     LoopDetectorCore& detector() { return det_; }
@@ -314,12 +350,14 @@ public:
     }
 
     // n_keyframes key frames through the whole hot path.  pool[e] = one micro-batch of images in (pinned) host memory,
-    // [up cameras of the MB frames (4 each) | down cameras of the MB frames] (PINHOLE_DEPTH: the MB gray images), u8, rows packed; micro-batch s uses pool[(first_slot + s) %
+    // [up cameras of the MB frames (4 each) | down cameras of the MB frames] (PINHOLE_DEPTH: the MB gray images; STEREO_PINHOLE: [the MB left frames | the MB right
+    // frames], at the camera's size when Config::src_width is set), u8, rows packed; micro-batch s uses pool[(first_slot + s) %
     // n_pool].  When n_keyframes is not a multiple of the micro-batch the last rem frames run as their own, smaller unit from `tail`
     // (same layout for rem frames): EXACTLY n_keyframes key frames are processed.  from_host: upload inside the loop
     // (omni_cam_enqueue_host); otherwise the pool entries are device pointers.  Returns the number of loop candidates found.
     int run(int n_keyframes, int64_t first_msg_id, const uint8_t* const* pool, int n_pool, int first_slot, const uint8_t* tail, bool from_host) {
         if (open_ || !stream_pending_.empty()) throw std::runtime_error("run: key frames pushed through push_keyframe are still open -- flush() first");
+        if (cfg_.camera_configuration == 0 && n_keyframes > 0) first_keyframe_seen_ = true;
         const int MB = cfg_.microbatch, nd = cfg_.dirs();
         const int full = n_keyframes / MB, rem = n_keyframes % MB;
         // The units of this call.  Host blocks can be cut anywhere (a unit's upload is a list of segments: omni_cam_enqueue_host_parts), so a run that is not a
@@ -341,7 +379,7 @@ public:
         const int n_units = (int)sizes.size();
         const int fifo = fifo_cfg_ >= 0 ? fifo_cfg_ : ((cfg_.precision != OMNI_PREC_F16 || n_units <= (int)lanes_.size()) ? 1 : 0);
         last_fifo_ = fifo;
-        const size_t img = (size_t)cfg_.width * cfg_.height;
+        const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         // key frame f of the call: its block (pool entry or the tail), the block's frame count, its index inside
         auto block_of = [&](int f, const uint8_t*& base, int& cnt, int& idx) {
             const int e = f / MB;
@@ -368,14 +406,19 @@ public:
                     block_of(f, base, cnt, idx);
                     const int take = std::min(cnt - idx, f0 + m - f);
                     up.push_back(base + (size_t)idx * nd * img); upn.push_back(take * nd);
-                    if (!cfg_.mono()) { down.push_back(base + ((size_t)cnt + idx) * nd * img); downn.push_back(take * nd); }
+                    if (cfg_.stereo()) { down.push_back(base + ((size_t)cnt + idx) * nd * img); downn.push_back(take * nd); }
                     f += take;
                 }
-                lane->cam.enqueue_host_parts(up, upn, down, downn, !cfg_.mono());
+                if (cfg_.raw()) lane->cam.enqueue_raw_host_parts(lane->resize->handle(), up, upn, down, downn, cfg_.src_width);
+                else lane->cam.enqueue_host_parts(up, upn, down, downn, cfg_.masked());
             } else {
                 const uint8_t* src = s < full ? pool[(first_slot + s) % n_pool] : tail;
-                if (from_host) lane->cam.enqueue_host(src, cfg_.width, !cfg_.mono());       // loop_cam.cpp:536: only STEREO_FISHEYE blanks rows
-                else lane->cam.enqueue_dev(src, cfg_.width, !cfg_.mono());
+                if (cfg_.raw()) {                                                             // the block's left frames, then its right frames, at the camera's size
+                    if (from_host) lane->cam.enqueue_raw_host(lane->resize->handle(), src, src + (size_t)want * img, cfg_.src_width, want);
+                    else lane->cam.enqueue_raw_dev(lane->resize->handle(), src, src + (size_t)want * img, cfg_.src_width, want);
+                }
+                else if (from_host) lane->cam.enqueue_host(src, cfg_.width, cfg_.masked());   // loop_cam.cpp:536: only STEREO_FISHEYE blanks rows
+                else lane->cam.enqueue_dev(src, cfg_.width, cfg_.masked());
             }
             host_ms_[0] += since(lane->t_enqueue);
             omni_trace_pop();
@@ -410,7 +453,8 @@ public:
     void sync() { for (auto& l : lanes_) l->sync(); for (auto& t : tail_lanes_) t.second->sync(); check(omni_ctx_sync(index_ctx_.get()), "sync"); }
 
     // one key frame as SwarmLoop::VIOKF_callback hands it on (swarm_loop.cpp:140-170): the flattened views -- images[0..dirs) = up cameras, images[dirs..2*dirs)
-    // = down cameras (PINHOLE_DEPTH: the one gray image), each height rows of `stride` bytes -- the key-frame id and stamp (StereoFrame::keyframe_id,
+    // = down cameras (PINHOLE_DEPTH: the one gray image; STEREO_PINHOLE: images[0] = the left frame, images[1] = the right frame, of the camera's size when
+    // Config::src_width is set), each Config::in_height() rows of `stride` bytes -- the key-frame id and stamp (StereoFrame::keyframe_id,
     // ::stamp), VIO's pose, and prevent_adding_db (:156: a non-key frame that moved less than min_movement_keyframe is matched but not added);
     // depth: PINHOLE_DEPTH's 16-bit depth image (rows packed), borrowed until the key frame's unit is finished
     struct KeyframeIn {
@@ -429,10 +473,11 @@ public:
     int push_keyframe(const KeyframeIn& k) {
         std::lock_guard<std::mutex> lk(intake_mu_);
         if (shard_) throw std::runtime_error("push_keyframe: the sharded database is driven through run()");
-        if (!k.images || k.stride < cfg_.width) throw std::invalid_argument("push_keyframe: no images / a row stride below the image width");
-        const int MB = cfg_.microbatch, nd = cfg_.dirs(), cams = cfg_.mono() ? 1 : 2;
+        if (!k.images || k.stride < cfg_.in_width()) throw std::invalid_argument("push_keyframe: no images / a row stride below the image width");
+        const int MB = cfg_.microbatch, nd = cfg_.dirs(), cams = cfg_.stereo() ? 2 : 1;
         for (int i = 0; i < cams * nd; ++i) if (!k.images[i]) throw std::invalid_argument("push_keyframe: a null image pointer");
-        const size_t img = (size_t)cfg_.width * cfg_.height;
+        const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
+        if (cfg_.camera_configuration == 0) first_keyframe_seen_ = true;      // (set_stereo_extrinsics is refused from here on)
         int hits = carried_hits_; carried_hits_ = 0;
         // whatever throws below: the candidates counted so far are not lost -- they go back into carried_hits_ and the next call returns them
         struct Carry { int& hits; int& carried; bool ok = false; ~Carry() { if (!ok) carried += hits; } } carry{hits, carried_hits_};
@@ -457,7 +502,7 @@ public:
             for (int d = 0; d < nd; ++d) {
                 uint8_t* dst = open_->stage + ((size_t)c * nd * MB + (size_t)nd * m + d) * img;
                 const uint8_t* src = k.images[c * nd + d];
-                for (int y = 0; y < cfg_.height; ++y) std::memcpy(dst + (size_t)y * cfg_.width, src + (size_t)y * k.stride, (size_t)cfg_.width);
+                for (int y = 0; y < cfg_.in_height(); ++y) std::memcpy(dst + (size_t)y * cfg_.in_width(), src + (size_t)y * k.stride, (size_t)cfg_.in_width());
             }
         SlotMeta sm; sm.msg_id = k.msg_id; sm.stamp = k.stamp; sm.pose = k.pose_drone; sm.prevent_adding_db = k.prevent_adding_db; sm.depth = k.depth;
         open_->meta.push_back(sm);
@@ -515,11 +560,12 @@ private:
     struct Lane {                                      // one micro-batch in flight: its own streams, networks and result block
         Lane(const Config& c, int mb_)
             : mb(mb_), sp_ctx(c.device), vlad_ctx(c.device),
-              sp(sp_ctx, c.sp_weights, c.pca_comp, c.pca_mean, c.width, c.height, c.thres, c.max_num, false, c.precision, (c.mono() ? 1 : 8) * mb_),
+              sp(sp_ctx, c.sp_weights, c.pca_comp, c.pca_mean, c.width, c.height, c.thres, c.max_num, false, c.precision, (c.stereo() ? 2 : 1) * c.dirs() * mb_),
               one_stream(cfg_int("OMNI_PIPELINE_ONE_STREAM") != 0),
               vlad(one_stream ? sp_ctx : vlad_ctx, c.vlad_weights, c.width, c.height, false, c.dirs() * mb_),
-              cam(sp_ctx, sp, one_stream ? sp_ctx : vlad_ctx, vlad, c.dirs() * mb_, c.max_num, c.width, c.height, c.mono()) {
+              cam(sp_ctx, sp, one_stream ? sp_ctx : vlad_ctx, vlad, c.dirs() * mb_, c.max_num, c.width, c.height, !c.stereo()) {
             check(omni_vlad_dev_output(vlad.handle(), &rows_dev), "omni_vlad_dev_output");
+            if (c.raw()) resize = std::make_unique<ResizeHIP>(sp_ctx, c.src_width, c.src_height, c.width, c.height);
             cur = mb_;
         }
         void sync() { check(omni_ctx_sync(sp_ctx.get()), "sync"); check(omni_ctx_sync(vlad_ctx.get()), "sync"); }
@@ -536,6 +582,7 @@ private:
         Context& vlad_stream_ctx() { return one_stream ? sp_ctx : vlad_ctx; }
         Swarm::MobileNetVLADHIP vlad;
         LoopCamHIP cam;
+        std::unique_ptr<ResizeHIP> resize;             // STEREO_PINHOLE with camera-size frames: the tables of the resize that runs inside the unit
         const float* rows_dev = nullptr;
     };
 
@@ -546,12 +593,13 @@ private:
         Lane* u = open_;
         open_ = nullptr;
         const int MB = cfg_.microbatch, nd = cfg_.dirs(), rem = (int)u->meta.size();
-        const size_t img = (size_t)cfg_.width * cfg_.height;
+        const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         try {
-            if (rem < MB && !cfg_.mono()) std::memmove(u->stage + (size_t)nd * rem * img, u->stage + (size_t)nd * MB * img, (size_t)nd * rem * img);
+            if (rem < MB && cfg_.stereo()) std::memmove(u->stage + (size_t)nd * rem * img, u->stage + (size_t)nd * MB * img, (size_t)nd * rem * img);
             if (u->cur != rem) { u->cam.set_active(nd * rem); u->cur = rem; }
             chain(u, fifo_cfg_ >= 0 ? fifo_cfg_ : (cfg_.precision == OMNI_PREC_F16 ? 0 : 1));
-            u->cam.enqueue_host(u->stage, cfg_.width, !cfg_.mono());
+            if (cfg_.raw()) u->cam.enqueue_raw_host(u->resize->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.src_width, rem);
+            else u->cam.enqueue_host(u->stage, cfg_.width, cfg_.masked());
         } catch (...) { u->meta.clear(); throw; }
         stream_pending_.push_back(u);
     }
@@ -629,7 +677,7 @@ private:
             // collected when the NEXT micro-batch gets here (or at the end of run()): meanwhile the host enqueues the next CNN unit
             int hits = collect_exchange();
             const int k = LoopDetectorCore::SEARCH_NEAREST_NUM + cfg_.match_index_dist;
-            check(omni_shard_step_enqueue(shard_, lane.cur, cfg_.dirs(), lane.rows_dev, cfg_.mono() ? 0 : 1, k), "omni_shard_step_enqueue");
+            check(omni_shard_step_enqueue(shard_, lane.cur, cfg_.dirs(), lane.rows_dev, cfg_.masked() ? 1 : 0, k), "omni_shard_step_enqueue");      // the query image: direction 1 of a fisheye key frame, else 0
             pend_lane_ = &lane; pend_mb_ = lane.cur; pend_base_ = omni_shard_ntotal(shard_);
             return hits;
         }
@@ -659,7 +707,7 @@ private:
                 // extractor_img_desc_deepnet (loop_cam.cpp:525-585) + the stamps of generate_stereo_image_descriptor (:362-374)
                 if (defer_heavy) im.landmark_num = r.n_kps[i]; else heavy(im, i);
                 stamp_image_descriptor(im, stamp, cfg_.self_id, to_msg(view_extrinsic(d, true)), pose, kf_id);
-                if (cfg_.geometry && cfg_.mono()) {
+                if (cfg_.geometry && !cfg_.stereo()) {
                     // generate_gray_depth_image_descriptor's landmarks (loop_cam.cpp:260-304): read from the depth image under each key point
                     const bool have = streamed ? lane.meta[m].depth != nullptr : (depth_ && kf_id >= depth_base_ && kf_id < depth_base_ + depth_n_);
                     if (have) fill_depth_landmarks(im, streamed ? lane.meta[m].depth : depth_ + (size_t)(kf_id - depth_base_) * cfg_.width * cfg_.height, cfg_.width, cfg_.width, cfg_.height, cfg_.depth_near,
@@ -667,7 +715,7 @@ private:
                 } else if (cfg_.geometry) {
                     // the stereo half of generate_stereo_image_descriptor (loop_cam.cpp:341-454): the down image of this direction, triangulation
                     // (one task per direction on the geometry pool: ~170 SVD triangulations each; joined before the frames reach the detector)
-                    if (downs_.size() < (size_t)4 * lane.cur) downs_.resize((size_t)4 * lane.cur);
+                    if (downs_.size() < (size_t)nd * lane.cur) downs_.resize((size_t)nd * lane.cur);
                     ImageDescriptor& down = downs_[(size_t)i];
                     down = ImageDescriptor{};
                     const int j = n + i;
@@ -779,6 +827,7 @@ private:
     std::deque<Lane*> stream_pending_;          // ... and the units in flight, oldest first
     size_t next_lane_ = 0;
     int carried_hits_ = 0;
+    bool first_keyframe_seen_ = false;          // STEREO_PINHOLE: set_stereo_extrinsics is refused from the first key frame on
     std::vector<FisheyeFrameDescriptor> frames_;
     std::unique_ptr<IndexFlatIP> shard_index_;
     omni_shard* shard_ = nullptr;

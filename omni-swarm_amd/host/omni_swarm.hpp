@@ -259,6 +259,21 @@ private:
 
 namespace omni {
 
+// camera-size frames -> network-size images (omni_resize_*): the cv::resize in front of both reference engines (superpoint_tensorrt.cpp:123-125), one object per
+// source size -> destination size; LoopCamHIP::enqueue_raw_* runs it inside a key-frame unit
+class ResizeHIP {
+public:
+    ResizeHIP(Context& ctx, int src_width, int src_height, int dst_width, int dst_height) : h_(omni_resize_create(ctx.get(), src_width, src_height, dst_width, dst_height)) {
+        if (!h_) throw std::runtime_error(std::string("omni_resize_create: ") + omni_last_error());
+    }
+    ~ResizeHIP() { omni_resize_destroy(h_); }
+    ResizeHIP(const ResizeHIP&) = delete;
+    ResizeHIP& operator=(const ResizeHIP&) = delete;
+    omni_resize* handle() const { return h_; }
+private:
+    omni_resize* h_ = nullptr;
+};
+
 // The CNN + matching part of LoopCam::on_flattened_images (loop_cam.cpp:178-229): SuperPoint on the 2*n_dirs images of one
 // fisheye key frame (up cameras, then down cameras), MobileNetVLAD on the n_dirs up images, BFMatcher(L2, crossCheck) up <->
 // down per direction -- one asynchronous unit on the GPU (omni_cam_*), results in one pinned host block.  The reference runs
@@ -322,6 +337,19 @@ public:
     void enqueue_fisheye_dev(omni_flatten* up, omni_flatten* down, const uint8_t* up_dev, const uint8_t* down_dev, int src_stride, int n_keyframes,
                              int first_view = 1, bool fisheye_mask = true) {
         check(omni_cam_enqueue_fisheye_dev(h_, up, down, up_dev, down_dev, src_stride, n_keyframes, first_view, fisheye_mask ? 1 : 0), "omni_cam_enqueue_fisheye_dev");
+    }
+    // STEREO_PINHOLE key frames' RAW left / right frames (n_keyframes per camera, u8, src_stride, of the camera's size): resized to the networks' size inside the
+    // unit (omni_cam_enqueue_raw_*); n_keyframes = the unit's active size.  `resize` outlives wait().
+    void enqueue_raw_host(omni_resize* resize, const uint8_t* left_host, const uint8_t* right_host, int src_stride, int n_keyframes) {
+        check(omni_cam_enqueue_raw_host(h_, resize, left_host, right_host, src_stride, n_keyframes), "omni_cam_enqueue_raw_host");
+    }
+    void enqueue_raw_dev(omni_resize* resize, const uint8_t* left_dev, const uint8_t* right_dev, int src_stride, int n_keyframes) {
+        check(omni_cam_enqueue_raw_dev(h_, resize, left_dev, right_dev, src_stride, n_keyframes), "omni_cam_enqueue_raw_dev");
+    }
+    void enqueue_raw_host_parts(omni_resize* resize, const std::vector<const uint8_t*>& left, const std::vector<int>& left_images, const std::vector<const uint8_t*>& right,
+                                const std::vector<int>& right_images, int src_stride) {
+        check(omni_cam_enqueue_raw_host_parts(h_, resize, left.data(), left_images.data(), (int)left.size(), right.data(), right_images.data(), (int)right.size(), src_stride),
+              "omni_cam_enqueue_raw_host_parts");
     }
     // the next enqueue on this object starts behind the convolution stack of `earlier`'s last one (omni_cam_order_after)
     void order_after(LoopCamHIP& earlier, int streams) { check(omni_cam_order_after(h_, earlier.h_, streams), "omni_cam_order_after"); }

@@ -19,7 +19,11 @@ SYMBOLS = ["omni_pipeline_last_error", "omni_pipeline_create", "omni_pipeline_de
            "omni_pipeline_run", "omni_pipeline_attach_shard", "omni_pipeline_prepare", "omni_pipeline_geometry_stats", "omni_pipeline_sync",
            "omni_pipeline_set_poses", "omni_pipeline_create_pinhole_depth", "omni_pipeline_set_depth", "omni_pipeline_push_keyframe", "omni_pipeline_flush", "omni_pipeline_host_times", "omni_pipeline_get_candidates", "omni_pipeline_get_edges", "omni_pipeline_get_latencies",
            "omni_pipeline_poll", "omni_pipeline_set_latency", "omni_pipeline_units", "omni_pipeline_get_exchange_us", "omni_swarm_params_from_launch", "omni_swarm_params_table", "omni_pipeline_apply_launch", "omni_pipeline_create_from_launch"]
+# CameraConfig::STEREO_PINHOLE's entry points: include/omni_host_stereo.h, lib/libomni_host_stereo.so (the same handle)
+STEREO_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_stereo.so")
+STEREO_SYMBOLS = ["omni_stereo_last_error", "omni_pipeline_create_stereo_pinhole", "omni_pipeline_set_stereo_extrinsics"]
 _lib = None
+_stereo_lib = None
 
 
 def lib():
@@ -69,6 +73,21 @@ def lib():
     return _lib
 
 
+def stereo_lib():
+    global _stereo_lib
+    if _stereo_lib is None:
+        if not os.path.exists(STEREO_LIB_PATH):
+            raise OSError(f"{STEREO_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        lib()
+        L = C.CDLL(STEREO_LIB_PATH)
+        L.omni_stereo_last_error.restype = C.c_char_p
+        L.omni_pipeline_create_stereo_pinhole.restype = C.c_void_p
+        L.omni_pipeline_create_stereo_pinhole.argtypes = lib().omni_pipeline_create.argtypes + [C.c_double] * 4 + [C.c_int, C.c_int, C.c_double, C.c_int]
+        L.omni_pipeline_set_stereo_extrinsics.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _stereo_lib = L
+    return _stereo_lib
+
+
 def _err(what):
     return capi.OmniError(f"{what}: {lib().omni_pipeline_last_error().decode()}")
 
@@ -103,15 +122,27 @@ def swarm_params_table():
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
-                 inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None):
+                 inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
+                 stereo_pinhole=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
+        stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
+        frame per key frame, of src_width x src_height (the camera's size: resized to width x height inside every unit, on the GPU) or, without them, of
+        the networks' size; fx fy cx cy are those of the width x height image.  set_stereo_extrinsics gives the rig's two extrinsics.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
                   precision, microbatch, pipelines, storage, self_id, inner_product_thres, init_mode_product_thres, match_index_dist, min_loop_num,
                   min_direction_loop, int(geometry))
-        if pinhole_depth is None:
+        if stereo_pinhole is not None:
+            if pinhole_depth is not None:
+                raise ValueError("pinhole_depth and stereo_pinhole are two camera configurations")
+            d = stereo_pinhole
+            self.h = stereo_lib().omni_pipeline_create_stereo_pinhole(*common, d["fx"], d["fy"], d["cx"], d["cy"], d.get("src_width", 0), d.get("src_height", 0),
+                                                                      d.get("triangle_thres", 0.006), d.get("accept_min_3d_pts", 50))
+            if not self.h:
+                raise capi.OmniError(f"omni_pipeline_create_stereo_pinhole: {stereo_lib().omni_stereo_last_error().decode()}")
+        elif pinhole_depth is None:
             self.h = lib().omni_pipeline_create(*common)
         else:
             d = pinhole_depth
@@ -144,6 +175,12 @@ class KeyframePipeline:
         self._depth = np.ascontiguousarray(depth, np.uint16)
         if lib().omni_pipeline_set_depth(self.h, first_msg_id, self._depth.shape[0], self._depth.ctypes.data):
             raise _err("omni_pipeline_set_depth")
+
+    def set_stereo_extrinsics(self, left7, right7):
+        """STEREO_PINHOLE: body -> camera of the left and the right camera, xyz + quaternion wxyz each; before the first key frame"""
+        a, b = (np.ascontiguousarray(v, np.float64).reshape(7) for v in (left7, right7))
+        if stereo_lib().omni_pipeline_set_stereo_extrinsics(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), b.ctypes.data_as(C.POINTER(C.c_double))):
+            raise capi.OmniError(f"omni_pipeline_set_stereo_extrinsics: {stereo_lib().omni_stereo_last_error().decode()}")
 
     def close(self):
         if getattr(self, "h", None):
@@ -179,7 +216,8 @@ class KeyframePipeline:
         return hits.value
 
     def push_keyframe(self, images, msg_id: int, stamp: float, pose7=None, prevent_adding_db: bool = False, depth: np.ndarray = None) -> int:
-        """The streaming intake: one key frame (images: list of u8 arrays [H][W], up cameras then down cameras; PINHOLE_DEPTH: one) with its id, stamp,
+        """The streaming intake: one key frame (images: list of u8 arrays [H][W], up cameras then down cameras; PINHOLE_DEPTH: one; STEREO_PINHOLE: the left
+        and the right frame, at the camera's size when the pipeline was given src_width / src_height) with its id, stamp,
         odometry pose and prevent_adding_db flag (swarm_loop.cpp:140-170); returns the loop candidates found by the units this call finished.  The
         images are copied before the call returns; a depth image must stay alive until flush()."""
         imgs = [np.ascontiguousarray(i, np.uint8) for i in images]
