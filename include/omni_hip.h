@@ -359,7 +359,8 @@ int          omni_resize_enqueue_dev(omni_resize* r, const uint8_t* src_dev, int
  * as one asynchronous unit: SuperPoint on the 2*n_dirs images (up cameras first, then down), MobileNetVLAD on the n_dirs
  * up images, BFMatcher(L2, crossCheck) up <-> down per direction, and the D2H copy of every result into one pinned block.
  * The handles are borrowed (sp created with max_batch >= 2*n_dirs on sp_ctx, vlad with max_batch >= n_dirs on vlad_ctx,
- * both contexts on the same device).  Camera lifting / triangulation (:73-106, 405-454, 558-576) stay with the caller. */
+ * both contexts on the same device).  Camera lifting / triangulation (:73-106, 405-454, 558-576): inside the unit for a pinhole model set with
+ * omni_cam_set_stereo_model (below); other camera models stay with the caller. */
 typedef struct omni_cam_result {      /* pointers into the handle's pinned host block; valid until its next enqueue */
     int n_dirs, max_num, desc_dim, global_dim;
     const float* kps_xy;      /* [2*n_dirs][max_num][2] */
@@ -431,6 +432,45 @@ int       omni_cam_ready(omni_cam* cam, int* ready);
  * oldest unit finishes first while the next one's convolutions run under its small-grid tail (NMS, descriptor sampling, matcher).
  * streams: 1 = `later`'s SuperPoint stream waits, 2 = its MobileNetVLAD stream too, 0 = no-op. */
 int       omni_cam_order_after(omni_cam* later, omni_cam* earlier, int streams);
+
+/* ---- stereo landmarks: the lifting and the up/down triangulation of generate_stereo_image_descriptor (loop_cam.cpp:397-444; triangulatePoint :73-106; the lifted
+ * key points of extractor_img_desc_deepnet :558-566) for PINHOLE views -- the flattened fisheye views and the stereo-pinhole pair.  The arithmetic is stated once, in
+ * csrc/landmark_plan.h: f64, every product and sum rounded on its own, the same operations in the same order as host/geometry.hpp (triangulate_point,
+ * stereo_landmarks) and host/loop_geometry.hpp (fill_stereo_landmarks).  Poses and extrinsics are xyz + quaternion wxyz (7 doubles; the quaternion is normalised
+ * on the way in).  The match lists must be one-to-one (every matcher mode of this library); a match whose index is outside its image's key points is skipped. */
+#define OMNI_STEREO_MAX_DIRS 8
+typedef struct omni_stereo_model {
+    double fx, fy, cx, cy;            /* of the network-size image: lift = ((double)x - cx) / fx, ((double)y - cy) / fy */
+    double triangle_thres;            /* a match is dropped when err > triangle_thres || the point lies behind the up camera */
+    int accept_min_3d_pts;            /* no landmarks at all unless the up image has MORE key points than this (loop_cam.cpp:385) */
+    int dirs_per_keyframe;            /* 1 .. OMNI_STEREO_MAX_DIRS: image pair p belongs to key frame p / dirs_per_keyframe, direction p % dirs_per_keyframe */
+    double up_extrinsic[OMNI_STEREO_MAX_DIRS][7], down_extrinsic[OMNI_STEREO_MAX_DIRS][7];   /* body -> camera, per direction */
+} omni_stereo_model;
+/* The stage on HBM-resident arrays laid out as the key-frame unit's, [up images | down images]: kps_xy_dev [2*n_pairs][max_num][2], n_kps_dev [2*n_pairs],
+ * match_up_dev / match_down_dev [n_pairs][max_num], n_matches_dev [n_pairs], poses7_dev [n_pairs / dirs_per_keyframe][7] (pose_drone per key frame).
+ * Outputs (device): norm2d_out [2*n_pairs][max_num][2] float (zeros behind an image's last key point), l3d_out [2*n_pairs][max_num][3] float,
+ * flag_out [2*n_pairs][max_num] u8, count_out [n_pairs] (count_3d).  dirs_per_keyframe must be the model's and divide n_pairs; max_num <= 1024.
+ * Asynchronous on the context's stream. */
+int omni_landmarks_enqueue_dev(omni_ctx* ctx, const omni_stereo_model* model, const double* poses7_dev, int n_pairs, int dirs_per_keyframe, int max_num,
+                               const float* kps_xy_dev, const int* n_kps_dev, const int* match_up_dev, const int* match_down_dev, const int* n_matches_dev,
+                               float* norm2d_out, float* l3d_out, uint8_t* flag_out, int* count_out);
+/* The same stage inside the key-frame unit: with a model set, every unit runs the kernel on its SuperPoint stream right behind the up/down match and copies the
+ * four arrays into the handle's pinned block in front of the unit's event.  model == NULL switches the stage off again.  Refused: a mono handle, a
+ * dirs_per_keyframe that does not divide the handle's n_dirs, a unit in flight. */
+int omni_cam_set_stereo_model(omni_cam* cam, const omni_stereo_model* model);
+/* pose_drone of the n_keyframes key frames of the NEXT unit (poses7 [n_keyframes][7], host memory, copied before the call returns; uploaded on the SuperPoint
+ * stream at enqueue).  Refused with a unit in flight or without a model.  While a model is set EVERY enqueue entry (_dev, _host, _host_parts, _fisheye_*, _raw_*)
+ * refuses, before anything is enqueued, a unit whose active size is not n_keyframes * dirs_per_keyframe -- also one whose poses were not set since the last unit. */
+int omni_cam_set_poses(omni_cam* cam, const double* poses7, int n_keyframes);
+typedef struct omni_cam_landmarks_result {      /* pointers into the handle's pinned host block; valid after omni_cam_wait until the handle's next enqueue */
+    int n_images, n_dirs, max_num;              /* of that unit: n_images = 2 * n_dirs */
+    const float*   norm2d;                      /* [n_images][max_num][2]  the message's landmarks_2d_norm */
+    const float*   landmarks_3d;                /* [n_images][max_num][3] */
+    const uint8_t* landmarks_flag;              /* [n_images][max_num] */
+    const int*     count_3d;                    /* [n_dirs] */
+} omni_cam_landmarks_result;
+/* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran without a model */
+int omni_cam_landmarks(omni_cam* cam, omni_cam_landmarks_result* out);
 
 #ifdef __cplusplus
 }

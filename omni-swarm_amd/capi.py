@@ -39,6 +39,7 @@ SYMBOLS = [
     "omni_shard_unique_id", "omni_shard_library_path", "omni_shard_create", "omni_shard_destroy", "omni_shard_ntotal", "omni_shard_preload_local", "omni_shard_step_batch_dev", "omni_shard_step_enqueue", "omni_shard_rows_consumed", "omni_shard_step_wait", "omni_shard_last_exchange_us",
     "omni_shard_search", "omni_flatten_create", "omni_flatten_destroy", "omni_flatten_out_bytes", "omni_flatten_enqueue_dev",
     "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
+    "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
 ]
 
 
@@ -60,6 +61,33 @@ class _CamResult(C.Structure):
                 ("kps_xy", C.POINTER(C.c_float)), ("n_kps", C.POINTER(C.c_int)), ("desc", C.POINTER(C.c_float)),
                 ("scores", C.POINTER(C.c_float)), ("global_desc", C.POINTER(C.c_float)), ("match_up", C.POINTER(C.c_int)),
                 ("match_down", C.POINTER(C.c_int)), ("match_dist", C.POINTER(C.c_float)), ("n_matches", C.POINTER(C.c_int)), ("n_images", C.c_int)]
+
+
+STEREO_MAX_DIRS = 8           # OMNI_STEREO_MAX_DIRS
+
+
+class StereoModel(C.Structure):
+    """omni_stereo_model: the pinhole model, the accept rule and the per-direction extrinsics (xyz + quaternion wxyz) of the stereo-landmark stage"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("triangle_thres", C.c_double),
+                ("accept_min_3d_pts", C.c_int), ("dirs_per_keyframe", C.c_int),
+                ("up_extrinsic", (C.c_double * 7) * STEREO_MAX_DIRS), ("down_extrinsic", (C.c_double * 7) * STEREO_MAX_DIRS)]
+
+
+def stereo_model(fx, fy, cx, cy, triangle_thres, accept_min_3d_pts, up_extrinsics, down_extrinsics) -> StereoModel:
+    """up_extrinsics / down_extrinsics: [dirs][7] (body -> camera of every direction of a key frame)"""
+    up, down = np.asarray(up_extrinsics, np.float64).reshape(-1, 7), np.asarray(down_extrinsics, np.float64).reshape(-1, 7)
+    if not (1 <= len(up) <= STEREO_MAX_DIRS and len(down) == len(up)):
+        raise ValueError(f"stereo_model: {len(up)} up and {len(down)} down extrinsics, 1..{STEREO_MAX_DIRS} of each")
+    m = StereoModel(fx, fy, cx, cy, triangle_thres, int(accept_min_3d_pts), len(up))
+    for d in range(len(up)):
+        m.up_extrinsic[d][:] = up[d].tolist()
+        m.down_extrinsic[d][:] = down[d].tolist()
+    return m
+
+
+class _CamLandmarks(C.Structure):
+    _fields_ = [("n_images", C.c_int), ("n_dirs", C.c_int), ("max_num", C.c_int), ("norm2d", C.POINTER(C.c_float)), ("landmarks_3d", C.POINTER(C.c_float)),
+                ("landmarks_flag", C.POINTER(C.c_uint8)), ("count_3d", C.POINTER(C.c_int))]
 
 
 class _VladWeights(C.Structure):
@@ -176,6 +204,10 @@ def lib():
     sig("omni_cam_enqueue_raw_host", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int])
     sig("omni_cam_enqueue_raw_host_parts", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int])
     sig("omni_cam_wait", C.c_int, [_vp, C.POINTER(_CamResult)])
+    sig("omni_landmarks_enqueue_dev", C.c_int, [_vp, C.POINTER(StereoModel), _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+    sig("omni_cam_set_stereo_model", C.c_int, [_vp, C.POINTER(StereoModel)])
+    sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
+    sig("omni_cam_landmarks", C.c_int, [_vp, C.POINTER(_CamLandmarks)])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
     sig("omni_cam_ready", C.c_int, [_vp, C.POINTER(C.c_int)])
@@ -867,6 +899,36 @@ def bf_match_batched_dev(ctx: Context, n_pairs, max_n, dim, mode, q_dev, q_strid
                                            nt_dev, qidx_dev, tidx_dev, dist_dev, n_dev))
 
 
+def landmarks_dev(ctx: Context, model: StereoModel, poses7_dev, n_pairs, max_num, kps_xy_dev, n_kps_dev, match_up_dev, match_down_dev, n_matches_dev,
+                  norm2d_out, l3d_out, flag_out, count_out):
+    """omni_landmarks_enqueue_dev: lifting + up/down triangulation on HBM-resident arrays laid out [up images | down images]; asynchronous on ctx"""
+    _check(lib().omni_landmarks_enqueue_dev(ctx.h, C.byref(model), poses7_dev, n_pairs, model.dirs_per_keyframe, max_num, kps_xy_dev, n_kps_dev, match_up_dev,
+                                            match_down_dev, n_matches_dev, norm2d_out, l3d_out, flag_out, count_out))
+
+
+def landmarks(ctx: Context, model: StereoModel, poses7, kps_xy, n_kps, match_up, match_down, n_matches) -> dict:
+    """host convenience around landmarks_dev (upload, run, download): kps_xy [2P][M][2], n_kps [2P], match_* [P][M], n_matches [P], poses7 [P / dirs][7]"""
+    kps_xy, n_kps = _f32(kps_xy), np.ascontiguousarray(n_kps, np.int32)
+    P, M = n_kps.shape[0] // 2, kps_xy.shape[1]
+    ins = [np.ascontiguousarray(poses7, np.float64), kps_xy, n_kps, np.ascontiguousarray(match_up, np.int32), np.ascontiguousarray(match_down, np.int32),
+           np.ascontiguousarray(n_matches, np.int32)]
+    assert ins[0].shape == (P // model.dirs_per_keyframe, 7) and kps_xy.shape == (2 * P, M, 2) and ins[3].shape == ins[4].shape == (P, M) and ins[5].shape == (P,)
+    outs = [((2 * P, M, 2), np.float32), ((2 * P, M, 3), np.float32), ((2 * P, M), np.uint8), ((P,), np.int32)]
+    dev = []
+    try:
+        for a in ins:
+            dev.append(ctx.to_device(a))
+        for shape, dt in outs:
+            dev.append(ctx.alloc(int(np.prod(shape)) * np.dtype(dt).itemsize))
+        landmarks_dev(ctx, model, dev[0], P, M, *dev[1:])
+        ctx.sync()
+        res = [ctx.from_device(d, shape, dt) for d, (shape, dt) in zip(dev[6:], outs)]
+    finally:
+        for d in dev:
+            ctx.free(d)
+    return dict(zip(("norm2d", "landmarks_3d", "landmarks_flag", "count_3d"), res))
+
+
 class Cam:
     """omni_cam: one key frame's CNN + matching work as a single asynchronous unit (LoopCam::on_flattened_images,
     loop_cam.cpp:178-229).  wait() returns numpy VIEWS of the handle's pinned host block (valid until the next enqueue)."""
@@ -947,6 +1009,25 @@ class Cam:
         """a unit of fewer directions than the handle was created for: the next enqueues read cams * n_dirs images (up cameras first, down right behind)"""
         _check(lib().omni_cam_set_active(self.h, n_dirs))
         self.n_active = n_dirs
+
+    def set_stereo_model(self, model):
+        """a StereoModel: every following unit lifts and triangulates its stereo landmarks on the GPU (landmarks() after wait()); None switches it off"""
+        _check(lib().omni_cam_set_stereo_model(self.h, C.byref(model) if model is not None else None))
+        self._model = model
+
+    def set_poses(self, poses7):
+        """pose_drone (xyz + quaternion wxyz) of the key frames of the NEXT unit: [n_keyframes][7]"""
+        p = np.ascontiguousarray(poses7, np.float64).reshape(-1, 7)
+        _check(lib().omni_cam_set_poses(self.h, p.ctypes.data_as(C.POINTER(C.c_double)), p.shape[0]))
+
+    def landmarks(self) -> dict:
+        """after wait(): numpy VIEWS of the unit's lifted key points, 3-D landmarks, flags and count_3d (valid until the next enqueue)"""
+        r = _CamLandmarks()
+        _check(lib().omni_cam_landmarks(self.h, C.byref(r)))
+        A = np.ctypeslib.as_array
+        ni, n, m = r.n_images, r.n_dirs, r.max_num
+        return {"norm2d": A(r.norm2d, (ni, m, 2)), "landmarks_3d": A(r.landmarks_3d, (ni, m, 3)), "landmarks_flag": A(r.landmarks_flag, (ni, m)),
+                "count_3d": A(r.count_3d, (n,))}
 
     def ready(self) -> bool:
         r = C.c_int(0)

@@ -30,6 +30,15 @@ struct omni_cam {
     uint8_t* d_raw = nullptr;         // staging for omni_cam_enqueue_fisheye_host / _raw_host: the raw frames of the up (left) cameras, then of the down (right) cameras
     size_t d_raw_bytes = 0;
     bool pending = false;
+    // stereo landmarks inside the unit (omni_cam_set_stereo_model; landmarks.hip): the model, the NEXT unit's poses (pinned staging in `host`, uploaded at enqueue),
+    // the stage's device outputs -- laid out as the key points, [up images | down images] of the active size
+    bool lm_on = false, lm_unit = false;      // lm_unit: the unit enqueued last ran the stage (omni_cam_landmarks)
+    omni_stereo_model model;
+    int n_poses = 0;                          // key frames omni_cam_set_poses set since the last unit (0: none)
+    int lm_n = 0;                             // directions of the unit that ran the stage last
+    double* d_poses = nullptr;
+    char* d_lm = nullptr;                     // ONE block laid out as host + off_norm .. off_lm_end: norm2d | landmarks_3d | flags | count_3d (one copy down)
+    size_t off_poses = 0, off_norm = 0, off_l3d = 0, off_flag = 0, off_cnt = 0, off_lm_end = 0;
     std::mutex mu;
 };
 
@@ -70,10 +79,19 @@ static omni_cam* cam_create(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, o
     c->off_t = o;   o += al(n * M * 4);
     c->off_d = o;   o += al(n * M * 4);
     c->off_nm = o;  o += al(n * 4);
+    if (cams == 2) {                                                          // the landmark stage's part of the block (a few kilobytes per image)
+        c->off_poses = o; o += al(n * 7 * 8);
+        c->off_norm = o;  o += al(ni * M * 2 * 4);
+        c->off_l3d = o;   o += al(ni * M * 3 * 4);
+        c->off_flag = o;  o += al(ni * M);
+        c->off_cnt = o;   o += al(n * 4);
+        c->off_lm_end = o;
+    }
     c->host_bytes = o;
     bool ok = hipHostMalloc((void**)&c->host, o, hipHostMallocDefault) == hipSuccess &&
               hipMalloc((void**)&c->d_qidx, n * M * 4) == hipSuccess && hipMalloc((void**)&c->d_tidx, n * M * 4) == hipSuccess &&
               hipMalloc((void**)&c->d_dist, n * M * 4) == hipSuccess && hipMalloc((void**)&c->d_nm, n * 4) == hipSuccess &&
+              (cams != 2 || (hipMalloc((void**)&c->d_poses, n * 7 * 8) == hipSuccess && hipMalloc((void**)&c->d_lm, c->off_lm_end - c->off_norm) == hipSuccess)) &&
               hipEventCreateWithFlags(&c->e1, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->e2, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->e_up, hipEventDisableTiming) == hipSuccess &&
@@ -89,7 +107,7 @@ void omni_cam_destroy(omni_cam* c) {
     (void)hipSetDevice(c->c1->device);
     (void)hipStreamSynchronize(c->c1->stream);
     (void)hipStreamSynchronize(c->c2->stream);
-    void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw};
+    void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw, c->d_poses, c->d_lm};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->host) (void)hipHostFree(c->host);
     if (c->e1) (void)hipEventDestroy(c->e1);
@@ -112,10 +130,21 @@ static int cam_staging(omni_cam* c, uint8_t*& buf, size_t& have, size_t need) {
     return OMNI_OK;
 }
 
+// with a stereo model set, a unit needs the poses of ITS key frames: checked by every enqueue entry before anything is enqueued (c->mu held)
+static int cam_poses_check(omni_cam* c) {
+    if (!c->lm_on) return OMNI_OK;
+    OMNI_REQUIRE(c->n_poses > 0, OMNI_ERR_INVALID, "a stereo model is set but the unit's poses are not (omni_cam_set_poses before every enqueue)");
+    OMNI_REQUIRE(c->n_poses * c->model.dirs_per_keyframe == c->n, OMNI_ERR_INVALID, "poses of %d key frames x %d directions for a unit of %d (omni_cam_set_poses, omni_cam_set_active)",
+                 c->n_poses, c->model.dirs_per_keyframe, c->n);
+    return OMNI_OK;
+}
+
 int omni_cam_enqueue_dev(omni_cam* c, const uint8_t* gray_dev, int stride, int fisheye_mask) {
     omni::TraceRange trace_range("omni_cam_enqueue_dev");
     OMNI_REQUIRE(c && gray_dev, OMNI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
+    int rc;
+    if ((rc = cam_poses_check(c))) return rc;
     (void)hipSetDevice(c->c1->device);
     return cam_enqueue_locked(c, gray_dev, stride, fisheye_mask);
 }
@@ -127,8 +156,9 @@ int omni_cam_enqueue_host(omni_cam* c, const uint8_t* gray_host, int stride, int
     // the networks read cams * n images of THEIR size from the staging buffer: any other size would run them past its end
     OMNI_REQUIRE(width == c->W && height == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_host: images are %dx%d but the networks were created for %dx%d", width, height, c->W, c->H);
     std::lock_guard<std::mutex> lk(c->mu);
-    (void)hipSetDevice(c->c1->device);
     int rc;
+    if ((rc = cam_poses_check(c))) return rc;
+    (void)hipSetDevice(c->c1->device);
     if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, (size_t)c->cams * c->n * width * height))) return rc;
     // the reference uploads one image per engine call and blocks (tensorrt_generic.cpp:58-75); here the key frame's 2n images go up as one
     // asynchronous copy on the SuperPoint stream (pinned source: the copy engine runs it next to the other pipelines' kernels) and the
@@ -156,15 +186,16 @@ int omni_cam_enqueue_host_parts(omni_cam* c, const uint8_t* const* up, const int
                                 int width, int height, int fisheye_mask) {
     omni::TraceRange trace_range("omni_cam_enqueue_host_parts (upload + unit)");
     OMNI_REQUIRE(c && up && up_images && n_up > 0 && (n_down == 0 || (down && down_images)), OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);                 // (before anything of the handle is read: omni_cam_set_active writes c->n under this lock)
     OMNI_REQUIRE(width == c->W && height == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: images are %dx%d but the networks were created for %dx%d", width, height, c->W, c->H);
     int nu = 0, nd = 0;
     for (int i = 0; i < n_up; ++i) { OMNI_REQUIRE(up[i] && up_images[i] > 0, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: empty part"); nu += up_images[i]; }
     for (int i = 0; i < n_down; ++i) { OMNI_REQUIRE(down[i] && down_images[i] > 0, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: empty part"); nd += down_images[i]; }
-    std::lock_guard<std::mutex> lk(c->mu);                 // (before c->n is read: omni_cam_set_active writes it under this lock)
     OMNI_REQUIRE(nu == c->n && nd == (c->cams - 1) * c->n, OMNI_ERR_INVALID, "omni_cam_enqueue_host_parts: %d + %d images for a unit of %d x %d", nu, nd, c->cams, c->n);
+    int rc;
+    if ((rc = cam_poses_check(c))) return rc;
     (void)hipSetDevice(c->c1->device);
     const size_t img = (size_t)width * height;
-    int rc;
     if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, (size_t)c->cams * c->n * img))) return rc;
     size_t at = 0;
     for (int i = 0; i < n_up; ++i) { OMNI_HIP_TRY(hipMemcpyAsync(c->d_gray + at, up[i], up_images[i] * img, hipMemcpyHostToDevice, c->c1->stream)); at += up_images[i] * img; }
@@ -192,7 +223,7 @@ static int cam_fisheye_check(omni_cam* c, const omni_flatten* up, const omni_fla
             OMNI_REQUIRE(f->vw[v] == c->W && f->vh[v] == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye: view %d is %dx%d but the networks were created for %dx%d", v,
                          f->vw[v], f->vh[v], c->W, c->H);
     }
-    return OMNI_OK;
+    return cam_poses_check(c);
 }
 
 // up camera first and MobileNetVLAD behind it, then the down camera: the overlap omni_cam_enqueue_host arranges for its two uploads.  *_host != nullptr: the raw
@@ -248,7 +279,7 @@ static int cam_raw_check(omni_cam* c, const omni_resize* r, int src_stride, int 
     OMNI_REQUIRE(n_keyframes == c->n, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: %d key frames for a unit of %d (omni_cam_set_active)", n_keyframes, c->n);
     OMNI_REQUIRE(src_stride >= r->src_w, OMNI_ERR_INVALID, "omni_cam_enqueue_raw: stride %d for frames %d wide", src_stride, r->src_w);
     OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_enqueue_raw with a unit in flight (omni_cam_wait first)");
-    return OMNI_OK;
+    return cam_poses_check(c);
 }
 
 // left camera first and MobileNetVLAD behind it, then the right camera: the order of cam_fisheye_locked.  n_left > 0: the frames are in host memory, each camera's
@@ -350,6 +381,23 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
         OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_d, c->d_dist, (size_t)n * M * 4, hipMemcpyDeviceToHost, s1));
         OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_nm, c->d_nm, (size_t)n * 4, hipMemcpyDeviceToHost, s1));
     }
+    c->lm_unit = false;
+    if (c->lm_on) {
+        // generate_stereo_image_descriptor's lifting and triangulation (loop_cam.cpp:397-444), right behind the up <-> down match it reads; its four arrays go
+        // down in front of the unit's event.  (The down images' key points lie right behind the up images' in the network's output, as the outputs here.)
+        const size_t half = (size_t)n * M;
+        float *d_norm = reinterpret_cast<float*>(c->d_lm), *d_l3d = reinterpret_cast<float*>(c->d_lm + (c->off_l3d - c->off_norm));
+        uint8_t* d_flag = reinterpret_cast<uint8_t*>(c->d_lm + (c->off_flag - c->off_norm));
+        int* d_cnt = reinterpret_cast<int*>(c->d_lm + (c->off_cnt - c->off_norm));
+        OMNI_HIP_TRY(hipMemcpyAsync(c->d_poses, h + c->off_poses, (size_t)c->n_poses * 7 * 8, hipMemcpyHostToDevice, s1));
+        if ((rc = omni::landmarks_launch(s1, c->model, c->d_poses, n, M, c->kps_dev, c->kps_dev + half * 2, c->n_dev, c->n_dev + n, c->d_qidx, c->d_tidx, c->d_nm, d_norm,
+                                         d_norm + half * 2, d_l3d, d_l3d + half * 3, d_flag, d_flag + half, d_cnt)))
+            return rc;
+        // (the whole block in one copy, a few hundred kilobytes at most; a smaller unit leaves the tail of each array as it was)
+        OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_norm, c->d_lm, c->off_lm_end - c->off_norm, hipMemcpyDeviceToHost, s1));
+        c->lm_unit = true; c->lm_n = n;
+        c->n_poses = 0;                                                       // (consumed: the next unit needs its own)
+    }
     OMNI_HIP_TRY(hipEventRecord(c->e1, s1));
     OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_g, c->g_dev, (size_t)n * c->out_dim * 4, hipMemcpyDeviceToHost, s2));
     OMNI_HIP_TRY(hipEventRecord(c->e2, s2));
@@ -377,6 +425,49 @@ int omni_cam_set_active(omni_cam* c, int n_dirs) {
     OMNI_REQUIRE(n_dirs >= 1 && n_dirs <= c->n_cap, OMNI_ERR_INVALID, "omni_cam_set_active: %d directions, the handle holds 1..%d", n_dirs, c->n_cap);
     OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_active with a unit in flight (omni_cam_wait first)");
     c->n = n_dirs;
+    return OMNI_OK;
+}
+
+// ---- stereo landmarks inside the unit ----------------------------------------------------------------------------------------------------------------
+int omni_cam_set_stereo_model(omni_cam* c, const omni_stereo_model* model) {
+    OMNI_REQUIRE(c, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_stereo_model with a unit in flight (omni_cam_wait first)");
+    if (!model) { c->lm_on = false; c->n_poses = 0; return OMNI_OK; }
+    OMNI_REQUIRE(c->cams == 2, OMNI_ERR_INVALID, "omni_cam_set_stereo_model: a mono handle has no up / down camera pair to triangulate from");
+    int rc;
+    if ((rc = omni::landmarks_check_model(model))) return rc;
+    OMNI_REQUIRE(c->n_cap % model->dirs_per_keyframe == 0, OMNI_ERR_INVALID, "omni_cam_set_stereo_model: %d directions per key frame do not divide the handle's %d",
+                 model->dirs_per_keyframe, c->n_cap);
+    c->model = *model;
+    c->lm_on = true;
+    c->n_poses = 0;
+    return OMNI_OK;
+}
+
+int omni_cam_set_poses(omni_cam* c, const double* poses7, int n_keyframes) {
+    OMNI_REQUIRE(c && poses7, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_poses with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->lm_on, OMNI_ERR_INVALID, "omni_cam_set_poses without a stereo model (omni_cam_set_stereo_model)");
+    OMNI_REQUIRE(n_keyframes >= 1 && (int64_t)n_keyframes * c->model.dirs_per_keyframe <= c->n_cap, OMNI_ERR_INVALID,
+                 "omni_cam_set_poses: %d key frames x %d directions, the handle holds %d directions", n_keyframes, c->model.dirs_per_keyframe, c->n_cap);
+    memcpy(c->host + c->off_poses, poses7, (size_t)n_keyframes * 7 * sizeof(double));
+    c->n_poses = n_keyframes;
+    return OMNI_OK;
+}
+
+int omni_cam_landmarks(omni_cam* c, omni_cam_landmarks_result* out) {
+    OMNI_REQUIRE(c && out, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_landmarks with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->lm_unit, OMNI_ERR_INVALID, "omni_cam_landmarks: the last unit ran without a stereo model (omni_cam_set_stereo_model)");
+    const char* h = c->host;
+    out->n_images = 2 * c->lm_n; out->n_dirs = c->lm_n; out->max_num = c->M;
+    out->norm2d = reinterpret_cast<const float*>(h + c->off_norm);
+    out->landmarks_3d = reinterpret_cast<const float*>(h + c->off_l3d);
+    out->landmarks_flag = reinterpret_cast<const uint8_t*>(h + c->off_flag);
+    out->count_3d = reinterpret_cast<const int*>(h + c->off_cnt);
     return OMNI_OK;
 }
 

@@ -192,6 +192,15 @@ namespace omni {
 int resize_unit_launch(const omni_resize* r, hipStream_t stream, const uint8_t* src_dev, int src_stride, int n_images, uint8_t* out_dev);
 }  // namespace omni
 
+namespace omni {
+// landmarks.hip: the stereo landmarks of n_pairs image pairs (landmark_plan.h) -- pair p = up image p of the *_up arrays and down image p of the *_down arrays,
+// key frame p / m.dirs_per_keyframe of poses7_dev.  Asynchronous on `stream`; the caller has checked the model (landmarks_check_model) and the sizes.
+int landmarks_launch(hipStream_t stream, const omni_stereo_model& m, const double* poses7_dev, int n_pairs, int max_num, const float* kps_up, const float* kps_down,
+                     const int* n_up, const int* n_down, const int* match_up, const int* match_down, const int* n_matches, float* norm_up, float* norm_down,
+                     float* l3d_up, float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int* count);
+int landmarks_check_model(const omni_stereo_model* m);
+}  // namespace omni
+
 // ---- 64-bit sortable keys -------------------------------------------------------------------------------------
 // key = (orderable(score) << 32) | (0xFFFFFFFF - id): descending key order == (score desc, id asc).
 __host__ __device__ static inline uint32_t omni_f32_orderable(float f) {

@@ -9,9 +9,10 @@ The reference runs these 8 + 4 engine calls and 4 matches strictly one after ano
 stream sync; here one key frame is three batched enqueues on one HIP stream (8 SuperPoint images, 4
 MobileNetVLAD images on a second stream, 4 descriptor-set pairs) with every intermediate resident in HBM and one small
 D2H at the end.
-Camera geometry (camodocal liftProjective, SVD triangulation, loop_cam.cpp:73-106,405-454,558-576) is host-side f64
-work outside the kernel scope and is left to the caller: the 2-D key points, descriptors, global
-descriptors and the up/down match lists are everything those steps consume.
+Camera geometry (liftProjective, SVD triangulation, loop_cam.cpp:73-106,405-454,558-576): for pinhole views a
+capi.StereoModel (stereo_model=) moves it into the unit -- f64 on the GPU (csrc/landmarks.hip), the key frame's
+pose_drone set with set_poses() before every key frame; without a model it is left to the caller, for whom the 2-D key
+points, descriptors, global descriptors and the up/down match lists are everything those steps consume.
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ class LoopCam:
     def __init__(self, ctx: capi.Context, sp_weights: dict, pca_comp, pca_mean, vlad_weights: dict, vlad_specs,
                  vlad_shape=(32, 112, 4096), width: int = 600, height: int = 480, thres: float = 0.015,
                  max_num: int = 200, precision: int = capi.PREC_F16, n_dirs: int = 4, fisheye: bool = True,
-                 accept_min_3d_pts: int = 0):
+                 accept_min_3d_pts: int = 0, stereo_model: capi.StereoModel = None):
         self.ctx, self.W, self.H, self.n_dirs, self.max_num, self.fisheye = ctx, width, height, n_dirs, max_num, fisheye
         self.accept_min_3d_pts = accept_min_3d_pts
         self.sp = capi.SuperPoint(ctx, sp_weights, pca_comp, pca_mean, width, height, thres, max_num, precision, 2 * n_dirs)
@@ -38,6 +39,13 @@ class LoopCam:
         self.dim = self.sp.desc_dim
         # the whole key frame as one asynchronous unit with a single pinned result block (csrc/cam.hip)
         self.cam = capi.Cam(self.sp, self.vlad, n_dirs, o, capi.BF_OPENCV)
+        self.stereo_model = stereo_model
+        if stereo_model is not None:
+            self.cam.set_stereo_model(stereo_model)
+
+    def set_poses(self, poses7):
+        """pose_drone (xyz + quaternion wxyz) of the key frames of the NEXT unit, [n_keyframes][7]: needed before every key frame when a stereo_model is set"""
+        self.cam.set_poses(poses7)
 
     def close(self):
         self.cam.close()
@@ -71,6 +79,14 @@ class LoopCam:
                            "scores": r["scores"][d, :nu].copy(), "landmark_num": nu, "image_desc": r["global_desc"][d].copy(),
                            "landmarks_2d_down": r["kps_xy"][n + d, :nd].copy(), "feature_descriptor_down": r["desc"][n + d, :nd].copy(),
                            "ids_up": r["match_up"][d, :k].copy(), "ids_down": r["match_down"][d, :k].copy(), "direction": d})
+        if self.stereo_model is not None:        # generate_stereo_image_descriptor's landmarks (:397-444), computed inside the unit
+            lm = self.cam.landmarks()
+            for d, im in enumerate(images):
+                nu, nd = int(nk[d]), int(nk[n + d])
+                im.update({"landmarks_2d_norm": lm["norm2d"][d, :nu].copy(), "landmarks_3d": lm["landmarks_3d"][d, :nu].copy(),
+                           "landmarks_flag": lm["landmarks_flag"][d, :nu].copy(), "landmarks_2d_norm_down": lm["norm2d"][n + d, :nd].copy(),
+                           "landmarks_3d_down": lm["landmarks_3d"][n + d, :nd].copy(), "landmarks_flag_down": lm["landmarks_flag"][n + d, :nd].copy(),
+                           "count_3d": int(lm["count_3d"][d])})
         return {"images": images, "landmark_num": int(sum(i["landmark_num"] for i in images))}
 
     def on_fisheye_images(self, up_raw: np.ndarray, down_raw: np.ndarray, undist_up, undist_down) -> dict:

@@ -72,6 +72,11 @@ public:
         bool geometry = false;
         double fx = 300, fy = 300, cx = 300, cy = 240, triangle_thres = 0.006, stereo_baseline = 0.10;
         int accept_min_3d_pts = 50;
+        // STEREO_FISHEYE / STEREO_PINHOLE with `geometry`: the lifting and the up/down triangulation of generate_stereo_image_descriptor (loop_cam.cpp:397-444) run
+        // inside the key-frame unit, f64 on the GPU (csrc/landmarks.hip: bit-identical to the host functions, tests/test_gpu_landmarks.py), and finish() copies the
+        // landmarks out of the unit's result block instead of submitting one triangulation task per direction.  Off: the host path (fill_stereo_landmarks on the
+        // geometry pool).  PINHOLE_DEPTH reads its landmarks from the depth image on the host either way.  (set_device_landmarks: before the first key frame.)
+        bool device_landmarks = true;
         // CameraConfig (loop_defines.h:111-116): STEREO_FISHEYE = 1 -- a key frame is 4 directions x (up, down) flattened views, the bottom quarter of
         // every view blanked; PINHOLE_DEPTH = 2 (launch/realsense.launch, BASELINE.json configs[0]: 640 x 480) -- a key frame is ONE gray image, not
         // blanked, plus its 16-bit depth image in millimetres (set_depth), MAX_DIRS = 1 (swarm_loop.cpp:279-280), the query image is direction 0
@@ -125,6 +130,7 @@ private:
         det_.stereo_fisheye = c.masked();
         geo_.MAX_DIRS = c.dirs();
         for (int p = 0; p < c.pipelines; ++p) lanes_.push_back(std::make_unique<Lane>(c, c.microbatch));
+        apply_stereo_model();
         if (c.geometry) {
             geo_.self_id = c.self_id; geo_.MIN_LOOP_NUM = c.min_loop_num; geo_.MIN_DIRECTION_LOOP = c.min_direction_loop;
             // Per candidate: (1) on this thread, the up to four direction pairs of compute_correspond_features (loop_detector.cpp:431-537) are
@@ -273,6 +279,7 @@ public:
     const std::vector<Candidate>& candidates() const { return candidates_; }
     // odometry poses of the key frames (VIO's pose_drone, swarm_loop.cpp:140-170 takes it from the key-frame message): key frame msg_id gets
     // poses7[msg_id - first_msg_id] = position xyz + quaternion wxyz; key frames outside the range keep the identity
+    PoseMsg pose_of(int64_t kf_id) const { return (kf_id >= pose_base_ && kf_id < pose_base_ + (int64_t)poses_.size()) ? poses_[(size_t)(kf_id - pose_base_)] : PoseMsg{}; }
     void set_poses(int64_t first_msg_id, const double* poses7, int64_t n) {
         pose_base_ = first_msg_id;
         poses_.resize((size_t)n);
@@ -305,6 +312,50 @@ public:
         return {{0, 0, (up ? 0.5 : -0.5) * cfg_.stereo_baseline}, geom::quat_from_R(R)};
     }
 
+    // ---- the stereo landmarks inside the key-frame unit (Config::device_landmarks) ----------------------------------------------------------------------
+    bool device_landmarks() const { return cfg_.device_landmarks && cfg_.geometry && cfg_.stereo() && !shard_; }      // (the sharded database builds no messages)
+    // what every lane's unit is given: the pinhole model, the accept rule and the extrinsics finish() stamps on the messages (as PoseMsg: to_pose normalises them)
+    omni_stereo_model stereo_model() const {
+        omni_stereo_model m{};
+        m.fx = cfg_.fx; m.fy = cfg_.fy; m.cx = cfg_.cx; m.cy = cfg_.cy; m.triangle_thres = cfg_.triangle_thres; m.accept_min_3d_pts = cfg_.accept_min_3d_pts;
+        m.dirs_per_keyframe = cfg_.dirs();
+        for (int d = 0; d < cfg_.dirs(); ++d)
+            for (int up = 0; up < 2; ++up) {
+                const PoseMsg e = to_msg(view_extrinsic(d, up != 0));
+                double* o = up ? m.up_extrinsic[d] : m.down_extrinsic[d];
+                std::copy(e.position, e.position + 3, o); std::copy(e.quat_wxyz, e.quat_wxyz + 4, o + 3);
+            }
+        return m;
+    }
+    // before the first key frame: switches the stage on or off on every lane (what the C entry point omni_pipeline_set_device_landmarks sets)
+    void set_device_landmarks(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_device_landmarks after the first key frame");
+        cfg_.device_landmarks = on;
+        apply_stereo_model();
+    }
+private:
+    struct Lane;
+    void apply_stereo_model(Lane& l) {
+        const omni_stereo_model m = stereo_model();
+        l.cam.set_stereo_model(device_landmarks() ? &m : nullptr);
+    }
+    void apply_stereo_model() {
+        for (auto& l : lanes_) apply_stereo_model(*l);
+        for (auto& t : tail_lanes_) apply_stereo_model(*t.second);
+    }
+    // pose_drone of the m key frames of the unit about to be enqueued on `lane` -- the PoseMsgs finish() stamps on its messages
+    void unit_poses(Lane* lane, int m, int64_t first_id) {
+        if (!device_landmarks()) return;
+        pose_stage_.resize((size_t)7 * m);
+        for (int k = 0; k < m; ++k) {
+            const PoseMsg p = lane->meta.empty() ? pose_of(first_id + k) : lane->meta[(size_t)k].pose;
+            std::copy(p.position, p.position + 3, pose_stage_.data() + 7 * k); std::copy(p.quat_wxyz, p.quat_wxyz + 4, pose_stage_.data() + 7 * k + 3);
+        }
+        lane->cam.set_poses(pose_stage_.data(), m);
+    }
+public:
+
     // STEREO_PINHOLE: the rig's two extrinsics (body -> camera, xyz + quaternion wxyz; swarm_loop.cpp:294-306) instead of the defaults.  Every key frame's
     // messages carry them, so they are fixed before the first key frame
     void set_stereo_extrinsics(const double* left7, const double* right7) {
@@ -314,6 +365,7 @@ public:
         if (!left7 || !right7) throw std::invalid_argument("set_stereo_extrinsics: null argument");
         std::copy(left7, left7 + 7, cfg_.left_extrinsic); std::copy(right7, right7 + 7, cfg_.right_extrinsic);
         cfg_.have_stereo_extrinsics = true;
+        apply_stereo_model();                                  // (the units triangulate from the same extrinsics the messages carry)
     }
 
     LoopDetectorCore& detector() { return det_; }
@@ -336,6 +388,7 @@ public:
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
         if (!shard_) throw std::runtime_error(std::string("omni_shard_create: ") + omni_last_error());
         world_ = world;
+        apply_stereo_model();                                  // (off: this mode builds no messages)
     }
     ~KeyframePipeline() { if (shard_) omni_shard_destroy(shard_); }
     int64_t db_rows() const { return shard_ ? omni_shard_ntotal(shard_) : det_.local_index.ntotal + det_.remote_index.ntotal; }
@@ -358,6 +411,7 @@ public:
     int run(int n_keyframes, int64_t first_msg_id, const uint8_t* const* pool, int n_pool, int first_slot, const uint8_t* tail, bool from_host) {
         if (open_ || !stream_pending_.empty()) throw std::runtime_error("run: key frames pushed through push_keyframe are still open -- flush() first");
         if (cfg_.camera_configuration == 0 && n_keyframes > 0) first_keyframe_seen_ = true;
+        if (n_keyframes > 0) any_keyframe_seen_ = true;
         const int MB = cfg_.microbatch, nd = cfg_.dirs();
         const int full = n_keyframes / MB, rem = n_keyframes % MB;
         // The units of this call.  Host blocks can be cut anywhere (a unit's upload is a list of segments: omni_cam_enqueue_host_parts), so a run that is not a
@@ -399,6 +453,7 @@ public:
             const int want = recut ? m : lane->mb;
             if (lane->cur != want) { lane->cam.set_active(nd * want); lane->cur = want; }     // (the streaming intake or a recut run may have left another size)
             chain(lane, fifo);
+            unit_poses(lane, want, first_msg_id + f0);
             if (recut) {
                 up.clear(); down.clear(); upn.clear(); downn.clear();
                 for (int f = f0; f < f0 + m;) {                                  // maximal runs of frames inside one block
@@ -464,7 +519,6 @@ public:
     };
 private:
     struct SlotMeta { int64_t msg_id = 0; double stamp = 0; PoseMsg pose; bool prevent_adding_db = false; const uint16_t* depth = nullptr; };
-    struct Lane;
 public:
     // The streaming intake (what a ROS callback calls per key frame; KeyframeIntake::extract in keyframe_intake.hpp): the images are packed into the
     // open micro-batch's pinned block and the call returns; the `microbatch`-th key frame sends the unit to the GPU (one upload, SuperPoint,
@@ -478,6 +532,7 @@ public:
         for (int i = 0; i < cams * nd; ++i) if (!k.images[i]) throw std::invalid_argument("push_keyframe: a null image pointer");
         const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         if (cfg_.camera_configuration == 0) first_keyframe_seen_ = true;      // (set_stereo_extrinsics is refused from here on)
+        any_keyframe_seen_ = true;
         int hits = carried_hits_; carried_hits_ = 0;
         // whatever throws below: the candidates counted so far are not lost -- they go back into carried_hits_ and the next call returns them
         struct Carry { int& hits; int& carried; bool ok = false; ~Carry() { if (!ok) carried += hits; } } carry{hits, carried_hits_};
@@ -552,7 +607,7 @@ public:
         const int rem = n_keyframes % cfg_.microbatch;
         if (!rem) return nullptr;
         auto it = tail_lanes_.find(rem);
-        if (it == tail_lanes_.end()) it = tail_lanes_.emplace(rem, std::make_unique<Lane>(cfg_, rem)).first;
+        if (it == tail_lanes_.end()) { it = tail_lanes_.emplace(rem, std::make_unique<Lane>(cfg_, rem)).first; apply_stereo_model(*it->second); }
         return it->second.get();
     }
 
@@ -598,6 +653,7 @@ private:
             if (rem < MB && cfg_.stereo()) std::memmove(u->stage + (size_t)nd * rem * img, u->stage + (size_t)nd * MB * img, (size_t)nd * rem * img);
             if (u->cur != rem) { u->cam.set_active(nd * rem); u->cur = rem; }
             chain(u, fifo_cfg_ >= 0 ? fifo_cfg_ : (cfg_.precision == OMNI_PREC_F16 ? 0 : 1));
+            unit_poses(u, rem, 0);
             if (cfg_.raw()) u->cam.enqueue_raw_host(u->resize->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.src_width, rem);
             else u->cam.enqueue_host(u->stage, cfg_.width, cfg_.masked());
         } catch (...) { u->meta.clear(); throw; }
@@ -666,12 +722,11 @@ private:
     // buffer in HBM ([4*mb][4096], key-frame major) -- wait() has synchronised with the MobileNetVLAD stream
     int finish(Lane& lane, int64_t first_id) {
         auto t_a = std::chrono::steady_clock::now();
-        omni_trace_push("host: wait for the unit's GPU work");
-        const omni_cam_result r = lane.cam.wait();
-        omni_trace_pop();
+        struct Range { explicit Range(const char* n) { omni_trace_push(n); } ~Range() { omni_trace_pop(); } };
+        const omni_cam_result r = [&lane] { Range range_wait("host: wait for the unit's GPU work"); return lane.cam.wait(); }();
         host_ms_[1] += since(t_a); ++host_units_;
         t_a = std::chrono::steady_clock::now();
-        struct Range { explicit Range(const char* n) { omni_trace_push(n); } ~Range() { omni_trace_pop(); } } range_rest("host: messages + detector step of the unit");
+        Range range_rest("host: messages + detector step of the unit");
         if (shard_) {
             // the exchange of THIS micro-batch is enqueued (two collectives, the scan, the copy of the lists: no host wait) and its results are
             // collected when the NEXT micro-batch gets here (or at the end of run()): meanwhile the host enqueues the next CNN unit
@@ -689,16 +744,20 @@ private:
         // lifted points per image -- is copied into the frames the detector now holds while its searches run on the GPU.  With the geometry stage the landmarks
         // can change landmark_num (generate_gray_depth_image_descriptor drops an image below ACCEPT_MIN_3D_PTS): everything is built first, as before.
         const bool defer_heavy = !cfg_.geometry;
+        // the unit's own landmarks (Config::device_landmarks): lifted floats, 3-D points and flags of every image, already in the pinned block
+        const bool dev_lm = device_landmarks();
+        const omni_cam_landmarks_result lmr = dev_lm ? lane.cam.landmarks() : omni_cam_landmarks_result{};
         auto heavy = [&](ImageDescriptor& im, int i) {
-            fill_image_descriptor(im, r.kps_xy + (size_t)i * M * 2, r.n_kps[i], r.desc + (size_t)i * M * D, D, r.global_desc + (size_t)i * G, G, lift64_);
+            if (dev_lm) fill_image_descriptor_device(im, r.kps_xy + (size_t)i * M * 2, r.n_kps[i], r.desc + (size_t)i * M * D, D, r.global_desc + (size_t)i * G, G,
+                                                     lmr.norm2d + (size_t)i * M * 2, lmr.landmarks_3d + (size_t)i * M * 3, lmr.landmarks_flag + (size_t)i * M);
+            else fill_image_descriptor(im, r.kps_xy + (size_t)i * M * 2, r.n_kps[i], r.desc + (size_t)i * M * D, D, r.global_desc + (size_t)i * G, G, lift64_);
         };
         for (int m = 0; m < lane.cur; ++m) {
             FisheyeFrameDescriptor& f = frames_[m];
             const bool streamed = !lane.meta.empty();
             const int64_t kf_id = streamed ? lane.meta[m].msg_id : first_id + m;
             const double stamp = streamed ? lane.meta[m].stamp : (double)kf_id;
-            const PoseMsg pose = streamed ? lane.meta[m].pose
-                                          : (kf_id >= pose_base_ && kf_id < pose_base_ + (int64_t)poses_.size()) ? poses_[(size_t)(kf_id - pose_base_)] : PoseMsg{};
+            const PoseMsg pose = streamed ? lane.meta[m].pose : pose_of(kf_id);
             f.prevent_adding_db = streamed && lane.meta[m].prevent_adding_db;
             f.images.resize(nd);
             for (int d = 0; d < nd; ++d) {
@@ -719,6 +778,12 @@ private:
                     ImageDescriptor& down = downs_[(size_t)i];
                     down = ImageDescriptor{};
                     const int j = n + i;
+                    if (dev_lm) {                                                    // both messages are complete as they come out of the block: no task
+                        fill_image_descriptor_device(down, r.kps_xy + (size_t)j * M * 2, r.n_kps[j], nullptr, D, nullptr, 0, lmr.norm2d + (size_t)j * M * 2,
+                                                     lmr.landmarks_3d + (size_t)j * M * 3, lmr.landmarks_flag + (size_t)j * M);
+                        stamp_image_descriptor(down, stamp, cfg_.self_id, to_msg(view_extrinsic(d, false)), pose, kf_id);
+                        continue;
+                    }
                     fill_image_descriptor(down, r.kps_xy + (size_t)j * M * 2, r.n_kps[j], nullptr, D, nullptr, 0, lift64_);     // (its descriptors were matched on the device)
                     stamp_image_descriptor(down, stamp, cfg_.self_id, to_msg(view_extrinsic(d, false)), pose, kf_id);
                     auto tri = [this, &im, &down, r, i, M] {
@@ -828,6 +893,8 @@ private:
     size_t next_lane_ = 0;
     int carried_hits_ = 0;
     bool first_keyframe_seen_ = false;          // STEREO_PINHOLE: set_stereo_extrinsics is refused from the first key frame on
+    bool any_keyframe_seen_ = false;            // set_device_landmarks is refused from the first key frame on
+    std::vector<double> pose_stage_;            // unit_poses: the unit's poses on their way into the handle's pinned staging
     std::vector<FisheyeFrameDescriptor> frames_;
     std::unique_ptr<IndexFlatIP> shard_index_;
     omni_shard* shard_ = nullptr;

@@ -55,6 +55,24 @@ inline void fill_image_descriptor(ImageDescriptor& im, const float* kps_xy, int 
     im.landmarks_3d.assign((size_t)n, Point3f{});
     im.landmarks_flag.assign((size_t)n, 0);
 }
+// The same message from a key-frame unit that ran the stereo-landmark stage itself (omni_cam_landmarks: csrc/landmarks.hip): the lifted floats, the 3-D
+// landmarks and the flags are copied from the unit's result block -- norm2d [n][2], l3d [n][3], flag [n] of this image -- instead of being computed here;
+// bit for bit what fill_image_descriptor + fill_stereo_landmarks leave in both messages of a direction for a pinhole lift.
+inline void fill_image_descriptor_device(ImageDescriptor& im, const float* kps_xy, int n, const float* desc, int desc_dim, const float* global_desc, int global_dim,
+                                         const float* norm2d, const float* l3d, const uint8_t* flag) {
+    im.landmark_num = n;
+    im.landmarks_2d.resize((size_t)n);
+    for (int k = 0; k < n; ++k) im.landmarks_2d[(size_t)k] = {kps_xy[2 * k], kps_xy[2 * k + 1]};
+    if (desc) im.feature_descriptor.assign(desc, desc + (size_t)n * desc_dim); else im.feature_descriptor.clear();
+    if (global_desc) im.image_desc.assign(global_desc, global_desc + global_dim); else im.image_desc.clear();
+    im.landmarks_2d_norm.resize((size_t)n);
+    im.landmarks_3d.resize((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        im.landmarks_2d_norm[(size_t)k] = {norm2d[2 * k], norm2d[2 * k + 1]};
+        im.landmarks_3d[(size_t)k] = {l3d[3 * k], l3d[3 * k + 1], l3d[3 * k + 2]};
+    }
+    im.landmarks_flag.assign(flag, flag + n);
+}
 // The per-image fields generate_stereo_image_descriptor stamps on both messages of a direction (loop_cam.cpp:362-374)
 inline void stamp_image_descriptor(ImageDescriptor& im, double stamp, int self_id, const PoseMsg& camera_extrinsic, const PoseMsg& pose_drone, int64_t keyframe_id) {
     im.timestamp = stamp; im.drone_id = self_id; im.camera_extrinsic = camera_extrinsic; im.pose_drone = pose_drone; im.frame_id = keyframe_id;

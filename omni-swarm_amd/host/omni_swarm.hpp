@@ -277,7 +277,8 @@ private:
 // The CNN + matching part of LoopCam::on_flattened_images (loop_cam.cpp:178-229): SuperPoint on the 2*n_dirs images of one
 // fisheye key frame (up cameras, then down cameras), MobileNetVLAD on the n_dirs up images, BFMatcher(L2, crossCheck) up <->
 // down per direction -- one asynchronous unit on the GPU (omni_cam_*), results in one pinned host block.  The reference runs
-// these 12 engine calls and 4 matches strictly serially; camera lifting / triangulation stay in LoopCam.
+// these 12 engine calls and 4 matches strictly serially; camera lifting / triangulation run inside the unit for a pinhole model
+// (set_stereo_model) and stay in LoopCam otherwise.
 //   superpoint_net must have been created with max_batch >= 2*n_dirs (on sp_ctx), netvlad_net with max_batch >= n_dirs (on
 //   vlad_ctx; a second Context = a second HIP stream lets the two networks overlap).
 class LoopCamHIP {
@@ -355,6 +356,15 @@ public:
     void order_after(LoopCamHIP& earlier, int streams) { check(omni_cam_order_after(h_, earlier.h_, streams), "omni_cam_order_after"); }
     // a unit of fewer directions than this object was created for (omni_cam_set_active): the next enqueues read cams * n_dirs images
     void set_active(int n_dirs) { check(omni_cam_set_active(h_, n_dirs), "omni_cam_set_active"); }
+    // the stereo landmarks of a pinhole model inside the unit (csrc/landmarks.hip; loop_cam.cpp:397-444): set_stereo_model once (nullptr: off again), set_poses
+    // (pose_drone of the next unit's key frames, [n_keyframes][7] xyz + quaternion wxyz) before every enqueue, landmarks() after wait()
+    void set_stereo_model(const omni_stereo_model* model) { check(omni_cam_set_stereo_model(h_, model), "omni_cam_set_stereo_model"); }
+    void set_poses(const double* poses7, int n_keyframes) { check(omni_cam_set_poses(h_, poses7, n_keyframes), "omni_cam_set_poses"); }
+    omni_cam_landmarks_result landmarks() {
+        omni_cam_landmarks_result r{};
+        check(omni_cam_landmarks(h_, &r), "omni_cam_landmarks");
+        return r;
+    }
     // non-blocking: would wait() return at once?
     bool ready() { int r = 0; check(omni_cam_ready(h_, &r), "omni_cam_ready"); return r != 0; }
     // blocks until the key frame is done; pointers stay valid until the next enqueue on this object

@@ -23,7 +23,11 @@ SYMBOLS = ["omni_pipeline_last_error", "omni_pipeline_create", "omni_pipeline_de
 STEREO_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_stereo.so")
 STEREO_SYMBOLS = ["omni_stereo_last_error", "omni_pipeline_create_stereo_pinhole", "omni_pipeline_set_stereo_extrinsics"]
 _lib = None
+# where the pipeline computes its stereo landmarks: include/omni_host_landmarks.h, lib/libomni_host_landmarks.so (the same handle)
+LANDMARKS_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_landmarks.so")
+LANDMARKS_SYMBOLS = ["omni_landmarks_last_error", "omni_pipeline_set_device_landmarks"]
 _stereo_lib = None
+_landmarks_lib = None
 
 
 def lib():
@@ -119,16 +123,31 @@ def swarm_params_table():
     return [tuple(l.split("\t")) if l.count("\t") == 2 else tuple(l.split("\t")) + ("",) for l in buf.value.decode().split("\n") if l]
 
 
+def landmarks_lib():
+    global _landmarks_lib
+    if _landmarks_lib is None:
+        lib()                                   # (libomni_hip.so / OMNI_LIB first, as for the other host libraries)
+        if not os.path.exists(LANDMARKS_LIB_PATH):
+            raise OSError(f"{LANDMARKS_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(LANDMARKS_LIB_PATH)
+        L.omni_landmarks_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_device_landmarks.argtypes = [C.c_void_p, C.c_int]
+        _landmarks_lib = L
+    return _landmarks_lib
+
+
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None):
+                 stereo_pinhole=None, device_landmarks=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
         frame per key frame, of src_width x src_height (the camera's size: resized to width x height inside every unit, on the GPU) or, without them, of
         the networks' size; fx fy cx cy are those of the width x height image.  set_stereo_extrinsics gives the rig's two extrinsics.
+        device_landmarks: True / False = the stereo landmarks of a `geometry` pipeline inside the key-frame unit on the GPU / on the host's geometry
+        threads (the same bits either way); None: the library's default.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -151,6 +170,13 @@ class KeyframePipeline:
         self._depth = None
         if not self.h:
             raise _err("omni_pipeline_create")
+        if device_landmarks is not None:
+            self.set_device_landmarks(device_landmarks)
+
+    def set_device_landmarks(self, on: bool):
+        """before the first key frame: stereo landmarks inside the key-frame unit (GPU) or on the host's geometry threads"""
+        if landmarks_lib().omni_pipeline_set_device_landmarks(self.h, int(bool(on))):
+            raise capi.OmniError(f"omni_pipeline_set_device_landmarks: {landmarks_lib().omni_landmarks_last_error().decode()}")
 
     @classmethod
     def from_launch(cls, device: int, launch_xml: str, sp_weights_path: str, vlad_weights_path: str, pca_comp_csv: str | None = None, pca_mean_csv: str | None = None,

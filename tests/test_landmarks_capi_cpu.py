@@ -1,0 +1,100 @@
+"""CPU-side checks of what the stereo-landmark stage adds to the C boundaries (no GPU): include/omni_host_landmarks.h is valid C99, libomni_host_landmarks.so exports
+exactly what it declares and pipeline.py binds exactly that, a C program built with gcc alone links against it; libomni_hip.so exports the four new entries of
+include/omni_hip.h, which refuse bad arguments with a code and a message; the C++ adapters compile from a plain C++ program; the arithmetic lives in one header."""
+import ctypes
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "omni-swarm_amd")
+LIBDIR = os.path.join(PKG, "lib")
+NEW = {"omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks"}
+
+
+def test_landmarks_host_library_exports_what_its_c_header_declares():
+    hdr_path = os.path.join(ROOT, "include", "omni_host_landmarks.h")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", hdr_path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    text = re.sub(r"/\*.*?\*/", "", open(hdr_path).read(), flags=re.S)
+    declared = set(re.findall(r"\b(omni_[a-z0-9_]+)\s*\(", text))
+    lib = os.path.join(LIBDIR, "libomni_host_landmarks.so")
+    assert os.path.exists(lib), "libomni_host_landmarks.so missing: run __graft_entry__.build()"
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True).stdout
+    exported = {l.split()[-1] for l in nm.splitlines() if l.split() and l.split()[-1].startswith("omni_") and " T " in l}
+    assert declared == exported, (sorted(declared - exported), sorted(exported - declared))
+    from omni_swarm_amd import pipeline
+    assert set(pipeline.LANDMARKS_SYMBOLS) == declared == {"omni_landmarks_last_error", "omni_pipeline_set_device_landmarks"}
+    L = pipeline.landmarks_lib()
+    assert all(hasattr(L, s) for s in declared)
+    assert L.omni_pipeline_set_device_landmarks(None, 1) == 1 and b"null pipeline" in L.omni_landmarks_last_error()      # a code and a message, not an abort
+
+
+def test_a_c_program_links_and_calls_the_library(tmp_path):
+    src = tmp_path / "lm.c"
+    src.write_text('#include <stdio.h>\n#include <string.h>\n#include "omni_host_landmarks.h"\n'
+                   'int main(void) {\n'
+                   '    if (strlen(omni_landmarks_last_error()) != 0) return 1;                /* no failure yet on this thread */\n'
+                   '    if (omni_pipeline_set_device_landmarks(NULL, 1) != 1) return 2;\n'
+                   '    printf("%s\\n", omni_landmarks_last_error());\n'
+                   '    return 0;\n}\n')
+    exe = tmp_path / "lm"
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe), "-L", LIBDIR,
+                        "-lomni_host_landmarks", "-Wl,-rpath," + LIBDIR], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "null pipeline" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
+def test_new_entries_of_the_hip_library_are_declared_exported_bound_and_refuse_bad_arguments(omni):
+    c = omni.capi
+    L = c.lib()
+    hdr = open(os.path.join(ROOT, "include", "omni_hip.h")).read()
+    assert NEW <= set(re.findall(r"\b(omni_[a-z0-9_]+)\s*\(", hdr)) and NEW <= set(c.SYMBOLS) and all(hasattr(L, s) for s in NEW)
+    assert "#define OMNI_ABI_VERSION 2 " in hdr and L.omni_abi_version() == 2                 # additions only
+    assert ctypes.sizeof(c.StereoModel) == 5 * 8 + 2 * 4 + 2 * c.STEREO_MAX_DIRS * 7 * 8 and c.STEREO_MAX_DIRS == int(re.search(r"#define OMNI_STEREO_MAX_DIRS (\d+)", hdr).group(1))
+    m = c.stereo_model(300, 300, 300, 240, 0.006, 50, [[0, 0, 0, 1, 0, 0, 0]] * 4, [[0, 0, -0.1, 1, 0, 0, 0]] * 4)
+    assert m.dirs_per_keyframe == 4 and list(m.down_extrinsic[3]) == [0, 0, -0.1, 1, 0, 0, 0]
+    assert L.omni_landmarks_enqueue_dev(None, ctypes.byref(m), None, 4, 4, 100, *([None] * 9)) == c.ERR_INVALID and b"null" in L.omni_last_error()
+    assert L.omni_cam_set_stereo_model(None, ctypes.byref(m)) == c.ERR_INVALID
+    assert L.omni_cam_set_poses(None, None, 1) == c.ERR_INVALID
+    assert L.omni_cam_landmarks(None, None) == c.ERR_INVALID
+
+
+def test_the_arithmetic_is_stated_once():
+    """landmark_plan.h is plain C++ for both compilers (no HIP header, no containers); the kernel and the unit only call it"""
+    plan = open(os.path.join(PKG, "csrc", "landmark_plan.h")).read()
+    code = re.sub(r"//.*", "", plan)
+    for word in ("hip/", "common.h", "std::vector", "std::function", "std::sort", "<vector>", "<functional>", "<algorithm>"):
+        assert word not in code, word
+    assert "#pragma clang fp contract(off)" in plan
+    assert "build/landmarks.o: HIPFLAGS += -ffp-contract=off" in open(os.path.join(PKG, "Makefile")).read()
+    for f in ("landmarks.hip", "cam.hip"):
+        text = re.sub(r"//.*", "", open(os.path.join(PKG, "csrc", f)).read())
+        assert "sqrt" not in text and "fabs" not in text, f
+
+
+def test_cpp_adapters_compile_from_a_plain_cpp_program(tmp_path):
+    """LoopCamHIP::set_stereo_model / set_poses / landmarks (host/omni_swarm.hpp) and KeyframePipeline::Config::device_landmarks are plain C++17 over the C ABI"""
+    src = tmp_path / "adapters.cpp"
+    src.write_text('#include "keyframe_pipeline.hpp"\n'
+                   'int main() {\n'
+                   '    omni::KeyframePipeline::Config c;\n'
+                   '    const bool dflt = c.device_landmarks;\n'
+                   '    c.device_landmarks = !dflt;\n'
+                   '    void (omni::LoopCamHIP::*a)(const omni_stereo_model*) = &omni::LoopCamHIP::set_stereo_model;\n'
+                   '    void (omni::LoopCamHIP::*b)(const double*, int) = &omni::LoopCamHIP::set_poses;\n'
+                   '    omni_cam_landmarks_result (omni::LoopCamHIP::*l)() = &omni::LoopCamHIP::landmarks;\n'
+                   '    void (omni::KeyframePipeline::*s)(bool) = &omni::KeyframePipeline::set_device_landmarks;\n'
+                   '    omni::ImageDescriptor im;\n'
+                   '    const float k[2] = {3, 4}, n2[2] = {0.5f, 0.25f}, p3[3] = {1, 2, 3};\n'
+                   '    const uint8_t f[1] = {1};\n'
+                   '    omni::fill_image_descriptor_device(im, k, 1, nullptr, 0, nullptr, 0, n2, p3, f);\n'
+                   '    if (im.landmark_num != 1 || im.landmarks_2d_norm[0].y != 0.25f || im.landmarks_3d[0].z != 3 || im.landmarks_flag[0] != 1) return 1;\n'
+                   '    return a && b && l && s ? 0 : 2;\n}\n')
+    exe = tmp_path / "adapters"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKG, "host"), str(src), "-o", str(exe),
+                        "-L", LIBDIR, "-lomni_hip", "-Wl,-rpath," + LIBDIR], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
