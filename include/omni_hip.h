@@ -472,6 +472,34 @@ typedef struct omni_cam_landmarks_result {      /* pointers into the handle's pi
 /* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran without a model */
 int omni_cam_landmarks(omni_cam* cam, omni_cam_landmarks_result* out);
 
+/* ---- loop verification: the homography RANSAC of compute_correspond_features (loop_detector.cpp:574-598: the 3-D-flag filter, then
+ * cv::findHomography(old_2d, new_2d, RANSAC, 3, mask)) on the GPU, f64 (csrc/homography.hip; the arithmetic: csrc/ransac_plan.h, operation for operation
+ * that of host/geometry.hpp's find_homography_ransac -- the same mask, the same best model).  Per pair:
+ *   status  OMNI_HG_UNFILTERED  fewer than 4 points: nothing was estimated (the reference keeps the flagged matches as they are);
+ *           OMNI_HG_OK          mask[i] = 1 for the inliers of the best model, H = that model (9 doubles, row major, H[8] = 1);
+ *           OMNI_HG_NO_MODEL    the host function's `false`: mask all 0;
+ *           OMNI_HG_HOST        the device gave up on degenerate input (more than 256 attempts for one subset, or more than 262 144 random numbers):
+ *                               run the host function for this pair.
+ *   info    {count, iterations run, iteration of the best model (-1: none), inliers of the best model}. */
+#define OMNI_HG_UNFILTERED 0
+#define OMNI_HG_OK 1
+#define OMNI_HG_NO_MODEL 2
+#define OMNI_HG_HOST 3
+/* The RANSAC kernel alone on point lists from the host: src_xy / dst_xy [n_pairs][max_n][2] float (pair p: the OLD and the NEW image's pixels of its count[p]
+ * correspondences), count [n_pairs] in [0, max_n].  Outputs (host): status [n_pairs], mask [n_pairs][max_n] u8 (zeros behind count), H [n_pairs][9],
+ * info [n_pairs][4].  1 <= n_pairs <= 64, 1 <= max_n <= 1024.  Blocking. */
+int omni_homography_ransac_multi(omni_ctx* ctx, int n_pairs, int max_n, const float* src_xy, const float* dst_xy, const int* count, int* status, uint8_t* mask,
+                                 double* H, int* info);
+/* omni_bf_match_multi followed, in the same round trip (one upload, four launches, one download), by the flag filter and the RANSAC of every pair: besides
+ * omni_bf_match_multi's arguments, per pair q_xy[p] [nq[p]][2] / t_xy[p] [nt[p]][2] = landmarks_2d of the new (query) and the old (train) image and
+ * q_flags[p] [n_flags[p]] = landmarks_flag of the new image (n_flags[p] in [0, max_n]; q_flags[p] may be NULL when it is 0).  Match i of pair p is kept
+ * when q_idx[i] < n_flags[p] && q_flags[p][q_idx[i]], in match order.  Further outputs (host): kept [n_pairs][max_n] = the positions in the match list of
+ * the n_kept[p] matches kept; mask [n_pairs][max_n] over the KEPT list; H, info, status as above (count = n_kept[p]).  The stop rule's table (count x inliers
+ * -> iterations, evaluated on the host with its own pow / log) is kept in HBM per context and grows with the largest max_n seen. */
+int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* const* q_host, const int* nq, const float* const* t_host, const int* nt, int dim,
+                                   int mode, int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags,
+                                   int* q_idx, int* t_idx, float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,9 @@ SYMBOLS = [
     "omni_shard_search", "omni_flatten_create", "omni_flatten_destroy", "omni_flatten_out_bytes", "omni_flatten_enqueue_dev",
     "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
     "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
+    "omni_homography_ransac_multi", "omni_bf_match_homography_multi",
 ]
+HG_UNFILTERED, HG_OK, HG_NO_MODEL, HG_HOST = 0, 1, 2, 3     # include/omni_hip.h OMNI_HG_*: the status of one pair's homography RANSAC
 
 
 class OmniError(RuntimeError):
@@ -204,6 +206,9 @@ def lib():
     sig("omni_cam_enqueue_raw_host", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int])
     sig("omni_cam_enqueue_raw_host_parts", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int])
     sig("omni_cam_wait", C.c_int, [_vp, C.POINTER(_CamResult)])
+    sig("omni_homography_ransac_multi", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _ip, _ip, _vp, C.POINTER(C.c_double), _ip])
+    sig("omni_bf_match_homography_multi", C.c_int, [_vp, C.c_int, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
+                                                  C.POINTER(_vp), _ip, _ip, _ip, _fp, _ip, _ip, _ip, _vp, C.POINTER(C.c_double), _ip, _ip])
     sig("omni_landmarks_enqueue_dev", C.c_int, [_vp, C.POINTER(StereoModel), _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
     sig("omni_cam_set_stereo_model", C.c_int, [_vp, C.POINTER(StereoModel)])
     sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
@@ -891,6 +896,45 @@ def bf_match_multi(ctx: Context, pairs, mode: int = BF_OPENCV):
     _check(lib().omni_bf_match_multi(ctx.h, P, qp, nq.ctypes.data_as(_ip), tp, nt.ctypes.data_as(_ip), dim, mode, max_n, qi.ctypes.data_as(_ip),
                                      ti.ctypes.data_as(_ip), _pf(dd), n.ctypes.data_as(_ip)))
     return [(qi[p, :n[p]].copy(), ti[p, :n[p]].copy(), dd[p, :n[p]].copy()) for p in range(P)]
+
+
+def homography_ransac_multi(ctx: Context, pairs) -> list:
+    """[(src_xy, dst_xy), ...] ([n][2] float pixels of the old / the new image) -> [{status, mask [n], H [9], info [4]}]: cv::findHomography(src, dst, RANSAC, 3, mask)
+    of every pair in one GPU round trip (omni_homography_ransac_multi); status is one of HG_*"""
+    P = len(pairs)
+    count = np.array([len(a) for a, _ in pairs], np.int32)
+    max_n = int(max(1, count.max()))
+    src, dst = np.zeros((P, max_n, 2), np.float32), np.zeros((P, max_n, 2), np.float32)
+    for p, (a, b) in enumerate(pairs):
+        src[p, :count[p]], dst[p, :count[p]] = _f32(a).reshape(-1, 2), _f32(b).reshape(-1, 2)
+    status, mask, H, info = np.zeros(P, np.int32), np.zeros((P, max_n), np.uint8), np.zeros((P, 9), np.float64), np.zeros((P, 4), np.int32)
+    _check(lib().omni_homography_ransac_multi(ctx.h, P, max_n, _pf(src), _pf(dst), count.ctypes.data_as(_ip), status.ctypes.data_as(_ip), mask.ctypes.data,
+                                              H.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(_ip)))
+    return [{"status": int(status[p]), "mask": mask[p, :count[p]].copy(), "H": H[p].copy(), "info": info[p].copy()} for p in range(P)]
+
+
+def bf_match_homography_multi(ctx: Context, pairs, mode: int = BF_OPENCV) -> list:
+    """[(q_desc, t_desc, q_xy, t_xy, q_flags), ...] -> per pair {q_idx, t_idx, dist (bf_match's), kept (positions in the match list of the matches whose query key
+    point is flagged), mask (over kept), H, info, status}: the matcher, the flag filter and the homography RANSAC of compute_correspond_features in one GPU round
+    trip (omni_bf_match_homography_multi)"""
+    P = len(pairs)
+    qs, ts = [_f32(x[0]) for x in pairs], [_f32(x[1]) for x in pairs]
+    qx, tx = [_f32(x[2]).reshape(-1, 2) for x in pairs], [_f32(x[3]).reshape(-1, 2) for x in pairs]
+    fl = [np.ascontiguousarray(x[4], np.uint8) for x in pairs]
+    dim = next((a.shape[1] for a in qs + ts if a.ndim == 2 and a.shape[0]), 64)
+    nq, nt = np.array([q.shape[0] for q in qs], np.int32), np.array([t.shape[0] for t in ts], np.int32)
+    nf = np.array([f.shape[0] for f in fl], np.int32)
+    max_n = int(max(1, nq.max(), nt.max(), nf.max()))
+    ptrs = lambda arrs: (_fp * P)(*[_pf(a) if a.shape[0] else None for a in arrs])
+    fp = (_vp * P)(*[f.ctypes.data if f.shape[0] else None for f in fl])
+    qi, ti, dd, n = np.zeros((P, max_n), np.int32), np.zeros((P, max_n), np.int32), np.zeros((P, max_n), np.float32), np.zeros(P, np.int32)
+    kept, nk, mask = np.zeros((P, max_n), np.int32), np.zeros(P, np.int32), np.zeros((P, max_n), np.uint8)
+    H, info, status = np.zeros((P, 9), np.float64), np.zeros((P, 4), np.int32), np.zeros(P, np.int32)
+    ip = lambda a: a.ctypes.data_as(_ip)
+    _check(lib().omni_bf_match_homography_multi(ctx.h, P, ptrs(qs), ip(nq), ptrs(ts), ip(nt), dim, mode, max_n, ptrs(qx), ptrs(tx), fp, ip(nf), ip(qi), ip(ti), _pf(dd), ip(n),
+                                                ip(kept), ip(nk), mask.ctypes.data, H.ctypes.data_as(C.POINTER(C.c_double)), ip(info), ip(status)))
+    return [{"q_idx": qi[p, :n[p]].copy(), "t_idx": ti[p, :n[p]].copy(), "dist": dd[p, :n[p]].copy(), "kept": kept[p, :nk[p]].copy(), "mask": mask[p, :nk[p]].copy(),
+             "H": H[p].copy(), "info": info[p].copy(), "status": int(status[p])} for p in range(P)]
 
 
 def bf_match_batched_dev(ctx: Context, n_pairs, max_n, dim, mode, q_dev, q_stride, nq_dev, t_dev, t_stride, nt_dev,

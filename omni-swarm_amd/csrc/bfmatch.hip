@@ -169,7 +169,8 @@ bf_cross_kernel(int max_n, int mode, const int* __restrict__ nq_arr, const int* 
     }
 }
 
-static int bf_launch(omni_ctx* ctx, int n_pairs, int max_n, int dim, int mode, const float* q, int64_t qs, const int* nq,
+// (homography.hip's fused entry launches the same pair of kernels)
+int bf_launch(omni_ctx* ctx, int n_pairs, int max_n, int dim, int mode, const float* q, int64_t qs, const int* nq,
                      const float* t, int64_t ts, const int* nt, int* oq, int* ot, float* od, int* on) {
     OMNI_REQUIRE(dim >= 4 && dim % 4 == 0 && dim <= BF_MAX_DIM, OMNI_ERR_INVALID, "dim=%d must be a multiple of 4 in [4,%d]", dim, BF_MAX_DIM);
     OMNI_REQUIRE(max_n >= 1 && max_n <= BF_MAX_N, OMNI_ERR_CAPACITY, "max_n=%d outside [1,%d]", max_n, BF_MAX_N);

@@ -146,6 +146,8 @@ struct omni_ctx {
     omni::DevBuf scratch;     // generic per-call scratch (bf match, host-entry staging)
     omni::DevBuf scratch2;
     omni::HostBuf hstage;
+    omni::DevBuf ransac_T;    // homography.hip: the stop rule's table T[count][good] for count <= ransac_T_n (csrc/ransac_plan.h), filled once
+    int ransac_T_n = 0;
     int ensure_zero_page() {
         if (zero_page) return OMNI_OK;
         OMNI_HIP_TRY(hipMalloc(&zero_page, OMNI_ZERO_PAGE_BYTES));

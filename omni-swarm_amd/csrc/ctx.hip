@@ -97,7 +97,7 @@ void omni_ctx_destroy(omni_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->scratch.release(); c->scratch2.release(); c->hstage.release();
+    c->scratch.release(); c->scratch2.release(); c->hstage.release(); c->ransac_T.release();
     if (c->zero_page) (void)hipFree(c->zero_page);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

@@ -6,6 +6,7 @@
 // serially, one blocking engine call at a time.  This is the host loop bench.py times (through host_capi.cpp); Python only
 // prepares the synthetic inputs and brackets the run with the barrier.
 #pragma once
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -77,6 +78,12 @@ public:
         // landmarks out of the unit's result block instead of submitting one triangulation task per direction.  Off: the host path (fill_stereo_landmarks on the
         // geometry pool).  PINHOLE_DEPTH reads its landmarks from the depth image on the host either way.  (set_device_landmarks: before the first key frame.)
         bool device_landmarks = true;
+        // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
+        // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
+        // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
+        // that is NOT a loop.  A pair the device hands back (degenerate points: status HOST) runs on the host as before.  Off: the host path for every pair.
+        // On by default: DESIGN.md section 0.2b has the gates and the measurements.  (set_device_homography: any time between two calls.)
+        bool device_homography = true;
         // CameraConfig (loop_defines.h:111-116): STEREO_FISHEYE = 1 -- a key frame is 4 directions x (up, down) flattened views, the bottom quarter of
         // every view blanked; PINHOLE_DEPTH = 2 (launch/realsense.launch, BASELINE.json configs[0]: 640 x 480) -- a key frame is ONE gray image, not
         // blanked, plus its 16-bit depth image in millimetres (set_depth), MAX_DIRS = 1 (swarm_loop.cpp:279-280), the query image is direction 0
@@ -193,6 +200,8 @@ public:
         if (deferred_.empty()) return false;
         struct Prepared { size_t first = 0, count = 0; };
         std::vector<BFMatcherL2X::Pair> pairs;
+        std::vector<BFMatcherL2X::PairH> pairs_h;                    // device_homography: the same pairs with their 2-D points and flags
+        const bool dev_hg = device_homography();
         std::vector<int> pair_dim;                                   // descriptor length of every pair (one match_multi call per distinct length)
         std::vector<Prepared> prep(deferred_.size());
         const int nd = geo_.MAX_DIRS;
@@ -207,24 +216,32 @@ public:
                     const int nx = (int)x.landmarks_2d.size(), ny = (int)y.landmarks_2d.size();
                     if (nx > 0 && ny > 0 && x.feature_descriptor.size() % nx == 0) {
                         const int dim = (int)(x.feature_descriptor.size() / nx);
-                        if (dim > 0 && (int)y.feature_descriptor.size() == ny * dim) { pairs.push_back({x.feature_descriptor.data(), nx, y.feature_descriptor.data(), ny}); pair_dim.push_back(dim); }
+                        if (dim > 0 && (int)y.feature_descriptor.size() == ny * dim) {
+                            pairs.push_back({x.feature_descriptor.data(), nx, y.feature_descriptor.data(), ny}); pair_dim.push_back(dim);
+                            if (dev_hg) pairs_h.push_back({x.feature_descriptor.data(), nx, y.feature_descriptor.data(), ny, &x.landmarks_2d[0].x, &y.landmarks_2d[0].x,
+                                                           x.landmarks_flag.data(), (int)std::min(x.landmarks_flag.size(), (size_t)nx)});
+                        }
                     }
                 }
             }
             prep[ci].count = pairs.size() - prep[ci].first;
         }
         std::vector<std::vector<DMatch>> outs(pairs.size());
+        std::vector<BFMatcherL2X::Homography> hgs(dev_hg ? pairs.size() : 0);
         {
             std::vector<char> done(pairs.size(), 0);
             for (size_t p0 = 0; p0 < pairs.size(); ++p0) {
                 if (done[p0]) continue;
                 std::vector<BFMatcherL2X::Pair> sub;
+                std::vector<BFMatcherL2X::PairH> sub_h;
                 std::vector<size_t> where;
                 for (size_t p = p0; p < pairs.size(); ++p)
-                    if (!done[p] && pair_dim[p] == pair_dim[p0]) { sub.push_back(pairs[p]); where.push_back(p); done[p] = 1; }
+                    if (!done[p] && pair_dim[p] == pair_dim[p0]) { sub.push_back(pairs[p]); if (dev_hg) sub_h.push_back(pairs_h[p]); where.push_back(p); done[p] = 1; }
                 std::vector<std::vector<DMatch>> so;
-                bf_.match_multi(sub, pair_dim[p0], so);
-                for (size_t j = 0; j < where.size(); ++j) outs[where[j]] = std::move(so[j]);
+                std::vector<BFMatcherL2X::Homography> sh;
+                if (dev_hg) bf_.match_homography_multi(sub_h, pair_dim[p0], so, sh);
+                else bf_.match_multi(sub, pair_dim[p0], so);
+                for (size_t j = 0; j < where.size(); ++j) { outs[where[j]] = std::move(so[j]); if (dev_hg) hgs[where[j]] = std::move(sh[j]); }
             }
         }
         using Result = std::pair<bool, LoopEdge>;
@@ -237,10 +254,25 @@ public:
             auto mine_p = std::make_shared<std::vector<BFMatcherL2X::Pair>>(pairs.begin() + prep[ci].first, pairs.begin() + prep[ci].first + prep[ci].count);
             auto mine_o = std::make_shared<std::vector<std::vector<DMatch>>>();
             auto mine_d = std::make_shared<std::vector<int>>(pair_dim.begin() + prep[ci].first, pair_dim.begin() + prep[ci].first + prep[ci].count);
-            for (size_t j = 0; j < prep[ci].count; ++j) mine_o->push_back(std::move(outs[prep[ci].first + j]));
+            auto mine_h = std::make_shared<std::vector<BFMatcherL2X::Homography>>();
+            for (size_t j = 0; j < prep[ci].count; ++j) { mine_o->push_back(std::move(outs[prep[ci].first + j])); if (dev_hg) mine_h->push_back(std::move(hgs[prep[ci].first + j])); }
             const Deferred c = deferred_[ci];
-            auto work = [g0 = geo_, mine_p, mine_o, mine_d, c]() -> Result {    // g0: the parameters, copied on this thread
+            auto work = [this, g0 = geo_, mine_p, mine_o, mine_d, mine_h, c]() -> Result {    // g0: the parameters, copied on this thread
                 LoopGeometry g = g0;
+                if (!mine_h->empty())                                  // the pair's mask from the round trip above; a pair the device handed back runs on the host
+                    g.homography_mask = [&](const ImageDescriptor& nw, const ImageDescriptor& old, const std::vector<geom::Vec2>& old_2d, const std::vector<geom::Vec2>&,
+                                            std::vector<uint8_t>& mask) {
+                        for (size_t p = 0; p < mine_p->size(); ++p) {
+                            if ((*mine_p)[p].query != nw.feature_descriptor.data() || (*mine_p)[p].train != old.feature_descriptor.data()) continue;
+                            const BFMatcherL2X::Homography& h = (*mine_h)[p];
+                            if ((h.status != OMNI_HG_OK && h.status != OMNI_HG_NO_MODEL) || h.mask.size() != old_2d.size()) break;
+                            mask = h.mask;
+                            ++homography_pairs_device_;
+                            return true;
+                        }
+                        ++homography_pairs_host_;
+                        return false;
+                    };
                 g.match = [&](const float* q, int nq, const float* t, int nt, int dim, std::vector<DMatch>& out) {
                     for (size_t p = 0; p < mine_p->size(); ++p)
                         if ((*mine_p)[p].query == q && (*mine_p)[p].train == t && (*mine_p)[p].nq == nq && (*mine_p)[p].nt == nt && (*mine_d)[p] == dim) { out = (*mine_o)[p]; return; }
@@ -327,6 +359,14 @@ public:
             }
         return m;
     }
+    // ---- the homography RANSAC of the loop candidates on the GPU (Config::device_homography) --------------------------------------------------------------
+    bool device_homography() const { return cfg_.device_homography && cfg_.geometry && !shard_; }      // (the sharded database builds no messages)
+    bool device_homography_config() const { return cfg_.device_homography; }      // the switch as set, whatever the mode makes of it
+    // between two calls of run / push_keyframe / poll / flush (what the C entry point omni_pipeline_set_device_homography sets): the next micro-batch's candidates
+    void set_device_homography(bool on) { std::lock_guard<std::mutex> lk(intake_mu_); cfg_.device_homography = on; }
+    // direction pairs whose mask came from the device / that ran geom::find_homography_ransac although the switch was on (the device's status HOST), so far
+    int homography_pairs_device() const { return homography_pairs_device_.load(); }
+    int homography_pairs_host() const { return homography_pairs_host_.load(); }
     // before the first key frame: switches the stage on or off on every lane (what the C entry point omni_pipeline_set_device_landmarks sets)
     void set_device_landmarks(bool on) {
         std::lock_guard<std::mutex> lk(intake_mu_);
@@ -859,6 +899,7 @@ private:
     struct DetPending { bool active = false; std::vector<int64_t> ids; std::chrono::steady_clock::time_point t_enqueue; } det_pending_;
     bool async_detector_ = [] { int v = 1; check(omni_config_value("OMNI_DETECTOR_ASYNC", &v), "omni_config_value"); return v != 0; }();
     bool async_geometry_ = [] { int v = 1; check(omni_config_value("OMNI_GEOMETRY_ASYNC", &v), "omni_config_value"); return v != 0; }();
+    std::atomic<int> homography_pairs_device_{0}, homography_pairs_host_{0};      // (counted by the geometry tasks; declared before the pool: outlive its threads)
     std::unique_ptr<TaskPool> pool_;
     std::unique_ptr<TaskPool> msg_pool_ = [] { const int n = cfg_int("OMNI_MESSAGE_THREADS"); return n > 0 ? std::make_unique<TaskPool>(n) : nullptr; }();
     std::vector<ImageDescriptor> downs_;        // the down-camera halves of the micro-batch being finished

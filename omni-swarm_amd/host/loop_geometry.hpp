@@ -158,6 +158,11 @@ public:
     std::function<void(const float* q, int nq, const float* t, int nt, int dim, std::vector<DMatch>& out)> match;
     // ego_motion_traj.get_relative_pose_by_ts(ts_a, ts_b) -> (relative pose, 6x6 covariance diagonal as [pos3, ang3]); unset = gate passes
     std::function<bool(double ts_a, double ts_b, geom::Pose& rel, double cov6[6])> relative_odometry;
+    // optional: the homography-RANSAC mask of one image pair computed elsewhere (the GPU: BFMatcherL2X::match_homography_multi, csrc/homography.hip -- the same
+    // mask, bit for bit).  Given the two images and the pixels of the flagged matches (old_2d, new_2d, in match order) it fills `mask`, one entry per flagged
+    // match, and returns true; false (a pair it cannot serve: the device's status HOST) and an unset hook run geom::find_homography_ransac here
+    std::function<bool(const ImageDescriptor& nw, const ImageDescriptor& old, const std::vector<geom::Vec2>& old_2d, const std::vector<geom::Vec2>& new_2d,
+                       std::vector<uint8_t>& mask)> homography_mask;
     int loop_count = 0;
 
     struct Correspondence {
@@ -189,7 +194,8 @@ public:
         }
         if (old_2d.size() < 4) return false;
         std::vector<uint8_t> mask;
-        geom::find_homography_ransac(old_2d, new_2d, 3.0, mask);                                              // :590
+        if (!homography_mask || !homography_mask(nw, old, old_2d, new_2d, mask) || mask.size() != old_2d.size())
+            geom::find_homography_ransac(old_2d, new_2d, 3.0, mask);                                          // :590
         auto reduce = [&](auto& v) { size_t j = 0; for (size_t i = 0; i < v.size(); ++i) if (mask[i]) v[j++] = v[i]; v.resize(j); };
         reduce(new_idx); reduce(old_idx); reduce(new_3d); reduce(new_norm_2d); reduce(old_3d); reduce(old_norm_2d);
         return true;

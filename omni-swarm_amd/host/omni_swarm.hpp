@@ -438,6 +438,39 @@ public:
         for (size_t p = 0; p < pairs.size(); ++p)
             for (int i = 0; i < n[p]; ++i) out[p].push_back({qi[p * max_n + i], ti[p * max_n + i], dd[p * max_n + i]});
     }
+    // match_multi followed, in the same GPU round trip, by the flag filter and the homography RANSAC of compute_correspond_features (loop_detector.cpp:574-598;
+    // omni_bf_match_homography_multi): per pair the two images' landmarks_2d ([n][2] floats) and the new image's landmarks_flag next to the descriptors.
+    // hg[p]: status (OMNI_HG_*), kept = the positions in out[p] of the flagged matches, mask over kept, the best model and {count, iterations, best iteration, inliers}
+    struct PairH { const float* query; int nq; const float* train; int nt; const float* q_xy; const float* t_xy; const uint8_t* q_flags; int n_flags; };
+    struct Homography { int status = OMNI_HG_UNFILTERED; std::vector<int> kept; std::vector<uint8_t> mask; double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int info[4] = {0, 0, -1, 0}; };
+    void match_homography_multi(const std::vector<PairH>& pairs, int dim, std::vector<std::vector<DMatch>>& out, std::vector<Homography>& hg) {
+        out.assign(pairs.size(), {}); hg.assign(pairs.size(), {});
+        if (pairs.empty()) return;
+        const size_t P = pairs.size();
+        int max_n = 1;
+        std::vector<const float*> q(P), t(P), qx(P), tx(P);
+        std::vector<const uint8_t*> fl(P);
+        std::vector<int> nq(P), nt(P), nf(P), n(P), nk(P), status(P), info(P * 4);
+        for (size_t p = 0; p < P; ++p) {
+            q[p] = pairs[p].query; t[p] = pairs[p].train; nq[p] = pairs[p].nq; nt[p] = pairs[p].nt;
+            qx[p] = pairs[p].q_xy; tx[p] = pairs[p].t_xy; fl[p] = pairs[p].q_flags; nf[p] = pairs[p].n_flags;
+            max_n = std::max(max_n, std::max(std::max(nq[p], nt[p]), nf[p]));
+        }
+        std::vector<int> qi(P * max_n), ti(P * max_n), kept(P * max_n);
+        std::vector<float> dd(P * max_n);
+        std::vector<uint8_t> mask(P * max_n);
+        std::vector<double> H(P * 9);
+        check(omni_bf_match_homography_multi(ctx_.get(), (int)P, q.data(), nq.data(), t.data(), nt.data(), dim, mode_, max_n, qx.data(), tx.data(), fl.data(), nf.data(), qi.data(),
+                                             ti.data(), dd.data(), n.data(), kept.data(), nk.data(), mask.data(), H.data(), info.data(), status.data()),
+              "BFMatcherL2X::match_homography_multi");
+        for (size_t p = 0; p < P; ++p) {
+            for (int i = 0; i < n[p]; ++i) out[p].push_back({qi[p * max_n + i], ti[p * max_n + i], dd[p * max_n + i]});
+            hg[p].status = status[p];
+            hg[p].kept.assign(kept.begin() + p * max_n, kept.begin() + p * max_n + nk[p]);
+            hg[p].mask.assign(mask.begin() + p * max_n, mask.begin() + p * max_n + nk[p]);
+            std::copy(H.begin() + p * 9, H.begin() + p * 9 + 9, hg[p].H); std::copy(info.begin() + p * 4, info.begin() + p * 4 + 4, hg[p].info);
+        }
+    }
 #ifdef OMNI_WITH_OPENCV
     void match(const cv::Mat& query, const cv::Mat& train, std::vector<cv::DMatch>& matches) {
         std::vector<DMatch> m;

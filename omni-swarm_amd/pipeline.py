@@ -26,8 +26,12 @@ _lib = None
 # where the pipeline computes its stereo landmarks: include/omni_host_landmarks.h, lib/libomni_host_landmarks.so (the same handle)
 LANDMARKS_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_landmarks.so")
 LANDMARKS_SYMBOLS = ["omni_landmarks_last_error", "omni_pipeline_set_device_landmarks"]
+# where the pipeline runs the homography RANSAC of its loop candidates: include/omni_host_homography.h, lib/libomni_host_homography.so (the same handle)
+HOMOGRAPHY_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_homography.so")
+HOMOGRAPHY_SYMBOLS = ["omni_homography_last_error", "omni_pipeline_set_device_homography", "omni_pipeline_get_device_homography"]
 _stereo_lib = None
 _landmarks_lib = None
+_homography_lib = None
 
 
 def lib():
@@ -136,11 +140,25 @@ def landmarks_lib():
     return _landmarks_lib
 
 
+def homography_lib():
+    global _homography_lib
+    if _homography_lib is None:
+        lib()
+        if not os.path.exists(HOMOGRAPHY_LIB_PATH):
+            raise OSError(f"{HOMOGRAPHY_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(HOMOGRAPHY_LIB_PATH)
+        L.omni_homography_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_device_homography.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_device_homography.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _homography_lib = L
+    return _homography_lib
+
+
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -148,6 +166,8 @@ class KeyframePipeline:
         the networks' size; fx fy cx cy are those of the width x height image.  set_stereo_extrinsics gives the rig's two extrinsics.
         device_landmarks: True / False = the stereo landmarks of a `geometry` pipeline inside the key-frame unit on the GPU / on the host's geometry
         threads (the same bits either way); None: the library's default.
+        device_homography: True / False = the homography RANSAC of a `geometry` pipeline's loop candidates on the GPU, in the round trip that matches their
+        direction pairs / on the host's geometry threads (the same masks either way); None: the library's default.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -172,11 +192,25 @@ class KeyframePipeline:
             raise _err("omni_pipeline_create")
         if device_landmarks is not None:
             self.set_device_landmarks(device_landmarks)
+        if device_homography is not None:
+            self.set_device_homography(device_homography)
 
     def set_device_landmarks(self, on: bool):
         """before the first key frame: stereo landmarks inside the key-frame unit (GPU) or on the host's geometry threads"""
         if landmarks_lib().omni_pipeline_set_device_landmarks(self.h, int(bool(on))):
             raise capi.OmniError(f"omni_pipeline_set_device_landmarks: {landmarks_lib().omni_landmarks_last_error().decode()}")
+
+    def set_device_homography(self, on: bool):
+        """the homography RANSAC of the loop candidates on the GPU (next to the matcher) or on the host's geometry threads; between any two calls"""
+        if homography_lib().omni_pipeline_set_device_homography(self.h, int(bool(on))):
+            raise capi.OmniError(f"omni_pipeline_set_device_homography: {homography_lib().omni_homography_last_error().decode()}")
+
+    def device_homography(self):
+        """(the switch, direction pairs whose mask came from the GPU so far, pairs the device handed back to the host)"""
+        on, dev, host = C.c_int(0), C.c_int(0), C.c_int(0)
+        if homography_lib().omni_pipeline_get_device_homography(self.h, C.byref(on), C.byref(dev), C.byref(host)):
+            raise capi.OmniError(f"omni_pipeline_get_device_homography: {homography_lib().omni_homography_last_error().decode()}")
+        return bool(on.value), dev.value, host.value
 
     @classmethod
     def from_launch(cls, device: int, launch_xml: str, sp_weights_path: str, vlad_weights_path: str, pca_comp_csv: str | None = None, pca_mean_csv: str | None = None,
