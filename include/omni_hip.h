@@ -236,6 +236,22 @@ int omni_vlad_dev_output(omni_vlad* v, const float** out_dev);
 /* The layers (0 = stem + block 0, k = block k) whose tiles inside the constant region of the fisheye mask a masked pass leaves out (loop_cam.cpp:536-539
  * blanks the rows before netvlad_net.inference, :556-558): returns their number, frac[k] = the share of layer k's tiles left out (up to max_layers). */
 int omni_vlad_mask_skip_layers(const omni_vlad* v, double* frac, int max_layers);
+/* Test hooks: the activations of a pass, layer by layer (what omni_sp_debug_layer is to SuperPoint).  The three activation buffers of a handle rotate, so a
+ * pass keeps no intermediate map unless asked to.  omni_vlad_debug_taps(v, 1): from now on a pass runs the same kernels with the same arguments and, behind the
+ * stem (where it runs on its own) and behind every inverted-residual block, copies that layer's output on the device into a buffer of its own (allocated by the
+ * first such pass); a layer that wrote into its mask-skip buffer is copied whole, rectangle included.  Off (the default): a pass enqueues nothing for it.
+ * omni_vlad_debug_layer: one layer of the LAST pass as NCHW float32; name = "stem" (an error when the stem is fused into block 0), "b0" .. "b16" (the output
+ * of that block, residual included; on the layer-by-layer path the output of its projection layer), "assign" (K x hf x wf), "vlad" (K * D x 1 x 1: the
+ * intra- and L2-normalised vector the FC reads), "out" (out_dim x 1 x 1).  out may be NULL to query the shape only.  Errors (a code, no abort): the taps
+ * are off, an unknown name, batch larger than the last tapped pass's. */
+int omni_vlad_debug_taps(omni_vlad* v, int on);
+int omni_vlad_debug_layer(omni_vlad* v, const char* name, int batch, float* out_nchw_host, int* C, int* H, int* W);
+/* Which kernels the handle's current plan runs: paths[0] = the stem's form (OMNI_VLAD_STEM_*), paths[1 + k] = block k's kernel (OMNI_VB_*; OMNI_VB_NONE for
+ * block 0 when the stem kernel computes it).  On the layer-by-layer path only paths[0] = OMNI_VLAD_STEM_LAYERS is returned.  Returns the number of entries
+ * (up to max are written). */
+enum { OMNI_VB_NONE = -1, OMNI_VB_HBLOCK = 0, OMNI_VB_SBLOCK = 1, OMNI_VB_MBLOCK = 2, OMNI_VB_PW_MFMA3 = 3, OMNI_VB_VALU = 4 };
+enum { OMNI_VLAD_STEM_OWN = 0, OMNI_VLAD_STEM_WITH_B0 = 1, OMNI_VLAD_STEM_LAYERS = 2 };
+int omni_vlad_block_paths(const omni_vlad* v, int* paths, int max);
 
 /* ---- global-descriptor index: faiss::IndexFlatIP(d) --------------------------------------------------------- */
 omni_index* omni_index_create(omni_ctx* ctx, int dim, int storage, int64_t initial_capacity_rows);

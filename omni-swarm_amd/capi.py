@@ -22,6 +22,8 @@ SP_NUM_LAYERS = 12
 SP_NUM_STAGES = 16
 SP_LAYER_NAMES = ["conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b",
                   "convPa", "convPb", "convDa", "convDb"]
+VB_NAMES = ["hblock", "sblock", "mblock", "pw_mfma3", "valu"]      # include/omni_hip.h OMNI_VB_*
+VLAD_STEM_NAMES = ["stem", "stem_b0", "layers"]                     # OMNI_VLAD_STEM_*
 VLAD_KINDS = {"conv3x3": 0, "pw_relu6": 1, "dw3x3_relu6": 2, "pw_linear": 3, "pw_linear_res": 4}
 
 # every symbol include/omni_hip.h declares (tests check the .so exports all of them)
@@ -31,7 +33,7 @@ SYMBOLS = [
     "omni_timer_stop", "omni_sp_create", "omni_sp_destroy", "omni_sp_desc_dim", "omni_sp_image_size", "omni_sp_infer", "omni_sp_enqueue_dev",
     "omni_sp_fetch", "omni_sp_dev_outputs", "omni_sp_get_dense", "omni_sp_postprocess_dense", "omni_sp_debug_layer",
     "omni_sp_profile", "omni_sp_stage_name", "omni_sp_stage_flops", "omni_sp_stage_tiles_left_out", "omni_sp_mask_skip_plan", "omni_vlad_create", "omni_vlad_destroy", "omni_vlad_set_precision", "omni_vlad_pack_block", "omni_sp_pack_constants",
-    "omni_vlad_infer", "omni_vlad_enqueue_dev", "omni_vlad_fetch", "omni_vlad_dev_output", "omni_vlad_mask_skip_layers", "omni_index_create",
+    "omni_vlad_infer", "omni_vlad_enqueue_dev", "omni_vlad_fetch", "omni_vlad_dev_output", "omni_vlad_mask_skip_layers", "omni_vlad_debug_taps", "omni_vlad_debug_layer", "omni_vlad_block_paths", "omni_index_create",
     "omni_index_destroy", "omni_index_add", "omni_index_add_dev", "omni_index_ntotal", "omni_index_dim", "omni_index_reset", "omni_index_truncate", "omni_index_cert_stats",
     "omni_index_search", "omni_index_search_dev", "omni_index_search_prefix_dev", "omni_index_search_batch_prefix_dev", "omni_index_set_shard", "omni_topk_merge", "omni_index_last_scan_ms",
     "omni_index_save", "omni_index_load",
@@ -165,6 +167,9 @@ def lib():
     sig("omni_vlad_fetch", C.c_int, [_vp, C.c_int, _fp])
     sig("omni_vlad_dev_output", C.c_int, [_vp, C.POINTER(_vp)])
     sig("omni_vlad_mask_skip_layers", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
+    sig("omni_vlad_debug_taps", C.c_int, [_vp, C.c_int])
+    sig("omni_vlad_debug_layer", C.c_int, [_vp, C.c_char_p, C.c_int, _fp, _ip, _ip, _ip])
+    sig("omni_vlad_block_paths", C.c_int, [_vp, _ip, C.c_int])
     sig("omni_index_create", _vp, [_vp, C.c_int, C.c_int, C.c_int64])
     sig("omni_index_destroy", None, [_vp])
     sig("omni_index_add", C.c_int, [_vp, C.c_int64, _fp])
@@ -516,6 +521,24 @@ class MobileNetVLAD:
         f = (C.c_double * 32)()
         n = lib().omni_vlad_mask_skip_layers(self.h, f, 32)
         return [f[i] for i in range(min(n, 32))]
+
+    def debug_taps(self, on: bool = True):
+        """Test hook: from now on a pass keeps a copy of the stem's (where it runs on its own) and every block's output for ``debug_layer``."""
+        _check(lib().omni_vlad_debug_taps(self.h, int(on)))
+
+    def debug_layer(self, name: str, batch: int = 1) -> np.ndarray:
+        """One layer of the last pass with the taps on, NCHW float32: "stem", "b0" .. "b16", "assign", "vlad", "out"."""
+        c, h, w = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().omni_vlad_debug_layer(self.h, name.encode(), batch, None, C.byref(c), C.byref(h), C.byref(w)))
+        out = np.empty((batch, c.value, h.value, w.value), np.float32)
+        _check(lib().omni_vlad_debug_layer(self.h, name.encode(), batch, _pf(out), C.byref(c), C.byref(h), C.byref(w)))
+        return out
+
+    def block_paths(self) -> dict:
+        """The kernels of the current plan: {"stem": "stem" | "stem_b0" | "layers", "blocks": [VB_NAMES entry per block; None = inside the stem kernel]}."""
+        p = (C.c_int * 64)()
+        n = lib().omni_vlad_block_paths(self.h, p, 64)
+        return {"stem": VLAD_STEM_NAMES[p[0]], "blocks": [VB_NAMES[p[i]] if p[i] >= 0 else None for i in range(1, min(n, 64))]}
 
 
 def sp_pack_constants(which, w, bias=None, cout=64):

@@ -61,6 +61,12 @@ struct omni_vlad {
     std::vector<MaskSkip> mskip;
     bool mask_skip_ready = false;
     uint8_t* zero_gray = nullptr;             // the calibration's blank frame (allocated by the first masked pass that skips)
+    // Test hook (omni_vlad_debug_taps / omni_vlad_debug_layer).  Off: a pass enqueues nothing for it.  On: behind the stem (where it runs on its own) and behind
+    // every block a device-to-device copy of that layer's output, as the next layer reads it, into a buffer of its own ([0] = stem, [1 + k] = block k; NHWC,
+    // max_batch images, allocated by the first pass that taps).
+    bool taps_on = false;
+    std::vector<float*> tap;
+    int tap_batch = 0;                        // images of the last tapped pass (0: none)
     mutable std::mutex mu;
 };
 
@@ -1021,8 +1027,19 @@ static int upload(omni_vlad* v, T** dst, const void* src, size_t bytes) {
     return OMNI_OK;
 }
 
+// test hook: the output of the stem (slot 0) or of block k (slot 1 + k) -> the slot's own buffer, behind the layer on the pass's stream
+static int vlad_tap(omni_vlad* v, size_t slot, const float* src, int batch, int h, int w, int c) {
+    if (v->tap.size() <= slot) v->tap.resize(slot + 1, nullptr);
+    int rc;
+    if (!v->tap[slot] && (rc = v->mem.alloc(&v->tap[slot], (size_t)v->max_batch * h * w * c * 4))) return rc;
+    OMNI_HIP_TRY(hipMemcpyAsync(v->tap[slot], src, (size_t)batch * h * w * c * 4, hipMemcpyDeviceToDevice, v->ctx->stream));
+    return OMNI_OK;
+}
+
 static int vlad_backbone_unfused(omni_vlad* v, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, int* cur_out) {
     hipStream_t st = v->ctx->stream;
+    size_t n_proj = 0;        // projections so far = the block the next one ends (test hook)
+    int rc;
     const int H = v->H, W = v->W;
     int m0, m1;
     omni_fisheye_mask_rows(H, fisheye_mask, &m0, &m1);
@@ -1054,6 +1071,10 @@ static int vlad_backbone_unfused(omni_vlad* v, const uint8_t* gray_dev, int stri
             if (!expand) block_in = cur;         // a projection ends the block; the next block starts from here
         }
         OMNI_LAUNCH_CHECK();
+        if (v->taps_on && L.kind != OMNI_VLAD_DW3X3_RELU6 && L.kind != OMNI_VLAD_PW_RELU6) {
+            const size_t slot = L.kind == OMNI_VLAD_CONV3X3_RELU6 ? 0 : ++n_proj;
+            if ((rc = vlad_tap(v, slot, v->buf[cur], batch, L.hout, L.wout, L.cout))) return rc;
+        }
     }
     *cur_out = cur;
     return OMNI_OK;
@@ -1183,7 +1204,7 @@ static Args vlad_block_args(const VladFusedBlock& B, const float* in, float* out
 
 // stem + one fused kernel per inverted-residual block (v->blocks, built at create time), each as v->plan says.  The layers `ps` names write into their
 // own buffers instead of the next rotating one and may leave their rectangle of the mask's constant region out.  *out_ptr = the backbone's output.
-static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, const VladPassSkip& ps, const float** out_ptr) {
+static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, const VladPassSkip& ps, bool tap, const float** out_ptr) {
     hipStream_t st = v->ctx->stream;
     const VladPlan& plan = v->plan;
     const int H = v->H, W = v->W;
@@ -1208,6 +1229,10 @@ static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride
                            m1, S.hout, S.wout, S.cout, S.stride, S.w, S.b, v->buf[0]);
     }
     OMNI_LAUNCH_CHECK();
+    if (tap) {
+        const VladFusedBlock& B0 = v->blocks[0];
+        if ((rc = first ? vlad_tap(v, 1, in, batch, B0.hout, B0.wout, B0.cout) : vlad_tap(v, 0, in, batch, S.hout, S.wout, S.cout))) return rc;
+    }
     for (size_t bi = first; bi < v->blocks.size(); ++bi) {
         const VladFusedBlock& B = v->blocks[bi];
         const int next = (cur + 1) % 3;
@@ -1249,6 +1274,7 @@ static int vlad_backbone_fused(omni_vlad* v, const uint8_t* gray_dev, int stride
         }
         if (!own(bi)) cur = next;
         in = out;
+        if (tap && (rc = vlad_tap(v, 1 + bi, in, batch, B.hout, B.wout, B.cout))) return rc;
     }
     *out_ptr = in;
     return OMNI_OK;
@@ -1261,7 +1287,7 @@ static int vlad_calibrate_mask_skip(omni_vlad* v) {
     int rc;
     if (!v->zero_gray && (rc = v->mem.alloc(&v->zero_gray, (size_t)v->W * v->H, st, true))) return rc;
     const float* unused;
-    if ((rc = vlad_backbone_fused(v, v->zero_gray, v->W, 1, 1, vlad_pass_skip(v->plan, v->prec, true, true), &unused))) return rc;
+    if ((rc = vlad_backbone_fused(v, v->zero_gray, v->W, 1, 1, vlad_pass_skip(v->plan, v->prec, true, true), false, &unused))) return rc;
     for (size_t i = 0; i < v->mskip.size(); ++i) {
         const VladSkipRect& k = v->plan.skip[i];
         const omni_vlad::MaskSkip& m = v->mskip[i];
@@ -1316,11 +1342,12 @@ static int vlad_forward(omni_vlad* v, const uint8_t* gray_dev, int stride, int b
     if (plan.fused) {
         const VladPassSkip ps = vlad_pass_skip(plan, v->prec, fisheye_mask != 0, false);
         if (ps.leave_out && !v->mask_skip_ready && (rc = vlad_calibrate_mask_skip(v))) return rc;
-        if ((rc = vlad_backbone_fused(v, gray_dev, stride, batch, fisheye_mask, ps, &feat))) return rc;
+        if ((rc = vlad_backbone_fused(v, gray_dev, stride, batch, fisheye_mask, ps, v->taps_on, &feat))) return rc;
     } else {
         if ((rc = vlad_backbone_unfused(v, gray_dev, stride, batch, fisheye_mask, &cur))) return rc;
         feat = v->buf[cur];
     }
+    if (v->taps_on) v->tap_batch = batch;
     const int n_pos = v->hf * v->wf, n_in = v->K * v->Dm;
     const int64_t n_all = (int64_t)batch * n_pos;
     if (plan.head == VLAD_ASSIGN2_AGG8) {
@@ -1581,6 +1608,72 @@ int omni_vlad_mask_skip_layers(const omni_vlad* v, double* frac, int max_layers)
     std::lock_guard<std::mutex> lk(v->mu);                  // (omni_vlad_set_precision makes the plan again)
     const int n = v->plan.n_skip();
     for (int i = 0; i < n && i < max_layers && frac; ++i) frac[i] = v->plan.skip[i].frac;
+    return n;
+}
+
+int omni_vlad_debug_taps(omni_vlad* v, int on) {
+    OMNI_REQUIRE(v, OMNI_ERR_INVALID, "null handle");
+    std::lock_guard<std::mutex> lk(v->mu);
+    v->taps_on = on != 0;
+    v->tap_batch = 0;
+    return OMNI_OK;
+}
+
+int omni_vlad_debug_layer(omni_vlad* v, const char* name, int batch, float* out_nchw_host, int* C, int* Hl, int* Wl) {
+    OMNI_REQUIRE(v && name, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(v->mu);
+    OMNI_REQUIRE(v->taps_on, OMNI_ERR_INVALID, "omni_vlad_debug_layer: the taps are off (omni_vlad_debug_taps)");
+    const float* src = nullptr;               // NHWC on the device
+    int c = 0, h = 1, w = 1;
+    char* end = nullptr;
+    const long bi = name[0] == 'b' && name[1] >= '0' && name[1] <= '9' ? strtol(name + 1, &end, 10) : -1;
+    const size_t n_blocks = v->plan.fused ? v->blocks.size() : [&] { size_t n = 0; for (auto& L : v->layers) n += L.kind == OMNI_VLAD_PW_LINEAR || L.kind == OMNI_VLAD_PW_LINEAR_RES; return n; }();
+    auto slot = [&](size_t s) { return s < v->tap.size() ? v->tap[s] : nullptr; };
+    if (!strcmp(name, "stem")) {
+        if (v->plan.fused && v->plan.stem == omni::VLAD_STEM_B0) { omni::set_error("the stem is fused into block 0 on this path and not materialised (OMNI_VLAD_STEM_FUSE=0 keeps it)"); return OMNI_ERR_INVALID; }
+        const VladLayerDev& S = v->layers[0];
+        src = slot(0); c = S.cout; h = S.hout; w = S.wout;
+    } else if (bi >= 0 && end && *end == 0 && (size_t)bi < n_blocks) {
+        size_t seen = 0;
+        for (const VladLayerDev& L : v->layers)                           // block bi ends with the (bi + 1)-th projection of the layer table
+            if ((L.kind == OMNI_VLAD_PW_LINEAR || L.kind == OMNI_VLAD_PW_LINEAR_RES) && seen++ == (size_t)bi) { c = L.cout; h = L.hout; w = L.wout; }
+        src = slot(1 + (size_t)bi);
+    } else if (!strcmp(name, "assign")) { src = v->assign; c = v->K; h = v->hf; w = v->wf; }
+    else if (!strcmp(name, "vlad")) { src = v->vlad; c = v->K * v->Dm; }
+    else if (!strcmp(name, "out")) { src = v->out; c = v->out_dim; }
+    else { omni::set_error("unknown layer '%s'", name); return OMNI_ERR_INVALID; }
+    if (C) *C = c;
+    if (Hl) *Hl = h;
+    if (Wl) *Wl = w;
+    if (!out_nchw_host) return OMNI_OK;
+    OMNI_REQUIRE(batch >= 1 && batch <= v->tap_batch, OMNI_ERR_INVALID, "no pass of >= %d images with the taps on to take layer %s from (last: %d)", batch, name, v->tap_batch);
+    OMNI_REQUIRE(src, OMNI_ERR_INVALID, "layer %s was not tapped by the last pass", name);
+    (void)hipSetDevice(v->ctx->device);
+    const size_t per = (size_t)c * h * w, n = (size_t)batch * per;
+    int rc;
+    if ((rc = v->hstage.ensure(n * 4))) return rc;
+    OMNI_HIP_TRY(hipMemcpyAsync(v->hstage.p, src, n * 4, hipMemcpyDeviceToHost, v->ctx->stream));
+    OMNI_HIP_TRY(hipStreamSynchronize(v->ctx->stream));
+    const float* s = v->hstage.as<float>();
+    const size_t px = (size_t)h * w;
+    for (int b = 0; b < batch; ++b)                                       // NHWC -> NCHW on the host
+        for (size_t p = 0; p < px; ++p)
+            for (int ch = 0; ch < c; ++ch) out_nchw_host[(size_t)b * per + (size_t)ch * px + p] = s[(size_t)b * per + p * c + ch];
+    return OMNI_OK;
+}
+
+int omni_vlad_block_paths(const omni_vlad* v, int* paths, int max) {
+    static_assert(OMNI_VB_HBLOCK == omni::VB_HBLOCK && OMNI_VB_SBLOCK == omni::VB_SBLOCK && OMNI_VB_MBLOCK == omni::VB_MBLOCK &&
+                  OMNI_VB_PW_MFMA3 == omni::VB_PW_MFMA3 && OMNI_VB_VALU == omni::VB_VALU, "omni_hip.h restates VladBlockPath");
+    static_assert(OMNI_VLAD_STEM_OWN == omni::VLAD_STEM4 && OMNI_VLAD_STEM_WITH_B0 == omni::VLAD_STEM_B0, "omni_hip.h restates VladStem");
+    if (!v) return 0;
+    std::lock_guard<std::mutex> lk(v->mu);                  // (omni_vlad_set_precision makes the plan again)
+    const omni::VladPlan& plan = v->plan;
+    const int n = 1 + (int)(plan.fused ? v->blocks.size() : 0);
+    for (int i = 0; i < n && i < max && paths; ++i) {
+        if (i == 0) paths[0] = plan.fused ? (int)plan.stem : OMNI_VLAD_STEM_LAYERS;
+        else paths[i] = i == 1 && plan.stem == omni::VLAD_STEM_B0 ? OMNI_VB_NONE : (int)plan.blocks[i - 1];
+    }
     return n;
 }
 
