@@ -516,6 +516,48 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
                                    int mode, int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags,
                                    int* q_idx, int* t_idx, float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status);
 
+/* ---- send_img: the main image of every direction as a baseline JPEG, what encode_image's cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, JPG_QUALITY}) asks of
+ * libjpeg (loop_cam.cpp:56-71, 306-308, 463-469), on the GPU (csrc/jpeg.hip).  The arithmetic is stated once, in csrc/jpeg_plan.h: one 8-bit component, the IJG
+ * luminance table scaled by the quality, jfdctint's integer DCT, the standard Huffman tables, JFIF APP0 -- libjpeg's defaults, PINNED byte for byte against Pillow
+ * (libjpeg-turbo) by the CPU tests.  What cv::imencode adds beyond those defaults is UNPINNED: OpenCV is not vendored.
+ * Per image: status OMNI_JPEG_OK and size = the file's bytes; or OMNI_JPEG_TRUNCATED and size 0 when the file exceeds the capacity -- nothing is ever written
+ * past the capacity, and what a truncated image leaves below it is unspecified.  zero_from_row: rows at or beyond it are read as 0 (height: none) -- the rows the
+ * fisheye mask blanks. */
+#define OMNI_JPEG_OK 0
+#define OMNI_JPEG_TRUNCATED 1
+#define OMNI_JPEG_HEADER_BYTES 328   /* SOI, APP0, DQT, SOF0, DHT DC, DHT AC, SOS: the scan starts here */
+typedef struct omni_jpeg omni_jpeg;
+/* A handle owns the tables of one quality, the header of one size and all device scratch for up to max_images images of width x height.  1 <= width, height <=
+ * 65535 (and at most 2^21 blocks of 8 x 8), max_images >= 1, quality clamped to 1..100, capacity_per_image >= OMNI_JPEG_HEADER_BYTES + 2. */
+omni_jpeg* omni_jpeg_create(omni_ctx* ctx, int width, int height, int max_images, int quality, int64_t capacity_per_image);
+void       omni_jpeg_destroy(omni_jpeg* j);
+/* n_images images (u8, `stride` bytes between rows, image i at gray_dev + i * stride * height) -> out_dev [n_images][capacity_per_image], sizes_dev [n_images] int32,
+ * status_dev [n_images] int32.  Asynchronous on the context's stream, no host synchronisation.  Refused before anything is launched: n_images outside
+ * [1, max_images], stride below the width, zero_from_row outside [0, height]. */
+int        omni_jpeg_enqueue_dev(omni_jpeg* j, const uint8_t* gray_dev, int stride, int n_images, int zero_from_row, uint8_t* out_dev, int* sizes_dev, int* status_dev);
+/* everything in front of the scan: OMNI_JPEG_HEADER_BYTES bytes to out_host (no GPU) */
+int        omni_jpeg_header(int width, int height, int quality, uint8_t* out_host);
+/* csrc/jpeg_plan.h compiled by g++ into the library: the same bytes without a GPU.  *size and *status as above; OMNI_ERR_INVALID for sizes outside 1..65535,
+ * a stride below the width, a capacity below OMNI_JPEG_HEADER_BYTES + 2, zero_from_row outside [0, height]. */
+int        omni_jpeg_encode_host(const uint8_t* gray, int stride, int width, int height, int quality, int zero_from_row, uint8_t* out, int64_t capacity,
+                                 int64_t* size, int* status);
+/* The same stage inside the key-frame unit: with a quality set, every enqueue entry (_dev, _host, _host_parts, _fisheye_*, _raw_*; mono and stereo) also encodes the
+ * unit's MAIN images -- on a stereo handle the up / left images [0, n_dirs) (image_left, :463-468; LOWER_CAM_AS_MAIN is false in this build), on a mono handle all
+ * n_images images (:306-308) -- on the MobileNetVLAD stream behind that stream's read of the same images, and copies bytes, sizes and statuses into the handle's
+ * pinned block in front of the unit's event.  A unit enqueued with fisheye_mask != 0 encodes with zero_from_row = omni_fisheye_mask_rows' first row: the reference
+ * blanks those rows in the very pixels it encodes (loop_cam.cpp:536-539 writes through a cv::Mat that shares its data with msg.left_images[vcam_id]).
+ * quality 0 switches the stage off again.  Refused with a unit in flight, and for a capacity below OMNI_JPEG_HEADER_BYTES + 2. */
+int        omni_cam_set_jpeg(omni_cam* cam, int quality, int64_t capacity_per_image);
+typedef struct omni_cam_jpeg_result {           /* pointers into the handle's pinned host block; valid after omni_cam_wait until the handle's next enqueue */
+    int n_images;                               /* the main images of that unit */
+    int64_t capacity;                           /* bytes between two images in `bytes` */
+    const uint8_t* bytes;                       /* [n_images][capacity] */
+    const int*     sizes;                       /* [n_images] */
+    const int*     status;                      /* [n_images] OMNI_JPEG_OK / OMNI_JPEG_TRUNCATED */
+} omni_cam_jpeg_result;
+/* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran with the stage off */
+int        omni_cam_jpeg(omni_cam* cam, omni_cam_jpeg_result* out);
+
 #ifdef __cplusplus
 }
 #endif

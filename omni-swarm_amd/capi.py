@@ -43,7 +43,9 @@ SYMBOLS = [
     "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
     "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi",
+    "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
 ]
+JPEG_OK, JPEG_TRUNCATED, JPEG_HEADER_BYTES = 0, 1, 328      # include/omni_hip.h OMNI_JPEG_*
 HG_UNFILTERED, HG_OK, HG_NO_MODEL, HG_HOST = 0, 1, 2, 3     # include/omni_hip.h OMNI_HG_*: the status of one pair's homography RANSAC
 
 
@@ -92,6 +94,10 @@ def stereo_model(fx, fy, cx, cy, triangle_thres, accept_min_3d_pts, up_extrinsic
 class _CamLandmarks(C.Structure):
     _fields_ = [("n_images", C.c_int), ("n_dirs", C.c_int), ("max_num", C.c_int), ("norm2d", C.POINTER(C.c_float)), ("landmarks_3d", C.POINTER(C.c_float)),
                 ("landmarks_flag", C.POINTER(C.c_uint8)), ("count_3d", C.POINTER(C.c_int))]
+
+
+class _CamJpeg(C.Structure):
+    _fields_ = [("n_images", C.c_int), ("capacity", C.c_int64), ("bytes", C.POINTER(C.c_uint8)), ("sizes", C.POINTER(C.c_int)), ("status", C.POINTER(C.c_int))]
 
 
 class _VladWeights(C.Structure):
@@ -218,6 +224,13 @@ def lib():
     sig("omni_cam_set_stereo_model", C.c_int, [_vp, C.POINTER(StereoModel)])
     sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
     sig("omni_cam_landmarks", C.c_int, [_vp, C.POINTER(_CamLandmarks)])
+    sig("omni_jpeg_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64])
+    sig("omni_jpeg_destroy", None, [_vp])
+    sig("omni_jpeg_enqueue_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp])
+    sig("omni_jpeg_header", C.c_int, [C.c_int, C.c_int, C.c_int, _vp])
+    sig("omni_jpeg_encode_host", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _i64p, _ip])
+    sig("omni_cam_set_jpeg", C.c_int, [_vp, C.c_int, C.c_int64])
+    sig("omni_cam_jpeg", C.c_int, [_vp, C.POINTER(_CamJpeg)])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
     sig("omni_cam_ready", C.c_int, [_vp, C.POINTER(C.c_int)])
@@ -779,6 +792,82 @@ class Resize:
 
 
 RESIZE_COPY, RESIZE_AREA2, RESIZE_LINEAR = 0, 1, 2
+
+
+def jpeg_header(width: int, height: int, quality: int) -> bytes:
+    """everything a file of this size and quality holds in front of its scan (csrc/jpeg_plan.h; no GPU)"""
+    out = np.empty(JPEG_HEADER_BYTES, np.uint8)
+    _check(lib().omni_jpeg_header(width, height, quality, out.ctypes.data_as(_vp)))
+    return out.tobytes()
+
+
+def jpeg_encode_host(gray: np.ndarray, quality: int, zero_from_row: int = -1, capacity: int = 0, width: int = 0):
+    """csrc/jpeg_plan.h on the host (g++ inside the library; no GPU): gray [h][stride] u8 of which `width` columns (default all) are the picture ->
+    (status, the file's bytes).  zero_from_row < 0: no row is blanked.  capacity 0: room for any file of this size."""
+    g = np.ascontiguousarray(gray, np.uint8)
+    h, stride = g.shape
+    w = width or stride
+    cap = capacity or JPEG_HEADER_BYTES + 2 + ((w + 7) // 8) * ((h + 7) // 8) * 416 + 8
+    out = np.empty(cap, np.uint8)
+    size, status = C.c_int64(0), C.c_int(0)
+    _check(lib().omni_jpeg_encode_host(g.ctypes.data_as(_vp), stride, w, h, quality, h if zero_from_row < 0 else zero_from_row, out.ctypes.data_as(_vp), cap,
+                                       C.byref(size), C.byref(status)))
+    return status.value, out[:size.value].tobytes()
+
+
+class Jpeg:
+    """omni_jpeg: up to max_images images of width x height as baseline JPEG files on the GPU (send_img; csrc/jpeg.hip, the arithmetic: csrc/jpeg_plan.h)"""
+
+    def __init__(self, ctx: Context, width: int, height: int, max_images: int, quality: int, capacity_per_image: int = 0):
+        self.ctx, self.w, self.h_img, self.max_images = ctx, width, height, max_images
+        self.capacity = capacity_per_image or max(width * height // 2, JPEG_HEADER_BYTES + 2)
+        self.h = lib().omni_jpeg_create(ctx.h, width, height, max_images, quality, self.capacity)
+        if not self.h:
+            raise OmniError(f"omni_jpeg_create failed: {lib().omni_last_error().decode()}")
+        ctx._adopt(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().omni_jpeg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def enqueue_dev(self, gray_dev: int, stride: int, n_images: int, zero_from_row: int, out_dev: int, sizes_dev: int, status_dev: int):
+        _check(lib().omni_jpeg_enqueue_dev(self.h, gray_dev, stride, n_images, zero_from_row, out_dev, sizes_dev, status_dev))
+
+    def __call__(self, images_u8: np.ndarray, zero_from_row: int = -1, stride: int = 0):
+        """[h,w] or [B,h,w] uint8 -> [(status, bytes)] per image (host convenience: upload, encode, download).  stride > w: the rows are laid out with that pitch on
+        the device (the padding bytes are 0xA5).  The output block is 0xA5 before the call and has a guard behind it: `last_guard_ok` tells whether the stage kept
+        to every image's capacity, `last_raw` is the block as it came back."""
+        g = np.ascontiguousarray(images_u8, np.uint8)
+        if g.ndim == 2:
+            g = g[None]
+        assert g.shape[1:] == (self.h_img, self.w)
+        n, st = g.shape[0], stride or self.w
+        if st != self.w:
+            padded = np.full((n, self.h_img, st), 0xA5, np.uint8)
+            padded[:, :, :self.w] = g
+            g = padded
+        guard = 64
+        src = self.ctx.to_device(g)
+        out = self.ctx.to_device(np.full(n * self.capacity + guard, 0xA5, np.uint8))
+        meta = self.ctx.to_device(np.full(2 * n, -1, np.int32))
+        try:
+            self.enqueue_dev(src, st, n, self.h_img if zero_from_row < 0 else zero_from_row, out, meta, meta + 4 * n)
+            raw = self.ctx.from_device(out, (n * self.capacity + guard,), np.uint8)
+            m = self.ctx.from_device(meta, (2, n), np.int32)
+        finally:
+            for p in (src, out, meta):
+                self.ctx.free(p)
+        self.last_raw = raw[:n * self.capacity].reshape(n, self.capacity)
+        self.last_guard_ok = bool((raw[n * self.capacity:] == 0xA5).all())
+        self.last_sizes = m[0].copy()
+        return [(int(m[1, i]), self.last_raw[i, :m[0, i]].tobytes()) for i in range(n)]
 SHARD_ID_BYTES = 128
 
 
@@ -1095,6 +1184,19 @@ class Cam:
         ni, n, m = r.n_images, r.n_dirs, r.max_num
         return {"norm2d": A(r.norm2d, (ni, m, 2)), "landmarks_3d": A(r.landmarks_3d, (ni, m, 3)), "landmarks_flag": A(r.landmarks_flag, (ni, m)),
                 "count_3d": A(r.count_3d, (n,))}
+
+    def set_jpeg(self, quality: int, capacity_per_image: int = 0):
+        """send_img: every following unit also encodes its main images as JPEG files (jpeg() after wait()); quality 0 switches it off.
+        capacity 0: width * height / 2 per image"""
+        _check(lib().omni_cam_set_jpeg(self.h, quality, capacity_per_image or max(self.sp.W * self.sp.H // 2, JPEG_HEADER_BYTES + 2)))
+
+    def jpeg(self) -> list:
+        """after wait(): [(status, bytes)] of the unit's main images -- the up / left images of a stereo handle, every image of a mono handle"""
+        r = _CamJpeg()
+        _check(lib().omni_cam_jpeg(self.h, C.byref(r)))
+        A = np.ctypeslib.as_array
+        raw, sizes, status = A(r.bytes, (r.n_images, r.capacity)), A(r.sizes, (r.n_images,)), A(r.status, (r.n_images,))
+        return [(int(status[i]), raw[i, :sizes[i]].tobytes()) for i in range(r.n_images)]
 
     def ready(self) -> bool:
         r = C.c_int(0)

@@ -39,6 +39,15 @@ struct omni_cam {
     double* d_poses = nullptr;
     char* d_lm = nullptr;                     // ONE block laid out as host + off_norm .. off_lm_end: norm2d | landmarks_3d | flags | count_3d (one copy down)
     size_t off_poses = 0, off_norm = 0, off_l3d = 0, off_flag = 0, off_cnt = 0, off_lm_end = 0;
+    // send_img inside the unit (omni_cam_set_jpeg; jpeg.hip): the unit's main images [0, n) as JPEG files, on the MobileNetVLAD stream.  d_jpeg / h_jpeg: the
+    // images' bytes [n_cap][jpeg_cap], then (at jpeg_meta) sizes [n_cap] and statuses [n_cap] -- a block of its own, pinned on the host side
+    omni_jpeg* jpeg = nullptr;
+    int jpeg_quality = 0;                     // 0: the stage is off
+    int64_t jpeg_cap = 0;
+    size_t jpeg_meta = 0;
+    uint8_t *d_jpeg = nullptr, *h_jpeg = nullptr;
+    bool jpeg_unit = false;                   // the unit enqueued last ran the stage (omni_cam_jpeg)
+    int jpeg_n = 0;                           // main images of that unit
     std::mutex mu;
 };
 
@@ -109,6 +118,9 @@ void omni_cam_destroy(omni_cam* c) {
     (void)hipStreamSynchronize(c->c2->stream);
     void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw, c->d_poses, c->d_lm};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (c->jpeg) omni_jpeg_destroy(c->jpeg);
+    if (c->d_jpeg) (void)hipFree(c->d_jpeg);
+    if (c->h_jpeg) (void)hipHostFree(c->h_jpeg);
     if (c->host) (void)hipHostFree(c->host);
     if (c->e1) (void)hipEventDestroy(c->e1);
     if (c->e2) (void)hipEventDestroy(c->e2);
@@ -400,6 +412,20 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
     }
     OMNI_HIP_TRY(hipEventRecord(c->e1, s1));
     OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_g, c->g_dev, (size_t)n * c->out_dim * 4, hipMemcpyDeviceToHost, s2));
+    c->jpeg_unit = false;
+    if (c->jpeg_quality) {
+        // encode_image on the main image of every direction (loop_cam.cpp:306-308, 463-469): behind MobileNetVLAD's read of the same n images on ITS stream, next
+        // to the SuperPoint stack.  The reference blanks the mask's rows in the very pixels it encodes (:536-539 through a cv::Mat that shares its data); the
+        // unit's input block keeps them, so the kernel reads those rows as zeros
+        int row0 = c->H, row1 = c->H;
+        if (fisheye_mask) omni_fisheye_mask_rows(c->H, fisheye_mask, &row0, &row1);
+        int* d_meta = reinterpret_cast<int*>(c->d_jpeg + c->jpeg_meta);
+        if ((rc = omni::jpeg_check_enqueue(c->jpeg, stride, n, row0))) return rc;
+        if ((rc = omni::jpeg_launch(c->jpeg, s2, gray_dev, stride, n, row0, c->d_jpeg, d_meta, d_meta + c->n_cap))) return rc;
+        OMNI_HIP_TRY(hipMemcpyAsync(c->h_jpeg, c->d_jpeg, (size_t)n * c->jpeg_cap, hipMemcpyDeviceToHost, s2));
+        OMNI_HIP_TRY(hipMemcpyAsync(c->h_jpeg + c->jpeg_meta, d_meta, (size_t)2 * c->n_cap * 4, hipMemcpyDeviceToHost, s2));
+        c->jpeg_unit = true; c->jpeg_n = n;
+    }
     OMNI_HIP_TRY(hipEventRecord(c->e2, s2));
     c->pending = true;
     return OMNI_OK;
@@ -468,6 +494,49 @@ int omni_cam_landmarks(omni_cam* c, omni_cam_landmarks_result* out) {
     out->landmarks_3d = reinterpret_cast<const float*>(h + c->off_l3d);
     out->landmarks_flag = reinterpret_cast<const uint8_t*>(h + c->off_flag);
     out->count_3d = reinterpret_cast<const int*>(h + c->off_cnt);
+    return OMNI_OK;
+}
+
+// ---- send_img inside the unit --------------------------------------------------------------------------------------------------------------------------
+int omni_cam_set_jpeg(omni_cam* c, int quality, int64_t capacity_per_image) {
+    OMNI_REQUIRE(c, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_jpeg with a unit in flight (omni_cam_wait first)");
+    if (quality == 0) { c->jpeg_quality = 0; return OMNI_OK; }
+    OMNI_REQUIRE(quality >= 1 && quality <= 100, OMNI_ERR_INVALID, "omni_cam_set_jpeg: quality %d outside 1..100 (0: off)", quality);
+    OMNI_REQUIRE(capacity_per_image >= OMNI_JPEG_HEADER_BYTES + 2 && capacity_per_image <= 0x7fffffff, OMNI_ERR_INVALID,
+                 "omni_cam_set_jpeg: a capacity of %lld bytes, the header and EOI alone take %d", (long long)capacity_per_image, OMNI_JPEG_HEADER_BYTES + 2);
+    if (c->jpeg && quality == c->jpeg_quality && capacity_per_image == c->jpeg_cap) return OMNI_OK;
+    (void)hipSetDevice(c->c1->device);
+    // (set-up time: the frees below wait for the device)
+    if (c->jpeg) { omni_jpeg_destroy(c->jpeg); c->jpeg = nullptr; }
+    c->jpeg_quality = 0;
+    if (capacity_per_image != c->jpeg_cap || !c->d_jpeg) {
+        if (c->d_jpeg) (void)hipFree(c->d_jpeg);
+        if (c->h_jpeg) (void)hipHostFree(c->h_jpeg);
+        c->d_jpeg = c->h_jpeg = nullptr; c->jpeg_cap = 0;
+        c->jpeg_meta = ((size_t)c->n_cap * capacity_per_image + 255) & ~(size_t)255;
+        const size_t bytes = c->jpeg_meta + (size_t)2 * c->n_cap * 4;
+        OMNI_HIP_TRY(hipMalloc((void**)&c->d_jpeg, bytes));
+        OMNI_HIP_TRY(hipHostMalloc((void**)&c->h_jpeg, bytes, hipHostMallocDefault));
+        memset(c->h_jpeg, 0, bytes);
+        c->jpeg_cap = capacity_per_image;
+    }
+    c->jpeg = omni_jpeg_create(c->c2, c->W, c->H, c->n_cap, quality, capacity_per_image);
+    if (!c->jpeg) return OMNI_ERR_INVALID;                                    // (omni_jpeg_create left the message)
+    c->jpeg_quality = quality;
+    return OMNI_OK;
+}
+
+int omni_cam_jpeg(omni_cam* c, omni_cam_jpeg_result* out) {
+    OMNI_REQUIRE(c && out, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_jpeg with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->jpeg_unit, OMNI_ERR_INVALID, "omni_cam_jpeg: the last unit ran with the stage off (omni_cam_set_jpeg)");
+    out->n_images = c->jpeg_n; out->capacity = c->jpeg_cap;
+    out->bytes = c->h_jpeg;
+    out->sizes = reinterpret_cast<const int*>(c->h_jpeg + c->jpeg_meta);
+    out->status = out->sizes + c->n_cap;
     return OMNI_OK;
 }
 

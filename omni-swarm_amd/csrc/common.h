@@ -203,6 +203,15 @@ int landmarks_launch(hipStream_t stream, const omni_stereo_model& m, const doubl
 int landmarks_check_model(const omni_stereo_model* m);
 }  // namespace omni
 
+struct omni_jpeg;
+namespace omni {
+// jpeg.hip: n_images images as JPEG files (jpeg_plan.h) -- out_dev [n_images][the handle's capacity], sizes_dev / status_dev [n_images].  Asynchronous on `stream`,
+// which need not be the handle's own; jpeg_check_enqueue first.
+int jpeg_check_enqueue(const omni_jpeg* j, int stride, int n_images, int zero_from_row);
+int jpeg_launch(omni_jpeg* j, hipStream_t stream, const uint8_t* gray_dev, int stride, int n_images, int zero_from_row, uint8_t* out_dev, int* sizes_dev,
+                int* status_dev);
+}  // namespace omni
+
 // ---- 64-bit sortable keys -------------------------------------------------------------------------------------
 // key = (orderable(score) << 32) | (0xFFFFFFFF - id): descending key order == (score desc, id asc).
 __host__ __device__ static inline uint32_t omni_f32_orderable(float f) {

@@ -84,6 +84,14 @@ public:
         // that is NOT a loop.  A pair the device hands back (degenerate points: status HOST) runs on the host as before.  Off: the host path for every pair.
         // On by default: DESIGN.md section 0.2b has the gates and the measurements.  (set_device_homography: any time between two calls.)
         bool device_homography = true;
+        // send_img (swarm_loop.cpp:224-225; launch/pc-outdoor-fisheye.launch sets it with jpg_quality 75): the main image of every direction goes into its message as
+        // a JPEG file (encode_image, loop_cam.cpp:56-71, 306-308, 463-469), encoded inside the key-frame unit on the GPU (csrc/jpeg.hip) and copied by finish() into
+        // ImageDescriptor::image.  The bytes are libjpeg's defaults, pinned against Pillow (csrc/jpeg_plan.h); cv::imencode's own parity is unpinned.  The fisheye
+        // mask reaches the picture, as in the reference.  jpeg_capacity: bytes per image in the unit's result block (<= 0: width * height / 2); an image that does
+        // not fit leaves `image` empty and counts in jpeg_truncated().  (set_send_img: before the first key frame.)
+        bool send_img = false;
+        int jpg_quality = 50;
+        int64_t jpeg_capacity = 0;
         // CameraConfig (loop_defines.h:111-116): STEREO_FISHEYE = 1 -- a key frame is 4 directions x (up, down) flattened views, the bottom quarter of
         // every view blanked; PINHOLE_DEPTH = 2 (launch/realsense.launch, BASELINE.json configs[0]: 640 x 480) -- a key frame is ONE gray image, not
         // blanked, plus its 16-bit depth image in millimetres (set_depth), MAX_DIRS = 1 (swarm_loop.cpp:279-280), the query image is direction 0
@@ -138,6 +146,7 @@ private:
         geo_.MAX_DIRS = c.dirs();
         for (int p = 0; p < c.pipelines; ++p) lanes_.push_back(std::make_unique<Lane>(c, c.microbatch));
         apply_stereo_model();
+        apply_jpeg();
         if (c.geometry) {
             geo_.self_id = c.self_id; geo_.MIN_LOOP_NUM = c.min_loop_num; geo_.MIN_DIRECTION_LOOP = c.min_direction_loop;
             // Per candidate: (1) on this thread, the up to four direction pairs of compute_correspond_features (loop_detector.cpp:431-537) are
@@ -374,8 +383,28 @@ public:
         cfg_.device_landmarks = on;
         apply_stereo_model();
     }
+    // ---- send_img: the main images as JPEG files inside the key-frame unit (Config::send_img) ------------------------------------------------------------
+    bool send_img() const { return cfg_.send_img && !shard_; }      // (the sharded database builds no messages: the switch is ignored there, like device_landmarks)
+    bool send_img_config() const { return cfg_.send_img; }          // the switch as set, whatever the mode makes of it
+    int jpg_quality() const { return cfg_.jpg_quality; }
+    int64_t jpeg_capacity() const { return cfg_.jpeg_capacity > 0 ? cfg_.jpeg_capacity : std::max<int64_t>((int64_t)cfg_.width * cfg_.height / 2, OMNI_JPEG_HEADER_BYTES + 2); }
+    int64_t jpeg_truncated() const { return jpeg_truncated_.load(); }      // main images whose file did not fit jpeg_capacity(), so far: their `image` stayed empty
+    // before the first key frame: switches the stage on or off on every lane (what the C entry point omni_pipeline_set_send_img sets); quality 1..100
+    void set_send_img(bool on, int quality) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_send_img after the first key frame");
+        if (on && (quality < 1 || quality > 100)) throw std::invalid_argument("set_send_img: jpg_quality outside 1..100");
+        cfg_.send_img = on;
+        if (on) cfg_.jpg_quality = quality;
+        apply_jpeg();
+    }
 private:
     struct Lane;
+    void apply_jpeg(Lane& l) { l.cam.set_jpeg(send_img() ? cfg_.jpg_quality : 0, jpeg_capacity()); }
+    void apply_jpeg() {
+        for (auto& l : lanes_) apply_jpeg(*l);
+        for (auto& t : tail_lanes_) apply_jpeg(*t.second);
+    }
     void apply_stereo_model(Lane& l) {
         const omni_stereo_model m = stereo_model();
         l.cam.set_stereo_model(device_landmarks() ? &m : nullptr);
@@ -429,6 +458,7 @@ public:
         if (!shard_) throw std::runtime_error(std::string("omni_shard_create: ") + omni_last_error());
         world_ = world;
         apply_stereo_model();                                  // (off: this mode builds no messages)
+        apply_jpeg();
     }
     ~KeyframePipeline() { if (shard_) omni_shard_destroy(shard_); }
     int64_t db_rows() const { return shard_ ? omni_shard_ntotal(shard_) : det_.local_index.ntotal + det_.remote_index.ntotal; }
@@ -647,7 +677,7 @@ public:
         const int rem = n_keyframes % cfg_.microbatch;
         if (!rem) return nullptr;
         auto it = tail_lanes_.find(rem);
-        if (it == tail_lanes_.end()) { it = tail_lanes_.emplace(rem, std::make_unique<Lane>(cfg_, rem)).first; apply_stereo_model(*it->second); }
+        if (it == tail_lanes_.end()) { it = tail_lanes_.emplace(rem, std::make_unique<Lane>(cfg_, rem)).first; apply_stereo_model(*it->second); apply_jpeg(*it->second); }
         return it->second.get();
     }
 
@@ -787,6 +817,9 @@ private:
         // the unit's own landmarks (Config::device_landmarks): lifted floats, 3-D points and flags of every image, already in the pinned block
         const bool dev_lm = device_landmarks();
         const omni_cam_landmarks_result lmr = dev_lm ? lane.cam.landmarks() : omni_cam_landmarks_result{};
+        // the unit's own JPEG files of its main images (Config::send_img), already in the lane's pinned block
+        const bool jpg = send_img();
+        const omni_cam_jpeg_result jr = jpg ? lane.cam.jpeg() : omni_cam_jpeg_result{};
         auto heavy = [&](ImageDescriptor& im, int i) {
             if (dev_lm) fill_image_descriptor_device(im, r.kps_xy + (size_t)i * M * 2, r.n_kps[i], r.desc + (size_t)i * M * D, D, r.global_desc + (size_t)i * G, G,
                                                      lmr.norm2d + (size_t)i * M * 2, lmr.landmarks_3d + (size_t)i * M * 3, lmr.landmarks_flag + (size_t)i * M);
@@ -805,6 +838,10 @@ private:
                 ImageDescriptor& im = f.images[d];
                 // extractor_img_desc_deepnet (loop_cam.cpp:525-585) + the stamps of generate_stereo_image_descriptor (:362-374)
                 if (defer_heavy) im.landmark_num = r.n_kps[i]; else heavy(im, i);
+                if (jpg) {                                                          // encode_image (loop_cam.cpp:306-308, 463-469)
+                    if (jr.status[i] == OMNI_JPEG_OK) im.image.assign(jr.bytes + (size_t)i * jr.capacity, jr.bytes + (size_t)i * jr.capacity + jr.sizes[i]);
+                    else { im.image.clear(); ++jpeg_truncated_; }
+                }
                 stamp_image_descriptor(im, stamp, cfg_.self_id, to_msg(view_extrinsic(d, true)), pose, kf_id);
                 if (cfg_.geometry && !cfg_.stereo()) {
                     // generate_gray_depth_image_descriptor's landmarks (loop_cam.cpp:260-304): read from the depth image under each key point
@@ -934,6 +971,7 @@ private:
     size_t next_lane_ = 0;
     int carried_hits_ = 0;
     bool first_keyframe_seen_ = false;          // STEREO_PINHOLE: set_stereo_extrinsics is refused from the first key frame on
+    std::atomic<int64_t> jpeg_truncated_{0};
     bool any_keyframe_seen_ = false;            // set_device_landmarks is refused from the first key frame on
     std::vector<double> pose_stage_;            // unit_poses: the unit's poses on their way into the handle's pinned staging
     std::vector<FisheyeFrameDescriptor> frames_;

@@ -365,6 +365,14 @@ public:
         check(omni_cam_landmarks(h_, &r), "omni_cam_landmarks");
         return r;
     }
+    // send_img inside the unit (csrc/jpeg.hip; encode_image, loop_cam.cpp:56-71): set_jpeg once (quality 0: off again), jpeg() after wait() -- the unit's MAIN
+    // images (up / left cameras; every image of a mono handle) as baseline JPEG files, libjpeg's defaults (csrc/jpeg_plan.h; cv::imencode's parity unpinned)
+    void set_jpeg(int quality, int64_t capacity_per_image) { check(omni_cam_set_jpeg(h_, quality, capacity_per_image), "omni_cam_set_jpeg"); }
+    omni_cam_jpeg_result jpeg() {
+        omni_cam_jpeg_result r{};
+        check(omni_cam_jpeg(h_, &r), "omni_cam_jpeg");
+        return r;
+    }
     // non-blocking: would wait() return at once?
     bool ready() { int r = 0; check(omni_cam_ready(h_, &r), "omni_cam_ready"); return r != 0; }
     // blocks until the key frame is done; pointers stay valid until the next enqueue on this object

@@ -206,6 +206,7 @@ struct SwarmLoopParams {
         c.min_loop_num = min_loop_feature_num; c.min_direction_loop = min_direction_loop; c.triangle_thres = triangle_thres; c.accept_min_3d_pts = accept_min_3d_pts;
         c.camera_configuration = camera_configuration; c.depth_near = depth_near_thres; c.depth_far = depth_far_thres;
         c.pca_comp = pca_comp_path; c.pca_mean = pca_mean_path;
+        c.send_img = send_img; c.jpg_quality = jpg_quality;                 // swarm_loop.cpp:224-225 -> LoopCam (encode_image, loop_cam.cpp:56-71)
     }
     template <class Intake> void to_intake(Intake& i) const {              // swarm_loop.cpp:217-218, 238 -> KeyframeIntake
         i.max_freq = max_freq; i.min_movement_keyframe = min_movement_keyframe; i.accept_nonkeyframe_waitsec = nonkeyframe_waitsec;

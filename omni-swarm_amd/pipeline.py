@@ -32,6 +32,9 @@ HOMOGRAPHY_SYMBOLS = ["omni_homography_last_error", "omni_pipeline_set_device_ho
 _stereo_lib = None
 _landmarks_lib = None
 _homography_lib = None
+JPEG_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpeg.so")
+JPEG_SYMBOLS = ["omni_jpeg_host_last_error", "omni_pipeline_set_send_img", "omni_pipeline_get_send_img", "omni_pipeline_jpeg_truncated", "omni_pipeline_frame_image"]
+_jpeg_lib = None
 
 
 def lib():
@@ -154,11 +157,27 @@ def homography_lib():
     return _homography_lib
 
 
+def jpeg_lib():
+    global _jpeg_lib
+    if _jpeg_lib is None:
+        lib()
+        if not os.path.exists(JPEG_LIB_PATH):
+            raise OSError(f"{JPEG_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(JPEG_LIB_PATH)
+        L.omni_jpeg_host_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_send_img.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.omni_pipeline_get_send_img.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.omni_pipeline_jpeg_truncated.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_pipeline_frame_image.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        _jpeg_lib = L
+    return _jpeg_lib
+
+
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None, device_homography=None):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -168,6 +187,8 @@ class KeyframePipeline:
         threads (the same bits either way); None: the library's default.
         device_homography: True / False = the homography RANSAC of a `geometry` pipeline's loop candidates on the GPU, in the round trip that matches their
         direction pairs / on the host's geometry threads (the same masks either way); None: the library's default.
+        send_img / jpg_quality: the reference's switch of the same name (default off, quality 50): the main image of every direction goes into its message as a
+        JPEG file, encoded inside the key-frame unit on the GPU (set_send_img).
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -194,11 +215,41 @@ class KeyframePipeline:
             self.set_device_landmarks(device_landmarks)
         if device_homography is not None:
             self.set_device_homography(device_homography)
+        if send_img:
+            self.set_send_img(True, jpg_quality)
 
     def set_device_landmarks(self, on: bool):
         """before the first key frame: stereo landmarks inside the key-frame unit (GPU) or on the host's geometry threads"""
         if landmarks_lib().omni_pipeline_set_device_landmarks(self.h, int(bool(on))):
             raise capi.OmniError(f"omni_pipeline_set_device_landmarks: {landmarks_lib().omni_landmarks_last_error().decode()}")
+
+    def _jpeg(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {jpeg_lib().omni_jpeg_host_last_error().decode()}")
+
+    def set_send_img(self, on: bool, jpg_quality: int = 50):
+        """send_img: every following key frame's main images go into their messages as JPEG files, encoded inside the key-frame unit on the GPU (csrc/jpeg.hip;
+        libjpeg's defaults, pinned against Pillow -- cv::imencode's own parity is unpinned).  Before the first key frame.  Ignored under a sharded database."""
+        self._jpeg(jpeg_lib().omni_pipeline_set_send_img(self.h, int(bool(on)), int(jpg_quality)), "omni_pipeline_set_send_img")
+
+    def send_img(self):
+        """(the switch as set, jpg_quality, whether this pipeline's mode encodes at all)"""
+        on, q, act = C.c_int(), C.c_int(), C.c_int()
+        self._jpeg(jpeg_lib().omni_pipeline_get_send_img(self.h, C.byref(on), C.byref(q), C.byref(act)), "omni_pipeline_get_send_img")
+        return bool(on.value), q.value, bool(act.value)
+
+    def jpeg_truncated(self) -> int:
+        n = C.c_int64()
+        self._jpeg(jpeg_lib().omni_pipeline_jpeg_truncated(self.h, C.byref(n)), "omni_pipeline_jpeg_truncated")
+        return n.value
+
+    def frame_image(self, msg_id: int, direction: int) -> bytes:
+        """the JPEG file direction `direction` of key frame `msg_id` carries in the detector's database (b"": none); between two calls of run / push_keyframe / flush"""
+        n = C.c_int64()
+        self._jpeg(jpeg_lib().omni_pipeline_frame_image(self.h, msg_id, direction, None, 0, C.byref(n)), "omni_pipeline_frame_image")
+        out = np.empty(max(n.value, 1), np.uint8)
+        self._jpeg(jpeg_lib().omni_pipeline_frame_image(self.h, msg_id, direction, out.ctypes.data, n.value, C.byref(n)), "omni_pipeline_frame_image")
+        return out[:n.value].tobytes()
 
     def set_device_homography(self, on: bool):
         """the homography RANSAC of the loop candidates on the GPU (next to the matcher) or on the host's geometry threads; between any two calls"""
