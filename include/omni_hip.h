@@ -516,6 +516,26 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
                                    int mode, int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags,
                                    int* q_idx, int* t_idx, float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status);
 
+/* ---- loop verification: the RANSAC half of compute_relative_pose (loop_detector.cpp:355-413: cv::solvePnPRansac over EPnP models of 5 points, reprojection
+ * error 3, confidence 0.99) on the GPU, f64 (csrc/pnp.hip; the arithmetic: csrc/pnp_plan.h, operation for operation that of host/geometry.hpp's
+ * ransac_run<PnPModel> -- the same mask, the same best model).  The refit on the inliers (geom::pnp_refit) stays with the caller.  Per candidate:
+ *   status  OMNI_PNP_SKIPPED   fewer than 6 correspondences: solve_pnp_ransac returns false without drawing;
+ *           OMNI_PNP_OK        the best model has at least 6 inliers: mask[i] = 1 for them, Rt = that model (R row major, then t: X_cam = R X + t);
+ *           OMNI_PNP_NO_MODEL  the host function's `false` (no model, or a best model with five inliers): mask all 0, Rt all 0;
+ *           OMNI_PNP_HOST      the device gave up (more than 256 random numbers for one group of five distinct indices): run the host function.
+ *   info    {count, iterations run, iteration of the best model (-1: none), inliers of the best model}. */
+#define OMNI_PNP_SKIPPED 0
+#define OMNI_PNP_OK 1
+#define OMNI_PNP_NO_MODEL 2
+#define OMNI_PNP_HOST 3
+/* X_xyz [n_cands][max_n][3] / u_xy [n_cands][max_n][2] float (candidate c: the 3-D points and the normalised image points of its count[c] correspondences),
+ * count [n_cands] in [0, max_n], max_iters [n_cands] in [1, 1000] (compute_relative_pose: 100, 1 000 in init_mode).  Outputs (host): status [n_cands],
+ * mask [n_cands][max_n] u8 (zeros behind count), Rt [n_cands][12], info [n_cands][4].  1 <= n_cands <= 64, 1 <= max_n <= 2048.  One upload, one launch, one
+ * download; blocking.  The stop rule's table rows (inliers -> iterations, evaluated on the host with its own pow / log) are kept per context and travel with
+ * the upload. */
+int omni_pnp_ransac_multi(omni_ctx* ctx, int n_cands, int max_n, const float* X_xyz, const float* u_xy, const int* count, const int* max_iters, int* status,
+                          uint8_t* mask, double* Rt, int* info);
+
 /* ---- send_img: the main image of every direction as a baseline JPEG, what encode_image's cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, JPG_QUALITY}) asks of
  * libjpeg (loop_cam.cpp:56-71, 306-308, 463-469), on the GPU (csrc/jpeg.hip).  The arithmetic is stated once, in csrc/jpeg_plan.h: one 8-bit component, the IJG
  * luminance table scaled by the quality, jfdctint's integer DCT, the standard Huffman tables, JFIF APP0 -- libjpeg's defaults, PINNED byte for byte against Pillow

@@ -42,11 +42,13 @@ SYMBOLS = [
     "omni_shard_search", "omni_flatten_create", "omni_flatten_destroy", "omni_flatten_out_bytes", "omni_flatten_enqueue_dev",
     "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
     "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
-    "omni_homography_ransac_multi", "omni_bf_match_homography_multi",
+    "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
 ]
 JPEG_OK, JPEG_TRUNCATED, JPEG_HEADER_BYTES = 0, 1, 328      # include/omni_hip.h OMNI_JPEG_*
 HG_UNFILTERED, HG_OK, HG_NO_MODEL, HG_HOST = 0, 1, 2, 3     # include/omni_hip.h OMNI_HG_*: the status of one pair's homography RANSAC
+PNP_SKIPPED, PNP_OK, PNP_NO_MODEL, PNP_HOST = 0, 1, 2, 3    # include/omni_hip.h OMNI_PNP_*: the status of one candidate's PnP RANSAC
+PNP_MAX_POINTS, PNP_MAX_ITERS = 2048, 1000
 
 
 class OmniError(RuntimeError):
@@ -218,6 +220,7 @@ def lib():
     sig("omni_cam_enqueue_raw_host_parts", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int])
     sig("omni_cam_wait", C.c_int, [_vp, C.POINTER(_CamResult)])
     sig("omni_homography_ransac_multi", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _ip, _ip, _vp, C.POINTER(C.c_double), _ip])
+    sig("omni_pnp_ransac_multi", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _ip, _ip, _ip, _vp, C.POINTER(C.c_double), _ip])
     sig("omni_bf_match_homography_multi", C.c_int, [_vp, C.c_int, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
                                                   C.POINTER(_vp), _ip, _ip, _ip, _fp, _ip, _ip, _ip, _vp, C.POINTER(C.c_double), _ip, _ip])
     sig("omni_landmarks_enqueue_dev", C.c_int, [_vp, C.POINTER(StereoModel), _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -1023,6 +1026,22 @@ def homography_ransac_multi(ctx: Context, pairs) -> list:
     _check(lib().omni_homography_ransac_multi(ctx.h, P, max_n, _pf(src), _pf(dst), count.ctypes.data_as(_ip), status.ctypes.data_as(_ip), mask.ctypes.data,
                                               H.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(_ip)))
     return [{"status": int(status[p]), "mask": mask[p, :count[p]].copy(), "H": H[p].copy(), "info": info[p].copy()} for p in range(P)]
+
+
+def pnp_ransac_multi(ctx: Context, cands) -> list:
+    """[(X_xyz [n][3], u_xy [n][2], max_iters), ...] (float 3-D points and normalised image points) -> [{status, mask [n], Rt [12], info [4]}]: the RANSAC half of
+    cv::solvePnPRansac(X, u, K = I, ..., max_iters, 3, 0.99, inliers) of every candidate in one GPU round trip (omni_pnp_ransac_multi); status is one of PNP_*"""
+    P = len(cands)
+    count = np.array([len(a) for a, _, _ in cands], np.int32)
+    iters = np.array([it for _, _, it in cands], np.int32)
+    max_n = int(max(1, count.max()))
+    X, u = np.zeros((P, max_n, 3), np.float32), np.zeros((P, max_n, 2), np.float32)
+    for p, (a, b, _) in enumerate(cands):
+        X[p, :count[p]], u[p, :count[p]] = _f32(a).reshape(-1, 3), _f32(b).reshape(-1, 2)
+    status, mask, Rt, info = np.zeros(P, np.int32), np.zeros((P, max_n), np.uint8), np.zeros((P, 12), np.float64), np.zeros((P, 4), np.int32)
+    _check(lib().omni_pnp_ransac_multi(ctx.h, P, max_n, _pf(X), _pf(u), count.ctypes.data_as(_ip), iters.ctypes.data_as(_ip), status.ctypes.data_as(_ip), mask.ctypes.data,
+                                       Rt.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(_ip)))
+    return [{"status": int(status[p]), "mask": mask[p, :count[p]].copy(), "Rt": Rt[p].copy(), "info": info[p].copy()} for p in range(P)]
 
 
 def bf_match_homography_multi(ctx: Context, pairs, mode: int = BF_OPENCV) -> list:

@@ -148,6 +148,7 @@ struct omni_ctx {
     omni::HostBuf hstage;
     omni::DevBuf ransac_T;    // homography.hip: the stop rule's table T[count][good] for count <= ransac_T_n (csrc/ransac_plan.h), filled once
     int ransac_T_n = 0;
+    std::vector<std::vector<int>> pnp_T;      // pnp.hip: the PnP RANSAC's stop-rule rows T[good] by count (csrc/pnp_plan.h), each filled on first use; on the host
     int ensure_zero_page() {
         if (zero_page) return OMNI_OK;
         OMNI_HIP_TRY(hipMalloc(&zero_page, OMNI_ZERO_PAGE_BYTES));

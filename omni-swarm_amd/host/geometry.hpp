@@ -640,21 +640,37 @@ struct PnPModel {
 // solvePnPRansac(objectPoints, imagePoints, K = I, no distortion, rvec, tvec, false, iterations, reprojectionError, confidence, inliers), OpenCV 3.4
 // with flags = SOLVEPNP_ITERATIVE: RANSAC over EPnP models of 5 points, then solvePnP(ITERATIVE) on the inliers = a DLT start + the
 // Levenberg-Marquardt least-squares refit.  inliers = indices, ascending.
-inline bool solve_pnp_ransac(const std::vector<Vec3>& X, const std::vector<Vec2>& u, int iterations, double reproj_error, double confidence,
-                             Rt& pose, std::vector<int>& inliers) {
-    inliers.clear();
+// Two halves: pnp_ransac (the mask and the best EPnP model; csrc/pnp_plan.h restates it for the GPU) and pnp_refit (everything behind the mask).
+inline bool pnp_ransac(const std::vector<Vec3>& X, const std::vector<Vec2>& u, int iterations, double reproj_error, double confidence, std::vector<uint8_t>& mask,
+                       Rt& best) {
     const int n = (int)X.size();
+    mask.clear();
     if (n < 6 || (int)u.size() != n) return false;
     PnPModel m{X, u, {}, {}};
-    std::vector<uint8_t> mask;
     if (!ransac_run(m, n, 5, reproj_error, confidence, iterations, mask)) return false;
+    best = m.best;
+    return true;
+}
+// the inlier list of `mask`, the `< 6` test, the DLT start (or `best`, the RANSAC's model, when the DLT fails) and the Levenberg-Marquardt refit
+inline bool pnp_refit(const std::vector<Vec3>& X, const std::vector<Vec2>& u, const std::vector<uint8_t>& mask, const Rt& best, Rt& pose, std::vector<int>& inliers) {
+    inliers.clear();
+    const int n = (int)X.size();
+    if ((int)mask.size() != n || (int)u.size() != n) return false;
     for (int i = 0; i < n; ++i) if (mask[i]) inliers.push_back(i);
     if ((int)inliers.size() < 6) return false;
     Rt fit;
-    if (!pnp_dlt(X, u, inliers.data(), (int)inliers.size(), fit)) fit = m.best;
+    if (!pnp_dlt(X, u, inliers.data(), (int)inliers.size(), fit)) fit = best;
     pnp_refine(X, u, inliers.data(), (int)inliers.size(), fit, 30);
     pose = fit;
     return true;
+}
+inline bool solve_pnp_ransac(const std::vector<Vec3>& X, const std::vector<Vec2>& u, int iterations, double reproj_error, double confidence,
+                             Rt& pose, std::vector<int>& inliers) {
+    inliers.clear();
+    std::vector<uint8_t> mask;
+    Rt best;
+    if (!pnp_ransac(X, u, iterations, reproj_error, confidence, mask, best)) return false;
+    return pnp_refit(X, u, mask, best, pose, inliers);
 }
 // PnPRestoCamPose (loop_utils.cpp:69-81): camera pose in the frame of the 3-D points from (R, t) of X_cam = R X + t
 inline Pose pnp_res_to_cam_pose(const Rt& p) { const Mat3 Rwc = p.R.T(); return {Rwc * (-1.0 * p.t), quat_from_R(Rwc)}; }

@@ -84,6 +84,12 @@ public:
         // that is NOT a loop.  A pair the device hands back (degenerate points: status HOST) runs on the host as before.  Off: the host path for every pair.
         // On by default: DESIGN.md section 0.2b has the gates and the measurements.  (set_device_homography: any time between two calls.)
         bool device_homography = true;
+        // `geometry`: the RANSAC half of compute_relative_pose's solvePnPRansac (loop_detector.cpp:390-391: 100 EPnP hypotheses, 1 000 in init_mode) runs on the
+        // GPU (omni_pnp_ransac_multi, csrc/pnp.hip: the same mask and best model bit for bit, tests/test_gpu_pnp.py), one blocking call per candidate from its
+        // geometry task on a context of its own; the refit (geom::pnp_refit) stays in the task.  A candidate the device hands back (status HOST) or that has more
+        // points than the entry takes runs geom::solve_pnp_ransac as before.  OFF by default: DESIGN.md section 0.2d has the measurements a later change will
+        // decide on.  (set_device_pnp: any time between two calls.)
+        bool device_pnp = false;
         // send_img (swarm_loop.cpp:224-225; launch/pc-outdoor-fisheye.launch sets it with jpg_quality 75): the main image of every direction goes into its message as
         // a JPEG file (encode_image, loop_cam.cpp:56-71, 306-308, 463-469), encoded inside the key-frame unit on the GPU (csrc/jpeg.hip) and copied by finish() into
         // ImageDescriptor::image.  The bytes are libjpeg's defaults, pinned against Pillow (csrc/jpeg_plan.h); cv::imencode's own parity is unpinned.  The fisheye
@@ -147,6 +153,7 @@ private:
         for (int p = 0; p < c.pipelines; ++p) lanes_.push_back(std::make_unique<Lane>(c, c.microbatch));
         apply_stereo_model();
         apply_jpeg();
+        if (c.device_pnp) ensure_pnp_context();
         if (c.geometry) {
             geo_.self_id = c.self_id; geo_.MIN_LOOP_NUM = c.min_loop_num; geo_.MIN_DIRECTION_LOOP = c.min_direction_loop;
             // Per candidate: (1) on this thread, the up to four direction pairs of compute_correspond_features (loop_detector.cpp:431-537) are
@@ -211,6 +218,7 @@ public:
         std::vector<BFMatcherL2X::Pair> pairs;
         std::vector<BFMatcherL2X::PairH> pairs_h;                    // device_homography: the same pairs with their 2-D points and flags
         const bool dev_hg = device_homography();
+        PnPRansacX* const dev_pnp = device_pnp() ? pnp_.get() : nullptr;      // (lives as long as the pipeline once made: the tasks may keep the pointer)
         std::vector<int> pair_dim;                                   // descriptor length of every pair (one match_multi call per distinct length)
         std::vector<Prepared> prep(deferred_.size());
         const int nd = geo_.MAX_DIRS;
@@ -266,8 +274,25 @@ public:
             auto mine_h = std::make_shared<std::vector<BFMatcherL2X::Homography>>();
             for (size_t j = 0; j < prep[ci].count; ++j) { mine_o->push_back(std::move(outs[prep[ci].first + j])); if (dev_hg) mine_h->push_back(std::move(hgs[prep[ci].first + j])); }
             const Deferred c = deferred_[ci];
-            auto work = [this, g0 = geo_, mine_p, mine_o, mine_d, mine_h, c]() -> Result {    // g0: the parameters, copied on this thread
+            auto work = [this, g0 = geo_, mine_p, mine_o, mine_d, mine_h, c, dev_pnp]() -> Result {    // g0: the parameters, copied on this thread
                 LoopGeometry g = g0;
+                if (dev_pnp)                                           // the candidate's PnP RANSAC on the device, from this thread; what it hands back runs on the host
+                    g.pnp_ransac = [this, dev_pnp](const std::vector<geom::Vec3>& X, const std::vector<geom::Vec2>& u, int iterations, std::vector<uint8_t>& mask, geom::Rt& best) {
+                        const size_t n = X.size();
+                        if (n < 6 && u.size() == n) return 0;          // solve_pnp_ransac's `false` without any work: no round trip for it, and it is not counted
+                        if (u.size() != n || n > (size_t)PnPRansacX::kMaxPoints) { ++pnp_candidates_host_; return -1; }
+                        std::vector<float> Xf(n * 3), uf(n * 2);       // float-valued already (Point3f landmarks, rotate_pt_norm2d's float cast): exact
+                        for (size_t i = 0; i < n; ++i) { Xf[3 * i] = (float)X[i].x; Xf[3 * i + 1] = (float)X[i].y; Xf[3 * i + 2] = (float)X[i].z; uf[2 * i] = (float)u[i].x; uf[2 * i + 1] = (float)u[i].y; }
+                        std::vector<PnPRansacX::Result> r;
+                        dev_pnp->run_multi({{Xf.data(), uf.data(), (int)n, iterations}}, r);
+                        if (r[0].status == OMNI_PNP_HOST) { ++pnp_candidates_host_; return -1; }
+                        ++pnp_candidates_device_;
+                        if (r[0].status != OMNI_PNP_OK) return 0;
+                        mask = r[0].mask;
+                        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) best.R.m[a][b] = r[0].Rt[3 * a + b];
+                        best.t = {r[0].Rt[9], r[0].Rt[10], r[0].Rt[11]};
+                        return 1;
+                    };
                 if (!mine_h->empty())                                  // the pair's mask from the round trip above; a pair the device handed back runs on the host
                     g.homography_mask = [&](const ImageDescriptor& nw, const ImageDescriptor& old, const std::vector<geom::Vec2>& old_2d, const std::vector<geom::Vec2>&,
                                             std::vector<uint8_t>& mask) {
@@ -376,6 +401,14 @@ public:
     // direction pairs whose mask came from the device / that ran geom::find_homography_ransac although the switch was on (the device's status HOST), so far
     int homography_pairs_device() const { return homography_pairs_device_.load(); }
     int homography_pairs_host() const { return homography_pairs_host_.load(); }
+    // ---- the PnP RANSAC of the loop candidates on the GPU (Config::device_pnp) ------------------------------------------------------------------------------
+    bool device_pnp() const { return cfg_.device_pnp && cfg_.geometry && !shard_; }      // (the sharded database builds no messages)
+    bool device_pnp_config() const { return cfg_.device_pnp; }      // the switch as set, whatever the mode makes of it
+    // between two calls of run / push_keyframe / poll / flush (what the C entry point omni_pipeline_set_device_pnp sets): the next micro-batch's candidates
+    void set_device_pnp(bool on) { std::lock_guard<std::mutex> lk(intake_mu_); if (on) ensure_pnp_context(); cfg_.device_pnp = on; }
+    // candidates whose RANSAC ran on the device / that ran geom::solve_pnp_ransac although the switch was on (handed back, or too many points), so far
+    int pnp_candidates_device() const { return pnp_candidates_device_.load(); }
+    int pnp_candidates_host() const { return pnp_candidates_host_.load(); }
     // before the first key frame: switches the stage on or off on every lane (what the C entry point omni_pipeline_set_device_landmarks sets)
     void set_device_landmarks(bool on) {
         std::lock_guard<std::mutex> lk(intake_mu_);
@@ -437,6 +470,20 @@ public:
         apply_stereo_model();                                  // (the units triangulate from the same extrinsics the messages carry)
     }
 
+    // A key frame that arrived from ANOTHER drone (LoopNet's reassembled message; LoopDetector::on_image_recv, loop_detector.cpp:11-137), handed to the detector on
+    // the calling thread between two calls of run / push_keyframe / poll / flush, after a flush().  Everything deferred earlier is verified first; the frame's own
+    // candidate is verified on the spot -- the detector needs the verdict for its init-mode counters -- with init_mode's limits (1 000 PnP iterations, the lower
+    // gates) while fewer than inter_drone_init_frames loops connect the two drones.  The candidate goes into candidates(), an accepted loop into edges().
+    LoopCandidate on_remote_frame(const FisheyeFrameDescriptor& f) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (shard_) throw std::runtime_error("on_remote_frame: the sharded database builds no messages");
+        if (f.drone_id == cfg_.self_id) throw std::invalid_argument("on_remote_frame: the frame carries this drone's own id");
+        collect_geometry();
+        const LoopCandidate r = det_.on_image_recv(f);
+        collect_geometry();
+        if (r.found) candidates_.push_back({f.msg_id, r.old_msg_id, r.direction_new, r.direction_old});
+        return r;
+    }
     LoopDetectorCore& detector() { return det_; }
     LoopGeometry& geometry() { return geo_; }
     // the reference's launch parameters (host/swarm_loop_params.hpp) that reach the detector and the geometry stage AFTER construction (the constructor took
@@ -937,6 +984,13 @@ private:
     bool async_detector_ = [] { int v = 1; check(omni_config_value("OMNI_DETECTOR_ASYNC", &v), "omni_config_value"); return v != 0; }();
     bool async_geometry_ = [] { int v = 1; check(omni_config_value("OMNI_GEOMETRY_ASYNC", &v), "omni_config_value"); return v != 0; }();
     std::atomic<int> homography_pairs_device_{0}, homography_pairs_host_{0};      // (counted by the geometry tasks; declared before the pool: outlive its threads)
+    std::atomic<int> pnp_candidates_device_{0}, pnp_candidates_host_{0};
+    // device_pnp: a context (stream, staging, mutex) of its own -- the geometry tasks block on it for the length of a candidate's RANSAC, and neither the unit
+    // enqueues, the detector step nor the matcher round trip of the host thread (the lanes' contexts, index_ctx_) ever wait for that mutex.  Made when the
+    // switch is first on, kept until the pipeline goes (declared before the pool: outlives its threads)
+    std::unique_ptr<Context> pnp_ctx_;
+    std::unique_ptr<PnPRansacX> pnp_;
+    void ensure_pnp_context() { if (!pnp_) { pnp_ctx_ = std::make_unique<Context>(cfg_.device, false); pnp_ = std::make_unique<PnPRansacX>(*pnp_ctx_); } }
     std::unique_ptr<TaskPool> pool_;
     std::unique_ptr<TaskPool> msg_pool_ = [] { const int n = cfg_int("OMNI_MESSAGE_THREADS"); return n > 0 ? std::make_unique<TaskPool>(n) : nullptr; }();
     std::vector<ImageDescriptor> downs_;        // the down-camera halves of the micro-batch being finished

@@ -163,6 +163,11 @@ public:
     // match, and returns true; false (a pair it cannot serve: the device's status HOST) and an unset hook run geom::find_homography_ransac here
     std::function<bool(const ImageDescriptor& nw, const ImageDescriptor& old, const std::vector<geom::Vec2>& old_2d, const std::vector<geom::Vec2>& new_2d,
                        std::vector<uint8_t>& mask)> homography_mask;
+    // optional: the RANSAC half of compute_relative_pose's solvePnPRansac computed elsewhere (the GPU: PnPRansacX, csrc/pnp.hip -- the same mask and the same best
+    // EPnP model, bit for bit).  Given the correspondences and the iteration limit it returns 1 with `mask` (one entry per correspondence) and `best` filled: a
+    // model; 0: no model (geom::pnp_ransac's `false`, or fewer than six inliers); -1 (a candidate it cannot serve: the device's status HOST, more points than
+    // the device takes) and an unset hook run geom::solve_pnp_ransac here.  geom::pnp_refit follows a model either way.
+    std::function<int(const std::vector<geom::Vec3>& X, const std::vector<geom::Vec2>& u, int iterations, std::vector<uint8_t>& mask, geom::Rt& best)> pnp_ransac;
     int loop_count = 0;
 
     struct Correspondence {
@@ -235,7 +240,14 @@ public:
                               const geom::Pose& drone_pose_now, const geom::Pose& drone_pose_old, geom::Pose& DP_old_to_new, bool init_mode, int& inlier_num) const {
         geom::Rt rt;
         std::vector<int> inliers;
-        const bool ok = geom::solve_pnp_ransac(matched_3d_now, matched_2d_norm_old, init_mode ? 1000 : 100, 3.0, 0.99, rt, inliers);
+        const int iterations = init_mode ? 1000 : 100;
+        std::vector<uint8_t> mask;
+        geom::Rt best;
+        const int served = pnp_ransac ? pnp_ransac(matched_3d_now, matched_2d_norm_old, iterations, mask, best) : -1;
+        bool ok;
+        if (served == 0) ok = false;
+        else if (served > 0 && mask.size() == matched_3d_now.size()) ok = geom::pnp_refit(matched_3d_now, matched_2d_norm_old, mask, best, rt, inliers);
+        else ok = geom::solve_pnp_ransac(matched_3d_now, matched_2d_norm_old, iterations, 3.0, 0.99, rt, inliers);
         if (!ok) return 0;
         const geom::Pose p_cam_old_in_new = geom::pnp_res_to_cam_pose(rt);
         const geom::Pose p_drone_old_in_new = p_cam_old_in_new * old_extrinsic.inverse();

@@ -492,6 +492,41 @@ private:
     int mode_;
 };
 
+// The RANSAC half of cv::solvePnPRansac(3d, 2d, K = I, ..., iterations, 3, 0.99, inliers) as compute_relative_pose calls it (loop_detector.cpp:390-391), on the GPU
+// (omni_pnp_ransac_multi, csrc/pnp.hip): per candidate the float-valued 3-D points [count][3] and normalised image points [count][2].  out[c]: status (OMNI_PNP_*),
+// mask over the correspondences, the best EPnP model (R row major, then t) and {count, iterations, best iteration, inliers}.  Blocking; callers on several
+// threads take turns on the context, so give it one that nothing latency-critical shares.
+class PnPRansacX {
+public:
+    static constexpr int kMaxPoints = 2048;      // the entry's max_n limit
+    explicit PnPRansacX(Context& ctx) : ctx_(ctx) {}
+    struct Candidate { const float* X_xyz; const float* u_xy; int count; int max_iters; };
+    struct Result { int status = OMNI_PNP_SKIPPED; std::vector<uint8_t> mask; double Rt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int info[4] = {0, 0, -1, 0}; };
+    void run_multi(const std::vector<Candidate>& cands, std::vector<Result>& out) {
+        out.assign(cands.size(), {});
+        if (cands.empty()) return;
+        const size_t C = cands.size();
+        int max_n = 1;
+        for (const Candidate& c : cands) max_n = std::max(max_n, c.count);
+        std::vector<float> X(C * max_n * 3, 0.f), u(C * max_n * 2, 0.f);
+        std::vector<int> count(C), iters(C), status(C), info(C * 4);
+        for (size_t c = 0; c < C; ++c) {
+            count[c] = cands[c].count; iters[c] = cands[c].max_iters;
+            if (count[c] > 0) { std::copy(cands[c].X_xyz, cands[c].X_xyz + (size_t)count[c] * 3, X.begin() + c * max_n * 3); std::copy(cands[c].u_xy, cands[c].u_xy + (size_t)count[c] * 2, u.begin() + c * max_n * 2); }
+        }
+        std::vector<uint8_t> mask(C * max_n);
+        std::vector<double> Rt(C * 12);
+        check(omni_pnp_ransac_multi(ctx_.get(), (int)C, max_n, X.data(), u.data(), count.data(), iters.data(), status.data(), mask.data(), Rt.data(), info.data()), "PnPRansacX::run_multi");
+        for (size_t c = 0; c < C; ++c) {
+            out[c].status = status[c];
+            out[c].mask.assign(mask.begin() + c * max_n, mask.begin() + c * max_n + count[c]);
+            std::copy(Rt.begin() + c * 12, Rt.begin() + c * 12 + 12, out[c].Rt); std::copy(info.begin() + c * 4, info.begin() + c * 4 + 4, out[c].info);
+        }
+    }
+private:
+    Context& ctx_;
+};
+
 // ---- LoopDetector's database and decision rules (loop_detector.cpp:11-287), POD messages instead of swarm_msgs -------
 struct Point3f { float x = 0, y = 0, z = 0; };
 struct PoseMsg { double position[3] = {0, 0, 0}; double quat_wxyz[4] = {1, 0, 0, 0}; };     // Pose_t as fromROSPose fills it (loop_cam.cpp:366-368)

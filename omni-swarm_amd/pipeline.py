@@ -29,9 +29,13 @@ LANDMARKS_SYMBOLS = ["omni_landmarks_last_error", "omni_pipeline_set_device_land
 # where the pipeline runs the homography RANSAC of its loop candidates: include/omni_host_homography.h, lib/libomni_host_homography.so (the same handle)
 HOMOGRAPHY_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_homography.so")
 HOMOGRAPHY_SYMBOLS = ["omni_homography_last_error", "omni_pipeline_set_device_homography", "omni_pipeline_get_device_homography"]
+# where the pipeline runs the PnP RANSAC of its loop candidates: include/omni_host_pnp.h, lib/libomni_host_pnp.so (the same handle)
+PNP_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_pnp.so")
+PNP_SYMBOLS = ["omni_pnp_last_error", "omni_pipeline_set_device_pnp", "omni_pipeline_get_device_pnp", "omni_pipeline_recv_copy_as_remote"]
 _stereo_lib = None
 _landmarks_lib = None
 _homography_lib = None
+_pnp_lib = None
 JPEG_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpeg.so")
 JPEG_SYMBOLS = ["omni_jpeg_host_last_error", "omni_pipeline_set_send_img", "omni_pipeline_get_send_img", "omni_pipeline_jpeg_truncated", "omni_pipeline_frame_image"]
 _jpeg_lib = None
@@ -157,6 +161,21 @@ def homography_lib():
     return _homography_lib
 
 
+def pnp_lib():
+    global _pnp_lib
+    if _pnp_lib is None:
+        lib()
+        if not os.path.exists(PNP_LIB_PATH):
+            raise OSError(f"{PNP_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(PNP_LIB_PATH)
+        L.omni_pnp_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_device_pnp.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_device_pnp.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.omni_pipeline_recv_copy_as_remote.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        _pnp_lib = L
+    return _pnp_lib
+
+
 def jpeg_lib():
     global _jpeg_lib
     if _jpeg_lib is None:
@@ -177,7 +196,7 @@ class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -187,6 +206,8 @@ class KeyframePipeline:
         threads (the same bits either way); None: the library's default.
         device_homography: True / False = the homography RANSAC of a `geometry` pipeline's loop candidates on the GPU, in the round trip that matches their
         direction pairs / on the host's geometry threads (the same masks either way); None: the library's default.
+        device_pnp: True / False = the EPnP RANSAC of a `geometry` pipeline's loop candidates on the GPU, one call per candidate / on the host's geometry
+        threads (the same edges either way); None: the library's default, which is off.
         send_img / jpg_quality: the reference's switch of the same name (default off, quality 50): the main image of every direction goes into its message as a
         JPEG file, encoded inside the key-frame unit on the GPU (set_send_img).
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
@@ -215,6 +236,8 @@ class KeyframePipeline:
             self.set_device_landmarks(device_landmarks)
         if device_homography is not None:
             self.set_device_homography(device_homography)
+        if device_pnp is not None:
+            self.set_device_pnp(device_pnp)
         if send_img:
             self.set_send_img(True, jpg_quality)
 
@@ -261,6 +284,26 @@ class KeyframePipeline:
         on, dev, host = C.c_int(0), C.c_int(0), C.c_int(0)
         if homography_lib().omni_pipeline_get_device_homography(self.h, C.byref(on), C.byref(dev), C.byref(host)):
             raise capi.OmniError(f"omni_pipeline_get_device_homography: {homography_lib().omni_homography_last_error().decode()}")
+        return bool(on.value), dev.value, host.value
+
+    def set_device_pnp(self, on: bool):
+        """the EPnP RANSAC of the loop candidates' relative pose on the GPU or on the host's geometry threads (the refit stays there); between any two calls"""
+        if pnp_lib().omni_pipeline_set_device_pnp(self.h, int(bool(on))):
+            raise capi.OmniError(f"omni_pipeline_set_device_pnp: {pnp_lib().omni_pnp_last_error().decode()}")
+
+    def recv_copy_as_remote(self, src_msg_id: int, drone_id: int, new_msg_id: int):
+        """a copy of the database's key frame src_msg_id, handed to the detector as key frame new_msg_id of ANOTHER drone: the on-the-spot, init_mode path of a
+        frame received over the network (after a flush).  -> (msg_id of the database frame it was matched with or -1, whether the candidate became an edge)"""
+        old, loop = C.c_int64(-1), C.c_int(0)
+        if pnp_lib().omni_pipeline_recv_copy_as_remote(self.h, src_msg_id, drone_id, new_msg_id, C.byref(old), C.byref(loop)):
+            raise capi.OmniError(f"omni_pipeline_recv_copy_as_remote: {pnp_lib().omni_pnp_last_error().decode()}")
+        return old.value, bool(loop.value)
+
+    def device_pnp(self):
+        """(the switch, candidates whose RANSAC ran on the GPU so far, candidates that ran on the host although the switch was on)"""
+        on, dev, host = C.c_int(0), C.c_int(0), C.c_int(0)
+        if pnp_lib().omni_pipeline_get_device_pnp(self.h, C.byref(on), C.byref(dev), C.byref(host)):
+            raise capi.OmniError(f"omni_pipeline_get_device_pnp: {pnp_lib().omni_pnp_last_error().decode()}")
         return bool(on.value), dev.value, host.value
 
     @classmethod
