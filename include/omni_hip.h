@@ -182,12 +182,18 @@ int         omni_sp_set_perf(omni_sp* sp, int on);
 int         omni_sp_last_stage_ms(omni_sp* sp, float* stage_ms);
 const char* omni_sp_stage_name(int stage);
 double      omni_sp_stage_flops(const omni_sp* sp, int stage);   /* algorithmic FLOP per image for that stage */
-/* share of the stage's output tiles a fisheye-masked pass leaves out of the kernel's tile walk (the constant region of the mask, loop_cam.cpp:536-539:
- * written once per handle, bit-identical results); 0 when the stage computes every tile */
+/* share of the stage's output tiles a fisheye-masked pass leaves out of the kernel's tile walk (the image-independent band of the mask, loop_cam.cpp:536-539:
+ * computed once per handle over an all-zero image and copied into every image slot, bit-identical results); 0 when the stage computes every tile */
 double      omni_sp_stage_tiles_left_out(const omni_sp* sp, int stage);
-/* the plan itself (pure arithmetic on the image size and the kernels' tile shapes; no device needed): layer 0 = conv1a (OMNI_PREC_SPLIT only), 1..5 =
- * conv1b, conv2a, conv2b, conv3a, conv3b (both matrix-core precisions); rect = {tile row 0, tile row 1, tile column 0, tile column 1} of the layer's conv-output tile grid (empty = nothing
- * left out), frac = its share of the layer's tiles */
+/* the band itself (pure arithmetic on the image size and the kernels' tile shapes; no device needed): layer 1..5 = conv1b, conv2a, conv2b, conv3a, conv3b (both
+ * matrix-core precisions); the tile rows [*ty0, *tiles_y) of the layer's conv-output tile grid, over every tile column, hold the same bits whatever the image
+ * (every tap of their receptive fields lies in the blanked rows or in the zero padding) and are left out; *ty0 == *tiles_y = no band (a height that is no
+ * multiple of 4: the blanked rows stop short of the bottom edge; layer 0, conv1a: its rectangle below is a full-width band already); frac = its share of the tiles */
+int         omni_sp_mask_band_plan(int width, int height, int precision, int layer, int* ty0, int* tiles_y, double* frac);
+/* the rectangle inside the band where a layer's output is ONE constant vector (whole tiles one pixel per convolution away from the bottom and side edges, where
+ * the zero padding is not that vector); what a masked pass left out before the band, and what OMNI_SP_MASK_RECT=1 still leaves out.  Pure arithmetic as above:
+ * layer 0 = conv1a (OMNI_PREC_SPLIT only), 1..5 = conv1b, conv2a, conv2b, conv3a, conv3b (both matrix-core precisions); rect = {tile row 0, tile row 1, tile
+ * column 0, tile column 1} of the layer's conv-output tile grid (empty = no such tile), frac = its share of the layer's tiles */
 int         omni_sp_mask_skip_plan(int width, int height, int precision, int layer, int* rect, double* frac);
 
 /* ---- MobileNetVLAD (ASSUMED architecture -- the reference ships only the I/O contract) --------- */

@@ -32,7 +32,7 @@ SYMBOLS = [
     "omni_ctx_device_info", "omni_ctx_mfma_ceiling", "omni_dev_alloc", "omni_dev_free", "omni_host_alloc", "omni_host_free", "omni_memcpy_h2d", "omni_memcpy_d2h", "omni_timer_start",
     "omni_timer_stop", "omni_sp_create", "omni_sp_destroy", "omni_sp_desc_dim", "omni_sp_image_size", "omni_sp_infer", "omni_sp_enqueue_dev",
     "omni_sp_fetch", "omni_sp_dev_outputs", "omni_sp_get_dense", "omni_sp_postprocess_dense", "omni_sp_debug_layer",
-    "omni_sp_profile", "omni_sp_stage_name", "omni_sp_stage_flops", "omni_sp_stage_tiles_left_out", "omni_sp_mask_skip_plan", "omni_vlad_create", "omni_vlad_destroy", "omni_vlad_set_precision", "omni_vlad_pack_block", "omni_sp_pack_constants",
+    "omni_sp_profile", "omni_sp_stage_name", "omni_sp_stage_flops", "omni_sp_stage_tiles_left_out", "omni_sp_mask_skip_plan", "omni_sp_mask_band_plan", "omni_vlad_create", "omni_vlad_destroy", "omni_vlad_set_precision", "omni_vlad_pack_block", "omni_sp_pack_constants",
     "omni_vlad_infer", "omni_vlad_enqueue_dev", "omni_vlad_fetch", "omni_vlad_dev_output", "omni_vlad_mask_skip_layers", "omni_vlad_debug_taps", "omni_vlad_debug_layer", "omni_vlad_block_paths", "omni_index_create",
     "omni_index_destroy", "omni_index_add", "omni_index_add_dev", "omni_index_ntotal", "omni_index_dim", "omni_index_reset", "omni_index_truncate", "omni_index_cert_stats",
     "omni_index_search", "omni_index_search_dev", "omni_index_search_prefix_dev", "omni_index_search_batch_prefix_dev", "omni_index_set_shard", "omni_topk_merge", "omni_index_last_scan_ms",
@@ -165,6 +165,7 @@ def lib():
     sig("omni_sp_stage_flops", C.c_double, [_vp, C.c_int])
     sig("omni_sp_stage_tiles_left_out", C.c_double, [_vp, C.c_int])
     sig("omni_sp_mask_skip_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)])
+    sig("omni_sp_mask_band_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)])
     sig("omni_vlad_create", _vp, [_vp, C.POINTER(_VladWeights), C.c_int, C.c_int, C.c_int])
     sig("omni_vlad_destroy", None, [_vp])
     sig("omni_vlad_set_precision", C.c_int, [_vp, C.c_int])
@@ -881,9 +882,17 @@ def shard_unique_id() -> bytes:
     return buf.raw
 
 
+def sp_mask_band_plan(width: int, height: int, precision: int, layer: int):
+    """(first tile row, tile rows, share of the layer's tiles) of the full-width band of tile rows a fisheye-masked pass leaves out of layer `layer`
+    (1..5 = conv1b, conv2a, conv2b, conv3a, conv3b; first tile row == tile rows: no band): csrc/superpoint.hip, pure arithmetic (no device)."""
+    ty0, tiles_y, frac = C.c_int(), C.c_int(), C.c_double()
+    _check(lib().omni_sp_mask_band_plan(width, height, precision, layer, C.byref(ty0), C.byref(tiles_y), C.byref(frac)))
+    return ty0.value, tiles_y.value, frac.value
+
+
 def sp_mask_skip_plan(width: int, height: int, precision: int, layer: int):
-    """((tile row 0, tile row 1, tile column 0, tile column 1), share of the layer's tiles) a fisheye-masked pass leaves out of layer `layer`
-    (0 = conv1a [split only], 1..5 = conv1b, conv2a, conv2b, conv3a, conv3b): csrc/superpoint.hip, pure arithmetic (no device)."""
+    """((tile row 0, tile row 1, tile column 0, tile column 1), share of the layer's tiles) of the rectangle inside that band where layer `layer`'s output
+    is one constant vector (0 = conv1a [split only], 1..5 = conv1b, conv2a, conv2b, conv3a, conv3b): csrc/superpoint.hip, pure arithmetic (no device)."""
     rect = (C.c_int * 4)()
     frac = C.c_double()
     _check(lib().omni_sp_mask_skip_plan(width, height, precision, layer, rect, C.byref(frac)))

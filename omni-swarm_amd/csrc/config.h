@@ -14,7 +14,7 @@ namespace omni {
 
 enum CfgId {
     // SuperPoint
-    CFG_CONV_V1 = 0, CFG_RS_TRN, CFG_DET16, CFG_SP_SPARSE_DESC, CFG_SP_SPARSE_DA, CFG_SP_FUSED_CAND, CFG_SP_SPLIT_DB, CFG_SP_MASK_SKIP, CFG_SP_MASK_SKIP_SPLIT, CFG_SPLIT_FUSE1A, CFG_SPLIT_WINO,
+    CFG_CONV_V1 = 0, CFG_RS_TRN, CFG_DET16, CFG_SP_SPARSE_DESC, CFG_SP_SPARSE_DA, CFG_SP_FUSED_CAND, CFG_SP_SPLIT_DB, CFG_SP_MASK_SKIP, CFG_SP_MASK_SKIP_SPLIT, CFG_SP_MASK_RECT, CFG_SPLIT_FUSE1A, CFG_SPLIT_WINO,
     CFG_SPLIT_TRN, CFG_CONV_XCD, CFG_SP_PROFILE_MASK, CFG_PP_U8, CFG_PP_TRACE, CFG_PP_DBG, CFG_RS_TRACE, CFG_SPLIT_TRACE, CFG_SPLIT_DBG, CFG_WINO_TRACE, CFG_ROCTX,
     // MobileNetVLAD
     CFG_VLAD_BIG, CFG_VLAD_STEM_FUSE, CFG_VLAD_UNFUSED, CFG_VLAD_MFMA, CFG_VLAD_SBLOCK, CFG_VLAD_MBLOCK_PX, CFG_VLAD_MFMA_PX, CFG_VLAD_FC_MFMA, CFG_VLAD_MBLOCK_CPW,
@@ -33,7 +33,7 @@ enum CfgClass {
     CFG_VARIANT = 0,    // another kernel / algorithm for the same results: A/B measurements and bit-identity tests; the default is the production path
     CFG_TUNING = 1,     // a threshold between two equivalent paths
     CFG_DEBUG = 2,      // traces and timing ablations (some give WRONG results: never in production)
-    CFG_TEST = 3,       // fault injection for tests
+    CFG_TEST = 3,       // fault injection and the reference side of a bit-identity A/B, for tests and measurements
     CFG_STRING = 4      // a path (no integer value)
 };
 struct CfgOption { const char* env; int def, lo, hi; int cls; const char* doc; };

@@ -18,8 +18,10 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
     {"OMNI_SP_SPARSE_DA", 1, 0, 1, CFG_VARIANT, "convDa only at those cells too (fp16 and OMNI_PREC_SPLIT; 0: dense convDa)"},
     {"OMNI_SP_FUSED_CAND", 1, 0, 1, CFG_VARIANT, "getKeyPoints' threshold inside the detector head's epilogue + window masks from the candidate list (0: sp_cand_kernel re-reads the heat map)"},
     {"OMNI_SP_SPLIT_DB", 1, 0, 1, CFG_VARIANT, "OMNI_PREC_SPLIT: convDb + descriptor norm at the key points' cells with split (hi, lo) operands on the fp16 matrix cores (0: exact-f32 MFMA convolution)"},
-    {"OMNI_SP_MASK_SKIP", 1, 0, 1, CFG_VARIANT, "fp16: the tiles inside the constant region of the fisheye mask are left out of the tile walk (0: every tile)"},
+    {"OMNI_SP_MASK_SKIP", 1, 0, 1, CFG_VARIANT, "fp16: the tile rows inside the image-independent band of the fisheye mask are left out of the tile walk (0: every tile)"},
     {"OMNI_SP_MASK_SKIP_SPLIT", 1, 0, 1, CFG_VARIANT, "the same for OMNI_PREC_SPLIT"},
+    {"OMNI_SP_MASK_RECT", 0, 0, 1, CFG_TEST, "1: a masked pass leaves out only the rectangle of tiles where the output is one constant vector, filled by broadcasting that vector "
+                                             "(what was skipped before the band: the A/B reference, same results)"},
     {"OMNI_SPLIT_FUSE1A", 1, 0, 1, CFG_VARIANT, "OMNI_PREC_SPLIT: conv1a built inside the conv1b kernel from the u8 image (0: separate exact-f32 conv1a pass)"},
     {"OMNI_SPLIT_WINO", 7, 0, 15, CFG_VARIANT, "OMNI_PREC_SPLIT: the cin = 64 layers as Winograd F(2x2,3x3) kernels with split operands (conv_wino.hip), bit 0 = conv1b (with the conv1a "
                                                 "fusion), 1 = conv2a, 2 = conv2b, 3 = conv3a (off by default: same time as the direct kernel, profiles/r06g); 0: the direct kernels of conv_split.hip"},

@@ -58,6 +58,8 @@ int conv_fill_rect_f16(hipStream_t stream, void* map, int batch, int Ho, int Wo,
 int conv_read_pixel_bytes(hipStream_t stream, const void* map, int64_t row_bytes, int64_t org_bytes, int pix_bytes, int y, int x, void* vec);
 int conv_fill_rect_bytes(hipStream_t stream, void* map, int batch, int64_t img_bytes, int64_t row_bytes, int64_t org_bytes, int pix_bytes, int y0, int y1, int x0, int x1,
                          const void* vec);
+// bytes [first_byte, first_byte + bytes) of image slot 0 of a map of `slots` images, img_bytes apart, copied into the slots 1 .. slots - 1 (all multiples of 16)
+int conv_copy_slot0_bytes(hipStream_t stream, void* map, int slots, int64_t img_bytes, int64_t first_byte, int64_t bytes);
 
 // OMNI_PREC_SPLIT (conv_split.hip): 3x3 conv, cin 64 / 128, on the fp16 matrix cores with every operand split into hi + lo halfs (fp32-class).
 // Activations are "split-64" NHWC: per pixel and block of 64 channels [hi x 64 | lo x 64] halfs, values x conv_split_act_scale().

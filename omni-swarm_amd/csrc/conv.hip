@@ -2678,4 +2678,22 @@ int conv_fill_rect_bytes(hipStream_t st, void* map, int batch, int64_t img_bytes
     return OMNI_OK;
 }
 
+// ---- the band of the fisheye mask (superpoint.hip): one block of image slot 0 copied into every other slot, one thread per 16-byte chunk ---------
+__global__ void copy_slot0_kernel(uint4* map, int64_t img_chunks, int64_t first_chunk, int64_t len_chunks, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // (b - 1) * len_chunks + c
+    if (i >= total) return;
+    const int64_t b = i / len_chunks + 1, c = i - (b - 1) * len_chunks;
+    map[b * img_chunks + first_chunk + c] = map[first_chunk + c];
+}
+int conv_copy_slot0_bytes(hipStream_t st, void* map, int slots, int64_t img_bytes, int64_t first_byte, int64_t bytes) {
+    OMNI_REQUIRE(map && slots >= 1 && img_bytes % 16 == 0 && first_byte % 16 == 0 && bytes % 16 == 0 && first_byte >= 0 && bytes > 0 && first_byte + bytes <= img_bytes,
+                 OMNI_ERR_INVALID, "conv_copy_slot0_bytes: block outside the image slot");
+    if (slots == 1) return OMNI_OK;
+    const int64_t len = bytes / 16, total = (int64_t)(slots - 1) * len;
+    OMNI_REQUIRE(cdiv64(total, 256) < (1ll << 31), OMNI_ERR_INVALID, "conv_copy_slot0_bytes: too large for one grid");
+    hipLaunchKernelGGL(copy_slot0_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, (uint4*)map, img_bytes / 16, first_byte / 16, len, total);
+    OMNI_LAUNCH_CHECK();
+    return OMNI_OK;
+}
+
 }  // namespace omni

@@ -81,24 +81,33 @@ struct omni_sp {
     hipEvent_t ev[OMNI_SP_NUM_STAGES + 1] = {};
     hipEvent_t ev_convs = nullptr;           // recorded behind the last CU-filling kernel of a pass (the detector head): what omni_cam_order_after waits for
     bool perf = false, perf_valid = false;    // omni_sp_set_perf: every pass records its stage events (omni_sp_last_stage_ms)
-    // The constant region of the fisheye mask (fp16 path; OMNI_SP_MASK_SKIP=0 switches it off).  LoopCam blanks rows [3H/4, 3H/4 + H/4) of every image before the
-    // network sees it (loop_cam.cpp:536-539): a few pixels inside that band -- one per 3x3 convolution, doubling with every pool -- every
-    // activation is ONE vector per layer, whatever the image (its whole receptive field is zeros; the arithmetic of a pixel does not depend on
-    // where it is).  The vectors are read once from a pass over an all-zero image (sp_calibrate_mask_skip) and written once into the rectangle
-    // of CONV_TH x CONV_TW tiles that lies inside the region, in every image slot of the activation buffers; the persistent cin = 64 kernel then
-    // leaves those tiles out of its walk (ConvArgs::skip_*).  Results are bit-identical to the dense pass (tests/test_gpu_mask_skip.py).  A pass
-    // without the mask (or on another path) overwrites the rectangles: the next masked pass calibrates again (skip_state, sp_mask_skip_step).
+    // The image-independent band of the fisheye mask (fp16 and OMNI_PREC_SPLIT; OMNI_SP_MASK_SKIP=0 / OMNI_SP_MASK_SKIP_SPLIT=0 switch it off).  LoopCam blanks rows
+    // [3H/4, 3H/4 + H/4) of every image before the network sees it (loop_cam.cpp:536-539).  Where those rows reach the bottom edge (H % 4 == 0), every
+    // output pixel of a layer from row `a` down -- one row further per 3x3 convolution, halved by every pool -- has all its taps in blanked rows or in
+    // the zero padding, over the WHOLE width: it holds the same bits whatever the image.  (Away from the edges it is one vector per layer; near the
+    // side edges it varies with the column and near the bottom edge with the row, because padding is not that vector.)  The tile rows that lie in
+    // that region -- the BAND, [band_ty0, tiles_y) x [0, tiles_x) -- are computed once by a pass over an all-zero image into image slot 0
+    // (sp_calibrate_mask_skip) and copied into every other slot of the activation buffers; the persistent kernels then leave them out of their walk
+    // (ConvArgs::skip_*).  Results are bit-identical to the dense pass (tests/test_gpu_mask_skip.py, tests/test_gpu_mask_band.py).  A pass without
+    // the mask (or on another path) overwrites the band: the next masked pass calibrates again (skip_state, sp_mask_skip_step).
+    // The RECTANGLE (ty0 .. tx1) is the part of the band where the output is that one vector: whole tiles one pixel per convolution away from
+    // the bottom and side edges.  It is what omni_sp_mask_skip_plan reports, what conv1a's own band (OMNI_PREC_SPLIT, unfused) is filled by, what a
+    // height with H % 4 != 0 (blanked rows that stop short of the bottom edge) still skips, and, under OMNI_SP_MASK_RECT=1, all that is skipped
+    // (filled by broadcasting the vector: the A/B reference for the band).
     struct MaskSkip {
         int ty0 = 0, ty1 = 0, tx0 = 0, tx1 = 0;      // tile rectangle in the layer's conv-output tile grid (before the pool)
         int oy0 = 0, oy1 = 0, ox0 = 0, ox1 = 0;      // the same rectangle in the layer's output map (after the pool)
+        int band_ty0 = 0, tiles_y = 0, tiles_x = 0;  // the band: tile rows [band_ty0, tiles_y) of the same grid, every tile column (none: band_ty0 == tiles_y)
+        int band_oy0 = 0;                            // ... = rows [band_oy0, oh) of the output map
         int oh = 0, ow = 0, oc = 0;                  // output map: rows, cols, channels
         int pix_bytes = 0;                           // its layout: bytes per pixel, per row, per image, offset of pixel (0, 0) (fp16: NHWC; split: framed split-64)
         int64_t row_bytes = 0, img_bytes = 0, org_bytes = 0;
-        void* vec = nullptr;                         // [pix_bytes]: the constant
+        void* vec = nullptr;                         // [pix_bytes]: the rectangle's constant (only where the rectangle is what gets filled)
         void** map = nullptr;                        // the activation buffer
-        double frac = 0.0;                           // the rectangle's share of the layer's tiles (omni_sp_stage_tiles_left_out)
+        double frac = 0.0, band_frac = 0.0;          // the rectangle's / the band's share of the layer's tiles
     };
-    MaskSkip mskip[6];                       // conv1a (OMNI_PREC_SPLIT, unfused, only), conv1b (+pool), conv2a, conv2b (+pool), conv3a, conv3b (+pool; OMNI_PREC_SPLIT only)
+    MaskSkip mskip[6];                       // conv1a (OMNI_PREC_SPLIT, unfused, only: rectangle), conv1b (+pool), conv2a, conv2b (+pool), conv3a, conv3b (+pool)
+    bool mask_band = false;                  // layers 1..5 leave out their band (false: their rectangle -- OMNI_SP_MASK_RECT=1, or H % 4 != 0)
     uint8_t* zero_gray = nullptr;            // the calibration's all-zero image (grows with the largest stride seen)
     size_t zero_gray_bytes = 0;
     std::mutex mu;
@@ -115,8 +124,9 @@ static int dev_upload(omni_sp* s, T** dst, const void* src, size_t bytes) {
     return OMNI_OK;
 }
 
-// Where every layer's output is constant under the fisheye mask, and the tile rectangle inside it (see omni_sp::MaskSkip): pure integer arithmetic
-// on (H, W) and the kernels' tile shapes; k[0] = conv1a (OMNI_PREC_SPLIT only), k[1..4] = conv1b, conv2a, conv2b, conv3a
+// Where every layer's output does not depend on the image under the fisheye mask: the band of whole tile rows, and the tile rectangle inside it where
+// the output is one vector (see omni_sp::MaskSkip): pure integer arithmetic on (H, W) and the kernels' tile shapes; k[0] = conv1a (OMNI_PREC_SPLIT
+// only), k[1..5] = conv1b, conv2a, conv2b, conv3a, conv3b
 static void sp_mask_skip_rects(int H, int W, bool split, omni_sp::MaskSkip (&ks)[6]) {
     int m0, m1;
     omni_fisheye_mask_rows(H, 1, &m0, &m1);
@@ -137,16 +147,25 @@ static void sp_mask_skip_rects(int H, int W, bool split, omni_sp::MaskSkip (&ks)
     const int chans[5] = {64, 64, 64, 128, 128};
     static_assert(CONV_TW == 32, "tile width");
     const int TW = 32;
+    const bool to_bottom = m1 == H;                        // the blanked rows reach the bottom edge: from row `a` down nothing depends on the image (H % 4 != 0: they stop short of it)
+    bool rect = true;                                      // something is still constant
     for (int i = 0; i < 5; ++i) {                          // conv1b, conv2a, conv2b, conv3a, conv3b (cin = 128: the split kernel's 2 x 32 tiles, the fp16 register-stationary kernel's 6 x 32)
         const int TH = split ? (i == 4 ? 2 : 4) : (i == 4 ? conv_rs_pool_tile_rows() : CONV_TH);  // the kernels' output tiles (conv_split.hip: 4 x 32 / 2 x 32, conv.hip: CONV_TH x CONV_TW / RS_TH x RS_TW)
         a += 1; b -= 1; c += 1; d -= 1;                    // a 3x3 convolution (zero padding is NOT the constant): one pixel in from every side
         omni_sp::MaskSkip& k = ks[1 + i];
-        if (b < a || d < c) break;                         // nothing constant from here on
-        k.ty0 = (a + TH - 1) / TH; k.ty1 = (b + 1) / TH; k.tx0 = (c + TW - 1) / TW; k.tx1 = (d + 1) / TW;
-        if (k.ty1 <= k.ty0 || k.tx1 <= k.tx0) k.ty0 = k.ty1 = k.tx0 = k.tx1 = 0;
-        k.frac = (double)(k.ty1 - k.ty0) * (k.tx1 - k.tx0) / ((double)((h + TH - 1) / TH) * ((w + TW - 1) / TW));
         const int f = pool[i] ? 2 : 1;
-        k.oy0 = k.ty0 * TH / f; k.oy1 = k.ty1 * TH / f; k.ox0 = k.tx0 * TW / f; k.ox1 = k.tx1 * TW / f;
+        // the band: rows [a, h) over the whole width (padding is as independent of the image as the blanked rows are), in whole tile rows
+        k.tiles_y = (h + TH - 1) / TH; k.tiles_x = (w + TW - 1) / TW;
+        k.band_ty0 = to_bottom ? std::min((a + TH - 1) / TH, k.tiles_y) : k.tiles_y;
+        k.band_oy0 = k.band_ty0 * TH / f;
+        k.band_frac = (double)(k.tiles_y - k.band_ty0) / k.tiles_y;
+        rect = rect && b >= a && d >= c;                   // (false: nothing constant from here on)
+        if (rect) {
+            k.ty0 = (a + TH - 1) / TH; k.ty1 = (b + 1) / TH; k.tx0 = (c + TW - 1) / TW; k.tx1 = (d + 1) / TW;
+            if (k.ty1 <= k.ty0 || k.tx1 <= k.tx0) k.ty0 = k.ty1 = k.tx0 = k.tx1 = 0;
+            k.frac = (double)(k.ty1 - k.ty0) * (k.tx1 - k.tx0) / ((double)k.tiles_y * k.tiles_x);
+            k.oy0 = k.ty0 * TH / f; k.oy1 = k.ty1 * TH / f; k.ox0 = k.tx0 * TW / f; k.ox1 = k.tx1 * TW / f;
+        }
         if (pool[i]) { a = (a + 1) / 2; b = (b - 1) >> 1; c = (c + 1) / 2; d = (d - 1) >> 1; h /= 2; w /= 2; }      // pooled pixel r = conv pixels 2r, 2r + 1
         k.oh = h; k.ow = w; k.oc = chans[i];
     }
@@ -158,6 +177,9 @@ static int sp_plan_mask_skip(omni_sp* s) {
     if (s->facts.conv_variant != 0 || s->precision == OMNI_PREC_F32) return OMNI_OK;
     if (!s->cfg[split ? CFG_SP_MASK_SKIP_SPLIT : CFG_SP_MASK_SKIP]) return OMNI_OK;       // = 0: the dense pass (A/B, tests)
     sp_mask_skip_rects(s->H, s->W, split, s->mskip);
+    // the band wherever the plan has one (a height whose blanked rows stop short of the bottom edge has none: its rectangles); OMNI_SP_MASK_RECT=1: the rectangles
+    s->mask_band = false;
+    for (int i = 1; i < 6 && !s->cfg[CFG_SP_MASK_RECT]; ++i) s->mask_band = s->mask_band || s->mskip[i].band_ty0 < s->mskip[i].tiles_y;
     void** maps[6] = {&s->a1a, &s->a1b, &s->a2a, &s->a2b, &s->a3a, &s->a3b};
     for (int i = 0; i < 6; ++i) {
         omni_sp::MaskSkip& k = s->mskip[i];
@@ -171,7 +193,9 @@ static int sp_plan_mask_skip(omni_sp* s) {
         } else {
             k.pix_bytes = k.oc * 2; k.row_bytes = (int64_t)k.ow * k.pix_bytes; k.img_bytes = k.row_bytes * k.oh; k.org_bytes = 0;
         }
-        if (k.ty1 > k.ty0) {
+        if (s->mask_band && i > 0) {
+            if (k.band_ty0 < k.tiles_y) s->facts.mask_skip = true;                   // (filled by a copy: no vector)
+        } else if (k.ty1 > k.ty0) {
             if (int rc = s->mem.alloc(&k.vec, (size_t)k.pix_bytes * 4)) return rc;   // (x 4: conv2a as a Winograd layer keeps one vector per position in the 2 x 2 tile)
             s->facts.mask_skip = true;
         }
@@ -365,7 +389,11 @@ static ConvArgs sp_layer_args(const omni_sp* s, const SpPassPlan& p, int l, SpKe
     a.bias = l == LPA ? s->bias_heads : (split && !a.out_f32) ? s->bias_s[l] : s->bias[l];       // the scaled bias goes with scaled (split-64 / raw-32) outputs
     a.n_cu = s->ctx->prop.multiProcessorCount; a.zero_page = s->ctx->zero_page; a.variant = s->facts.conv_variant;
     const int i = l == L1B ? 1 : l == L2A ? 2 : l == L2B ? 3 : l == L3A ? 4 : l == L3B ? 5 : -1;
-    if (p.use_skip && i >= 0) { a.skip_ty0 = s->mskip[i].ty0; a.skip_ty1 = s->mskip[i].ty1; a.skip_tx0 = s->mskip[i].tx0; a.skip_tx1 = s->mskip[i].tx1; }
+    if (p.use_skip && i >= 0) {
+        const omni_sp::MaskSkip& k = s->mskip[i];
+        if (s->mask_band) { a.skip_ty0 = k.band_ty0; a.skip_ty1 = k.tiles_y; a.skip_tx0 = 0; a.skip_tx1 = k.tiles_x; }      // (full width down to the last tile row: tile_walk.h, bw = 0)
+        else { a.skip_ty0 = k.ty0; a.skip_ty1 = k.ty1; a.skip_tx0 = k.tx0; a.skip_tx1 = k.tx1; }
+    }
     return a;
 }
 // layer l on the precision's direct kernels (convDb: the tails' precision)
@@ -401,10 +429,11 @@ static SpSparseDesc sp_sparse_desc(const omni_sp* s, const SpPassPlan& p) {
 }
 
 static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch, int fisheye_mask, bool with_events, bool run_post, bool calibrating = false);
-// One dense pass over an all-zero image with the mask on; every planned layer's constant is read from the middle of its rectangle and written
-// into that rectangle of every image slot of the layer's activation buffer.  The pass starts zero_image_offset bytes into the zero image
-// (sp_mask_skip_step: so that it takes the conv1a form of the pass it serves, conv1a's own rectangle (OMNI_PREC_SPLIT) is filled when that pass
-// skips it, and the constants come from the same kernels).
+// One dense pass of one image, all zeros, with the mask on; then every planned layer's band -- the rows [band_oy0, oh) of its output map, one
+// contiguous block in both layouts -- is copied from image slot 0 into every other slot of the layer's activation buffer.  Where the rectangle
+// is what gets skipped (conv1a; every layer of a handle without bands) the layer's constant is read from the middle of its rectangle and written
+// into that rectangle of every slot.  The pass starts zero_image_offset bytes into the zero image (sp_mask_skip_step: so that it takes the conv1a
+// form of the pass it serves, conv1a's own rectangle (OMNI_PREC_SPLIT) is filled when that pass skips it, and the bands come from the same kernels).
 static int sp_calibrate_mask_skip(omni_sp* s, int stride, int zero_image_offset) {
     hipStream_t st = s->ctx->stream;
     int rc;
@@ -418,6 +447,14 @@ static int sp_calibrate_mask_skip(omni_sp* s, int stride, int zero_image_offset)
     if ((rc = sp_forward(s, s->zero_gray + zero_image_offset, stride, 1, 1, false, false, true))) return rc;
     const SpPassPlan& cal = s->last;       // the calibration pass's own plan
     for (const omni_sp::MaskSkip& k : s->mskip) {
+        if (s->mask_band && k.map != &s->a1a) {
+            if (k.band_ty0 >= k.tiles_y || k.band_oy0 >= k.oh) continue;
+            // rows [band_oy0, oh) from the first pixel of the first to the last pixel of the last: nothing outside the map's own rows (split: the frame columns
+            // between two rows are zeros in every slot)
+            const int64_t first = k.org_bytes + k.band_oy0 * k.row_bytes, bytes = (k.oh - 1 - k.band_oy0) * k.row_bytes + (int64_t)k.ow * k.pix_bytes;
+            if ((rc = conv_copy_slot0_bytes(st, *k.map, s->max_batch, k.img_bytes, first, bytes))) return rc;
+            continue;
+        }
         if (k.ty1 <= k.ty0 || (k.map == &s->a1a && cal.conv1a == SP_1A_FUSED)) continue;
         if ((k.map == &s->a2a && cal.conv2a.wino) || (k.map == &s->a3a && cal.conv3a.wino)) {     // an unpooled Winograd layer: constant per position in the 2 x 2 output tile
             if ((rc = conv_read_pixels2x2_bytes(st, *k.map, k.row_bytes, k.org_bytes, k.pix_bytes, ((k.oy0 + k.oy1) / 2) & ~1, ((k.ox0 + k.ox1) / 2) & ~1, k.vec))) return rc;
@@ -771,10 +808,20 @@ int omni_sp_mask_skip_plan(int width, int height, int precision, int layer, int*
     return OMNI_OK;
 }
 
+int omni_sp_mask_band_plan(int width, int height, int precision, int layer, int* ty0, int* tiles_y, double* frac) {
+    OMNI_REQUIRE(width > 0 && height > 0 && layer >= 0 && layer < 6, OMNI_ERR_INVALID, "bad argument");
+    omni_sp::MaskSkip ks[6];
+    if (precision != OMNI_PREC_F32) omni::sp_mask_skip_rects(height, width, precision == OMNI_PREC_SPLIT, ks);
+    if (ty0) *ty0 = ks[layer].band_ty0;
+    if (tiles_y) *tiles_y = ks[layer].tiles_y;
+    if (frac) *frac = ks[layer].band_ty0 < ks[layer].tiles_y ? ks[layer].band_frac : 0.0;
+    return OMNI_OK;
+}
+
 double omni_sp_stage_tiles_left_out(const omni_sp* s, int stage) {
     if (!s || !s->facts.mask_skip) return 0.0;
     const int i = stage == ST_CONV1A ? 0 : stage == ST_CONV1B ? 1 : stage == ST_CONV2A ? 2 : stage == ST_CONV2B ? 3 : stage == ST_CONV3A ? 4 : stage == ST_CONV3B ? 5 : -1;
-    return i < 0 ? 0.0 : s->mskip[i].frac;
+    return i < 0 ? 0.0 : (s->mask_band && i > 0) ? s->mskip[i].band_frac : s->mskip[i].frac;
 }
 
 // enable_perf of the reference's runners (superpoint_tensorrt.cpp:130-162 prints the engine time and the post-processing time of every call): with perf on, every
