@@ -170,8 +170,14 @@ int omni_sp_get_dense(omni_sp* sp, int batch, float* semi_host, float* desc_host
 int omni_sp_postprocess_dense(omni_sp* sp, const float* semi_host, const float* desc_host, int batch,
                               float* kps_xy, int* n_kps, float* desc, float* scores);
 /* test hook: one intermediate activation of the last forward pass as NCHW float32 (name in {"conv1a","conv1b",...,
- * "conv4b","heads","desc"}; post-ReLU, post-pool where the layer pools).  out may be NULL to query the shape only. */
+ * "conv4b","heads","desc"}; post-ReLU, post-pool where the layer pools).  out may be NULL to query the shape only.
+ * "desc_rows_in" / "desc_rows_out" (fp32-class paths behind a pass that sampled its descriptors sparsely): the compact cDa rows around the key points and
+ * their convDb + norm, as they lie: [batch][4 max_num][256] (C = 4 max_num, H = 256, W = 1); rows of key points that do not exist are not meaningful. */
 int omni_sp_debug_layer(omni_sp* sp, const char* name, int batch, float* out_nchw_host, int* C, int* H, int* W);
+/* test hook: the kernel forms of the last forward pass (csrc/sp_plan.h), as bits: 1, 2, 4, 8 = conv1b, conv2a, conv2b, conv3a ran the Winograd kernel; 16 = conv1a
+ * was fused into conv1b; 32 = the split detector head (detector_head_mfma16 over fp32 input); 64 = the sparse descriptor tail ran convdb_l2norm_split; 128 = the
+ * descriptors were sampled from compact fp32 rows ("desc_rows_in" / "desc_rows_out").  -1 for a null handle. */
+int omni_sp_last_plan(const omni_sp* sp);
 /* per-stage device time: runs the network `reps` times on HBM-resident input with HIP events between stages.
  * stage_ms [OMNI_SP_NUM_STAGES] MEDIAN ms per call over the repetitions; names via omni_sp_stage_name(). */
 #define OMNI_SP_NUM_STAGES 16
@@ -231,7 +237,10 @@ int64_t    omni_vlad_pack_block(int cin, int hid, int cout, int stride, const fl
 /* Host-only test hooks (no GPU): the packed constants of two SuperPoint kernels, so that their algebra can be checked on the CPU.
  * which = 0: conv1a's matrix-core fragments for operands taken straight from the image bytes (csrc/conv.hip conv1a_pack_u8_weights): w [64][9],
  *   bias [64] -> out [2048] halfs, *scale = 1; which = 1: a cin = 64 layer's Winograd F(2x2,3x3) fragments (csrc/conv_wino.hip conv_pack_weights_wino):
- *   w OIHW [cout][64][3][3] -> out [64 * cout * 32] halfs, *scale = 2^-k of the packed values.  Returns the number of halfs written, -2 on bad arguments. */
+ *   w OIHW [cout][64][3][3] -> out [64 * cout * 32] halfs, *scale = 2^-k of the packed values; which = 2: a direct split layer's fragments
+ *   (csrc/conv_split.hip conv_pack_weights_split): w OIHW [cout][cin][3][3], cin = 64 or 128 taken from out_halfs = cin * cout * 18, *scale = 2^-k;
+ *   which = 3: convDb's split fragments (csrc/conv.hip convdb_pack_weights_split): w [256][256] -> out [65536 hi | 65536 lo], *scale = 1.
+ *   Returns the number of halfs written, -2 on bad arguments. */
 int64_t omni_sp_pack_constants(int which, const float* w, const float* bias, int cout, uint16_t* out, int64_t out_halfs, float* scale);
 /* std::vector<float> MobileNetVLADTensorRT::inference(const cv::Mat&) (mobilenetvlad_tensorrt.cpp:4-14):
  * u8 -> f32 with NO scaling feeds the net; out [batch][out_dim] */

@@ -31,7 +31,7 @@ SYMBOLS = [
     "omni_abi_version", "omni_last_error", "omni_ctx_create", "omni_ctx_create_priority", "omni_ctx_order_after", "omni_memcpy_d2h_async", "omni_ctx_destroy", "omni_ctx_sync", "omni_ctx_stream",
     "omni_ctx_device_info", "omni_ctx_mfma_ceiling", "omni_dev_alloc", "omni_dev_free", "omni_host_alloc", "omni_host_free", "omni_memcpy_h2d", "omni_memcpy_d2h", "omni_timer_start",
     "omni_timer_stop", "omni_sp_create", "omni_sp_destroy", "omni_sp_desc_dim", "omni_sp_image_size", "omni_sp_infer", "omni_sp_enqueue_dev",
-    "omni_sp_fetch", "omni_sp_dev_outputs", "omni_sp_get_dense", "omni_sp_postprocess_dense", "omni_sp_debug_layer",
+    "omni_sp_fetch", "omni_sp_dev_outputs", "omni_sp_get_dense", "omni_sp_postprocess_dense", "omni_sp_debug_layer", "omni_sp_last_plan",
     "omni_sp_profile", "omni_sp_stage_name", "omni_sp_stage_flops", "omni_sp_stage_tiles_left_out", "omni_sp_mask_skip_plan", "omni_sp_mask_band_plan", "omni_vlad_create", "omni_vlad_destroy", "omni_vlad_set_precision", "omni_vlad_pack_block", "omni_sp_pack_constants",
     "omni_vlad_infer", "omni_vlad_enqueue_dev", "omni_vlad_fetch", "omni_vlad_dev_output", "omni_vlad_mask_skip_layers", "omni_vlad_debug_taps", "omni_vlad_debug_layer", "omni_vlad_block_paths", "omni_index_create",
     "omni_index_destroy", "omni_index_add", "omni_index_add_dev", "omni_index_ntotal", "omni_index_dim", "omni_index_reset", "omni_index_truncate", "omni_index_cert_stats",
@@ -160,6 +160,7 @@ def lib():
     sig("omni_sp_get_dense", C.c_int, [_vp, C.c_int, _fp, _fp])
     sig("omni_sp_postprocess_dense", C.c_int, [_vp, _fp, _fp, C.c_int, _fp, _ip, _fp, _fp])
     sig("omni_sp_debug_layer", C.c_int, [_vp, C.c_char_p, C.c_int, _fp, _ip, _ip, _ip])
+    sig("omni_sp_last_plan", C.c_int, [_vp])
     sig("omni_sp_profile", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _fp])
     sig("omni_sp_stage_name", C.c_char_p, [C.c_int])
     sig("omni_sp_stage_flops", C.c_double, [_vp, C.c_int])
@@ -464,6 +465,10 @@ class SuperPoint:
         _check(lib().omni_sp_debug_layer(self.h, name.encode(), batch, _pf(out), C.byref(c), C.byref(h), C.byref(w)))
         return out
 
+    def last_plan(self) -> int:
+        """The kernel forms of the last pass as bits (include/omni_hip.h omni_sp_last_plan)."""
+        return lib().omni_sp_last_plan(self.h)
+
     def profile(self, gray_dev: int, stride: int, batch: int, reps: int = 5):
         ms = np.zeros(SP_NUM_STAGES, np.float32)
         _check(lib().omni_sp_profile(self.h, gray_dev, stride, batch, reps, _pf(ms)))
@@ -559,10 +564,12 @@ class MobileNetVLAD:
 
 
 def sp_pack_constants(which, w, bias=None, cout=64):
-    """Host-only test hook: (halfs as uint16, scale) of conv1a's byte-operand fragments (which = 0) or a cin = 64 layer's Winograd fragments (which = 1)."""
+    """Host-only test hook: (halfs as uint16, scale) of conv1a's byte-operand fragments (which = 0), a cin = 64 layer's Winograd fragments (which = 1),
+    a direct split layer's fragments (which = 2: w [cout][cin][3][3], cin = 64 or 128) or convDb's split fragments (which = 3: hi, then lo)."""
     w = _f32(w)
     b = _f32(bias) if bias is not None else None
-    out = np.zeros(2048 if which == 0 else 64 * cout * 32, np.uint16)
+    n_out = {0: 2048, 1: 64 * cout * 32, 2: w.size * 2, 3: 2 * 65536}[which]
+    out = np.zeros(n_out, np.uint16)
     sc = C.c_float(0)
     n = lib().omni_sp_pack_constants(which, _pf(w), _pf(b) if b is not None else None, cout, out.ctypes.data_as(_vp), out.size, C.byref(sc))
     if n != out.size:

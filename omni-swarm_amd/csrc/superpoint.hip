@@ -739,6 +739,20 @@ int omni_sp_debug_layer(omni_sp* s, const char* name, int batch, float* out_nchw
     OMNI_REQUIRE(s && name, OMNI_ERR_INVALID, "null argument");
     OMNI_REQUIRE(batch >= 1 && batch <= s->max_batch, OMNI_ERR_CAPACITY, "batch=%d outside [1,%d]", batch, s->max_batch);
     struct Ent { const char* n; const void* p; int c, div, prec; };
+    const bool rows_in = strcmp(name, "desc_rows_in") == 0;
+    if (rows_in || strcmp(name, "desc_rows_out") == 0) {       // the sparse descriptor tail's compact rows as they lie: [batch][4 max_num][256] fp32
+        OMNI_REQUIRE(s->cx32 && (s->last.desc == omni::SP_DESC_SPARSE_DA_SPLIT || s->last.desc == omni::SP_DESC_GATHER_F32) && batch <= s->last_batch,
+                     OMNI_ERR_INVALID, "layer %s: the last pass of >= %d images left no compact descriptor rows", name, batch);
+        if (C) *C = 4 * s->max_num;
+        if (Hl) *Hl = 256;
+        if (Wl) *Wl = 1;
+        if (!out_nchw_host) return OMNI_OK;
+        std::lock_guard<std::mutex> lk(s->mu);
+        (void)hipSetDevice(s->ctx->device);
+        OMNI_HIP_TRY(hipMemcpyAsync(out_nchw_host, rows_in ? s->cx32 : s->cy32, (size_t)batch * s->max_num * 4 * 256 * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+        OMNI_HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+        return OMNI_OK;
+    }
     const int P = s->precision;
     const Ent tab[] = {{"conv1a", s->a1a, 64, 1, P},   {"conv1b", s->a1b, 64, 2, P},   {"conv2a", s->a2a, 64, 2, P},
                        {"conv2b", s->a2b, 64, 4, P},   {"conv3a", s->a3a, 128, 4, P},  {"conv3b", s->a3b, 128, 8, P},
@@ -774,6 +788,14 @@ int omni_sp_debug_layer(omni_sp* s, const char* name, int batch, float* out_nchw
     }
     omni::set_error("unknown layer '%s'", name);
     return OMNI_ERR_INVALID;
+}
+
+int omni_sp_last_plan(const omni_sp* s) {
+    if (!s) return -1;
+    const omni::SpPassPlan& p = s->last;
+    return (p.conv1b == omni::SP_1B_FUSED_WINO ? 1 : 0) | (p.conv2a.wino ? 2 : 0) | (p.conv2b.wino ? 4 : 0) | (p.conv3a.wino ? 8 : 0) | (p.conv1a == omni::SP_1A_FUSED ? 16 : 0)
+         | (p.det == omni::SP_DET_MFMA16_F32 ? 32 : 0) | (p.desc_split_db ? 64 : 0)
+         | (p.desc == omni::SP_DESC_SPARSE_DA_SPLIT || p.desc == omni::SP_DESC_GATHER_F32 ? 128 : 0);
 }
 
 // (internal, cam.hip) the event a pass records behind its convolution stack
@@ -839,6 +861,19 @@ int64_t omni_sp_pack_constants(int which, const float* w, const float* bias, int
         if (cout < 64 || cout % 64 || out_halfs < need) { omni::set_error("omni_sp_pack_constants: cout %d, %lld halfs", cout, (long long)out_halfs); return -2; }
         *scale = omni::conv_pack_weights_wino(w, 64, cout, out);
         return need;
+    }
+    if (which == 2) {                                      // a direct split layer; cin (64 or 128) from the room offered: cin * cout * 9 * 2 halfs
+        const int64_t per_cin = (int64_t)cout * 18;
+        const int cin = cout >= 64 && cout % 64 == 0 && out_halfs % per_cin == 0 ? (int)(out_halfs / per_cin) : 0;
+        if (cin != 64 && cin != 128) { omni::set_error("omni_sp_pack_constants: cout %d, %lld halfs", cout, (long long)out_halfs); return -2; }
+        *scale = omni::conv_pack_weights_split(w, cin, cout, out);
+        return out_halfs;
+    }
+    if (which == 3) {                                      // convDb [256][256]: the hi fragments, then the lo fragments
+        if (out_halfs < 2 * 65536) { omni::set_error("omni_sp_pack_constants: convDb needs 131072 halfs"); return -2; }
+        omni::convdb_pack_weights_split(w, out, out + 65536);
+        *scale = 1.f;
+        return 2 * 65536;
     }
     omni::set_error("omni_sp_pack_constants: which = %d", which);
     return -2;

@@ -231,7 +231,7 @@ def conv1a_interval(a: np.ndarray, delta: np.ndarray):
 # the two fp32 tails: detector head (semi) and dense descriptors
 # ------------------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def semi_ref(cpa16: np.ndarray, wPb: np.ndarray, bPb: np.ndarray):
+def semi_ref(cpa16: np.ndarray, wPb: np.ndarray, bPb: np.ndarray, x_f32: bool = False, exact_f32: bool = False):
     """Heat map: (ref, bound), each [N, 8 Hc, 8 Wc] float64.  ref = the fp64 softmax over 65 of convPb(cPa16) + b without the dustbin,
     arranged depth-to-space, with the fp32 weights as given.
 
@@ -242,7 +242,14 @@ def semi_ref(cpa16: np.ndarray, wPb: np.ndarray, bPb: np.ndarray):
     Softmax: logits off by d_j (|d_j| <= E_j) move p_c by the factor exp(d_c) / sum_j p_j exp(d_j), so |dp_c| <= p_c (exp(E_c + Emax) - 1).
     The fp32 evaluation (l - mx, expf, a sum of 65 positive terms, one division) adds a relative error of at most
         u |z_c - m| + 4 u  (the subtraction and expf, taken as 2 ulp)  +  u max_j |z_j - m| + 4 u + gamma_65  (the sum)  +  u  (the division),
-    where |z - m| grows by 2 Emax in the computed logits.  Near the ends of fp32's range an absolute 1e-37 covers underflow."""
+    where |z - m| grows by 2 Emax in the computed logits.  Near the ends of fp32's range an absolute 1e-37 covers underflow.
+
+    x_f32 (detector_head_mfma16_kernel<float>, OMNI_PREC_SPLIT: the input is the heads layer's fp32 output): the kernel splits the activation as well,
+    xh = half(x), xl = half(x - xh), and adds wl xh + wh xh + wh xl, 3 x 256 exact products and the bias, K = 769.  Against z = sum_k w_k x_k + b this
+    leaves out exactly (w - wh - wl) x + wh (x - xh - xl) + wl (x - xh), each bounded by its magnitude:
+        E_c = sum_k |x_k| |w - wh - wl| + |wh| |x_k - xh_k - xl_k| + |wl| |x_k - xh_k|  +  gamma_769 (sum_k |xh_k| (|wh| + |wl|) + |xl_k| |wh| + |b_c|).
+    exact_f32 (detector_head_mfma: v_mfma_f32_32x32x2_f32 over the fp32 weights; OMNI_PREC_F32 and OMNI_DET16=0): every product rounded into the fp32
+    accumulator, then the bias: E_c = gamma_258 (sum_k |x_k w_ck| + |b_c|) for all 65 channels."""
     x = _t(cpa16)
     w = np.asarray(wPb, np.float32).reshape(65, 256)
     wh = f16(w)
@@ -258,6 +265,18 @@ def semi_ref(cpa16: np.ndarray, wPb: np.ndarray, bPb: np.ndarray):
     g = np.full(65, gamma(513))
     g[64] = gamma(258)
     Ez = conv1(ax, rep) + _t(g)[None, :, None, None] * (conv1(ax, mag) + _t(np.abs(bPb))[None, :, None, None])
+    if exact_f32:
+        Ez = gamma(258) * (conv1(ax, np.abs(w.astype(np.float64))) + _t(np.abs(bPb))[None, :, None, None])
+    elif x_f32:
+        x32 = np.asarray(cpa16, np.float32)
+        xh = x32.astype(np.float16).astype(np.float32)
+        xl = (x32 - xh).astype(np.float16).astype(np.float32)
+        axh, axl = _t(np.abs(xh)), _t(np.abs(xl))
+        r1, r2 = _t(np.abs(x32.astype(np.float64) - xh - xl)), _t(np.abs(x32.astype(np.float64) - xh))
+        awh, awl = np.abs(wh64), np.abs(wl64)                 # (row 64, the dustbin, is overwritten below)
+        Ez = (conv1(ax, rep) + conv1(r1, awh) + conv1(r2, awl)
+              + gamma(769) * (conv1(axh, mag) + conv1(axl, awh) + _t(np.abs(bPb))[None, :, None, None]))
+        Ez[:, 64] = gamma(258) * (conv1(ax, mag)[:, 64] + abs(float(np.asarray(bPb)[64])))
     p = torch.softmax(z, 1)
     Emax = Ez.max(1, keepdim=True).values
     prop = p * torch.expm1(Ez + Emax)
@@ -273,7 +292,7 @@ def semi_ref(cpa16: np.ndarray, wPb: np.ndarray, bPb: np.ndarray):
 
 
 @torch.no_grad()
-def desc_ref(cda16: np.ndarray, wDb: np.ndarray, bDb: np.ndarray):
+def desc_ref(cda16: np.ndarray, wDb: np.ndarray, bDb: np.ndarray, round_w: bool = True, split: bool = False):
     """Dense descriptors: (ref, bound), each [N, 256, Hc, Wc] float64.  ref = the fp64 normalize(convDb(cDa16; fp16(wDb)) + b).
 
     convdb_l2norm_kernel (weights from convdb_pack_weights, rounded to nearest fp16): v_c = 256 exact products summed in fp32 MFMA
@@ -281,13 +300,33 @@ def desc_ref(cda16: np.ndarray, wDb: np.ndarray, bDb: np.ndarray):
         |v_c / ||v|| - d_c / ||d||| <= (E_c + |ref_c| ||E||) / (||d|| - ||E||)
     (v_c/||v|| - d_c/||d|| = e_c / ||v|| + d_c (||d|| - ||v||) / (||v|| ||d||)).  The norm is evaluated in fp32: 256 non-negative squares
     (fmaf) summed: relative gamma_256, halved by the square root; sqrtf and the division round once each (correctly rounded: the build
-    keeps HIP's default correctly rounded fp32 division and square root).  A cell whose ||d|| <= ||E|| has no bound (inf)."""
+    keeps HIP's default correctly rounded fp32 division and square root).  A cell whose ||d|| <= ||E|| has no bound (inf).
+
+    round_w=False (the fp32-class paths' dense map: the exact-f32 1x1 convolution over the fp32 cDa with the weights as given, then l2norm_kernel):
+    256 products rounded into the fp32 accumulator and the bias, the same gamma_257; the norm's 256 squares are summed in a tree: within gamma_256.
+
+    split=True (convdb_l2norm_split_kernel, the sparse tail of OMNI_PREC_SPLIT over the compact fp32 cDa rows, given as [rows, 256, 1, 1]): xh = half(x),
+    xl = half(x - xh), wh = half(w), wl = half(w - wh) (convdb_pack_weights_split); the kernel adds wl xh + wh xh + wh xl, 3 x 256 exact products in fp32 MFMA
+    accumulators, then the bias: d is the exact value of THAT sum (the dropped wl xl, the residues w - wh - wl and x - xh - xl are in the reference) and
+    E_c = gamma_769 (sum_k |xh_k| (|wh_ck| + |wl_ck|) + |xl_k| |wh_ck| + |b_c|); the norm as above (fmaf chains of 16, then a tree: within gamma_256)."""
     x = _t(cda16)
-    w16 = f16(np.asarray(wDb, np.float32).reshape(256, 256)).astype(np.float64)
+    w16 = np.asarray(wDb, np.float32).reshape(256, 256).astype(np.float64)
+    if round_w:
+        w16 = f16(w16).astype(np.float64)
     conv1 = lambda inp, ww: torch.einsum("nkhw,ck->nchw", inp, _t(ww))
     bt = _t(bDb)[None, :, None, None]
-    d = conv1(x, w16) + bt
-    E = gamma(257) * (conv1(x.abs(), np.abs(w16)) + bt.abs())
+    if split:
+        x32, w32 = np.asarray(cda16, np.float32), np.asarray(wDb, np.float32).reshape(256, 256)
+        xh = x32.astype(np.float16).astype(np.float32)
+        xl = (x32 - xh).astype(np.float16).astype(np.float64)
+        wh = w32.astype(np.float16).astype(np.float32)
+        wl = (w32 - wh).astype(np.float16).astype(np.float64)
+        xh, wh = xh.astype(np.float64), wh.astype(np.float64)
+        d = conv1(_t(xh), wh + wl) + conv1(_t(xl), wh) + bt
+        E = gamma(769) * (conv1(_t(np.abs(xh)), np.abs(wh) + np.abs(wl)) + conv1(_t(np.abs(xl)), np.abs(wh)) + bt.abs())
+    else:
+        d = conv1(x, w16) + bt
+        E = gamma(257) * (conv1(x.abs(), np.abs(w16)) + bt.abs())
     n = d.norm(dim=1, keepdim=True)
     En = E.norm(dim=1, keepdim=True)
     ref = d / n
