@@ -281,7 +281,7 @@ int         omni_index_truncate(omni_index* idx, int64_t n_rows);
 /* OMNI_STORE_F32 shards keep an fp16 mirror of their rows (+50 % HBM; OMNI_INDEX_MIRROR=0 disables it): a batch of >= 4 queries is scored
  * against the mirror in one matrix-core pass, the best k+24 candidates per query are re-scored exactly against the fp32 rows, and a per-query
  * certificate proves the result is the exact fp32 top-k (scores bit-identical to the single-query path); uncertified queries are re-run with
- * the exact scan.  Counters since creation: queries answered through the mirror / of those, the ones that needed the exact re-run. */
+ * the exact scan (so are all queries over rows fp16 cannot hold, norm >= 6e4, and a query whose largest element lies outside [1e-15, 1e15]).  Counters since creation: queries answered through the mirror / of those, the ones that needed the exact re-run. */
 int         omni_index_cert_stats(omni_index* idx, int64_t* searches, int64_t* fallbacks);
 /* IndexFlatIP::search(nq, q, k, D, I): exact inner product, k best descending, ties -> lower row id,
  * missing results padded with I = -1, D = -FLT_MAX.  k <= 1024 (the reference caps at 1000, loop_detector.cpp:200). */
@@ -313,6 +313,21 @@ int         omni_topk_merge(int n_lists, int nq, int k_each, const float* D_list
  * staging buffer.  load() replaces the handle's contents; dim and storage must match the handle. */
 int         omni_index_save(omni_index* idx, const char* path);
 int         omni_index_load(omni_index* idx, const char* path);
+/* Test hook: ONE named scan kernel over local rows [0, n) (1 <= n <= ntotal), every raw 64-bit key back on the host -- keys_host [nq][n], undecoded
+ * (csrc/common.h omni_make_key: high word = the order-preserving map of the fp32 score, low word = 0xFFFFFFFF - row; 0 = the empty key of a row at or beyond
+ * its query's limit).  What a search shows of a scan is the best k of its scores; this shows all of them.  The kernel is launched by the search's own launch
+ * functions with the search's grid and arguments; `which`:
+ *   OMNI_SCAN_F32        ip_scan_kernel<float, nq>          fp32 rows, nq <= 8 (and nq x dim x 4 <= 128 KB, the search's query block)
+ *   OMNI_SCAN_F32_ROWS   ip_scan_rows_kernel<nq, 4>         fp32 rows, 4 <= nq <= 8
+ *   OMNI_SCAN_T16        ip_scan_t16_kernel<nq>             fp16 rows, nq <= 8
+ *   OMNI_SCAN_MQ         mq_prep_kernel + ip_scan_mq_kernel fp16 rows, nq <= 64
+ *   OMNI_SCAN_MQ_MIRROR  the same over an fp32 shard's fp16 mirror (the first pass of its batched search), nq <= 64
+ * limits (host, [nq], or NULL): query q sees rows [0, limits[q]).  rotate: the matrix-core kernel's k-slice rotation (what OMNI_MQ_ROT sets for a search), 0 / 1.
+ * OMNI_ERR_INVALID for a `which` that does not fit the handle's storage or nq.  Takes the handle's lock; uses buffers of its own: omni_index_cert_stats,
+ * omni_index_last_scan_ms and the results of other searches are as they were without the call. */
+enum { OMNI_SCAN_F32 = 0, OMNI_SCAN_F32_ROWS = 1, OMNI_SCAN_T16 = 2, OMNI_SCAN_MQ = 3, OMNI_SCAN_MQ_MIRROR = 4 };
+int         omni_index_debug_scan(omni_index* idx, int which, int nq, const float* q_host, int64_t n, const int64_t* limits, int rotate,
+                                  uint64_t* keys_host);
 /* device time of the dominant scan kernel for the last search on this handle (HIP events on the ctx stream) */
 int         omni_index_last_scan_ms(omni_index* idx, float* ms);
 

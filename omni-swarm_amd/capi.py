@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("OMNI_LIB") or os.path.join(_HERE, "lib", "libomni_hip
 OK, ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_CAPACITY = 0, 1, 2, 3, 4
 PREC_F32, PREC_F16, PREC_SPLIT = 0, 1, 2
 STORE_F32, STORE_F16 = 0, 1
+SCAN_F32, SCAN_F32_ROWS, SCAN_T16, SCAN_MQ, SCAN_MQ_MIRROR = range(5)      # omni_index_debug_scan
 BF_OPENCV, BF_MUTUAL = 0, 1
 ABI_VERSION = 2               # include/omni_hip.h OMNI_ABI_VERSION: checked when the library is loaded
 SP_NUM_LAYERS = 12
@@ -35,7 +36,7 @@ SYMBOLS = [
     "omni_sp_profile", "omni_sp_stage_name", "omni_sp_stage_flops", "omni_sp_stage_tiles_left_out", "omni_sp_mask_skip_plan", "omni_sp_mask_band_plan", "omni_vlad_create", "omni_vlad_destroy", "omni_vlad_set_precision", "omni_vlad_pack_block", "omni_sp_pack_constants",
     "omni_vlad_infer", "omni_vlad_enqueue_dev", "omni_vlad_fetch", "omni_vlad_dev_output", "omni_vlad_mask_skip_layers", "omni_vlad_debug_taps", "omni_vlad_debug_layer", "omni_vlad_block_paths", "omni_index_create",
     "omni_index_destroy", "omni_index_add", "omni_index_add_dev", "omni_index_ntotal", "omni_index_dim", "omni_index_reset", "omni_index_truncate", "omni_index_cert_stats",
-    "omni_index_search", "omni_index_search_dev", "omni_index_search_prefix_dev", "omni_index_search_batch_prefix_dev", "omni_index_set_shard", "omni_topk_merge", "omni_index_last_scan_ms",
+    "omni_index_search", "omni_index_search_dev", "omni_index_search_prefix_dev", "omni_index_search_batch_prefix_dev", "omni_index_set_shard", "omni_topk_merge", "omni_index_last_scan_ms", "omni_index_debug_scan",
     "omni_index_save", "omni_index_load",
     "omni_trace_push", "omni_trace_pop", "omni_sp_set_perf", "omni_sp_last_stage_ms", "omni_bf_match", "omni_bf_match_multi", "omni_bf_match_batched_dev", "omni_config_count", "omni_config_describe", "omni_config_value", "omni_config_is_process_wide", "omni_cam_create", "omni_cam_create_mono", "omni_cam_destroy", "omni_cam_enqueue_dev", "omni_cam_enqueue_host", "omni_cam_enqueue_host_parts", "omni_cam_enqueue_fisheye_dev", "omni_cam_enqueue_fisheye_host", "omni_cam_get_input", "omni_cam_wait", "omni_cam_order_after", "omni_cam_set_active", "omni_cam_ready",
     "omni_shard_unique_id", "omni_shard_library_path", "omni_shard_create", "omni_shard_destroy", "omni_shard_ntotal", "omni_shard_preload_local", "omni_shard_step_batch_dev", "omni_shard_step_enqueue", "omni_shard_rows_consumed", "omni_shard_step_wait", "omni_shard_last_exchange_us",
@@ -197,6 +198,7 @@ def lib():
     sig("omni_index_set_shard", C.c_int, [_vp, C.c_int, C.c_int])
     sig("omni_topk_merge", C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _i64p, C.c_int, _fp, _i64p])
     sig("omni_index_last_scan_ms", C.c_int, [_vp, _fp])
+    sig("omni_index_debug_scan", C.c_int, [_vp, C.c_int, C.c_int, _fp, C.c_int64, _i64p, C.c_int, C.c_void_p])
     sig("omni_index_save", C.c_int, [_vp, C.c_char_p])
     sig("omni_index_load", C.c_int, [_vp, C.c_char_p])
     sig("omni_bf_match", C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _ip, _ip, _fp, _ip])
@@ -691,6 +693,19 @@ class IndexFlatIP:
         for f in live:
             D[f], I[f] = Da[f], Ia[f]
         return D, I
+
+    def debug_scan(self, which: int, q: np.ndarray, n: int = None, limits=None, rotate: bool = True) -> np.ndarray:
+        """Test hook (omni_index_debug_scan): ONE named scan kernel (SCAN_F32, SCAN_F32_ROWS, SCAN_T16, SCAN_MQ, SCAN_MQ_MIRROR) over rows [0, n) -> the
+        raw 64-bit keys [nq][n] (uint64): high word = the order-preserving map of the fp32 score, low word = 0xFFFFFFFF - row, 0 = beyond the query's limit."""
+        q = _f32(np.atleast_2d(q))
+        assert q.shape[1] == self.d
+        n = self.ntotal if n is None else int(n)
+        lim = None if limits is None else np.ascontiguousarray(limits, np.int64)
+        assert lim is None or len(lim) == q.shape[0]
+        keys = np.empty((q.shape[0], max(n, 0)), np.uint64)
+        _check(lib().omni_index_debug_scan(self.h, which, q.shape[0], _pf(q), n, None if lim is None else lim.ctypes.data_as(_i64p), int(bool(rotate)),
+                                           keys.ctypes.data))
+        return keys
 
     def last_scan_ms(self) -> float:
         ms = C.c_float()

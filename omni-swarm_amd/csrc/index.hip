@@ -573,6 +573,8 @@ cert_refine_kernel(const float* __restrict__ db, int dim, const float* __restric
 //   every row NOT among the candidates has a mirror score <= m = the kp-th mirror score, hence an exact score <= m + eps with
 //   eps = 2^-11 |q| max|row|  (fp16 rounding of the row, element-wise relative 2^-11, Cauchy-Schwarz)  +  slack for the mirror pass's own
 //   fp32-class arithmetic and for fp16 subnormals;  if the k-th exact score is above that, no other row can enter the top k.
+//   (tests/index_scan_ref.py cert_eps restates the formula; tests/test_gpu_index_scores.py holds every mirror score to it and measures the share of the
+//   4e-6 budget the mirror scan uses: at most 0.29 for queries inside the certifiable range.)
 __global__ void __launch_bounds__(64)
 cert_select_kernel(const uint64_t* __restrict__ exact /*[nq][kp]*/, const uint64_t* __restrict__ mirror /*[nq][kp]*/, int kp, int k, const float* __restrict__ queries,
                    int dim, const uint32_t* __restrict__ norm_max, int rank, int world, float* __restrict__ D, int64_t* __restrict__ I, int* __restrict__ flags) {
@@ -582,9 +584,11 @@ cert_select_kernel(const uint64_t* __restrict__ exact /*[nq][kp]*/, const uint64
     if (lane == 0) kth_key = OMNI_KEY_EMPTY;
     const uint64_t mine = lane < kp ? exact[(int64_t)q * kp + lane] : OMNI_KEY_EMPTY;
     s[lane] = mine;
-    float qn = 0.f, q1 = 0.f;
-    for (int c = lane; c < dim; c += 64) { const float v = queries[(int64_t)q * dim + c]; qn = fmaf(v, v, qn); q1 += fabsf(v); }
+    float qn = 0.f, q1 = 0.f, qm = 0.f;
+    for (int c = lane; c < dim; c += 64) { const float v = queries[(int64_t)q * dim + c]; qn = fmaf(v, v, qn); q1 += fabsf(v); qm = fmaxf(qm, fabsf(v)); }
     qn = wave_sum(qn); q1 = wave_sum(q1);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) qm = fmaxf(qm, __shfl_xor(qm, off, 64));
     __syncthreads();
     int r = 0;
     for (int j = 0; j < 64; ++j) r += (s[j] > mine);
@@ -610,14 +614,19 @@ cert_select_kernel(const uint64_t* __restrict__ exact /*[nq][kp]*/, const uint64
                 const float rn = sqrtf(__uint_as_float(*norm_max)), qnorm = sqrtf(qn);
                 const float eps = 4.8829e-4f * 1.0001f * qnorm * rn + 6.0e-8f * q1 + 4.0e-6f * qnorm * rn;
                 need = !(kth > m + eps) || !(rn < 6.0e4f);                // NaN / inf / fp16-overflowing rows: not certifiable
+                // nor is a query whose largest element lies outside [1e-15, 1e15]: below, the squares under qn go subnormal and vanish (eps shrinks to its
+                // |q|_1 term, 400 times too small at 1e-32) and mq_prep_kernel's shift is clamped, so the lo halves are lost (the mirror scan's own error
+                // was measured at 1.5 x its 4e-6 budget); above, qn overflows.  Descriptors are unit vectors; such a query takes the exact path.
+                need = need || !(qm > 1.0e-15f && qm < 1.0e15f);
             }
         }
         flags[q] = need;
     }
 }
 
+// form (omni_index_debug_scan): -1 = the choice below, 0 = the one-row-per-wave kernel, 1 = ip_scan_rows_kernel
 static int launch_scan(hipStream_t st, const omni_index* ix, int64_t n, int qb, const float* q_dev, uint64_t* keys, int64_t key_stride,
-                       const int64_t* limits) {
+                       const int64_t* limits, int form = -1) {
     ScanLimits<SCAN_MAX_QB> lim;
     for (int q = 0; q < SCAN_MAX_QB; ++q) lim.v[q] = limits && q < qb ? limits[q] : INT64_MAX;
     const bool f16 = ix->storage == OMNI_STORE_F16;
@@ -627,7 +636,7 @@ static int launch_scan(hipStream_t st, const omni_index* ix, int64_t n, int qb, 
     if (grid < 1) grid = 1;
     size_t smem = (size_t)qb * ix->dim * sizeof(float);
     static const int rows_min_qb = config_process()[CFG_SCAN_ROWS_MIN];
-    if (!f16 && qb >= rows_min_qb && qb >= 4) {
+    if (!f16 && qb >= 4 && (form < 0 ? qb >= rows_min_qb : form == 1)) {
         constexpr int R = 4;
         int64_t want_g = cdiv64(cdiv64(n, R), SCAN_WAVES);
         int grid_g = (int)(want_g < (int64_t)cus * 8 ? want_g : (int64_t)cus * 8);
@@ -667,9 +676,9 @@ static int launch_scan(hipStream_t st, const omni_index* ix, int64_t n, int qb, 
     return OMNI_OK;
 }
 
-// up to MQ_NQ queries in one pass over an fp16 shard (ip_scan_mq_kernel)
+// up to MQ_NQ queries in one pass over an fp16 shard (ip_scan_mq_kernel); rotate_arg (omni_index_debug_scan): -1 = OMNI_MQ_ROT, else 0 / 1
 static int launch_scan_mq(hipStream_t st, omni_index* ix, int64_t n, int nq, const float* q_dev, uint64_t* keys, int64_t key_stride,
-                          const int64_t* limits, const void* db_t16 = nullptr) {
+                          const int64_t* limits, const void* db_t16 = nullptr, int rotate_arg = -1) {
     ScanLimits<MQ_NQ> lim;
     for (int q = 0; q < MQ_NQ; ++q) lim.v[q] = limits && q < nq ? limits[q] : INT64_MAX;
     auto kfn = ip_scan_mq_kernel;
@@ -686,7 +695,8 @@ static int launch_scan_mq(hipStream_t st, omni_index* ix, int64_t n, int nq, con
     // one workgroup per CU (128 KB of LDS each) walking 512-row blocks b, b + grid, ...
     const int64_t blocks = cdiv64(tiles, MQ_WAVES * MQ_RT);
     const int64_t grid = blocks < cus ? blocks : cus;
-    static const int rotate = config_process()[CFG_MQ_ROT];
+    static const int rotate_cfg = config_process()[CFG_MQ_ROT];
+    const int rotate = rotate_arg < 0 ? rotate_cfg : rotate_arg;
     hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(MQ_THREADS), MQ_SMEM, st, reinterpret_cast<const _Float16*>(db_t16 ? db_t16 : ix->db),
                        n, ix->dim, ix->mq_q.as<char>(), ix->mq_inv.as<float>(), nq, keys, key_stride, rotate, lim);
     OMNI_LAUNCH_CHECK();
@@ -1147,6 +1157,41 @@ int omni_index_cert_stats(omni_index* ix, int64_t* searches, int64_t* fallbacks)
     if (searches) *searches = ix->cert_searches;
     if (fallbacks) *fallbacks = ix->cert_fallbacks;
     return OMNI_OK;
+}
+
+int omni_index_debug_scan(omni_index* ix, int which, int nq, const float* q_host, int64_t n, const int64_t* limits, int rotate, uint64_t* keys_host) {
+    OMNI_REQUIRE(ix && q_host && keys_host, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    OMNI_REQUIRE(n >= 1 && n <= ix->ntotal, OMNI_ERR_INVALID, "n=%lld outside [1, ntotal=%lld]", (long long)n, (long long)ix->ntotal);
+    const bool f16 = ix->storage == OMNI_STORE_F16;
+    const int max_qb = (int)(131072 / ((size_t)ix->dim * 4)) < SCAN_MAX_QB ? (int)(131072 / ((size_t)ix->dim * 4)) : SCAN_MAX_QB;      // search_dev's query block
+    switch (which) {
+        case OMNI_SCAN_F32:       OMNI_REQUIRE(!f16 && nq >= 1 && nq <= max_qb, OMNI_ERR_INVALID, "ip_scan_kernel: fp32 rows, 1 <= nq <= %d", max_qb); break;
+        case OMNI_SCAN_F32_ROWS:  OMNI_REQUIRE(!f16 && nq >= 4 && nq <= max_qb, OMNI_ERR_INVALID, "ip_scan_rows_kernel: fp32 rows, 4 <= nq <= %d", max_qb); break;
+        case OMNI_SCAN_T16:       OMNI_REQUIRE(f16 && nq >= 1 && nq <= max_qb, OMNI_ERR_INVALID, "ip_scan_t16_kernel: fp16 rows, 1 <= nq <= %d", max_qb); break;
+        case OMNI_SCAN_MQ:        OMNI_REQUIRE(f16 && nq >= 1 && nq <= MQ_NQ, OMNI_ERR_INVALID, "ip_scan_mq_kernel: fp16 rows, 1 <= nq <= %d", MQ_NQ); break;
+        case OMNI_SCAN_MQ_MIRROR: OMNI_REQUIRE(!f16 && ix->db16 && nq >= 1 && nq <= MQ_NQ, OMNI_ERR_INVALID, "ip_scan_mq_kernel on the mirror: fp32 rows with a mirror, 1 <= nq <= %d", MQ_NQ); break;
+        default: omni::set_error("omni_index_debug_scan: unknown kernel %d", which); return OMNI_ERR_INVALID;
+    }
+    (void)hipSetDevice(ix->ctx->device);
+    hipStream_t st = ix->ctx->stream;
+    // buffers of its own: the handle's key, result and query buffers, its counters and its scan events stay as the last search left them
+    omni::DevBuf q_dev, keys;
+    int rc;
+    const size_t qbytes = (size_t)nq * ix->dim * 4, kbytes = (size_t)nq * n * 8;
+    if ((rc = q_dev.ensure(qbytes)) || (rc = keys.ensure(kbytes))) { q_dev.release(); keys.release(); return rc; }
+    auto done = [&](int code) { (void)hipStreamSynchronize(st); q_dev.release(); keys.release(); return code; };
+    if (hipMemcpyAsync(q_dev.p, q_host, qbytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(keys.p, 0xFF, kbytes, st) != hipSuccess) { omni::set_error("omni_index_debug_scan: upload failed"); return done(OMNI_ERR_HIP); }
+    if (which == OMNI_SCAN_MQ || which == OMNI_SCAN_MQ_MIRROR)
+        rc = omni::launch_scan_mq(st, ix, n, nq, q_dev.as<float>(), keys.as<uint64_t>(), n, limits, which == OMNI_SCAN_MQ_MIRROR ? ix->db16 : nullptr, rotate ? 1 : 0);
+    else
+        rc = omni::launch_scan(st, ix, n, nq, q_dev.as<float>(), keys.as<uint64_t>(), n, limits, which == OMNI_SCAN_F32_ROWS ? 1 : 0);
+    if (rc) return done(rc);
+    if (hipMemcpyAsync(keys_host, keys.p, kbytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        omni::set_error("omni_index_debug_scan: read-back failed"); return done(OMNI_ERR_HIP);
+    }
+    return done(OMNI_OK);
 }
 
 int omni_index_last_scan_ms(omni_index* ix, float* ms) {
