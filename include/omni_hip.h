@@ -608,6 +608,68 @@ typedef struct omni_cam_jpeg_result {           /* pointers into the handle's pi
 /* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran with the stage off */
 int        omni_cam_jpeg(omni_cam* cam, omni_cam_jpeg_result* out);
 
+/* ---- is_compressed_images: camera frames that arrive as JPEG files (sensor_msgs::CompressedImage; swarm_loop.cpp:72-89, 291-292, 341-360) become gray images,
+ * what cv::imdecode(data, cv::IMREAD_GRAYSCALE) asks of libjpeg (loop_utils.cpp:8), on the GPU (csrc/jpeg_dec.hip).  The arithmetic is stated once, in
+ * csrc/jpeg_dec_plan.h: the first component alone, dequantised, jidctint's islow IDCT, range limit -- libjpeg-turbo's JCS_GRAYSCALE output, PINNED pixel for
+ * pixel against Pillow (Image.draft('L') for colour files) by the CPU tests.  cv::imdecode itself is UNPINNED: OpenCV is not vendored, and that it asks libjpeg
+ * for JCS_GRAYSCALE is read from knowledge, not run.
+ * A file is classified as
+ *   OMNI_JPEGDEC_OK           baseline, one scan, no restart interval, the first component sampled {1,2} x {1,2} and the others 1 x 1: decoded by the kernels
+ *   OMNI_JPEGDEC_HOST         a valid baseline file the kernels do not take (restart interval, several scans, other sampling, a file above the handle's capacity):
+ *                             decoded on the calling thread by the g++ build, its pixels uploaded
+ *   OMNI_JPEGDEC_UNSUPPORTED  progressive, arithmetic, lossless, 12-bit, 16-bit quantisation tables, a component count other than 1 or 3: refused
+ *   OMNI_JPEGDEC_CORRUPT      not a decodable file, or a scan that errs or ends before the picture's last block: the picture is ALL ZEROS */
+#define OMNI_JPEGDEC_OK 0
+#define OMNI_JPEGDEC_HOST 1
+#define OMNI_JPEGDEC_UNSUPPORTED 2
+#define OMNI_JPEGDEC_CORRUPT 3
+typedef struct omni_jpegdec omni_jpegdec;
+/* A handle owns the pinned staging block and all device scratch for up to max_images files of at most capacity_per_image bytes whose pictures are width x height.
+ * 1 <= width, height <= 65535 (at most 2^20 blocks of 8 x 8), 1 <= max_images <= 65535, 1024 <= capacity_per_image <= 2^28.  The subsequence length of the
+ * entropy kernel is OMNI_JPEGDEC_SUBSEQ_BITS (a power of two) as it is when the handle is created. */
+omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int height, int max_images, int64_t capacity_per_image);
+void          omni_jpegdec_destroy(omni_jpegdec* d);
+/* n_images files -> out_dev: picture i at out_dev + i * out_stride * height, out_stride bytes between rows (bytes between the rows' ends are not touched);
+ * status_dev [n_images] int32 OMNI_JPEGDEC_OK / HOST / CORRUPT.  Parses on the calling thread, packs descriptors + unstuffed scans (+ the pixels of HOST files)
+ * into ONE pinned block, one asynchronous upload, then the kernels on the context's stream; the files may be released on return.
+ * Refused before anything is enqueued: an UNSUPPORTED file, a file whose picture is not width x height, n_images outside [1, max_images], out_stride < width. */
+int           omni_jpegdec_enqueue_host(omni_jpegdec* d, const uint8_t* const* files, const int64_t* sizes, int n_images, uint8_t* out_dev, int out_stride,
+                                        int* status_dev);
+/* Of the handle's last enqueue, after a synchronisation with the context's stream: per image the relaxation rounds that changed something, the number of
+ * subsequences and their length in bits (0 0 0 for an image the kernels did not decode).  Each output [n_images] or null. */
+int           omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subseq, int* subseq_bits);
+/* MEASUREMENT: of the handle's last enqueue, once it has run: the time of its upload and of everything behind it (memsets + kernels) on the GPU, and the bytes it
+ * uploaded (tools/jpegdec_timing.py) */
+int           omni_jpegdec_last_ms(omni_jpegdec* d, float* upload_ms, float* kernels_ms, int64_t* uploaded_bytes);
+/* TEST INFRASTRUCTURE: the device addresses and sizes of the coefficient and the DC buffer; each is followed by OMNI_JPEGDEC_GUARD_BYTES bytes of 0xA5 that
+ * nothing ever writes */
+#define OMNI_JPEGDEC_GUARD_BYTES 256
+int           omni_jpegdec_debug_buffers(omni_jpegdec* d, void** coef_dev, int64_t* coef_bytes, void** dc_dev, int64_t* dc_bytes);
+/* the classification of a file without a capacity, and its picture's size (0 x 0 when no frame header can be read); no GPU */
+int           omni_jpegdec_classify(const uint8_t* file, int64_t size, int* width, int* height);
+/* csrc/jpeg_dec_plan.h's sequential decoder compiled by g++ into the library, next to omni_jpeg_encode_host: the same pixels without a GPU, restart intervals
+ * and the other HOST files included.  out: the picture (its size: omni_jpegdec_classify), `stride` bytes between rows.  *status = the classification, or
+ * OMNI_JPEGDEC_CORRUPT with the picture zeroed; an UNSUPPORTED file writes nothing.  OMNI_ERR_INVALID for null arguments and a stride below the width. */
+int           omni_jpeg_decode_host(const uint8_t* file, int64_t size, uint8_t* out, int stride, int* width, int* height, int* status);
+/* TEST INFRASTRUCTURE: the CPU stand-in for the kernels (jpeg_decode_parallel_host: the phase functions driven by plain loops) with subseq_bits per subsequence;
+ * stats[4] = subsequences, their length, relaxation rounds that changed something, subsequences whose first-pass exit state was wrong */
+int           omni_jpeg_decode_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, uint8_t* out, int stride, int* width, int* height, int* status,
+                                             int* stats);
+
+/* The same stage inside the key-frame unit: a unit whose frames arrive as JPEG files.  The decode runs on the unit's SuperPoint stream in front of the resize, and
+ * the decoded frames take the place of omni_cam_enqueue_raw_*'s: n_keyframes left files and as many right files for a stereo handle (STEREO_PINHOLE), left files
+ * alone (right_files = right_sizes = NULL) for a mono handle (PINHOLE_DEPTH's gray image; the depth image stays uncompressed).  resize: camera-size pictures ->
+ * the networks' size; NULL: the files hold network-size pictures, decoded straight into the unit's input block.  Everything behind is the existing unit, no
+ * fisheye mask (the reference has no compressed path for STEREO_FISHEYE); omni_cam_get_input shows the block the networks read.  The handle makes its decoder at
+ * first use for the pictures' size (capacity: width x height / 2 bytes per file; a larger file is decoded on the calling thread).  Refused before anything is
+ * enqueued: an UNSUPPORTED file, a picture of another size, a unit in flight, n_keyframes other than the active size.  A CORRUPT frame is all zeros: no key
+ * points, landmark_num 0, and the reference's own rule drops the frame. */
+int        omni_cam_enqueue_jpeg_host(omni_cam* cam, omni_resize* resize_or_null, const uint8_t* const* left_files, const int64_t* left_sizes,
+                                      const uint8_t* const* right_files_or_null, const int64_t* right_sizes, int n_keyframes);
+/* after omni_cam_wait: OMNI_JPEGDEC_OK / HOST / CORRUPT of every frame of that unit, [left frames | right frames]; n_frames = cams x the unit's active size.
+ * OMNI_ERR_INVALID while a unit is pending, and when the last unit did not come as files */
+int        omni_cam_jpegdec_status(omni_cam* cam, int* status, int n_frames);
+
 #ifdef __cplusplus
 }
 #endif

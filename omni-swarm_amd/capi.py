@@ -45,7 +45,11 @@ SYMBOLS = [
     "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
+    "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
+    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status",
 ]
+JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
+JPEGDEC_GUARD_BYTES = 256
 JPEG_OK, JPEG_TRUNCATED, JPEG_HEADER_BYTES = 0, 1, 328      # include/omni_hip.h OMNI_JPEG_*
 HG_UNFILTERED, HG_OK, HG_NO_MODEL, HG_HOST = 0, 1, 2, 3     # include/omni_hip.h OMNI_HG_*: the status of one pair's homography RANSAC
 PNP_SKIPPED, PNP_OK, PNP_NO_MODEL, PNP_HOST = 0, 1, 2, 3    # include/omni_hip.h OMNI_PNP_*: the status of one candidate's PnP RANSAC
@@ -238,6 +242,17 @@ def lib():
     sig("omni_jpeg_encode_host", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _i64p, _ip])
     sig("omni_cam_set_jpeg", C.c_int, [_vp, C.c_int, C.c_int64])
     sig("omni_cam_jpeg", C.c_int, [_vp, C.POINTER(_CamJpeg)])
+    sig("omni_jpegdec_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int64])
+    sig("omni_jpegdec_destroy", None, [_vp])
+    sig("omni_jpegdec_enqueue_host", C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _vp, C.c_int, _vp])
+    sig("omni_jpegdec_last_stats", C.c_int, [_vp, _ip, _ip, _ip])
+    sig("omni_jpegdec_last_ms", C.c_int, [_vp, _fp, _fp, _i64p])
+    sig("omni_jpegdec_debug_buffers", C.c_int, [_vp, C.POINTER(_vp), _i64p, C.POINTER(_vp), _i64p])
+    sig("omni_jpegdec_classify", C.c_int, [_vp, C.c_int64, _ip, _ip])
+    sig("omni_jpeg_decode_host", C.c_int, [_vp, C.c_int64, _vp, C.c_int, _ip, _ip, _ip])
+    sig("omni_cam_enqueue_jpeg_host", C.c_int, [_vp, _vp, C.POINTER(_vp), _i64p, C.POINTER(_vp), _i64p, C.c_int])
+    sig("omni_cam_jpegdec_status", C.c_int, [_vp, _ip, C.c_int])
+    sig("omni_jpeg_decode_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
     sig("omni_cam_ready", C.c_int, [_vp, C.POINTER(C.c_int)])
@@ -894,6 +909,103 @@ class Jpeg:
         self.last_guard_ok = bool((raw[n * self.capacity:] == 0xA5).all())
         self.last_sizes = m[0].copy()
         return [(int(m[1, i]), self.last_raw[i, :m[0, i]].tobytes()) for i in range(n)]
+
+def jpegdec_classify(data: bytes):
+    """(OMNI_JPEGDEC_* classification, width, height) of a JPEG file (csrc/jpeg_dec_plan.h's parser; no GPU).  0 x 0: no frame header could be read"""
+    w, h = C.c_int(0), C.c_int(0)
+    st = lib().omni_jpegdec_classify(data, len(data), C.byref(w), C.byref(h))
+    return st, w.value, h.value
+
+
+def _jpeg_decode(data: bytes, stride: int, call):
+    cls, w, h = jpegdec_classify(data)
+    st = stride or w
+    out = np.full((max(h, 1), max(st, 1)), 0xA5, np.uint8)
+    ww, hh, status = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(call(out.ctypes.data_as(_vp), st, C.byref(ww), C.byref(hh), C.byref(status)))
+    return status.value, (out[:h] if stride else out[:h, :w].copy())
+
+
+def jpeg_decode_host(data: bytes, stride: int = 0):
+    """csrc/jpeg_dec_plan.h's sequential decoder on the host (g++ inside the library; no GPU): a JPEG file -> (status, gray [h][w] u8).  stride > w: the
+    array returned is [h][stride], 0xA5 where nothing was written.  UNSUPPORTED: nothing is written"""
+    return _jpeg_decode(data, stride, lambda o, st, w, h, s: lib().omni_jpeg_decode_host(data, len(data), o, st, w, h, s))
+
+
+def jpeg_decode_parallel_host(data: bytes, subseq_bits: int):
+    """the CPU stand-in for the kernels -> (status, gray, dict(n_sub, subseq_bits, rounds, wrong_after_first))"""
+    stats = (C.c_int * 4)()
+    status, pix = _jpeg_decode(data, 0, lambda o, st, w, h, s: lib().omni_jpeg_decode_parallel_host(data, len(data), subseq_bits, o, st, w, h, s, stats))
+    return status, pix, dict(n_sub=stats[0], subseq_bits=stats[1], rounds=stats[2], wrong_after_first=stats[3])
+
+
+class JpegDec:
+    """omni_jpegdec: up to max_images JPEG files of at most capacity_per_image bytes -> gray images of width x height on the GPU (is_compressed_images;
+    csrc/jpeg_dec.hip, the arithmetic: csrc/jpeg_dec_plan.h)"""
+
+    def __init__(self, ctx: Context, width: int, height: int, max_images: int, capacity_per_image: int = 0):
+        self.ctx, self.w, self.h_img, self.max_images = ctx, width, height, max_images
+        self.capacity = capacity_per_image or max(width * height // 2, 1024)
+        self.h = lib().omni_jpegdec_create(ctx.h, width, height, max_images, self.capacity)
+        if not self.h:
+            raise OmniError(f"omni_jpegdec_create failed: {lib().omni_last_error().decode()}")
+        ctx._adopt(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().omni_jpegdec_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def enqueue_host(self, files, out_dev: int, out_stride: int, status_dev: int):
+        """files: [bytes]; asynchronous on the context's stream (the files may go on return)"""
+        n = len(files)
+        ptrs = (_vp * n)(*[C.cast(C.c_char_p(f), _vp) for f in files])
+        sizes = (C.c_int64 * n)(*[len(f) for f in files])
+        _check(lib().omni_jpegdec_enqueue_host(self.h, ptrs, sizes, n, out_dev, out_stride, status_dev))
+
+    def last_stats(self, n: int):
+        """per image of the last call: (relaxation rounds that changed something, subsequences, bits per subsequence)"""
+        r, s, b = (C.c_int * self.max_images)(), (C.c_int * self.max_images)(), (C.c_int * self.max_images)()
+        _check(lib().omni_jpegdec_last_stats(self.h, r, s, b))
+        return [(r[i], s[i], b[i]) for i in range(n)]
+
+    def last_ms(self):
+        """(upload ms, memsets + kernels ms, bytes uploaded) of the last call, on the GPU's clock"""
+        u, k, b = C.c_float(), C.c_float(), C.c_int64()
+        _check(lib().omni_jpegdec_last_ms(self.h, C.byref(u), C.byref(k), C.byref(b)))
+        return u.value, k.value, b.value
+
+    def guards_ok(self) -> bool:
+        """the 0xA5 bytes behind the coefficient and the DC buffer are as they were created"""
+        cp, cb, dp, db = _vp(), C.c_int64(), _vp(), C.c_int64()
+        _check(lib().omni_jpegdec_debug_buffers(self.h, C.byref(cp), C.byref(cb), C.byref(dp), C.byref(db)))
+        self.ctx.sync()
+        return all(bool((self.ctx.from_device(p.value + b.value, (JPEGDEC_GUARD_BYTES,), np.uint8) == 0xA5).all()) for p, b in ((cp, cb), (dp, db)))
+
+    def __call__(self, files, stride: int = 0):
+        """[bytes] -> ([status], pictures [n][h][stride or w] u8) (host convenience: enqueue, download).  The output block is 0xA5 before the call and has a guard
+        behind it: `last_guard_ok` tells whether the stage kept to it (and to its own buffers' guards)."""
+        n, st = len(files), stride or self.w
+        guard = 256
+        out = self.ctx.to_device(np.full(n * self.h_img * st + guard, 0xA5, np.uint8))
+        status = self.ctx.to_device(np.full(n, -1, np.int32))
+        try:
+            self.enqueue_host(files, out, st, status)
+            raw = self.ctx.from_device(out, (n * self.h_img * st + guard,), np.uint8)
+            stv = self.ctx.from_device(status, (n,), np.int32)
+        finally:
+            self.ctx.free(out)
+            self.ctx.free(status)
+        self.last_guard_ok = bool((raw[n * self.h_img * st:] == 0xA5).all()) and self.guards_ok()
+        return [int(v) for v in stv], raw[:n * self.h_img * st].reshape(n, self.h_img, st)
+
+
 SHARD_ID_BYTES = 128
 
 
@@ -1204,6 +1316,25 @@ class Cam:
         lp, ln, nl = pack(left_parts)
         rp, rn, nr = pack(right_parts)
         _check(lib().omni_cam_enqueue_raw_host_parts(self.h, resize.h, lp, ln, nl, rp, rn, nr, resize.src_w))
+
+    def enqueue_jpeg_host(self, resize, left_files, right_files=None):
+        """is_compressed_images: the unit's frames as JPEG files ([bytes] per camera; right_files None for a mono handle), decoded on the GPU inside the unit in
+        front of `resize` (None: the files hold network-size pictures).  The files may go on return."""
+        def pack(files):
+            if files is None:
+                return None, None
+            return (_vp * len(files))(*[C.cast(C.c_char_p(f), _vp) for f in files]), (C.c_int64 * len(files))(*[len(f) for f in files])
+        assert right_files is None or len(right_files) == len(left_files)
+        lp, ls = pack(left_files)
+        rp, rs = pack(right_files)
+        _check(lib().omni_cam_enqueue_jpeg_host(self.h, resize.h if resize is not None else None, lp, ls, rp, rs, len(left_files)))
+
+    def jpegdec_status(self) -> list:
+        """after wait(): the OMNI_JPEGDEC_* status of every frame of that unit, [left frames | right frames]"""
+        n = self.cams * self.n_active
+        st = (C.c_int * n)()
+        _check(lib().omni_cam_jpegdec_status(self.h, st, n))
+        return list(st)
 
     def get_input(self) -> np.ndarray:
         """[cams * n_active][H][W] u8: the handle's own input block as the last enqueue_host / enqueue_fisheye_* / enqueue_raw_* unit left it (not after enqueue_dev)"""

@@ -48,6 +48,12 @@ struct omni_cam {
     uint8_t *d_jpeg = nullptr, *h_jpeg = nullptr;
     bool jpeg_unit = false;                   // the unit enqueued last ran the stage (omni_cam_jpeg)
     int jpeg_n = 0;                           // main images of that unit
+    // is_compressed_images (omni_cam_enqueue_jpeg_host; jpeg_dec.hip): the unit's frames arrive as JPEG files and are decoded on the SuperPoint stream in front of
+    // the resize.  The decoder is made at first use for the frames' size; statuses [cams * n_cap] go down into a pinned block of their own
+    omni_jpegdec* jdec = nullptr;
+    int jdec_w = 0, jdec_h = 0;
+    int *d_jdec_status = nullptr, *h_jdec_status = nullptr;
+    int jdec_n = 0;                           // frames of the unit enqueued last if it came as files (omni_cam_jpegdec_status), else 0
     std::mutex mu;
 };
 
@@ -119,6 +125,9 @@ void omni_cam_destroy(omni_cam* c) {
     void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw, c->d_poses, c->d_lm};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->jpeg) omni_jpeg_destroy(c->jpeg);
+    if (c->jdec) omni_jpegdec_destroy(c->jdec);
+    if (c->d_jdec_status) (void)hipFree(c->d_jdec_status);
+    if (c->h_jdec_status) (void)hipHostFree(c->h_jdec_status);
     if (c->d_jpeg) (void)hipFree(c->d_jpeg);
     if (c->h_jpeg) (void)hipHostFree(c->h_jpeg);
     if (c->host) (void)hipHostFree(c->host);
@@ -355,6 +364,73 @@ int omni_cam_enqueue_raw_host_parts(omni_cam* c, omni_resize* r, const uint8_t* 
     return cam_raw_locked(c, r, nullptr, nullptr, left, left_images, n_left, right, right_images, n_right, src_stride, nl);
 }
 
+// A unit whose frames arrive as JPEG files (is_compressed_images: comp_stereo_images_callback / comp_depth_images_callback, swarm_loop.cpp:72-89, each frame through
+// cv::imdecode(data, IMREAD_GRAYSCALE)): the decode (jpeg_dec.hip) runs inside the unit, on the SuperPoint stream, in front of the resize, and the decoded frames
+// take the place of omni_cam_enqueue_raw_*'s.  n_keyframes left files (all files of a mono handle: right_files = NULL) and as many right files; `resize` NULL:
+// the files hold network-size pictures and are decoded straight into the unit's input block.  Everything behind is the existing unit.
+int omni_cam_enqueue_jpeg_host(omni_cam* c, omni_resize* r, const uint8_t* const* left_files, const int64_t* left_sizes, const uint8_t* const* right_files,
+                               const int64_t* right_sizes, int n_keyframes) {
+    OMNI_REQUIRE(c && left_files && left_sizes && (!right_files == !right_sizes), OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("omni_cam_enqueue_jpeg_host (decode + resize + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE((c->cams == 2) == (right_files != nullptr), OMNI_ERR_INVALID, "omni_cam_enqueue_jpeg_host: a stereo handle takes left and right files, a mono handle left files only");
+    OMNI_REQUIRE(n_keyframes == c->n, OMNI_ERR_INVALID, "omni_cam_enqueue_jpeg_host: %d key frames for a unit of %d (omni_cam_set_active)", n_keyframes, c->n);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_enqueue_jpeg_host with a unit in flight (omni_cam_wait first)");
+    c->jdec_n = 0;                                                            // (no unit is in flight: whatever fails below, an earlier unit's statuses are not handed out for this one)
+    if (r) {
+        OMNI_REQUIRE(r->dst_w == c->W && r->dst_h == c->H, OMNI_ERR_INVALID, "omni_cam_enqueue_jpeg_host: the resize object makes %dx%d images but the networks were created for %dx%d",
+                     r->dst_w, r->dst_h, c->W, c->H);
+        OMNI_REQUIRE(r->ctx->device == c->c1->device, OMNI_ERR_INVALID, "omni_cam_enqueue_jpeg_host: resize tables on device %d, the unit on device %d", r->ctx->device, c->c1->device);
+    }
+    int rc;
+    if ((rc = cam_poses_check(c))) return rc;
+    (void)hipSetDevice(c->c1->device);
+    const int sw = r ? r->src_w : c->W, sh = r ? r->src_h : c->H, n = c->n, ni = c->cams * n;
+    if (!c->jdec || c->jdec_w != sw || c->jdec_h != sh) {
+        if (c->jdec) omni_jpegdec_destroy(c->jdec);
+        const int64_t cap = (int64_t)sw * sh / 2 > 1024 ? (int64_t)sw * sh / 2 : 1024;       // (a larger file is decoded on the calling thread: same pixels)
+        c->jdec = omni_jpegdec_create(c->c1, sw, sh, c->cams * c->n_cap, cap);
+        if (!c->jdec) return OMNI_ERR_INVALID;
+        c->jdec_w = sw; c->jdec_h = sh;
+    }
+    if (!c->d_jdec_status) {
+        OMNI_HIP_TRY(hipMalloc((void**)&c->d_jdec_status, (size_t)c->cams * c->n_cap * sizeof(int)));
+        OMNI_HIP_TRY(hipHostMalloc((void**)&c->h_jdec_status, (size_t)c->cams * c->n_cap * sizeof(int), hipHostMallocDefault));
+    }
+    const size_t half = (size_t)n * c->W * c->H, frame = (size_t)sw * sh;
+    if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, (size_t)c->cams * half))) return rc;
+    if (r && (rc = cam_staging(c, c->d_raw, c->d_raw_bytes, (size_t)ni * frame))) return rc;
+    std::vector<const uint8_t*> files(left_files, left_files + n);
+    std::vector<int64_t> sizes(left_sizes, left_sizes + n);
+    if (right_files) {
+        files.insert(files.end(), right_files, right_files + n);
+        sizes.insert(sizes.end(), right_sizes, right_sizes + n);
+    }
+    hipStream_t s1 = c->c1->stream;
+    // all frames of the unit in one decode: [left frames | right frames], rows packed (an UNSUPPORTED file or another size is refused here, nothing enqueued)
+    uint8_t* dec = r ? c->d_raw : c->d_gray;
+    if ((rc = omni::jpegdec_enqueue_on(c->jdec, s1, files.data(), sizes.data(), ni, dec, sw, c->d_jdec_status))) return rc;
+    OMNI_HIP_TRY(hipMemcpyAsync(c->h_jdec_status, c->d_jdec_status, (size_t)ni * sizeof(int), hipMemcpyDeviceToHost, s1));
+    if (r && (rc = omni::resize_unit_launch(r, s1, c->d_raw, sw, n, c->d_gray))) return rc;
+    OMNI_HIP_TRY(hipEventRecord(c->e_up, s1));
+    OMNI_HIP_TRY(hipStreamWaitEvent(c->c2->stream, c->e_up, 0));
+    if (r && c->cams == 2 && (rc = omni::resize_unit_launch(r, s1, c->d_raw + (size_t)n * frame, sw, n, c->d_gray + half))) return rc;
+    rc = cam_enqueue_locked(c, c->d_gray, c->W, 0);                                          // (no compressed path for STEREO_FISHEYE: no mask)
+    c->jdec_n = rc == OMNI_OK ? ni : 0;
+    return rc;
+}
+
+// the OMNI_JPEGDEC_* status of every frame of the last unit, [left frames | right frames]; after omni_cam_wait
+int omni_cam_jpegdec_status(omni_cam* c, int* status, int n_frames) {
+    OMNI_REQUIRE(c && status, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_jpegdec_status with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->jdec_n > 0, OMNI_ERR_INVALID, "omni_cam_jpegdec_status: the last unit did not come as JPEG files");
+    OMNI_REQUIRE(n_frames == c->jdec_n, OMNI_ERR_INVALID, "omni_cam_jpegdec_status: %d frames asked for, the last unit had %d", n_frames, c->jdec_n);
+    memcpy(status, c->h_jdec_status, (size_t)n_frames * sizeof(int));
+    return OMNI_OK;
+}
+
 // the handle's own input block as the last unit's networks read it (the fisheye mask is applied inside the networks, not here: a unit of flattened views shows
 // them as uploaded, a unit of raw frames as flatten_unit_kernel wrote them)
 int omni_cam_get_input(omni_cam* c, uint8_t* out_host, int64_t bytes) {
@@ -413,6 +489,7 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
     OMNI_HIP_TRY(hipEventRecord(c->e1, s1));
     OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_g, c->g_dev, (size_t)n * c->out_dim * 4, hipMemcpyDeviceToHost, s2));
     c->jpeg_unit = false;
+    c->jdec_n = 0;                                                            // (omni_cam_enqueue_jpeg_host sets it behind this call)
     if (c->jpeg_quality) {
         // encode_image on the main image of every direction (loop_cam.cpp:306-308, 463-469): behind MobileNetVLAD's read of the same n images on ITS stream, next
         // to the SuperPoint stack.  The reference blanks the mask's rows in the very pixels it encodes (:536-539 through a cv::Mat that shares its data); the

@@ -213,6 +213,14 @@ int jpeg_launch(omni_jpeg* j, hipStream_t stream, const uint8_t* gray_dev, int s
                 int* status_dev);
 }  // namespace omni
 
+struct omni_jpegdec;
+namespace omni {
+// jpeg_dec.hip: n_images JPEG files -> gray pictures at out_dev (picture i at + i * out_stride * the handle's height), status_dev [n_images] -- parse, pack, ONE
+// upload and the kernels on `stream`, which need not be the handle's own.  Refuses before anything is enqueued (an UNSUPPORTED file, another size)
+int jpegdec_enqueue_on(omni_jpegdec* d, hipStream_t stream, const uint8_t* const* files, const int64_t* sizes, int n_images, uint8_t* out_dev, int out_stride,
+                       int* status_dev);
+}  // namespace omni
+
 // ---- 64-bit sortable keys -------------------------------------------------------------------------------------
 // key = (orderable(score) << 32) | (0xFFFFFFFF - id): descending key order == (score desc, id asc).
 __host__ __device__ static inline uint32_t omni_f32_orderable(float f) {

@@ -74,6 +74,9 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
                                                    "tails the next units' kernels fill (-5 % when chained)"},
     {"OMNI_PIPELINE_UNIT_PLAN", 1, 0, 2, CFG_VARIANT, "KeyframePipeline::run on host blocks, a run that is not a whole number of micro-batches: 1 = units of equal size (20 key frames = "
                                                        "7 + 7 + 6), 2 = the same behind half a unit, 0 = the blocks' own cut (8 + 8 + 4)"},
+    // ---- JPEG decode -----------------------------------------------------------------------------------------------------------------------------------
+    {"OMNI_JPEGDEC_SUBSEQ_BITS", 1024, 128, 65536, CFG_TUNING, "omni_jpegdec: bits per subsequence of the entropy kernel's self-synchronising decode, a power of two (csrc/jpeg_dec_plan.h); "
+                                                               "an image of more than 4096 subsequences is decoded with the next power of two that gives fewer.  Same pixels for every value"},
     // ---- runtime ---------------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_HW_QUEUES", 8, 0, 64, CFG_TUNING, "hardware queues asked of the HIP runtime when the library is loaded (GPU_MAX_HW_QUEUES, unless already set): the pipeline's five "
                                             "streams must not share one; 0 = the runtime's default of 4"},

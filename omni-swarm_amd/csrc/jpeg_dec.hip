@@ -1,0 +1,377 @@
+// omni_jpegdec_*: camera frames that arrive as baseline JPEG files (is_compressed_images: cv::imdecode(data, IMREAD_GRAYSCALE), swarm_loop.cpp:72-89) become gray
+// images on the GPU.  The arithmetic, the symbol step and the parallel scheme are jpeg_dec_plan.h's -- this file only spreads them over lanes:
+//   entropy  ONE workgroup per image, phases 1-4 of the plan in one launch.  A Huffman scan is one sequential bit stream: it is cut into subsequences of S bits,
+//            every lane decodes subsequences from a guessed state, and relaxation rounds repeat those whose predecessor's exit state changed until a round changes
+//            nothing (self-synchronisation; at most N rounds, a fixed point IS the sequential decode).  Exit states, entry states and block counts live in LDS; the
+//            round loop is workgroup-uniform (__syncthreads + an LDS flag).  Then the exclusive scan of the block counts, and the write pass: the first component's
+//            coefficients straight to global memory (zeroed before), every index checked against the image's block count;
+//   dc       one workgroup per image: the scan of the DC differences in scan order;
+//   block    across all images, one 8 x 8 block per lane: dequantise, islow IDCT, clamp, store cropped.  A CORRUPT image is written as zeros; the pixels of a
+//            file the host decoded are copied from the uploaded block.
+// The host side parses, unstuffs the scans into the handle's pinned block and uploads it once.  Everything runs on the caller's stream.
+#include "common.h"
+#include "config.h"
+#include "jpeg_dec_plan.h"
+
+#define JD_THREADS 256
+#define JD_MAX_SUBSEQ 4096                 // per image: 16 per lane (the lane's `need` bits); an image with more is decoded with a longer subsequence
+#define JD_BLOCK_THREADS 256
+
+struct omni_jpegdec {
+    omni_ctx* ctx = nullptr;
+    int w = 0, h = 0, max_images = 0, subseq_bits = 0;
+    int64_t capacity = 0;
+    uint32_t nyb_max = 0;                  // blocks of the first component of a w x h picture with 16 x 16 MCUs
+    size_t in_bytes = 0;
+    omni::DevMem mem;
+    uint8_t* d_in = nullptr;               // the uploaded block: descriptors | clean scans | host-decoded pixels
+    int16_t* d_coef = nullptr;             // [max_images][nyb_max][64] + guard
+    int32_t* d_dc = nullptr;               // [max_images][nyb_max] + guard
+    int* d_rounds = nullptr;               // [max_images]
+    omni::HostBuf hin;
+    hipEvent_t ev_upload = nullptr;        // the pinned block is free again
+    hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};      // in front of the upload, behind it, behind the kernels (omni_jpegdec_last_ms)
+    size_t last_bytes = 0;
+    bool timed = false;                    // ev_t hold ONE call's three events
+    int last_n = 0;
+    std::mutex mu;
+};
+
+namespace omni {
+
+static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// exclusive scan of one value per lane over a workgroup of kThreads (mod 2^32); *total = the sum.  lds: kThreads / 64 + 1 words, free again on return
+template <int kThreads>
+__device__ __forceinline__ uint32_t jd_wg_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = kThreads / 64;
+    uint32_t incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) lds[wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (int i = 0; i < nw; ++i) { const uint32_t t = lds[i]; lds[i] = run; run += t; }
+        lds[nw] = run;
+    }
+    __syncthreads();
+    const uint32_t r = lds[wave] + incl - v;
+    *total = lds[nw];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8_t* __restrict__ in, int16_t* __restrict__ coef, int32_t* __restrict__ dcd,
+                                                                     uint32_t nyb_max, int* __restrict__ status, int* __restrict__ rounds_out) {
+    __shared__ jd::Tables T;
+    __shared__ uint16_t ex[JD_MAX_SUBSEQ], used[JD_MAX_SUBSEQ];
+    __shared__ uint32_t cnt[JD_MAX_SUBSEQ];
+    __shared__ uint32_t lds[JD_THREADS / 64 + 1];
+    __shared__ int changed, errflag;
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
+    if (d->mode != jd::JD_MODE_DECODE) {                                                    // (uniform: the whole workgroup leaves)
+        if (tid == 0) { status[img] = d->status; rounds_out[img] = 0; }
+        return;
+    }
+    {
+        const uint32_t* s = reinterpret_cast<const uint32_t*>(&d->T);
+        uint32_t* t = reinterpret_cast<uint32_t*>(&T);
+        for (int i = tid; i < (int)(sizeof(jd::Tables) / 4); i += JD_THREADS) t[i] = s[i];
+    }
+    if (tid == 0) { changed = 0; errflag = 0; }
+    const uint32_t S = d->subseq_bits, total_bits = d->total_bits, n_blocks = d->n_blocks;
+    const uint32_t N = d->n_sub < JD_MAX_SUBSEQ ? d->n_sub : JD_MAX_SUBSEQ;                 // (the host made n_sub <= JD_MAX_SUBSEQ; the LDS arrays hold no more)
+    const uint8_t* scan = in + d->dev_off;
+    const uint32_t n_words = jd::scan_words((int64_t)(total_bits >> 3));
+    __syncthreads();
+    jd::NoEmit none;
+    int e;
+    for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 1: every subsequence from the guess
+        uint16_t x;
+        cnt[i] = jd::decode_subseq(T, scan, n_words, total_bits, i, S, (uint16_t)0, 0u, 0xffffffffu, none, &x, &e);
+        ex[i] = x;
+        used[i] = 0;
+    }
+    __syncthreads();
+    int rounds = 0;
+    for (uint32_t r = 0; r < N; ++r) {                                                      // 2: relaxation; every lane runs the same number of rounds
+        uint32_t need = 0;
+        for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
+            if (i == 0) continue;
+            const uint16_t en = ex[i - 1];
+            if (en != used[i]) { used[i] = en; need |= 1u << k; }
+        }
+        __syncthreads();                                                                    // every entry is read before any exit is written
+        for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
+            if (!(need >> k & 1u)) continue;
+            uint16_t x;
+            const uint32_t c = jd::decode_subseq(T, scan, n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, &x, &e);
+            if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = 1; }
+        }
+        __syncthreads();
+        const int ch = changed;
+        __syncthreads();
+        if (!ch) break;                                                                     // (uniform)
+        if (tid == 0) changed = 0;
+        ++rounds;
+    }
+    __syncthreads();
+    uint32_t carry = 0;                                                                     // 3: counts -> first blocks, in place
+    for (uint32_t base = 0; base < N; base += JD_THREADS) {
+        const uint32_t i = base + tid;
+        uint32_t sum;
+        const uint32_t excl = jd_wg_scan<JD_THREADS>(i < N ? cnt[i] : 0u, lds, &sum);
+        if (i < N) cnt[i] = carry + excl;
+        carry += sum;
+    }
+    __syncthreads();
+    int err = 0;
+    for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 4: the write pass
+        jd::CoefEmit em;
+        em.coef = coef + (size_t)img * nyb_max * 64;
+        em.dcd = dcd + (size_t)img * nyb_max;
+        em.n_yblocks = d->n_yblocks < nyb_max ? d->n_yblocks : nyb_max;
+        const uint16_t entry = i == 0 ? (uint16_t)0 : used[i];
+        em.start(T, cnt[i], entry >> 12);
+        uint16_t x;
+        jd::decode_subseq(T, scan, n_words, total_bits, i, S, entry, cnt[i], n_blocks, em, &x, &e);
+        err |= e;
+    }
+    if (err) atomicOr(&errflag, 1);
+    __syncthreads();
+    if (tid == 0) {
+        status[img] = (errflag || carry < n_blocks) ? OMNI_JPEGDEC_CORRUPT : d->status;
+        rounds_out[img] = rounds;
+    }
+}
+
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_dc_kernel(const uint8_t* __restrict__ in, int32_t* __restrict__ dcd, uint32_t nyb_max) {
+    __shared__ uint32_t lds[JD_THREADS / 64 + 1];
+    const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + blockIdx.x;
+    if (d->mode != jd::JD_MODE_DECODE) return;
+    const uint32_t n = d->n_yblocks < nyb_max ? d->n_yblocks : nyb_max;
+    int32_t* v = dcd + (size_t)blockIdx.x * nyb_max;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += JD_THREADS) {                                 // (uniform trip count: every lane reaches the barriers)
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t x = i < n ? (uint32_t)v[i] : 0u;
+        uint32_t sum;
+        const uint32_t excl = jd_wg_scan<JD_THREADS>(x, lds, &sum);
+        if (i < n) v[i] = (int32_t)(carry + excl + x);
+        carry += sum;
+    }
+}
+
+__global__ __launch_bounds__(JD_BLOCK_THREADS) void jpegdec_block_kernel(const uint8_t* __restrict__ in, const int16_t* __restrict__ coef, const int32_t* __restrict__ dcv,
+                                                                         uint32_t nyb_max, const int* __restrict__ status, int w, int h, uint8_t* __restrict__ out,
+                                                                         int64_t out_stride) {
+    const int img = blockIdx.y;
+    const uint32_t y = blockIdx.x * JD_BLOCK_THREADS + threadIdx.x;
+    const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
+    uint8_t* o = out + (int64_t)img * out_stride * h;
+    if (d->mode == jd::JD_MODE_DECODE && d->w == w && d->h == h) {
+        if (y >= d->n_yblocks || y >= nyb_max) return;
+        jd::block_out(*d, coef + (size_t)img * nyb_max * 64, dcv + (size_t)img * nyb_max, y, status[img] == OMNI_JPEGDEC_CORRUPT, o, out_stride);
+        return;
+    }
+    // a picture that comes as pixels (decoded on the host), or as zeros: block y of the w x h picture in raster order
+    const int bw = (w + 7) / 8, bh = (h + 7) / 8;
+    if (y >= (uint32_t)(bw * bh)) return;
+    const int bx = (int)(y % (uint32_t)bw), by = (int)(y / (uint32_t)bw);
+    const uint8_t* px = d->mode == jd::JD_MODE_PIXELS ? in + d->dev_off : nullptr;
+    for (int j = 0; j < 8 && by * 8 + j < h; ++j)
+        for (int i = 0; i < 8 && bx * 8 + i < w; ++i) {
+            const int64_t yy = by * 8 + j, xx = bx * 8 + i;
+            o[yy * out_stride + xx] = px ? px[yy * w + xx] : (uint8_t)0;
+        }
+}
+
+// The stage on `stream`; the caller holds d->mu, has checked the arguments, and d_in holds the block of n_images images
+static int jpegdec_launch(omni_jpegdec* d, hipStream_t stream, int n_images, uint8_t* out_dev, int out_stride, int* status_dev) {
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_coef, 0, (size_t)n_images * d->nyb_max * 64 * sizeof(int16_t), stream));
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_dc, 0, (size_t)n_images * d->nyb_max * sizeof(int32_t), stream));
+    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->nyb_max, status_dev, d->d_rounds);
+    OMNI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_dc, d->nyb_max);
+    OMNI_LAUNCH_CHECK();
+    const int raster = cdiv(d->w, 8) * cdiv(d->h, 8);
+    const int per_image = (int)d->nyb_max > raster ? (int)d->nyb_max : raster;
+    hipLaunchKernelGGL(jpegdec_block_kernel, dim3(cdiv(per_image, JD_BLOCK_THREADS), n_images), dim3(JD_BLOCK_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc,
+                       d->nyb_max, status_dev, d->w, d->h, out_dev, (int64_t)out_stride);
+    OMNI_LAUNCH_CHECK();
+    return OMNI_OK;
+}
+
+// Parses the files and fills the handle's pinned block: descriptors | clean scans | host-decoded pixels.  *bytes = what has to be uploaded.  Nothing is touched
+// when a file is refused.
+static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int64_t* sizes, int n_images, size_t* bytes) {
+    std::vector<jd::Desc> descs((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) {
+        OMNI_REQUIRE(files[i] && sizes[i] >= 0, OMNI_ERR_INVALID, "omni_jpegdec: file %d is null", i);
+        jd::Desc& D = descs[(size_t)i];
+        const int st = jd::parse(files[i], sizes[i], &D);
+        OMNI_REQUIRE(st != OMNI_JPEGDEC_UNSUPPORTED, OMNI_ERR_INVALID, "omni_jpegdec: file %d is not a baseline JPEG of 1 or 3 components (UNSUPPORTED)", i);
+        OMNI_REQUIRE((D.w == d->w && D.h == d->h) || (st == OMNI_JPEGDEC_CORRUPT && D.w == 0), OMNI_ERR_INVALID,
+                     "omni_jpegdec: file %d holds a picture of %dx%d, the handle decodes %dx%d", i, D.w, D.h, d->w, d->h);
+        if (st == OMNI_JPEGDEC_OK && (sizes[i] > d->capacity || D.n_yblocks > d->nyb_max)) D.status = OMNI_JPEGDEC_HOST;
+    }
+    if (d->ev_upload) OMNI_HIP_TRY(hipEventSynchronize(d->ev_upload));                        // the last upload has left the pinned block
+    uint8_t* base = d->hin.as<uint8_t>();
+    size_t at = align16((size_t)n_images * sizeof(jd::Desc));
+    for (int i = 0; i < n_images; ++i) {
+        jd::Desc& D = descs[(size_t)i];
+        D.dev_off = (int64_t)at;
+        if (D.status == OMNI_JPEGDEC_OK) {
+            const int64_t n = jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, nullptr, 0, nullptr);
+            D.mode = jd::JD_MODE_DECODE;
+            D.total_bits = (uint32_t)(n * 8);
+            D.subseq_bits = jd::subseq_bits_for(D.total_bits, (uint32_t)d->subseq_bits, JD_MAX_SUBSEQ);
+            D.n_sub = (D.total_bits + D.subseq_bits - 1) / D.subseq_bits;
+            at += align16((size_t)n + JD_SCAN_PAD);
+        } else if (D.status == OMNI_JPEGDEC_HOST) {
+            const int st = jd::decode_sequential(files[i], D, base + at, d->w);
+            D.status = st;
+            D.mode = st == OMNI_JPEGDEC_CORRUPT ? jd::JD_MODE_ZERO : jd::JD_MODE_PIXELS;
+            if (D.mode == jd::JD_MODE_PIXELS) at += align16((size_t)d->w * d->h);
+        } else {
+            D.mode = jd::JD_MODE_ZERO;
+        }
+    }
+    OMNI_REQUIRE(at <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: %zu bytes to upload, the handle holds %zu", at, d->in_bytes);
+    memcpy(base, descs.data(), (size_t)n_images * sizeof(jd::Desc));
+    *bytes = at;
+    return OMNI_OK;
+}
+
+}  // namespace omni
+
+extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int height, int max_images, int64_t capacity_per_image) {
+    using namespace omni;
+    if (!ctx) { set_error("null context"); return nullptr; }
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) { set_error("omni_jpegdec_create: %dx%d outside 1..65535", width, height); return nullptr; }
+    const int64_t nyb = (int64_t)cdiv(width, 16) * cdiv(height, 16) * 4;
+    if (nyb > (1 << 20)) { set_error("omni_jpegdec_create: %dx%d is more than 2^20 blocks", width, height); return nullptr; }
+    if (max_images < 1 || max_images > 65535) { set_error("omni_jpegdec_create: max_images=%d outside [1, 65535]", max_images); return nullptr; }
+    if (capacity_per_image < 1024 || capacity_per_image > (1 << 28)) {
+        set_error("omni_jpegdec_create: a capacity of %lld bytes outside [1024, 2^28]", (long long)capacity_per_image);
+        return nullptr;
+    }
+    Config cfg;
+    if (config_resolve(&cfg) != OMNI_OK) return nullptr;
+    const int S = cfg[CFG_JPEGDEC_SUBSEQ_BITS];
+    if (S & (S - 1)) { set_error("OMNI_JPEGDEC_SUBSEQ_BITS=%d: expected a power of two", S); return nullptr; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    omni_jpegdec* d = new omni_jpegdec();
+    d->ctx = ctx; d->w = width; d->h = height; d->max_images = max_images; d->capacity = capacity_per_image; d->subseq_bits = S; d->nyb_max = (uint32_t)nyb;
+    // per image: a descriptor and the larger of a clean scan and the picture itself
+    const size_t per_scan = align16((size_t)capacity_per_image + JD_SCAN_PAD), per_px = align16((size_t)width * height);
+    d->in_bytes = align16((size_t)max_images * sizeof(jd::Desc)) + (size_t)max_images * (per_scan > per_px ? per_scan : per_px);
+    const size_t coef_bytes = (size_t)max_images * nyb * 64 * sizeof(int16_t), dc_bytes = (size_t)max_images * nyb * sizeof(int32_t);
+    auto make = [&]() -> int {
+        int rc;
+        if ((rc = d->mem.alloc(&d->d_in, d->in_bytes)) || (rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
+            (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_rounds, (size_t)max_images * sizeof(int))))
+            return rc;
+        OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_coef) + coef_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
+        OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_dc) + dc_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
+        OMNI_HIP_TRY(hipMemset(d->d_rounds, 0, (size_t)max_images * sizeof(int)));
+        if ((rc = d->hin.ensure(d->in_bytes))) return rc;
+        OMNI_HIP_TRY(hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming));
+        for (hipEvent_t& e : d->ev_t) OMNI_HIP_TRY(hipEventCreate(&e));
+        return OMNI_OK;
+    };
+    if (make() != OMNI_OK) {
+        d->mem.release_all(); d->hin.release();
+        if (d->ev_upload) (void)hipEventDestroy(d->ev_upload);
+        for (hipEvent_t e : d->ev_t)
+            if (e) (void)hipEventDestroy(e);
+        delete d;
+        return nullptr;
+    }
+    return d;
+}
+
+extern "C" void omni_jpegdec_destroy(omni_jpegdec* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->ctx->device);
+    (void)hipDeviceSynchronize();
+    d->mem.release_all();
+    d->hin.release();
+    if (d->ev_upload) (void)hipEventDestroy(d->ev_upload);
+    for (hipEvent_t e : d->ev_t)
+        if (e) (void)hipEventDestroy(e);
+    delete d;
+}
+
+namespace omni {
+// The whole stage on `stream` (cam.hip: the unit's SuperPoint stream; the caller serialises its use of that stream): parse + pack under the handle's own lock,
+// then upload + kernels.  Refusals come before anything is enqueued.
+int jpegdec_enqueue_on(omni_jpegdec* d, hipStream_t stream, const uint8_t* const* files, const int64_t* sizes, int n_images, uint8_t* out_dev, int out_stride,
+                       int* status_dev) {
+    OMNI_REQUIRE(d && files && sizes && out_dev && status_dev, OMNI_ERR_INVALID, "null argument");
+    OMNI_REQUIRE(n_images >= 1 && n_images <= d->max_images, OMNI_ERR_INVALID, "omni_jpegdec: %d images, the handle holds 1..%d", n_images, d->max_images);
+    OMNI_REQUIRE(out_stride >= d->w, OMNI_ERR_INVALID, "omni_jpegdec: out_stride %d for pictures %d wide", out_stride, d->w);
+    std::lock_guard<std::mutex> lk(d->mu);
+    (void)hipSetDevice(d->ctx->device);
+    size_t bytes = 0;
+    int rc;
+    if ((rc = jpegdec_pack(d, files, sizes, n_images, &bytes))) return rc;
+    d->timed = false;                                                                       // (until this call's three events are all recorded)
+    OMNI_HIP_TRY(hipEventRecord(d->ev_t[0], stream));
+    OMNI_HIP_TRY(hipMemcpyAsync(d->d_in, d->hin.p, bytes, hipMemcpyHostToDevice, stream));
+    OMNI_HIP_TRY(hipEventRecord(d->ev_upload, stream));
+    OMNI_HIP_TRY(hipEventRecord(d->ev_t[1], stream));
+    d->last_n = n_images;
+    d->last_bytes = bytes;
+    if ((rc = jpegdec_launch(d, stream, n_images, out_dev, out_stride, status_dev))) return rc;
+    OMNI_HIP_TRY(hipEventRecord(d->ev_t[2], stream));
+    d->timed = true;
+    return OMNI_OK;
+}
+}  // namespace omni
+
+extern "C" int omni_jpegdec_enqueue_host(omni_jpegdec* d, const uint8_t* const* files, const int64_t* sizes, int n_images, uint8_t* out_dev, int out_stride,
+                                         int* status_dev) {
+    OMNI_REQUIRE(d, OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("jpeg decode (camera frames)");
+    return omni::jpegdec_enqueue_on(d, d->ctx->stream, files, sizes, n_images, out_dev, out_stride, status_dev);
+}
+
+extern "C" int omni_jpegdec_last_ms(omni_jpegdec* d, float* upload_ms, float* kernels_ms, int64_t* uploaded_bytes) {
+    OMNI_REQUIRE(d && upload_ms && kernels_ms && uploaded_bytes, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(d->mu);
+    OMNI_REQUIRE(d->last_n > 0 && d->timed, OMNI_ERR_INVALID, "omni_jpegdec_last_ms: no enqueue of this handle has run to its end");
+    (void)hipSetDevice(d->ctx->device);
+    OMNI_HIP_TRY(hipEventSynchronize(d->ev_t[2]));
+    OMNI_HIP_TRY(hipEventElapsedTime(upload_ms, d->ev_t[0], d->ev_t[1]));
+    OMNI_HIP_TRY(hipEventElapsedTime(kernels_ms, d->ev_t[1], d->ev_t[2]));
+    *uploaded_bytes = (int64_t)d->last_bytes;
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subseq, int* subseq_bits) {
+    OMNI_REQUIRE(d, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(d->mu);
+    (void)hipSetDevice(d->ctx->device);
+    OMNI_HIP_TRY(hipDeviceSynchronize());                                                     // (the last enqueue may have run on a unit's stream)
+    if (rounds && d->last_n) OMNI_HIP_TRY(hipMemcpy(rounds, d->d_rounds, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+    const omni::jd::Desc* descs = d->hin.as<omni::jd::Desc>();                                // (the pinned block still holds the last enqueue's descriptors)
+    for (int i = 0; i < d->last_n; ++i) {
+        const bool dec = descs[i].mode == omni::jd::JD_MODE_DECODE;
+        if (n_subseq) n_subseq[i] = dec ? (int)descs[i].n_sub : 0;
+        if (subseq_bits) subseq_bits[i] = dec ? (int)descs[i].subseq_bits : 0;
+    }
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_debug_buffers(omni_jpegdec* d, void** coef_dev, int64_t* coef_bytes, void** dc_dev, int64_t* dc_bytes) {
+    OMNI_REQUIRE(d && coef_dev && coef_bytes && dc_dev && dc_bytes, OMNI_ERR_INVALID, "null argument");
+    *coef_dev = d->d_coef; *coef_bytes = (int64_t)d->max_images * d->nyb_max * 64 * (int64_t)sizeof(int16_t);
+    *dc_dev = d->d_dc; *dc_bytes = (int64_t)d->max_images * d->nyb_max * (int64_t)sizeof(int32_t);
+    return OMNI_OK;
+}

@@ -1,0 +1,634 @@
+// jpeg_dec_plan.h -- the gray image of a baseline JPEG file, stated once: what cv::imdecode(data, cv::IMREAD_GRAYSCALE) asks of libjpeg for every frame of a
+// CompressedImage topic when is_compressed_images is set (swarm_loop/src/swarm_loop.cpp:72-89, 291-292, 341-360; loop_utils.cpp:8).  Plain C++ for g++ AND
+// hipcc: jpeg_dec.hip runs the phase functions lane-wise, jpeg_dec_host.cpp compiles the host decoders into the library, tests/cpp/jpegdec_plan_pin.cpp runs
+// them on the host; nothing else restates the arithmetic.  Integers only.
+//
+// PINNED: libjpeg-turbo's output for out_color_space = JCS_GRAYSCALE, JDCT_ISLOW -- the FIRST component alone, dequantised, jidctint.c's islow IDCT, range
+// limit -- as Pillow gives it (Image.open(..).convert-free 'L' files; Image.draft('L', size) for colour files): tests/test_jpegdec_plan_cpu.py compares every
+// pixel.  UNPINNED: cv::imdecode itself (OpenCV is not vendored); that it asks libjpeg for JCS_GRAYSCALE is read from knowledge, not run.
+//
+//   parser     SOI, APPn / COM (skipped), DQT (8-bit tables), SOF0, DHT (any tables), DRI, SOS, EOI -> Desc: sizes, MCU layout, the first component's
+//              quantisation table, the Huffman tables of the scan that holds the first component, that scan's byte range, and the classification
+//                OK           the device decodes it
+//                HOST         a valid baseline file the device does not take: restart interval != 0, more than one scan, a first component sampled other
+//                             than {1,2} x {1,2} or other components other than 1 x 1 (the caller adds: a file above the handle's capacity)
+//                UNSUPPORTED  progressive, arithmetic, lossless, extended / 12-bit, 16-bit quantisation tables, a component count other than 1 or 3, a first
+//                             component sampled below another one
+//                CORRUPT      anything else that cannot be a file
+//   bytes      0xFF00 unstuffing and the end at a marker happen in a FIRST PASS on the host (unstuff): the scan the decoders and the kernels read is the
+//              clean bit stream, MSB first, followed by >= JD_SCAN_PAD zero bytes.  Restart markers become a list of byte offsets (host decoder only)
+//   symbol     step(): ONE total function (bit position, z = next zig-zag index 0..63, b = block within the MCU) -> next state, at most one (block, natural
+//              index, value) emission, an error flag.  z == 0: a DC category + value bits; else an AC (run, size): ZRL (z += 16; reaching 64 ends the block, as
+//              libjpeg's loop does), EOB, value extension as in jpeg_plan.h.  Defined for EVERY bit pattern: an undefined code is 1 bit long and reads as symbol
+//              0 (+ error); a run past 63 ends the block without emission (+ error); EOBn with n > 0 ends the block (+ error); bits past the end of the data
+//              read as 0 (+ error).  Every step consumes at least one bit.  Only an error on the TRUE chain, before the picture's last block, means CORRUPT
+//   subseq     decode_subseq(i, entry) over the symbols that START in bits [i S, (i + 1) S): -> exit state (the overhang into i + 1: 0..30 bits, z, b; 16 bits),
+//              blocks completed, error
+//   parallel   1  every subsequence from the guess (overhang 0, z 0, b 0)
+//              2  relaxation rounds (Jacobi): subsequence i >= 1 again from the exit state of i - 1 whenever that differs from the entry it last used, until a
+//                 round changes nothing.  After round r the first r + 1 subsequences are final: N rounds bound it, and the fixed point IS the sequential decode
+//              3  exclusive scan of the block counts = every subsequence's first block
+//              4  write pass: the first component's AC coefficients (int16, natural order, into a zeroed array, blocks in SCAN order) and DC differences
+//                 (int32); other components are decoded and dropped.  Stops at the picture's last block; the error flag counts only up to there
+//              5  inclusive scan of the DC differences in scan order (mod 2^32) = the DC values
+//              6  per 8 x 8 block: dequantise, islow IDCT (CONST_BITS 13, PASS1_BITS 2; columns first with descale 11, rows with descale 18 -- the +128 level
+//                 shift and the final >> 3 in one), clamp to 0..255, store cropped to width x height.  All in uint32 arithmetic (= two's complement int32,
+//                 no overflow to be undefined for ANY coefficients); libjpeg's all-zero-AC column shortcut is arithmetically the same and is not restated
+//   CORRUPT    the picture is all zeros
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "jpeg_plan.h"
+
+#define JD_SCAN_PAD 16                                       // zero bytes behind a clean scan: the bit window reads up to 12 bytes past the last symbol
+#define JD_MAX_BPM 10                                        // blocks per MCU (the standard's limit)
+#define JD_MIN_SUBSEQ_BITS 128
+#define JD_MAX_SUBSEQ_BITS 65536
+
+namespace omni {
+namespace jd {
+
+// a Huffman table in the form the kernel reads: a first level over the next 8 bits, then Annex F's canonical walk for codes of 9..16 bits
+struct HuffTab {
+    uint16_t look[256];                                     // length << 8 | symbol of the code that starts these 8 bits; 0: longer than 8 bits, or none
+    int32_t maxcode[17];                                    // [l]: the largest code of l bits, -1: none
+    int32_t valoff[17];                                     // [l]: index of the first symbol of l bits - the smallest code of l bits
+    uint8_t vals[256];
+};
+// what step() reads (the kernel keeps it in LDS)
+struct Tables {
+    int32_t bpm, ny;                                        // blocks per MCU; of which the first ny belong to the first component
+    uint8_t blk_comp[JD_MAX_BPM + 2];                       // block of the MCU -> component of the scan (0: the first)
+    uint8_t zz[64];                                         // zig-zag index -> natural index
+    HuffTab dc[3], ac[3];                                   // per component of the scan
+};
+struct Desc {
+    int32_t status;                                         // OMNI_JPEGDEC_*
+    int32_t w, h, ncomp, hs, vs;                            // hs x vs: the first component's blocks per MCU
+    int32_t mcus_x, mcus_y, restart, multi_scan;
+    uint32_t n_blocks, n_yblocks;                           // of the scan; of the first component (MCU padding included)
+    int64_t scan_off, scan_bytes;                           // the scan's bytes in the file (stuffed, restart markers included)
+    // filled by whoever packs the image for the kernels (jpeg_dec.hip)
+    int32_t mode;                                           // JD_MODE_*
+    uint32_t total_bits, subseq_bits, n_sub;
+    int64_t dev_off;                                        // MODE_DECODE: the clean scan, MODE_PIXELS: w x h pixels -- byte offset inside the uploaded block
+    uint16_t q[64];                                         // the first component's quantisation table, natural order
+    Tables T;
+};
+enum { JD_MODE_DECODE = 0, JD_MODE_PIXELS = 1, JD_MODE_ZERO = 2 };
+
+// ---- parser (host) -----------------------------------------------------------------------------------------------------------------------------------
+inline int build_hufftab(const uint8_t* bits, const uint8_t* vals, bool dc, HuffTab* t) {
+    memset(t, 0, sizeof(*t));
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int n = bits[l - 1];
+        t->maxcode[l] = -1;
+        if (n) {
+            if (code + n > (1 << l) || k + n > 256) return 1;
+            t->valoff[l] = k - code;
+            t->maxcode[l] = code + n - 1;
+            if (l <= 8)
+                for (int j = 0; j < n; ++j)
+                    for (int f = 0; f < (1 << (8 - l)); ++f) t->look[((code + j) << (8 - l)) + f] = (uint16_t)(l << 8 | vals[k + j]);
+        }
+        k += n;
+        code = (code + n) << 1;
+    }
+    for (int i = 0; i < k; ++i) {
+        if (dc && vals[i] > 15) return 1;
+        t->vals[i] = vals[i];
+    }
+    return 0;
+}
+
+// the end of the entropy-coded data that starts at p: the first marker that is neither a stuffed 0xFF00 nor a restart marker (or the end of the file)
+inline int64_t scan_end(const uint8_t* f, int64_t size, int64_t p) {
+    while (p < size) {
+        if (f[p] != 0xff) { ++p; continue; }
+        int64_t q = p + 1;
+        while (q < size && f[q] == 0xff) ++q;
+        if (q >= size) return size;
+        if (f[q] == 0 || (f[q] >= 0xd0 && f[q] <= 0xd7)) { p = q + 1; continue; }
+        return p;
+    }
+    return size;
+}
+
+// The descriptor of a file.  Returns d->status; d->w / d->h are the frame's size as soon as a frame header was read (0 before).
+inline int parse(const uint8_t* f, int64_t size, Desc* d) {
+    memset(d, 0, sizeof(*d));
+    d->status = OMNI_JPEGDEC_CORRUPT;
+    d->dev_off = -1;
+    if (!f || size < 4 || f[0] != 0xff || f[1] != 0xd8) return d->status;
+    uint8_t qt[4][64], hbits[2][4][16], hvals[2][4][256];
+    bool qset[4] = {false, false, false, false}, hset[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    int cid[3] = {0, 0, 0}, ch[3] = {0, 0, 0}, cv[3] = {0, 0, 0}, ctq[3] = {0, 0, 0};
+    bool frame = false;
+    int64_t p = 2;
+    auto fail = [&](int st) { d->status = st; return st; };
+    for (;;) {
+        if (p >= size || f[p] != 0xff) return fail(OMNI_JPEGDEC_CORRUPT);
+        while (p < size && f[p] == 0xff) ++p;
+        if (p >= size) return fail(OMNI_JPEGDEC_CORRUPT);
+        const int m = f[p++];
+        if (m == 0xd8 || m == 0x01 || (m >= 0xd0 && m <= 0xd7)) continue;
+        if (m == 0xd9 || m == 0x00) return fail(OMNI_JPEGDEC_CORRUPT);                      // no scan holds the first component
+        if (p + 2 > size) return fail(OMNI_JPEGDEC_CORRUPT);
+        const int64_t len = (int64_t)f[p] << 8 | f[p + 1];
+        if (len < 2 || p + len > size) return fail(OMNI_JPEGDEC_CORRUPT);
+        const uint8_t* s = f + p + 2;
+        const int64_t n = len - 2;
+        if (m == 0xdb) {                                                                   // DQT
+            int64_t i = 0;
+            while (i < n) {
+                const int pq = s[i] >> 4, tq = s[i] & 15;
+                if (tq > 3) return fail(OMNI_JPEGDEC_CORRUPT);
+                if (pq == 1) return fail(OMNI_JPEGDEC_UNSUPPORTED);
+                if (pq != 0 || i + 65 > n) return fail(OMNI_JPEGDEC_CORRUPT);
+                for (int k = 0; k < 64; ++k) qt[tq][jp::kZigzag[k]] = s[i + 1 + k];
+                qset[tq] = true;
+                i += 65;
+            }
+        } else if (m == 0xc4) {                                                            // DHT
+            int64_t i = 0;
+            while (i < n) {
+                const int tc = s[i] >> 4, th = s[i] & 15;
+                if (tc > 1 || th > 3 || i + 17 > n) return fail(OMNI_JPEGDEC_CORRUPT);
+                int cnt = 0;
+                for (int k = 0; k < 16; ++k) cnt += s[i + 1 + k];
+                if (cnt > 256 || i + 17 + cnt > n) return fail(OMNI_JPEGDEC_CORRUPT);
+                memcpy(hbits[tc][th], s + i + 1, 16);
+                memset(hvals[tc][th], 0, 256);
+                memcpy(hvals[tc][th], s + i + 17, (size_t)cnt);
+                hset[tc][th] = true;
+                i += 17 + cnt;
+            }
+        } else if (m == 0xc0) {                                                            // SOF0
+            if (frame || n < 6) return fail(OMNI_JPEGDEC_CORRUPT);
+            if (s[0] != 8) return fail(OMNI_JPEGDEC_UNSUPPORTED);
+            d->h = s[1] << 8 | s[2];
+            d->w = s[3] << 8 | s[4];
+            d->ncomp = s[5];
+            if (d->w < 1 || d->h < 1) { d->w = d->h = 0; return fail(OMNI_JPEGDEC_CORRUPT); }
+            if (d->ncomp != 1 && d->ncomp != 3) return fail(OMNI_JPEGDEC_UNSUPPORTED);
+            if (n < 6 + 3 * d->ncomp) return fail(OMNI_JPEGDEC_CORRUPT);
+            for (int c = 0; c < d->ncomp; ++c) {
+                cid[c] = s[6 + 3 * c];
+                ch[c] = s[7 + 3 * c] >> 4;
+                cv[c] = s[7 + 3 * c] & 15;
+                ctq[c] = s[8 + 3 * c];
+                if (ch[c] < 1 || ch[c] > 4 || cv[c] < 1 || cv[c] > 4 || ctq[c] > 3) return fail(OMNI_JPEGDEC_CORRUPT);
+                if (ch[c] > ch[0] || cv[c] > cv[0]) return fail(OMNI_JPEGDEC_UNSUPPORTED);
+            }
+            frame = true;
+        } else if (m >= 0xc1 && m <= 0xcf) {                                               // every other frame type, DAC (0xc8 is reserved)
+            return fail(m == 0xc8 ? OMNI_JPEGDEC_CORRUPT : OMNI_JPEGDEC_UNSUPPORTED);
+        } else if (m == 0xdd) {                                                            // DRI
+            if (n < 2) return fail(OMNI_JPEGDEC_CORRUPT);
+            d->restart = s[0] << 8 | s[1];
+        } else if (m == 0xda) {                                                            // SOS
+            if (!frame || n < 1) return fail(OMNI_JPEGDEC_CORRUPT);
+            const int ns = s[0];
+            if (ns < 1 || ns > d->ncomp || n < 1 + 2 * ns + 3) return fail(OMNI_JPEGDEC_CORRUPT);
+            if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0) return fail(OMNI_JPEGDEC_CORRUPT);
+            const int64_t start = p + len, end = scan_end(f, size, start);
+            if (s[1] != cid[0]) {                                                          // a scan without the first component: skipped
+                d->multi_scan = 1;
+                p = end;
+                continue;
+            }
+            Tables& T = d->T;
+            int at = 0, comp_of[3] = {0, 0, 0};
+            for (int j = 0; j < ns; ++j) {
+                int c = -1;
+                for (int k = 0; k < d->ncomp; ++k)
+                    if (cid[k] == s[1 + 2 * j]) c = k;
+                if (c < j) return fail(OMNI_JPEGDEC_CORRUPT);                              // (unknown, or out of the frame's order)
+                comp_of[j] = c;
+                const int td = s[2 + 2 * j] >> 4, ta = s[2 + 2 * j] & 15;
+                if (td > 3 || ta > 3 || !hset[0][td] || !hset[1][ta]) return fail(OMNI_JPEGDEC_CORRUPT);
+                if (build_hufftab(hbits[0][td], hvals[0][td], true, &T.dc[j]) || build_hufftab(hbits[1][ta], hvals[1][ta], false, &T.ac[j]))
+                    return fail(OMNI_JPEGDEC_CORRUPT);
+                const int nb = ns == 1 ? 1 : ch[c] * cv[c];                                // (a scan of one component is not interleaved: one block per MCU)
+                if (at + nb > JD_MAX_BPM) return fail(OMNI_JPEGDEC_CORRUPT);
+                for (int k = 0; k < nb; ++k) T.blk_comp[at++] = (uint8_t)j;
+            }
+            if (!qset[ctq[0]]) return fail(OMNI_JPEGDEC_CORRUPT);
+            for (int k = 0; k < 64; ++k) {
+                d->q[k] = qt[ctq[0]][k];
+                T.zz[k] = jp::kZigzag[k];
+            }
+            d->hs = ns == 1 ? 1 : ch[0];
+            d->vs = ns == 1 ? 1 : cv[0];
+            T.bpm = at;
+            T.ny = d->hs * d->vs;
+            d->mcus_x = (d->w + 8 * d->hs - 1) / (8 * d->hs);                              // (the first component has the frame's largest factors)
+            d->mcus_y = (d->h + 8 * d->vs - 1) / (8 * d->vs);
+            d->n_blocks = (uint32_t)d->mcus_x * d->mcus_y * at;
+            d->n_yblocks = (uint32_t)d->mcus_x * d->mcus_y * T.ny;
+            d->scan_off = start;
+            d->scan_bytes = end - start;
+            if (ns < d->ncomp) d->multi_scan = 1;
+            bool dev = d->restart == 0 && !d->multi_scan && d->hs <= 2 && d->vs <= 2;
+            for (int j = 1; j < ns; ++j) dev = dev && ch[comp_of[j]] == 1 && cv[comp_of[j]] == 1;
+            return fail(dev ? OMNI_JPEGDEC_OK : OMNI_JPEGDEC_HOST);
+        }
+        // APPn, COM and anything else with a length: skipped
+        p += len;
+    }
+}
+
+// scan[0..n) of the file -> the clean bytes at out (room for n + JD_SCAN_PAD), JD_SCAN_PAD zero bytes behind them.  Returns their number.  rst (or null): the
+// clean byte offset behind every restart marker, at most max_rst of them, *n_rst their number
+inline int64_t unstuff(const uint8_t* s, int64_t n, uint8_t* out, int64_t* rst, int64_t max_rst, int64_t* n_rst) {
+    int64_t i = 0, o = 0, r = 0;
+    while (i < n) {
+        const uint8_t c = s[i++];
+        if (c != 0xff) { out[o++] = c; continue; }
+        while (i < n && s[i] == 0xff) ++i;
+        if (i >= n) break;
+        const uint8_t m = s[i++];
+        if (m == 0) out[o++] = 0xff;
+        else if (m >= 0xd0 && m <= 0xd7) { if (rst && r < max_rst) rst[r++] = o; }
+        else break;
+    }
+    memset(out + o, 0, JD_SCAN_PAD);
+    if (n_rst) *n_rst = r;
+    return o;
+}
+
+// ---- the bit reader: a 64-bit window over the clean scan (host and device) -----------------------------------------------------------------------------
+JP_HD uint32_t be32(const uint8_t* s, uint32_t word, uint32_t n_words) {                    // word `word` of the scan, MSB first; 0 beyond the padded scan
+    if (word >= n_words) return 0u;
+    const uint32_t v = reinterpret_cast<const uint32_t*>(s)[word];                         // (the scan starts on a 4-byte boundary)
+    return __builtin_bswap32(v);
+}
+struct Bits {
+    const uint8_t* s;
+    uint32_t n_words, pos, next;                            // pos: the bit the window starts at; next: the word to load
+    uint64_t win;                                           // `have` valid bits, left-aligned
+    int have;
+    JP_HD void init(const uint8_t* scan, uint32_t words, uint32_t bit) {
+        s = scan; n_words = words; pos = bit;
+        const uint32_t w0 = bit >> 5, sh = bit & 31;
+        win = ((uint64_t)be32(s, w0, n_words) << 32 | be32(s, w0 + 1, n_words)) << sh;
+        have = 64 - (int)sh;
+        next = w0 + 2;
+    }
+    JP_HD uint32_t peek32() const { return (uint32_t)(win >> 32); }                         // (have >= 32 always)
+    JP_HD void skip(int n) {                                                                // n <= 31
+        win <<= n; have -= n; pos += (uint32_t)n;
+        if (have < 32) {
+            win |= (uint64_t)be32(s, next++, n_words) << (32 - have);
+            have += 32;
+        }
+    }
+};
+// words a clean scan of `bytes` bytes occupies with its padding
+JP_HD uint32_t scan_words(int64_t bytes) { return (uint32_t)((bytes + JD_SCAN_PAD) >> 2); }
+
+// ---- the symbol step -------------------------------------------------------------------------------------------------------------------------------------
+#define JD_STEP_ERR 1
+#define JD_STEP_BLOCK 2
+// em.put(block of the MCU, natural index, value).  Returns JD_STEP_ERR | JD_STEP_BLOCK (a block was completed)
+template <class Emit>
+JP_HD int step(const Tables& T, Bits& br, uint32_t total_bits, int& z, int& b, Emit& em) {
+    const uint32_t v = br.peek32();
+    const int comp = T.blk_comp[b];
+    const HuffTab& t = z == 0 ? T.dc[comp] : T.ac[comp];
+    int len = 0, sym = 0, res = 0;
+    const uint32_t e = t.look[v >> 24];
+    if (e) {
+        len = (int)(e >> 8); sym = (int)(e & 255);
+    } else {
+        for (int l = 9; l <= 16; ++l) {
+            const int code = (int)(v >> (32 - l));
+            if (code <= t.maxcode[l]) { len = l; sym = t.vals[(code + t.valoff[l]) & 255]; break; }
+        }
+        if (!len) { len = 1; sym = 0; res = JD_STEP_ERR; }
+    }
+    const int n = sym & 15;
+    const int r = n ? (int)((v << len) >> (32 - n)) : 0;
+    const int val = n ? (r < (1 << (n - 1)) ? r - (1 << n) + 1 : r) : 0;
+    if (br.pos + (uint32_t)(len + n) > total_bits) res = JD_STEP_ERR;
+    br.skip(len + n);
+    if (z == 0) {
+        em.put(b, 0, val);
+        z = 1;
+    } else {
+        const int run = sym >> 4;
+        if (n == 0) {
+            if (run == 15) z += 16;
+            else { if (run) res = JD_STEP_ERR; z = 64; }
+        } else {
+            z += run;
+            if (z > 63) { res = JD_STEP_ERR; z = 64; }
+            else { em.put(b, T.zz[z], val); ++z; }
+        }
+    }
+    if (z >= 64) {
+        z = 0;
+        b = b + 1 >= T.bpm ? 0 : b + 1;
+        em.next_block();
+        res |= JD_STEP_BLOCK;
+    }
+    return res;
+}
+
+// ---- subsequences ------------------------------------------------------------------------------------------------------------------------------------------
+// a state between two subsequences: overhang (bits of the last symbol of i that lie in i + 1) | z << 6 | b << 12.  0: the guess
+JP_HD uint16_t pack_state(uint32_t ov, int z, int b) { return (uint16_t)(ov | (uint32_t)z << 6 | (uint32_t)b << 12); }
+struct NoEmit {
+    JP_HD void put(int, int, int) {}
+    JP_HD void next_block() {}
+};
+// The first component's coefficients into coef[block in scan order][64] (zeroed by the caller) and DC differences into dcd[block in scan order]; nothing is
+// stored at or beyond block n_yblocks
+struct CoefEmit {
+    int16_t* coef;
+    int32_t* dcd;
+    uint32_t n_yblocks, ybase;                              // ybase: the first block of the first component in the current MCU
+    int ny, bpm, b;
+    JP_HD void start(const Tables& T, uint32_t first_block, int entry_b) {
+        ny = T.ny; bpm = T.bpm; b = entry_b;
+        ybase = first_block / (uint32_t)bpm * (uint32_t)ny;
+    }
+    JP_HD void put(int blk, int nat, int val) {
+        const uint32_t y = ybase + (uint32_t)blk;
+        if (blk >= ny || y >= n_yblocks) return;
+        if (nat == 0) dcd[y] = val;
+        else coef[(size_t)y * 64 + nat] = (int16_t)val;
+    }
+    JP_HD void next_block() {
+        if (++b >= bpm) { b = 0; ybase += (uint32_t)ny; }
+    }
+};
+// Subsequence i from `entry`: the symbols that start in [i S + overhang, min((i + 1) S, total_bits)), and none once first_block + (blocks completed) reaches
+// max_blocks.  Returns the blocks completed; *exit_state, *err (any JD_STEP_ERR among its steps)
+template <class Emit>
+JP_HD uint32_t decode_subseq(const Tables& T, const uint8_t* scan, uint32_t n_words, uint32_t total_bits, uint32_t i, uint32_t S, uint16_t entry, uint32_t first_block,
+                             uint32_t max_blocks, Emit& em, uint16_t* exit_state, int* err) {
+    const uint32_t bound = (i + 1) * S, end = bound < total_bits ? bound : total_bits;
+    int z = (entry >> 6) & 63, b = entry >> 12, e = 0;
+    uint32_t blocks = 0;
+    Bits br;
+    br.init(scan, n_words, i * S + (entry & 63u));
+    while (br.pos < end && first_block + blocks < max_blocks) {
+        const int r = step(T, br, total_bits, z, b, em);
+        e |= r & JD_STEP_ERR;
+        blocks += (uint32_t)(r >> 1);
+    }
+    *exit_state = pack_state(br.pos > bound ? br.pos - bound : 0u, z, b);
+    *err = e;
+    return blocks;
+}
+// the subsequence length an image is decoded with: the configured one, doubled until there are at most max_sub subsequences
+JP_HD uint32_t subseq_bits_for(uint32_t total_bits, uint32_t S, uint32_t max_sub) {
+    while (S < (1u << 30) && (total_bits + S - 1) / S > max_sub) S <<= 1;
+    return S;
+}
+
+// ---- the block: dequantise, islow IDCT, level shift, clamp ---------------------------------------------------------------------------------------------------
+JP_HD int32_t jd_descale(uint32_t x, int n) { return (int32_t)(x + (1u << (n - 1))) >> n; }
+// one pass of jidctint.c over 8 values (stride st) of in -> out
+template <int kShift>
+JP_HD void idct_1d(const uint32_t* in, uint32_t* out, int st) {
+    uint32_t z2 = in[2 * st], z3 = in[6 * st];
+    uint32_t z1 = (z2 + z3) * 4433u;
+    uint32_t tmp2 = z1 + z3 * (uint32_t)(-15137), tmp3 = z1 + z2 * 6270u;
+    z2 = in[0]; z3 = in[4 * st];
+    uint32_t tmp0 = (z2 + z3) << 13, tmp1 = (z2 - z3) << 13;
+    const uint32_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = in[7 * st]; tmp1 = in[5 * st]; tmp2 = in[3 * st]; tmp3 = in[st];
+    z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
+    uint32_t z4 = tmp1 + tmp3;
+    const uint32_t z5 = (z3 + z4) * 9633u;
+    tmp0 *= 2446u; tmp1 *= 16819u; tmp2 *= 25172u; tmp3 *= 12299u;
+    z1 *= (uint32_t)(-7373); z2 *= (uint32_t)(-20995); z3 *= (uint32_t)(-16069); z4 *= (uint32_t)(-3196);
+    z3 += z5; z4 += z5;
+    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+    out[0] = (uint32_t)jd_descale(tmp10 + tmp3, kShift);
+    out[7 * st] = (uint32_t)jd_descale(tmp10 - tmp3, kShift);
+    out[st] = (uint32_t)jd_descale(tmp11 + tmp2, kShift);
+    out[6 * st] = (uint32_t)jd_descale(tmp11 - tmp2, kShift);
+    out[2 * st] = (uint32_t)jd_descale(tmp12 + tmp1, kShift);
+    out[5 * st] = (uint32_t)jd_descale(tmp12 - tmp1, kShift);
+    out[3 * st] = (uint32_t)jd_descale(tmp13 + tmp0, kShift);
+    out[4 * st] = (uint32_t)jd_descale(tmp13 - tmp0, kShift);
+}
+// coef: a block's 64 coefficients in natural order ([0] is not read), dc its DC value, q the table -> rows[j]: row j's 8 pixels, pixel i in bits 8 i
+JP_HD void idct_block(const int16_t* coef, int32_t dc, const uint16_t* q, uint64_t* rows) {
+    uint32_t ws[64];
+    JP_UNROLL
+    for (int i = 0; i < 64; ++i) ws[i] = (uint32_t)(int32_t)(i == 0 ? dc : (int32_t)coef[i]) * (uint32_t)q[i];
+    JP_UNROLL
+    for (int c = 0; c < 8; ++c) idct_1d<11>(ws + c, ws + c, 8);
+    JP_UNROLL
+    for (int r = 0; r < 8; ++r) {
+        idct_1d<18>(ws + 8 * r, ws + 8 * r, 1);
+        uint64_t row = 0;
+        JP_UNROLL
+        for (int i = 0; i < 8; ++i) {
+            const int32_t v = (int32_t)ws[8 * r + i] + 128;
+            row |= (uint64_t)(v < 0 ? 0 : v > 255 ? 255 : v) << (8 * i);
+        }
+        rows[r] = row;
+    }
+}
+// where block y of the first component (scan order) lies in the picture, in blocks
+JP_HD void yblock_pos(uint32_t y, int hs, int vs, int mcus_x, int* bx, int* by) {
+    const uint32_t ny = (uint32_t)(hs * vs), mcu = y / ny, k = y % ny;
+    *bx = (int)(mcu % (uint32_t)mcus_x) * hs + (int)(k % (uint32_t)hs);
+    *by = (int)(mcu / (uint32_t)mcus_x) * vs + (int)(k / (uint32_t)hs);
+}
+// block (bx, by)'s rows into the picture, cropped to w x h
+JP_HD void store_block(const uint64_t* rows, uint8_t* out, int64_t stride, int w, int h, int bx, int by) {
+    JP_UNROLL
+    for (int j = 0; j < 8; ++j) {
+        const int y = by * 8 + j;
+        if (y >= h) break;
+        uint8_t* o = out + (int64_t)y * stride + bx * 8;
+        if (bx * 8 + 8 <= w && ((uintptr_t)o & 7) == 0) {
+            *reinterpret_cast<uint64_t*>(o) = rows[j];
+        } else {
+            for (int i = 0; i < 8 && bx * 8 + i < w; ++i) o[i] = (uint8_t)(rows[j] >> (8 * i));
+        }
+    }
+}
+// phases 5 + 6 for block y, given the scanned DC values
+JP_HD void block_out(const Desc& d, const int16_t* coef, const int32_t* dcv, uint32_t y, bool zero, uint8_t* out, int64_t stride) {
+    int bx, by;
+    yblock_pos(y, d.hs, d.vs, d.mcus_x, &bx, &by);
+    if (bx * 8 >= d.w || by * 8 >= d.h) return;                                            // MCU padding
+    uint64_t rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!zero) idct_block(coef + (size_t)y * 64, dcv[y], d.q, rows);
+    store_block(rows, out, stride, d.w, d.h, bx, by);
+}
+
+}  // namespace jd
+}  // namespace omni
+
+// ---- the host decoders (they allocate) -----------------------------------------------------------------------------------------------------------------------
+#include <vector>
+namespace omni {
+namespace jd {
+
+inline void zero_picture(uint8_t* out, int64_t stride, int w, int h) {
+    for (int y = 0; y < h; ++y) memset(out + (int64_t)y * stride, 0, (size_t)w);
+}
+
+// The sequential decoder of a parsed file (status OK or HOST): restart intervals included.  out: d.w x d.h pixels, `stride` bytes between rows.  Returns
+// d.status, or OMNI_JPEGDEC_CORRUPT with the picture all zeros.
+inline int decode_sequential(const uint8_t* file, const Desc& d, uint8_t* out, int64_t stride) {
+    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
+    std::vector<int64_t> rst((size_t)(d.scan_bytes / 2 + 1));
+    int64_t n_rst = 0;
+    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), rst.data(), (int64_t)rst.size(), &n_rst);
+    const uint32_t total_bits = (uint32_t)(nclean * 8), n_words = scan_words(nclean);
+    struct BlockEmit {
+        int16_t blk[64];
+        int32_t diff;
+        int ny;
+        void put(int b, int nat, int val) {
+            if (b >= ny) return;
+            if (nat == 0) diff = val;
+            else blk[nat] = (int16_t)val;
+        }
+        void next_block() {}
+    } em;
+    memset(em.blk, 0, sizeof(em.blk));
+    em.diff = 0; em.ny = d.T.ny;
+    Bits br;
+    br.init(clean.data(), n_words, 0);
+    int z = 0, b = 0, err = 0;
+    uint32_t g = 0, pred = 0, ybase = 0;
+    int64_t seg = 0;
+    const uint32_t per_restart = d.restart ? (uint32_t)d.restart * (uint32_t)d.T.bpm : 0u;
+    while (g < d.n_blocks) {
+        if (br.pos >= total_bits) { err = 1; break; }
+        const int blk = b;
+        const int r = step(d.T, br, total_bits, z, b, em);
+        err |= r & JD_STEP_ERR;
+        if (!(r & JD_STEP_BLOCK)) continue;
+        if (blk < d.T.ny) {
+            pred += (uint32_t)em.diff;
+            uint64_t rows[8];
+            idct_block(em.blk, (int32_t)pred, d.q, rows);
+            int bx, by;
+            yblock_pos(ybase + (uint32_t)blk, d.hs, d.vs, d.mcus_x, &bx, &by);
+            if (bx * 8 < d.w && by * 8 < d.h) store_block(rows, out, stride, d.w, d.h, bx, by);
+            memset(em.blk, 0, sizeof(em.blk));
+            em.diff = 0;
+        }
+        ++g;
+        if (b == 0) ybase += (uint32_t)d.T.ny;
+        if (per_restart && g < d.n_blocks && g % per_restart == 0) {                        // the next interval starts behind the next restart marker
+            if (seg >= n_rst) { err = 1; break; }
+            br.init(clean.data(), n_words, (uint32_t)(rst[(size_t)seg++] * 8));
+            z = 0; b = 0; pred = 0;
+        }
+    }
+    if (err) {
+        zero_picture(out, stride, d.w, d.h);
+        return OMNI_JPEGDEC_CORRUPT;
+    }
+    return d.status;
+}
+
+// file -> gray picture.  *w, *h: the frame's size (0 x 0 when no frame header could be read).  out may be null (classification only); otherwise it has room for
+// the picture at `stride` >= *w ... which the caller can only know from a first call: max_w / max_h bound what is written (a larger picture: -1).
+// Returns OMNI_JPEGDEC_OK / HOST (decoded), UNSUPPORTED (nothing written), CORRUPT (zeros when the size is known).
+inline int jpeg_decode_host(const uint8_t* file, int64_t size, uint8_t* out, int64_t stride, int max_w, int max_h, int* w, int* h) {
+    Desc d;
+    const int st = parse(file, size, &d);
+    if (w) *w = d.w;
+    if (h) *h = d.h;
+    if (!out || st == OMNI_JPEGDEC_UNSUPPORTED) return st;
+    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
+    if (st == OMNI_JPEGDEC_CORRUPT) {
+        zero_picture(out, stride, d.w, d.h);
+        return st;
+    }
+    return decode_sequential(file, d, out, stride);
+}
+
+// what the parallel decoder reports about itself
+struct ParallelStats {
+    uint32_t n_sub = 0, subseq_bits = 0, rounds = 0, wrong_after_first = 0;     // rounds: relaxation rounds that changed something
+};
+// The CPU stand-in for the kernels: the phase functions driven by plain loops, S bits per subsequence (a power of two, at most max_sub subsequences: S is
+// doubled until they fit).  A file with restart intervals goes to the sequential decoder, as on the device.  Same results as jpeg_decode_host.
+inline int jpeg_decode_parallel_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t max_sub, uint8_t* out, int64_t stride, int max_w, int max_h, int* w,
+                                     int* h, ParallelStats* stats) {
+    Desc d;
+    const int st = parse(file, size, &d);
+    if (w) *w = d.w;
+    if (h) *h = d.h;
+    if (!out || st == OMNI_JPEGDEC_UNSUPPORTED) return st;
+    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
+    if (st == OMNI_JPEGDEC_CORRUPT) {
+        zero_picture(out, stride, d.w, d.h);
+        return st;
+    }
+    if (d.restart) return decode_sequential(file, d, out, stride);
+    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
+    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), nullptr, 0, nullptr);
+    const uint32_t total_bits = (uint32_t)(nclean * 8), n_words = scan_words(nclean);
+    S = subseq_bits_for(total_bits, S, max_sub);
+    const uint32_t N = (total_bits + S - 1) / S;
+    std::vector<uint16_t> ex(N), used(N, 0);
+    std::vector<uint32_t> cnt(N), first(N);
+    std::vector<uint8_t> need(N);
+    NoEmit none;
+    int e;
+    for (uint32_t i = 0; i < N; ++i) cnt[i] = decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, 0, 0u, 0xffffffffu, none, &ex[i], &e);      // 1
+    ParallelStats ps;
+    ps.n_sub = N; ps.subseq_bits = S;
+    {                                                                                       // (for the record: how many guesses were wrong)
+        uint16_t prev = 0;
+        for (uint32_t i = 0; i + 1 < N; ++i) {
+            uint16_t x;
+            decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, prev, 0u, 0xffffffffu, none, &x, &e);
+            ps.wrong_after_first += x != ex[i];
+            prev = x;
+        }
+    }
+    for (uint32_t r = 0; r < N; ++r) {                                                      // 2
+        for (uint32_t i = 1; i < N; ++i) {
+            need[i] = ex[i - 1] != used[i];
+            if (need[i]) used[i] = ex[i - 1];
+        }
+        bool changed = false;
+        for (uint32_t i = 1; i < N; ++i) {
+            if (!need[i]) continue;
+            uint16_t x;
+            const uint32_t c = decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, &x, &e);
+            if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = true; }
+        }
+        if (!changed) break;
+        ++ps.rounds;
+    }
+    if (stats) *stats = ps;
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < N; ++i) { first[i] = total; total += cnt[i]; }                 // 3
+    std::vector<int16_t> coef((size_t)d.n_yblocks * 64, 0);
+    std::vector<int32_t> dc(d.n_yblocks, 0);
+    int err = total < d.n_blocks;
+    for (uint32_t i = 0; i < N; ++i) {                                                      // 4
+        CoefEmit em;
+        em.coef = coef.data(); em.dcd = dc.data(); em.n_yblocks = d.n_yblocks;
+        em.start(d.T, first[i], used[i] >> 12);
+        uint16_t x;
+        decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], first[i], d.n_blocks, em, &x, &e);
+        err |= e;
+    }
+    uint32_t run = 0;
+    for (uint32_t y = 0; y < d.n_yblocks; ++y) { run += (uint32_t)dc[y]; dc[y] = (int32_t)run; }      // 5
+    for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
+    return err ? OMNI_JPEGDEC_CORRUPT : d.status;
+}
+
+}  // namespace jd
+}  // namespace omni

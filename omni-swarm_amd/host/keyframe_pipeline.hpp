@@ -96,6 +96,12 @@ public:
         // mask reaches the picture, as in the reference.  jpeg_capacity: bytes per image in the unit's result block (<= 0: width * height / 2); an image that does
         // not fit leaves `image` empty and counts in jpeg_truncated().  (set_send_img: before the first key frame.)
         bool send_img = false;
+        // is_compressed_images (the VINS settings file, swarm_loop.cpp:291-292, 303-304): the camera frames arrive as JPEG files (sensor_msgs::CompressedImage; every
+        // frame through cv::imdecode(data, IMREAD_GRAYSCALE), :72-89) and are decoded on the GPU inside the key-frame unit, in front of the resize
+        // (omni_cam_enqueue_jpeg_host; csrc/jpeg_dec.hip).  A key frame then carries (pointer, size) pairs instead of pixel pointers, in push_keyframe and in
+        // run().  STEREO_PINHOLE and PINHOLE_DEPTH only: STEREO_FISHEYE ignores the switch (the reference has no compressed path for it), and so does the sharded
+        // mode.  A frame that cannot be decoded comes out all zeros -- no key points, landmark_num 0 -- and counts in jpeg_corrupt().
+        bool compressed_images = false;
         int jpg_quality = 50;
         int64_t jpeg_capacity = 0;
         // CameraConfig (loop_defines.h:111-116): STEREO_FISHEYE = 1 -- a key frame is 4 directions x (up, down) flattened views, the bottom quarter of
@@ -142,6 +148,8 @@ public:
         return c;
     }
     int pipelines() const { return cfg_.pipelines; }
+    int microbatch() const { return cfg_.microbatch; }
+    bool stereo_rig() const { return cfg_.stereo(); }
 
     explicit KeyframePipeline(const Config& c0) : KeyframePipeline(resolved(c0), 0) {}
 private:
@@ -416,6 +424,19 @@ public:
         cfg_.device_landmarks = on;
         apply_stereo_model();
     }
+    // ---- is_compressed_images: the frames arrive as JPEG files (Config::compressed_images) ---------------------------------------------------------------
+    bool compressed() const { return cfg_.compressed_images && cfg_.camera_configuration != 1 && !shard_; }
+    bool compressed_config() const { return cfg_.compressed_images; }
+    int64_t jpeg_corrupt() const { return jpeg_corrupt_.load(); }       // frames whose file could not be decoded so far: their pictures were all zeros
+    // before the first key frame (what the C entry point omni_pipeline_set_compressed_images sets)
+    void set_compressed_images(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_compressed_images after the first key frame");
+        cfg_.compressed_images = on;
+    }
+    // one JPEG file of a key frame, borrowed for the call
+    struct JpegFile { const uint8_t* data = nullptr; int64_t size = 0; };
+
     // ---- send_img: the main images as JPEG files inside the key-frame unit (Config::send_img) ------------------------------------------------------------
     bool send_img() const { return cfg_.send_img && !shard_; }      // (the sharded database builds no messages: the switch is ignored there, like device_landmarks)
     bool send_img_config() const { return cfg_.send_img; }          // the switch as set, whatever the mode makes of it
@@ -571,7 +592,20 @@ public:
             if (lane->cur != want) { lane->cam.set_active(nd * want); lane->cur = want; }     // (the streaming intake or a recut run may have left another size)
             chain(lane, fifo);
             unit_poses(lane, want, first_msg_id + f0);
-            if (recut) {
+            if (compressed()) {
+                // pool[e] / tail: JpegFile[2 * cnt] (PINHOLE_DEPTH: [cnt]) -- the block's left files, then its right files; a unit takes its frames' files wherever
+                // the blocks are cut
+                if (!from_host) throw std::invalid_argument("run: compressed_images takes files in host memory");
+                std::vector<const uint8_t*> fp[2];
+                std::vector<int64_t> fs[2];
+                for (int f = f0; f < f0 + m; ++f) {
+                    const uint8_t* base; int cnt, idx;
+                    block_of(f, base, cnt, idx);
+                    const JpegFile* jf = reinterpret_cast<const JpegFile*>(base);
+                    for (int c = 0; c < (cfg_.stereo() ? 2 : 1); ++c) { fp[c].push_back(jf[c * cnt + idx].data); fs[c].push_back(jf[c * cnt + idx].size); }
+                }
+                enqueue_files(lane, fp, fs);
+            } else if (recut) {
                 up.clear(); down.clear(); upn.clear(); downn.clear();
                 for (int f = f0; f < f0 + m;) {                                  // maximal runs of frames inside one block
                     const uint8_t* base; int cnt, idx;
@@ -633,6 +667,7 @@ public:
         const uint8_t* const* images = nullptr; int stride = 0;
         int64_t msg_id = 0; double stamp = 0; PoseMsg pose_drone; bool prevent_adding_db = false;
         const uint16_t* depth = nullptr;
+        const int64_t* sizes = nullptr;                  // compressed(): images[i] is a JPEG file of sizes[i] bytes (copied before the call returns); `stride` is not read
     };
 private:
     struct SlotMeta { int64_t msg_id = 0; double stamp = 0; PoseMsg pose; bool prevent_adding_db = false; const uint16_t* depth = nullptr; };
@@ -644,9 +679,12 @@ public:
     int push_keyframe(const KeyframeIn& k) {
         std::lock_guard<std::mutex> lk(intake_mu_);
         if (shard_) throw std::runtime_error("push_keyframe: the sharded database is driven through run()");
-        if (!k.images || k.stride < cfg_.in_width()) throw std::invalid_argument("push_keyframe: no images / a row stride below the image width");
+        const bool jpg = compressed();
+        if (jpg && (!k.images || !k.sizes)) throw std::invalid_argument("push_keyframe: compressed_images is set: no files / no sizes");
+        if (!jpg && k.sizes) throw std::invalid_argument("push_keyframe: JPEG files for a pipeline that takes pixels (compressed_images is off, or ignored in this mode)");
+        if (!jpg && (!k.images || k.stride < cfg_.in_width())) throw std::invalid_argument("push_keyframe: no images / a row stride below the image width");
         const int MB = cfg_.microbatch, nd = cfg_.dirs(), cams = cfg_.stereo() ? 2 : 1;
-        for (int i = 0; i < cams * nd; ++i) if (!k.images[i]) throw std::invalid_argument("push_keyframe: a null image pointer");
+        for (int i = 0; i < cams * nd; ++i) if (!k.images[i] || (jpg && k.sizes[i] < 0)) throw std::invalid_argument("push_keyframe: a null image pointer");
         const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         if (cfg_.camera_configuration == 0) first_keyframe_seen_ = true;      // (set_stereo_extrinsics is refused from here on)
         any_keyframe_seen_ = true;
@@ -660,7 +698,8 @@ public:
             while (stream_pending_.size() >= lanes_.size()) { Lane* l = stream_pending_.front(); stream_pending_.pop_front(); hits += finish_timed(*l, 0); }
             Lane* l = lanes_[next_lane_++ % lanes_.size()].get();
             l->meta.clear();
-            if (!l->stage) {
+            for (auto& f : l->jfiles) f.clear();
+            if (!jpg && !l->stage) {
                 l->stage_bytes = (size_t)cams * nd * MB * img;
                 l->stage = static_cast<uint8_t*>(omni_host_alloc(l->stage_bytes));
                 if (!l->stage) throw std::runtime_error(std::string("omni_host_alloc: ") + omni_last_error());
@@ -670,7 +709,8 @@ public:
         }
         const int m = (int)open_->meta.size();
         if (m >= MB) throw std::logic_error("push_keyframe: the open micro-batch is already full");      // (cannot happen: a full unit leaves below, whatever throws)
-        for (int c = 0; c < cams; ++c)
+        for (int c = 0; c < cams && jpg; ++c) open_->jfiles[c].emplace_back(k.images[c], k.images[c] + k.sizes[c]);      // (nd = 1 in both configurations)
+        for (int c = 0; c < cams && !jpg; ++c)
             for (int d = 0; d < nd; ++d) {
                 uint8_t* dst = open_->stage + ((size_t)c * nd * MB + (size_t)nd * m + d) * img;
                 const uint8_t* src = k.images[c * nd + d];
@@ -745,6 +785,8 @@ private:
         int mb;                                        // key frames the unit was created for
         int cur = 0;                                   // ... and of the unit in flight (a partly filled micro-batch of the streaming intake: omni_cam_set_active)
         std::vector<SlotMeta> meta;                    // streaming intake (push_keyframe): what each key frame of the unit came with; empty = run()'s numbering
+        std::vector<std::vector<uint8_t>> jfiles[2];   // streaming intake with compressed_images: the unit's JPEG files, left then right camera, copied at the push
+        int jpeg_frames = 0;                           // > 0: the unit in flight came as that many JPEG files (their statuses are read when it is finished)
         uint8_t* stage = nullptr;                      // pinned block the streaming intake packs the unit's images into
         size_t stage_bytes = 0;
         ~Lane() { if (stage) omni_host_free(stage); }
@@ -767,14 +809,29 @@ private:
         const int MB = cfg_.microbatch, nd = cfg_.dirs(), rem = (int)u->meta.size();
         const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         try {
-            if (rem < MB && cfg_.stereo()) std::memmove(u->stage + (size_t)nd * rem * img, u->stage + (size_t)nd * MB * img, (size_t)nd * rem * img);
+            if (!compressed() && rem < MB && cfg_.stereo()) std::memmove(u->stage + (size_t)nd * rem * img, u->stage + (size_t)nd * MB * img, (size_t)nd * rem * img);
             if (u->cur != rem) { u->cam.set_active(nd * rem); u->cur = rem; }
             chain(u, fifo_cfg_ >= 0 ? fifo_cfg_ : (cfg_.precision == OMNI_PREC_F16 ? 0 : 1));
             unit_poses(u, rem, 0);
-            if (cfg_.raw()) u->cam.enqueue_raw_host(u->resize->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.src_width, rem);
+            if (compressed()) {
+                std::vector<const uint8_t*> fp[2];
+                std::vector<int64_t> fs[2];
+                for (int c = 0; c < 2; ++c)
+                    for (const auto& f : u->jfiles[c]) { fp[c].push_back(f.data()); fs[c].push_back((int64_t)f.size()); }
+                enqueue_files(u, fp, fs);
+            }
+            else if (cfg_.raw()) u->cam.enqueue_raw_host(u->resize->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.src_width, rem);
             else u->cam.enqueue_host(u->stage, cfg_.width, cfg_.masked());
         } catch (...) { u->meta.clear(); throw; }
         stream_pending_.push_back(u);
+    }
+    // a unit's JPEG files to the GPU: decoded inside the unit, in front of the resize (an empty file would read as a null pointer: it gets a byte to point at)
+    void enqueue_files(Lane* u, std::vector<const uint8_t*> (&fp)[2], std::vector<int64_t> (&fs)[2]) {
+        static const uint8_t kNothing = 0;
+        for (int c = 0; c < 2; ++c)
+            for (auto& p : fp[c]) if (!p) p = &kNothing;
+        u->cam.enqueue_jpeg_async(u->resize ? u->resize->handle() : nullptr, fp[0], fs[0], fp[1], fs[1]);
+        u->jpeg_frames = (int)(fp[0].size() + fp[1].size());
     }
     // finishes, oldest first, the units the GPU is done with (never waits for a CNN unit); with nothing left in flight also the detector step enqueued
     // last and its geometry
@@ -842,6 +899,10 @@ private:
         struct Range { explicit Range(const char* n) { omni_trace_push(n); } ~Range() { omni_trace_pop(); } };
         const omni_cam_result r = [&lane] { Range range_wait("host: wait for the unit's GPU work"); return lane.cam.wait(); }();
         host_ms_[1] += since(t_a); ++host_units_;
+        if (lane.jpeg_frames > 0) {
+            for (int st : lane.cam.jpegdec_status(lane.jpeg_frames)) jpeg_corrupt_ += st == OMNI_JPEGDEC_CORRUPT;
+            lane.jpeg_frames = 0;
+        }
         t_a = std::chrono::steady_clock::now();
         Range range_rest("host: messages + detector step of the unit");
         if (shard_) {
@@ -1026,6 +1087,7 @@ private:
     int carried_hits_ = 0;
     bool first_keyframe_seen_ = false;          // STEREO_PINHOLE: set_stereo_extrinsics is refused from the first key frame on
     std::atomic<int64_t> jpeg_truncated_{0};
+    std::atomic<int64_t> jpeg_corrupt_{0};
     bool any_keyframe_seen_ = false;            // set_device_landmarks is refused from the first key frame on
     std::vector<double> pose_stage_;            // unit_poses: the unit's poses on their way into the handle's pinned staging
     std::vector<FisheyeFrameDescriptor> frames_;

@@ -344,6 +344,19 @@ public:
     void enqueue_raw_host(omni_resize* resize, const uint8_t* left_host, const uint8_t* right_host, int src_stride, int n_keyframes) {
         check(omni_cam_enqueue_raw_host(h_, resize, left_host, right_host, src_stride, n_keyframes), "omni_cam_enqueue_raw_host");
     }
+    // is_compressed_images: the unit's frames as JPEG files (borrowed (pointer, size) pairs, free again on return), decoded on the GPU inside the unit in front of
+    // the resize (omni_cam_enqueue_jpeg_host).  right_files empty: a mono handle.  resize may be null: network-size pictures.  jpegdec_status() after wait().
+    void enqueue_jpeg_async(omni_resize* resize, const std::vector<const uint8_t*>& left_files, const std::vector<int64_t>& left_sizes,
+                            const std::vector<const uint8_t*>& right_files, const std::vector<int64_t>& right_sizes) {
+        check(omni_cam_enqueue_jpeg_host(h_, resize, left_files.data(), left_sizes.data(), right_files.empty() ? nullptr : right_files.data(),
+                                         right_files.empty() ? nullptr : right_sizes.data(), (int)left_files.size()),
+              "omni_cam_enqueue_jpeg_host");
+    }
+    std::vector<int> jpegdec_status(int n_frames) {
+        std::vector<int> st((size_t)n_frames);
+        check(omni_cam_jpegdec_status(h_, st.data(), n_frames), "omni_cam_jpegdec_status");
+        return st;
+    }
     void enqueue_raw_dev(omni_resize* resize, const uint8_t* left_dev, const uint8_t* right_dev, int src_stride, int n_keyframes) {
         check(omni_cam_enqueue_raw_dev(h_, resize, left_dev, right_dev, src_stride, n_keyframes), "omni_cam_enqueue_raw_dev");
     }

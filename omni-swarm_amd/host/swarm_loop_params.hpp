@@ -78,6 +78,32 @@ struct SwarmLoopParams {
 #define X(tag, type, name, def) type name = def;
     OMNI_SWARM_LOOP_PARAMS(X)
 #undef X
+    // not a node parameter: the node reads it from the VINS settings file that vins_config_path names (fsSettings["is_compressed_images"], swarm_loop.cpp:291-292,
+    // 303-304) -- read_vins_settings() below
+    bool is_compressed_images = false;
+    // The text of the VINS settings file (OpenCV FileStorage YAML: "key: value" lines, "%YAML:1.0" and "#" comments): learns is_compressed_images (an integer; absent
+    // = 0, as cv::FileNode's conversion of a missing node).  Returns whether the key was present.
+    bool read_vins_settings(const std::string& yaml_text) {
+        const std::string key = "is_compressed_images";
+        size_t line = 0;
+        while (line < yaml_text.size()) {
+            size_t end = yaml_text.find('\n', line);
+            if (end == std::string::npos) end = yaml_text.size();
+            size_t p = line;
+            while (p < end && (yaml_text[p] == ' ' || yaml_text[p] == '\t')) ++p;
+            if (yaml_text.compare(p, key.size(), key) == 0) {
+                p += key.size();
+                while (p < end && (yaml_text[p] == ' ' || yaml_text[p] == '\t')) ++p;
+                if (p < end && yaml_text[p] == ':') {
+                    is_compressed_images = std::atoi(yaml_text.substr(p + 1, end - p - 1).c_str()) != 0;
+                    return true;
+                }
+            }
+            line = end + 1;
+        }
+        is_compressed_images = false;
+        return false;
+    }
 
     struct Field { const char* name; char type; /* 'I' int, 'B' bool, 'D' double, 'S' string */ };
     static const std::vector<Field>& fields() {
@@ -207,6 +233,7 @@ struct SwarmLoopParams {
         c.camera_configuration = camera_configuration; c.depth_near = depth_near_thres; c.depth_far = depth_far_thres;
         c.pca_comp = pca_comp_path; c.pca_mean = pca_mean_path;
         c.send_img = send_img; c.jpg_quality = jpg_quality;                 // swarm_loop.cpp:224-225 -> LoopCam (encode_image, loop_cam.cpp:56-71)
+        c.compressed_images = is_compressed_images;                         // the VINS settings file (read_vins_settings): CompressedImage topics
     }
     template <class Intake> void to_intake(Intake& i) const {              // swarm_loop.cpp:217-218, 238 -> KeyframeIntake
         i.max_freq = max_freq; i.min_movement_keyframe = min_movement_keyframe; i.accept_nonkeyframe_waitsec = nonkeyframe_waitsec;

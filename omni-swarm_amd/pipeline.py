@@ -39,6 +39,10 @@ _pnp_lib = None
 JPEG_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpeg.so")
 JPEG_SYMBOLS = ["omni_jpeg_host_last_error", "omni_pipeline_set_send_img", "omni_pipeline_get_send_img", "omni_pipeline_jpeg_truncated", "omni_pipeline_frame_image"]
 _jpeg_lib = None
+JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
+JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
+                   "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
+_jpegdec_lib = None
 
 
 def lib():
@@ -176,6 +180,30 @@ def pnp_lib():
     return _pnp_lib
 
 
+def jpegdec_lib():
+    """libomni_host_jpegdec.so (include/omni_host_jpegdec.h): is_compressed_images of the key-frame pipeline"""
+    global _jpegdec_lib
+    if _jpegdec_lib is None:
+        lib()                                                    # (libomni_host.so first: the handle's type lives there)
+        L = C.CDLL(JPEGDEC_LIB_PATH)
+        L.omni_jpegdec_host_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_compressed_images.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_compressed_images.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.omni_pipeline_jpeg_corrupt.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_pipeline_push_keyframe_jpeg.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64, C.c_double, C.POINTER(C.c_double), C.c_int,
+                                                       C.c_void_p, C.POINTER(C.c_int)]
+        L.omni_pipeline_run_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.omni_swarm_vins_is_compressed_images.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+        L.omni_pipeline_apply_vins_settings.argtypes = [C.c_void_p, C.c_char_p]
+        _jpegdec_lib = L
+    return _jpegdec_lib
+
+
+def vins_is_compressed_images(vins_yaml_text: str) -> bool:
+    """is_compressed_images of the VINS settings file the node's vins_config_path names (False when the key is absent)"""
+    return bool(jpegdec_lib().omni_swarm_vins_is_compressed_images(vins_yaml_text.encode(), None))
+
+
 def jpeg_lib():
     global _jpeg_lib
     if _jpeg_lib is None:
@@ -196,7 +224,7 @@ class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -240,11 +268,68 @@ class KeyframePipeline:
             self.set_device_pnp(device_pnp)
         if send_img:
             self.set_send_img(True, jpg_quality)
+        if compressed_images:
+            self.set_compressed_images(True)
 
     def set_device_landmarks(self, on: bool):
         """before the first key frame: stereo landmarks inside the key-frame unit (GPU) or on the host's geometry threads"""
         if landmarks_lib().omni_pipeline_set_device_landmarks(self.h, int(bool(on))):
             raise capi.OmniError(f"omni_pipeline_set_device_landmarks: {landmarks_lib().omni_landmarks_last_error().decode()}")
+
+    def _jpegdec(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {jpegdec_lib().omni_jpegdec_host_last_error().decode()}")
+
+    def set_compressed_images(self, on: bool):
+        """is_compressed_images: every following key frame comes as JPEG files (push_keyframe with bytes, run_jpeg), decoded on the GPU inside the key-frame unit in
+        front of the resize (csrc/jpeg_dec.hip; libjpeg-turbo's gray pixels, pinned against Pillow -- cv::imdecode's own parity is unpinned).  Before the first
+        key frame.  STEREO_PINHOLE and PINHOLE_DEPTH; ignored by STEREO_FISHEYE and under a sharded database."""
+        self._jpegdec(jpegdec_lib().omni_pipeline_set_compressed_images(self.h, int(bool(on))), "omni_pipeline_set_compressed_images")
+
+    def apply_vins_settings(self, vins_yaml_text: str):
+        """sets the switch from the VINS settings file's is_compressed_images"""
+        self._jpegdec(jpegdec_lib().omni_pipeline_apply_vins_settings(self.h, vins_yaml_text.encode()), "omni_pipeline_apply_vins_settings")
+
+    def compressed_images(self):
+        """(the switch as set, whether this pipeline's mode takes files at all)"""
+        on, act = C.c_int(0), C.c_int(0)
+        self._jpegdec(jpegdec_lib().omni_pipeline_get_compressed_images(self.h, C.byref(on), C.byref(act)), "omni_pipeline_get_compressed_images")
+        return bool(on.value), bool(act.value)
+
+    def jpeg_corrupt(self) -> int:
+        """frames whose file could not be decoded so far (all-zero pictures: no key points)"""
+        n = C.c_int64(0)
+        self._jpegdec(jpegdec_lib().omni_pipeline_jpeg_corrupt(self.h, C.byref(n)), "omni_pipeline_jpeg_corrupt")
+        return n.value
+
+    @staticmethod
+    def _files(files):
+        keep = [bytes(f) for f in files]
+        return keep, (C.c_void_p * len(keep))(*[C.cast(C.c_char_p(f), C.c_void_p) for f in keep]), (C.c_int64 * len(keep))(*[len(f) for f in keep])
+
+    def push_keyframe_jpeg(self, files, msg_id: int, stamp: float, pose7=None, prevent_adding_db: bool = False, depth: np.ndarray = None) -> int:
+        """push_keyframe for a key frame that comes as JPEG files: [left, right] (STEREO_PINHOLE) or [the gray image] (PINHOLE_DEPTH) as bytes; copied before the
+        call returns"""
+        keep, fp, fs = self._files(files)
+        p7 = None
+        if pose7 is not None:
+            p7v = np.ascontiguousarray(pose7, np.float64).reshape(7)
+            p7 = p7v.ctypes.data_as(C.POINTER(C.c_double))
+        if depth is not None:
+            depth = np.ascontiguousarray(depth, np.uint16)
+            self._depths = getattr(self, "_depths", []) + [depth]
+        hits = C.c_int(0)
+        self._jpegdec(jpegdec_lib().omni_pipeline_push_keyframe_jpeg(self.h, fp, fs, msg_id, float(stamp), p7, int(prevent_adding_db),
+                                                                     depth.ctypes.data if depth is not None else None, C.byref(hits)), "omni_pipeline_push_keyframe_jpeg")
+        return hits.value
+
+    def run_jpeg(self, keyframes, first_msg_id: int = 0) -> int:
+        """run() for key frames that come as JPEG files: keyframes = [[left, right], ...] (PINHOLE_DEPTH: [[gray], ...]) as bytes"""
+        flat = [f for kf in keyframes for f in kf]
+        keep, fp, fs = self._files(flat)
+        hits = C.c_int(0)
+        self._jpegdec(jpegdec_lib().omni_pipeline_run_jpeg(self.h, len(keyframes), first_msg_id, fp, fs, C.byref(hits)), "omni_pipeline_run_jpeg")
+        return hits.value
 
     def _jpeg(self, rc, what):
         if rc:
