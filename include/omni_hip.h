@@ -669,6 +669,16 @@ int        omni_cam_enqueue_jpeg_host(omni_cam* cam, omni_resize* resize_or_null
 /* after omni_cam_wait: OMNI_JPEGDEC_OK / HOST / CORRUPT of every frame of that unit, [left frames | right frames]; n_frames = cams x the unit's active size.
  * OMNI_ERR_INVALID while a unit is pending, and when the last unit did not come as files */
 int        omni_cam_jpegdec_status(omni_cam* cam, int* status, int n_frames);
+/* STEREO_FISHEYE frames as JPEG files: omni_cam_enqueue_fisheye_host with each camera's n_keyframes RAW frames given as files (what the reference's upstream,
+ * VINS-Fisheye, decodes from the compressed fisheye topics in front of its own flattening; the reference itself has no such path).  ONE decode of
+ * [up frames | down frames] on the unit's SuperPoint stream into the staging block omni_cam_enqueue_fisheye_host uploads into, then that entry's two remaps and the
+ * unit, MobileNetVLAD behind the up camera's views.  The decoder is made at first use for the flatten objects' source size -- both must have the same --, for
+ * 2 x (the handle's capacity / directions) pictures and src_w x src_h / 2 bytes per file (a larger file: HOST, same pixels).  omni_cam_jpegdec_status reports
+ * 2 x n_keyframes statuses, [up frames | down frames]; a CORRUPT frame is an all-zero fisheye frame and so all-zero views; omni_cam_get_input shows the
+ * flattened block.  Refused before anything is enqueued: what omni_cam_enqueue_fisheye_host refuses (a mono handle, a wrong active size, views of another size),
+ * different source sizes, a unit in flight, an UNSUPPORTED file, a picture of another size. */
+int        omni_cam_enqueue_fisheye_jpeg_host(omni_cam* cam, omni_flatten* up, omni_flatten* down, const uint8_t* const* up_files, const int64_t* up_sizes,
+                                              const uint8_t* const* down_files, const int64_t* down_sizes, int n_keyframes, int first_view, int fisheye_mask);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 /* omni_host_jpegdec.h -- C entry points of libomni_host_jpegdec.so (omni-swarm_amd/host/host_jpegdec_capi.cpp): is_compressed_images of the key-frame pipeline of
  * omni_host.h -- the camera frames arrive as JPEG files (sensor_msgs::CompressedImage; cv::imdecode(data, IMREAD_GRAYSCALE) in the reference, swarm_loop.cpp:72-89,
  * 291-292, 341-360) and are decoded on the GPU inside the key-frame unit, in front of the resize (csrc/jpeg_dec.hip).  STEREO_PINHOLE (left + right file per key
- * frame) and PINHOLE_DEPTH (one file; the depth image stays uncompressed) only: STEREO_FISHEYE and a pipeline attached to a sharded database ignore the switch.
+ * frame), PINHOLE_DEPTH (one file; the depth image stays uncompressed) and STEREO_FISHEYE in its raw-fisheye mode (omni_host_fisheye.h: the up and the down
+ * fisheye frame as files).  A STEREO_FISHEYE pipeline fed flattened views and a pipeline attached to a sharded database ignore the switch.
  * The pixels are libjpeg-turbo's JCS_GRAYSCALE output, pinned against Pillow; parity with cv::imdecode itself is unpinned (OpenCV is not vendored).  The handle is
  * omni_host.h's omni_pipeline, whoever made it.  Returns as in omni_host.h: 0 on success; after a failure omni_jpegdec_host_last_error() holds the message (per
  * calling thread). */

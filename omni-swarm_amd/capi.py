@@ -46,7 +46,7 @@ SYMBOLS = [
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
     "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
-    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status",
+    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
 ]
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
@@ -252,6 +252,7 @@ def lib():
     sig("omni_jpeg_decode_host", C.c_int, [_vp, C.c_int64, _vp, C.c_int, _ip, _ip, _ip])
     sig("omni_cam_enqueue_jpeg_host", C.c_int, [_vp, _vp, C.POINTER(_vp), _i64p, C.POINTER(_vp), _i64p, C.c_int])
     sig("omni_cam_jpegdec_status", C.c_int, [_vp, _ip, C.c_int])
+    sig("omni_cam_enqueue_fisheye_jpeg_host", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp), _i64p, C.POINTER(_vp), _i64p, C.c_int, C.c_int, C.c_int])
     sig("omni_jpeg_decode_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
@@ -1328,10 +1329,22 @@ class Cam:
         lp, ls = pack(left_files)
         rp, rs = pack(right_files)
         _check(lib().omni_cam_enqueue_jpeg_host(self.h, resize.h if resize is not None else None, lp, ls, rp, rs, len(left_files)))
+        self._jdec_frames = None
+
+    def enqueue_fisheye_jpeg_host(self, up: "Flatten", down: "Flatten", up_files, down_files, first_view: int = 1, fisheye_mask: bool = True):
+        """enqueue_fisheye_host with each camera's raw frames as JPEG files ([bytes] per camera): decoded and flattened inside the unit
+        (omni_cam_enqueue_fisheye_jpeg_host).  The files may go on return; jpegdec_status() after wait() has 2 * len(up_files) entries."""
+        assert len(up_files) == len(down_files)
+        def pack(files):
+            return (_vp * len(files))(*[C.cast(C.c_char_p(f), _vp) for f in files]), (C.c_int64 * len(files))(*[len(f) for f in files])
+        up_p, up_s = pack(up_files)
+        dn_p, dn_s = pack(down_files)
+        _check(lib().omni_cam_enqueue_fisheye_jpeg_host(self.h, up.h, down.h, up_p, up_s, dn_p, dn_s, len(up_files), first_view, int(fisheye_mask)))
+        self._jdec_frames = 2 * len(up_files)
 
     def jpegdec_status(self) -> list:
-        """after wait(): the OMNI_JPEGDEC_* status of every frame of that unit, [left frames | right frames]"""
-        n = self.cams * self.n_active
+        """after wait(): the OMNI_JPEGDEC_* status of every frame of that unit, [left frames | right frames] ([up frames | down frames] of a fisheye unit)"""
+        n = getattr(self, "_jdec_frames", None) or self.cams * self.n_active
         st = (C.c_int * n)()
         _check(lib().omni_cam_jpegdec_status(self.h, st, n))
         return list(st)

@@ -28,6 +28,7 @@ struct omni_cam {
     size_t d_gray_bytes = 0;
     size_t input_bytes = 0;           // what the last unit read from d_gray (0: it read a caller's buffer): omni_cam_get_input
     uint8_t* d_raw = nullptr;         // staging for omni_cam_enqueue_fisheye_host / _raw_host: the raw frames of the up (left) cameras, then of the down (right) cameras
+                                      // (uploaded, or decoded there: omni_cam_enqueue_jpeg_host, omni_cam_enqueue_fisheye_jpeg_host)
     size_t d_raw_bytes = 0;
     bool pending = false;
     // stereo landmarks inside the unit (omni_cam_set_stereo_model; landmarks.hip): the model, the NEXT unit's poses (pinned staging in `host`, uploaded at enqueue),
@@ -51,7 +52,7 @@ struct omni_cam {
     // is_compressed_images (omni_cam_enqueue_jpeg_host; jpeg_dec.hip): the unit's frames arrive as JPEG files and are decoded on the SuperPoint stream in front of
     // the resize.  The decoder is made at first use for the frames' size; statuses [cams * n_cap] go down into a pinned block of their own
     omni_jpegdec* jdec = nullptr;
-    int jdec_w = 0, jdec_h = 0;
+    int jdec_w = 0, jdec_h = 0, jdec_max = 0;      // jdec_max: pictures the decoder was made for
     int *d_jdec_status = nullptr, *h_jdec_status = nullptr;
     int jdec_n = 0;                           // frames of the unit enqueued last if it came as files (omni_cam_jpegdec_status), else 0
     std::mutex mu;
@@ -288,6 +289,66 @@ int omni_cam_enqueue_fisheye_host(omni_cam* c, omni_flatten* up, omni_flatten* d
     return cam_fisheye_locked(c, up, down, nullptr, nullptr, up_host, down_host, src_stride, n_keyframes, first_view, fisheye_mask);
 }
 
+// the handle's decoder, made at first use for frames of sw x sh (and made again for another size or more pictures); its statuses [cams * n_cap] go down into a
+// pinned block of their own.  c->mu held, no unit in flight
+static int cam_jdec_ensure(omni_cam* c, int sw, int sh, int max_images) {
+    if (!c->jdec || c->jdec_w != sw || c->jdec_h != sh || c->jdec_max < max_images) {
+        if (c->jdec) omni_jpegdec_destroy(c->jdec);
+        c->jdec = nullptr;
+        const int64_t cap = (int64_t)sw * sh / 2 > 1024 ? (int64_t)sw * sh / 2 : 1024;       // (a larger file is decoded on the calling thread: same pixels)
+        c->jdec = omni_jpegdec_create(c->c1, sw, sh, max_images, cap);
+        if (!c->jdec) return OMNI_ERR_INVALID;
+        c->jdec_w = sw; c->jdec_h = sh; c->jdec_max = max_images;
+    }
+    if (!c->d_jdec_status) {
+        OMNI_HIP_TRY(hipMalloc((void**)&c->d_jdec_status, (size_t)c->cams * c->n_cap * sizeof(int)));
+        OMNI_HIP_TRY(hipHostMalloc((void**)&c->h_jdec_status, (size_t)c->cams * c->n_cap * sizeof(int), hipHostMallocDefault));
+    }
+    return OMNI_OK;
+}
+
+// The same with each camera's n_keyframes RAW frames given as JPEG files (the compressed fisheye topics the reference's upstream, VINS-Fisheye, decodes in front of
+// its own flattening): ONE decode of [up frames | down frames] (jpeg_dec.hip) on the SuperPoint stream into d_raw, rows packed, where omni_cam_enqueue_fisheye_host
+// uploads them; the two remaps and the unit follow as there, MobileNetVLAD behind the up camera's views.  A CORRUPT file is an all-zero frame and so all-zero views.
+int omni_cam_enqueue_fisheye_jpeg_host(omni_cam* c, omni_flatten* up, omni_flatten* down, const uint8_t* const* up_files, const int64_t* up_sizes,
+                                       const uint8_t* const* down_files, const int64_t* down_sizes, int n_keyframes, int first_view, int fisheye_mask) {
+    OMNI_REQUIRE(c && up && down && up_files && up_sizes && down_files && down_sizes, OMNI_ERR_INVALID, "null argument");
+    omni::TraceRange trace_range("omni_cam_enqueue_fisheye_jpeg_host (decode + flatten + unit)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye_jpeg_host with a unit in flight (omni_cam_wait first)");
+    c->jdec_n = 0;                                                            // (as omni_cam_enqueue_jpeg_host)
+    OMNI_REQUIRE(up->src_w == down->src_w && up->src_h == down->src_h, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye_jpeg_host: up frames of %dx%d, down frames of %dx%d (one decoder: one size)",
+                 up->src_w, up->src_h, down->src_w, down->src_h);
+    const int sw = up->src_w, sh = up->src_h;
+    int rc, dirs = 0;
+    if ((rc = cam_fisheye_check(c, up, down, sw, n_keyframes, first_view, &dirs))) return rc;
+    int row0 = 0, row1 = 0;                                                   // flatten_unit_launch's own refusal, in front of the decode
+    omni_fisheye_mask_rows(c->H, fisheye_mask, &row0, &row1);
+    OMNI_REQUIRE(c->W % 4 == 0 && row1 == c->H && sw >= 2, OMNI_ERR_INVALID, "omni_cam_enqueue_fisheye_jpeg_host: %dx%d views, frames %d wide", c->W, c->H, sw);
+    (void)hipSetDevice(c->c1->device);
+    if ((rc = cam_jdec_ensure(c, sw, sh, 2 * (c->n_cap / dirs)))) return rc;
+    const int nf = 2 * n_keyframes;
+    const size_t half = (size_t)c->n * c->W * c->H, frame = (size_t)sw * sh;
+    if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, 2 * half))) return rc;
+    if ((rc = cam_staging(c, c->d_raw, c->d_raw_bytes, (size_t)nf * frame))) return rc;
+    std::vector<const uint8_t*> files(up_files, up_files + n_keyframes);
+    std::vector<int64_t> sizes(up_sizes, up_sizes + n_keyframes);
+    files.insert(files.end(), down_files, down_files + n_keyframes);
+    sizes.insert(sizes.end(), down_sizes, down_sizes + n_keyframes);
+    hipStream_t s1 = c->c1->stream;
+    // (an UNSUPPORTED file or a picture of another size is refused here, nothing enqueued)
+    if ((rc = omni::jpegdec_enqueue_on(c->jdec, s1, files.data(), sizes.data(), nf, c->d_raw, sw, c->d_jdec_status))) return rc;
+    OMNI_HIP_TRY(hipMemcpyAsync(c->h_jdec_status, c->d_jdec_status, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s1));
+    if ((rc = omni::flatten_unit_launch(up, s1, c->d_raw, sw, n_keyframes, first_view, dirs, c->W, c->H, fisheye_mask, c->d_gray))) return rc;
+    OMNI_HIP_TRY(hipEventRecord(c->e_up, s1));
+    OMNI_HIP_TRY(hipStreamWaitEvent(c->c2->stream, c->e_up, 0));
+    if ((rc = omni::flatten_unit_launch(down, s1, c->d_raw + (size_t)n_keyframes * frame, sw, n_keyframes, first_view, dirs, c->W, c->H, fisheye_mask, c->d_gray + half)))
+        return rc;
+    rc = cam_enqueue_locked(c, c->d_gray, c->W, fisheye_mask);
+    c->jdec_n = rc == OMNI_OK ? nf : 0;
+    return rc;
+}
+
 // A key frame's two RAW stereo-pinhole frames (CameraConfig::STEREO_PINHOLE: generate_stereo_image_descriptor for ONE direction, loop_cam.cpp:189-196) of the
 // camera's size instead of network-size images: the resize both reference engines run on the host in front of their networks (resize.hip) runs inside the unit,
 // on the SuperPoint stream, and writes the unit's own input block.  With one direction the unit's active size counts key frames: n_keyframes left frames (the
@@ -386,17 +447,7 @@ int omni_cam_enqueue_jpeg_host(omni_cam* c, omni_resize* r, const uint8_t* const
     if ((rc = cam_poses_check(c))) return rc;
     (void)hipSetDevice(c->c1->device);
     const int sw = r ? r->src_w : c->W, sh = r ? r->src_h : c->H, n = c->n, ni = c->cams * n;
-    if (!c->jdec || c->jdec_w != sw || c->jdec_h != sh) {
-        if (c->jdec) omni_jpegdec_destroy(c->jdec);
-        const int64_t cap = (int64_t)sw * sh / 2 > 1024 ? (int64_t)sw * sh / 2 : 1024;       // (a larger file is decoded on the calling thread: same pixels)
-        c->jdec = omni_jpegdec_create(c->c1, sw, sh, c->cams * c->n_cap, cap);
-        if (!c->jdec) return OMNI_ERR_INVALID;
-        c->jdec_w = sw; c->jdec_h = sh;
-    }
-    if (!c->d_jdec_status) {
-        OMNI_HIP_TRY(hipMalloc((void**)&c->d_jdec_status, (size_t)c->cams * c->n_cap * sizeof(int)));
-        OMNI_HIP_TRY(hipHostMalloc((void**)&c->h_jdec_status, (size_t)c->cams * c->n_cap * sizeof(int), hipHostMallocDefault));
-    }
+    if ((rc = cam_jdec_ensure(c, sw, sh, c->cams * c->n_cap))) return rc;
     const size_t half = (size_t)n * c->W * c->H, frame = (size_t)sw * sh;
     if ((rc = cam_staging(c, c->d_gray, c->d_gray_bytes, (size_t)c->cams * half))) return rc;
     if (r && (rc = cam_staging(c, c->d_raw, c->d_raw_bytes, (size_t)ni * frame))) return rc;

@@ -99,6 +99,13 @@ class LoopCam:
         self.cam.enqueue_fisheye_host(fl[0], fl[1], raw[0], raw[1], len(fl[0].shapes) - self.cam.n_active, self.fisheye)
         return self.fetch()
 
+    def on_fisheye_jpeg(self, up_file: bytes, down_file: bytes, undist_up, undist_down) -> dict:
+        """on_fisheye_images with the key frame's two RAW fisheye frames as JPEG files (bytes): decoded and flattened inside the unit
+        (omni_cam_enqueue_fisheye_jpeg_host).  Returns what on_fisheye_images returns for the decoded frames; self.cam.jpegdec_status() holds the two statuses."""
+        fl = [getattr(u, "flatten", u) for u in (undist_up, undist_down)]
+        self.cam.enqueue_fisheye_jpeg_host(fl[0], fl[1], [bytes(up_file)], [bytes(down_file)], len(fl[0].shapes) - self.cam.n_active, self.fisheye)
+        return self.fetch()
+
     def on_stereo_images(self, left_raw: np.ndarray, right_raw: np.ndarray, resize: capi.Resize) -> dict:
         """The blocking call for a STEREO_PINHOLE key frame (generate_stereo_image_descriptor for one direction, loop_cam.cpp:189-196): the two RAW frames
         [src_h][src_w] uint8 of the camera's size -- or [k][src_h][src_w] for the k key frames of the unit's active size -- are resized to the networks' size

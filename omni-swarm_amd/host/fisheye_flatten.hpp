@@ -48,6 +48,14 @@ inline geom::Quat angle_axis(double angle, double ax, double ay, double az) {
     return {std::cos(angle / 2), ax * s, ay * s, az * s};
 }
 
+// the height of the four side views generateAllUndistMap makes for views img_width wide (0: a field of view of 180 degrees or less has none); their width is
+// img_width and their focal length img_width / 2
+inline int side_view_height(unsigned img_width, double fov_deg) {
+    double side_fov = (fov_deg - 180) * M_PI / 180.0;
+    if (side_fov < 0) side_fov = 0;
+    return (int)(2 * ((double)img_width / 2) * std::tan(side_fov / 2));
+}
+
 // generateAllUndistMap (:118-186): view 0 = top (or down, cam_id == 1: the rig is flipped about X), views 1..4 = the side views
 inline FlattenMaps generate_all_undist_maps(const MeiCamera& cam, unsigned img_width, double fov_deg, int cam_id) {
     FlattenMaps m;

@@ -14,6 +14,7 @@
 #include <memory>
 #include <thread>
 
+#include "fisheye_flatten.hpp"
 #include "loop_geometry.hpp"
 #include "omni_swarm.hpp"
 
@@ -99,7 +100,8 @@ public:
         // is_compressed_images (the VINS settings file, swarm_loop.cpp:291-292, 303-304): the camera frames arrive as JPEG files (sensor_msgs::CompressedImage; every
         // frame through cv::imdecode(data, IMREAD_GRAYSCALE), :72-89) and are decoded on the GPU inside the key-frame unit, in front of the resize
         // (omni_cam_enqueue_jpeg_host; csrc/jpeg_dec.hip).  A key frame then carries (pointer, size) pairs instead of pixel pointers, in push_keyframe and in
-        // run().  STEREO_PINHOLE and PINHOLE_DEPTH only: STEREO_FISHEYE ignores the switch (the reference has no compressed path for it), and so does the sharded
+        // run().  STEREO_PINHOLE, PINHOLE_DEPTH and STEREO_FISHEYE's raw-fisheye mode (below): a flattened-view STEREO_FISHEYE pipeline ignores the switch (the
+        // reference has no compressed path for it), and so does the sharded
         // mode.  A frame that cannot be decoded comes out all zeros -- no key points, landmark_num 0 -- and counts in jpeg_corrupt().
         bool compressed_images = false;
         int jpg_quality = 50;
@@ -127,13 +129,29 @@ public:
         // PINHOLE_DEPTH, and the same displaced by stereo_baseline along its own x axis (to its right)
         bool have_stereo_extrinsics = false;
         double left_extrinsic[7] = {0, 0, 0, 1, 0, 0, 0}, right_extrinsic[7] = {0, 0, 0, 1, 0, 0, 0};
+        // STEREO_FISHEYE = 1 with fisheye_src_width x fisheye_src_height > 0, the raw-fisheye mode: a key frame is ONE up frame and ONE down frame of the fisheye
+        // camera's size instead of 8 flattened views, and the flattening (the reference's upstream does it: VINS-Fisheye's FisheyeUndist publishes flattened_gray;
+        // the reference itself has no such path) runs inside the key-frame unit (omni_cam_enqueue_fisheye_*; csrc/flatten.hip).  The two cameras' maps are made at
+        // construction by generate_all_undist_maps(MEI model, width, fisheye_fov_deg, camera 0 / 1): their four side views, views fisheye_first_view.., must be
+        // width x height.  fisheye_mei_*: xi k1 k2 p1 p2 gamma1 gamma2 u0 v0, the order omni_fisheye_maps takes.  With compressed_images the two frames are
+        // JPEG files, decoded in front of the flattening (omni_cam_enqueue_fisheye_jpeg_host).
+        int fisheye_src_width = 0, fisheye_src_height = 0;
+        double fisheye_fov_deg = 235.0;
+        double fisheye_mei_up[9] = {0, 0, 0, 0, 0, 1, 1, 0, 0}, fisheye_mei_down[9] = {0, 0, 0, 0, 0, 1, 1, 0, 0};
+        int fisheye_first_view = 1;
         // what the camera configuration decides, one question each
         bool stereo() const { return camera_configuration != 2; }      // two cameras per direction: up / down (left / right), stereo match, triangulated landmarks
         int dirs() const { return camera_configuration == 1 ? 4 : 1; }
         bool masked() const { return camera_configuration == 1; }       // loop_cam.cpp:536 blanks rows for STEREO_FISHEYE only; its query image is direction 1
-        bool raw() const { return camera_configuration == 0 && src_width > 0; }
-        int in_width() const { return raw() ? src_width : width; }      // the size of the images a caller hands over
-        int in_height() const { return raw() ? src_height : height; }
+        bool resized() const { return camera_configuration == 0 && src_width > 0; }              // camera-size stereo-pinhole frames: resized inside the unit
+        bool fisheye_raw() const { return camera_configuration == 1 && fisheye_src_width > 0; }   // raw fisheye frames: flattened inside the unit
+        bool raw() const { return resized() || fisheye_raw(); }         // the caller hands over the camera's frames, not network-size images
+        int in_width() const { return fisheye_raw() ? fisheye_src_width : (resized() ? src_width : width); }      // the size of the images a caller hands over
+        int in_height() const { return fisheye_raw() ? fisheye_src_height : (resized() ? src_height : height); }
+        int frames_per_keyframe() const { return fisheye_raw() ? 2 : (stereo() ? 2 : 1) * dirs(); }       // ... and how many of them make a key frame
+        int frames_per_camera() const { return fisheye_raw() ? 1 : dirs(); }
+        // compressed_images as the mode takes it: a flattened-view STEREO_FISHEYE pipeline ignores the switch (the sharded database too: KeyframePipeline::compressed)
+        bool compressed() const { return compressed_images && (camera_configuration != 1 || fisheye_raw()); }
     };
 
     // units in flight when the caller does not say: fp16's small-grid tails (NMS, sampling, matcher, MobileNetVLAD's last blocks) are filled by the next
@@ -144,12 +162,27 @@ public:
             throw std::runtime_error("KeyframePipeline: camera_configuration must be 0 (STEREO_PINHOLE), 1 (STEREO_FISHEYE) or 2 (PINHOLE_DEPTH)");
         if ((c.src_width > 0) != (c.src_height > 0) || (c.src_width > 0 && c.camera_configuration != 0))
             throw std::runtime_error("KeyframePipeline: src_width x src_height (frames resized inside the unit) belongs to camera_configuration 0 (STEREO_PINHOLE), both or neither");
+        if ((c.fisheye_src_width > 0) != (c.fisheye_src_height > 0) || c.fisheye_src_width < 0 || (c.fisheye_src_width > 0 && c.camera_configuration != 1))
+            throw std::runtime_error("KeyframePipeline: fisheye_src_width x fisheye_src_height (raw fisheye frames flattened inside the unit) belongs to camera_configuration 1 (STEREO_FISHEYE), both or neither");
+        if (c.fisheye_raw()) {
+            // generate_all_undist_maps makes one top view and, for a field of view above 180 degrees, four side views of width x side_view_height
+            const int side_h = side_view_height((unsigned)c.width, c.fisheye_fov_deg), n_views = side_h > 0 ? 5 : 1;
+            if (c.fisheye_first_view < 0 || n_views != c.fisheye_first_view + 4)
+                throw std::runtime_error("KeyframePipeline: raw-fisheye mode needs fisheye_first_view + 4 = " + std::to_string(c.fisheye_first_view + 4) + " views, a field of view of " +
+                                         std::to_string(c.fisheye_fov_deg) + " degrees gives " + std::to_string(n_views));
+            if (side_h != c.height)
+                throw std::runtime_error("KeyframePipeline: raw-fisheye mode: the side views are " + std::to_string(c.width) + " x " + std::to_string(side_h) + " but the networks take " +
+                                         std::to_string(c.width) + " x " + std::to_string(c.height));
+        }
         if (c.pipelines <= 0) c.pipelines = default_pipelines(c.precision);
         return c;
     }
     int pipelines() const { return cfg_.pipelines; }
     int microbatch() const { return cfg_.microbatch; }
     bool stereo_rig() const { return cfg_.stereo(); }
+    bool fisheye_raw() const { return cfg_.fisheye_raw(); }
+    int in_width() const { return cfg_.in_width(); }       // the size of the images a caller hands over
+    int in_height() const { return cfg_.in_height(); }
 
     explicit KeyframePipeline(const Config& c0) : KeyframePipeline(resolved(c0), 0) {}
 private:
@@ -159,6 +192,20 @@ private:
         det_.stereo_fisheye = c.masked();
         geo_.MAX_DIRS = c.dirs();
         for (int p = 0; p < c.pipelines; ++p) lanes_.push_back(std::make_unique<Lane>(c, c.microbatch));
+        if (c.fisheye_raw()) {
+            // ONE pair of flatten objects serves every lane: omni_cam_enqueue_fisheye_* launches the remap on the UNIT's stream and only reads the maps and the
+            // view table (flatten_unit_launch, csrc/flatten.hip: neither the object's own stream nor its lock), which nothing writes after omni_flatten_create
+            for (int cam = 0; cam < 2; ++cam) {
+                const double* p = cam ? c.fisheye_mei_down : c.fisheye_mei_up;
+                MeiCamera mei;
+                mei.xi = p[0]; mei.k1 = p[1]; mei.k2 = p[2]; mei.p1 = p[3]; mei.p2 = p[4]; mei.gamma1 = p[5]; mei.gamma2 = p[6]; mei.u0 = p[7]; mei.v0 = p[8];
+                const FlattenMaps maps = generate_all_undist_maps(mei, (unsigned)c.width, c.fisheye_fov_deg, cam);
+                if ((int)maps.w.size() != c.fisheye_first_view + 4) throw std::runtime_error("KeyframePipeline: raw-fisheye mode: the maps have " + std::to_string(maps.w.size()) + " views");
+                for (size_t v = (size_t)c.fisheye_first_view; v < maps.w.size(); ++v)
+                    if (maps.w[v] != c.width || maps.h[v] != c.height) throw std::runtime_error("KeyframePipeline: raw-fisheye mode: a side view is not width x height");
+                flatten_[cam] = std::make_unique<FlattenHIP>(index_ctx_, c.fisheye_src_width, c.fisheye_src_height, maps.w, maps.h, maps.xy);
+            }
+        }
         apply_stereo_model();
         apply_jpeg();
         if (c.device_pnp) ensure_pnp_context();
@@ -425,7 +472,7 @@ public:
         apply_stereo_model();
     }
     // ---- is_compressed_images: the frames arrive as JPEG files (Config::compressed_images) ---------------------------------------------------------------
-    bool compressed() const { return cfg_.compressed_images && cfg_.camera_configuration != 1 && !shard_; }
+    bool compressed() const { return cfg_.compressed() && !shard_; }
     bool compressed_config() const { return cfg_.compressed_images; }
     int64_t jpeg_corrupt() const { return jpeg_corrupt_.load(); }       // frames whose file could not be decoded so far: their pictures were all zeros
     // before the first key frame (what the C entry point omni_pipeline_set_compressed_images sets)
@@ -521,6 +568,7 @@ public:
     // frame's candidate is decided on GLOBAL ids with the reference's rule (loop_detector.cpp:232: recency + threshold); the id maps of
     // LoopDetectorCore describe one drone's own database and are not used in this mode.
     void attach_shard(int rank, int world, const char* unique_id) {
+        if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
         if (!shard_) throw std::runtime_error(std::string("omni_shard_create: ") + omni_last_error());
@@ -557,7 +605,8 @@ public:
         // kernels' grids were sized for runs the same launches at a fraction of the work, and at the reference's key-frame rates (swarm_loop.cpp:140-170: 0.3-1 Hz
         // per drone) every run() is a short one.  Device-resident blocks and the sharded database keep the blocks' own cut (a unit there is one exchange step).
         std::vector<int> sizes;
-        const bool recut = from_host && !shard_ && unit_plan_ != 0 && rem != 0 && full >= 1;
+        // (The raw-fisheye mode keeps the blocks' own cut as well: the fisheye entry takes one segment per camera, it has no _host_parts flavour.)
+        const bool recut = from_host && !shard_ && unit_plan_ != 0 && rem != 0 && full >= 1 && !cfg_.fisheye_raw();
         if (recut) sizes = plan_units(n_keyframes, MB, unit_plan_);
         else { sizes.assign(full, MB); if (rem) sizes.push_back(rem); }
         Lane* tail_lane = (!recut && rem) ? prepare(n_keyframes) : nullptr;
@@ -593,8 +642,8 @@ public:
             chain(lane, fifo);
             unit_poses(lane, want, first_msg_id + f0);
             if (compressed()) {
-                // pool[e] / tail: JpegFile[2 * cnt] (PINHOLE_DEPTH: [cnt]) -- the block's left files, then its right files; a unit takes its frames' files wherever
-                // the blocks are cut
+                // pool[e] / tail: JpegFile[2 * cnt] (PINHOLE_DEPTH: [cnt]) -- the block's left (raw fisheye: up) files, then its right (down) files; a unit takes
+                // its frames' files wherever the blocks are cut
                 if (!from_host) throw std::invalid_argument("run: compressed_images takes files in host memory");
                 std::vector<const uint8_t*> fp[2];
                 std::vector<int64_t> fs[2];
@@ -615,11 +664,15 @@ public:
                     if (cfg_.stereo()) { down.push_back(base + ((size_t)cnt + idx) * nd * img); downn.push_back(take * nd); }
                     f += take;
                 }
-                if (cfg_.raw()) lane->cam.enqueue_raw_host_parts(lane->resize->handle(), up, upn, down, downn, cfg_.src_width);
+                if (cfg_.resized()) lane->cam.enqueue_raw_host_parts(lane->resize->handle(), up, upn, down, downn, cfg_.src_width);
                 else lane->cam.enqueue_host_parts(up, upn, down, downn, cfg_.masked());
             } else {
                 const uint8_t* src = s < full ? pool[(first_slot + s) % n_pool] : tail;
-                if (cfg_.raw()) {                                                             // the block's left frames, then its right frames, at the camera's size
+                if (cfg_.fisheye_raw()) {                                                     // the block's up frames, then its down frames, of the fisheye camera's size
+                    if (from_host) lane->cam.enqueue_fisheye_host(flatten_[0]->handle(), flatten_[1]->handle(), src, src + (size_t)want * img, cfg_.fisheye_src_width, want, cfg_.fisheye_first_view, true);
+                    else lane->cam.enqueue_fisheye_dev(flatten_[0]->handle(), flatten_[1]->handle(), src, src + (size_t)want * img, cfg_.fisheye_src_width, want, cfg_.fisheye_first_view, true);
+                }
+                else if (cfg_.resized()) {                                                    // the block's left frames, then its right frames, at the camera's size
                     if (from_host) lane->cam.enqueue_raw_host(lane->resize->handle(), src, src + (size_t)want * img, cfg_.src_width, want);
                     else lane->cam.enqueue_raw_dev(lane->resize->handle(), src, src + (size_t)want * img, cfg_.src_width, want);
                 }
@@ -660,7 +713,7 @@ public:
 
     // one key frame as SwarmLoop::VIOKF_callback hands it on (swarm_loop.cpp:140-170): the flattened views -- images[0..dirs) = up cameras, images[dirs..2*dirs)
     // = down cameras (PINHOLE_DEPTH: the one gray image; STEREO_PINHOLE: images[0] = the left frame, images[1] = the right frame, of the camera's size when
-    // Config::src_width is set), each Config::in_height() rows of `stride` bytes -- the key-frame id and stamp (StereoFrame::keyframe_id,
+    // Config::src_width is set; the raw-fisheye mode: images[0] = the up frame, images[1] = the down frame of the fisheye camera's size), each Config::in_height() rows of `stride` bytes -- the key-frame id and stamp (StereoFrame::keyframe_id,
     // ::stamp), VIO's pose, and prevent_adding_db (:156: a non-key frame that moved less than min_movement_keyframe is matched but not added);
     // depth: PINHOLE_DEPTH's 16-bit depth image (rows packed), borrowed until the key frame's unit is finished
     struct KeyframeIn {
@@ -683,8 +736,8 @@ public:
         if (jpg && (!k.images || !k.sizes)) throw std::invalid_argument("push_keyframe: compressed_images is set: no files / no sizes");
         if (!jpg && k.sizes) throw std::invalid_argument("push_keyframe: JPEG files for a pipeline that takes pixels (compressed_images is off, or ignored in this mode)");
         if (!jpg && (!k.images || k.stride < cfg_.in_width())) throw std::invalid_argument("push_keyframe: no images / a row stride below the image width");
-        const int MB = cfg_.microbatch, nd = cfg_.dirs(), cams = cfg_.stereo() ? 2 : 1;
-        for (int i = 0; i < cams * nd; ++i) if (!k.images[i] || (jpg && k.sizes[i] < 0)) throw std::invalid_argument("push_keyframe: a null image pointer");
+        const int MB = cfg_.microbatch, nd = cfg_.frames_per_camera(), cams = cfg_.stereo() ? 2 : 1;      // nd: images per camera and key frame
+        for (int i = 0; i < cfg_.frames_per_keyframe(); ++i) if (!k.images[i] || (jpg && k.sizes[i] < 0)) throw std::invalid_argument("push_keyframe: a null image pointer");
         const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         if (cfg_.camera_configuration == 0) first_keyframe_seen_ = true;      // (set_stereo_extrinsics is refused from here on)
         any_keyframe_seen_ = true;
@@ -709,7 +762,7 @@ public:
         }
         const int m = (int)open_->meta.size();
         if (m >= MB) throw std::logic_error("push_keyframe: the open micro-batch is already full");      // (cannot happen: a full unit leaves below, whatever throws)
-        for (int c = 0; c < cams && jpg; ++c) open_->jfiles[c].emplace_back(k.images[c], k.images[c] + k.sizes[c]);      // (nd = 1 in both configurations)
+        for (int c = 0; c < cams && jpg; ++c) open_->jfiles[c].emplace_back(k.images[c], k.images[c] + k.sizes[c]);      // (nd = 1 wherever files are taken)
         for (int c = 0; c < cams && !jpg; ++c)
             for (int d = 0; d < nd; ++d) {
                 uint8_t* dst = open_->stage + ((size_t)c * nd * MB + (size_t)nd * m + d) * img;
@@ -777,7 +830,7 @@ private:
               vlad(one_stream ? sp_ctx : vlad_ctx, c.vlad_weights, c.width, c.height, false, c.dirs() * mb_),
               cam(sp_ctx, sp, one_stream ? sp_ctx : vlad_ctx, vlad, c.dirs() * mb_, c.max_num, c.width, c.height, !c.stereo()) {
             check(omni_vlad_dev_output(vlad.handle(), &rows_dev), "omni_vlad_dev_output");
-            if (c.raw()) resize = std::make_unique<ResizeHIP>(sp_ctx, c.src_width, c.src_height, c.width, c.height);
+            if (c.resized()) resize = std::make_unique<ResizeHIP>(sp_ctx, c.src_width, c.src_height, c.width, c.height);
             cur = mb_;
         }
         void sync() { check(omni_ctx_sync(sp_ctx.get()), "sync"); check(omni_ctx_sync(vlad_ctx.get()), "sync"); }
@@ -806,10 +859,10 @@ private:
     void dispatch_open() {
         Lane* u = open_;
         open_ = nullptr;
-        const int MB = cfg_.microbatch, nd = cfg_.dirs(), rem = (int)u->meta.size();
+        const int MB = cfg_.microbatch, nd = cfg_.dirs(), nf = cfg_.frames_per_camera(), rem = (int)u->meta.size();
         const size_t img = (size_t)cfg_.in_width() * cfg_.in_height();
         try {
-            if (!compressed() && rem < MB && cfg_.stereo()) std::memmove(u->stage + (size_t)nd * rem * img, u->stage + (size_t)nd * MB * img, (size_t)nd * rem * img);
+            if (!compressed() && rem < MB && cfg_.stereo()) std::memmove(u->stage + (size_t)nf * rem * img, u->stage + (size_t)nf * MB * img, (size_t)nf * rem * img);
             if (u->cur != rem) { u->cam.set_active(nd * rem); u->cur = rem; }
             chain(u, fifo_cfg_ >= 0 ? fifo_cfg_ : (cfg_.precision == OMNI_PREC_F16 ? 0 : 1));
             unit_poses(u, rem, 0);
@@ -820,7 +873,9 @@ private:
                     for (const auto& f : u->jfiles[c]) { fp[c].push_back(f.data()); fs[c].push_back((int64_t)f.size()); }
                 enqueue_files(u, fp, fs);
             }
-            else if (cfg_.raw()) u->cam.enqueue_raw_host(u->resize->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.src_width, rem);
+            else if (cfg_.fisheye_raw())
+                u->cam.enqueue_fisheye_host(flatten_[0]->handle(), flatten_[1]->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.fisheye_src_width, rem, cfg_.fisheye_first_view, true);
+            else if (cfg_.resized()) u->cam.enqueue_raw_host(u->resize->handle(), u->stage, u->stage + (size_t)rem * img, cfg_.src_width, rem);
             else u->cam.enqueue_host(u->stage, cfg_.width, cfg_.masked());
         } catch (...) { u->meta.clear(); throw; }
         stream_pending_.push_back(u);
@@ -830,7 +885,8 @@ private:
         static const uint8_t kNothing = 0;
         for (int c = 0; c < 2; ++c)
             for (auto& p : fp[c]) if (!p) p = &kNothing;
-        u->cam.enqueue_jpeg_async(u->resize ? u->resize->handle() : nullptr, fp[0], fs[0], fp[1], fs[1]);
+        if (cfg_.fisheye_raw()) u->cam.enqueue_fisheye_jpeg_async(flatten_[0]->handle(), flatten_[1]->handle(), fp[0], fs[0], fp[1], fs[1], cfg_.fisheye_first_view, true);
+        else u->cam.enqueue_jpeg_async(u->resize ? u->resize->handle() : nullptr, fp[0], fs[0], fp[1], fs[1]);
         u->jpeg_frames = (int)(fp[0].size() + fp[1].size());
     }
     // finishes, oldest first, the units the GPU is done with (never waits for a CNN unit); with nothing left in flight also the detector step enqueued
@@ -1065,6 +1121,7 @@ private:
     const uint16_t* depth_ = nullptr;           // PINHOLE_DEPTH: borrowed depth images (set_depth)
     int64_t depth_base_ = 0, depth_n_ = 0;
     int geometry_calls_ = 0;
+    std::unique_ptr<FlattenHIP> flatten_[2];    // the raw-fisheye mode: the up and the down camera's maps, read by every lane's units (declared before the lanes: outlive their streams)
     std::vector<std::unique_ptr<Lane>> lanes_;
     std::map<int, std::unique_ptr<Lane>> tail_lanes_;
     double host_ms_[5] = {0, 0, 0, 0, 0};

@@ -274,6 +274,25 @@ private:
     omni_resize* h_ = nullptr;
 };
 
+// one fisheye camera's undistortion maps in HBM (omni_flatten_*): view v is view_w[v] x view_h[v], map_xy[v] its [h][w][2] float source coordinates
+// (host/fisheye_flatten.hpp makes them); LoopCamHIP::enqueue_fisheye_* runs the remap inside a key-frame unit
+class FlattenHIP {
+public:
+    FlattenHIP(Context& ctx, int src_width, int src_height, const std::vector<int>& view_w, const std::vector<int>& view_h, const std::vector<std::vector<float>>& map_xy) {
+        std::vector<const float*> maps;
+        for (const auto& m : map_xy) maps.push_back(m.data());
+        if (view_w.size() != maps.size() || view_h.size() != maps.size()) throw std::invalid_argument("FlattenHIP: one width, height and map per view");
+        h_ = omni_flatten_create(ctx.get(), src_width, src_height, (int)maps.size(), view_w.data(), view_h.data(), maps.data());
+        if (!h_) throw std::runtime_error(std::string("omni_flatten_create: ") + omni_last_error());
+    }
+    ~FlattenHIP() { omni_flatten_destroy(h_); }
+    FlattenHIP(const FlattenHIP&) = delete;
+    FlattenHIP& operator=(const FlattenHIP&) = delete;
+    omni_flatten* handle() const { return h_; }
+private:
+    omni_flatten* h_ = nullptr;
+};
+
 // The CNN + matching part of LoopCam::on_flattened_images (loop_cam.cpp:178-229): SuperPoint on the 2*n_dirs images of one
 // fisheye key frame (up cameras, then down cameras), MobileNetVLAD on the n_dirs up images, BFMatcher(L2, crossCheck) up <->
 // down per direction -- one asynchronous unit on the GPU (omni_cam_*), results in one pinned host block.  The reference runs
@@ -351,6 +370,16 @@ public:
         check(omni_cam_enqueue_jpeg_host(h_, resize, left_files.data(), left_sizes.data(), right_files.empty() ? nullptr : right_files.data(),
                                          right_files.empty() ? nullptr : right_sizes.data(), (int)left_files.size()),
               "omni_cam_enqueue_jpeg_host");
+    }
+    // STEREO_FISHEYE with compressed frames: each camera's RAW frames as JPEG files, decoded and flattened inside the unit (omni_cam_enqueue_fisheye_jpeg_host);
+    // jpegdec_status(2 * files per camera) after wait().  up / down outlive wait().
+    void enqueue_fisheye_jpeg_async(omni_flatten* up, omni_flatten* down, const std::vector<const uint8_t*>& up_files, const std::vector<int64_t>& up_sizes,
+                                    const std::vector<const uint8_t*>& down_files, const std::vector<int64_t>& down_sizes, int first_view = 1, bool fisheye_mask = true) {
+        if (up_files.size() != down_files.size() || up_files.size() != up_sizes.size() || down_files.size() != down_sizes.size())
+            throw std::runtime_error("enqueue_fisheye_jpeg_async: as many up files as down files, one size per file");
+        check(omni_cam_enqueue_fisheye_jpeg_host(h_, up, down, up_files.data(), up_sizes.data(), down_files.data(), down_sizes.data(), (int)up_files.size(), first_view,
+                                                 fisheye_mask ? 1 : 0),
+              "omni_cam_enqueue_fisheye_jpeg_host");
     }
     std::vector<int> jpegdec_status(int n_frames) {
         std::vector<int> st((size_t)n_frames);

@@ -43,6 +43,10 @@ JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
 JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
                    "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
 _jpegdec_lib = None
+# STEREO_FISHEYE fed the fisheye camera's own frames: include/omni_host_fisheye.h, lib/libomni_host_fisheye.so (the same handle)
+FISHEYE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_fisheye.so")
+FISHEYE_SYMBOLS = ["omni_fisheye_last_error", "omni_pipeline_create_stereo_fisheye_raw", "omni_pipeline_get_fisheye_raw"]
+_fisheye_lib = None
 
 
 def lib():
@@ -105,6 +109,23 @@ def stereo_lib():
         L.omni_pipeline_set_stereo_extrinsics.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _stereo_lib = L
     return _stereo_lib
+
+
+def fisheye_lib():
+    """libomni_host_fisheye.so (include/omni_host_fisheye.h): the raw-fisheye mode of the key-frame pipeline"""
+    global _fisheye_lib
+    if _fisheye_lib is None:
+        if not os.path.exists(FISHEYE_LIB_PATH):
+            raise OSError(f"{FISHEYE_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        lib()
+        L = C.CDLL(FISHEYE_LIB_PATH)
+        L.omni_fisheye_last_error.restype = C.c_char_p
+        L.omni_pipeline_create_stereo_fisheye_raw.restype = C.c_void_p
+        L.omni_pipeline_create_stereo_fisheye_raw.argtypes = lib().omni_pipeline_create.argtypes + [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                                                                  C.c_int]
+        L.omni_pipeline_get_fisheye_raw.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _fisheye_lib = L
+    return _fisheye_lib
 
 
 def _err(what):
@@ -224,7 +245,7 @@ class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -238,12 +259,24 @@ class KeyframePipeline:
         threads (the same edges either way); None: the library's default, which is off.
         send_img / jpg_quality: the reference's switch of the same name (default off, quality 50): the main image of every direction goes into its message as a
         JPEG file, encoded inside the key-frame unit on the GPU (set_send_img).
+        raw_fisheye: a dict(src_width, src_height, fov_deg, mei_up, mei_down[, first_view]) = CameraConfig::STEREO_FISHEYE fed the fisheye camera's own frames:
+        ONE up frame and ONE down frame of src_width x src_height per key frame, flattened into the four side views (width x height) inside every unit, on the
+        GPU; mei_up / mei_down: the cameras' nine MEI parameters as flatten.generate_undist_maps takes them.  With compressed_images the two frames are JPEG
+        files (push_keyframe_jpeg, run_jpeg).  The reference has no such path: its upstream (VINS-Fisheye) flattens.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
                   precision, microbatch, pipelines, storage, self_id, inner_product_thres, init_mode_product_thres, match_index_dist, min_loop_num,
                   min_direction_loop, int(geometry))
-        if stereo_pinhole is not None:
+        if raw_fisheye is not None:
+            if pinhole_depth is not None or stereo_pinhole is not None:
+                raise ValueError("raw_fisheye belongs to STEREO_FISHEYE: neither pinhole_depth nor stereo_pinhole")
+            d = raw_fisheye
+            up9, down9 = ((C.c_double * 9)(*[float(v) for v in d[k]]) for k in ("mei_up", "mei_down"))
+            self.h = fisheye_lib().omni_pipeline_create_stereo_fisheye_raw(*common, d["src_width"], d["src_height"], d["fov_deg"], up9, down9, d.get("first_view", 1))
+            if not self.h:
+                raise capi.OmniError(f"omni_pipeline_create_stereo_fisheye_raw: {fisheye_lib().omni_fisheye_last_error().decode()}")
+        elif stereo_pinhole is not None:
             if pinhole_depth is not None:
                 raise ValueError("pinhole_depth and stereo_pinhole are two camera configurations")
             d = stereo_pinhole
@@ -283,8 +316,16 @@ class KeyframePipeline:
     def set_compressed_images(self, on: bool):
         """is_compressed_images: every following key frame comes as JPEG files (push_keyframe with bytes, run_jpeg), decoded on the GPU inside the key-frame unit in
         front of the resize (csrc/jpeg_dec.hip; libjpeg-turbo's gray pixels, pinned against Pillow -- cv::imdecode's own parity is unpinned).  Before the first
-        key frame.  STEREO_PINHOLE and PINHOLE_DEPTH; ignored by STEREO_FISHEYE and under a sharded database."""
+        key frame.  STEREO_PINHOLE, PINHOLE_DEPTH and STEREO_FISHEYE in its raw-fisheye mode; ignored by a flattened-view STEREO_FISHEYE pipeline and under a
+        sharded database."""
         self._jpegdec(jpegdec_lib().omni_pipeline_set_compressed_images(self.h, int(bool(on))), "omni_pipeline_set_compressed_images")
+
+    def fisheye_raw(self):
+        """(src_width, src_height) of a raw-fisheye pipeline, (0, 0) of every other"""
+        w, h = C.c_int(0), C.c_int(0)
+        if fisheye_lib().omni_pipeline_get_fisheye_raw(self.h, C.byref(w), C.byref(h)):
+            raise capi.OmniError(f"omni_pipeline_get_fisheye_raw: {fisheye_lib().omni_fisheye_last_error().decode()}")
+        return w.value, h.value
 
     def apply_vins_settings(self, vins_yaml_text: str):
         """sets the switch from the VINS settings file's is_compressed_images"""
