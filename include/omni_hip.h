@@ -618,7 +618,13 @@ int        omni_cam_jpeg(omni_cam* cam, omni_cam_jpeg_result* out);
  *   OMNI_JPEGDEC_HOST         a valid baseline file the kernels do not take (restart interval, several scans, other sampling, a file above the handle's capacity):
  *                             decoded on the calling thread by the g++ build, its pixels uploaded
  *   OMNI_JPEGDEC_UNSUPPORTED  progressive, arithmetic, lossless, 12-bit, 16-bit quantisation tables, a component count other than 1 or 3: refused
- *   OMNI_JPEGDEC_CORRUPT      not a decodable file, or a scan that errs or ends before the picture's last block: the picture is ALL ZEROS */
+ *   OMNI_JPEGDEC_CORRUPT      not a decodable file, or a scan that errs or ends before the picture's last block: the picture is ALL ZEROS
+ * Restart intervals: OMNI_JPEGDEC_RESTART_WGS (0..64, default 0), as it is when the handle is created.  0: as listed above.  W >= 1: a file whose ONLY obstacle is
+ * its restart interval (DRI) is decoded by the kernels and reports OMNI_JPEGDEC_OK; its intervals -- independent streams: byte-aligned, known entry state, DC
+ * predictor zero, known first block -- are spread over at most W workgroups balanced by bits.  The pixels are the same.  Such a file stays HOST when it cannot be
+ * planned (more intervals in one workgroup's share than that workgroup holds subsequences: 4096), and is CORRUPT when its scan holds fewer restart markers than
+ * ceil(MCUs / interval) - 1 or when an interval's bits end before its blocks do (there the host decoder reads on into the next interval: the one divergence;
+ * libjpeg's own resynchronisation is UNPINNED either way).  Surplus markers are ignored. */
 #define OMNI_JPEGDEC_OK 0
 #define OMNI_JPEGDEC_HOST 1
 #define OMNI_JPEGDEC_UNSUPPORTED 2
@@ -638,6 +644,9 @@ int           omni_jpegdec_enqueue_host(omni_jpegdec* d, const uint8_t* const* f
 /* Of the handle's last enqueue, after a synchronisation with the context's stream: per image the relaxation rounds that changed something, the number of
  * subsequences and their length in bits (0 0 0 for an image the kernels did not decode).  Each output [n_images] or null. */
 int           omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subseq, int* subseq_bits);
+/* ... and the workgroups of the entropy kernel that decoded a share of each image (counted on the GPU): 1, or the chunks of a restart-interval file; 0 for an
+ * image the kernels did not decode.  A restart-interval file's rounds above are the maximum over its chunks, its subsequences their total.  chunks [n_images] */
+int           omni_jpegdec_last_chunks(omni_jpegdec* d, int* chunks);
 /* MEASUREMENT: of the handle's last enqueue, once it has run: the time of its upload and of everything behind it (memsets + kernels) on the GPU, and the bytes it
  * uploaded (tools/jpegdec_timing.py) */
 int           omni_jpegdec_last_ms(omni_jpegdec* d, float* upload_ms, float* kernels_ms, int64_t* uploaded_bytes);
@@ -655,6 +664,12 @@ int           omni_jpeg_decode_host(const uint8_t* file, int64_t size, uint8_t* 
  * stats[4] = subsequences, their length, relaxation rounds that changed something, subsequences whose first-pass exit state was wrong */
 int           omni_jpeg_decode_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, uint8_t* out, int stride, int* width, int* height, int* status,
                                              int* stats);
+/* TEST INFRASTRUCTURE: the CPU stand-in for the kernels of a handle with OMNI_JPEGDEC_RESTART_WGS = restart_wgs (1..64), where a workgroup holds at most max_subseq
+ * subsequences (the kernels: 4096): the chunk plan and the same phase functions by plain loops (jpeg_decode_restart_parallel_host).  A file without a restart
+ * interval goes the way of omni_jpeg_decode_parallel_host.  stats[4] = subsequences, their length, chunks, the maximum over the chunks of the relaxation rounds
+ * that changed something (0 0 0 0 for a file the plan leaves to the host) */
+int           omni_jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int restart_wgs, int max_subseq, uint8_t* out, int stride,
+                                                     int* width, int* height, int* status, int* stats);
 
 /* The same stage inside the key-frame unit: a unit whose frames arrive as JPEG files.  The decode runs on the unit's SuperPoint stream in front of the resize, and
  * the decoded frames take the place of omni_cam_enqueue_raw_*'s: n_keyframes left files and as many right files for a stereo handle (STEREO_PINHOLE), left files

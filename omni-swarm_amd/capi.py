@@ -46,7 +46,7 @@ SYMBOLS = [
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
     "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
-    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
+    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_jpeg_decode_restart_parallel_host", "omni_jpegdec_last_chunks", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
 ]
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
@@ -254,6 +254,8 @@ def lib():
     sig("omni_cam_jpegdec_status", C.c_int, [_vp, _ip, C.c_int])
     sig("omni_cam_enqueue_fisheye_jpeg_host", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp), _i64p, C.POINTER(_vp), _i64p, C.c_int, C.c_int, C.c_int])
     sig("omni_jpeg_decode_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
+    sig("omni_jpeg_decode_restart_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
+    sig("omni_jpegdec_last_chunks", C.c_int, [_vp, _ip])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
     sig("omni_cam_ready", C.c_int, [_vp, C.POINTER(C.c_int)])
@@ -940,6 +942,18 @@ def jpeg_decode_parallel_host(data: bytes, subseq_bits: int):
     return status, pix, dict(n_sub=stats[0], subseq_bits=stats[1], rounds=stats[2], wrong_after_first=stats[3])
 
 
+JPEGDEC_MAX_SUBSEQ = 4096                     # csrc/jpeg_dec_plan.h JD_MAX_SUBSEQ: subsequences one workgroup of the entropy kernel holds
+
+
+def jpeg_decode_restart_parallel_host(data: bytes, subseq_bits: int, restart_wgs: int, max_subseq: int = JPEGDEC_MAX_SUBSEQ):
+    """the CPU stand-in for the kernels of a handle with OMNI_JPEGDEC_RESTART_WGS = restart_wgs -> (status, gray, dict(n_sub, subseq_bits, chunks, rounds)): a
+    restart-interval file is planned into chunks and decoded by the phase functions (OK), or left to the sequential decoder when it cannot be planned (HOST)"""
+    stats = (C.c_int * 4)()
+    status, pix = _jpeg_decode(data, 0, lambda o, st, w, h, s: lib().omni_jpeg_decode_restart_parallel_host(data, len(data), subseq_bits, restart_wgs, max_subseq, o, st,
+                                                                                                           w, h, s, stats))
+    return status, pix, dict(n_sub=stats[0], subseq_bits=stats[1], chunks=stats[2], rounds=stats[3])
+
+
 class JpegDec:
     """omni_jpegdec: up to max_images JPEG files of at most capacity_per_image bytes -> gray images of width x height on the GPU (is_compressed_images;
     csrc/jpeg_dec.hip, the arithmetic: csrc/jpeg_dec_plan.h)"""
@@ -975,6 +989,12 @@ class JpegDec:
         r, s, b = (C.c_int * self.max_images)(), (C.c_int * self.max_images)(), (C.c_int * self.max_images)()
         _check(lib().omni_jpegdec_last_stats(self.h, r, s, b))
         return [(r[i], s[i], b[i]) for i in range(n)]
+
+    def last_chunks(self, n: int):
+        """per image of the last call: the entropy kernel's workgroups that decoded a share of it (the chunks of a restart-interval file)"""
+        k = (C.c_int * self.max_images)()
+        _check(lib().omni_jpegdec_last_chunks(self.h, k))
+        return [k[i] for i in range(n)]
 
     def last_ms(self):
         """(upload ms, memsets + kernels ms, bytes uploaded) of the last call, on the GPU's clock"""

@@ -77,6 +77,9 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
     // ---- JPEG decode -----------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_JPEGDEC_SUBSEQ_BITS", 1024, 128, 65536, CFG_TUNING, "omni_jpegdec: bits per subsequence of the entropy kernel's self-synchronising decode, a power of two (csrc/jpeg_dec_plan.h); "
                                                                "an image of more than 4096 subsequences is decoded with the next power of two that gives fewer.  Same pixels for every value"},
+    {"OMNI_JPEGDEC_RESTART_WGS", 0, 0, 64, CFG_TUNING, "omni_jpegdec: 0 = a file with a restart interval (DRI) is decoded on the calling thread (HOST); W >= 1 = one whose only obstacle is "
+                                                       "the interval is decoded by the kernels (OK), its intervals -- independent streams -- spread over at most W workgroups balanced by "
+                                                       "bits (csrc/jpeg_dec_plan.h plan_chunks); a file that cannot be planned stays HOST.  Same pixels for every value"},
     // ---- runtime ---------------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_HW_QUEUES", 8, 0, 64, CFG_TUNING, "hardware queues asked of the HIP runtime when the library is loaded (GPU_MAX_HW_QUEUES, unless already set): the pipeline's five "
                                             "streams must not share one; 0 = the runtime's default of 4"},

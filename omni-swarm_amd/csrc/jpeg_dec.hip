@@ -1,39 +1,45 @@
 // omni_jpegdec_*: camera frames that arrive as baseline JPEG files (is_compressed_images: cv::imdecode(data, IMREAD_GRAYSCALE), swarm_loop.cpp:72-89) become gray
 // images on the GPU.  The arithmetic, the symbol step and the parallel scheme are jpeg_dec_plan.h's -- this file only spreads them over lanes:
-//   entropy  ONE workgroup per image, phases 1-4 of the plan in one launch.  A Huffman scan is one sequential bit stream: it is cut into subsequences of S bits,
+//   entropy  ONE workgroup per CHUNK of an image, phases 1-4 of the plan in one launch; grid (most chunks of a picture, images).  A picture without a restart
+//            interval is one chunk.  A restart-interval file (OMNI_JPEGDEC_RESTART_WGS = W >= 1, snapshotted by the handle; 0: such files are decoded on the host)
+//            is up to W chunks of consecutive intervals: every interval is a stream of its own (byte-aligned, entry state 0, DC predictor 0, first block known), so
+//            no workgroup reads what another wrote and NONE WAITS FOR ANOTHER -- they meet only in three atomically combined words per picture (error bits OR,
+//            rounds max, chunks that ran) zeroed on the stream; the status is derived once, by the DC kernel.  Inside a chunk:
+//            a Huffman stream is sequential: it is cut into subsequences of S bits,
 //            every lane decodes subsequences from a guessed state, and relaxation rounds repeat those whose predecessor's exit state changed until a round changes
 //            nothing (self-synchronisation; at most N rounds, a fixed point IS the sequential decode).  Exit states, entry states and block counts live in LDS; the
 //            round loop is workgroup-uniform (__syncthreads + an LDS flag).  Then the exclusive scan of the block counts, and the write pass: the first component's
 //            coefficients straight to global memory (zeroed before), every index checked against the image's block count;
-//   dc       one workgroup per image: the scan of the DC differences in scan order;
+//   dc       one workgroup per image: the status, then the scan of the DC differences in scan order -- segmented at every restart interval's first block;
 //   block    across all images, one 8 x 8 block per lane: dequantise, islow IDCT, clamp, store cropped.  A CORRUPT image is written as zeros; the pixels of a
 //            file the host decoded are copied from the uploaded block.
-// The host side parses, unstuffs the scans into the handle's pinned block and uploads it once.  Everything runs on the caller's stream.
+// The host side parses, unstuffs the scans into the handle's pinned block (a planned restart file: + its interval and chunk tables behind its scan) and uploads it once.
+// Everything runs on the caller's stream.
 #include "common.h"
 #include "config.h"
 #include "jpeg_dec_plan.h"
 
 #define JD_THREADS 256
-#define JD_MAX_SUBSEQ 4096                 // per image: 16 per lane (the lane's `need` bits); an image with more is decoded with a longer subsequence
+static_assert(JD_MAX_SUBSEQ == 16 * JD_THREADS, "16 subsequences per lane: the lane's `need` bits");      // per workgroup; more: a longer subsequence
 #define JD_BLOCK_THREADS 256
 
 struct omni_jpegdec {
     omni_ctx* ctx = nullptr;
-    int w = 0, h = 0, max_images = 0, subseq_bits = 0;
+    int w = 0, h = 0, max_images = 0, subseq_bits = 0, restart_wgs = 0;
     int64_t capacity = 0;
     uint32_t nyb_max = 0;                  // blocks of the first component of a w x h picture with 16 x 16 MCUs
-    size_t in_bytes = 0;
+    size_t in_bytes = 0, tab_bytes = 0;    // tab_bytes: room for one picture's interval and chunk tables (restart_wgs >= 1)
     omni::DevMem mem;
     uint8_t* d_in = nullptr;               // the uploaded block: descriptors | clean scans | host-decoded pixels
     int16_t* d_coef = nullptr;             // [max_images][nyb_max][64] + guard
     int32_t* d_dc = nullptr;               // [max_images][nyb_max] + guard
-    int* d_rounds = nullptr;               // [max_images]
+    int* d_flags = nullptr;                // [3][max_images]: error bits, relaxation rounds, chunks that ran -- zeroed in front of every entropy launch
     omni::HostBuf hin;
     hipEvent_t ev_upload = nullptr;        // the pinned block is free again
     hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};      // in front of the upload, behind it, behind the kernels (omni_jpegdec_last_ms)
     size_t last_bytes = 0;
     bool timed = false;                    // ev_t hold ONE call's three events
-    int last_n = 0;
+    int last_n = 0, last_chunks = 1;       // last_chunks: the most chunks of a picture of the last pack (the entropy kernel's grid)
     std::mutex mu;
 };
 
@@ -64,19 +70,31 @@ __device__ __forceinline__ uint32_t jd_wg_scan(uint32_t v, uint32_t* lds, uint32
     return r;
 }
 
+// The interval table of a picture as the entropy kernel sees it: a planned restart file's own table, or -- no restart interval -- the whole scan as ONE interval
+struct JdIntervals {
+    const jd::Interval* iv;                                 // null: one interval over the whole scan
+    uint32_t total_bits, n_sub, n_blocks;
+    __device__ __forceinline__ jd::Interval at(uint32_t k) const {
+        if (iv) return iv[k];
+        return k == 0 ? jd::Interval{0u, total_bits, 0u, 0u} : jd::Interval{total_bits, total_bits, n_sub, n_blocks};
+    }
+};
+
+// flags: [3][max_images] int32 zeroed on the stream in front of the launch -- error bits (OR), relaxation rounds (max), chunks that ran (+1): a picture's
+// workgroups meet nowhere else, and none waits for another
 __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8_t* __restrict__ in, int16_t* __restrict__ coef, int32_t* __restrict__ dcd,
-                                                                     uint32_t nyb_max, int* __restrict__ status, int* __restrict__ rounds_out) {
+                                                                     uint32_t nyb_max, int* __restrict__ flags, int max_images) {
     __shared__ jd::Tables T;
-    __shared__ uint16_t ex[JD_MAX_SUBSEQ], used[JD_MAX_SUBSEQ];
+    __shared__ uint16_t ex[JD_MAX_SUBSEQ], used[JD_MAX_SUBSEQ], of[JD_MAX_SUBSEQ];          // of: a subsequence's interval, counted from the chunk's first
     __shared__ uint32_t cnt[JD_MAX_SUBSEQ];
     __shared__ uint32_t lds[JD_THREADS / 64 + 1];
     __shared__ int changed, errflag;
-    const int img = blockIdx.x, tid = threadIdx.x;
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const uint32_t chunk = blockIdx.x;
     const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
-    if (d->mode != jd::JD_MODE_DECODE) {                                                    // (uniform: the whole workgroup leaves)
-        if (tid == 0) { status[img] = d->status; rounds_out[img] = 0; }
-        return;
-    }
+    if (d->mode != jd::JD_MODE_DECODE) return;                                              // (uniform: the whole workgroup leaves; the DC kernel writes the status)
+    const uint32_t n_int = d->n_int, n_chunks = n_int ? d->n_chunks : 1u;
+    if (chunk >= n_chunks) return;                                                          // (uniform)
     {
         const uint32_t* s = reinterpret_cast<const uint32_t*>(&d->T);
         uint32_t* t = reinterpret_cast<uint32_t*>(&T);
@@ -84,32 +102,45 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8
     }
     if (tid == 0) { changed = 0; errflag = 0; }
     const uint32_t S = d->subseq_bits, total_bits = d->total_bits, n_blocks = d->n_blocks;
-    const uint32_t N = d->n_sub < JD_MAX_SUBSEQ ? d->n_sub : JD_MAX_SUBSEQ;                 // (the host made n_sub <= JD_MAX_SUBSEQ; the LDS arrays hold no more)
+    JdIntervals ivs{n_int ? reinterpret_cast<const jd::Interval*>(in + d->tab_off) : nullptr, total_bits, d->n_sub, n_blocks};
+    uint32_t k0 = 0, k1 = 1;                                                                // the chunk's intervals [k0, k1)
+    if (n_int) {
+        const uint32_t* cf = reinterpret_cast<const uint32_t*>(ivs.iv + n_int + 1);
+        k0 = cf[chunk]; k1 = cf[chunk + 1];
+        if (k1 > n_int) k1 = n_int;
+        if (k0 >= k1) return;                                                               // (uniform; the host plans no empty chunk)
+    }
+    const uint32_t sub0 = ivs.at(k0).first_sub, sub1 = ivs.at(k1).first_sub;
+    const uint32_t N = sub1 - sub0 < JD_MAX_SUBSEQ ? sub1 - sub0 : JD_MAX_SUBSEQ;           // (the host made every chunk <= JD_MAX_SUBSEQ; the LDS arrays hold no more)
     const uint8_t* scan = in + d->dev_off;
     const uint32_t n_words = jd::scan_words((int64_t)(total_bits >> 3));
     __syncthreads();
     jd::NoEmit none;
     int e;
     for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 1: every subsequence from the guess
+        const uint32_t k = ivs.iv ? jd::interval_of(ivs.iv, k0, k1, sub0 + i) : 0u;
+        const jd::Interval I = ivs.at(k);
         uint16_t x;
-        cnt[i] = jd::decode_subseq(T, scan, n_words, total_bits, i, S, (uint16_t)0, 0u, 0xffffffffu, none, &x, &e);
+        cnt[i] = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, (uint16_t)0, 0u, 0xffffffffu, none, &x, &e);
         ex[i] = x;
         used[i] = 0;
+        of[i] = (uint16_t)(k - k0);
     }
     __syncthreads();
     int rounds = 0;
     for (uint32_t r = 0; r < N; ++r) {                                                      // 2: relaxation; every lane runs the same number of rounds
         uint32_t need = 0;
         for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
-            if (i == 0) continue;
+            if (i == 0 || of[i] != of[i - 1]) continue;                                     // the first of its interval: the entry 0 is the true one
             const uint16_t en = ex[i - 1];
             if (en != used[i]) { used[i] = en; need |= 1u << k; }
         }
         __syncthreads();                                                                    // every entry is read before any exit is written
         for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
             if (!(need >> k & 1u)) continue;
+            const jd::Interval I = ivs.at(k0 + of[i]);
             uint16_t x;
-            const uint32_t c = jd::decode_subseq(T, scan, n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, &x, &e);
+            const uint32_t c = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, used[i], 0u, 0xffffffffu, none, &x, &e);
             if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = 1; }
         }
         __syncthreads();
@@ -120,7 +151,7 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8
         ++rounds;
     }
     __syncthreads();
-    uint32_t carry = 0;                                                                     // 3: counts -> first blocks, in place
+    uint32_t carry = 0;                                                                     // 3: counts -> their exclusive prefix over the chunk, in place
     for (uint32_t base = 0; base < N; base += JD_THREADS) {
         const uint32_t i = base + tid;
         uint32_t sum;
@@ -130,39 +161,60 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8
     }
     __syncthreads();
     int err = 0;
-    for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 4: the write pass
+    for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 4: the write pass, every interval bounded to its own blocks
+        const uint32_t k = k0 + of[i];
+        const jd::Interval I = ivs.at(k), next = ivs.at(k + 1);
+        const uint32_t j = sub0 + i - I.first_sub;
+        // the first block: the interval's + the counts before the subsequence INSIDE the interval (i - j: the interval's first subsequence, in this chunk)
+        const uint32_t fb = I.first_block + (cnt[i] - cnt[i - j]);
+        const uint32_t max_blocks = next.first_block < n_blocks ? next.first_block : n_blocks;
         jd::CoefEmit em;
         em.coef = coef + (size_t)img * nyb_max * 64;
         em.dcd = dcd + (size_t)img * nyb_max;
         em.n_yblocks = d->n_yblocks < nyb_max ? d->n_yblocks : nyb_max;
-        const uint16_t entry = i == 0 ? (uint16_t)0 : used[i];
-        em.start(T, cnt[i], entry >> 12);
+        const uint16_t entry = j == 0 ? (uint16_t)0 : used[i];
+        em.start(T, fb, entry >> 12);
         uint16_t x;
-        jd::decode_subseq(T, scan, n_words, total_bits, i, S, entry, cnt[i], n_blocks, em, &x, &e);
+        const uint32_t wrote = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, j, S, entry, fb, max_blocks, em, &x, &e);
         err |= e;
+        if (sub0 + i + 1 == next.first_sub && fb + wrote < max_blocks) err = 1;             // the interval's bits end before its blocks do
     }
     if (err) atomicOr(&errflag, 1);
     __syncthreads();
     if (tid == 0) {
-        status[img] = (errflag || carry < n_blocks) ? OMNI_JPEGDEC_CORRUPT : d->status;
-        rounds_out[img] = rounds;
+        // (an empty scan completes no block; a chunk above the LDS arrays -- the host plans none -- would be decoded in part: CORRUPT, not OK)
+        if (errflag || (N == 0 && n_blocks) || sub1 - sub0 > JD_MAX_SUBSEQ) atomicOr(&flags[img], 1);
+        atomicMax(&flags[max_images + img], rounds);
+        atomicAdd(&flags[2 * max_images + img], 1);
     }
 }
 
-__global__ __launch_bounds__(JD_THREADS) void jpegdec_dc_kernel(const uint8_t* __restrict__ in, int32_t* __restrict__ dcd, uint32_t nyb_max) {
+// one workgroup per image: the status, once, behind every workgroup of the entropy kernel; then the scan of the DC differences in scan order -- with a restart
+// interval a segmented one: the running sum starts again every restart * ny blocks
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_dc_kernel(const uint8_t* __restrict__ in, int32_t* __restrict__ dcd, uint32_t nyb_max, const int* __restrict__ flags,
+                                                                int* __restrict__ status) {
     __shared__ uint32_t lds[JD_THREADS / 64 + 1];
+    __shared__ uint32_t tile[JD_THREADS];
     const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + blockIdx.x;
-    if (d->mode != jd::JD_MODE_DECODE) return;
+    const bool dec = d->mode == jd::JD_MODE_DECODE;
+    if (threadIdx.x == 0) status[blockIdx.x] = dec && flags[blockIdx.x] ? OMNI_JPEGDEC_CORRUPT : d->status;
+    if (!dec) return;
     const uint32_t n = d->n_yblocks < nyb_max ? d->n_yblocks : nyb_max;
+    const uint32_t L = d->n_int ? (uint32_t)d->restart * (uint32_t)d->T.ny : 0u;            // blocks per segment (0: one segment)
     int32_t* v = dcd + (size_t)blockIdx.x * nyb_max;
-    uint32_t carry = 0;
+    uint32_t carry = 0;                                                                     // the sum from the start of the segment that holds `base` up to base - 1
     for (uint32_t base = 0; base < n; base += JD_THREADS) {                                 // (uniform trip count: every lane reaches the barriers)
         const uint32_t i = base + threadIdx.x;
         const uint32_t x = i < n ? (uint32_t)v[i] : 0u;
         uint32_t sum;
-        const uint32_t excl = jd_wg_scan<JD_THREADS>(x, lds, &sum);
-        if (i < n) v[i] = (int32_t)(carry + excl + x);
-        carry += sum;
+        const uint32_t incl = jd_wg_scan<JD_THREADS>(x, lds, &sum) + x;
+        tile[threadIdx.x] = incl;
+        __syncthreads();
+        const uint32_t s = L ? i / L * L : 0u;                                              // the first block of i's segment
+        if (i < n) v[i] = (int32_t)(s <= base ? carry + incl : incl - tile[s - 1 - base]);
+        const uint32_t nb = base + JD_THREADS, sn = L ? nb / L * L : 0u;                    // the next tile's first block and its segment's start
+        carry = sn <= base ? carry + sum : sum - tile[sn - 1 - base];
+        __syncthreads();
     }
 }
 
@@ -194,9 +246,11 @@ __global__ __launch_bounds__(JD_BLOCK_THREADS) void jpegdec_block_kernel(const u
 static int jpegdec_launch(omni_jpegdec* d, hipStream_t stream, int n_images, uint8_t* out_dev, int out_stride, int* status_dev) {
     OMNI_HIP_TRY(hipMemsetAsync(d->d_coef, 0, (size_t)n_images * d->nyb_max * 64 * sizeof(int16_t), stream));
     OMNI_HIP_TRY(hipMemsetAsync(d->d_dc, 0, (size_t)n_images * d->nyb_max * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->nyb_max, status_dev, d->d_rounds);
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_flags, 0, (size_t)3 * d->max_images * sizeof(int), stream));
+    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(d->last_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->nyb_max, d->d_flags,
+                       d->max_images);
     OMNI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_dc, d->nyb_max);
+    hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_dc, d->nyb_max, d->d_flags, status_dev);
     OMNI_LAUNCH_CHECK();
     const int raster = cdiv(d->w, 8) * cdiv(d->h, 8);
     const int per_image = (int)d->nyb_max > raster ? (int)d->nyb_max : raster;
@@ -222,9 +276,40 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
     if (d->ev_upload) OMNI_HIP_TRY(hipEventSynchronize(d->ev_upload));                        // the last upload has left the pinned block
     uint8_t* base = d->hin.as<uint8_t>();
     size_t at = align16((size_t)n_images * sizeof(jd::Desc));
+    int max_chunks = 1;
+    jd::ChunkPlan plan;
+    std::vector<int64_t> rst;
     for (int i = 0; i < n_images; ++i) {
         jd::Desc& D = descs[(size_t)i];
         D.dev_off = (int64_t)at;
+        // (intervals: every one costs a subsequence and 16 bytes of table -- a file that cannot be planned for that alone is not unstuffed twice)
+        const size_t n_int = D.restart_only ? ((size_t)D.mcus_x * D.mcus_y + D.restart - 1) / D.restart : 0;
+        if (d->restart_wgs && D.status == OMNI_JPEGDEC_HOST && D.restart_only && sizes[i] <= d->capacity && D.n_yblocks <= d->nyb_max &&
+            n_int <= (size_t)d->restart_wgs * JD_MAX_SUBSEQ && (n_int + 1) * sizeof(jd::Interval) + ((size_t)d->restart_wgs + 1) * sizeof(uint32_t) <= d->tab_bytes) {
+            // the restart interval is the file's only obstacle: its scan with the markers' offsets, the chunk plan, the tables behind the scan.  Too few markers:
+            // CORRUPT; a plan that cannot be made, or tables above the handle's room for them: the file stays HOST (below)
+            rst.resize((size_t)(D.scan_bytes / 2 + 1));
+            int64_t n_rst = 0;
+            const int64_t n = jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, rst.data(), (int64_t)rst.size(), &n_rst);
+            jd::plan_chunks(D, n, rst.data(), n_rst, (uint32_t)d->subseq_bits, (uint32_t)d->restart_wgs, JD_MAX_SUBSEQ, &plan);
+            if (plan.status == OMNI_JPEGDEC_CORRUPT) {
+                D.status = OMNI_JPEGDEC_CORRUPT;
+            } else if (plan.status == OMNI_JPEGDEC_OK && plan.table_bytes() <= d->tab_bytes) {
+                const size_t scan_bytes = align16((size_t)n + JD_SCAN_PAD);
+                plan.store(base + at + scan_bytes);
+                D.status = OMNI_JPEGDEC_OK;
+                D.mode = jd::JD_MODE_DECODE;
+                D.total_bits = (uint32_t)(n * 8);
+                D.subseq_bits = plan.subseq_bits;
+                D.n_sub = plan.n_sub;
+                D.n_int = plan.n_int;
+                D.n_chunks = plan.n_chunks;
+                D.tab_off = (int64_t)(at + scan_bytes);
+                if ((int)plan.n_chunks > max_chunks) max_chunks = (int)plan.n_chunks;
+                at += scan_bytes + align16(plan.table_bytes());
+                continue;
+            }
+        }
         if (D.status == OMNI_JPEGDEC_OK) {
             const int64_t n = jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, nullptr, 0, nullptr);
             D.mode = jd::JD_MODE_DECODE;
@@ -243,6 +328,7 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
     }
     OMNI_REQUIRE(at <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: %zu bytes to upload, the handle holds %zu", at, d->in_bytes);
     memcpy(base, descs.data(), (size_t)n_images * sizeof(jd::Desc));
+    d->last_chunks = max_chunks;
     *bytes = at;
     return OMNI_OK;
 }
@@ -264,22 +350,28 @@ extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int heigh
     if (config_resolve(&cfg) != OMNI_OK) return nullptr;
     const int S = cfg[CFG_JPEGDEC_SUBSEQ_BITS];
     if (S & (S - 1)) { set_error("OMNI_JPEGDEC_SUBSEQ_BITS=%d: expected a power of two", S); return nullptr; }
+    const int W = cfg[CFG_JPEGDEC_RESTART_WGS];
     std::lock_guard<std::mutex> lk(ctx->mu);
     (void)hipSetDevice(ctx->device);
     omni_jpegdec* d = new omni_jpegdec();
-    d->ctx = ctx; d->w = width; d->h = height; d->max_images = max_images; d->capacity = capacity_per_image; d->subseq_bits = S; d->nyb_max = (uint32_t)nyb;
+    d->ctx = ctx; d->w = width; d->h = height; d->max_images = max_images; d->capacity = capacity_per_image; d->subseq_bits = S; d->restart_wgs = W; d->nyb_max = (uint32_t)nyb;
     // per image: a descriptor and the larger of a clean scan and the picture itself
     const size_t per_scan = align16((size_t)capacity_per_image + JD_SCAN_PAD), per_px = align16((size_t)width * height);
-    d->in_bytes = align16((size_t)max_images * sizeof(jd::Desc)) + (size_t)max_images * (per_scan > per_px ? per_scan : per_px);
+    // ... and, with OMNI_JPEGDEC_RESTART_WGS on, its interval and chunk tables: one interval per MCU of 8 x 8 at the most, and no more than W chunks hold
+    if (W) {
+        const size_t mcus = (size_t)cdiv(width, 8) * cdiv(height, 8), planned = (size_t)W * JD_MAX_SUBSEQ;
+        d->tab_bytes = align16(((mcus < planned ? mcus : planned) + 1) * sizeof(jd::Interval) + ((size_t)W + 1) * sizeof(uint32_t));
+    }
+    d->in_bytes = align16((size_t)max_images * sizeof(jd::Desc)) + (size_t)max_images * ((per_scan > per_px ? per_scan : per_px) + d->tab_bytes);
     const size_t coef_bytes = (size_t)max_images * nyb * 64 * sizeof(int16_t), dc_bytes = (size_t)max_images * nyb * sizeof(int32_t);
     auto make = [&]() -> int {
         int rc;
         if ((rc = d->mem.alloc(&d->d_in, d->in_bytes)) || (rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
-            (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_rounds, (size_t)max_images * sizeof(int))))
+            (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_flags, (size_t)3 * max_images * sizeof(int))))
             return rc;
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_coef) + coef_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_dc) + dc_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
-        OMNI_HIP_TRY(hipMemset(d->d_rounds, 0, (size_t)max_images * sizeof(int)));
+        OMNI_HIP_TRY(hipMemset(d->d_flags, 0, (size_t)3 * max_images * sizeof(int)));
         if ((rc = d->hin.ensure(d->in_bytes))) return rc;
         OMNI_HIP_TRY(hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming));
         for (hipEvent_t& e : d->ev_t) OMNI_HIP_TRY(hipEventCreate(&e));
@@ -359,13 +451,22 @@ extern "C" int omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subs
     std::lock_guard<std::mutex> lk(d->mu);
     (void)hipSetDevice(d->ctx->device);
     OMNI_HIP_TRY(hipDeviceSynchronize());                                                     // (the last enqueue may have run on a unit's stream)
-    if (rounds && d->last_n) OMNI_HIP_TRY(hipMemcpy(rounds, d->d_rounds, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+    if (rounds && d->last_n) OMNI_HIP_TRY(hipMemcpy(rounds, d->d_flags + d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
     const omni::jd::Desc* descs = d->hin.as<omni::jd::Desc>();                                // (the pinned block still holds the last enqueue's descriptors)
     for (int i = 0; i < d->last_n; ++i) {
         const bool dec = descs[i].mode == omni::jd::JD_MODE_DECODE;
         if (n_subseq) n_subseq[i] = dec ? (int)descs[i].n_sub : 0;
         if (subseq_bits) subseq_bits[i] = dec ? (int)descs[i].subseq_bits : 0;
     }
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_last_chunks(omni_jpegdec* d, int* chunks) {
+    OMNI_REQUIRE(d && chunks, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(d->mu);
+    (void)hipSetDevice(d->ctx->device);
+    OMNI_HIP_TRY(hipDeviceSynchronize());
+    if (d->last_n) OMNI_HIP_TRY(hipMemcpy(chunks, d->d_flags + 2 * (size_t)d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
     return OMNI_OK;
 }
 

@@ -16,7 +16,7 @@
 //                             component sampled below another one
 //                CORRUPT      anything else that cannot be a file
 //   bytes      0xFF00 unstuffing and the end at a marker happen in a FIRST PASS on the host (unstuff): the scan the decoders and the kernels read is the
-//              clean bit stream, MSB first, followed by >= JD_SCAN_PAD zero bytes.  Restart markers become a list of byte offsets (host decoder only)
+//              clean bit stream, MSB first, followed by >= JD_SCAN_PAD zero bytes.  Restart markers become a list of byte offsets (the host decoder and the chunk plan)
 //   symbol     step(): ONE total function (bit position, z = next zig-zag index 0..63, b = block within the MCU) -> next state, at most one (block, natural
 //              index, value) emission, an error flag.  z == 0: a DC category + value bits; else an AC (run, size): ZRL (z += 16; reaching 64 ends the block, as
 //              libjpeg's loop does), EOB, value extension as in jpeg_plan.h.  Defined for EVERY bit pattern: an undefined code is 1 bit long and reads as symbol
@@ -35,6 +35,17 @@
 //                 shift and the final >> 3 in one), clamp to 0..255, store cropped to width x height.  All in uint32 arithmetic (= two's complement int32,
 //                 no overflow to be undefined for ANY coefficients); libjpeg's all-zero-AC column shortcut is arithmetically the same and is not restated
 //   CORRUPT    the picture is all zeros
+//   restart    a file with a restart interval (DRI) stays HOST at parse time; a handle whose OMNI_JPEGDEC_RESTART_WGS is W >= 1 promotes one whose ONLY obstacle is
+//              the interval (Desc::restart_only).  Every interval starts byte-aligned behind its marker from the known state pack_state(0, 0, 0) with a DC
+//              predictor of zero at block k * restart * bpm: intervals are independent streams.  plan_chunks() cuts every interval into subsequences of its own
+//              ([bit_begin + j S, ...), bounded by the interval's end: decode_subseq_seg) and groups consecutive intervals into at most W chunks balanced by bits,
+//              each of at most max_sub subsequences (S doubled until that holds) -- one workgroup per chunk, none reads what another wrote.  Phases 1-4 run per
+//              chunk; the first subsequence of an interval has the fixed entry 0; a subsequence's first block is its interval's first block + the counts before
+//              it INSIDE the interval; the write pass bounds every interval to its own blocks, and an interval that completes fewer inside its own bits is
+//              CORRUPT (DIVERGENCE from decode_sequential, which reads on into the next interval; libjpeg's own resynchronisation is unpinned either way).
+//              Fewer markers than ceil(mcus / restart) - 1: CORRUPT (decode_sequential: seg >= n_rst); surplus markers are ignored.  Phase 5 becomes a
+//              segmented scan: the running DC sum restarts every restart * ny blocks of the first component.  A file that cannot be planned (more intervals in a
+//              chunk than max_sub) stays HOST
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -45,6 +56,8 @@
 #define JD_MAX_BPM 10                                        // blocks per MCU (the standard's limit)
 #define JD_MIN_SUBSEQ_BITS 128
 #define JD_MAX_SUBSEQ_BITS 65536
+#define JD_MAX_SUBSEQ 4096                                   // subsequences a workgroup of the entropy kernel holds (csrc/jpeg_dec.hip: 16 per lane)
+#define JD_MAX_RESTART_WGS 64                                // workgroups a restart-interval picture is spread over, at most (OMNI_JPEGDEC_RESTART_WGS)
 
 namespace omni {
 namespace jd {
@@ -67,12 +80,15 @@ struct Desc {
     int32_t status;                                         // OMNI_JPEGDEC_*
     int32_t w, h, ncomp, hs, vs;                            // hs x vs: the first component's blocks per MCU
     int32_t mcus_x, mcus_y, restart, multi_scan;
+    int32_t restart_only;                                   // HOST for its restart interval alone: without it the file would be OK
     uint32_t n_blocks, n_yblocks;                           // of the scan; of the first component (MCU padding included)
     int64_t scan_off, scan_bytes;                           // the scan's bytes in the file (stuffed, restart markers included)
     // filled by whoever packs the image for the kernels (jpeg_dec.hip)
     int32_t mode;                                           // JD_MODE_*
     uint32_t total_bits, subseq_bits, n_sub;
     int64_t dev_off;                                        // MODE_DECODE: the clean scan, MODE_PIXELS: w x h pixels -- byte offset inside the uploaded block
+    uint32_t n_int, n_chunks;                               // a planned restart file: intervals and chunks (0 0: no restart interval, one chunk over the whole scan)
+    int64_t tab_off;                                        // ... its tables: Interval[n_int + 1] (the last one a sentinel), then uint32 first interval of chunk [n_chunks + 1]
     uint16_t q[64];                                         // the first component's quantisation table, natural order
     Tables T;
 };
@@ -231,9 +247,10 @@ inline int parse(const uint8_t* f, int64_t size, Desc* d) {
             d->scan_off = start;
             d->scan_bytes = end - start;
             if (ns < d->ncomp) d->multi_scan = 1;
-            bool dev = d->restart == 0 && !d->multi_scan && d->hs <= 2 && d->vs <= 2;
+            bool dev = !d->multi_scan && d->hs <= 2 && d->vs <= 2;
             for (int j = 1; j < ns; ++j) dev = dev && ch[comp_of[j]] == 1 && cv[comp_of[j]] == 1;
-            return fail(dev ? OMNI_JPEGDEC_OK : OMNI_JPEGDEC_HOST);
+            d->restart_only = dev && d->restart != 0;
+            return fail(dev && d->restart == 0 ? OMNI_JPEGDEC_OK : OMNI_JPEGDEC_HOST);
         }
         // APPn, COM and anything else with a length: skipped
         p += len;
@@ -365,18 +382,19 @@ struct CoefEmit {
         if (++b >= bpm) { b = 0; ybase += (uint32_t)ny; }
     }
 };
-// Subsequence i from `entry`: the symbols that start in [i S + overhang, min((i + 1) S, total_bits)), and none once first_block + (blocks completed) reaches
-// max_blocks.  Returns the blocks completed; *exit_state, *err (any JD_STEP_ERR among its steps)
+// Subsequence i of the segment [seg_begin, seg_end) of the scan (absolute bit positions: a restart interval; the whole scan is the segment [0, total_bits)) from
+// `entry`: the symbols that start in [seg_begin + i S + overhang, min(seg_begin + (i + 1) S, seg_end)), and none once first_block + (blocks completed) reaches
+// max_blocks.  seg_end is step()'s end of the data.  Returns the blocks completed; *exit_state, *err (any JD_STEP_ERR among its steps)
 template <class Emit>
-JP_HD uint32_t decode_subseq(const Tables& T, const uint8_t* scan, uint32_t n_words, uint32_t total_bits, uint32_t i, uint32_t S, uint16_t entry, uint32_t first_block,
-                             uint32_t max_blocks, Emit& em, uint16_t* exit_state, int* err) {
-    const uint32_t bound = (i + 1) * S, end = bound < total_bits ? bound : total_bits;
+JP_HD uint32_t decode_subseq_seg(const Tables& T, const uint8_t* scan, uint32_t n_words, uint32_t seg_begin, uint32_t seg_end, uint32_t i, uint32_t S, uint16_t entry,
+                                 uint32_t first_block, uint32_t max_blocks, Emit& em, uint16_t* exit_state, int* err) {
+    const uint32_t bound = seg_begin + (i + 1) * S, end = bound < seg_end ? bound : seg_end;
     int z = (entry >> 6) & 63, b = entry >> 12, e = 0;
     uint32_t blocks = 0;
     Bits br;
-    br.init(scan, n_words, i * S + (entry & 63u));
+    br.init(scan, n_words, seg_begin + i * S + (entry & 63u));
     while (br.pos < end && first_block + blocks < max_blocks) {
-        const int r = step(T, br, total_bits, z, b, em);
+        const int r = step(T, br, seg_end, z, b, em);
         e |= r & JD_STEP_ERR;
         blocks += (uint32_t)(r >> 1);
     }
@@ -384,11 +402,32 @@ JP_HD uint32_t decode_subseq(const Tables& T, const uint8_t* scan, uint32_t n_wo
     *err = e;
     return blocks;
 }
+// ... of the whole scan
+template <class Emit>
+JP_HD uint32_t decode_subseq(const Tables& T, const uint8_t* scan, uint32_t n_words, uint32_t total_bits, uint32_t i, uint32_t S, uint16_t entry, uint32_t first_block,
+                             uint32_t max_blocks, Emit& em, uint16_t* exit_state, int* err) {
+    return decode_subseq_seg(T, scan, n_words, 0u, total_bits, i, S, entry, first_block, max_blocks, em, exit_state, err);
+}
 // the subsequence length an image is decoded with: the configured one, doubled until there are at most max_sub subsequences
 JP_HD uint32_t subseq_bits_for(uint32_t total_bits, uint32_t S, uint32_t max_sub) {
     while (S < (1u << 30) && (total_bits + S - 1) / S > max_sub) S <<= 1;
     return S;
 }
+
+// ---- restart intervals ---------------------------------------------------------------------------------------------------------------------------------------
+// one interval of a planned restart file: its bits on the clean scan (absolute), its first subsequence (numbered through the picture) and its first block.  The
+// table ends with a sentinel {total_bits, total_bits, n_sub, n_blocks}: interval k's subsequences are [first_sub, [k + 1].first_sub), its blocks likewise
+struct Interval { uint32_t bit_begin, bit_end, first_sub, first_block; };
+// the interval among [lo, hi) that holds subsequence g (first_sub is increasing; [lo].first_sub <= g)
+JP_HD uint32_t interval_of(const Interval* iv, uint32_t lo, uint32_t hi, uint32_t g) {
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (iv[mid].first_sub <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// subsequences of an interval of `bits` bits: at least one
+JP_HD uint32_t interval_subs(uint32_t bits, uint32_t S) { return bits ? (bits + S - 1) / S : 1u; }
 
 // ---- the block: dequantise, islow IDCT, level shift, clamp ---------------------------------------------------------------------------------------------------
 JP_HD int32_t jd_descale(uint32_t x, int n) { return (int32_t)(x + (1u << (n - 1))) >> n; }
@@ -628,6 +667,170 @@ inline int jpeg_decode_parallel_host(const uint8_t* file, int64_t size, uint32_t
     for (uint32_t y = 0; y < d.n_yblocks; ++y) { run += (uint32_t)dc[y]; dc[y] = (int32_t)run; }      // 5
     for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
     return err ? OMNI_JPEGDEC_CORRUPT : d.status;
+}
+
+// ---- restart-interval files over several workgroups: the chunk plan and its CPU stand-in ------------------------------------------------------------------------
+struct ChunkPlan {
+    int status = OMNI_JPEGDEC_HOST;                         // OK: planned; HOST: cannot be planned; CORRUPT: fewer restart markers than the picture needs
+    uint32_t subseq_bits = 0, n_sub = 0, n_int = 0, n_chunks = 0, max_chunk_sub = 0;
+    std::vector<Interval> iv;                               // n_int + 1 (sentinel)
+    std::vector<uint32_t> chunk_first;                      // n_chunks + 1: chunk c holds the intervals [chunk_first[c], chunk_first[c + 1])
+    size_t table_bytes() const { return iv.size() * sizeof(Interval) + chunk_first.size() * sizeof(uint32_t); }
+    void store(uint8_t* at) const {                         // the form the kernel reads (Desc::tab_off; 4-byte aligned)
+        memcpy(at, iv.data(), iv.size() * sizeof(Interval));
+        memcpy(at + iv.size() * sizeof(Interval), chunk_first.data(), chunk_first.size() * sizeof(uint32_t));
+    }
+};
+// The plan of a parsed restart file (d.restart != 0) whose clean scan has nclean bytes and whose restart markers stood at the clean byte offsets rst[0..n_rst):
+// intervals of S bits per subsequence in at most W chunks of consecutive intervals, balanced by bits, each of at most max_sub subsequences (S is doubled until
+// that holds; every interval costs at least one, so a chunk of more than max_sub intervals cannot be planned)
+inline void plan_chunks(const Desc& d, int64_t nclean, const int64_t* rst, int64_t n_rst, uint32_t S, uint32_t W, uint32_t max_sub, ChunkPlan* p) {
+    *p = ChunkPlan();
+    const uint32_t mcus = (uint32_t)d.mcus_x * (uint32_t)d.mcus_y, restart = (uint32_t)d.restart;
+    if (!restart || !mcus || !W || !max_sub || nclean < 0 || nclean > (1 << 28)) return;
+    const uint32_t n_int = (mcus + restart - 1) / restart, total_bits = (uint32_t)(nclean * 8);
+    if (n_rst < (int64_t)n_int - 1) { p->status = OMNI_JPEGDEC_CORRUPT; return; }
+    p->n_int = n_int;
+    p->iv.resize((size_t)n_int + 1);
+    std::vector<uint32_t> chunk_of(n_int);
+    uint32_t n_chunks = 0, in_chunk = 0, max_in_chunk = 0, max_bits = 0;
+    for (uint32_t k = 0; k < n_int; ++k) {
+        Interval& I = p->iv[k];
+        I.bit_begin = k ? (uint32_t)(rst[k - 1] * 8) : 0u;
+        I.bit_end = k + 1 < n_int ? (uint32_t)(rst[k] * 8) : total_bits;
+        I.first_block = k * restart * (uint32_t)d.T.bpm;
+        if (I.bit_end - I.bit_begin > max_bits) max_bits = I.bit_end - I.bit_begin;
+        uint32_t c = total_bits ? (uint32_t)((uint64_t)I.bit_begin * W / total_bits) : 0u;
+        if (c >= W) c = W - 1;
+        if (k == 0 || c != chunk_of[k - 1]) {               // (c never decreases: the offsets never do)
+            p->chunk_first.push_back(k);
+            ++n_chunks;
+            in_chunk = 0;
+        }
+        chunk_of[k] = c;
+        if (++in_chunk > max_in_chunk) max_in_chunk = in_chunk;
+    }
+    p->chunk_first.push_back(n_int);
+    p->n_chunks = n_chunks;
+    if (max_in_chunk > max_sub) return;                                                     // HOST
+    for (;; S <<= 1) {
+        uint32_t sub = 0, worst = 0;
+        for (uint32_t c = 0; c < n_chunks; ++c) {
+            const uint32_t before = sub;
+            for (uint32_t k = p->chunk_first[c]; k < p->chunk_first[c + 1]; ++k) {
+                p->iv[k].first_sub = sub;
+                sub += interval_subs(p->iv[k].bit_end - p->iv[k].bit_begin, S);
+            }
+            if (sub - before > worst) worst = sub - before;
+        }
+        p->n_sub = sub;
+        p->max_chunk_sub = worst;
+        if (worst <= max_sub) break;
+        if (S >= (1u << 30) || S >= max_bits) return;                                       // (cannot happen: S >= max_bits makes every interval one subsequence)
+    }
+    p->subseq_bits = S;
+    p->iv[n_int] = Interval{total_bits, total_bits, p->n_sub, d.n_blocks};
+    p->status = OMNI_JPEGDEC_OK;
+}
+
+// phase 5 with a restart interval: the running sum starts again every `seg` blocks of the first component (seg = restart * ny; 0: never)
+inline void dc_scan_host(int32_t* dc, uint32_t n, uint32_t seg) {
+    uint32_t run = 0;
+    for (uint32_t y = 0; y < n; ++y) {
+        if (seg && y % seg == 0) run = 0;
+        run += (uint32_t)dc[y];
+        dc[y] = (int32_t)run;
+    }
+}
+
+struct RestartStats {
+    uint32_t n_sub = 0, subseq_bits = 0, n_chunks = 0, rounds = 0;      // rounds: the maximum over the chunks of the relaxation rounds that changed something
+};
+// The CPU stand-in for the kernels of a handle whose OMNI_JPEGDEC_RESTART_WGS is W >= 1: a file that is HOST for its restart interval alone runs the chunk plan
+// and the phase functions, chunk by chunk, by plain loops, and is OK; every other file goes the way of jpeg_decode_parallel_host (one chunk).  A file that cannot
+// be planned: the sequential decoder, HOST.
+inline int jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t W, uint32_t max_sub, uint8_t* out, int64_t stride, int max_w,
+                                             int max_h, int* w, int* h, RestartStats* stats) {
+    Desc d;
+    const int st = parse(file, size, &d);
+    RestartStats rs;
+    if (stats) *stats = rs;
+    if (!d.restart_only || !out) {
+        ParallelStats ps;
+        const int r = jpeg_decode_parallel_host(file, size, S, max_sub, out, stride, max_w, max_h, w, h, &ps);
+        if (stats && out && st == OMNI_JPEGDEC_OK && r >= 0) { stats->n_sub = ps.n_sub; stats->subseq_bits = ps.subseq_bits; stats->n_chunks = 1; stats->rounds = ps.rounds; }
+        return r;
+    }
+    if (w) *w = d.w;
+    if (h) *h = d.h;
+    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
+    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
+    std::vector<int64_t> rst((size_t)(d.scan_bytes / 2 + 1));
+    int64_t n_rst = 0;
+    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), rst.data(), (int64_t)rst.size(), &n_rst);
+    ChunkPlan P;
+    plan_chunks(d, nclean, rst.data(), n_rst, S, W, max_sub, &P);
+    if (P.status == OMNI_JPEGDEC_CORRUPT) {
+        zero_picture(out, stride, d.w, d.h);
+        return OMNI_JPEGDEC_CORRUPT;
+    }
+    if (P.status != OMNI_JPEGDEC_OK) return decode_sequential(file, d, out, stride);
+    S = P.subseq_bits;
+    const uint32_t n_words = scan_words(nclean);
+    const Interval* iv = P.iv.data();
+    std::vector<int16_t> coef((size_t)d.n_yblocks * 64, 0);
+    std::vector<int32_t> dc(d.n_yblocks, 0);
+    NoEmit none;
+    int e, err = 0;
+    rs.n_sub = P.n_sub; rs.subseq_bits = S; rs.n_chunks = P.n_chunks;
+    for (uint32_t c = 0; c < P.n_chunks; ++c) {
+        const uint32_t k0 = P.chunk_first[c], k1 = P.chunk_first[c + 1], sub0 = iv[k0].first_sub, N = iv[k1].first_sub - sub0;
+        std::vector<uint16_t> ex(N), used(N, 0);
+        std::vector<uint32_t> cnt(N), first(N), of(N);
+        std::vector<uint8_t> need(N);
+        auto run = [&](uint32_t i, uint16_t entry, uint32_t first_block, uint32_t max_blocks, auto& em, uint16_t* x) {
+            const Interval& I = iv[of[i]];
+            return decode_subseq_seg(d.T, clean.data(), n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, entry, first_block, max_blocks, em, x, &e);
+        };
+        for (uint32_t i = 0; i < N; ++i) {                                                  // 1
+            of[i] = interval_of(iv, k0, k1, sub0 + i);
+            cnt[i] = run(i, 0, 0u, 0xffffffffu, none, &ex[i]);
+        }
+        uint32_t rounds = 0;
+        for (uint32_t r = 0; r < N; ++r) {                                                  // 2: the first subsequence of an interval keeps its entry 0
+            for (uint32_t i = 0; i < N; ++i) {
+                need[i] = sub0 + i != iv[of[i]].first_sub && ex[i - 1] != used[i];
+                if (need[i]) used[i] = ex[i - 1];
+            }
+            bool changed = false;
+            for (uint32_t i = 0; i < N; ++i) {
+                if (!need[i]) continue;
+                uint16_t x;
+                const uint32_t n = run(i, used[i], 0u, 0xffffffffu, none, &x);
+                if (x != ex[i] || n != cnt[i]) { ex[i] = x; cnt[i] = n; changed = true; }
+            }
+            if (!changed) break;
+            ++rounds;
+        }
+        if (rounds > rs.rounds) rs.rounds = rounds;
+        uint32_t total = 0;
+        for (uint32_t i = 0; i < N; ++i) { first[i] = total; total += cnt[i]; }             // 3: a prefix that never crosses an interval's start
+        for (uint32_t i = 0; i < N; ++i) {                                                  // 4
+            const Interval& I = iv[of[i]];
+            const uint32_t fb = I.first_block + (first[i] - first[I.first_sub - sub0]), max_blocks = iv[of[i] + 1].first_block;
+            CoefEmit em;
+            em.coef = coef.data(); em.dcd = dc.data(); em.n_yblocks = d.n_yblocks;
+            em.start(d.T, fb, used[i] >> 12);
+            uint16_t x;
+            const uint32_t wrote = run(i, used[i], fb, max_blocks, em, &x);
+            err |= e;
+            if (sub0 + i + 1 == iv[of[i] + 1].first_sub && fb + wrote < max_blocks) err = 1;      // the interval ends short of its blocks
+        }
+    }
+    if (stats) *stats = rs;
+    dc_scan_host(dc.data(), d.n_yblocks, (uint32_t)d.restart * (uint32_t)d.T.ny);           // 5
+    for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
+    return err ? OMNI_JPEGDEC_CORRUPT : OMNI_JPEGDEC_OK;
 }
 
 }  // namespace jd
