@@ -624,7 +624,12 @@ int        omni_cam_jpeg(omni_cam* cam, omni_cam_jpeg_result* out);
  * predictor zero, known first block -- are spread over at most W workgroups balanced by bits.  The pixels are the same.  Such a file stays HOST when it cannot be
  * planned (more intervals in one workgroup's share than that workgroup holds subsequences: 4096), and is CORRUPT when its scan holds fewer restart markers than
  * ceil(MCUs / interval) - 1 or when an interval's bits end before its blocks do (there the host decoder reads on into the next interval: the one divergence;
- * libjpeg's own resynchronisation is UNPINNED either way).  Surplus markers are ignored. */
+ * libjpeg's own resynchronisation is UNPINNED either way).  Surplus markers are ignored.
+ * Files without a restart interval: OMNI_JPEGDEC_PLAIN_WGS (0..64, default 0), as it is when the handle is created.  0 or 1: one workgroup of the entropy kernel
+ * decodes such a picture.  W >= 2: an OMNI_JPEGDEC_OK file is decoded over min(W, subsequences) chunks of consecutive subsequences that relax on their own, a seam
+ * relaxation over the whole picture that repairs what the seams between chunks got wrong, and a write pass of one subsequence per lane; the subsequence length
+ * is OMNI_JPEGDEC_SUBSEQ_BITS doubled only until W chunks of 4096 subsequences hold the picture.  No workgroup waits for another.  Same pixels, same status, the
+ * classification untouched; the two switches are independent and one batch may hold both kinds of file. */
 #define OMNI_JPEGDEC_OK 0
 #define OMNI_JPEGDEC_HOST 1
 #define OMNI_JPEGDEC_UNSUPPORTED 2
@@ -644,9 +649,13 @@ int           omni_jpegdec_enqueue_host(omni_jpegdec* d, const uint8_t* const* f
 /* Of the handle's last enqueue, after a synchronisation with the context's stream: per image the relaxation rounds that changed something, the number of
  * subsequences and their length in bits (0 0 0 for an image the kernels did not decode).  Each output [n_images] or null. */
 int           omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subseq, int* subseq_bits);
-/* ... and the workgroups of the entropy kernel that decoded a share of each image (counted on the GPU): 1, or the chunks of a restart-interval file; 0 for an
- * image the kernels did not decode.  A restart-interval file's rounds above are the maximum over its chunks, its subsequences their total.  chunks [n_images] */
+/* ... and the workgroups of the entropy kernel that decoded a share of each image (counted on the GPU): 1, or the chunks of a restart-interval file, or the
+ * chunks of a picture spread by OMNI_JPEGDEC_PLAIN_WGS; 0 for an image the kernels did not decode.  A restart-interval file's rounds above are the maximum over
+ * its chunks, its subsequences their total; a spread picture's rounds are the maximum over its chunks + the seam relaxation's.  chunks [n_images] */
 int           omni_jpegdec_last_chunks(omni_jpegdec* d, int* chunks);
+/* ... and of a picture spread by OMNI_JPEGDEC_PLAIN_WGS the seam relaxation's rounds that changed something and the subsequences it changed at least once (0 0
+ * for every other image, and on a handle whose switch is 0 or 1).  Each output [n_images] or null. */
+int           omni_jpegdec_last_seam(omni_jpegdec* d, int* seam_rounds, int* seam_changed);
 /* MEASUREMENT: of the handle's last enqueue, once it has run: the time of its upload and of everything behind it (memsets + kernels) on the GPU, and the bytes it
  * uploaded (tools/jpegdec_timing.py) */
 int           omni_jpegdec_last_ms(omni_jpegdec* d, float* upload_ms, float* kernels_ms, int64_t* uploaded_bytes);
@@ -654,6 +663,9 @@ int           omni_jpegdec_last_ms(omni_jpegdec* d, float* upload_ms, float* ker
  * nothing ever writes */
 #define OMNI_JPEGDEC_GUARD_BYTES 256
 int           omni_jpegdec_debug_buffers(omni_jpegdec* d, void** coef_dev, int64_t* coef_bytes, void** dc_dev, int64_t* dc_bytes);
+/* ... and of the state arrays of a handle whose OMNI_JPEGDEC_PLAIN_WGS is W >= 2 (max_images x W x 4096 x 8 bytes, the same guard behind them); NULL and 0 on
+ * every other handle: nothing is allocated there */
+int           omni_jpegdec_debug_state_buffer(omni_jpegdec* d, void** state_dev, int64_t* state_bytes);
 /* the classification of a file without a capacity, and its picture's size (0 x 0 when no frame header can be read); no GPU */
 int           omni_jpegdec_classify(const uint8_t* file, int64_t size, int* width, int* height);
 /* csrc/jpeg_dec_plan.h's sequential decoder compiled by g++ into the library, next to omni_jpeg_encode_host: the same pixels without a GPU, restart intervals
@@ -670,6 +682,13 @@ int           omni_jpeg_decode_parallel_host(const uint8_t* file, int64_t size, 
  * that changed something (0 0 0 0 for a file the plan leaves to the host) */
 int           omni_jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int restart_wgs, int max_subseq, uint8_t* out, int stride,
                                                      int* width, int* height, int* status, int* stats);
+/* TEST INFRASTRUCTURE: the CPU stand-in for the kernels of a handle with OMNI_JPEGDEC_PLAIN_WGS = plain_wgs (1..64), where a workgroup holds at most max_subseq
+ * subsequences (the kernels: 4096): the chunk partition, the chunk relaxation, the seam relaxation and the same phase functions by plain loops
+ * (jpeg_decode_plain_parallel_host).  Every file that is not OMNI_JPEGDEC_OK goes the way of omni_jpeg_decode_parallel_host.  stats[7] = subsequences, their
+ * length, chunks, the maximum over the chunks of the relaxation rounds that changed something, the seam relaxation's rounds that changed something, the
+ * subsequences it changed at least once, the chunks those lie in (all 0 for a file that is not OK) */
+int           omni_jpeg_decode_plain_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int plain_wgs, int max_subseq, uint8_t* out, int stride,
+                                                   int* width, int* height, int* status, int* stats);
 
 /* The same stage inside the key-frame unit: a unit whose frames arrive as JPEG files.  The decode runs on the unit's SuperPoint stream in front of the resize, and
  * the decoded frames take the place of omni_cam_enqueue_raw_*'s: n_keyframes left files and as many right files for a stereo handle (STEREO_PINHOLE), left files

@@ -46,7 +46,7 @@ SYMBOLS = [
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
     "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
-    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_jpeg_decode_restart_parallel_host", "omni_jpegdec_last_chunks", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
+    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_jpeg_decode_restart_parallel_host", "omni_jpegdec_last_chunks", "omni_jpeg_decode_plain_parallel_host", "omni_jpegdec_last_seam", "omni_jpegdec_debug_state_buffer", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
 ]
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
@@ -256,6 +256,9 @@ def lib():
     sig("omni_jpeg_decode_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
     sig("omni_jpeg_decode_restart_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
     sig("omni_jpegdec_last_chunks", C.c_int, [_vp, _ip])
+    sig("omni_jpeg_decode_plain_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
+    sig("omni_jpegdec_last_seam", C.c_int, [_vp, _ip, _ip])
+    sig("omni_jpegdec_debug_state_buffer", C.c_int, [_vp, C.POINTER(_vp), _i64p])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
     sig("omni_cam_ready", C.c_int, [_vp, C.POINTER(C.c_int)])
@@ -954,6 +957,17 @@ def jpeg_decode_restart_parallel_host(data: bytes, subseq_bits: int, restart_wgs
     return status, pix, dict(n_sub=stats[0], subseq_bits=stats[1], chunks=stats[2], rounds=stats[3])
 
 
+def jpeg_decode_plain_parallel_host(data: bytes, subseq_bits: int, plain_wgs: int, max_subseq: int = JPEGDEC_MAX_SUBSEQ):
+    """the CPU stand-in for the kernels of a handle with OMNI_JPEGDEC_PLAIN_WGS = plain_wgs -> (status, gray, dict(n_sub, subseq_bits, chunks, chunk_rounds,
+    seam_rounds, seam_changed, seam_chunks, rounds = chunk_rounds + seam_rounds: what omni_jpegdec_last_stats reports)): a file without a restart interval over
+    min(plain_wgs, n_sub) chunks that relax on their own, then the seam relaxation over the whole picture"""
+    stats = (C.c_int * 7)()
+    status, pix = _jpeg_decode(data, 0, lambda o, st, w, h, s: lib().omni_jpeg_decode_plain_parallel_host(data, len(data), subseq_bits, plain_wgs, max_subseq, o, st,
+                                                                                                         w, h, s, stats))
+    return status, pix, dict(n_sub=stats[0], subseq_bits=stats[1], chunks=stats[2], chunk_rounds=stats[3], seam_rounds=stats[4], seam_changed=stats[5],
+                             seam_chunks=stats[6], rounds=stats[3] + stats[4])
+
+
 class JpegDec:
     """omni_jpegdec: up to max_images JPEG files of at most capacity_per_image bytes -> gray images of width x height on the GPU (is_compressed_images;
     csrc/jpeg_dec.hip, the arithmetic: csrc/jpeg_dec_plan.h)"""
@@ -996,6 +1010,13 @@ class JpegDec:
         _check(lib().omni_jpegdec_last_chunks(self.h, k))
         return [k[i] for i in range(n)]
 
+    def last_seam(self, n: int):
+        """per image of the last call: (seam relaxation rounds that changed something, subsequences it changed) of a picture spread by OMNI_JPEGDEC_PLAIN_WGS;
+        (0, 0) for every other image"""
+        r, m = (C.c_int * self.max_images)(), (C.c_int * self.max_images)()
+        _check(lib().omni_jpegdec_last_seam(self.h, r, m))
+        return [(r[i], m[i]) for i in range(n)]
+
     def last_ms(self):
         """(upload ms, memsets + kernels ms, bytes uploaded) of the last call, on the GPU's clock"""
         u, k, b = C.c_float(), C.c_float(), C.c_int64()
@@ -1003,11 +1024,13 @@ class JpegDec:
         return u.value, k.value, b.value
 
     def guards_ok(self) -> bool:
-        """the 0xA5 bytes behind the coefficient and the DC buffer are as they were created"""
-        cp, cb, dp, db = _vp(), C.c_int64(), _vp(), C.c_int64()
+        """the 0xA5 bytes behind the coefficient buffer, the DC buffer and (OMNI_JPEGDEC_PLAIN_WGS >= 2) the state arrays are as they were created"""
+        cp, cb, dp, db, sp, sb = _vp(), C.c_int64(), _vp(), C.c_int64(), _vp(), C.c_int64()
         _check(lib().omni_jpegdec_debug_buffers(self.h, C.byref(cp), C.byref(cb), C.byref(dp), C.byref(db)))
+        _check(lib().omni_jpegdec_debug_state_buffer(self.h, C.byref(sp), C.byref(sb)))
         self.ctx.sync()
-        return all(bool((self.ctx.from_device(p.value + b.value, (JPEGDEC_GUARD_BYTES,), np.uint8) == 0xA5).all()) for p, b in ((cp, cb), (dp, db)))
+        self.guarded = 2 + bool(sp.value)                      # the buffers whose guards were looked at
+        return all(bool((self.ctx.from_device(p.value + b.value, (JPEGDEC_GUARD_BYTES,), np.uint8) == 0xA5).all()) for p, b in ((cp, cb), (dp, db), (sp, sb)) if p.value)
 
     def __call__(self, files, stride: int = 0):
         """[bytes] -> ([status], pictures [n][h][stride or w] u8) (host convenience: enqueue, download).  The output block is 0xA5 before the call and has a guard

@@ -80,6 +80,10 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
     {"OMNI_JPEGDEC_RESTART_WGS", 0, 0, 64, CFG_TUNING, "omni_jpegdec: 0 = a file with a restart interval (DRI) is decoded on the calling thread (HOST); W >= 1 = one whose only obstacle is "
                                                        "the interval is decoded by the kernels (OK), its intervals -- independent streams -- spread over at most W workgroups balanced by "
                                                        "bits (csrc/jpeg_dec_plan.h plan_chunks); a file that cannot be planned stays HOST.  Same pixels for every value"},
+    {"OMNI_JPEGDEC_PLAIN_WGS", 0, 0, 64, CFG_TUNING, "omni_jpegdec: 0 or 1 = a file without a restart interval is decoded by ONE workgroup of the entropy kernel; W >= 2 = over min(W, subsequences) "
+                                                     "chunks of consecutive subsequences that relax on their own, a seam relaxation over the whole picture behind them, and a write "
+                                                     "pass of one subsequence per lane (csrc/jpeg_dec_plan.h, plain); the subsequence length is doubled only until W chunks of 4096 "
+                                                     "hold the picture.  Same pixels for every value"},
     // ---- runtime ---------------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_HW_QUEUES", 8, 0, 64, CFG_TUNING, "hardware queues asked of the HIP runtime when the library is loaded (GPU_MAX_HW_QUEUES, unless already set): the pipeline's five "
                                             "streams must not share one; 0 = the runtime's default of 4"},

@@ -10,6 +10,20 @@
 //            nothing (self-synchronisation; at most N rounds, a fixed point IS the sequential decode).  Exit states, entry states and block counts live in LDS; the
 //            round loop is workgroup-uniform (__syncthreads + an LDS flag).  Then the exclusive scan of the block counts, and the write pass: the first component's
 //            coefficients straight to global memory (zeroed before), every index checked against the image's block count;
+//   plain    a picture WITHOUT a restart interval on a handle whose OMNI_JPEGDEC_PLAIN_WGS is W >= 2 (snapshotted by the handle; 0 or 1: the entropy kernel as
+//            above, nothing else launched or allocated) is JD_MODE_SPREAD: no business of the entropy kernel's, whose code stays what it was.  It takes three
+//            launches instead, all on the caller's stream:
+//              chunk  grid (most chunks of a picture, images): phases 1-2 (jd_relax, the entropy kernel's own) over the chunk's subsequences in LDS, the guess as
+//                     the entry of the chunk's first one; exit state, entry used and count of every subsequence go to the handle's state arrays
+//                     [image][subsequence]; rounds (max) and chunks that ran (+1) to the picture's flag words;
+//              seam   one workgroup per picture: the SAME relaxation over all the picture's subsequences on the state arrays -- a subsequence is decoded again only
+//                     when its predecessor's exit differs from the entry it last used, so only what the seams between chunks got wrong is repaired; at most n_sub
+//                     rounds, the break workgroup-uniform through LDS; then the exclusive scan of the counts over the picture, in place.  The workgroup's waves
+//                     exchange the state through GLOBAL memory across __syncthreads() (one CU, one L1; the arrays are neither const nor __restrict__, so no load is
+//                     hoisted over a barrier or sent down the scalar path);
+//              write  grid (ceil(most subsequences / JD_THREADS), images), one subsequence per lane: phase 4 from the stored entry and first block.
+//            NO WORKGROUP WAITS FOR ANOTHER: the three launches are ordered by the stream alone, every loop has a bound known at launch, every barrier is
+//            workgroup-uniform, and a picture's workgroups meet only in the atomically combined flag words;
 //   dc       one workgroup per image: the status, then the scan of the DC differences in scan order -- segmented at every restart interval's first block;
 //   block    across all images, one 8 x 8 block per lane: dequantise, islow IDCT, clamp, store cropped.  A CORRUPT image is written as zeros; the pixels of a
 //            file the host decoded are copied from the uploaded block.
@@ -25,7 +39,7 @@ static_assert(JD_MAX_SUBSEQ == 16 * JD_THREADS, "16 subsequences per lane: the l
 
 struct omni_jpegdec {
     omni_ctx* ctx = nullptr;
-    int w = 0, h = 0, max_images = 0, subseq_bits = 0, restart_wgs = 0;
+    int w = 0, h = 0, max_images = 0, subseq_bits = 0, restart_wgs = 0, plain_wgs = 0;
     int64_t capacity = 0;
     uint32_t nyb_max = 0;                  // blocks of the first component of a w x h picture with 16 x 16 MCUs
     size_t in_bytes = 0, tab_bytes = 0;    // tab_bytes: room for one picture's interval and chunk tables (restart_wgs >= 1)
@@ -33,13 +47,20 @@ struct omni_jpegdec {
     uint8_t* d_in = nullptr;               // the uploaded block: descriptors | clean scans | host-decoded pixels
     int16_t* d_coef = nullptr;             // [max_images][nyb_max][64] + guard
     int32_t* d_dc = nullptr;               // [max_images][nyb_max] + guard
-    int* d_flags = nullptr;                // [3][max_images]: error bits, relaxation rounds, chunks that ran -- zeroed in front of every entropy launch
+    int* d_flags = nullptr;                // [flag_words][max_images]: error bits, relaxation rounds, chunks that ran (plain_wgs >= 2: + seam rounds, subsequences
+                                           // the seam relaxation changed) -- zeroed in front of every entropy launch
+    int flag_words = 3;
+    uint8_t* d_state = nullptr;            // plain_wgs >= 2: counts u32 | exit states u16 | entries used u16, each [max_images][state_cap], + guard
+    uint32_t state_cap = 0;                // plain_wgs * JD_MAX_SUBSEQ: subsequences of a spread picture, at most
     omni::HostBuf hin;
     hipEvent_t ev_upload = nullptr;        // the pinned block is free again
     hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};      // in front of the upload, behind it, behind the kernels (omni_jpegdec_last_ms)
     size_t last_bytes = 0;
     bool timed = false;                    // ev_t hold ONE call's three events
     int last_n = 0, last_chunks = 1;       // last_chunks: the most chunks of a picture of the last pack (the entropy kernel's grid)
+    int last_spread_chunks = 0;            // ... of a picture that takes the spread path (the chunk kernel's grid; 0: none does, nothing more is launched)
+    uint32_t last_spread_sub = 0;          // ... and the most subsequences of one (the write kernel's grid)
+    bool last_unspread = true;             // a picture of the last pack is decoded by the entropy kernel
     std::mutex mu;
 };
 
@@ -80,6 +101,58 @@ struct JdIntervals {
     }
 };
 
+// Phases 1 and 2 over the N subsequences [sub0, sub0 + N) of the intervals [k0, k1), for the whole workgroup: ex / used / of / cnt [N] and *changed (zero on entry)
+// in LDS; a barrier stands in front of the call and behind it.  The first subsequence of an interval -- and the first of the N, where the caller starts inside an
+// interval: a chunk of a picture without a restart interval -- keeps the entry 0.  Returns the rounds that changed something, the same in every lane
+__device__ __forceinline__ int jd_relax(const jd::Tables& T, const uint8_t* scan, uint32_t n_words, uint32_t S, const JdIntervals& ivs, uint32_t k0, uint32_t k1,
+                                        uint32_t sub0, uint32_t N, uint16_t* ex, uint16_t* used, uint16_t* of, uint32_t* cnt, int* changed) {
+    const int tid = threadIdx.x;
+    jd::NoEmit none;
+    int e;
+    for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 1: every subsequence from the guess
+        const uint32_t k = ivs.iv ? jd::interval_of(ivs.iv, k0, k1, sub0 + i) : 0u;
+        const jd::Interval I = ivs.at(k);
+        uint16_t x;
+        cnt[i] = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, (uint16_t)0, 0u, 0xffffffffu, none, &x, &e);
+        ex[i] = x;
+        used[i] = 0;
+        of[i] = (uint16_t)(k - k0);
+    }
+    __syncthreads();
+    int rounds = 0;
+    for (uint32_t r = 0; r < N; ++r) {                                                      // 2: relaxation; every lane runs the same number of rounds
+        uint32_t need = 0;
+        for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
+            if (i == 0 || of[i] != of[i - 1]) continue;                                     // the first of its interval: the entry 0 is the true one
+            const uint16_t en = ex[i - 1];
+            if (en != used[i]) { used[i] = en; need |= 1u << k; }
+        }
+        __syncthreads();                                                                    // every entry is read before any exit is written
+        for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
+            if (!(need >> k & 1u)) continue;
+            const jd::Interval I = ivs.at(k0 + of[i]);
+            uint16_t x;
+            const uint32_t c = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, used[i], 0u, 0xffffffffu, none, &x, &e);
+            if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; *changed = 1; }
+        }
+        __syncthreads();
+        const int ch = *changed;
+        __syncthreads();
+        if (!ch) break;                                                                     // (uniform)
+        if (tid == 0) *changed = 0;
+        ++rounds;
+    }
+    __syncthreads();
+    return rounds;
+}
+
+// the handle's state arrays (OMNI_JPEGDEC_PLAIN_WGS >= 2), each [max_images][cap]: what the chunk kernel leaves for the seam kernel, and that one for the write kernel
+struct JdState {
+    uint32_t* cnt;                                          // blocks completed (the seam kernel: + JD_SEAM_* marks; behind it: the first block)
+    uint16_t *ex, *used;                                    // exit state; the entry it was last decoded from
+    uint32_t cap;
+};
+
 // flags: [3][max_images] int32 zeroed on the stream in front of the launch -- error bits (OR), relaxation rounds (max), chunks that ran (+1): a picture's
 // workgroups meet nowhere else, and none waits for another
 __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8_t* __restrict__ in, int16_t* __restrict__ coef, int32_t* __restrict__ dcd,
@@ -115,42 +188,8 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8
     const uint8_t* scan = in + d->dev_off;
     const uint32_t n_words = jd::scan_words((int64_t)(total_bits >> 3));
     __syncthreads();
-    jd::NoEmit none;
+    const int rounds = jd_relax(T, scan, n_words, S, ivs, k0, k1, sub0, N, ex, used, of, cnt, &changed);      // 1, 2
     int e;
-    for (uint32_t i = tid; i < N; i += JD_THREADS) {                                        // 1: every subsequence from the guess
-        const uint32_t k = ivs.iv ? jd::interval_of(ivs.iv, k0, k1, sub0 + i) : 0u;
-        const jd::Interval I = ivs.at(k);
-        uint16_t x;
-        cnt[i] = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, (uint16_t)0, 0u, 0xffffffffu, none, &x, &e);
-        ex[i] = x;
-        used[i] = 0;
-        of[i] = (uint16_t)(k - k0);
-    }
-    __syncthreads();
-    int rounds = 0;
-    for (uint32_t r = 0; r < N; ++r) {                                                      // 2: relaxation; every lane runs the same number of rounds
-        uint32_t need = 0;
-        for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
-            if (i == 0 || of[i] != of[i - 1]) continue;                                     // the first of its interval: the entry 0 is the true one
-            const uint16_t en = ex[i - 1];
-            if (en != used[i]) { used[i] = en; need |= 1u << k; }
-        }
-        __syncthreads();                                                                    // every entry is read before any exit is written
-        for (uint32_t i = tid, k = 0; i < N; i += JD_THREADS, ++k) {
-            if (!(need >> k & 1u)) continue;
-            const jd::Interval I = ivs.at(k0 + of[i]);
-            uint16_t x;
-            const uint32_t c = jd::decode_subseq_seg(T, scan, n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, used[i], 0u, 0xffffffffu, none, &x, &e);
-            if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = 1; }
-        }
-        __syncthreads();
-        const int ch = changed;
-        __syncthreads();
-        if (!ch) break;                                                                     // (uniform)
-        if (tid == 0) changed = 0;
-        ++rounds;
-    }
-    __syncthreads();
     uint32_t carry = 0;                                                                     // 3: counts -> their exclusive prefix over the chunk, in place
     for (uint32_t base = 0; base < N; base += JD_THREADS) {
         const uint32_t i = base + tid;
@@ -189,6 +228,149 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_entropy_kernel(const uint8
     }
 }
 
+// ---- a picture without a restart interval over several workgroups (OMNI_JPEGDEC_PLAIN_WGS >= 2; jpeg_dec_plan.h, plain) ------------------------------------------
+__device__ __forceinline__ void jd_load_tables(jd::Tables* T, const jd::Desc* d) {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(&d->T);
+    uint32_t* t = reinterpret_cast<uint32_t*>(T);
+    for (int i = threadIdx.x; i < (int)(sizeof(jd::Tables) / 4); i += JD_THREADS) t[i] = s[i];
+}
+
+// chunk: grid (most chunks of a spread picture, images).  Phases 1-2 over the chunk's subsequences; nothing another workgroup wrote is read
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_chunk_kernel(const uint8_t* __restrict__ in, JdState st, int* __restrict__ flags, int max_images) {
+    __shared__ jd::Tables T;
+    __shared__ uint16_t ex[JD_MAX_SUBSEQ], used[JD_MAX_SUBSEQ], of[JD_MAX_SUBSEQ];
+    __shared__ uint32_t cnt[JD_MAX_SUBSEQ];
+    __shared__ int changed;
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
+    const uint32_t C = d->spread_chunks;
+    if (d->mode != jd::JD_MODE_SPREAD || blockIdx.x >= C) return;                           // (uniform)
+    const uint32_t n_sub = d->n_sub < st.cap ? d->n_sub : st.cap;                           // (the host plans no more; the seam kernel reports more as an error)
+    const uint32_t sub0 = jd::plain_chunk_begin(blockIdx.x, n_sub, C), sub1 = jd::plain_chunk_begin(blockIdx.x + 1, n_sub, C);
+    const uint32_t N = sub1 - sub0 < JD_MAX_SUBSEQ ? sub1 - sub0 : JD_MAX_SUBSEQ;           // (the host made every chunk <= JD_MAX_SUBSEQ; the LDS arrays hold no more)
+    jd_load_tables(&T, d);
+    if (tid == 0) changed = 0;
+    const uint32_t total_bits = d->total_bits;
+    const JdIntervals ivs{nullptr, total_bits, d->n_sub, d->n_blocks};                      // the whole scan as one interval; the chunk starts inside it
+    __syncthreads();
+    const int rounds = jd_relax(T, in + d->dev_off, jd::scan_words((int64_t)(total_bits >> 3)), d->subseq_bits, ivs, 0u, 1u, sub0, N, ex, used, of, cnt, &changed);
+    const size_t at = (size_t)img * st.cap + sub0;
+    for (uint32_t i = tid; i < N; i += JD_THREADS) {
+        st.ex[at + i] = ex[i];
+        st.used[at + i] = used[i];
+        st.cnt[at + i] = cnt[i];
+    }
+    if (tid == 0) {
+        if (sub1 - sub0 > JD_MAX_SUBSEQ) atomicOr(&flags[img], 1);                          // decoded in part: CORRUPT, not OK
+        atomicMax(&flags[max_images + img], rounds);
+        atomicAdd(&flags[2 * max_images + img], 1);
+    }
+}
+
+// seam: one workgroup per picture, behind every workgroup of the chunk kernel (the stream orders them).  The relaxation of phase 2 over ALL the picture's
+// subsequences, on the state arrays: after a round, only the subsequences behind one that changed can need another decode, so a round looks at [lo, hi) alone
+// -- the same rounds and the same fixed point as looking at all of them.  The arrays are exchanged between the workgroup's waves across __syncthreads(): plain
+// pointers, neither const nor __restrict__
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_seam_kernel(const uint8_t* __restrict__ in, uint32_t* cnt_all, uint16_t* ex_all, uint16_t* used_all, uint32_t cap,
+                                                                  int* __restrict__ flags, int max_images) {
+    __shared__ jd::Tables T;
+    __shared__ uint32_t lds[JD_THREADS / 64 + 1];
+    __shared__ int changed;
+    __shared__ uint32_t lo_next, hi_next, n_moved;
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
+    if (d->mode != jd::JD_MODE_SPREAD) return;                                              // (uniform)
+    const uint32_t N = d->n_sub < cap ? d->n_sub : cap;
+    uint32_t* cnt = cnt_all + (size_t)img * cap;
+    uint16_t* ex = ex_all + (size_t)img * cap;
+    uint16_t* used = used_all + (size_t)img * cap;
+    jd_load_tables(&T, d);
+    if (tid == 0) { changed = 0; lo_next = 0xffffffffu; hi_next = 0u; n_moved = 0u; }
+    const uint32_t S = d->subseq_bits, total_bits = d->total_bits;
+    const uint8_t* scan = in + d->dev_off;
+    const uint32_t n_words = jd::scan_words((int64_t)(total_bits >> 3));
+    __syncthreads();
+    jd::NoEmit none;
+    int e, rounds = 0;
+    uint32_t lo = 1u, hi = N;                                                               // the subsequences whose predecessor may have changed
+    for (uint32_t r = 0; r < N; ++r) {                                                      // at most N rounds; every lane runs the same number
+        for (uint32_t i = lo + tid; i < hi; i += JD_THREADS) {
+            const uint16_t en = ex[i - 1];
+            if (en != used[i]) { used[i] = en; cnt[i] |= JD_SEAM_NEED; }
+        }
+        __syncthreads();                                                                    // every entry is read before any exit is written
+        for (uint32_t i = lo + tid; i < hi; i += JD_THREADS) {
+            const uint32_t c0 = cnt[i];
+            if (!(c0 & JD_SEAM_NEED)) continue;
+            uint16_t x;
+            const uint32_t c = jd::decode_subseq(T, scan, n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, &x, &e) & JD_SEAM_COUNT;
+            if (x != ex[i] || c != (c0 & JD_SEAM_COUNT)) {
+                ex[i] = x;
+                cnt[i] = c | JD_SEAM_CHANGED;
+                changed = 1;
+                atomicMin(&lo_next, i);
+                atomicMax(&hi_next, i);
+            } else {
+                cnt[i] = c0 & ~JD_SEAM_NEED;
+            }
+        }
+        __syncthreads();
+        const int ch = changed;
+        const uint32_t first = lo_next, last = hi_next;
+        __syncthreads();
+        if (!ch) break;                                                                     // (uniform)
+        if (tid == 0) { changed = 0; lo_next = 0xffffffffu; hi_next = 0u; }
+        lo = first + 1u;                                                                    // (first <= last < N)
+        hi = last + 2u < N ? last + 2u : N;
+        ++rounds;
+    }
+    __syncthreads();
+    uint32_t carry = 0, moved = 0;                                                          // 3: counts -> their exclusive prefix over the picture, in place
+    for (uint32_t base = 0; base < N; base += JD_THREADS) {
+        const uint32_t i = base + tid, v = i < N ? cnt[i] : 0u;
+        moved += v >> 30 & 1u;
+        uint32_t sum;
+        const uint32_t excl = jd_wg_scan<JD_THREADS>(v & JD_SEAM_COUNT, lds, &sum);
+        if (i < N) cnt[i] = carry + excl;
+        carry += sum;
+    }
+    if (moved) atomicAdd(&n_moved, moved);
+    __syncthreads();
+    if (tid == 0) {
+        if (d->n_sub > cap) atomicOr(&flags[img], 1);                                       // (the host plans no such picture)
+        atomicAdd(&flags[max_images + img], rounds);                                        // behind the chunk kernel's maximum: the picture's rounds
+        flags[3 * max_images + img] = rounds;
+        flags[4 * max_images + img] = (int)n_moved;
+    }
+}
+
+// write: grid (ceil(most subsequences of a spread picture / JD_THREADS), images), one subsequence per lane: phase 4 from the stored entry and first block
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_write_kernel(const uint8_t* __restrict__ in, int16_t* __restrict__ coef, int32_t* __restrict__ dcd, uint32_t nyb_max,
+                                                                   const uint32_t* __restrict__ first_all, const uint16_t* __restrict__ used_all, uint32_t cap,
+                                                                   int* __restrict__ flags) {
+    __shared__ jd::Tables T;
+    const int img = blockIdx.y;
+    const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
+    if (d->mode != jd::JD_MODE_SPREAD) return;                                              // (uniform)
+    const uint32_t N = d->n_sub < cap ? d->n_sub : cap;
+    if (blockIdx.x * JD_THREADS >= N) return;                                               // (uniform)
+    jd_load_tables(&T, d);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * JD_THREADS + threadIdx.x;
+    if (i >= N) return;                                                                     // (no barrier below)
+    const uint32_t total_bits = d->total_bits, n_blocks = d->n_blocks, fb = first_all[(size_t)img * cap + i];
+    const uint16_t entry = i ? used_all[(size_t)img * cap + i] : (uint16_t)0;
+    jd::CoefEmit em;
+    em.coef = coef + (size_t)img * nyb_max * 64;
+    em.dcd = dcd + (size_t)img * nyb_max;
+    em.n_yblocks = d->n_yblocks < nyb_max ? d->n_yblocks : nyb_max;
+    em.start(T, fb, entry >> 12);
+    uint16_t x;
+    int e;
+    const uint32_t wrote = jd::decode_subseq(T, in + d->dev_off, jd::scan_words((int64_t)(total_bits >> 3)), total_bits, i, d->subseq_bits, entry, fb, n_blocks, em, &x, &e);
+    if (e || (i + 1 == N && fb + wrote < n_blocks)) atomicOr(&flags[img], 1);               // an error on the true chain, or the scan ends before the picture's last block
+}
+
 // one workgroup per image: the status, once, behind every workgroup of the entropy kernel; then the scan of the DC differences in scan order -- with a restart
 // interval a segmented one: the running sum starts again every restart * ny blocks
 __global__ __launch_bounds__(JD_THREADS) void jpegdec_dc_kernel(const uint8_t* __restrict__ in, int32_t* __restrict__ dcd, uint32_t nyb_max, const int* __restrict__ flags,
@@ -196,7 +378,7 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_dc_kernel(const uint8_t* _
     __shared__ uint32_t lds[JD_THREADS / 64 + 1];
     __shared__ uint32_t tile[JD_THREADS];
     const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + blockIdx.x;
-    const bool dec = d->mode == jd::JD_MODE_DECODE;
+    const bool dec = d->mode == jd::JD_MODE_DECODE || d->mode == jd::JD_MODE_SPREAD;
     if (threadIdx.x == 0) status[blockIdx.x] = dec && flags[blockIdx.x] ? OMNI_JPEGDEC_CORRUPT : d->status;
     if (!dec) return;
     const uint32_t n = d->n_yblocks < nyb_max ? d->n_yblocks : nyb_max;
@@ -225,7 +407,7 @@ __global__ __launch_bounds__(JD_BLOCK_THREADS) void jpegdec_block_kernel(const u
     const uint32_t y = blockIdx.x * JD_BLOCK_THREADS + threadIdx.x;
     const jd::Desc* d = reinterpret_cast<const jd::Desc*>(in) + img;
     uint8_t* o = out + (int64_t)img * out_stride * h;
-    if (d->mode == jd::JD_MODE_DECODE && d->w == w && d->h == h) {
+    if ((d->mode == jd::JD_MODE_DECODE || d->mode == jd::JD_MODE_SPREAD) && d->w == w && d->h == h) {
         if (y >= d->n_yblocks || y >= nyb_max) return;
         jd::block_out(*d, coef + (size_t)img * nyb_max * 64, dcv + (size_t)img * nyb_max, y, status[img] == OMNI_JPEGDEC_CORRUPT, o, out_stride);
         return;
@@ -246,10 +428,24 @@ __global__ __launch_bounds__(JD_BLOCK_THREADS) void jpegdec_block_kernel(const u
 static int jpegdec_launch(omni_jpegdec* d, hipStream_t stream, int n_images, uint8_t* out_dev, int out_stride, int* status_dev) {
     OMNI_HIP_TRY(hipMemsetAsync(d->d_coef, 0, (size_t)n_images * d->nyb_max * 64 * sizeof(int16_t), stream));
     OMNI_HIP_TRY(hipMemsetAsync(d->d_dc, 0, (size_t)n_images * d->nyb_max * sizeof(int32_t), stream));
-    OMNI_HIP_TRY(hipMemsetAsync(d->d_flags, 0, (size_t)3 * d->max_images * sizeof(int), stream));
-    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(d->last_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->nyb_max, d->d_flags,
-                       d->max_images);
-    OMNI_LAUNCH_CHECK();
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_flags, 0, (size_t)d->flag_words * d->max_images * sizeof(int), stream));
+    if (d->last_unspread) {                                                                 // (always, unless OMNI_JPEGDEC_PLAIN_WGS spread every picture of the batch)
+        hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(d->last_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->nyb_max, d->d_flags,
+                           d->max_images);
+        OMNI_LAUNCH_CHECK();
+    }
+    if (d->last_spread_chunks) {                                                            // pictures without a restart interval over several workgroups
+        const size_t subs = (size_t)d->max_images * d->state_cap;
+        JdState st{reinterpret_cast<uint32_t*>(d->d_state), reinterpret_cast<uint16_t*>(d->d_state + subs * 4), reinterpret_cast<uint16_t*>(d->d_state + subs * 6),
+                   d->state_cap};
+        hipLaunchKernelGGL(jpegdec_chunk_kernel, dim3(d->last_spread_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, st, d->d_flags, d->max_images);
+        OMNI_LAUNCH_CHECK();
+        hipLaunchKernelGGL(jpegdec_seam_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, st.cnt, st.ex, st.used, st.cap, d->d_flags, d->max_images);
+        OMNI_LAUNCH_CHECK();
+        hipLaunchKernelGGL(jpegdec_write_kernel, dim3(cdiv((int)d->last_spread_sub, JD_THREADS), n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc,
+                           d->nyb_max, st.cnt, st.used, st.cap, d->d_flags);
+        OMNI_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_dc, d->nyb_max, d->d_flags, status_dev);
     OMNI_LAUNCH_CHECK();
     const int raster = cdiv(d->w, 8) * cdiv(d->h, 8);
@@ -276,7 +472,9 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
     if (d->ev_upload) OMNI_HIP_TRY(hipEventSynchronize(d->ev_upload));                        // the last upload has left the pinned block
     uint8_t* base = d->hin.as<uint8_t>();
     size_t at = align16((size_t)n_images * sizeof(jd::Desc));
-    int max_chunks = 1;
+    int max_chunks = 1, spread_chunks = 0;
+    uint32_t spread_sub = 0;
+    bool unspread = d->plain_wgs < 2;                                                       // (switch off: the entropy kernel is launched whatever the batch holds)
     jd::ChunkPlan plan;
     std::vector<int64_t> rst;
     for (int i = 0; i < n_images; ++i) {
@@ -306,6 +504,7 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
                 D.n_chunks = plan.n_chunks;
                 D.tab_off = (int64_t)(at + scan_bytes);
                 if ((int)plan.n_chunks > max_chunks) max_chunks = (int)plan.n_chunks;
+                unspread = true;
                 at += scan_bytes + align16(plan.table_bytes());
                 continue;
             }
@@ -314,8 +513,18 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
             const int64_t n = jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, nullptr, 0, nullptr);
             D.mode = jd::JD_MODE_DECODE;
             D.total_bits = (uint32_t)(n * 8);
-            D.subseq_bits = jd::subseq_bits_for(D.total_bits, (uint32_t)d->subseq_bits, JD_MAX_SUBSEQ);
+            D.subseq_bits = d->plain_wgs >= 2 ? jd::plain_subseq_bits(D.total_bits, (uint32_t)d->subseq_bits, (uint32_t)d->plain_wgs, JD_MAX_SUBSEQ)
+                                              : jd::subseq_bits_for(D.total_bits, (uint32_t)d->subseq_bits, JD_MAX_SUBSEQ);
             D.n_sub = (D.total_bits + D.subseq_bits - 1) / D.subseq_bits;
+            const uint32_t C = d->plain_wgs >= 2 ? jd::plain_chunks(D.n_sub, (uint32_t)d->plain_wgs) : 1u;
+            if (C >= 2 && D.n_sub <= d->state_cap) {                                        // the spread path; one chunk is the entropy kernel's, as ever
+                D.mode = jd::JD_MODE_SPREAD;
+                D.spread_chunks = C;
+                if ((int)C > spread_chunks) spread_chunks = (int)C;
+                if (D.n_sub > spread_sub) spread_sub = D.n_sub;
+            } else {
+                unspread = true;
+            }
             at += align16((size_t)n + JD_SCAN_PAD);
         } else if (D.status == OMNI_JPEGDEC_HOST) {
             const int st = jd::decode_sequential(files[i], D, base + at, d->w);
@@ -329,6 +538,9 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
     OMNI_REQUIRE(at <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: %zu bytes to upload, the handle holds %zu", at, d->in_bytes);
     memcpy(base, descs.data(), (size_t)n_images * sizeof(jd::Desc));
     d->last_chunks = max_chunks;
+    d->last_spread_chunks = spread_chunks;
+    d->last_spread_sub = spread_sub;
+    d->last_unspread = unspread;
     *bytes = at;
     return OMNI_OK;
 }
@@ -350,11 +562,11 @@ extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int heigh
     if (config_resolve(&cfg) != OMNI_OK) return nullptr;
     const int S = cfg[CFG_JPEGDEC_SUBSEQ_BITS];
     if (S & (S - 1)) { set_error("OMNI_JPEGDEC_SUBSEQ_BITS=%d: expected a power of two", S); return nullptr; }
-    const int W = cfg[CFG_JPEGDEC_RESTART_WGS];
+    const int W = cfg[CFG_JPEGDEC_RESTART_WGS], PW = cfg[CFG_JPEGDEC_PLAIN_WGS];
     std::lock_guard<std::mutex> lk(ctx->mu);
     (void)hipSetDevice(ctx->device);
     omni_jpegdec* d = new omni_jpegdec();
-    d->ctx = ctx; d->w = width; d->h = height; d->max_images = max_images; d->capacity = capacity_per_image; d->subseq_bits = S; d->restart_wgs = W; d->nyb_max = (uint32_t)nyb;
+    d->ctx = ctx; d->w = width; d->h = height; d->max_images = max_images; d->capacity = capacity_per_image; d->subseq_bits = S; d->restart_wgs = W; d->plain_wgs = PW; d->nyb_max = (uint32_t)nyb;
     // per image: a descriptor and the larger of a clean scan and the picture itself
     const size_t per_scan = align16((size_t)capacity_per_image + JD_SCAN_PAD), per_px = align16((size_t)width * height);
     // ... and, with OMNI_JPEGDEC_RESTART_WGS on, its interval and chunk tables: one interval per MCU of 8 x 8 at the most, and no more than W chunks hold
@@ -364,14 +576,21 @@ extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int heigh
     }
     d->in_bytes = align16((size_t)max_images * sizeof(jd::Desc)) + (size_t)max_images * ((per_scan > per_px ? per_scan : per_px) + d->tab_bytes);
     const size_t coef_bytes = (size_t)max_images * nyb * 64 * sizeof(int16_t), dc_bytes = (size_t)max_images * nyb * sizeof(int32_t);
+    // OMNI_JPEGDEC_PLAIN_WGS >= 2: the state arrays of the spread path (8 bytes per subsequence) and two more flag words per picture; otherwise neither
+    if (PW >= 2) { d->state_cap = (uint32_t)PW * JD_MAX_SUBSEQ; d->flag_words = 5; }
+    const size_t state_bytes = (size_t)max_images * d->state_cap * 8;
     auto make = [&]() -> int {
         int rc;
         if ((rc = d->mem.alloc(&d->d_in, d->in_bytes)) || (rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
-            (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_flags, (size_t)3 * max_images * sizeof(int))))
+            (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_flags, (size_t)d->flag_words * max_images * sizeof(int))))
             return rc;
+        if (state_bytes) {
+            if ((rc = d->mem.alloc(&d->d_state, state_bytes + OMNI_JPEGDEC_GUARD_BYTES))) return rc;
+            OMNI_HIP_TRY(hipMemset(d->d_state + state_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
+        }
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_coef) + coef_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_dc) + dc_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
-        OMNI_HIP_TRY(hipMemset(d->d_flags, 0, (size_t)3 * max_images * sizeof(int)));
+        OMNI_HIP_TRY(hipMemset(d->d_flags, 0, (size_t)d->flag_words * max_images * sizeof(int)));
         if ((rc = d->hin.ensure(d->in_bytes))) return rc;
         OMNI_HIP_TRY(hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming));
         for (hipEvent_t& e : d->ev_t) OMNI_HIP_TRY(hipEventCreate(&e));
@@ -454,7 +673,7 @@ extern "C" int omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subs
     if (rounds && d->last_n) OMNI_HIP_TRY(hipMemcpy(rounds, d->d_flags + d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
     const omni::jd::Desc* descs = d->hin.as<omni::jd::Desc>();                                // (the pinned block still holds the last enqueue's descriptors)
     for (int i = 0; i < d->last_n; ++i) {
-        const bool dec = descs[i].mode == omni::jd::JD_MODE_DECODE;
+        const bool dec = descs[i].mode == omni::jd::JD_MODE_DECODE || descs[i].mode == omni::jd::JD_MODE_SPREAD;
         if (n_subseq) n_subseq[i] = dec ? (int)descs[i].n_sub : 0;
         if (subseq_bits) subseq_bits[i] = dec ? (int)descs[i].subseq_bits : 0;
     }
@@ -467,6 +686,26 @@ extern "C" int omni_jpegdec_last_chunks(omni_jpegdec* d, int* chunks) {
     (void)hipSetDevice(d->ctx->device);
     OMNI_HIP_TRY(hipDeviceSynchronize());
     if (d->last_n) OMNI_HIP_TRY(hipMemcpy(chunks, d->d_flags + 2 * (size_t)d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_last_seam(omni_jpegdec* d, int* seam_rounds, int* seam_changed) {
+    OMNI_REQUIRE(d, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(d->mu);
+    (void)hipSetDevice(d->ctx->device);
+    OMNI_HIP_TRY(hipDeviceSynchronize());
+    int* const out[2] = {seam_rounds, seam_changed};
+    for (int k = 0; k < 2; ++k) {
+        if (!out[k] || !d->last_n) continue;
+        if (d->flag_words < 5) memset(out[k], 0, (size_t)d->last_n * sizeof(int));            // (the switch is off: no picture has a seam)
+        else OMNI_HIP_TRY(hipMemcpy(out[k], d->d_flags + (size_t)(3 + k) * d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_debug_state_buffer(omni_jpegdec* d, void** state_dev, int64_t* state_bytes) {
+    OMNI_REQUIRE(d && state_dev && state_bytes, OMNI_ERR_INVALID, "null argument");
+    *state_dev = d->d_state; *state_bytes = (int64_t)d->max_images * d->state_cap * 8;
     return OMNI_OK;
 }
 

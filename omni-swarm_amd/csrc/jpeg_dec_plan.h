@@ -46,6 +46,14 @@
 //              Fewer markers than ceil(mcus / restart) - 1: CORRUPT (decode_sequential: seg >= n_rst); surplus markers are ignored.  Phase 5 becomes a
 //              segmented scan: the running DC sum restarts every restart * ny blocks of the first component.  A file that cannot be planned (more intervals in a
 //              chunk than max_sub) stays HOST
+//   plain      a file WITHOUT a restart interval is one stream: no point inside it has a known state.  A handle whose OMNI_JPEGDEC_PLAIN_WGS is W >= 2 still spreads
+//              it, because the relaxation of phase 2 reaches its fixed point from ANY starting state: C = plain_chunks(n_sub, W) = min(W, n_sub) chunks of consecutive
+//              subsequences, chunk c = [plain_chunk_begin(c, n_sub, C), plain_chunk_begin(c + 1, n_sub, C)) = [c n_sub / C, (c + 1) n_sub / C), with S =
+//              plain_subseq_bits(): the configured length doubled only until every chunk holds at most max_sub subsequences.  Phases 1-2 run per chunk, the chunk's
+//              first subsequence keeping the guess as its entry -- one workgroup per chunk, none reads what another wrote; then ONE relaxation over all the
+//              picture's subsequences (the SEAM relaxation: only what the seams between chunks got wrong is decoded again) ends in the same fixed point, the
+//              sequential decode; phase 3 is one scan over the picture, phase 4 one subsequence at a time from the stored entry and first block.  Phases 5-6 as
+//              ever.  Same pixels, same status as the one-chunk path for EVERY input (jpeg_decode_plain_parallel_host is the stand-in)
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -58,6 +66,7 @@
 #define JD_MAX_SUBSEQ_BITS 65536
 #define JD_MAX_SUBSEQ 4096                                   // subsequences a workgroup of the entropy kernel holds (csrc/jpeg_dec.hip: 16 per lane)
 #define JD_MAX_RESTART_WGS 64                                // workgroups a restart-interval picture is spread over, at most (OMNI_JPEGDEC_RESTART_WGS)
+#define JD_MAX_PLAIN_WGS 64                                  // ... and a picture without a restart interval (OMNI_JPEGDEC_PLAIN_WGS)
 
 namespace omni {
 namespace jd {
@@ -82,6 +91,8 @@ struct Desc {
     int32_t mcus_x, mcus_y, restart, multi_scan;
     int32_t restart_only;                                   // HOST for its restart interval alone: without it the file would be OK
     uint32_t n_blocks, n_yblocks;                           // of the scan; of the first component (MCU padding included)
+    uint32_t spread_chunks;                                 // filled by whoever packs the image, like the fields below: >= 2: a picture without a restart interval
+                                                            // that takes the spread path (OMNI_JPEGDEC_PLAIN_WGS; mode JD_MODE_SPREAD) over that many chunks; 0: none
     int64_t scan_off, scan_bytes;                           // the scan's bytes in the file (stuffed, restart markers included)
     // filled by whoever packs the image for the kernels (jpeg_dec.hip)
     int32_t mode;                                           // JD_MODE_*
@@ -92,7 +103,7 @@ struct Desc {
     uint16_t q[64];                                         // the first component's quantisation table, natural order
     Tables T;
 };
-enum { JD_MODE_DECODE = 0, JD_MODE_PIXELS = 1, JD_MODE_ZERO = 2 };
+enum { JD_MODE_DECODE = 0, JD_MODE_PIXELS = 1, JD_MODE_ZERO = 2, JD_MODE_SPREAD = 3 };      // SPREAD: decoded like DECODE, by the chunk, seam and write kernels
 
 // ---- parser (host) -----------------------------------------------------------------------------------------------------------------------------------
 inline int build_hufftab(const uint8_t* bits, const uint8_t* vals, bool dc, HuffTab* t) {
@@ -413,6 +424,22 @@ JP_HD uint32_t subseq_bits_for(uint32_t total_bits, uint32_t S, uint32_t max_sub
     while (S < (1u << 30) && (total_bits + S - 1) / S > max_sub) S <<= 1;
     return S;
 }
+
+// ---- a picture without a restart interval over several workgroups: the partition ----------------------------------------------------------------------------------
+// the subsequence length of a handle whose OMNI_JPEGDEC_PLAIN_WGS is W: the configured one, doubled only until W chunks of at most max_sub hold the picture
+JP_HD uint32_t plain_subseq_bits(uint32_t total_bits, uint32_t S, uint32_t W, uint32_t max_sub) {
+    const uint64_t room = (uint64_t)W * max_sub;
+    return subseq_bits_for(total_bits, S, room > 0xffffffffull ? 0xffffffffu : (uint32_t)room);
+}
+// the chunks of a picture of n_sub subsequences: at least one, none empty
+JP_HD uint32_t plain_chunks(uint32_t n_sub, uint32_t W) { return n_sub < W ? (n_sub ? n_sub : 1u) : (W ? W : 1u); }
+// chunk c of C holds the subsequences [plain_chunk_begin(c), plain_chunk_begin(c + 1)); c == C: n_sub
+JP_HD uint32_t plain_chunk_begin(uint32_t c, uint32_t n_sub, uint32_t C) { return (uint32_t)((uint64_t)c * n_sub / C); }
+// a subsequence's words between the chunk relaxation, the seam relaxation and the write pass ([image][subsequence]: exit state, entry used, block count).  The
+// seam relaxation keeps two marks in a count's top bits; a subsequence of at most 2^30 bits completes fewer than 2^30 blocks
+#define JD_SEAM_NEED 0x80000000u                             // its predecessor's exit differs from the entry it last used: decode it again in this round
+#define JD_SEAM_CHANGED 0x40000000u                          // the seam relaxation changed its exit state or its count at least once
+#define JD_SEAM_COUNT 0x3fffffffu
 
 // ---- restart intervals ---------------------------------------------------------------------------------------------------------------------------------------
 // one interval of a planned restart file: its bits on the clean scan (absolute), its first subsequence (numbered through the picture) and its first block.  The
@@ -831,6 +858,89 @@ inline int jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, 
     dc_scan_host(dc.data(), d.n_yblocks, (uint32_t)d.restart * (uint32_t)d.T.ny);           // 5
     for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
     return err ? OMNI_JPEGDEC_CORRUPT : OMNI_JPEGDEC_OK;
+}
+
+// ---- files without a restart interval over several workgroups: the CPU stand-in ----------------------------------------------------------------------------------
+struct PlainStats {
+    uint32_t n_sub = 0, subseq_bits = 0, n_chunks = 0, chunk_rounds = 0;      // chunk_rounds: the maximum over the chunks of the rounds that changed something
+    uint32_t seam_rounds = 0, seam_changed = 0, seam_chunks = 0;              // seam relaxation: rounds that changed something, subsequences it changed at least
+                                                                              // once, and the chunks those lie in
+};
+// The CPU stand-in for the kernels of a handle whose OMNI_JPEGDEC_PLAIN_WGS is W >= 2: a file classified OK runs, by plain loops and in the kernels' order,
+//   1  every subsequence from the guess;  2a  Jacobi rounds inside each chunk until nothing changes (a chunk's first subsequence keeps the guess);
+//   2b Jacobi rounds over the whole picture until nothing changes (the seam relaxation);  3  one exclusive scan of the counts over the picture;  4-6 as
+//   jpeg_decode_parallel_host.  Every other file -- a restart interval included -- goes the way of jpeg_decode_parallel_host, its statistics zero.
+inline int jpeg_decode_plain_parallel_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t W, uint32_t max_sub, uint8_t* out, int64_t stride, int max_w,
+                                           int max_h, int* w, int* h, PlainStats* stats) {
+    Desc d;
+    const int st = parse(file, size, &d);
+    PlainStats ps;
+    if (stats) *stats = ps;
+    if (st != OMNI_JPEGDEC_OK || !out) return jpeg_decode_parallel_host(file, size, S, max_sub, out, stride, max_w, max_h, w, h, nullptr);
+    if (w) *w = d.w;
+    if (h) *h = d.h;
+    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
+    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
+    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), nullptr, 0, nullptr);
+    const uint32_t total_bits = (uint32_t)(nclean * 8), n_words = scan_words(nclean);
+    S = plain_subseq_bits(total_bits, S, W, max_sub);
+    const uint32_t N = (total_bits + S - 1) / S, C = plain_chunks(N, W);
+    std::vector<uint16_t> ex(N), used(N, 0);
+    std::vector<uint32_t> cnt(N), first(N);
+    std::vector<uint8_t> need(N), moved(N, 0);
+    NoEmit none;
+    int e;
+    auto again = [&](uint32_t i, uint16_t* x) { return decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, x, &e); };
+    // Jacobi rounds over [lo, hi), lo keeping its entry: the rounds that changed something
+    auto relax = [&](uint32_t lo, uint32_t hi, bool seam) {
+        uint32_t rounds = 0;
+        for (uint32_t r = 0; r < hi - lo; ++r) {
+            for (uint32_t i = lo + 1; i < hi; ++i) {
+                need[i] = ex[i - 1] != used[i];
+                if (need[i]) used[i] = ex[i - 1];
+            }
+            bool changed = false;
+            for (uint32_t i = lo + 1; i < hi; ++i) {
+                if (!need[i]) continue;
+                uint16_t x;
+                const uint32_t c = again(i, &x);
+                if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = true; if (seam) moved[i] = 1; }
+            }
+            if (!changed) break;
+            ++rounds;
+        }
+        return rounds;
+    };
+    ps.n_sub = N; ps.subseq_bits = S; ps.n_chunks = C;
+    for (uint32_t i = 0; i < N; ++i) cnt[i] = again(i, &ex[i]);                             // 1
+    for (uint32_t c = 0; c < C && N; ++c) {                                                 // 2a
+        const uint32_t rounds = relax(plain_chunk_begin(c, N, C), plain_chunk_begin(c + 1, N, C), false);
+        if (rounds > ps.chunk_rounds) ps.chunk_rounds = rounds;
+    }
+    if (N) ps.seam_rounds = relax(0, N, true);                                              // 2b
+    for (uint32_t c = 0; c < C && N; ++c) {
+        uint32_t n = 0;
+        for (uint32_t i = plain_chunk_begin(c, N, C); i < plain_chunk_begin(c + 1, N, C); ++i) n += moved[i];
+        ps.seam_changed += n;
+        ps.seam_chunks += n != 0;
+    }
+    if (stats) *stats = ps;
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < N; ++i) { first[i] = total; total += cnt[i]; }                 // 3
+    std::vector<int16_t> coef((size_t)d.n_yblocks * 64, 0);
+    std::vector<int32_t> dc(d.n_yblocks, 0);
+    int err = total < d.n_blocks;
+    for (uint32_t i = 0; i < N; ++i) {                                                      // 4
+        CoefEmit em;
+        em.coef = coef.data(); em.dcd = dc.data(); em.n_yblocks = d.n_yblocks;
+        em.start(d.T, first[i], used[i] >> 12);
+        uint16_t x;
+        decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], first[i], d.n_blocks, em, &x, &e);
+        err |= e;
+    }
+    dc_scan_host(dc.data(), d.n_yblocks, 0u);                                               // 5
+    for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
+    return err ? OMNI_JPEGDEC_CORRUPT : d.status;
 }
 
 }  // namespace jd
