@@ -629,7 +629,12 @@ int        omni_cam_jpeg(omni_cam* cam, omni_cam_jpeg_result* out);
  * decodes such a picture.  W >= 2: an OMNI_JPEGDEC_OK file is decoded over min(W, subsequences) chunks of consecutive subsequences that relax on their own, a seam
  * relaxation over the whole picture that repairs what the seams between chunks got wrong, and a write pass of one subsequence per lane; the subsequence length
  * is OMNI_JPEGDEC_SUBSEQ_BITS doubled only until W chunks of 4096 subsequences hold the picture.  No workgroup waits for another.  Same pixels, same status, the
- * classification untouched; the two switches are independent and one batch may hold both kinds of file. */
+ * classification untouched; the two switches are independent and one batch may hold both kinds of file.
+ * Unstuffing: OMNI_JPEGDEC_UNSTUFF_DEV (0 or 1, default 0), as it is when the handle is created.  0: the calling thread removes the 0xFF00 stuffing and the restart
+ * markers of every scan the kernels decode, byte by byte, and uploads the clean scans.  1: it visits the 0xFF bytes alone (the scan's end, the clean length, the
+ * restart offsets, the clean offset of every tile of 4096 raw bytes), uploads the scans as they stand in the files, and one kernel in front of the others compacts
+ * them tile by tile; the handle's device block and pinned block grow by max_images x (capacity_per_image + 32) bytes and the tile tables.  Same pixels, same
+ * status, same statistics; independent of the two switches above. */
 #define OMNI_JPEGDEC_OK 0
 #define OMNI_JPEGDEC_HOST 1
 #define OMNI_JPEGDEC_UNSUPPORTED 2
@@ -666,6 +671,26 @@ int           omni_jpegdec_debug_buffers(omni_jpegdec* d, void** coef_dev, int64
 /* ... and of the state arrays of a handle whose OMNI_JPEGDEC_PLAIN_WGS is W >= 2 (max_images x W x 4096 x 8 bytes, the same guard behind them); NULL and 0 on
  * every other handle: nothing is allocated there */
 int           omni_jpegdec_debug_state_buffer(omni_jpegdec* d, void** state_dev, int64_t* state_bytes);
+/* Of the handle's last enqueue on a handle whose OMNI_JPEGDEC_UNSTUFF_DEV is 1: the pictures whose scan the device unstuffed, the raw scan bytes uploaded for
+ * them and the clean bytes those became; 0 0 0 on a handle with the switch off */
+int           omni_jpegdec_last_unstuff(omni_jpegdec* d, int* device_pictures, int64_t* raw_bytes, int64_t* clean_bytes);
+/* TEST INFRASTRUCTURE: the device address behind the last clean area of the last enqueue (OMNI_JPEGDEC_UNSTUFF_DEV = 1) and the number of 0xA5 bytes that stand
+ * there, written on the stream in front of the unstuff kernel; NULL and 0 with the switch off */
+int           omni_jpegdec_debug_in_buffer(omni_jpegdec* d, void** clean_end_dev, int64_t* guard_bytes);
+/* TEST INFRASTRUCTURE: the unstuff kernel alone on an arbitrary byte string taken as a scan: survey on the host, upload, the kernel, download.  out_host
+ * [out_cap >= clean bytes + 16]: the clean bytes and the 16 zero bytes behind them, from a device block that was all 0xA5; *n_clean their number.  OMNI_ERR_HIP
+ * when anything behind the padding was written */
+int           omni_jpegdec_unstuff_dev(omni_ctx* ctx, const uint8_t* scan, int64_t n, uint8_t* out_host, int64_t out_cap, int64_t* n_clean);
+/* TEST INFRASTRUCTURE, no GPU: csrc/jpeg_dec_plan.h's unstuffing compiled by g++.  omni_jpeg_unstuff_tile_bytes: raw bytes per tile.  omni_jpeg_unstuff_host: the
+ * byte-wise pass (unstuff) over scan[0..n) -> out [out_cap >= n + 16]: the clean bytes + 16 zero bytes, *n_clean, and the clean offset behind every restart
+ * marker (rst [max_rst], *n_rst).  omni_jpeg_unstuff_tiled_host: survey + every tile compacted on its own (unstuff_tiled_host), out filled with 0xA5 beforehand;
+ * also *raw_end (where the scan's data end), *surveyed_clean (survey's count; *n_clean is the end of the last tile), tile_off [max_tiles >= n / tile + 1] and
+ * *n_tiles.  omni_jpeg_scan_end: scan_end() from `from`; -1 for bad arguments */
+int           omni_jpeg_unstuff_tile_bytes(void);
+int           omni_jpeg_unstuff_host(const uint8_t* scan, int64_t n, uint8_t* out, int64_t out_cap, int64_t* n_clean, int64_t* rst, int64_t max_rst, int64_t* n_rst);
+int           omni_jpeg_unstuff_tiled_host(const uint8_t* scan, int64_t n, uint8_t* out, int64_t out_cap, int64_t* n_clean, int64_t* rst, int64_t max_rst, int64_t* n_rst,
+                                           int64_t* raw_end, int64_t* surveyed_clean, uint32_t* tile_off, int64_t max_tiles, int64_t* n_tiles);
+int64_t       omni_jpeg_scan_end(const uint8_t* file, int64_t size, int64_t from);
 /* the classification of a file without a capacity, and its picture's size (0 x 0 when no frame header can be read); no GPU */
 int           omni_jpegdec_classify(const uint8_t* file, int64_t size, int* width, int* height);
 /* csrc/jpeg_dec_plan.h's sequential decoder compiled by g++ into the library, next to omni_jpeg_encode_host: the same pixels without a GPU, restart intervals

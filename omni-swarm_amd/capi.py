@@ -46,7 +46,9 @@ SYMBOLS = [
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
     "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
-    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_jpeg_decode_restart_parallel_host", "omni_jpegdec_last_chunks", "omni_jpeg_decode_plain_parallel_host", "omni_jpegdec_last_seam", "omni_jpegdec_debug_state_buffer", "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
+    "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_jpeg_decode_restart_parallel_host", "omni_jpegdec_last_chunks", "omni_jpeg_decode_plain_parallel_host", "omni_jpegdec_last_seam", "omni_jpegdec_debug_state_buffer",
+    "omni_jpegdec_last_unstuff", "omni_jpegdec_debug_in_buffer", "omni_jpegdec_unstuff_dev", "omni_jpeg_unstuff_tile_bytes", "omni_jpeg_unstuff_host", "omni_jpeg_unstuff_tiled_host", "omni_jpeg_scan_end",
+    "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
 ]
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
@@ -259,6 +261,13 @@ def lib():
     sig("omni_jpeg_decode_plain_parallel_host", C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _ip, _ip, _ip, _ip])
     sig("omni_jpegdec_last_seam", C.c_int, [_vp, _ip, _ip])
     sig("omni_jpegdec_debug_state_buffer", C.c_int, [_vp, C.POINTER(_vp), _i64p])
+    sig("omni_jpegdec_last_unstuff", C.c_int, [_vp, _ip, _i64p, _i64p])
+    sig("omni_jpegdec_debug_in_buffer", C.c_int, [_vp, C.POINTER(_vp), _i64p])
+    sig("omni_jpegdec_unstuff_dev", C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _i64p])
+    sig("omni_jpeg_unstuff_tile_bytes", C.c_int, [])
+    sig("omni_jpeg_unstuff_host", C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _i64p, _i64p, C.c_int64, _i64p])
+    sig("omni_jpeg_unstuff_tiled_host", C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _i64p, _i64p, C.c_int64, _i64p, _i64p, _i64p, _vp, C.c_int64, _i64p])
+    sig("omni_jpeg_scan_end", C.c_int64, [_vp, C.c_int64, C.c_int64])
     sig("omni_cam_order_after", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_set_active", C.c_int, [_vp, C.c_int])
     sig("omni_cam_ready", C.c_int, [_vp, C.POINTER(C.c_int)])
@@ -968,6 +977,48 @@ def jpeg_decode_plain_parallel_host(data: bytes, subseq_bits: int, plain_wgs: in
                              seam_chunks=stats[6], rounds=stats[3] + stats[4])
 
 
+def jpeg_unstuff_tile_bytes() -> int:
+    """csrc/jpeg_dec_plan.h JD_UNSTUFF_TILE: raw scan bytes per tile of the unstuffing by tiles"""
+    return lib().omni_jpeg_unstuff_tile_bytes()
+
+
+def jpeg_scan_end(data: bytes, start: int = 0) -> int:
+    """csrc/jpeg_dec_plan.h scan_end: where the entropy-coded data that start at `start` end"""
+    return lib().omni_jpeg_scan_end(data, len(data), start)
+
+
+def jpeg_unstuff_host(scan: bytes):
+    """the byte-wise pass (jd::unstuff; g++, no GPU) -> (clean bytes + the 16 bytes behind them u8, clean count, [clean offset behind every restart marker])"""
+    n = len(scan)
+    out = np.full(n + 16, 0xA5, np.uint8)
+    rst = (C.c_int64 * (n // 2 + 1))()
+    k, nr = C.c_int64(), C.c_int64()
+    _check(lib().omni_jpeg_unstuff_host(scan, n, out.ctypes.data_as(_vp), out.size, C.byref(k), rst, len(rst), C.byref(nr)))
+    return out[:k.value + 16].copy(), k.value, list(rst[:nr.value])
+
+
+def jpeg_unstuff_tiled_host(scan: bytes):
+    """survey + every tile compacted on its own into a buffer of 0xA5 (jd::survey, jd::unstuff_tiled_host: the CPU stand-in for jpegdec_unstuff_kernel) ->
+    dict(out: the clean bytes + 16 u8, n_clean: the end of the last tile, rst, raw_end, surveyed_clean, tile_off [n_tiles])"""
+    n = len(scan)
+    out = np.zeros(n + 16, np.uint8)
+    rst = (C.c_int64 * (n // 2 + 1))()
+    tiles = np.zeros(n // jpeg_unstuff_tile_bytes() + 1, np.uint32)
+    k, nr, re, sc, nt = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _check(lib().omni_jpeg_unstuff_tiled_host(scan, n, out.ctypes.data_as(_vp), out.size, C.byref(k), rst, len(rst), C.byref(nr), C.byref(re), C.byref(sc),
+                                              tiles.ctypes.data_as(_vp), tiles.size, C.byref(nt)))
+    return dict(out=out[:max(k.value, 0) + 16].copy(), n_clean=k.value, rst=list(rst[:nr.value]), raw_end=re.value, surveyed_clean=sc.value,
+                tile_off=[int(t) for t in tiles[:nt.value]])
+
+
+def jpegdec_unstuff_dev(ctx: "Context", scan: bytes):
+    """TEST INFRASTRUCTURE: jpegdec_unstuff_kernel alone on a byte string taken as a scan -> (clean bytes + the 16 bytes behind them u8, clean count)"""
+    out = np.full(len(scan) + 16, 0xA5, np.uint8)
+    k = C.c_int64()
+    _check(lib().omni_jpegdec_unstuff_dev(ctx.h, scan, len(scan), out.ctypes.data_as(_vp), out.size, C.byref(k)))
+    return out[:k.value + 16].copy(), k.value
+
+
 class JpegDec:
     """omni_jpegdec: up to max_images JPEG files of at most capacity_per_image bytes -> gray images of width x height on the GPU (is_compressed_images;
     csrc/jpeg_dec.hip, the arithmetic: csrc/jpeg_dec_plan.h)"""
@@ -1031,6 +1082,24 @@ class JpegDec:
         self.ctx.sync()
         self.guarded = 2 + bool(sp.value)                      # the buffers whose guards were looked at
         return all(bool((self.ctx.from_device(p.value + b.value, (JPEGDEC_GUARD_BYTES,), np.uint8) == 0xA5).all()) for p, b in ((cp, cb), (dp, db), (sp, sb)) if p.value)
+
+    def last_unstuff(self):
+        """(pictures whose scan the device unstuffed, raw scan bytes uploaded for them, clean bytes they became) of the last call; (0, 0, 0) on a handle whose
+        OMNI_JPEGDEC_UNSTUFF_DEV is 0"""
+        n, r, k = C.c_int(), C.c_int64(), C.c_int64()
+        _check(lib().omni_jpegdec_last_unstuff(self.h, C.byref(n), C.byref(r), C.byref(k)))
+        return n.value, r.value, k.value
+
+    def unstuff_guard_ok(self) -> bool:
+        """the 0xA5 bytes behind the last clean area of the last call (OMNI_JPEGDEC_UNSTUFF_DEV = 1) are intact; `unstuff_guarded`: whether there was such a guard
+        to look at (0 on a handle with the switch off: True)"""
+        p, b = _vp(), C.c_int64()
+        _check(lib().omni_jpegdec_debug_in_buffer(self.h, C.byref(p), C.byref(b)))
+        self.unstuff_guarded = int(bool(p.value))
+        if not p.value:
+            return True
+        self.ctx.sync()
+        return bool((self.ctx.from_device(p.value, (b.value,), np.uint8) == 0xA5).all())
 
     def __call__(self, files, stride: int = 0):
         """[bytes] -> ([status], pictures [n][h][stride or w] u8) (host convenience: enqueue, download).  The output block is 0xA5 before the call and has a guard

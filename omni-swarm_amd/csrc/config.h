@@ -24,7 +24,7 @@ enum CfgId {
     // host loop (libomni_host.so reads them through omni_config_value)
     CFG_GEOMETRY_THREADS, CFG_MESSAGE_THREADS, CFG_GEOMETRY_ASYNC, CFG_DETECTOR_ASYNC, CFG_PIPELINE_ONE_STREAM, CFG_PIPELINE_FIFO, CFG_PIPELINE_UNIT_PLAN,
     // JPEG decode
-    CFG_JPEGDEC_SUBSEQ_BITS, CFG_JPEGDEC_RESTART_WGS, CFG_JPEGDEC_PLAIN_WGS,
+    CFG_JPEGDEC_SUBSEQ_BITS, CFG_JPEGDEC_RESTART_WGS, CFG_JPEGDEC_PLAIN_WGS, CFG_JPEGDEC_UNSTUFF_DEV,
     // runtime
     CFG_HW_QUEUES,
     // strings

@@ -84,6 +84,9 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
                                                      "chunks of consecutive subsequences that relax on their own, a seam relaxation over the whole picture behind them, and a write "
                                                      "pass of one subsequence per lane (csrc/jpeg_dec_plan.h, plain); the subsequence length is doubled only until W chunks of 4096 "
                                                      "hold the picture.  Same pixels for every value"},
+    {"OMNI_JPEGDEC_UNSTUFF_DEV", 0, 0, 1, CFG_TUNING, "omni_jpegdec: 0 = the calling thread removes the 0xFF00 stuffing and the restart markers byte by byte and uploads the clean scans; "
+                                                      "1 = it only surveys the 0xFF bytes (csrc/jpeg_dec_plan.h survey), uploads the scans as they are, and one kernel in front of "
+                                                      "the others compacts them by tiles of 4096 bytes.  Same pixels, same statistics"},
     // ---- runtime ---------------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_HW_QUEUES", 8, 0, 64, CFG_TUNING, "hardware queues asked of the HIP runtime when the library is loaded (GPU_MAX_HW_QUEUES, unless already set): the pipeline's five "
                                             "streams must not share one; 0 = the runtime's default of 4"},

@@ -27,7 +27,12 @@
 //   dc       one workgroup per image: the status, then the scan of the DC differences in scan order -- segmented at every restart interval's first block;
 //   block    across all images, one 8 x 8 block per lane: dequantise, islow IDCT, clamp, store cropped.  A CORRUPT image is written as zeros; the pixels of a
 //            file the host decoded are copied from the uploaded block.
+//   unstuff  (OMNI_JPEGDEC_UNSTUFF_DEV = 1, snapshotted by the handle; 0: not launched, nothing allocated) in front of all of them: the scans were uploaded as they
+//            stand in the files, and one workgroup per tile of 4096 raw bytes removes the 0xFF00 stuffing and the restart markers (jpeg_dec_plan.h, unstuff_keep)
+//            from the clean offset the host's survey found for that tile.  NO WORKGROUP WAITS FOR ANOTHER, none reads what another wrote.
 // The host side parses, unstuffs the scans into the handle's pinned block (a planned restart file: + its interval and chunk tables behind its scan) and uploads it once.
+// With OMNI_JPEGDEC_UNSTUFF_DEV = 1 it unstuffs nothing: it surveys the scans' 0xFF bytes (memchr) for the lengths, the restart offsets and the tiles' clean
+// offsets, copies the raw scans into the block (descriptors | jobs + tile tables | restart tables | host-decoded pixels | raw scans) and uploads that.
 // Everything runs on the caller's stream.
 #include "common.h"
 #include "config.h"
@@ -61,6 +66,13 @@ struct omni_jpegdec {
     int last_spread_chunks = 0;            // ... of a picture that takes the spread path (the chunk kernel's grid; 0: none does, nothing more is launched)
     uint32_t last_spread_sub = 0;          // ... and the most subsequences of one (the write kernel's grid)
     bool last_unspread = true;             // a picture of the last pack is decoded by the entropy kernel
+    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: the uploaded block is descriptors | unstuff jobs + tile tables | interval and chunk tables | host-decoded pixels | RAW scans,
+    // the clean scans (Desc::dev_off) lie behind it and are written by jpegdec_unstuff_kernel, OMNI_JPEGDEC_GUARD_BYTES of 0xA5 behind the last of them
+    int unstuff_dev = 0;
+    size_t jobs_off = 0;                   // of the last pack: where its jobs stand in the block,
+    int last_jobs = 0;                     // ... their number (the pictures whose scan the device unstuffs), the most tiles of one,
+    int64_t last_job_tiles = 0, last_raw = 0, last_clean = 0;      // ... and the raw bytes uploaded for them / the clean bytes they become
+    size_t last_clean_end = 0;             // the end of the last clean area: the guard's place
     std::mutex mu;
 };
 
@@ -424,8 +436,84 @@ __global__ __launch_bounds__(JD_BLOCK_THREADS) void jpegdec_block_kernel(const u
         }
 }
 
+// ---- unstuffing on the device (OMNI_JPEGDEC_UNSTUFF_DEV = 1; jpeg_dec_plan.h, unstuff_keep / survey) ------------------------------------------------------------
+// grid (most tiles of a scan, scans with a job); one workgroup compacts ONE tile of JD_UNSTUFF_TILE raw bytes, 16 per lane from one aligned 128-bit load: keep
+// masks from unstuff_keep (the neighbour across a lane's edge from the adjacent lane, across a wave's or the tile's edge from global memory), popcounts, an
+// exclusive scan over the workgroup, the kept bytes into LDS at the position their dwords have in global memory, then whole dwords where all four bytes are
+// this tile's and single bytes for the ragged first and last dword -- the neighbouring tile's workgroup writes the other bytes of those.  The tile's clean
+// offset is the host's (survey): no scan across workgroups, no atomics, no flags, NO WORKGROUP WAITS FOR ANOTHER, every loop has a constant trip count.  The
+// workgroup of a scan's last tile also writes the JD_SCAN_PAD zero bytes (the clean area holds the last call's bytes).  Every store is checked against the
+// scan's clean bytes, and a job that does not lie inside the block is not run at all.  `block` is read (jobs, tables, raw scans) and written (clean areas): no
+// __restrict__, no const
+#define JD_UNSTUFF_ROUNDS ((JD_UNSTUFF_TILE / 4 + 2 + JD_THREADS - 1) / JD_THREADS)
+static_assert(JD_UNSTUFF_TILE == 16 * JD_THREADS, "16 raw bytes per lane");
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_unstuff_kernel(uint8_t* block, int64_t jobs_off, int64_t block_bytes) {
+    __shared__ uint32_t lds[JD_THREADS / 64 + 1];
+    __shared__ uint32_t stage[JD_UNSTUFF_TILE / 4 + 2];                                     // up to 3 bytes of the dword the tile's first clean byte lies in + the tile
+    const jd::UnstuffJob J = reinterpret_cast<const jd::UnstuffJob*>(block + jobs_off)[blockIdx.y];
+    const int64_t raw_end = J.raw_bytes, tile = blockIdx.x;
+    if (raw_end < 0 || raw_end > block_bytes || J.clean_bytes < 0 || J.clean_bytes > raw_end) return;       // (uniform, as every return below)
+    const int64_t n_tiles = ((raw_end > 1 ? raw_end : 1) + JD_UNSTUFF_TILE - 1) / JD_UNSTUFF_TILE, raw_room = (raw_end + 15) & ~(int64_t)15;
+    if (tile >= n_tiles) return;
+    if (J.raw_off < 0 || (J.raw_off & 15) || J.raw_off > block_bytes - raw_room || J.clean_off < 0 || (J.clean_off & 3) ||
+        J.clean_off > block_bytes - J.clean_bytes - JD_SCAN_PAD || J.tile_off < 0 || (J.tile_off & 3) || J.tile_off > block_bytes - n_tiles * 4)
+        return;                                                                             // (the host builds no such job)
+    const uint8_t* raw = block + J.raw_off;
+    uint8_t* clean = block + J.clean_off;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t base = tile * JD_UNSTUFF_TILE + tid * 16;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (base < raw_end) {                                                                   // (16 bytes inside the zero-padded scan)
+        const uint4 v = *reinterpret_cast<const uint4*>(raw + base);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+    uint32_t prev = __shfl_up(w[3] >> 24, 1, 64), next = __shfl_down(w[0] & 255u, 1, 64);
+    if (lane == 0) prev = base > 0 && base - 1 < raw_end ? raw[base - 1] : (uint32_t)JD_UNSTUFF_OUTSIDE;
+    if (lane == 63) next = base + 16 < raw_end ? raw[base + 16] : (uint32_t)JD_UNSTUFF_OUTSIDE;
+    uint32_t keep = 0;
+    JP_UNROLL
+    for (int b = 0; b < 16; ++b) {
+        const uint32_t cur = w[b >> 2] >> (8 * (b & 3)) & 255u;
+        const uint32_t p = b ? w[(b - 1) >> 2] >> (8 * ((b - 1) & 3)) & 255u : prev;
+        const uint32_t nx = b < 15 ? w[(b + 1) >> 2] >> (8 * ((b + 1) & 3)) & 255u : next;
+        const int64_t x = base + b;
+        if (x < raw_end && jd::unstuff_keep((uint8_t)p, (uint8_t)cur, x + 1 < raw_end ? (uint8_t)nx : (uint8_t)JD_UNSTUFF_OUTSIDE)) keep |= 1u << b;
+    }
+    uint32_t total;
+    const uint32_t excl = jd_wg_scan<JD_THREADS>((uint32_t)__popc(keep), lds, &total);
+    const int64_t o0 = (int64_t)reinterpret_cast<const uint32_t*>(block + J.tile_off)[tile];
+    const uint32_t a = (uint32_t)(o0 & 3), e = a + total;                                  // the tile's clean bytes are the staged bytes [a, e), e <= 3 + JD_UNSTUFF_TILE
+    uint8_t* sb = reinterpret_cast<uint8_t*>(stage);
+    uint32_t pos = a + excl;
+    JP_UNROLL
+    for (int b = 0; b < 16; ++b)
+        if (keep >> b & 1u) sb[pos++] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+    __syncthreads();
+    const int64_t g0 = o0 - a;                                                              // the clean offset of staged byte 0: a multiple of 4
+    JP_UNROLL
+    for (int r = 0; r < JD_UNSTUFF_ROUNDS; ++r) {
+        const uint32_t j = (uint32_t)(r * JD_THREADS + tid), lo = 4u * j, hi = lo + 4u;
+        if (lo >= e) continue;
+        if (lo >= a && hi <= e && g0 + hi <= J.clean_bytes) {
+            *reinterpret_cast<uint32_t*>(clean + g0 + lo) = stage[j];
+        } else {
+            for (uint32_t k = lo > a ? lo : a; k < (hi < e ? hi : e); ++k)
+                if (g0 + k < J.clean_bytes) clean[g0 + k] = sb[k];
+        }
+    }
+    if (tile == n_tiles - 1 && tid < JD_SCAN_PAD) clean[J.clean_bytes + tid] = 0;
+}
+
 // The stage on `stream`; the caller holds d->mu, has checked the arguments, and d_in holds the block of n_images images
 static int jpegdec_launch(omni_jpegdec* d, hipStream_t stream, int n_images, uint8_t* out_dev, int out_stride, int* status_dev) {
+    if (d->unstuff_dev) {                                                                   // the raw scans -> the clean areas behind the uploaded range, and the guard behind those
+        OMNI_HIP_TRY(hipMemsetAsync(d->d_in + d->last_clean_end, 0xA5, OMNI_JPEGDEC_GUARD_BYTES, stream));
+        if (d->last_jobs) {
+            hipLaunchKernelGGL(jpegdec_unstuff_kernel, dim3((unsigned)d->last_job_tiles, (unsigned)d->last_jobs), dim3(JD_THREADS), 0, stream, d->d_in, (int64_t)d->jobs_off,
+                               (int64_t)d->last_clean_end);
+            OMNI_LAUNCH_CHECK();
+        }
+    }
     OMNI_HIP_TRY(hipMemsetAsync(d->d_coef, 0, (size_t)n_images * d->nyb_max * 64 * sizeof(int16_t), stream));
     OMNI_HIP_TRY(hipMemsetAsync(d->d_dc, 0, (size_t)n_images * d->nyb_max * sizeof(int32_t), stream));
     OMNI_HIP_TRY(hipMemsetAsync(d->d_flags, 0, (size_t)d->flag_words * d->max_images * sizeof(int), stream));
@@ -458,6 +546,9 @@ static int jpegdec_launch(omni_jpegdec* d, hipStream_t stream, int n_images, uin
 
 // Parses the files and fills the handle's pinned block: descriptors | clean scans | host-decoded pixels.  *bytes = what has to be uploaded.  Nothing is touched
 // when a file is refused.
+// OMNI_JPEGDEC_UNSTUFF_DEV = 1: wherever the loop below would unstuff a scan into the block it surveys it instead (jd::survey: the 0xFF bytes alone) and notes a
+// job; the block is laid out behind the loop -- descriptors | jobs + tile tables | interval and chunk tables | host-decoded pixels | raw scans (memcpy) -- and
+// the clean areas the descriptors point to follow the uploaded range.  The classification, the plans and every statistic are what they are with the switch off
 static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int64_t* sizes, int n_images, size_t* bytes) {
     std::vector<jd::Desc> descs((size_t)n_images);
     for (int i = 0; i < n_images; ++i) {
@@ -477,6 +568,30 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
     bool unspread = d->plain_wgs < 2;                                                       // (switch off: the entropy kernel is launched whatever the batch holds)
     jd::ChunkPlan plan;
     std::vector<int64_t> rst;
+    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: what the loop notes instead of writing into the block
+    const bool dev = d->unstuff_dev != 0;
+    struct Pending { int img; int64_t raw_end, n_clean; size_t first_tile, n_tiles; };
+    std::vector<Pending> jobs;
+    std::vector<uint32_t> tiles;                                                            // the jobs' tile tables, one behind the other
+    std::vector<uint8_t> tabs;                                                              // the planned restart files' tables, each 16-aligned (Desc::tab_off: inside it)
+    std::vector<int> host_pictures;
+    // the clean bytes of picture i's scan: unstuffed into the block at `at` -- or surveyed, its tile table appended to `tiles`
+    auto clean_scan = [&](int i, int64_t* rst_out, int64_t max_rst, int64_t* n_rst, Pending* job) -> int64_t {
+        const jd::Desc& D = descs[(size_t)i];
+        if (!dev) return jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, rst_out, max_rst, n_rst);
+        const size_t first = tiles.size(), room = (size_t)(D.scan_bytes / JD_UNSTUFF_TILE + 1);
+        tiles.resize(first + room);
+        const jd::Survey v = jd::survey(files[i] + D.scan_off, D.scan_bytes, tiles.data() + first, (int64_t)room, rst_out, max_rst);
+        if (n_rst) *n_rst = v.n_rst;
+        *job = Pending{i, v.raw_end, v.n_clean, first, (size_t)v.n_tiles};
+        return v.n_clean;
+    };
+    // ... and the scan is the kernels' to decode: the table stays (a scan that is not: dropped)
+    auto keep_job = [&](const Pending& job, bool keep) {
+        if (!dev) return;
+        tiles.resize(job.first_tile + (keep ? job.n_tiles : 0));
+        if (keep) jobs.push_back(job);
+    };
     for (int i = 0; i < n_images; ++i) {
         jd::Desc& D = descs[(size_t)i];
         D.dev_off = (int64_t)at;
@@ -488,13 +603,23 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
             // CORRUPT; a plan that cannot be made, or tables above the handle's room for them: the file stays HOST (below)
             rst.resize((size_t)(D.scan_bytes / 2 + 1));
             int64_t n_rst = 0;
-            const int64_t n = jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, rst.data(), (int64_t)rst.size(), &n_rst);
+            Pending job{};
+            const int64_t n = clean_scan(i, rst.data(), (int64_t)rst.size(), &n_rst, &job);
             jd::plan_chunks(D, n, rst.data(), n_rst, (uint32_t)d->subseq_bits, (uint32_t)d->restart_wgs, JD_MAX_SUBSEQ, &plan);
+            const bool planned = plan.status == OMNI_JPEGDEC_OK && plan.table_bytes() <= d->tab_bytes;
+            keep_job(job, planned);
             if (plan.status == OMNI_JPEGDEC_CORRUPT) {
                 D.status = OMNI_JPEGDEC_CORRUPT;
-            } else if (plan.status == OMNI_JPEGDEC_OK && plan.table_bytes() <= d->tab_bytes) {
+            } else if (planned) {
                 const size_t scan_bytes = align16((size_t)n + JD_SCAN_PAD);
-                plan.store(base + at + scan_bytes);
+                if (dev) {                                                                  // (both offsets are moved to their place behind the loop)
+                    D.tab_off = (int64_t)tabs.size();
+                    tabs.resize(tabs.size() + align16(plan.table_bytes()));
+                    plan.store(tabs.data() + D.tab_off);
+                } else {
+                    plan.store(base + at + scan_bytes);
+                    D.tab_off = (int64_t)(at + scan_bytes);
+                }
                 D.status = OMNI_JPEGDEC_OK;
                 D.mode = jd::JD_MODE_DECODE;
                 D.total_bits = (uint32_t)(n * 8);
@@ -502,15 +627,16 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
                 D.n_sub = plan.n_sub;
                 D.n_int = plan.n_int;
                 D.n_chunks = plan.n_chunks;
-                D.tab_off = (int64_t)(at + scan_bytes);
                 if ((int)plan.n_chunks > max_chunks) max_chunks = (int)plan.n_chunks;
                 unspread = true;
-                at += scan_bytes + align16(plan.table_bytes());
+                if (!dev) at += scan_bytes + align16(plan.table_bytes());
                 continue;
             }
         }
         if (D.status == OMNI_JPEGDEC_OK) {
-            const int64_t n = jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, nullptr, 0, nullptr);
+            Pending job{};
+            const int64_t n = clean_scan(i, nullptr, 0, nullptr, &job);
+            keep_job(job, true);
             D.mode = jd::JD_MODE_DECODE;
             D.total_bits = (uint32_t)(n * 8);
             D.subseq_bits = d->plain_wgs >= 2 ? jd::plain_subseq_bits(D.total_bits, (uint32_t)d->subseq_bits, (uint32_t)d->plain_wgs, JD_MAX_SUBSEQ)
@@ -525,7 +651,9 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
             } else {
                 unspread = true;
             }
-            at += align16((size_t)n + JD_SCAN_PAD);
+            if (!dev) at += align16((size_t)n + JD_SCAN_PAD);
+        } else if (D.status == OMNI_JPEGDEC_HOST && dev) {
+            host_pictures.push_back(i);                                                     // (decoded behind the loop, where its pixels' place is known)
         } else if (D.status == OMNI_JPEGDEC_HOST) {
             const int st = jd::decode_sequential(files[i], D, base + at, d->w);
             D.status = st;
@@ -534,6 +662,46 @@ static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int6
         } else {
             D.mode = jd::JD_MODE_ZERO;
         }
+    }
+    if (dev) {
+        // the layout: everything but the pixels and the scans themselves has its size by now, and the handle was made for the largest of each
+        const size_t jobs_off = at, tiles_off = jobs_off + align16(jobs.size() * sizeof(jd::UnstuffJob)), tabs_off = tiles_off + align16(tiles.size() * sizeof(uint32_t));
+        size_t need = tabs_off + tabs.size() + host_pictures.size() * align16((size_t)d->w * d->h);
+        for (const Pending& j : jobs) need += align16((size_t)j.raw_end) + align16((size_t)j.n_clean + JD_SCAN_PAD);
+        OMNI_REQUIRE(need <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: a block of %zu bytes, the handle holds %zu", need, d->in_bytes);
+        at = tabs_off + tabs.size();
+        if (!tiles.empty()) memcpy(base + tiles_off, tiles.data(), tiles.size() * sizeof(uint32_t));
+        if (!tabs.empty()) memcpy(base + tabs_off, tabs.data(), tabs.size());
+        for (int i : host_pictures) {
+            jd::Desc& D = descs[(size_t)i];
+            D.dev_off = (int64_t)at;
+            const int st = jd::decode_sequential(files[i], D, base + at, d->w);
+            D.status = st;
+            D.mode = st == OMNI_JPEGDEC_CORRUPT ? jd::JD_MODE_ZERO : jd::JD_MODE_PIXELS;
+            if (D.mode == jd::JD_MODE_PIXELS) at += align16((size_t)d->w * d->h);
+        }
+        jd::UnstuffJob* J = reinterpret_cast<jd::UnstuffJob*>(base + jobs_off);
+        int64_t most_tiles = 0, raw_total = 0, clean_total = 0;
+        for (size_t k = 0; k < jobs.size(); ++k) {                                          // the scans as they stand in the files, zero-padded to a multiple of 16
+            const Pending& j = jobs[k];
+            const size_t room = align16((size_t)j.raw_end);
+            if (j.raw_end) memcpy(base + at, files[j.img] + descs[(size_t)j.img].scan_off, (size_t)j.raw_end);
+            memset(base + at + j.raw_end, 0, room - (size_t)j.raw_end);
+            J[k].raw_off = (int64_t)at; J[k].raw_bytes = j.raw_end; J[k].clean_bytes = j.n_clean;
+            J[k].tile_off = (int64_t)(tiles_off + j.first_tile * sizeof(uint32_t));
+            at += room;
+            if ((int64_t)j.n_tiles > most_tiles) most_tiles = (int64_t)j.n_tiles;
+            raw_total += j.raw_end; clean_total += j.n_clean;
+        }
+        size_t clean_at = at;                                                               // behind the uploaded range: the clean areas, the kernel's to write
+        for (size_t k = 0; k < jobs.size(); ++k) {
+            jd::Desc& D = descs[(size_t)jobs[k].img];
+            J[k].clean_off = D.dev_off = (int64_t)clean_at;
+            if (D.n_int) D.tab_off += (int64_t)tabs_off;
+            clean_at += align16((size_t)jobs[k].n_clean + JD_SCAN_PAD);
+        }
+        d->jobs_off = jobs_off; d->last_jobs = (int)jobs.size(); d->last_job_tiles = most_tiles; d->last_raw = raw_total; d->last_clean = clean_total;
+        d->last_clean_end = clean_at;
     }
     OMNI_REQUIRE(at <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: %zu bytes to upload, the handle holds %zu", at, d->in_bytes);
     memcpy(base, descs.data(), (size_t)n_images * sizeof(jd::Desc));
@@ -575,19 +743,28 @@ extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int heigh
         d->tab_bytes = align16(((mcus < planned ? mcus : planned) + 1) * sizeof(jd::Interval) + ((size_t)W + 1) * sizeof(uint32_t));
     }
     d->in_bytes = align16((size_t)max_images * sizeof(jd::Desc)) + (size_t)max_images * ((per_scan > per_px ? per_scan : per_px) + d->tab_bytes);
+    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: + per image its raw scan next to its clean one, a job and a tile table; the guard stands behind the last clean area in use
+    d->unstuff_dev = cfg[CFG_JPEGDEC_UNSTUFF_DEV];
+    if (d->unstuff_dev) {
+        const size_t tile_tab = ((size_t)capacity_per_image / JD_UNSTUFF_TILE + 2) * sizeof(uint32_t);
+        d->in_bytes += (size_t)max_images * (align16((size_t)capacity_per_image) + 16) + align16((size_t)max_images * sizeof(jd::UnstuffJob)) + align16((size_t)max_images * tile_tab);
+        d->last_clean_end = d->in_bytes;
+    }
+    const size_t in_guard = d->unstuff_dev ? OMNI_JPEGDEC_GUARD_BYTES : 0;
     const size_t coef_bytes = (size_t)max_images * nyb * 64 * sizeof(int16_t), dc_bytes = (size_t)max_images * nyb * sizeof(int32_t);
     // OMNI_JPEGDEC_PLAIN_WGS >= 2: the state arrays of the spread path (8 bytes per subsequence) and two more flag words per picture; otherwise neither
     if (PW >= 2) { d->state_cap = (uint32_t)PW * JD_MAX_SUBSEQ; d->flag_words = 5; }
     const size_t state_bytes = (size_t)max_images * d->state_cap * 8;
     auto make = [&]() -> int {
         int rc;
-        if ((rc = d->mem.alloc(&d->d_in, d->in_bytes)) || (rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
+        if ((rc = d->mem.alloc(&d->d_in, d->in_bytes + in_guard)) ||(rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
             (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_flags, (size_t)d->flag_words * max_images * sizeof(int))))
             return rc;
         if (state_bytes) {
             if ((rc = d->mem.alloc(&d->d_state, state_bytes + OMNI_JPEGDEC_GUARD_BYTES))) return rc;
             OMNI_HIP_TRY(hipMemset(d->d_state + state_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         }
+        if (in_guard) OMNI_HIP_TRY(hipMemset(d->d_in + d->in_bytes, 0xA5, in_guard));
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_coef) + coef_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_dc) + dc_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         OMNI_HIP_TRY(hipMemset(d->d_flags, 0, (size_t)d->flag_words * max_images * sizeof(int)));
@@ -706,6 +883,68 @@ extern "C" int omni_jpegdec_last_seam(omni_jpegdec* d, int* seam_rounds, int* se
 extern "C" int omni_jpegdec_debug_state_buffer(omni_jpegdec* d, void** state_dev, int64_t* state_bytes) {
     OMNI_REQUIRE(d && state_dev && state_bytes, OMNI_ERR_INVALID, "null argument");
     *state_dev = d->d_state; *state_bytes = (int64_t)d->max_images * d->state_cap * 8;
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_last_unstuff(omni_jpegdec* d, int* device_pictures, int64_t* raw_bytes, int64_t* clean_bytes) {
+    OMNI_REQUIRE(d && device_pictures && raw_bytes && clean_bytes, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(d->mu);
+    *device_pictures = d->unstuff_dev ? d->last_jobs : 0;
+    *raw_bytes = d->unstuff_dev ? d->last_raw : 0;
+    *clean_bytes = d->unstuff_dev ? d->last_clean : 0;
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpegdec_debug_in_buffer(omni_jpegdec* d, void** clean_end_dev, int64_t* guard_bytes) {
+    OMNI_REQUIRE(d && clean_end_dev && guard_bytes, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(d->mu);
+    *clean_end_dev = d->unstuff_dev ? d->d_in + d->last_clean_end : nullptr;
+    *guard_bytes = d->unstuff_dev ? OMNI_JPEGDEC_GUARD_BYTES : 0;
+    return OMNI_OK;
+}
+
+// survey, upload, jpegdec_unstuff_kernel alone, download: a block of its own -- job | tile table | raw scan | clean area | guard -- filled with 0xA5 beforehand
+extern "C" int omni_jpegdec_unstuff_dev(omni_ctx* ctx, const uint8_t* scan, int64_t n, uint8_t* out_host, int64_t out_cap, int64_t* n_clean) {
+    using namespace omni;
+    OMNI_REQUIRE(ctx && scan && out_host && n_clean, OMNI_ERR_INVALID, "null argument");
+    OMNI_REQUIRE(n >= 0 && n <= (1 << 28), OMNI_ERR_INVALID, "omni_jpegdec_unstuff_dev: a scan of %lld bytes outside [0, 2^28]", (long long)n);
+    std::vector<uint32_t> tiles((size_t)(n / JD_UNSTUFF_TILE + 1));
+    const jd::Survey v = jd::survey(scan, n, tiles.data(), (int64_t)tiles.size(), nullptr, 0);
+    OMNI_REQUIRE(out_cap >= v.n_clean + JD_SCAN_PAD, OMNI_ERR_INVALID, "omni_jpegdec_unstuff_dev: room for %lld bytes, %lld clean bytes + %d", (long long)out_cap,
+                 (long long)v.n_clean, JD_SCAN_PAD);
+    const size_t tiles_off = align16(sizeof(jd::UnstuffJob)), raw_off = tiles_off + align16((size_t)v.n_tiles * sizeof(uint32_t)), clean_off = raw_off + align16((size_t)v.raw_end);
+    const size_t clean_end = clean_off + align16((size_t)v.n_clean + JD_SCAN_PAD);
+    std::vector<uint8_t> host(clean_off, 0);
+    const jd::UnstuffJob job{(int64_t)raw_off, v.raw_end, (int64_t)clean_off, v.n_clean, (int64_t)tiles_off};
+    memcpy(host.data(), &job, sizeof(job));
+    memcpy(host.data() + tiles_off, tiles.data(), (size_t)v.n_tiles * sizeof(uint32_t));
+    if (v.raw_end) memcpy(host.data() + raw_off, scan, (size_t)v.raw_end);
+    std::vector<uint8_t> back(clean_end - clean_off + OMNI_JPEGDEC_GUARD_BYTES);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    DevMem mem;
+    uint8_t* block = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = mem.alloc(&block, clean_end + OMNI_JPEGDEC_GUARD_BYTES))) return rc;
+        OMNI_HIP_TRY(hipMemsetAsync(block, 0xA5, clean_end + OMNI_JPEGDEC_GUARD_BYTES, ctx->stream));
+        OMNI_HIP_TRY(hipMemcpyAsync(block, host.data(), clean_off, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(jpegdec_unstuff_kernel, dim3((unsigned)v.n_tiles, 1), dim3(JD_THREADS), 0, ctx->stream, block, (int64_t)0, (int64_t)clean_end);
+        OMNI_LAUNCH_CHECK();
+        OMNI_HIP_TRY(hipMemcpyAsync(back.data(), block + clean_off, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+        OMNI_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return OMNI_OK;
+    };
+    const int rc = run();
+    if (block) (void)hipStreamSynchronize(ctx->stream);
+    mem.release_all();
+    if (rc) return rc;
+    for (size_t i = clean_end - clean_off; i < back.size(); ++i)
+        OMNI_REQUIRE(back[i] == 0xA5, OMNI_ERR_HIP, "omni_jpegdec_unstuff_dev: the kernel wrote behind the clean area (guard byte %zu)", i - (clean_end - clean_off));
+    for (size_t i = (size_t)v.n_clean + JD_SCAN_PAD; i < clean_end - clean_off; ++i)
+        OMNI_REQUIRE(back[i] == 0xA5, OMNI_ERR_HIP, "omni_jpegdec_unstuff_dev: the kernel wrote behind the padding (byte %zu)", i);
+    memcpy(out_host, back.data(), (size_t)v.n_clean + JD_SCAN_PAD);
+    *n_clean = v.n_clean;
     return OMNI_OK;
 }
 

@@ -90,3 +90,41 @@ extern "C" int omni_jpeg_decode_plain_parallel_host(const uint8_t* file, int64_t
     }
     return OMNI_OK;
 }
+
+// ---- unstuffing by tiles (OMNI_JPEGDEC_UNSTUFF_DEV): the byte-wise pass, and survey + the tile-by-tile stand-in for jpegdec_unstuff_kernel ----------------------
+extern "C" int omni_jpeg_unstuff_tile_bytes(void) { return JD_UNSTUFF_TILE; }
+
+extern "C" int64_t omni_jpeg_scan_end(const uint8_t* file, int64_t size, int64_t from) {
+    if (!file || size < 0 || from < 0 || from > size) return -1;
+    return omni::jd::scan_end(file, size, from);
+}
+
+static int unstuff_args(const char* who, const uint8_t* scan, int64_t n, const uint8_t* out, int64_t out_cap, const int64_t* n_clean, const int64_t* rst, int64_t max_rst,
+                        const int64_t* n_rst) {
+    if (!scan || !out || !n_clean || !n_rst || n < 0 || max_rst < 0 || (max_rst && !rst)) { omni::set_error("%s: null argument", who); return OMNI_ERR_INVALID; }
+    if (out_cap < n + JD_SCAN_PAD) { omni::set_error("%s: room for %lld bytes, a scan of %lld needs %lld", who, (long long)out_cap, (long long)n, (long long)(n + JD_SCAN_PAD)); return OMNI_ERR_INVALID; }
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpeg_unstuff_host(const uint8_t* scan, int64_t n, uint8_t* out, int64_t out_cap, int64_t* n_clean, int64_t* rst, int64_t max_rst, int64_t* n_rst) {
+    const int rc = unstuff_args("omni_jpeg_unstuff_host", scan, n, out, out_cap, n_clean, rst, max_rst, n_rst);
+    if (rc) return rc;
+    *n_clean = omni::jd::unstuff(scan, n, out, max_rst ? rst : nullptr, max_rst, n_rst);
+    return OMNI_OK;
+}
+
+extern "C" int omni_jpeg_unstuff_tiled_host(const uint8_t* scan, int64_t n, uint8_t* out, int64_t out_cap, int64_t* n_clean, int64_t* rst, int64_t max_rst, int64_t* n_rst,
+                                            int64_t* raw_end, int64_t* surveyed_clean, uint32_t* tile_off, int64_t max_tiles, int64_t* n_tiles) {
+    const int rc = unstuff_args("omni_jpeg_unstuff_tiled_host", scan, n, out, out_cap, n_clean, rst, max_rst, n_rst);
+    if (rc) return rc;
+    if (!raw_end || !surveyed_clean || !tile_off || !n_tiles || max_tiles < n / JD_UNSTUFF_TILE + 1) {
+        omni::set_error("omni_jpeg_unstuff_tiled_host: a tile table of %lld entries, a scan of %lld bytes needs %lld", (long long)max_tiles, (long long)n,
+                        (long long)(n / JD_UNSTUFF_TILE + 1));
+        return OMNI_ERR_INVALID;
+    }
+    const omni::jd::Survey v = omni::jd::survey(scan, n, tile_off, max_tiles, max_rst ? rst : nullptr, max_rst);
+    memset(out, 0xA5, (size_t)out_cap);                                                     // (the tiles and the padding are all that is written)
+    *n_clean = omni::jd::unstuff_tiled_host(scan, v, tile_off, out);
+    *n_rst = v.n_rst; *raw_end = v.raw_end; *surveyed_clean = v.n_clean; *n_tiles = v.n_tiles;
+    return OMNI_OK;
+}

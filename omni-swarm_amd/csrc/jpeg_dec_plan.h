@@ -16,7 +16,10 @@
 //                             component sampled below another one
 //                CORRUPT      anything else that cannot be a file
 //   bytes      0xFF00 unstuffing and the end at a marker happen in a FIRST PASS on the host (unstuff): the scan the decoders and the kernels read is the
-//              clean bit stream, MSB first, followed by >= JD_SCAN_PAD zero bytes.  Restart markers become a list of byte offsets (the host decoder and the chunk plan)
+//              clean bit stream, MSB first, followed by >= JD_SCAN_PAD zero bytes.  Restart markers become a list of byte offsets (the host decoder and the chunk plan).
+//              A handle whose OMNI_JPEGDEC_UNSTUFF_DEV is 1 splits that pass: survey() visits the 0xFF bytes alone (memchr) for the scan's end, the clean length,
+//              the markers' offsets and the clean offset of every tile of JD_UNSTUFF_TILE raw bytes; the raw scan is uploaded as it is and every tile is compacted
+//              on its own with unstuff_keep() -- the same clean bytes (unstuff_tiled_host is the stand-in for jpegdec_unstuff_kernel)
 //   symbol     step(): ONE total function (bit position, z = next zig-zag index 0..63, b = block within the MCU) -> next state, at most one (block, natural
 //              index, value) emission, an error flag.  z == 0: a DC category + value bits; else an AC (run, size): ZRL (z += 16; reaching 64 ends the block, as
 //              libjpeg's loop does), EOB, value extension as in jpeg_plan.h.  Defined for EVERY bit pattern: an undefined code is 1 bit long and reads as symbol
@@ -61,6 +64,8 @@
 #include "jpeg_plan.h"
 
 #define JD_SCAN_PAD 16                                       // zero bytes behind a clean scan: the bit window reads up to 12 bytes past the last symbol
+#define JD_UNSTUFF_TILE 4096                                 // raw scan bytes per tile of the unstuffing by tiles (csrc/jpeg_dec.hip: 16 per lane)
+#define JD_UNSTUFF_OUTSIDE 0x01                              // stands for a neighbour outside the scan: neither 0x00 nor 0xFF
 #define JD_MAX_BPM 10                                        // blocks per MCU (the standard's limit)
 #define JD_MIN_SUBSEQ_BITS 128
 #define JD_MAX_SUBSEQ_BITS 65536
@@ -131,9 +136,12 @@ inline int build_hufftab(const uint8_t* bits, const uint8_t* vals, bool dc, Huff
 }
 
 // the end of the entropy-coded data that starts at p: the first marker that is neither a stuffed 0xFF00 nor a restart marker (or the end of the file)
+// (memchr finds the 0xFF bytes; only they and the byte behind each run are looked at one by one)
 inline int64_t scan_end(const uint8_t* f, int64_t size, int64_t p) {
     while (p < size) {
-        if (f[p] != 0xff) { ++p; continue; }
+        const uint8_t* ff = static_cast<const uint8_t*>(memchr(f + p, 0xff, (size_t)(size - p)));
+        if (!ff) return size;
+        p = ff - f;
         int64_t q = p + 1;
         while (q < size && f[q] == 0xff) ++q;
         if (q >= size) return size;
@@ -285,6 +293,84 @@ inline int64_t unstuff(const uint8_t* s, int64_t n, uint8_t* out, int64_t* rst, 
     memset(out + o, 0, JD_SCAN_PAD);
     if (n_rst) *n_rst = r;
     return o;
+}
+
+// ---- the same bytes by tiles: what a handle whose OMNI_JPEGDEC_UNSTUFF_DEV is 1 leaves to the device -------------------------------------------------------------
+// unstuff() is a stream compaction with a one-byte neighbourhood rule.  The host keeps the part that needs the whole scan -- where it ends, how many clean bytes it
+// has, where the restart markers stand, and how many clean bytes lie in front of every tile of JD_UNSTUFF_TILE raw bytes (survey: it visits the 0xFF bytes alone)
+// -- and every tile can then be compacted on its own (unstuff_tiled_host by plain loops, jpegdec_unstuff_kernel by one workgroup per tile).
+// Whether raw byte `cur` of [0, raw_end) is a clean byte, given its neighbours; one outside [0, raw_end) is passed as JD_UNSTUFF_OUTSIDE (neither 0x00 nor 0xFF):
+//   cur != 0xFF  kept unless it stands behind an 0xFF: that byte is the stuffed 00 or the RSTn of the run in front of it (the run's terminator lies beyond raw_end)
+//   cur == 0xFF  kept when a 00 follows: the last 0xFF of a run in front of a stuffed zero; fill bytes and marker prefixes are dropped
+JP_HD bool unstuff_keep(uint8_t prev, uint8_t cur, uint8_t next) { return cur != 0xff ? prev != 0xff : next == 0x00; }
+
+struct Survey {
+    int64_t raw_end = 0;                                    // where unstuff() stops: the start of the 0xFF run that ends in a marker other than RSTn (or runs off the
+                                                            // end of the scan); n when there is none
+    int64_t n_clean = 0, n_rst = 0;                         // unstuff()'s return value and its *n_rst
+    int64_t n_tiles = 1;                                    // tiles of [0, max(raw_end, 1)): an empty scan still has one
+};
+// The host pass over scan[0..n).  tile_off[t] (t < min(n_tiles, max_tiles)): the clean bytes in front of raw byte t * JD_UNSTUFF_TILE; rst as unstuff()'s
+inline Survey survey(const uint8_t* s, int64_t n, uint32_t* tile_off, int64_t max_tiles, int64_t* rst, int64_t max_rst) {
+    Survey v;
+    int64_t i = 0, o = 0, t = 1;                            // o: the clean bytes in front of raw byte i; t: the next tile to be filled, at raw byte t * TILE
+    if (max_tiles > 0) tile_off[0] = 0;
+    // the tiles that start in [from, to): `clean` clean bytes lie in front of `from`, and every byte of [from, to) adds `each` (1: data; 0: a run of 0xFF)
+    auto fill = [&](int64_t from, int64_t to, int64_t clean, int64_t each) {
+        for (; t * JD_UNSTUFF_TILE < to; ++t)
+            if (t < max_tiles) tile_off[t] = (uint32_t)(clean + (t * JD_UNSTUFF_TILE - from) * each);
+    };
+    v.raw_end = n;
+    while (i < n) {
+        const uint8_t* ff = static_cast<const uint8_t*>(memchr(s + i, 0xff, (size_t)(n - i)));
+        const int64_t j = ff ? ff - s : n;                  // [i, j): data
+        fill(i, j, o, 1);
+        o += j - i;
+        if (!ff) break;
+        int64_t k = j + 1;
+        while (k < n && s[k] == 0xff) ++k;                  // [j, k): the run; s[k]: what it announces
+        const bool zero = k < n && s[k] == 0, restart = k < n && s[k] >= 0xd0 && s[k] <= 0xd7;
+        if (!zero && !restart) { v.raw_end = j; break; }
+        fill(j, k + 1, o, 0);                               // (a tile that starts at k, behind a run's last 0xFF, is filled below)
+        if (zero) {
+            if (k % JD_UNSTUFF_TILE == 0 && k / JD_UNSTUFF_TILE < max_tiles) tile_off[k / JD_UNSTUFF_TILE] = (uint32_t)(o + 1);
+            ++o;
+        } else if (rst && v.n_rst < max_rst) {
+            rst[v.n_rst++] = o;
+        }
+        i = k + 1;
+    }
+    v.n_clean = o;
+    v.n_tiles = ((v.raw_end > 1 ? v.raw_end : 1) + JD_UNSTUFF_TILE - 1) / JD_UNSTUFF_TILE;
+    return v;
+}
+// what jpegdec_unstuff_kernel reads about one scan, in a table of its own (Desc stays what it was): byte offsets inside the handle's device block
+struct UnstuffJob {
+    int64_t raw_off, raw_bytes;                             // the scan as it stands in the file, [0, raw_end), 16-aligned and zero-padded to a multiple of 16
+    int64_t clean_off, clean_bytes;                         // where its clean bytes go (Desc::dev_off) and their number; JD_SCAN_PAD zero bytes follow
+    int64_t tile_off;                                       // uint32 [tiles]: survey()'s table
+};
+// one tile of the compaction, by plain loops: raw bytes [t * TILE, min((t + 1) * TILE, raw_end)) from clean offset `at`.  Returns the clean offset behind it
+inline int64_t unstuff_tile_host(const uint8_t* s, int64_t raw_end, int64_t t, int64_t at, uint8_t* out) {
+    const int64_t lo = t * JD_UNSTUFF_TILE, hi = lo + JD_UNSTUFF_TILE < raw_end ? lo + JD_UNSTUFF_TILE : raw_end;
+    for (int64_t x = lo; x < hi; ++x) {
+        const uint8_t prev = x > 0 ? s[x - 1] : JD_UNSTUFF_OUTSIDE, next = x + 1 < raw_end ? s[x + 1] : JD_UNSTUFF_OUTSIDE;
+        if (unstuff_keep(prev, s[x], next)) out[at++] = s[x];
+    }
+    return at;
+}
+// The CPU stand-in for jpegdec_unstuff_kernel: every tile on its own from tile_off[t]; the last one also writes the JD_SCAN_PAD zero bytes.  out need not be
+// zeroed (room for n_clean + JD_SCAN_PAD).  Returns the clean offset behind the last tile: unstuff()'s count when the table is survey()'s
+inline int64_t unstuff_tiled_host(const uint8_t* s, const Survey& v, const uint32_t* tile_off, uint8_t* out) {
+    int64_t end = 0;
+    for (int64_t t = v.n_tiles - 1; t >= 0; --t) {          // (no order among the tiles: backwards, so that none relies on the one in front of it)
+        const int64_t e = unstuff_tile_host(s, v.raw_end, t, (int64_t)tile_off[t], out);
+        if (t == v.n_tiles - 1) {
+            end = e;
+            memset(out + v.n_clean, 0, JD_SCAN_PAD);
+        }
+    }
+    return end;
 }
 
 // ---- the bit reader: a 64-bit window over the clean scan (host and device) -----------------------------------------------------------------------------
