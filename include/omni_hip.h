@@ -405,8 +405,8 @@ int          omni_resize_enqueue_dev(omni_resize* r, const uint8_t* src_dev, int
  * as one asynchronous unit: SuperPoint on the 2*n_dirs images (up cameras first, then down), MobileNetVLAD on the n_dirs
  * up images, BFMatcher(L2, crossCheck) up <-> down per direction, and the D2H copy of every result into one pinned block.
  * The handles are borrowed (sp created with max_batch >= 2*n_dirs on sp_ctx, vlad with max_batch >= n_dirs on vlad_ctx,
- * both contexts on the same device).  Camera lifting / triangulation (:73-106, 405-454, 558-576): inside the unit for a pinhole model set with
- * omni_cam_set_stereo_model (below); other camera models stay with the caller. */
+ * both contexts on the same device).  Camera lifting / triangulation (:73-106, 405-454, 558-576): inside the unit for the model set with
+ * omni_cam_set_stereo_model and the lens set with omni_cam_set_camera_model (below: camodocal's PINHOLE with distortion and MEI; the ideal pinhole unless set). */
 typedef struct omni_cam_result {      /* pointers into the handle's pinned host block; valid until its next enqueue */
     int n_dirs, max_num, desc_dim, global_dim;
     const float* kps_xy;      /* [2*n_dirs][max_num][2] */
@@ -480,13 +480,14 @@ int       omni_cam_ready(omni_cam* cam, int* ready);
 int       omni_cam_order_after(omni_cam* later, omni_cam* earlier, int streams);
 
 /* ---- stereo landmarks: the lifting and the up/down triangulation of generate_stereo_image_descriptor (loop_cam.cpp:397-444; triangulatePoint :73-106; the lifted
- * key points of extractor_img_desc_deepnet :558-566) for PINHOLE views -- the flattened fisheye views and the stereo-pinhole pair.  The arithmetic is stated once, in
- * csrc/landmark_plan.h: f64, every product and sum rounded on its own, the same operations in the same order as host/geometry.hpp (triangulate_point,
+ * key points of extractor_img_desc_deepnet :558-566) -- the flattened fisheye views (ideal pinholes) and the stereo-pinhole pair with the lens model of
+ * omni_camera_model, below (the ideal pinhole unless one is given).  The arithmetic is stated once, in csrc/landmark_plan.h and csrc/camera_plan.h: f64, every product and sum rounded on its own, the same operations in the same order as host/geometry.hpp (triangulate_point,
  * stereo_landmarks) and host/loop_geometry.hpp (fill_stereo_landmarks).  Poses and extrinsics are xyz + quaternion wxyz (7 doubles; the quaternion is normalised
  * on the way in).  The match lists must be one-to-one (every matcher mode of this library); a match whose index is outside its image's key points is skipped. */
 #define OMNI_STEREO_MAX_DIRS 8
 typedef struct omni_stereo_model {
-    double fx, fy, cx, cy;            /* of the network-size image: lift = ((double)x - cx) / fx, ((double)y - cy) / fy */
+    double fx, fy, cx, cy;            /* of the network-size image: the lift starts as ((double)x - cx) / fx, ((double)y - cy) / fy and, for the ideal pinhole, ends there;
+                                         with an omni_camera_model, below, the undistortion follows; MEI: gamma1, gamma2, u0, v0 */
     double triangle_thres;            /* a match is dropped when err > triangle_thres || the point lies behind the up camera */
     int accept_min_3d_pts;            /* no landmarks at all unless the up image has MORE key points than this (loop_cam.cpp:385) */
     int dirs_per_keyframe;            /* 1 .. OMNI_STEREO_MAX_DIRS: image pair p belongs to key frame p / dirs_per_keyframe, direction p % dirs_per_keyframe */
@@ -517,6 +518,29 @@ typedef struct omni_cam_landmarks_result {      /* pointers into the handle's pi
 } omni_cam_landmarks_result;
 /* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran without a model */
 int omni_cam_landmarks(omni_cam* cam, omni_cam_landmarks_result* out);
+
+/* ---- the lens model of the lift: what the reference's camodocal camera (camera_config_path, loop_cam.cpp:31-33) does in cam->liftProjective before the division by z
+ * (:403-407, :289-291, :558-569).  The arithmetic is stated once, in csrc/camera_plan.h (f64, every product and sum rounded on its own): the distorted
+ * normalised point from the intrinsics, camodocal's fixed number of undistortion rounds (8 for PINHOLE, 6 for MEI, no convergence test), then the ray divided by
+ * its z.  camodocal is not vendored: the header's formulas are the specification and parity with camodocal itself is UNPINNED.  The intrinsics stay where they
+ * were -- omni_stereo_model's fx fy cx cy (for MEI they hold gamma1, gamma2, u0, v0).  PINHOLE with all four coefficients exactly 0 is the ideal pinhole: the
+ * rounds are skipped (camodocal's m_noDistortion) and the result has the bits of ((double)x - cx) / fx.  Nothing is clamped: an iteration that diverges or a
+ * negative radicand gives inf / NaN, on the device as on the host. */
+#define OMNI_CAMERA_PINHOLE 0
+#define OMNI_CAMERA_MEI 1
+typedef struct omni_camera_model { int type; double k1, k2, p1, p2, xi; } omni_camera_model;
+/* omni_landmarks_enqueue_dev with a lens model (camera == NULL: the ideal pinhole, which is what omni_landmarks_enqueue_dev passes).  Refused before anything is
+ * launched: an unknown type, a non-finite coefficient, MEI with xi <= 0. */
+int omni_landmarks_enqueue_dev_camera(omni_ctx* ctx, const omni_stereo_model* model, const omni_camera_model* camera, const double* poses7_dev, int n_pairs,
+                                      int dirs_per_keyframe, int max_num, const float* kps_xy_dev, const int* n_kps_dev, const int* match_up_dev, const int* match_down_dev,
+                                      const int* n_matches_dev, float* norm2d_out, float* l3d_out, uint8_t* flag_out, int* count_out);
+/* The lens model of the unit's stereo-landmark stage (camera == NULL: ideal again).  It is kept next to the stereo model, not inside it: a later
+ * omni_cam_set_stereo_model leaves it as it is.  Refused: a mono handle, a unit in flight, what omni_landmarks_enqueue_dev_camera refuses. */
+int omni_cam_set_camera_model(omni_cam* cam, const omni_camera_model* camera);
+/* csrc/camera_plan.h on the host, no GPU, no context: n pixels xy [n][2] float -> out_xy_f64 [n][2] lifted and divided by z (camera == NULL: ideal);
+ * intrinsics4 = fx fy cx cy (gamma1 gamma2 u0 v0).  _project_host is the forward model (tests, synthetic data): xyz [n][3] double -> pixels [n][2] double. */
+int omni_camera_lift_host(const omni_camera_model* camera, const double* intrinsics4, const float* xy, int n, double* out_xy_f64);
+int omni_camera_project_host(const omni_camera_model* camera, const double* intrinsics4, const double* xyz, int n, double* out_xy_f64);
 
 /* ---- loop verification: the homography RANSAC of compute_correspond_features (loop_detector.cpp:574-598: the 3-D-flag filter, then
  * cv::findHomography(old_2d, new_2d, RANSAC, 3, mask)) on the GPU, f64 (csrc/homography.hip; the arithmetic: csrc/ransac_plan.h, operation for operation

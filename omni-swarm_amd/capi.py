@@ -43,6 +43,7 @@ SYMBOLS = [
     "omni_shard_search", "omni_flatten_create", "omni_flatten_destroy", "omni_flatten_out_bytes", "omni_flatten_enqueue_dev",
     "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
     "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
+    "omni_landmarks_enqueue_dev_camera", "omni_cam_set_camera_model", "omni_camera_lift_host", "omni_camera_project_host",
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
     "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
@@ -98,6 +99,43 @@ def stereo_model(fx, fy, cx, cy, triangle_thres, accept_min_3d_pts, up_extrinsic
         m.up_extrinsic[d][:] = up[d].tolist()
         m.down_extrinsic[d][:] = down[d].tolist()
     return m
+
+
+CAMERA_PINHOLE, CAMERA_MEI = 0, 1      # OMNI_CAMERA_*
+CAMERA_TYPES = {"PINHOLE": CAMERA_PINHOLE, "MEI": CAMERA_MEI}
+
+
+class CameraModel(C.Structure):
+    """omni_camera_model: the lens of the lift (csrc/camera_plan.h) -- camodocal's PINHOLE with distortion coefficients, or MEI (xi; the stereo model's
+    fx fy cx cy then hold gamma1 gamma2 u0 v0).  All zeros: the ideal pinhole."""
+    _fields_ = [("type", C.c_int), ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("xi", C.c_double)]
+
+
+def camera_model(type=CAMERA_PINHOLE, k1=0.0, k2=0.0, p1=0.0, p2=0.0, xi=0.0) -> CameraModel:
+    """type: CAMERA_PINHOLE / CAMERA_MEI or their names; nothing is checked here -- the entry points refuse what csrc/camera_plan.h's check refuses"""
+    if isinstance(type, str):
+        if type.upper() not in CAMERA_TYPES:
+            raise ValueError(f"camera_model: type {type!r}, one of {sorted(CAMERA_TYPES)}")
+        type = CAMERA_TYPES[type.upper()]
+    return CameraModel(int(type), float(k1), float(k2), float(p1), float(p2), float(xi))
+
+
+def camera_lift_host(camera, intrinsics4, xy) -> np.ndarray:
+    """omni_camera_lift_host (no GPU): pixels xy [n][2] float32 -> lifted and divided by z, [n][2] float64; camera None: the ideal pinhole"""
+    xy = _f32(xy).reshape(-1, 2)
+    k = np.ascontiguousarray(intrinsics4, np.float64).reshape(4)
+    out = np.zeros((len(xy), 2), np.float64)
+    _check(lib().omni_camera_lift_host(C.byref(camera) if camera is not None else None, k.ctypes.data, xy.ctypes.data, len(xy), out.ctypes.data))
+    return out
+
+
+def camera_project_host(camera, intrinsics4, xyz) -> np.ndarray:
+    """omni_camera_project_host (no GPU): the forward model, points xyz [n][3] in the camera's frame -> pixels [n][2] float64"""
+    xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    k = np.ascontiguousarray(intrinsics4, np.float64).reshape(4)
+    out = np.zeros((len(xyz), 2), np.float64)
+    _check(lib().omni_camera_project_host(C.byref(camera) if camera is not None else None, k.ctypes.data, xyz.ctypes.data, len(xyz), out.ctypes.data))
+    return out
 
 
 class _CamLandmarks(C.Structure):
@@ -235,6 +273,10 @@ def lib():
                                                   C.POINTER(_vp), _ip, _ip, _ip, _fp, _ip, _ip, _ip, _vp, C.POINTER(C.c_double), _ip, _ip])
     sig("omni_landmarks_enqueue_dev", C.c_int, [_vp, C.POINTER(StereoModel), _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
     sig("omni_cam_set_stereo_model", C.c_int, [_vp, C.POINTER(StereoModel)])
+    sig("omni_landmarks_enqueue_dev_camera", C.c_int, [_vp, C.POINTER(StereoModel), C.POINTER(CameraModel), _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+    sig("omni_cam_set_camera_model", C.c_int, [_vp, C.POINTER(CameraModel)])
+    sig("omni_camera_lift_host", C.c_int, [C.POINTER(CameraModel), _vp, _vp, C.c_int, _vp])
+    sig("omni_camera_project_host", C.c_int, [C.POINTER(CameraModel), _vp, _vp, C.c_int, _vp])
     sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
     sig("omni_cam_landmarks", C.c_int, [_vp, C.POINTER(_CamLandmarks)])
     sig("omni_jpeg_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64])
@@ -1331,13 +1373,19 @@ def bf_match_batched_dev(ctx: Context, n_pairs, max_n, dim, mode, q_dev, q_strid
 
 
 def landmarks_dev(ctx: Context, model: StereoModel, poses7_dev, n_pairs, max_num, kps_xy_dev, n_kps_dev, match_up_dev, match_down_dev, n_matches_dev,
-                  norm2d_out, l3d_out, flag_out, count_out):
-    """omni_landmarks_enqueue_dev: lifting + up/down triangulation on HBM-resident arrays laid out [up images | down images]; asynchronous on ctx"""
+                  norm2d_out, l3d_out, flag_out, count_out, camera=None, camera_entry=False):
+    """omni_landmarks_enqueue_dev: lifting + up/down triangulation on HBM-resident arrays laid out [up images | down images]; asynchronous on ctx.
+    camera: a CameraModel -> omni_landmarks_enqueue_dev_camera (camera_entry=True takes that entry with camera None too: its NULL, the ideal pinhole)"""
+    if camera is not None or camera_entry:
+        _check(lib().omni_landmarks_enqueue_dev_camera(ctx.h, C.byref(model), C.byref(camera) if camera is not None else None, poses7_dev, n_pairs,
+                                                       model.dirs_per_keyframe, max_num, kps_xy_dev, n_kps_dev, match_up_dev, match_down_dev, n_matches_dev, norm2d_out,
+                                                       l3d_out, flag_out, count_out))
+        return
     _check(lib().omni_landmarks_enqueue_dev(ctx.h, C.byref(model), poses7_dev, n_pairs, model.dirs_per_keyframe, max_num, kps_xy_dev, n_kps_dev, match_up_dev,
                                             match_down_dev, n_matches_dev, norm2d_out, l3d_out, flag_out, count_out))
 
 
-def landmarks(ctx: Context, model: StereoModel, poses7, kps_xy, n_kps, match_up, match_down, n_matches) -> dict:
+def landmarks(ctx: Context, model: StereoModel, poses7, kps_xy, n_kps, match_up, match_down, n_matches, camera=None, camera_entry=False) -> dict:
     """host convenience around landmarks_dev (upload, run, download): kps_xy [2P][M][2], n_kps [2P], match_* [P][M], n_matches [P], poses7 [P / dirs][7]"""
     kps_xy, n_kps = _f32(kps_xy), np.ascontiguousarray(n_kps, np.int32)
     P, M = n_kps.shape[0] // 2, kps_xy.shape[1]
@@ -1351,7 +1399,7 @@ def landmarks(ctx: Context, model: StereoModel, poses7, kps_xy, n_kps, match_up,
             dev.append(ctx.to_device(a))
         for shape, dt in outs:
             dev.append(ctx.alloc(int(np.prod(shape)) * np.dtype(dt).itemsize))
-        landmarks_dev(ctx, model, dev[0], P, M, *dev[1:])
+        landmarks_dev(ctx, model, dev[0], P, M, *dev[1:], camera=camera, camera_entry=camera_entry)
         ctx.sync()
         res = [ctx.from_device(d, shape, dt) for d, (shape, dt) in zip(dev[6:], outs)]
     finally:
@@ -1481,6 +1529,10 @@ class Cam:
         """pose_drone (xyz + quaternion wxyz) of the key frames of the NEXT unit: [n_keyframes][7]"""
         p = np.ascontiguousarray(poses7, np.float64).reshape(-1, 7)
         _check(lib().omni_cam_set_poses(self.h, p.ctypes.data_as(C.POINTER(C.c_double)), p.shape[0]))
+
+    def set_camera_model(self, camera):
+        """a CameraModel: the lens of the stage's lifts (csrc/camera_plan.h); None: the ideal pinhole again.  Kept over set_stereo_model."""
+        _check(lib().omni_cam_set_camera_model(self.h, C.byref(camera) if camera is not None else None))
 
     def landmarks(self) -> dict:
         """after wait(): numpy VIEWS of the unit's lifted key points, 3-D landmarks, flags and count_3d (valid until the next enqueue)"""

@@ -9,6 +9,7 @@
 // two events and hands out pointers into the pinned block (valid until the next enqueue on this handle).  Several handles
 // (each with its own SuperPoint / MobileNetVLAD instance) keep several key frames in flight.
 #include "common.h"
+#include "camera_plan.h"
 
 struct omni_cam {
     omni_sp* sp = nullptr;
@@ -35,6 +36,7 @@ struct omni_cam {
     // the stage's device outputs -- laid out as the key points, [up images | down images] of the active size
     bool lm_on = false, lm_unit = false;      // lm_unit: the unit enqueued last ran the stage (omni_cam_landmarks)
     omni_stereo_model model;
+    omni_camera_model camera = omni::cam::ideal();      // the lens of the stage's lifts (omni_cam_set_camera_model): kept over omni_cam_set_stereo_model
     int n_poses = 0;                          // key frames omni_cam_set_poses set since the last unit (0: none)
     int lm_n = 0;                             // directions of the unit that ran the stage last
     double* d_poses = nullptr;
@@ -529,7 +531,7 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
         uint8_t* d_flag = reinterpret_cast<uint8_t*>(c->d_lm + (c->off_flag - c->off_norm));
         int* d_cnt = reinterpret_cast<int*>(c->d_lm + (c->off_cnt - c->off_norm));
         OMNI_HIP_TRY(hipMemcpyAsync(c->d_poses, h + c->off_poses, (size_t)c->n_poses * 7 * 8, hipMemcpyHostToDevice, s1));
-        if ((rc = omni::landmarks_launch(s1, c->model, c->d_poses, n, M, c->kps_dev, c->kps_dev + half * 2, c->n_dev, c->n_dev + n, c->d_qidx, c->d_tidx, c->d_nm, d_norm,
+        if ((rc = omni::landmarks_launch(s1, c->model, c->camera, c->d_poses, n, M, c->kps_dev, c->kps_dev + half * 2, c->n_dev, c->n_dev + n, c->d_qidx, c->d_tidx, c->d_nm, d_norm,
                                          d_norm + half * 2, d_l3d, d_l3d + half * 3, d_flag, d_flag + half, d_cnt)))
             return rc;
         // (the whole block in one copy, a few hundred kilobytes at most; a smaller unit leaves the tail of each array as it was)
@@ -596,6 +598,18 @@ int omni_cam_set_stereo_model(omni_cam* c, const omni_stereo_model* model) {
     c->model = *model;
     c->lm_on = true;
     c->n_poses = 0;
+    return OMNI_OK;
+}
+
+int omni_cam_set_camera_model(omni_cam* c, const omni_camera_model* camera) {
+    OMNI_REQUIRE(c, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_camera_model with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->cams == 2, OMNI_ERR_INVALID, "omni_cam_set_camera_model: a mono handle runs no stereo-landmark stage to lift in");
+    const omni_camera_model cm = camera ? *camera : omni::cam::ideal();
+    int rc;
+    if ((rc = omni::landmarks_check_camera(&cm))) return rc;
+    c->camera = cm;
     return OMNI_OK;
 }
 

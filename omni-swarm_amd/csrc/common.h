@@ -198,10 +198,11 @@ int resize_unit_launch(const omni_resize* r, hipStream_t stream, const uint8_t* 
 namespace omni {
 // landmarks.hip: the stereo landmarks of n_pairs image pairs (landmark_plan.h) -- pair p = up image p of the *_up arrays and down image p of the *_down arrays,
 // key frame p / m.dirs_per_keyframe of poses7_dev.  Asynchronous on `stream`; the caller has checked the model (landmarks_check_model) and the sizes.
-int landmarks_launch(hipStream_t stream, const omni_stereo_model& m, const double* poses7_dev, int n_pairs, int max_num, const float* kps_up, const float* kps_down,
+int landmarks_launch(hipStream_t stream, const omni_stereo_model& m, const omni_camera_model& cm, const double* poses7_dev, int n_pairs, int max_num, const float* kps_up, const float* kps_down,
                      const int* n_up, const int* n_down, const int* match_up, const int* match_down, const int* n_matches, float* norm_up, float* norm_down,
                      float* l3d_up, float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int* count);
 int landmarks_check_model(const omni_stereo_model* m);
+int landmarks_check_camera(const omni_camera_model* cm);      // csrc/camera_plan.h's cam::check as an error code
 }  // namespace omni
 
 struct omni_jpeg;

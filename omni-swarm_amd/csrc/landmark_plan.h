@@ -7,13 +7,16 @@
 // SAME OPERATIONS IN THE SAME ORDER as geometry.hpp, every product and sum rounded on its own (contraction off: hipcc's default would fuse a * b + c), IEEE
 // division and square root: a g++ build of this header is bit-identical to the host functions, and the gfx950 build is meant to be.
 //
-//   lift          pinhole: ((double)x - cx) / fx, ((double)y - cy) / fy (KeyframePipeline::lift64_); the message keeps the floats.  Other camera models
-//                 stay with the caller, on the host path.
+//   lift          camera_plan.h's cam::lift with the model's fx fy cx cy: the ideal pinhole ((double)x - cx) / fx, ((double)y - cy) / fy unless an
+//                 omni_camera_model says otherwise (camodocal's PINHOLE with distortion, MEI); the message keeps the floats.  Every function that lifts has
+//                 two forms: with the lens model, and the earlier signature, which is the ideal pinhole.
 //   poses         pose_up = pose_drone * extrinsic_up, pose_down likewise; input xyz + quaternion wxyz, normalised as to_pose() does.
 //   triangulate   design matrix, D^T D, the cyclic Jacobi of jacobi_eigen<4> (sweep limit 60, the same stop and skip rules, the same rotation order),
 //                 v / v[3], the residual.  Only the eigenvector of the SMALLEST eigenvalue is read: the arg-min of the diagonal replaces the sort.  Where
 //                 the smallest eigenvalue is unique both give the same row; a tie is a two-dimensional null space in which the sorted form's choice is
-//                 arbitrary too -- ties are reported (*tie) and are outside what the tests gate.
+//                 arbitrary too -- ties are reported (*tie) and are outside what the tests gate on finite input.  The arg-min walks from the last row down,
+//                 so among equal entries it lands where the host's stable sort does: a lift that diverged to inf (camera_plan.h) makes the whole diagonal
+//                 inf before the first sweep, and both forms then read the untouched last row.
 //   accept        nothing at all unless the up image has MORE than accept_min_3d_pts key points; a match is dropped when
 //                 `err > triangle_thres || pt_cam.z < 0` (literally: a NaN residual passes, as on the host); the float point and flag 1 go to both
 //                 images at the matched indices, zeros elsewhere; the number kept is count_3d.
@@ -26,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/omni_hip.h"
+#include "camera_plan.h"
 
 #if defined(__HIPCC__)
 #define LM_HD __host__ __device__ inline
@@ -103,11 +107,9 @@ LM_HD void pair_geom(const double* pose_drone7, const double* up7, const double*
     g.pos_up[0] = pose_up.p[0]; g.pos_up[1] = pose_up.p[1]; g.pos_up[2] = pose_up.p[2];
 }
 
-// the pinhole lift of one pixel, in double
-LM_HD void lift(const omni_stereo_model& m, float x, float y, double* o) {
-    o[0] = ((double)x - m.cx) / m.fx;
-    o[1] = ((double)y - m.cy) / m.fy;
-}
+// the lift of one pixel, in double: the lens model `c` on the stereo model's intrinsics; without one, the ideal pinhole
+LM_HD void lift(const omni_stereo_model& m, const omni_camera_model& c, float x, float y, double* o) { cam::lift(c, m.fx, m.fy, m.cx, m.cy, x, y, o); }
+LM_HD void lift(const omni_stereo_model& m, float x, float y, double* o) { lift(m, cam::ideal(), x, y, o); }
 
 // geom::triangulate_point from the pair's projections: the point (world frame) and the residual |design * [X; 1]| / 4.  *tie = 1 when the smallest
 // diagonal entry after the Jacobi sweeps is not unique.
@@ -142,9 +144,11 @@ LM_HD double triangulate(const PairGeom& g, const double* p0, const double* p1, 
         }
     }
     // the row of the smallest eigenvalue (selects, not an indexed read: the rows stay in registers)
-    double wmin = A[0][0], v0 = V[0][0], v1 = V[0][1], v2 = V[0][2], v3 = V[0][3];
+    // Walked from the LAST row down with a strict comparison: among equal smallest entries the last one wins, which is where the host's stable descending sort
+    // leaves it (and row 3 when every entry is NaN) -- so the all-inf diagonal of a lift that diverged picks the host's row too
+    double wmin = A[3][3], v0 = V[3][0], v1 = V[3][1], v2 = V[3][2], v3 = V[3][3];
     int n_min = 1;
-    LM_UNROLL for (int i = 1; i < 4; ++i) {
+    LM_UNROLL for (int i = 2; i >= 0; --i) {
         const double w = A[i][i];
         if (w < wmin) { wmin = w; v0 = V[i][0]; v1 = V[i][1]; v2 = V[i][2]; v3 = V[i][3]; n_min = 1; }
         else if (w == wmin) ++n_min;
@@ -161,7 +165,7 @@ LM_HD double triangulate(const PairGeom& g, const double* p0, const double* p1, 
 LM_HD int clamp_count(int n, int max_num) { return n < 0 ? 0 : (n > max_num ? max_num : n); }
 
 // phase 0: the message's lifted floats of every key point of both images (zeros behind the last key point), landmarks and flags zeroed
-LM_HD void pair_phase0(const omni_stereo_model& m, int max_num, const float* kps_up, int n_up, const float* kps_down, int n_down, float* norm_up, float* norm_down,
+LM_HD void pair_phase0(const omni_stereo_model& m, const omni_camera_model& c, int max_num, const float* kps_up, int n_up, const float* kps_down, int n_down, float* norm_up, float* norm_down,
                        float* l3d_up, float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int lane, int n_lanes) {
     n_up = clamp_count(n_up, max_num); n_down = clamp_count(n_down, max_num);
     for (int k = lane; k < 2 * max_num; k += n_lanes) {
@@ -172,21 +176,25 @@ LM_HD void pair_phase0(const omni_stereo_model& m, int max_num, const float* kps
         float* l3 = dn ? l3d_down : l3d_up;
         double q[2] = {0, 0};
         const bool live = i < (dn ? n_down : n_up);
-        if (live) lift(m, kp[2 * i], kp[2 * i + 1], q);
+        if (live) lift(m, c, kp[2 * i], kp[2 * i + 1], q);
         nrm[2 * i] = live ? (float)q[0] : 0.f; nrm[2 * i + 1] = live ? (float)q[1] : 0.f;
         l3[3 * i] = 0.f; l3[3 * i + 1] = 0.f; l3[3 * i + 2] = 0.f;
         (dn ? flag_down : flag_up)[i] = 0;
     }
 }
+LM_HD void pair_phase0(const omni_stereo_model& m, int max_num, const float* kps_up, int n_up, const float* kps_down, int n_down, float* norm_up, float* norm_down,
+                       float* l3d_up, float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int lane, int n_lanes) {
+    pair_phase0(m, cam::ideal(), max_num, kps_up, n_up, kps_down, n_down, norm_up, norm_down, l3d_up, l3d_down, flag_up, flag_down, lane, n_lanes);
+}
 
 // phase 1, ONE match: returns 1 when it was kept (and written), 0 otherwise.  *tie as triangulate().
-LM_HD int pair_match(const omni_stereo_model& m, const PairGeom& g, const float* kps_up, int n_up, const float* kps_down, int n_down, int iu, int id, float* l3d_up,
+LM_HD int pair_match(const omni_stereo_model& m, const omni_camera_model& c, const PairGeom& g, const float* kps_up, int n_up, const float* kps_down, int n_down, int iu, int id, float* l3d_up,
                      float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int* tie) {
     *tie = 0;
     if (iu < 0 || iu >= n_up || id < 0 || id >= n_down) return 0;
     double p0[2], p1[2], p[3], d[3], cam[3];
-    lift(m, kps_up[2 * iu], kps_up[2 * iu + 1], p0);
-    lift(m, kps_down[2 * id], kps_down[2 * id + 1], p1);
+    lift(m, c, kps_up[2 * iu], kps_up[2 * iu + 1], p0);
+    lift(m, c, kps_down[2 * id], kps_down[2 * id + 1], p1);
     const double err = triangulate(g, p0, p1, p, tie);
     d[0] = p[0] - g.pos_up[0]; d[1] = p[1] - g.pos_up[1]; d[2] = p[2] - g.pos_up[2];
     mat_vec(g.Rinv, d, cam);
@@ -196,6 +204,10 @@ LM_HD int pair_match(const omni_stereo_model& m, const PairGeom& g, const float*
     l3d_down[3 * id] = x; l3d_down[3 * id + 1] = y; l3d_down[3 * id + 2] = z; flag_down[id] = 1;
     return 1;
 }
+LM_HD int pair_match(const omni_stereo_model& m, const PairGeom& g, const float* kps_up, int n_up, const float* kps_down, int n_down, int iu, int id, float* l3d_up,
+                     float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int* tie) {
+    return pair_match(m, cam::ideal(), g, kps_up, n_up, kps_down, n_down, iu, id, l3d_up, l3d_down, flag_up, flag_down, tie);
+}
 
 // the number of matches phase 1 walks: none unless the up image has MORE than accept_min_3d_pts key points (loop_cam.cpp:385)
 LM_HD int pair_live_matches(const omni_stereo_model& m, int max_num, int n_up, int n_matches) {
@@ -204,7 +216,7 @@ LM_HD int pair_live_matches(const omni_stereo_model& m, int max_num, int n_up, i
 
 // host form of the whole stage on the arrays of omni_landmarks_enqueue_dev ([up images | down images], pair p of key frame p / dirs, direction p % dirs):
 // what the kernel computes, sequentially.  Returns the number of tied smallest eigenvalues met.
-inline int landmarks_host(const omni_stereo_model& m, const double* poses7, int n_pairs, int max_num, const float* kps_xy, const int* n_kps, const int* match_up,
+inline int landmarks_host(const omni_stereo_model& m, const omni_camera_model& cm, const double* poses7, int n_pairs, int max_num, const float* kps_xy, const int* n_kps, const int* match_up,
                           const int* match_down, const int* n_matches, float* norm2d, float* l3d, uint8_t* flag, int* count) {
     int ties = 0;
     const int dirs = m.dirs_per_keyframe;
@@ -213,19 +225,23 @@ inline int landmarks_host(const omni_stereo_model& m, const double* poses7, int 
         const float *ku = kps_xy + (int64_t)iu * max_num * 2, *kd = kps_xy + (int64_t)id * max_num * 2;
         float *l3u = l3d + (int64_t)iu * max_num * 3, *l3d_ = l3d + (int64_t)id * max_num * 3;
         uint8_t *fu = flag + (int64_t)iu * max_num, *fd = flag + (int64_t)id * max_num;
-        pair_phase0(m, max_num, ku, n_kps[iu], kd, n_kps[id], norm2d + (int64_t)iu * max_num * 2, norm2d + (int64_t)id * max_num * 2, l3u, l3d_, fu, fd, 0, 1);
+        pair_phase0(m, cm, max_num, ku, n_kps[iu], kd, n_kps[id], norm2d + (int64_t)iu * max_num * 2, norm2d + (int64_t)id * max_num * 2, l3u, l3d_, fu, fd, 0, 1);
         PairGeom g;
         pair_geom(poses7 + 7 * (p / dirs), m.up_extrinsic[p % dirs], m.down_extrinsic[p % dirs], g);
         const int nu = clamp_count(n_kps[iu], max_num), nd = clamp_count(n_kps[id], max_num), nm = pair_live_matches(m, max_num, n_kps[iu], n_matches[p]);
         int c = 0;
         for (int i = 0; i < nm; ++i) {
             int tie = 0;
-            c += pair_match(m, g, ku, nu, kd, nd, match_up[(int64_t)p * max_num + i], match_down[(int64_t)p * max_num + i], l3u, l3d_, fu, fd, &tie);
+            c += pair_match(m, cm, g, ku, nu, kd, nd, match_up[(int64_t)p * max_num + i], match_down[(int64_t)p * max_num + i], l3u, l3d_, fu, fd, &tie);
             ties += tie;
         }
         count[p] = c;
     }
     return ties;
+}
+inline int landmarks_host(const omni_stereo_model& m, const double* poses7, int n_pairs, int max_num, const float* kps_xy, const int* n_kps, const int* match_up,
+                          const int* match_down, const int* n_matches, float* norm2d, float* l3d, uint8_t* flag, int* count) {
+    return landmarks_host(m, cam::ideal(), poses7, n_pairs, max_num, kps_xy, n_kps, match_up, match_down, n_matches, norm2d, l3d, flag, count);
 }
 
 }  // namespace lm

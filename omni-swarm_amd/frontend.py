@@ -9,8 +9,9 @@ The reference runs these 8 + 4 engine calls and 4 matches strictly one after ano
 stream sync; here one key frame is three batched enqueues on one HIP stream (8 SuperPoint images, 4
 MobileNetVLAD images on a second stream, 4 descriptor-set pairs) with every intermediate resident in HBM and one small
 D2H at the end.
-Camera geometry (liftProjective, SVD triangulation, loop_cam.cpp:73-106,405-454,558-576): for pinhole views a
-capi.StereoModel (stereo_model=) moves it into the unit -- f64 on the GPU (csrc/landmarks.hip), the key frame's
+Camera geometry (liftProjective, SVD triangulation, loop_cam.cpp:73-106,405-454,558-576): a capi.StereoModel
+(stereo_model=) moves it into the unit -- f64 on the GPU (csrc/landmarks.hip), the lens a capi.CameraModel
+(camera_model=: camodocal's PINHOLE with distortion or MEI; the ideal pinhole without one), the key frame's
 pose_drone set with set_poses() before every key frame; without a model it is left to the caller, for whom the 2-D key
 points, descriptors, global descriptors and the up/down match lists are everything those steps consume.
 """
@@ -25,7 +26,7 @@ class LoopCam:
     def __init__(self, ctx: capi.Context, sp_weights: dict, pca_comp, pca_mean, vlad_weights: dict, vlad_specs,
                  vlad_shape=(32, 112, 4096), width: int = 600, height: int = 480, thres: float = 0.015,
                  max_num: int = 200, precision: int = capi.PREC_F16, n_dirs: int = 4, fisheye: bool = True,
-                 accept_min_3d_pts: int = 0, stereo_model: capi.StereoModel = None):
+                 accept_min_3d_pts: int = 0, stereo_model: capi.StereoModel = None, camera_model: capi.CameraModel = None):
         self.ctx, self.W, self.H, self.n_dirs, self.max_num, self.fisheye = ctx, width, height, n_dirs, max_num, fisheye
         self.accept_min_3d_pts = accept_min_3d_pts
         self.sp = capi.SuperPoint(ctx, sp_weights, pca_comp, pca_mean, width, height, thres, max_num, precision, 2 * n_dirs)
@@ -42,6 +43,9 @@ class LoopCam:
         self.stereo_model = stereo_model
         if stereo_model is not None:
             self.cam.set_stereo_model(stereo_model)
+        self.camera_model = camera_model
+        if camera_model is not None:
+            self.cam.set_camera_model(camera_model)
 
     def set_poses(self, poses7):
         """pose_drone (xyz + quaternion wxyz) of the key frames of the NEXT unit, [n_keyframes][7]: needed before every key frame when a stereo_model is set"""

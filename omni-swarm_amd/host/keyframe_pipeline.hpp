@@ -14,6 +14,7 @@
 #include <memory>
 #include <thread>
 
+#include "camera_model.hpp"
 #include "fisheye_flatten.hpp"
 #include "loop_geometry.hpp"
 #include "omni_swarm.hpp"
@@ -74,6 +75,11 @@ public:
         bool geometry = false;
         double fx = 300, fy = 300, cx = 300, cy = 240, triangle_thres = 0.006, stereo_baseline = 0.10;
         int accept_min_3d_pts = 50;
+        // the lens behind fx fy cx cy (camera_model.hpp, csrc/camera_plan.h): camodocal's PINHOLE with distortion coefficients or MEI (fx fy cx cy then hold
+        // gamma1 gamma2 u0 v0), what the reference's camera_config_path file describes.  Every lift goes through it -- the message's landmarks_2d_norm, the
+        // triangulation's double lift on either path, PINHOLE_DEPTH's depth landmarks.  Default: the ideal pinhole.  The raw-fisheye mode flattens into ideal
+        // views and refuses anything else.  (set_camera_model: before the first key frame.)
+        omni_camera_model camera_model = cam::ideal();
         // STEREO_FISHEYE / STEREO_PINHOLE with `geometry`: the lifting and the up/down triangulation of generate_stereo_image_descriptor (loop_cam.cpp:397-444) run
         // inside the key-frame unit, f64 on the GPU (csrc/landmarks.hip: bit-identical to the host functions, tests/test_gpu_landmarks.py), and finish() copies the
         // landmarks out of the unit's result block instead of submitting one triangulation task per direction.  Off: the host path (fill_stereo_landmarks on the
@@ -174,8 +180,16 @@ public:
                 throw std::runtime_error("KeyframePipeline: raw-fisheye mode: the side views are " + std::to_string(c.width) + " x " + std::to_string(side_h) + " but the networks take " +
                                          std::to_string(c.width) + " x " + std::to_string(c.height));
         }
+        check_camera_model(c, c.camera_model);
         if (c.pipelines <= 0) c.pipelines = default_pipelines(c.precision);
         return c;
+    }
+    // what cam::check refuses, and a lens in the one mode whose views are ideal by construction
+    static void check_camera_model(const Config& c, const omni_camera_model& m) {
+        if (const char* why = cam::check(m)) throw std::runtime_error(std::string("KeyframePipeline: ") + why);
+        if (c.fisheye_raw() && !cam::is_ideal(m))
+            throw std::runtime_error("KeyframePipeline: the raw-fisheye mode flattens the frames into ideal pinhole views inside the unit, so its key points have no lens to undo: "
+                                     "camera_model must stay the ideal pinhole (the fisheye lens itself is fisheye_mei_up / fisheye_mei_down)");
     }
     int pipelines() const { return cfg_.pipelines; }
     int microbatch() const { return cfg_.microbatch; }
@@ -464,6 +478,20 @@ public:
     // candidates whose RANSAC ran on the device / that ran geom::solve_pnp_ransac although the switch was on (handed back, or too many points), so far
     int pnp_candidates_device() const { return pnp_candidates_device_.load(); }
     int pnp_candidates_host() const { return pnp_candidates_host_.load(); }
+    // ---- the lens of every lift (Config::camera_model) ---------------------------------------------------------------------------------------------------
+    CameraModel camera() const { CameraModel c; c.model = cfg_.camera_model; c.fx = cfg_.fx; c.fy = cfg_.fy; c.cx = cfg_.cx; c.cy = cfg_.cy; return c; }
+    omni_camera_model camera_model() const { return cfg_.camera_model; }
+    // before the first key frame (what the C entry point omni_pipeline_set_camera_model sets); intrinsics4 = fx fy cx cy of the network-size image, nullptr: kept
+    void set_camera_model(const omni_camera_model& m, const double* intrinsics4 = nullptr) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_camera_model after the first key frame");
+        check_camera_model(cfg_, m);
+        if (intrinsics4 && !(intrinsics4[0] != 0 && intrinsics4[1] != 0 && intrinsics4[0] == intrinsics4[0] && intrinsics4[1] == intrinsics4[1]))
+            throw std::invalid_argument("set_camera_model: focal lengths " + std::to_string(intrinsics4[0]) + ", " + std::to_string(intrinsics4[1]));
+        cfg_.camera_model = m;
+        if (intrinsics4) { cfg_.fx = intrinsics4[0]; cfg_.fy = intrinsics4[1]; cfg_.cx = intrinsics4[2]; cfg_.cy = intrinsics4[3]; }
+        apply_stereo_model();
+    }
     // before the first key frame: switches the stage on or off on every lane (what the C entry point omni_pipeline_set_device_landmarks sets)
     void set_device_landmarks(bool on) {
         std::lock_guard<std::mutex> lk(intake_mu_);
@@ -508,6 +536,7 @@ private:
     }
     void apply_stereo_model(Lane& l) {
         const omni_stereo_model m = stereo_model();
+        if (cfg_.stereo()) l.cam.set_camera_model(&cfg_.camera_model);      // (a mono unit runs no landmark stage: PINHOLE_DEPTH lifts on the host)
         l.cam.set_stereo_model(device_landmarks() ? &m : nullptr);
     }
     void apply_stereo_model() {
@@ -1083,7 +1112,8 @@ private:
 
     Config cfg_;
     // cam->liftProjective of the flattened (pinhole) views, then the division by z: in double, as the reference's camera model
-    const std::function<geom::Vec2(const Point2f&)> lift64_ = [this](const Point2f& p) { return geom::Vec2{((double)p.x - cfg_.cx) / cfg_.fx, ((double)p.y - cfg_.cy) / cfg_.fy}; };
+    // the camera's lift in double (camera_model.hpp -> csrc/camera_plan.h: the header the unit's landmark kernel runs; the ideal pinhole by default)
+    const std::function<geom::Vec2(const Point2f&)> lift64_ = [this](const Point2f& p) { return camera().lift(p); };
     Context index_ctx_;
     LoopDetectorCore det_;
     BFMatcherL2X bf_{index_ctx_};

@@ -57,7 +57,7 @@ inline void fill_image_descriptor(ImageDescriptor& im, const float* kps_xy, int 
 }
 // The same message from a key-frame unit that ran the stereo-landmark stage itself (omni_cam_landmarks: csrc/landmarks.hip): the lifted floats, the 3-D
 // landmarks and the flags are copied from the unit's result block -- norm2d [n][2], l3d [n][3], flag [n] of this image -- instead of being computed here;
-// bit for bit what fill_image_descriptor + fill_stereo_landmarks leave in both messages of a direction for a pinhole lift.
+// bit for bit what fill_image_descriptor + fill_stereo_landmarks leave in both messages of a direction for the unit's lens model (omni::CameraModel::lift).
 inline void fill_image_descriptor_device(ImageDescriptor& im, const float* kps_xy, int n, const float* desc, int desc_dim, const float* global_desc, int global_dim,
                                          const float* norm2d, const float* l3d, const uint8_t* flag) {
     im.landmark_num = n;
@@ -119,7 +119,7 @@ inline int fill_stereo_landmarks(ImageDescriptor& up, ImageDescriptor& down, con
 // than accept_min_3d_pts key points (:266-270); the pixel gate is the reference's literal 640 x 480 with INCLUSIVE upper bounds (:280); the depth is read at
 // the pixel cv::Mat::at<ushort>(Point2f) addresses, i.e. the coordinates rounded half to even (cv::Point_<int>(Point_<float>) = saturate_cast = cvRound).
 // Deviation: a key point the gate lets through but which lies outside THIS depth image (x = 640 on a 640-wide image: the reference reads past the row)
-// gets no landmark.  `lift` = cam->liftProjective (camodocal is un-vendored: the camera model stays with the caller), applied to the pixel in double
+// gets no landmark.  `lift` = cam->liftProjective (host/camera_model.hpp: omni::CameraModel::lift, csrc/camera_plan.h's arithmetic), applied to the pixel in double
 // (:289) and divided by z (:291).  Returns the number of landmarks set (count_3d).
 inline int fill_depth_landmarks(ImageDescriptor& im, const uint16_t* depth, int depth_stride, int depth_w, int depth_h, double depth_near, double depth_far,
                                 int accept_min_3d_pts, const std::function<geom::Vec2(const Point2f&)>& lift) {

@@ -398,9 +398,11 @@ public:
     void order_after(LoopCamHIP& earlier, int streams) { check(omni_cam_order_after(h_, earlier.h_, streams), "omni_cam_order_after"); }
     // a unit of fewer directions than this object was created for (omni_cam_set_active): the next enqueues read cams * n_dirs images
     void set_active(int n_dirs) { check(omni_cam_set_active(h_, n_dirs), "omni_cam_set_active"); }
-    // the stereo landmarks of a pinhole model inside the unit (csrc/landmarks.hip; loop_cam.cpp:397-444): set_stereo_model once (nullptr: off again), set_poses
+    // the stereo landmarks inside the unit (csrc/landmarks.hip; loop_cam.cpp:397-444): set_stereo_model once (nullptr: off again), set_poses
     // (pose_drone of the next unit's key frames, [n_keyframes][7] xyz + quaternion wxyz) before every enqueue, landmarks() after wait()
     void set_stereo_model(const omni_stereo_model* model) { check(omni_cam_set_stereo_model(h_, model), "omni_cam_set_stereo_model"); }
+    // the lens of the stage's lifts (csrc/camera_plan.h: camodocal's PINHOLE with distortion, MEI; nullptr: the ideal pinhole); kept over set_stereo_model
+    void set_camera_model(const omni_camera_model* camera) { check(omni_cam_set_camera_model(h_, camera), "omni_cam_set_camera_model"); }
     void set_poses(const double* poses7, int n_keyframes) { check(omni_cam_set_poses(h_, poses7, n_keyframes), "omni_cam_set_poses"); }
     omni_cam_landmarks_result landmarks() {
         omni_cam_landmarks_result r{};

@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "camera_model.hpp"
+
 namespace omni {
 
 // X(type tag, C++ type, ROS parameter name, default)   -- in the order of swarm_loop.cpp:215-270
@@ -104,6 +106,12 @@ struct SwarmLoopParams {
         is_compressed_images = false;
         return false;
     }
+
+    // not a node parameter either: the camera the node builds from the camodocal file that camera_config_path names (loop_cam.cpp:31-33) --
+    // read_camera_config() below takes the file's TEXT (this header opens no files).  Without one the pipeline keeps the ideal pinhole and the caller's intrinsics.
+    bool have_camera_config = false;
+    CameraModel camera;
+    void read_camera_config(const std::string& yaml_text) { camera = CameraModel::from_camodocal_yaml(yaml_text); have_camera_config = true; }
 
     struct Field { const char* name; char type; /* 'I' int, 'B' bool, 'D' double, 'S' string */ };
     static const std::vector<Field>& fields() {
@@ -234,6 +242,12 @@ struct SwarmLoopParams {
         c.pca_comp = pca_comp_path; c.pca_mean = pca_mean_path;
         c.send_img = send_img; c.jpg_quality = jpg_quality;                 // swarm_loop.cpp:224-225 -> LoopCam (encode_image, loop_cam.cpp:56-71)
         c.compressed_images = is_compressed_images;                         // the VINS settings file (read_vins_settings): CompressedImage topics
+        if (have_camera_config) {
+            // the camodocal file (read_camera_config): lens and intrinsics, the latter scaled to the networks' image size when the file was calibrated at another
+            // one.  DEVIATION: the reference does not scale (CameraModel::scaled has the reason)
+            const CameraModel k = camera.scaled(width, height);
+            c.camera_model = k.model; c.fx = k.fx; c.fy = k.fy; c.cx = k.cx; c.cy = k.cy;
+        }
     }
     template <class Intake> void to_intake(Intake& i) const {              // swarm_loop.cpp:217-218, 238 -> KeyframeIntake
         i.max_freq = max_freq; i.min_movement_keyframe = min_movement_keyframe; i.accept_nonkeyframe_waitsec = nonkeyframe_waitsec;

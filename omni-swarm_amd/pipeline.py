@@ -47,6 +47,11 @@ _jpegdec_lib = None
 FISHEYE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_fisheye.so")
 FISHEYE_SYMBOLS = ["omni_fisheye_last_error", "omni_pipeline_create_stereo_fisheye_raw", "omni_pipeline_get_fisheye_raw"]
 _fisheye_lib = None
+# the lens model of the pipeline's lifts and the camodocal file reader: include/omni_host_camera.h, lib/libomni_host_camera.so (the same handle)
+CAMERA_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_camera.so")
+CAMERA_SYMBOLS = ["omni_camera_last_error", "omni_pipeline_set_camera_model", "omni_pipeline_get_camera_model", "omni_camera_from_yaml",
+                  "omni_pipeline_create_from_launch_camera", "omni_pipeline_frame_landmarks"]
+_camera_lib = None
 
 
 def lib():
@@ -172,6 +177,50 @@ def landmarks_lib():
     return _landmarks_lib
 
 
+def camera_lib():
+    """libomni_host_camera.so (include/omni_host_camera.h): the lens model of the key-frame pipeline, the camodocal file reader"""
+    global _camera_lib
+    if _camera_lib is None:
+        lib()
+        if not os.path.exists(CAMERA_LIB_PATH):
+            raise OSError(f"{CAMERA_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(CAMERA_LIB_PATH)
+        L.omni_camera_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_camera_model.argtypes = [C.c_void_p, C.POINTER(capi.CameraModel), C.POINTER(C.c_double)]
+        L.omni_pipeline_get_camera_model.argtypes = [C.c_void_p, C.POINTER(capi.CameraModel), C.POINTER(C.c_double)]
+        L.omni_camera_from_yaml.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(capi.CameraModel), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.omni_pipeline_create_from_launch_camera.restype = C.c_void_p
+        L.omni_pipeline_create_from_launch_camera.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                              C.c_int, C.c_int, C.c_int, C.c_char_p]
+        L.omni_pipeline_frame_landmarks.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _camera_lib = L
+    return _camera_lib
+
+
+_CAMERA_NAMES = {v: k for k, v in capi.CAMERA_TYPES.items()}
+
+
+def _camera_struct(camera_model) -> capi.CameraModel:
+    """a capi.CameraModel, or a dict(type=, k1=, k2=, p1=, p2=, xi=) with type "PINHOLE" / "MEI" (or 0 / 1)"""
+    if isinstance(camera_model, capi.CameraModel):
+        return camera_model
+    d = dict(camera_model)
+    extra = set(d) - {"type", "k1", "k2", "p1", "p2", "xi", "intrinsics", "image_size"}
+    if extra:
+        raise ValueError(f"camera_model: unknown entries {sorted(extra)}")
+    return capi.camera_model(d.get("type", capi.CAMERA_PINHOLE), d.get("k1", 0.0), d.get("k2", 0.0), d.get("p1", 0.0), d.get("p2", 0.0), d.get("xi", 0.0))
+
+
+def camera_from_yaml(text: str, width: int = 0, height: int = 0) -> dict:
+    """the camodocal file the node's camera_config_path names (its TEXT): dict(type="PINHOLE" | "MEI", k1, k2, p1, p2, xi, intrinsics=[fx, fy, cx, cy] -- MEI:
+    gamma1 gamma2 u0 v0 --, image_size=(image_width, image_height)).  width, height > 0: the intrinsics scaled to images of that size.  The dict is what
+    KeyframePipeline(camera_model=) and set_camera_model take."""
+    m, k, wh = capi.CameraModel(), (C.c_double * 4)(), (C.c_int * 2)()
+    if camera_lib().omni_camera_from_yaml(text.encode(), int(width), int(height), C.byref(m), k, wh):
+        raise capi.OmniError(f"omni_camera_from_yaml: {camera_lib().omni_camera_last_error().decode()}")
+    return {"type": _CAMERA_NAMES[m.type], "k1": m.k1, "k2": m.k2, "p1": m.p1, "p2": m.p2, "xi": m.xi, "intrinsics": list(k), "image_size": (wh[0], wh[1])}
+
+
 def homography_lib():
     global _homography_lib
     if _homography_lib is None:
@@ -245,7 +294,7 @@ class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -263,6 +312,9 @@ class KeyframePipeline:
         ONE up frame and ONE down frame of src_width x src_height per key frame, flattened into the four side views (width x height) inside every unit, on the
         GPU; mei_up / mei_down: the cameras' nine MEI parameters as flatten.generate_undist_maps takes them.  With compressed_images the two frames are JPEG
         files (push_keyframe_jpeg, run_jpeg).  The reference has no such path: its upstream (VINS-Fisheye) flattens.
+        camera_model: a dict(type="PINHOLE" | "MEI", k1=, k2=, p1=, p2=, xi=) (what camera_from_yaml returns; its "intrinsics", when present, replace fx fy cx cy)
+        or a capi.CameraModel = the lens behind the intrinsics, as the reference's camodocal file describes it: every lift -- landmarks_2d_norm, the triangulation on
+        either path, PINHOLE_DEPTH's depth landmarks -- undoes it (csrc/camera_plan.h).  None: the ideal pinhole.  Refused in the raw_fisheye mode.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -293,6 +345,8 @@ class KeyframePipeline:
         self._depth = None
         if not self.h:
             raise _err("omni_pipeline_create")
+        if camera_model is not None:
+            self.set_camera_model(camera_model)
         if device_landmarks is not None:
             self.set_device_landmarks(device_landmarks)
         if device_homography is not None:
@@ -303,6 +357,35 @@ class KeyframePipeline:
             self.set_send_img(True, jpg_quality)
         if compressed_images:
             self.set_compressed_images(True)
+
+    def set_camera_model(self, camera_model, intrinsics=None):
+        """before the first key frame: the lens of every lift (see __init__); None: the ideal pinhole.  intrinsics [fx, fy, cx, cy] of the network-size image
+        (or the dict's own "intrinsics"): None keeps the pipeline's"""
+        m = _camera_struct(camera_model) if camera_model is not None else None
+        if intrinsics is None and isinstance(camera_model, dict):
+            intrinsics = camera_model.get("intrinsics")
+        k = (C.c_double * 4)(*[float(v) for v in intrinsics]) if intrinsics is not None else None
+        if camera_lib().omni_pipeline_set_camera_model(self.h, C.byref(m) if m is not None else None, k):
+            raise capi.OmniError(f"omni_pipeline_set_camera_model: {camera_lib().omni_camera_last_error().decode()}")
+
+    def camera_model(self) -> dict:
+        """the lens and the intrinsics the pipeline lifts with, as camera_from_yaml's dict (without image_size)"""
+        m, k = capi.CameraModel(), (C.c_double * 4)()
+        if camera_lib().omni_pipeline_get_camera_model(self.h, C.byref(m), k):
+            raise capi.OmniError(f"omni_pipeline_get_camera_model: {camera_lib().omni_camera_last_error().decode()}")
+        return {"type": _CAMERA_NAMES[m.type], "k1": m.k1, "k2": m.k2, "p1": m.p1, "p2": m.p2, "xi": m.xi, "intrinsics": list(k)}
+
+    def frame_landmarks(self, msg_id: int, direction: int = 0, max_n: int = 1024) -> dict:
+        """the landmarks of one image of a key frame in the database as its message carries them: landmarks_2d [n][2], landmarks_2d_norm [n][2] (the lifted
+        floats), landmarks_3d [n][3], landmarks_flag [n]"""
+        n = C.c_int(0)
+        a2, an, a3, af = np.zeros((max_n, 2), np.float32), np.zeros((max_n, 2), np.float32), np.zeros((max_n, 3), np.float32), np.zeros(max_n, np.uint8)
+        if camera_lib().omni_pipeline_frame_landmarks(self.h, msg_id, direction, max_n, C.byref(n), a2.ctypes.data, an.ctypes.data, a3.ctypes.data, af.ctypes.data):
+            raise capi.OmniError(f"omni_pipeline_frame_landmarks: {camera_lib().omni_camera_last_error().decode()}")
+        if n.value > max_n:
+            raise ValueError(f"frame_landmarks: {n.value} key points, max_n = {max_n}")
+        k = n.value
+        return {"landmarks_2d": a2[:k].copy(), "landmarks_2d_norm": an[:k].copy(), "landmarks_3d": a3[:k].copy(), "landmarks_flag": af[:k].copy()}
 
     def set_device_landmarks(self, on: bool):
         """before the first key frame: stereo landmarks inside the key-frame unit (GPU) or on the host's geometry threads"""
@@ -435,14 +518,25 @@ class KeyframePipeline:
     @classmethod
     def from_launch(cls, device: int, launch_xml: str, sp_weights_path: str, vlad_weights_path: str, pca_comp_csv: str | None = None, pca_mean_csv: str | None = None,
                     precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, geometry=False, node_name="swarm_loop", args: dict | None = None,
-                    intrinsics=None):
+                    intrinsics=None, camera_yaml: str | None = None):
         """A pipeline configured by one of the reference's launch files (omni_pipeline_create_from_launch): image size, thresholds, camera configuration and
-        self_id come from the file; weights, precision and batching are this build's."""
+        self_id come from the file; weights, precision and batching are this build's.  camera_yaml: the TEXT of the camodocal file the launch file's
+        camera_config_path names (omni_pipeline_create_from_launch_camera): lens and intrinsics come from it, scaled to the launch file's image size, in the
+        place of `intrinsics`."""
         self = cls.__new__(cls)
         a = "\n".join(f"{k}:={v}" for k, v in (args or {}).items()).encode() or None
         k4 = (C.c_double * 4)(*intrinsics) if intrinsics is not None else None
         self.microbatch = microbatch
         self._depth = None
+        if camera_yaml is not None:
+            if intrinsics is not None:
+                raise ValueError("from_launch: camera_yaml carries the intrinsics; give one of the two")
+            self.h = camera_lib().omni_pipeline_create_from_launch_camera(device, launch_xml.encode(), node_name.encode(), a, sp_weights_path.encode(), vlad_weights_path.encode(),
+                                                                          pca_comp_csv.encode() if pca_comp_csv else None, pca_mean_csv.encode() if pca_mean_csv else None,
+                                                                          precision, microbatch, pipelines, storage, int(geometry), camera_yaml.encode())
+            if not self.h:
+                raise capi.OmniError(f"omni_pipeline_create_from_launch_camera: {camera_lib().omni_camera_last_error().decode()}")
+            return self
         self.h = lib().omni_pipeline_create_from_launch(device, launch_xml.encode(), node_name.encode(), a, sp_weights_path.encode(), vlad_weights_path.encode(),
                                                        pca_comp_csv.encode() if pca_comp_csv else None, pca_mean_csv.encode() if pca_mean_csv else None, precision,
                                                        microbatch, pipelines, storage, int(geometry), k4)
