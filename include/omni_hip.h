@@ -721,19 +721,21 @@ int           omni_jpegdec_classify(const uint8_t* file, int64_t size, int* widt
  * and the other HOST files included.  out: the picture (its size: omni_jpegdec_classify), `stride` bytes between rows.  *status = the classification, or
  * OMNI_JPEGDEC_CORRUPT with the picture zeroed; an UNSUPPORTED file writes nothing.  OMNI_ERR_INVALID for null arguments and a stride below the width. */
 int           omni_jpeg_decode_host(const uint8_t* file, int64_t size, uint8_t* out, int stride, int* width, int* height, int* status);
-/* TEST INFRASTRUCTURE: the CPU stand-in for the kernels (jpeg_decode_parallel_host: the phase functions driven by plain loops) with subseq_bits per subsequence;
- * stats[4] = subsequences, their length, relaxation rounds that changed something, subsequences whose first-pass exit state was wrong */
+/* TEST INFRASTRUCTURE: the CPU stand-in for the kernels (csrc/jpeg_dec_plan.h decode_planned_host: the phase functions driven by plain loops over the picture's
+ * interval table and chunk bounds, as the kernels see it) under the switches of each of three entries.  This one: both switches off, one chunk, subseq_bits per
+ * subsequence; stats[4] = subsequences, their length, relaxation rounds that changed something, subsequences whose first-pass exit state was wrong
+ * (wrong_after_first) */
 int           omni_jpeg_decode_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, uint8_t* out, int stride, int* width, int* height, int* status,
                                              int* stats);
 /* TEST INFRASTRUCTURE: the CPU stand-in for the kernels of a handle with OMNI_JPEGDEC_RESTART_WGS = restart_wgs (1..64), where a workgroup holds at most max_subseq
- * subsequences (the kernels: 4096): the chunk plan and the same phase functions by plain loops (jpeg_decode_restart_parallel_host).  A file without a restart
+ * subsequences (the kernels: 4096): decode_planned_host over the chunk plan's interval table and chunks.  A file without a restart
  * interval goes the way of omni_jpeg_decode_parallel_host.  stats[4] = subsequences, their length, chunks, the maximum over the chunks of the relaxation rounds
  * that changed something (0 0 0 0 for a file the plan leaves to the host) */
 int           omni_jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int restart_wgs, int max_subseq, uint8_t* out, int stride,
                                                      int* width, int* height, int* status, int* stats);
 /* TEST INFRASTRUCTURE: the CPU stand-in for the kernels of a handle with OMNI_JPEGDEC_PLAIN_WGS = plain_wgs (1..64), where a workgroup holds at most max_subseq
- * subsequences (the kernels: 4096): the chunk partition, the chunk relaxation, the seam relaxation and the same phase functions by plain loops
- * (jpeg_decode_plain_parallel_host).  Every file that is not OMNI_JPEGDEC_OK goes the way of omni_jpeg_decode_parallel_host.  stats[7] = subsequences, their
+ * subsequences (the kernels: 4096): decode_planned_host over one interval cut into plain_chunks' chunks -- the chunk relaxation, then the seam
+ * relaxation.  Every file that is not OMNI_JPEGDEC_OK goes the way of omni_jpeg_decode_parallel_host.  stats[7] = subsequences, their
  * length, chunks, the maximum over the chunks of the relaxation rounds that changed something, the seam relaxation's rounds that changed something, the
  * subsequences it changed at least once, the chunks those lie in (all 0 for a file that is not OK) */
 int           omni_jpeg_decode_plain_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int plain_wgs, int max_subseq, uint8_t* out, int stride,

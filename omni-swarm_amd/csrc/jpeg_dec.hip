@@ -30,12 +30,13 @@
 //   unstuff  (OMNI_JPEGDEC_UNSTUFF_DEV = 1, snapshotted by the handle; 0: not launched, nothing allocated) in front of all of them: the scans were uploaded as they
 //            stand in the files, and one workgroup per tile of 4096 raw bytes removes the 0xFF00 stuffing and the restart markers (jpeg_dec_plan.h, unstuff_keep)
 //            from the clean offset the host's survey found for that tile.  NO WORKGROUP WAITS FOR ANOTHER, none reads what another wrote.
-// The host side parses, unstuffs the scans into the handle's pinned block (a planned restart file: + its interval and chunk tables behind its scan) and uploads it once.
-// With OMNI_JPEGDEC_UNSTUFF_DEV = 1 it unstuffs nothing: it surveys the scans' 0xFF bytes (memchr) for the lengths, the restart offsets and the tiles' clean
-// offsets, copies the raw scans into the block (descriptors | jobs + tile tables | restart tables | host-decoded pixels | raw scans) and uploads that.
+// The host side is jpeg_dec_pack.h's, plain C++ that knows nothing of this file: pack_room sizes a handle's block, pack_parse parses and classifies a batch (and
+// refuses it before anything is touched), pack_fill plans every picture and writes the block in one of two layouts (clean scans in upload order; or raw scans with
+// the clean areas behind the upload), and a PackResult tells jpegdec_launch the upload's size and the grids.  Here: wait for the last upload, upload once, launch.
 // Everything runs on the caller's stream.
 #include "common.h"
 #include "config.h"
+#include "jpeg_dec_pack.h"
 #include "jpeg_dec_plan.h"
 
 #define JD_THREADS 256
@@ -44,41 +45,28 @@ static_assert(JD_MAX_SUBSEQ == 16 * JD_THREADS, "16 subsequences per lane: the l
 
 struct omni_jpegdec {
     omni_ctx* ctx = nullptr;
-    int w = 0, h = 0, max_images = 0, subseq_bits = 0, restart_wgs = 0, plain_wgs = 0;
-    int64_t capacity = 0;
-    uint32_t nyb_max = 0;                  // blocks of the first component of a w x h picture with 16 x 16 MCUs
-    size_t in_bytes = 0, tab_bytes = 0;    // tab_bytes: room for one picture's interval and chunk tables (restart_wgs >= 1)
+    omni::jd::PackConfig cfg;              // the picture size, the batch, the capacity and the four switches, snapshotted
+    omni::jd::PackRoom room;               // what pack_room makes of them: the block's size and the kernels' bounds
     omni::DevMem mem;
-    uint8_t* d_in = nullptr;               // the uploaded block: descriptors | clean scans | host-decoded pixels
+    uint8_t* d_in = nullptr;               // the uploaded block (jpeg_dec_pack.h: the two layouts); unstuff_dev: OMNI_JPEGDEC_GUARD_BYTES of 0xA5 behind the last
+                                           // clean area in use
     int16_t* d_coef = nullptr;             // [max_images][nyb_max][64] + guard
     int32_t* d_dc = nullptr;               // [max_images][nyb_max] + guard
     int* d_flags = nullptr;                // [flag_words][max_images]: error bits, relaxation rounds, chunks that ran (plain_wgs >= 2: + seam rounds, subsequences
                                            // the seam relaxation changed) -- zeroed in front of every entropy launch
     int flag_words = 3;
     uint8_t* d_state = nullptr;            // plain_wgs >= 2: counts u32 | exit states u16 | entries used u16, each [max_images][state_cap], + guard
-    uint32_t state_cap = 0;                // plain_wgs * JD_MAX_SUBSEQ: subsequences of a spread picture, at most
     omni::HostBuf hin;
     hipEvent_t ev_upload = nullptr;        // the pinned block is free again
     hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};      // in front of the upload, behind it, behind the kernels (omni_jpegdec_last_ms)
-    size_t last_bytes = 0;
     bool timed = false;                    // ev_t hold ONE call's three events
-    int last_n = 0, last_chunks = 1;       // last_chunks: the most chunks of a picture of the last pack (the entropy kernel's grid)
-    int last_spread_chunks = 0;            // ... of a picture that takes the spread path (the chunk kernel's grid; 0: none does, nothing more is launched)
-    uint32_t last_spread_sub = 0;          // ... and the most subsequences of one (the write kernel's grid)
-    bool last_unspread = true;             // a picture of the last pack is decoded by the entropy kernel
-    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: the uploaded block is descriptors | unstuff jobs + tile tables | interval and chunk tables | host-decoded pixels | RAW scans,
-    // the clean scans (Desc::dev_off) lie behind it and are written by jpegdec_unstuff_kernel, OMNI_JPEGDEC_GUARD_BYTES of 0xA5 behind the last of them
-    int unstuff_dev = 0;
-    size_t jobs_off = 0;                   // of the last pack: where its jobs stand in the block,
-    int last_jobs = 0;                     // ... their number (the pictures whose scan the device unstuffs), the most tiles of one,
-    int64_t last_job_tiles = 0, last_raw = 0, last_clean = 0;      // ... and the raw bytes uploaded for them / the clean bytes they become
-    size_t last_clean_end = 0;             // the end of the last clean area: the guard's place
+    int last_n = 0;
+    omni::jd::PackBatch batch;             // the last pack's descriptors as parsed (kept for its allocations)
+    omni::jd::PackResult pack;             // what the last pack_fill wrote: the upload's size and the grids of jpegdec_launch
     std::mutex mu;
 };
 
 namespace omni {
-
-static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // exclusive scan of one value per lane over a workgroup of kThreads (mod 2^32); *total = the sum.  lds: kThreads / 64 + 1 words, free again on return
 template <int kThreads>
@@ -506,210 +494,51 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_unstuff_kernel(uint8_t* bl
 
 // The stage on `stream`; the caller holds d->mu, has checked the arguments, and d_in holds the block of n_images images
 static int jpegdec_launch(omni_jpegdec* d, hipStream_t stream, int n_images, uint8_t* out_dev, int out_stride, int* status_dev) {
-    if (d->unstuff_dev) {                                                                   // the raw scans -> the clean areas behind the uploaded range, and the guard behind those
-        OMNI_HIP_TRY(hipMemsetAsync(d->d_in + d->last_clean_end, 0xA5, OMNI_JPEGDEC_GUARD_BYTES, stream));
-        if (d->last_jobs) {
-            hipLaunchKernelGGL(jpegdec_unstuff_kernel, dim3((unsigned)d->last_job_tiles, (unsigned)d->last_jobs), dim3(JD_THREADS), 0, stream, d->d_in, (int64_t)d->jobs_off,
-                               (int64_t)d->last_clean_end);
+    if (d->cfg.unstuff_dev) {                                                               // the raw scans -> the clean areas behind the uploaded range, and the guard behind those
+        OMNI_HIP_TRY(hipMemsetAsync(d->d_in + d->pack.clean_end, 0xA5, OMNI_JPEGDEC_GUARD_BYTES, stream));
+        if (d->pack.n_jobs) {
+            hipLaunchKernelGGL(jpegdec_unstuff_kernel, dim3((unsigned)d->pack.job_tiles, (unsigned)d->pack.n_jobs), dim3(JD_THREADS), 0, stream, d->d_in,
+                               (int64_t)d->pack.jobs_off, (int64_t)d->pack.clean_end);
             OMNI_LAUNCH_CHECK();
         }
     }
-    OMNI_HIP_TRY(hipMemsetAsync(d->d_coef, 0, (size_t)n_images * d->nyb_max * 64 * sizeof(int16_t), stream));
-    OMNI_HIP_TRY(hipMemsetAsync(d->d_dc, 0, (size_t)n_images * d->nyb_max * sizeof(int32_t), stream));
-    OMNI_HIP_TRY(hipMemsetAsync(d->d_flags, 0, (size_t)d->flag_words * d->max_images * sizeof(int), stream));
-    if (d->last_unspread) {                                                                 // (always, unless OMNI_JPEGDEC_PLAIN_WGS spread every picture of the batch)
-        hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(d->last_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->nyb_max, d->d_flags,
-                           d->max_images);
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_coef, 0, (size_t)n_images * d->room.nyb_max * 64 * sizeof(int16_t), stream));
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_dc, 0, (size_t)n_images * d->room.nyb_max * sizeof(int32_t), stream));
+    OMNI_HIP_TRY(hipMemsetAsync(d->d_flags, 0, (size_t)d->flag_words * d->cfg.max_images * sizeof(int), stream));
+    if (d->pack.unspread) {                                                                 // (always, unless OMNI_JPEGDEC_PLAIN_WGS spread every picture of the batch)
+        hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(d->pack.max_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc, d->room.nyb_max, d->d_flags,
+                           d->cfg.max_images);
         OMNI_LAUNCH_CHECK();
     }
-    if (d->last_spread_chunks) {                                                            // pictures without a restart interval over several workgroups
-        const size_t subs = (size_t)d->max_images * d->state_cap;
+    if (d->pack.spread_chunks) {                                                            // pictures without a restart interval over several workgroups
+        const size_t subs = (size_t)d->cfg.max_images * d->room.state_cap;
         JdState st{reinterpret_cast<uint32_t*>(d->d_state), reinterpret_cast<uint16_t*>(d->d_state + subs * 4), reinterpret_cast<uint16_t*>(d->d_state + subs * 6),
-                   d->state_cap};
-        hipLaunchKernelGGL(jpegdec_chunk_kernel, dim3(d->last_spread_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, st, d->d_flags, d->max_images);
+                   d->room.state_cap};
+        hipLaunchKernelGGL(jpegdec_chunk_kernel, dim3(d->pack.spread_chunks, n_images), dim3(JD_THREADS), 0, stream, d->d_in, st, d->d_flags, d->cfg.max_images);
         OMNI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(jpegdec_seam_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, st.cnt, st.ex, st.used, st.cap, d->d_flags, d->max_images);
+        hipLaunchKernelGGL(jpegdec_seam_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, st.cnt, st.ex, st.used, st.cap, d->d_flags, d->cfg.max_images);
         OMNI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(jpegdec_write_kernel, dim3(cdiv((int)d->last_spread_sub, JD_THREADS), n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc,
-                           d->nyb_max, st.cnt, st.used, st.cap, d->d_flags);
+        hipLaunchKernelGGL(jpegdec_write_kernel, dim3(cdiv((int)d->pack.spread_sub, JD_THREADS), n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc,
+                           d->room.nyb_max, st.cnt, st.used, st.cap, d->d_flags);
         OMNI_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_dc, d->nyb_max, d->d_flags, status_dev);
+    hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(n_images), dim3(JD_THREADS), 0, stream, d->d_in, d->d_dc, d->room.nyb_max, d->d_flags, status_dev);
     OMNI_LAUNCH_CHECK();
-    const int raster = cdiv(d->w, 8) * cdiv(d->h, 8);
-    const int per_image = (int)d->nyb_max > raster ? (int)d->nyb_max : raster;
+    const int raster = cdiv(d->cfg.w, 8) * cdiv(d->cfg.h, 8);
+    const int per_image = (int)d->room.nyb_max > raster ? (int)d->room.nyb_max : raster;
     hipLaunchKernelGGL(jpegdec_block_kernel, dim3(cdiv(per_image, JD_BLOCK_THREADS), n_images), dim3(JD_BLOCK_THREADS), 0, stream, d->d_in, d->d_coef, d->d_dc,
-                       d->nyb_max, status_dev, d->w, d->h, out_dev, (int64_t)out_stride);
+                       d->room.nyb_max, status_dev, d->cfg.w, d->cfg.h, out_dev, (int64_t)out_stride);
     OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 
-// Parses the files and fills the handle's pinned block: descriptors | clean scans | host-decoded pixels.  *bytes = what has to be uploaded.  Nothing is touched
-// when a file is refused.
-// OMNI_JPEGDEC_UNSTUFF_DEV = 1: wherever the loop below would unstuff a scan into the block it surveys it instead (jd::survey: the 0xFF bytes alone) and notes a
-// job; the block is laid out behind the loop -- descriptors | jobs + tile tables | interval and chunk tables | host-decoded pixels | raw scans (memcpy) -- and
-// the clean areas the descriptors point to follow the uploaded range.  The classification, the plans and every statistic are what they are with the switch off
-static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int64_t* sizes, int n_images, size_t* bytes) {
-    std::vector<jd::Desc> descs((size_t)n_images);
-    for (int i = 0; i < n_images; ++i) {
-        OMNI_REQUIRE(files[i] && sizes[i] >= 0, OMNI_ERR_INVALID, "omni_jpegdec: file %d is null", i);
-        jd::Desc& D = descs[(size_t)i];
-        const int st = jd::parse(files[i], sizes[i], &D);
-        OMNI_REQUIRE(st != OMNI_JPEGDEC_UNSUPPORTED, OMNI_ERR_INVALID, "omni_jpegdec: file %d is not a baseline JPEG of 1 or 3 components (UNSUPPORTED)", i);
-        OMNI_REQUIRE((D.w == d->w && D.h == d->h) || (st == OMNI_JPEGDEC_CORRUPT && D.w == 0), OMNI_ERR_INVALID,
-                     "omni_jpegdec: file %d holds a picture of %dx%d, the handle decodes %dx%d", i, D.w, D.h, d->w, d->h);
-        if (st == OMNI_JPEGDEC_OK && (sizes[i] > d->capacity || D.n_yblocks > d->nyb_max)) D.status = OMNI_JPEGDEC_HOST;
-    }
+// Parses the files and fills the handle's pinned block (jpeg_dec_pack.h: pack_parse, pack_fill -> d->pack).  The parse overlaps the last upload; nothing is
+// touched when a file is refused
+static int jpegdec_pack(omni_jpegdec* d, const uint8_t* const* files, const int64_t* sizes, int n_images) {
+    jd::PackRefusal no;
+    if (jd::pack_parse(d->cfg, d->room, files, sizes, n_images, &d->batch, &no)) { set_error("%s", no.message.c_str()); return no.code; }
     if (d->ev_upload) OMNI_HIP_TRY(hipEventSynchronize(d->ev_upload));                        // the last upload has left the pinned block
-    uint8_t* base = d->hin.as<uint8_t>();
-    size_t at = align16((size_t)n_images * sizeof(jd::Desc));
-    int max_chunks = 1, spread_chunks = 0;
-    uint32_t spread_sub = 0;
-    bool unspread = d->plain_wgs < 2;                                                       // (switch off: the entropy kernel is launched whatever the batch holds)
-    jd::ChunkPlan plan;
-    std::vector<int64_t> rst;
-    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: what the loop notes instead of writing into the block
-    const bool dev = d->unstuff_dev != 0;
-    struct Pending { int img; int64_t raw_end, n_clean; size_t first_tile, n_tiles; };
-    std::vector<Pending> jobs;
-    std::vector<uint32_t> tiles;                                                            // the jobs' tile tables, one behind the other
-    std::vector<uint8_t> tabs;                                                              // the planned restart files' tables, each 16-aligned (Desc::tab_off: inside it)
-    std::vector<int> host_pictures;
-    // the clean bytes of picture i's scan: unstuffed into the block at `at` -- or surveyed, its tile table appended to `tiles`
-    auto clean_scan = [&](int i, int64_t* rst_out, int64_t max_rst, int64_t* n_rst, Pending* job) -> int64_t {
-        const jd::Desc& D = descs[(size_t)i];
-        if (!dev) return jd::unstuff(files[i] + D.scan_off, D.scan_bytes, base + at, rst_out, max_rst, n_rst);
-        const size_t first = tiles.size(), room = (size_t)(D.scan_bytes / JD_UNSTUFF_TILE + 1);
-        tiles.resize(first + room);
-        const jd::Survey v = jd::survey(files[i] + D.scan_off, D.scan_bytes, tiles.data() + first, (int64_t)room, rst_out, max_rst);
-        if (n_rst) *n_rst = v.n_rst;
-        *job = Pending{i, v.raw_end, v.n_clean, first, (size_t)v.n_tiles};
-        return v.n_clean;
-    };
-    // ... and the scan is the kernels' to decode: the table stays (a scan that is not: dropped)
-    auto keep_job = [&](const Pending& job, bool keep) {
-        if (!dev) return;
-        tiles.resize(job.first_tile + (keep ? job.n_tiles : 0));
-        if (keep) jobs.push_back(job);
-    };
-    for (int i = 0; i < n_images; ++i) {
-        jd::Desc& D = descs[(size_t)i];
-        D.dev_off = (int64_t)at;
-        // (intervals: every one costs a subsequence and 16 bytes of table -- a file that cannot be planned for that alone is not unstuffed twice)
-        const size_t n_int = D.restart_only ? ((size_t)D.mcus_x * D.mcus_y + D.restart - 1) / D.restart : 0;
-        if (d->restart_wgs && D.status == OMNI_JPEGDEC_HOST && D.restart_only && sizes[i] <= d->capacity && D.n_yblocks <= d->nyb_max &&
-            n_int <= (size_t)d->restart_wgs * JD_MAX_SUBSEQ && (n_int + 1) * sizeof(jd::Interval) + ((size_t)d->restart_wgs + 1) * sizeof(uint32_t) <= d->tab_bytes) {
-            // the restart interval is the file's only obstacle: its scan with the markers' offsets, the chunk plan, the tables behind the scan.  Too few markers:
-            // CORRUPT; a plan that cannot be made, or tables above the handle's room for them: the file stays HOST (below)
-            rst.resize((size_t)(D.scan_bytes / 2 + 1));
-            int64_t n_rst = 0;
-            Pending job{};
-            const int64_t n = clean_scan(i, rst.data(), (int64_t)rst.size(), &n_rst, &job);
-            jd::plan_chunks(D, n, rst.data(), n_rst, (uint32_t)d->subseq_bits, (uint32_t)d->restart_wgs, JD_MAX_SUBSEQ, &plan);
-            const bool planned = plan.status == OMNI_JPEGDEC_OK && plan.table_bytes() <= d->tab_bytes;
-            keep_job(job, planned);
-            if (plan.status == OMNI_JPEGDEC_CORRUPT) {
-                D.status = OMNI_JPEGDEC_CORRUPT;
-            } else if (planned) {
-                const size_t scan_bytes = align16((size_t)n + JD_SCAN_PAD);
-                if (dev) {                                                                  // (both offsets are moved to their place behind the loop)
-                    D.tab_off = (int64_t)tabs.size();
-                    tabs.resize(tabs.size() + align16(plan.table_bytes()));
-                    plan.store(tabs.data() + D.tab_off);
-                } else {
-                    plan.store(base + at + scan_bytes);
-                    D.tab_off = (int64_t)(at + scan_bytes);
-                }
-                D.status = OMNI_JPEGDEC_OK;
-                D.mode = jd::JD_MODE_DECODE;
-                D.total_bits = (uint32_t)(n * 8);
-                D.subseq_bits = plan.subseq_bits;
-                D.n_sub = plan.n_sub;
-                D.n_int = plan.n_int;
-                D.n_chunks = plan.n_chunks;
-                if ((int)plan.n_chunks > max_chunks) max_chunks = (int)plan.n_chunks;
-                unspread = true;
-                if (!dev) at += scan_bytes + align16(plan.table_bytes());
-                continue;
-            }
-        }
-        if (D.status == OMNI_JPEGDEC_OK) {
-            Pending job{};
-            const int64_t n = clean_scan(i, nullptr, 0, nullptr, &job);
-            keep_job(job, true);
-            D.mode = jd::JD_MODE_DECODE;
-            D.total_bits = (uint32_t)(n * 8);
-            D.subseq_bits = d->plain_wgs >= 2 ? jd::plain_subseq_bits(D.total_bits, (uint32_t)d->subseq_bits, (uint32_t)d->plain_wgs, JD_MAX_SUBSEQ)
-                                              : jd::subseq_bits_for(D.total_bits, (uint32_t)d->subseq_bits, JD_MAX_SUBSEQ);
-            D.n_sub = (D.total_bits + D.subseq_bits - 1) / D.subseq_bits;
-            const uint32_t C = d->plain_wgs >= 2 ? jd::plain_chunks(D.n_sub, (uint32_t)d->plain_wgs) : 1u;
-            if (C >= 2 && D.n_sub <= d->state_cap) {                                        // the spread path; one chunk is the entropy kernel's, as ever
-                D.mode = jd::JD_MODE_SPREAD;
-                D.spread_chunks = C;
-                if ((int)C > spread_chunks) spread_chunks = (int)C;
-                if (D.n_sub > spread_sub) spread_sub = D.n_sub;
-            } else {
-                unspread = true;
-            }
-            if (!dev) at += align16((size_t)n + JD_SCAN_PAD);
-        } else if (D.status == OMNI_JPEGDEC_HOST && dev) {
-            host_pictures.push_back(i);                                                     // (decoded behind the loop, where its pixels' place is known)
-        } else if (D.status == OMNI_JPEGDEC_HOST) {
-            const int st = jd::decode_sequential(files[i], D, base + at, d->w);
-            D.status = st;
-            D.mode = st == OMNI_JPEGDEC_CORRUPT ? jd::JD_MODE_ZERO : jd::JD_MODE_PIXELS;
-            if (D.mode == jd::JD_MODE_PIXELS) at += align16((size_t)d->w * d->h);
-        } else {
-            D.mode = jd::JD_MODE_ZERO;
-        }
-    }
-    if (dev) {
-        // the layout: everything but the pixels and the scans themselves has its size by now, and the handle was made for the largest of each
-        const size_t jobs_off = at, tiles_off = jobs_off + align16(jobs.size() * sizeof(jd::UnstuffJob)), tabs_off = tiles_off + align16(tiles.size() * sizeof(uint32_t));
-        size_t need = tabs_off + tabs.size() + host_pictures.size() * align16((size_t)d->w * d->h);
-        for (const Pending& j : jobs) need += align16((size_t)j.raw_end) + align16((size_t)j.n_clean + JD_SCAN_PAD);
-        OMNI_REQUIRE(need <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: a block of %zu bytes, the handle holds %zu", need, d->in_bytes);
-        at = tabs_off + tabs.size();
-        if (!tiles.empty()) memcpy(base + tiles_off, tiles.data(), tiles.size() * sizeof(uint32_t));
-        if (!tabs.empty()) memcpy(base + tabs_off, tabs.data(), tabs.size());
-        for (int i : host_pictures) {
-            jd::Desc& D = descs[(size_t)i];
-            D.dev_off = (int64_t)at;
-            const int st = jd::decode_sequential(files[i], D, base + at, d->w);
-            D.status = st;
-            D.mode = st == OMNI_JPEGDEC_CORRUPT ? jd::JD_MODE_ZERO : jd::JD_MODE_PIXELS;
-            if (D.mode == jd::JD_MODE_PIXELS) at += align16((size_t)d->w * d->h);
-        }
-        jd::UnstuffJob* J = reinterpret_cast<jd::UnstuffJob*>(base + jobs_off);
-        int64_t most_tiles = 0, raw_total = 0, clean_total = 0;
-        for (size_t k = 0; k < jobs.size(); ++k) {                                          // the scans as they stand in the files, zero-padded to a multiple of 16
-            const Pending& j = jobs[k];
-            const size_t room = align16((size_t)j.raw_end);
-            if (j.raw_end) memcpy(base + at, files[j.img] + descs[(size_t)j.img].scan_off, (size_t)j.raw_end);
-            memset(base + at + j.raw_end, 0, room - (size_t)j.raw_end);
-            J[k].raw_off = (int64_t)at; J[k].raw_bytes = j.raw_end; J[k].clean_bytes = j.n_clean;
-            J[k].tile_off = (int64_t)(tiles_off + j.first_tile * sizeof(uint32_t));
-            at += room;
-            if ((int64_t)j.n_tiles > most_tiles) most_tiles = (int64_t)j.n_tiles;
-            raw_total += j.raw_end; clean_total += j.n_clean;
-        }
-        size_t clean_at = at;                                                               // behind the uploaded range: the clean areas, the kernel's to write
-        for (size_t k = 0; k < jobs.size(); ++k) {
-            jd::Desc& D = descs[(size_t)jobs[k].img];
-            J[k].clean_off = D.dev_off = (int64_t)clean_at;
-            if (D.n_int) D.tab_off += (int64_t)tabs_off;
-            clean_at += align16((size_t)jobs[k].n_clean + JD_SCAN_PAD);
-        }
-        d->jobs_off = jobs_off; d->last_jobs = (int)jobs.size(); d->last_job_tiles = most_tiles; d->last_raw = raw_total; d->last_clean = clean_total;
-        d->last_clean_end = clean_at;
-    }
-    OMNI_REQUIRE(at <= d->in_bytes, OMNI_ERR_CAPACITY, "omni_jpegdec: %zu bytes to upload, the handle holds %zu", at, d->in_bytes);
-    memcpy(base, descs.data(), (size_t)n_images * sizeof(jd::Desc));
-    d->last_chunks = max_chunks;
-    d->last_spread_chunks = spread_chunks;
-    d->last_spread_sub = spread_sub;
-    d->last_unspread = unspread;
-    *bytes = at;
+    if (jd::pack_fill(d->cfg, d->room, d->batch, files, d->hin.as<uint8_t>(), &d->pack, &no)) { set_error("%s", no.message.c_str()); return no.code; }
     return OMNI_OK;
 }
 
@@ -719,7 +548,7 @@ extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int heigh
     using namespace omni;
     if (!ctx) { set_error("null context"); return nullptr; }
     if (width < 1 || height < 1 || width > 65535 || height > 65535) { set_error("omni_jpegdec_create: %dx%d outside 1..65535", width, height); return nullptr; }
-    const int64_t nyb = (int64_t)cdiv(width, 16) * cdiv(height, 16) * 4;
+    const int64_t nyb = jd::pack_nyb(width, height);
     if (nyb > (1 << 20)) { set_error("omni_jpegdec_create: %dx%d is more than 2^20 blocks", width, height); return nullptr; }
     if (max_images < 1 || max_images > 65535) { set_error("omni_jpegdec_create: max_images=%d outside [1, 65535]", max_images); return nullptr; }
     if (capacity_per_image < 1024 || capacity_per_image > (1 << 28)) {
@@ -734,41 +563,31 @@ extern "C" omni_jpegdec* omni_jpegdec_create(omni_ctx* ctx, int width, int heigh
     std::lock_guard<std::mutex> lk(ctx->mu);
     (void)hipSetDevice(ctx->device);
     omni_jpegdec* d = new omni_jpegdec();
-    d->ctx = ctx; d->w = width; d->h = height; d->max_images = max_images; d->capacity = capacity_per_image; d->subseq_bits = S; d->restart_wgs = W; d->plain_wgs = PW; d->nyb_max = (uint32_t)nyb;
-    // per image: a descriptor and the larger of a clean scan and the picture itself
-    const size_t per_scan = align16((size_t)capacity_per_image + JD_SCAN_PAD), per_px = align16((size_t)width * height);
-    // ... and, with OMNI_JPEGDEC_RESTART_WGS on, its interval and chunk tables: one interval per MCU of 8 x 8 at the most, and no more than W chunks hold
-    if (W) {
-        const size_t mcus = (size_t)cdiv(width, 8) * cdiv(height, 8), planned = (size_t)W * JD_MAX_SUBSEQ;
-        d->tab_bytes = align16(((mcus < planned ? mcus : planned) + 1) * sizeof(jd::Interval) + ((size_t)W + 1) * sizeof(uint32_t));
-    }
-    d->in_bytes = align16((size_t)max_images * sizeof(jd::Desc)) + (size_t)max_images * ((per_scan > per_px ? per_scan : per_px) + d->tab_bytes);
-    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: + per image its raw scan next to its clean one, a job and a tile table; the guard stands behind the last clean area in use
-    d->unstuff_dev = cfg[CFG_JPEGDEC_UNSTUFF_DEV];
-    if (d->unstuff_dev) {
-        const size_t tile_tab = ((size_t)capacity_per_image / JD_UNSTUFF_TILE + 2) * sizeof(uint32_t);
-        d->in_bytes += (size_t)max_images * (align16((size_t)capacity_per_image) + 16) + align16((size_t)max_images * sizeof(jd::UnstuffJob)) + align16((size_t)max_images * tile_tab);
-        d->last_clean_end = d->in_bytes;
-    }
-    const size_t in_guard = d->unstuff_dev ? OMNI_JPEGDEC_GUARD_BYTES : 0;
+    d->ctx = ctx;
+    d->cfg.w = width; d->cfg.h = height; d->cfg.max_images = max_images; d->cfg.capacity = capacity_per_image;
+    d->cfg.subseq_bits = S; d->cfg.restart_wgs = W; d->cfg.plain_wgs = PW; d->cfg.unstuff_dev = cfg[CFG_JPEGDEC_UNSTUFF_DEV];
+    d->room = jd::pack_room(d->cfg);
+    // OMNI_JPEGDEC_UNSTUFF_DEV = 1: the guard stands behind the last clean area in use
+    if (d->cfg.unstuff_dev) d->pack.clean_end = d->room.in_bytes;
+    const size_t in_guard = d->cfg.unstuff_dev ? OMNI_JPEGDEC_GUARD_BYTES : 0;
     const size_t coef_bytes = (size_t)max_images * nyb * 64 * sizeof(int16_t), dc_bytes = (size_t)max_images * nyb * sizeof(int32_t);
     // OMNI_JPEGDEC_PLAIN_WGS >= 2: the state arrays of the spread path (8 bytes per subsequence) and two more flag words per picture; otherwise neither
-    if (PW >= 2) { d->state_cap = (uint32_t)PW * JD_MAX_SUBSEQ; d->flag_words = 5; }
-    const size_t state_bytes = (size_t)max_images * d->state_cap * 8;
+    if (PW >= 2) d->flag_words = 5;
+    const size_t state_bytes = (size_t)max_images * d->room.state_cap * 8;
     auto make = [&]() -> int {
         int rc;
-        if ((rc = d->mem.alloc(&d->d_in, d->in_bytes + in_guard)) ||(rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
+        if ((rc = d->mem.alloc(&d->d_in, d->room.in_bytes + in_guard)) ||(rc = d->mem.alloc(&d->d_coef, coef_bytes + OMNI_JPEGDEC_GUARD_BYTES)) ||
             (rc = d->mem.alloc(&d->d_dc, dc_bytes + OMNI_JPEGDEC_GUARD_BYTES)) || (rc = d->mem.alloc(&d->d_flags, (size_t)d->flag_words * max_images * sizeof(int))))
             return rc;
         if (state_bytes) {
             if ((rc = d->mem.alloc(&d->d_state, state_bytes + OMNI_JPEGDEC_GUARD_BYTES))) return rc;
             OMNI_HIP_TRY(hipMemset(d->d_state + state_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         }
-        if (in_guard) OMNI_HIP_TRY(hipMemset(d->d_in + d->in_bytes, 0xA5, in_guard));
+        if (in_guard) OMNI_HIP_TRY(hipMemset(d->d_in + d->room.in_bytes, 0xA5, in_guard));
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_coef) + coef_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         OMNI_HIP_TRY(hipMemset(reinterpret_cast<uint8_t*>(d->d_dc) + dc_bytes, 0xA5, OMNI_JPEGDEC_GUARD_BYTES));
         OMNI_HIP_TRY(hipMemset(d->d_flags, 0, (size_t)d->flag_words * max_images * sizeof(int)));
-        if ((rc = d->hin.ensure(d->in_bytes))) return rc;
+        if ((rc = d->hin.ensure(d->room.in_bytes))) return rc;
         OMNI_HIP_TRY(hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming));
         for (hipEvent_t& e : d->ev_t) OMNI_HIP_TRY(hipEventCreate(&e));
         return OMNI_OK;
@@ -802,20 +621,18 @@ namespace omni {
 int jpegdec_enqueue_on(omni_jpegdec* d, hipStream_t stream, const uint8_t* const* files, const int64_t* sizes, int n_images, uint8_t* out_dev, int out_stride,
                        int* status_dev) {
     OMNI_REQUIRE(d && files && sizes && out_dev && status_dev, OMNI_ERR_INVALID, "null argument");
-    OMNI_REQUIRE(n_images >= 1 && n_images <= d->max_images, OMNI_ERR_INVALID, "omni_jpegdec: %d images, the handle holds 1..%d", n_images, d->max_images);
-    OMNI_REQUIRE(out_stride >= d->w, OMNI_ERR_INVALID, "omni_jpegdec: out_stride %d for pictures %d wide", out_stride, d->w);
+    OMNI_REQUIRE(n_images >= 1 && n_images <= d->cfg.max_images, OMNI_ERR_INVALID, "omni_jpegdec: %d images, the handle holds 1..%d", n_images, d->cfg.max_images);
+    OMNI_REQUIRE(out_stride >= d->cfg.w, OMNI_ERR_INVALID, "omni_jpegdec: out_stride %d for pictures %d wide", out_stride, d->cfg.w);
     std::lock_guard<std::mutex> lk(d->mu);
     (void)hipSetDevice(d->ctx->device);
-    size_t bytes = 0;
     int rc;
-    if ((rc = jpegdec_pack(d, files, sizes, n_images, &bytes))) return rc;
+    if ((rc = jpegdec_pack(d, files, sizes, n_images))) return rc;
     d->timed = false;                                                                       // (until this call's three events are all recorded)
     OMNI_HIP_TRY(hipEventRecord(d->ev_t[0], stream));
-    OMNI_HIP_TRY(hipMemcpyAsync(d->d_in, d->hin.p, bytes, hipMemcpyHostToDevice, stream));
+    OMNI_HIP_TRY(hipMemcpyAsync(d->d_in, d->hin.p, d->pack.upload_bytes, hipMemcpyHostToDevice, stream));
     OMNI_HIP_TRY(hipEventRecord(d->ev_upload, stream));
     OMNI_HIP_TRY(hipEventRecord(d->ev_t[1], stream));
     d->last_n = n_images;
-    d->last_bytes = bytes;
     if ((rc = jpegdec_launch(d, stream, n_images, out_dev, out_stride, status_dev))) return rc;
     OMNI_HIP_TRY(hipEventRecord(d->ev_t[2], stream));
     d->timed = true;
@@ -838,7 +655,7 @@ extern "C" int omni_jpegdec_last_ms(omni_jpegdec* d, float* upload_ms, float* ke
     OMNI_HIP_TRY(hipEventSynchronize(d->ev_t[2]));
     OMNI_HIP_TRY(hipEventElapsedTime(upload_ms, d->ev_t[0], d->ev_t[1]));
     OMNI_HIP_TRY(hipEventElapsedTime(kernels_ms, d->ev_t[1], d->ev_t[2]));
-    *uploaded_bytes = (int64_t)d->last_bytes;
+    *uploaded_bytes = (int64_t)d->pack.upload_bytes;
     return OMNI_OK;
 }
 
@@ -847,7 +664,7 @@ extern "C" int omni_jpegdec_last_stats(omni_jpegdec* d, int* rounds, int* n_subs
     std::lock_guard<std::mutex> lk(d->mu);
     (void)hipSetDevice(d->ctx->device);
     OMNI_HIP_TRY(hipDeviceSynchronize());                                                     // (the last enqueue may have run on a unit's stream)
-    if (rounds && d->last_n) OMNI_HIP_TRY(hipMemcpy(rounds, d->d_flags + d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+    if (rounds && d->last_n) OMNI_HIP_TRY(hipMemcpy(rounds, d->d_flags + d->cfg.max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
     const omni::jd::Desc* descs = d->hin.as<omni::jd::Desc>();                                // (the pinned block still holds the last enqueue's descriptors)
     for (int i = 0; i < d->last_n; ++i) {
         const bool dec = descs[i].mode == omni::jd::JD_MODE_DECODE || descs[i].mode == omni::jd::JD_MODE_SPREAD;
@@ -862,7 +679,7 @@ extern "C" int omni_jpegdec_last_chunks(omni_jpegdec* d, int* chunks) {
     std::lock_guard<std::mutex> lk(d->mu);
     (void)hipSetDevice(d->ctx->device);
     OMNI_HIP_TRY(hipDeviceSynchronize());
-    if (d->last_n) OMNI_HIP_TRY(hipMemcpy(chunks, d->d_flags + 2 * (size_t)d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+    if (d->last_n) OMNI_HIP_TRY(hipMemcpy(chunks, d->d_flags + 2 * (size_t)d->cfg.max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
     return OMNI_OK;
 }
 
@@ -875,31 +692,31 @@ extern "C" int omni_jpegdec_last_seam(omni_jpegdec* d, int* seam_rounds, int* se
     for (int k = 0; k < 2; ++k) {
         if (!out[k] || !d->last_n) continue;
         if (d->flag_words < 5) memset(out[k], 0, (size_t)d->last_n * sizeof(int));            // (the switch is off: no picture has a seam)
-        else OMNI_HIP_TRY(hipMemcpy(out[k], d->d_flags + (size_t)(3 + k) * d->max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
+        else OMNI_HIP_TRY(hipMemcpy(out[k], d->d_flags + (size_t)(3 + k) * d->cfg.max_images, (size_t)d->last_n * sizeof(int), hipMemcpyDeviceToHost));
     }
     return OMNI_OK;
 }
 
 extern "C" int omni_jpegdec_debug_state_buffer(omni_jpegdec* d, void** state_dev, int64_t* state_bytes) {
     OMNI_REQUIRE(d && state_dev && state_bytes, OMNI_ERR_INVALID, "null argument");
-    *state_dev = d->d_state; *state_bytes = (int64_t)d->max_images * d->state_cap * 8;
+    *state_dev = d->d_state; *state_bytes = (int64_t)d->cfg.max_images * d->room.state_cap * 8;
     return OMNI_OK;
 }
 
 extern "C" int omni_jpegdec_last_unstuff(omni_jpegdec* d, int* device_pictures, int64_t* raw_bytes, int64_t* clean_bytes) {
     OMNI_REQUIRE(d && device_pictures && raw_bytes && clean_bytes, OMNI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(d->mu);
-    *device_pictures = d->unstuff_dev ? d->last_jobs : 0;
-    *raw_bytes = d->unstuff_dev ? d->last_raw : 0;
-    *clean_bytes = d->unstuff_dev ? d->last_clean : 0;
+    *device_pictures = d->cfg.unstuff_dev ? d->pack.n_jobs : 0;
+    *raw_bytes = d->cfg.unstuff_dev ? d->pack.raw_bytes : 0;
+    *clean_bytes = d->cfg.unstuff_dev ? d->pack.clean_bytes : 0;
     return OMNI_OK;
 }
 
 extern "C" int omni_jpegdec_debug_in_buffer(omni_jpegdec* d, void** clean_end_dev, int64_t* guard_bytes) {
     OMNI_REQUIRE(d && clean_end_dev && guard_bytes, OMNI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(d->mu);
-    *clean_end_dev = d->unstuff_dev ? d->d_in + d->last_clean_end : nullptr;
-    *guard_bytes = d->unstuff_dev ? OMNI_JPEGDEC_GUARD_BYTES : 0;
+    *clean_end_dev = d->cfg.unstuff_dev ? d->d_in + d->pack.clean_end : nullptr;
+    *guard_bytes = d->cfg.unstuff_dev ? OMNI_JPEGDEC_GUARD_BYTES : 0;
     return OMNI_OK;
 }
 
@@ -912,8 +729,8 @@ extern "C" int omni_jpegdec_unstuff_dev(omni_ctx* ctx, const uint8_t* scan, int6
     const jd::Survey v = jd::survey(scan, n, tiles.data(), (int64_t)tiles.size(), nullptr, 0);
     OMNI_REQUIRE(out_cap >= v.n_clean + JD_SCAN_PAD, OMNI_ERR_INVALID, "omni_jpegdec_unstuff_dev: room for %lld bytes, %lld clean bytes + %d", (long long)out_cap,
                  (long long)v.n_clean, JD_SCAN_PAD);
-    const size_t tiles_off = align16(sizeof(jd::UnstuffJob)), raw_off = tiles_off + align16((size_t)v.n_tiles * sizeof(uint32_t)), clean_off = raw_off + align16((size_t)v.raw_end);
-    const size_t clean_end = clean_off + align16((size_t)v.n_clean + JD_SCAN_PAD);
+    const size_t tiles_off = jd::pack_align16(sizeof(jd::UnstuffJob)), raw_off = tiles_off + jd::pack_align16((size_t)v.n_tiles * sizeof(uint32_t)), clean_off = raw_off + jd::pack_align16((size_t)v.raw_end);
+    const size_t clean_end = clean_off + jd::pack_align16((size_t)v.n_clean + JD_SCAN_PAD);
     std::vector<uint8_t> host(clean_off, 0);
     const jd::UnstuffJob job{(int64_t)raw_off, v.raw_end, (int64_t)clean_off, v.n_clean, (int64_t)tiles_off};
     memcpy(host.data(), &job, sizeof(job));
@@ -950,7 +767,7 @@ extern "C" int omni_jpegdec_unstuff_dev(omni_ctx* ctx, const uint8_t* scan, int6
 
 extern "C" int omni_jpegdec_debug_buffers(omni_jpegdec* d, void** coef_dev, int64_t* coef_bytes, void** dc_dev, int64_t* dc_bytes) {
     OMNI_REQUIRE(d && coef_dev && coef_bytes && dc_dev && dc_bytes, OMNI_ERR_INVALID, "null argument");
-    *coef_dev = d->d_coef; *coef_bytes = (int64_t)d->max_images * d->nyb_max * 64 * (int64_t)sizeof(int16_t);
-    *dc_dev = d->d_dc; *dc_bytes = (int64_t)d->max_images * d->nyb_max * (int64_t)sizeof(int32_t);
+    *coef_dev = d->d_coef; *coef_bytes = (int64_t)d->cfg.max_images * d->room.nyb_max * 64 * (int64_t)sizeof(int16_t);
+    *dc_dev = d->d_dc; *dc_bytes = (int64_t)d->cfg.max_images * d->room.nyb_max * (int64_t)sizeof(int32_t);
     return OMNI_OK;
 }

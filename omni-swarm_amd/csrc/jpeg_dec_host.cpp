@@ -1,6 +1,6 @@
 // csrc/jpeg_dec_plan.h compiled by g++ into libomni_hip.so: omni_jpegdec_classify / omni_jpeg_decode_host / omni_jpeg_decode_parallel_host /
-// omni_jpeg_decode_restart_parallel_host / omni_jpeg_decode_plain_parallel_host (the stand-ins for a handle that spreads restart-interval files, or files without
-// a restart interval, over workgroups) give host callers and the tests the pixels of the GPU stage (jpeg_dec.hip) without a GPU -- and "what a host decoder would cost" on one thread.
+// omni_jpeg_decode_restart_parallel_host / omni_jpeg_decode_plain_parallel_host (one stand-in for the kernels under three settings of a handle's switches) give
+// host callers and the tests the pixels of the GPU stage (jpeg_dec.hip) without a GPU -- and "what a host decoder would cost" on one thread.
 #include <climits>
 
 #include "jpeg_dec_plan.h"
@@ -32,58 +32,56 @@ extern "C" int omni_jpeg_decode_host(const uint8_t* file, int64_t size, uint8_t*
     return OMNI_OK;
 }
 
-extern "C" int omni_jpeg_decode_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, uint8_t* out, int stride, int* width, int* height, int* status,
-                                              int* stats) {
+// ---- the CPU stand-in for the kernels (jd::decode_planned_host) under the switches of each of its three entries ------------------------------------------------------
+// what all three take, checked once
+static int planned_args(const char* who, const uint8_t* file, int64_t size, int subseq_bits, uint8_t* out, int stride, int* width, int* height, int* status) {
     const int rc = decode_args(file, size, out, stride, width, height, status);
     if (rc) return rc;
     if (subseq_bits < JD_MIN_SUBSEQ_BITS || subseq_bits > JD_MAX_SUBSEQ_BITS || (subseq_bits & (subseq_bits - 1))) {
-        omni::set_error("omni_jpeg_decode_parallel_host: %d bits per subsequence, a power of two in [%d, %d]", subseq_bits, JD_MIN_SUBSEQ_BITS, JD_MAX_SUBSEQ_BITS);
+        omni::set_error("%s: %d bits per subsequence, a power of two in [%d, %d]", who, subseq_bits, JD_MIN_SUBSEQ_BITS, JD_MAX_SUBSEQ_BITS);
         return OMNI_ERR_INVALID;
     }
-    omni::jd::ParallelStats ps;
-    *status = omni::jd::jpeg_decode_parallel_host(file, size, (uint32_t)subseq_bits, 0xffffffffu, out, stride, stride, INT_MAX, width, height, &ps);
-    if (stats) { stats[0] = (int)ps.n_sub; stats[1] = (int)ps.subseq_bits; stats[2] = (int)ps.rounds; stats[3] = (int)ps.wrong_after_first; }
+    return OMNI_OK;
+}
+// ... and the workgroup count of the two entries that have one
+static int wgs_args(const char* who, int wgs, int max_wgs, int max_subseq) {
+    if (wgs >= 1 && wgs <= max_wgs && max_subseq >= 1) return OMNI_OK;
+    omni::set_error("%s: %d workgroups of at most %d subsequences, expected 1..%d and >= 1", who, wgs, max_subseq, max_wgs);
+    return OMNI_ERR_INVALID;
+}
+
+extern "C" int omni_jpeg_decode_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, uint8_t* out, int stride, int* width, int* height, int* status,
+                                              int* stats) {
+    const int rc = planned_args("omni_jpeg_decode_parallel_host", file, size, subseq_bits, out, stride, width, height, status);
+    if (rc) return rc;
+    omni::jd::PlannedStats ps;
+    *status = omni::jd::decode_planned_host(file, size, (uint32_t)subseq_bits, 0u, 0u, 0xffffffffu, out, stride, stride, INT_MAX, width, height, &ps);
+    if (!stats) return OMNI_OK;
+    stats[0] = (int)ps.n_sub; stats[1] = (int)ps.subseq_bits; stats[2] = (int)ps.chunk_rounds;
+    stats[3] = (int)omni::jd::wrong_after_first(file, size, (uint32_t)subseq_bits, 0xffffffffu);
     return OMNI_OK;
 }
 
 extern "C" int omni_jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int restart_wgs, int max_subseq, uint8_t* out, int stride,
                                                       int* width, int* height, int* status, int* stats) {
-    const int rc = decode_args(file, size, out, stride, width, height, status);
-    if (rc) return rc;
-    if (subseq_bits < JD_MIN_SUBSEQ_BITS || subseq_bits > JD_MAX_SUBSEQ_BITS || (subseq_bits & (subseq_bits - 1))) {
-        omni::set_error("omni_jpeg_decode_restart_parallel_host: %d bits per subsequence, a power of two in [%d, %d]", subseq_bits, JD_MIN_SUBSEQ_BITS,
-                        JD_MAX_SUBSEQ_BITS);
-        return OMNI_ERR_INVALID;
-    }
-    if (restart_wgs < 1 || restart_wgs > JD_MAX_RESTART_WGS || max_subseq < 1) {
-        omni::set_error("omni_jpeg_decode_restart_parallel_host: %d workgroups of at most %d subsequences, expected 1..%d and >= 1", restart_wgs, max_subseq,
-                        JD_MAX_RESTART_WGS);
-        return OMNI_ERR_INVALID;
-    }
-    omni::jd::RestartStats rs;
-    *status = omni::jd::jpeg_decode_restart_parallel_host(file, size, (uint32_t)subseq_bits, (uint32_t)restart_wgs, (uint32_t)max_subseq, out, stride, stride, INT_MAX,
-                                                          width, height, &rs);
-    if (stats) { stats[0] = (int)rs.n_sub; stats[1] = (int)rs.subseq_bits; stats[2] = (int)rs.n_chunks; stats[3] = (int)rs.rounds; }
+    const char* who = "omni_jpeg_decode_restart_parallel_host";
+    int rc = planned_args(who, file, size, subseq_bits, out, stride, width, height, status);
+    if (rc || (rc = wgs_args(who, restart_wgs, JD_MAX_RESTART_WGS, max_subseq))) return rc;
+    omni::jd::PlannedStats ps;
+    *status = omni::jd::decode_planned_host(file, size, (uint32_t)subseq_bits, (uint32_t)restart_wgs, 0u, (uint32_t)max_subseq, out, stride, stride, INT_MAX, width,
+                                            height, &ps);
+    if (stats) { stats[0] = (int)ps.n_sub; stats[1] = (int)ps.subseq_bits; stats[2] = (int)ps.n_chunks; stats[3] = (int)ps.chunk_rounds; }
     return OMNI_OK;
 }
 
 extern "C" int omni_jpeg_decode_plain_parallel_host(const uint8_t* file, int64_t size, int subseq_bits, int plain_wgs, int max_subseq, uint8_t* out, int stride,
                                                     int* width, int* height, int* status, int* stats) {
-    const int rc = decode_args(file, size, out, stride, width, height, status);
-    if (rc) return rc;
-    if (subseq_bits < JD_MIN_SUBSEQ_BITS || subseq_bits > JD_MAX_SUBSEQ_BITS || (subseq_bits & (subseq_bits - 1))) {
-        omni::set_error("omni_jpeg_decode_plain_parallel_host: %d bits per subsequence, a power of two in [%d, %d]", subseq_bits, JD_MIN_SUBSEQ_BITS,
-                        JD_MAX_SUBSEQ_BITS);
-        return OMNI_ERR_INVALID;
-    }
-    if (plain_wgs < 1 || plain_wgs > JD_MAX_PLAIN_WGS || max_subseq < 1) {
-        omni::set_error("omni_jpeg_decode_plain_parallel_host: %d workgroups of at most %d subsequences, expected 1..%d and >= 1", plain_wgs, max_subseq,
-                        JD_MAX_PLAIN_WGS);
-        return OMNI_ERR_INVALID;
-    }
-    omni::jd::PlainStats ps;
-    *status = omni::jd::jpeg_decode_plain_parallel_host(file, size, (uint32_t)subseq_bits, (uint32_t)plain_wgs, (uint32_t)max_subseq, out, stride, stride, INT_MAX,
-                                                        width, height, &ps);
+    const char* who = "omni_jpeg_decode_plain_parallel_host";
+    int rc = planned_args(who, file, size, subseq_bits, out, stride, width, height, status);
+    if (rc || (rc = wgs_args(who, plain_wgs, JD_MAX_PLAIN_WGS, max_subseq))) return rc;
+    omni::jd::PlannedStats ps;
+    *status = omni::jd::decode_planned_host(file, size, (uint32_t)subseq_bits, 0u, (uint32_t)plain_wgs, (uint32_t)max_subseq, out, stride, stride, INT_MAX, width, height,
+                                            &ps);
     if (stats) {
         stats[0] = (int)ps.n_sub; stats[1] = (int)ps.subseq_bits; stats[2] = (int)ps.n_chunks; stats[3] = (int)ps.chunk_rounds;
         stats[4] = (int)ps.seam_rounds; stats[5] = (int)ps.seam_changed; stats[6] = (int)ps.seam_chunks;

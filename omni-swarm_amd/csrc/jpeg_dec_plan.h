@@ -56,7 +56,9 @@
 //              first subsequence keeping the guess as its entry -- one workgroup per chunk, none reads what another wrote; then ONE relaxation over all the
 //              picture's subsequences (the SEAM relaxation: only what the seams between chunks got wrong is decoded again) ends in the same fixed point, the
 //              sequential decode; phase 3 is one scan over the picture, phase 4 one subsequence at a time from the stored entry and first block.  Phases 5-6 as
-//              ever.  Same pixels, same status as the one-chunk path for EVERY input (jpeg_decode_plain_parallel_host is the stand-in)
+//              ever.  Same pixels, same status as the one-chunk path for EVERY input
+//   stand-in   decode_planned_host: ONE CPU stand-in for all the kernels' paths, under a handle's two switches.  It sees a picture as they do -- an Interval table
+//              and chunk bounds -- and has one relaxation, one scan, one write pass, one error rule.  jpeg_decode_host and Pillow's pixels share none of its code
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -706,83 +708,7 @@ inline int jpeg_decode_host(const uint8_t* file, int64_t size, uint8_t* out, int
     return decode_sequential(file, d, out, stride);
 }
 
-// what the parallel decoder reports about itself
-struct ParallelStats {
-    uint32_t n_sub = 0, subseq_bits = 0, rounds = 0, wrong_after_first = 0;     // rounds: relaxation rounds that changed something
-};
-// The CPU stand-in for the kernels: the phase functions driven by plain loops, S bits per subsequence (a power of two, at most max_sub subsequences: S is
-// doubled until they fit).  A file with restart intervals goes to the sequential decoder, as on the device.  Same results as jpeg_decode_host.
-inline int jpeg_decode_parallel_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t max_sub, uint8_t* out, int64_t stride, int max_w, int max_h, int* w,
-                                     int* h, ParallelStats* stats) {
-    Desc d;
-    const int st = parse(file, size, &d);
-    if (w) *w = d.w;
-    if (h) *h = d.h;
-    if (!out || st == OMNI_JPEGDEC_UNSUPPORTED) return st;
-    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
-    if (st == OMNI_JPEGDEC_CORRUPT) {
-        zero_picture(out, stride, d.w, d.h);
-        return st;
-    }
-    if (d.restart) return decode_sequential(file, d, out, stride);
-    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
-    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), nullptr, 0, nullptr);
-    const uint32_t total_bits = (uint32_t)(nclean * 8), n_words = scan_words(nclean);
-    S = subseq_bits_for(total_bits, S, max_sub);
-    const uint32_t N = (total_bits + S - 1) / S;
-    std::vector<uint16_t> ex(N), used(N, 0);
-    std::vector<uint32_t> cnt(N), first(N);
-    std::vector<uint8_t> need(N);
-    NoEmit none;
-    int e;
-    for (uint32_t i = 0; i < N; ++i) cnt[i] = decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, 0, 0u, 0xffffffffu, none, &ex[i], &e);      // 1
-    ParallelStats ps;
-    ps.n_sub = N; ps.subseq_bits = S;
-    {                                                                                       // (for the record: how many guesses were wrong)
-        uint16_t prev = 0;
-        for (uint32_t i = 0; i + 1 < N; ++i) {
-            uint16_t x;
-            decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, prev, 0u, 0xffffffffu, none, &x, &e);
-            ps.wrong_after_first += x != ex[i];
-            prev = x;
-        }
-    }
-    for (uint32_t r = 0; r < N; ++r) {                                                      // 2
-        for (uint32_t i = 1; i < N; ++i) {
-            need[i] = ex[i - 1] != used[i];
-            if (need[i]) used[i] = ex[i - 1];
-        }
-        bool changed = false;
-        for (uint32_t i = 1; i < N; ++i) {
-            if (!need[i]) continue;
-            uint16_t x;
-            const uint32_t c = decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, &x, &e);
-            if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = true; }
-        }
-        if (!changed) break;
-        ++ps.rounds;
-    }
-    if (stats) *stats = ps;
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < N; ++i) { first[i] = total; total += cnt[i]; }                 // 3
-    std::vector<int16_t> coef((size_t)d.n_yblocks * 64, 0);
-    std::vector<int32_t> dc(d.n_yblocks, 0);
-    int err = total < d.n_blocks;
-    for (uint32_t i = 0; i < N; ++i) {                                                      // 4
-        CoefEmit em;
-        em.coef = coef.data(); em.dcd = dc.data(); em.n_yblocks = d.n_yblocks;
-        em.start(d.T, first[i], used[i] >> 12);
-        uint16_t x;
-        decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], first[i], d.n_blocks, em, &x, &e);
-        err |= e;
-    }
-    uint32_t run = 0;
-    for (uint32_t y = 0; y < d.n_yblocks; ++y) { run += (uint32_t)dc[y]; dc[y] = (int32_t)run; }      // 5
-    for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
-    return err ? OMNI_JPEGDEC_CORRUPT : d.status;
-}
-
-// ---- restart-interval files over several workgroups: the chunk plan and its CPU stand-in ------------------------------------------------------------------------
+// ---- restart-interval files over several workgroups: the chunk plan ----------------------------------------------------------------------------------------------
 struct ChunkPlan {
     int status = OMNI_JPEGDEC_HOST;                         // OK: planned; HOST: cannot be planned; CORRUPT: fewer restart markers than the picture needs
     uint32_t subseq_bits = 0, n_sub = 0, n_int = 0, n_chunks = 0, max_chunk_sub = 0;
@@ -856,177 +782,142 @@ inline void dc_scan_host(int32_t* dc, uint32_t n, uint32_t seg) {
     }
 }
 
-struct RestartStats {
-    uint32_t n_sub = 0, subseq_bits = 0, n_chunks = 0, rounds = 0;      // rounds: the maximum over the chunks of the relaxation rounds that changed something
-};
-// The CPU stand-in for the kernels of a handle whose OMNI_JPEGDEC_RESTART_WGS is W >= 1: a file that is HOST for its restart interval alone runs the chunk plan
-// and the phase functions, chunk by chunk, by plain loops, and is OK; every other file goes the way of jpeg_decode_parallel_host (one chunk).  A file that cannot
-// be planned: the sequential decoder, HOST.
-inline int jpeg_decode_restart_parallel_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t W, uint32_t max_sub, uint8_t* out, int64_t stride, int max_w,
-                                             int max_h, int* w, int* h, RestartStats* stats) {
-    Desc d;
-    const int st = parse(file, size, &d);
-    RestartStats rs;
-    if (stats) *stats = rs;
-    if (!d.restart_only || !out) {
-        ParallelStats ps;
-        const int r = jpeg_decode_parallel_host(file, size, S, max_sub, out, stride, max_w, max_h, w, h, &ps);
-        if (stats && out && st == OMNI_JPEGDEC_OK && r >= 0) { stats->n_sub = ps.n_sub; stats->subseq_bits = ps.subseq_bits; stats->n_chunks = 1; stats->rounds = ps.rounds; }
-        return r;
-    }
-    if (w) *w = d.w;
-    if (h) *h = d.h;
-    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
-    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
-    std::vector<int64_t> rst((size_t)(d.scan_bytes / 2 + 1));
-    int64_t n_rst = 0;
-    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), rst.data(), (int64_t)rst.size(), &n_rst);
-    ChunkPlan P;
-    plan_chunks(d, nclean, rst.data(), n_rst, S, W, max_sub, &P);
-    if (P.status == OMNI_JPEGDEC_CORRUPT) {
-        zero_picture(out, stride, d.w, d.h);
-        return OMNI_JPEGDEC_CORRUPT;
-    }
-    if (P.status != OMNI_JPEGDEC_OK) return decode_sequential(file, d, out, stride);
-    S = P.subseq_bits;
-    const uint32_t n_words = scan_words(nclean);
-    const Interval* iv = P.iv.data();
-    std::vector<int16_t> coef((size_t)d.n_yblocks * 64, 0);
-    std::vector<int32_t> dc(d.n_yblocks, 0);
-    NoEmit none;
-    int e, err = 0;
-    rs.n_sub = P.n_sub; rs.subseq_bits = S; rs.n_chunks = P.n_chunks;
-    for (uint32_t c = 0; c < P.n_chunks; ++c) {
-        const uint32_t k0 = P.chunk_first[c], k1 = P.chunk_first[c + 1], sub0 = iv[k0].first_sub, N = iv[k1].first_sub - sub0;
-        std::vector<uint16_t> ex(N), used(N, 0);
-        std::vector<uint32_t> cnt(N), first(N), of(N);
-        std::vector<uint8_t> need(N);
-        auto run = [&](uint32_t i, uint16_t entry, uint32_t first_block, uint32_t max_blocks, auto& em, uint16_t* x) {
-            const Interval& I = iv[of[i]];
-            return decode_subseq_seg(d.T, clean.data(), n_words, I.bit_begin, I.bit_end, sub0 + i - I.first_sub, S, entry, first_block, max_blocks, em, x, &e);
-        };
-        for (uint32_t i = 0; i < N; ++i) {                                                  // 1
-            of[i] = interval_of(iv, k0, k1, sub0 + i);
-            cnt[i] = run(i, 0, 0u, 0xffffffffu, none, &ex[i]);
-        }
-        uint32_t rounds = 0;
-        for (uint32_t r = 0; r < N; ++r) {                                                  // 2: the first subsequence of an interval keeps its entry 0
-            for (uint32_t i = 0; i < N; ++i) {
-                need[i] = sub0 + i != iv[of[i]].first_sub && ex[i - 1] != used[i];
-                if (need[i]) used[i] = ex[i - 1];
-            }
-            bool changed = false;
-            for (uint32_t i = 0; i < N; ++i) {
-                if (!need[i]) continue;
-                uint16_t x;
-                const uint32_t n = run(i, used[i], 0u, 0xffffffffu, none, &x);
-                if (x != ex[i] || n != cnt[i]) { ex[i] = x; cnt[i] = n; changed = true; }
-            }
-            if (!changed) break;
-            ++rounds;
-        }
-        if (rounds > rs.rounds) rs.rounds = rounds;
-        uint32_t total = 0;
-        for (uint32_t i = 0; i < N; ++i) { first[i] = total; total += cnt[i]; }             // 3: a prefix that never crosses an interval's start
-        for (uint32_t i = 0; i < N; ++i) {                                                  // 4
-            const Interval& I = iv[of[i]];
-            const uint32_t fb = I.first_block + (first[i] - first[I.first_sub - sub0]), max_blocks = iv[of[i] + 1].first_block;
-            CoefEmit em;
-            em.coef = coef.data(); em.dcd = dc.data(); em.n_yblocks = d.n_yblocks;
-            em.start(d.T, fb, used[i] >> 12);
-            uint16_t x;
-            const uint32_t wrote = run(i, used[i], fb, max_blocks, em, &x);
-            err |= e;
-            if (sub0 + i + 1 == iv[of[i] + 1].first_sub && fb + wrote < max_blocks) err = 1;      // the interval ends short of its blocks
-        }
-    }
-    if (stats) *stats = rs;
-    dc_scan_host(dc.data(), d.n_yblocks, (uint32_t)d.restart * (uint32_t)d.T.ny);           // 5
-    for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
-    return err ? OMNI_JPEGDEC_CORRUPT : OMNI_JPEGDEC_OK;
-}
-
-// ---- files without a restart interval over several workgroups: the CPU stand-in ----------------------------------------------------------------------------------
-struct PlainStats {
+// ---- the CPU stand-in for the kernels ------------------------------------------------------------------------------------------------------------------------------
+struct PlannedStats {
     uint32_t n_sub = 0, subseq_bits = 0, n_chunks = 0, chunk_rounds = 0;      // chunk_rounds: the maximum over the chunks of the rounds that changed something
     uint32_t seam_rounds = 0, seam_changed = 0, seam_chunks = 0;              // seam relaxation: rounds that changed something, subsequences it changed at least
-                                                                              // once, and the chunks those lie in
-};
-// The CPU stand-in for the kernels of a handle whose OMNI_JPEGDEC_PLAIN_WGS is W >= 2: a file classified OK runs, by plain loops and in the kernels' order,
-//   1  every subsequence from the guess;  2a  Jacobi rounds inside each chunk until nothing changes (a chunk's first subsequence keeps the guess);
-//   2b Jacobi rounds over the whole picture until nothing changes (the seam relaxation);  3  one exclusive scan of the counts over the picture;  4-6 as
-//   jpeg_decode_parallel_host.  Every other file -- a restart interval included -- goes the way of jpeg_decode_parallel_host, its statistics zero.
-inline int jpeg_decode_plain_parallel_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t W, uint32_t max_sub, uint8_t* out, int64_t stride, int max_w,
-                                           int max_h, int* w, int* h, PlainStats* stats) {
+};                                                                            // once, and the chunks those lie in
+// The phase functions by plain loops, in the kernels' order, for a handle whose switches are restart_wgs and plain_wgs, with S bits per subsequence (a power of
+// two) and workgroups of max_sub subsequences.  A picture is an Interval table and chunk bounds in subsequence numbers: a planned restart file has plan_chunks'
+// table and chunks; every other file is ONE interval over the whole scan, cut into plain_chunks' chunks (plain_wgs >= 2 and status OK; S from plain_subseq_bits)
+// or one chunk (S from subseq_bits_for).  1 every subsequence from the guess; 2 Jacobi rounds inside each chunk until nothing changes -- a subsequence that
+// starts an interval keeps entry 0, a chunk's first one the entry it has -- and, where the chunks cut an interval, once more over the whole picture (the seam
+// relaxation); 3 the exclusive scan of the counts inside every interval; 4 the write pass, every interval bounded to its own blocks; 5-6.  CORRUPT: a step error
+// on the true chain, an interval whose last subsequence ends short of its blocks, no subsequence at all.
+// Files the kernels do not take go where a handle sends them: UNSUPPORTED and CORRUPT at parse as jpeg_decode_host; a restart file that the switch or
+// !restart_only leaves on the host, or whose plan is HOST: decode_sequential; a plan that is CORRUPT: zeros.  A HOST file without a restart interval takes the
+// one-chunk path all the same and stays HOST (its statistics are reported with both switches off only: a handle decodes it on the host).
+inline int decode_planned_host(const uint8_t* file, int64_t size, uint32_t S, uint32_t restart_wgs, uint32_t plain_wgs, uint32_t max_sub, uint8_t* out, int64_t stride,
+                               int max_w, int max_h, int* w, int* h, PlannedStats* stats) {
     Desc d;
     const int st = parse(file, size, &d);
-    PlainStats ps;
-    if (stats) *stats = ps;
-    if (st != OMNI_JPEGDEC_OK || !out) return jpeg_decode_parallel_host(file, size, S, max_sub, out, stride, max_w, max_h, w, h, nullptr);
+    if (stats) *stats = PlannedStats();
+    if (!out || (st != OMNI_JPEGDEC_OK && st != OMNI_JPEGDEC_HOST) || (d.restart && !(restart_wgs && d.restart_only)) || d.w > max_w || d.h > max_h || stride < d.w)
+        return jpeg_decode_host(file, size, out, stride, max_w, max_h, w, h);               // not the kernels' to decode (or no room for it: -1)
     if (w) *w = d.w;
     if (h) *h = d.h;
-    if (d.w > max_w || d.h > max_h || stride < d.w) return -1;
     std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
-    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), nullptr, 0, nullptr);
+    std::vector<int64_t> rst(d.restart ? (size_t)(d.scan_bytes / 2 + 1) : 0);
+    int64_t n_rst = 0;
+    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), rst.data(), (int64_t)rst.size(), &n_rst);
     const uint32_t total_bits = (uint32_t)(nclean * 8), n_words = scan_words(nclean);
-    S = plain_subseq_bits(total_bits, S, W, max_sub);
-    const uint32_t N = (total_bits + S - 1) / S, C = plain_chunks(N, W);
+    // the picture as a table: intervals, and chunk c = the subsequences [bound[c], bound[c + 1])
+    std::vector<Interval> iv;
+    std::vector<uint32_t> bound;
+    if (d.restart) {
+        ChunkPlan P;
+        plan_chunks(d, nclean, rst.data(), n_rst, S, restart_wgs, max_sub, &P);
+        if (P.status == OMNI_JPEGDEC_CORRUPT) zero_picture(out, stride, d.w, d.h);
+        if (P.status != OMNI_JPEGDEC_OK) return P.status == OMNI_JPEGDEC_CORRUPT ? OMNI_JPEGDEC_CORRUPT : decode_sequential(file, d, out, stride);
+        S = P.subseq_bits;
+        iv = P.iv;
+        for (uint32_t k : P.chunk_first) bound.push_back(iv[k].first_sub);
+    } else {
+        const bool spread = plain_wgs >= 2 && st == OMNI_JPEGDEC_OK;
+        S = spread ? plain_subseq_bits(total_bits, S, plain_wgs, max_sub) : subseq_bits_for(total_bits, S, max_sub);
+        const uint32_t n_sub = (total_bits + S - 1) / S, C = spread ? plain_chunks(n_sub, plain_wgs) : 1u;
+        iv = {Interval{0u, total_bits, 0u, 0u}, Interval{total_bits, total_bits, n_sub, d.n_blocks}};
+        for (uint32_t c = 0; c <= C; ++c) bound.push_back(plain_chunk_begin(c, n_sub, C));
+    }
+    const uint32_t n_int = (uint32_t)iv.size() - 1, C = (uint32_t)bound.size() - 1, N = iv[n_int].first_sub;
     std::vector<uint16_t> ex(N), used(N, 0);
-    std::vector<uint32_t> cnt(N), first(N);
+    std::vector<uint32_t> cnt(N), of(N);                                                    // of: the interval a subsequence lies in
     std::vector<uint8_t> need(N), moved(N, 0);
+    for (uint32_t k = 0, i = 0; k < n_int; ++k)
+        for (; i < iv[k + 1].first_sub; ++i) of[i] = k;
     NoEmit none;
     int e;
-    auto again = [&](uint32_t i, uint16_t* x) { return decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], 0u, 0xffffffffu, none, x, &e); };
-    // Jacobi rounds over [lo, hi), lo keeping its entry: the rounds that changed something
-    auto relax = [&](uint32_t lo, uint32_t hi, bool seam) {
+    auto run = [&](uint32_t i, uint16_t entry, uint32_t first_block, uint32_t max_blocks, auto& em, uint16_t* x) {
+        const Interval& I = iv[of[i]];
+        return decode_subseq_seg(d.T, clean.data(), n_words, I.bit_begin, I.bit_end, i - I.first_sub, S, entry, first_block, max_blocks, em, x, &e);
+    };
+    // Jacobi rounds over the subsequences [lo, hi), lo keeping its entry: the rounds that changed something
+    auto relax = [&](uint32_t lo, uint32_t hi, bool mark) {
         uint32_t rounds = 0;
         for (uint32_t r = 0; r < hi - lo; ++r) {
             for (uint32_t i = lo + 1; i < hi; ++i) {
-                need[i] = ex[i - 1] != used[i];
+                need[i] = i != iv[of[i]].first_sub && ex[i - 1] != used[i];
                 if (need[i]) used[i] = ex[i - 1];
             }
             bool changed = false;
             for (uint32_t i = lo + 1; i < hi; ++i) {
                 if (!need[i]) continue;
                 uint16_t x;
-                const uint32_t c = again(i, &x);
-                if (x != ex[i] || c != cnt[i]) { ex[i] = x; cnt[i] = c; changed = true; if (seam) moved[i] = 1; }
+                const uint32_t n = run(i, used[i], 0u, 0xffffffffu, none, &x);
+                if (x != ex[i] || n != cnt[i]) { ex[i] = x; cnt[i] = n; changed = true; if (mark) moved[i] = 1; }
             }
             if (!changed) break;
             ++rounds;
         }
         return rounds;
     };
+    PlannedStats ps;
     ps.n_sub = N; ps.subseq_bits = S; ps.n_chunks = C;
-    for (uint32_t i = 0; i < N; ++i) cnt[i] = again(i, &ex[i]);                             // 1
-    for (uint32_t c = 0; c < C && N; ++c) {                                                 // 2a
-        const uint32_t rounds = relax(plain_chunk_begin(c, N, C), plain_chunk_begin(c + 1, N, C), false);
+    for (uint32_t i = 0; i < N; ++i) cnt[i] = run(i, 0, 0u, 0xffffffffu, none, &ex[i]);     // 1
+    bool cut = false;                                                                       // a chunk starts inside an interval
+    for (uint32_t c = 0; c < C; ++c) {                                                      // 2
+        const uint32_t rounds = relax(bound[c], bound[c + 1], false);
         if (rounds > ps.chunk_rounds) ps.chunk_rounds = rounds;
+        if (bound[c] < N && bound[c] != iv[of[bound[c]]].first_sub) cut = true;
     }
-    if (N) ps.seam_rounds = relax(0, N, true);                                              // 2b
-    for (uint32_t c = 0; c < C && N; ++c) {
+    if (cut) ps.seam_rounds = relax(0, N, true);
+    for (uint32_t c = 0; c < C; ++c) {
         uint32_t n = 0;
-        for (uint32_t i = plain_chunk_begin(c, N, C); i < plain_chunk_begin(c + 1, N, C); ++i) n += moved[i];
+        for (uint32_t i = bound[c]; i < bound[c + 1]; ++i) n += moved[i];
         ps.seam_changed += n;
         ps.seam_chunks += n != 0;
     }
-    if (stats) *stats = ps;
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < N; ++i) { first[i] = total; total += cnt[i]; }                 // 3
+    if (stats && (st == OMNI_JPEGDEC_OK || d.restart || (!restart_wgs && !plain_wgs))) *stats = ps;
     std::vector<int16_t> coef((size_t)d.n_yblocks * 64, 0);
     std::vector<int32_t> dc(d.n_yblocks, 0);
-    int err = total < d.n_blocks;
-    for (uint32_t i = 0; i < N; ++i) {                                                      // 4
+    int err = N == 0;
+    for (uint32_t i = 0, fb = 0; i < N; ++i) {                                              // 3 + 4: fb, the subsequence's first block
+        const uint32_t max_blocks = iv[of[i] + 1].first_block;
+        if (i == iv[of[i]].first_sub) fb = iv[of[i]].first_block;
         CoefEmit em;
         em.coef = coef.data(); em.dcd = dc.data(); em.n_yblocks = d.n_yblocks;
-        em.start(d.T, first[i], used[i] >> 12);
+        em.start(d.T, fb, used[i] >> 12);
         uint16_t x;
-        decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, used[i], first[i], d.n_blocks, em, &x, &e);
+        const uint32_t wrote = run(i, used[i], fb, max_blocks, em, &x);
         err |= e;
+        if (i + 1 == iv[of[i] + 1].first_sub && fb + wrote < max_blocks) err = 1;           // the interval ends short of its blocks
+        fb += cnt[i];
     }
-    dc_scan_host(dc.data(), d.n_yblocks, 0u);                                               // 5
+    dc_scan_host(dc.data(), d.n_yblocks, (uint32_t)d.restart * (uint32_t)d.T.ny);           // 5
     for (uint32_t y = 0; y < d.n_yblocks; ++y) block_out(d, coef.data(), dc.data(), y, err != 0, out, stride);      // 6
-    return err ? OMNI_JPEGDEC_CORRUPT : d.status;
+    return err ? OMNI_JPEGDEC_CORRUPT : d.restart ? OMNI_JPEGDEC_OK : st;
+}
+
+// For the record of the one-chunk path (S doubled until there are at most max_sub subsequences): how many subsequences leave phase 1 -- every one from the
+// guess -- with an exit state other than the true chain's.  0 for a file that path does not take
+inline uint32_t wrong_after_first(const uint8_t* file, int64_t size, uint32_t S, uint32_t max_sub) {
+    Desc d;
+    const int st = parse(file, size, &d);
+    if ((st != OMNI_JPEGDEC_OK && st != OMNI_JPEGDEC_HOST) || d.restart) return 0;
+    std::vector<uint8_t> clean((size_t)d.scan_bytes + JD_SCAN_PAD + 4);
+    const int64_t nclean = unstuff(file + d.scan_off, d.scan_bytes, clean.data(), nullptr, 0, nullptr);
+    const uint32_t total_bits = (uint32_t)(nclean * 8), n_words = scan_words(nclean);
+    S = subseq_bits_for(total_bits, S, max_sub);
+    NoEmit none;
+    uint32_t wrong = 0;
+    uint16_t chain = 0, guessed;
+    for (uint32_t i = 0, N = (total_bits + S - 1) / S; i + 1 < N; ++i) {                    // (all but the last subsequence)
+        int e;
+        decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, 0, 0u, 0xffffffffu, none, &guessed, &e);
+        decode_subseq(d.T, clean.data(), n_words, total_bits, i, S, chain, 0u, 0xffffffffu, none, &chain, &e);
+        wrong += chain != guessed;
+    }
+    return wrong;
 }
 
 }  // namespace jd

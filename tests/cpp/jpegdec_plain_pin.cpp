@@ -1,5 +1,5 @@
 // jpegdec_plain_pin: the path of csrc/jpeg_dec_plan.h that spreads a file WITHOUT a restart interval over several workgroups -- plain_subseq_bits, plain_chunks,
-// plain_chunk_begin and jpeg_decode_plain_parallel_host -- built with g++ alone, with -fsanitize=address,undefined (tests/test_jpegdec_plain_cpu.py,
+// plain_chunk_begin and decode_planned_host with plain_wgs = W -- built with g++ alone, with -fsanitize=address,undefined (tests/test_jpegdec_plain_cpu.py,
 // tests/jpegdec_plain_cases.py), over the fixtures and the mutated files.
 //   jpegdec_plain_pin <in> <out>
 // in:  int32 n; per case int32 {size, S, W, max_sub} + the file
@@ -54,11 +54,11 @@ int main(int argc, char** argv) {
         int w = d.w, h = d.h;
         const int stride = w + 3;
         std::vector<uint8_t> buf((size_t)stride * (h + 1) + 8, 0xA5);
-        PlainStats ps;
+        PlannedStats ps;
         int st = cls;
         const bool pixels = cls != OMNI_JPEGDEC_UNSUPPORTED && w > 0 && h > 0;
         if (pixels) {
-            st = jpeg_decode_plain_parallel_host(file.data(), (int64_t)file.size(), S, W, max_sub, buf.data(), stride, w, h, &w, &h, &ps);
+            st = decode_planned_host(file.data(), (int64_t)file.size(), S, 0u, W, max_sub, buf.data(), stride, w, h, &w, &h, &ps);
             if (st < 0) return 4;
             for (int y = 0; y <= h; ++y)
                 for (int x = y < h ? w : 0; x < stride; ++x)

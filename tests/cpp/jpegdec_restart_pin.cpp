@@ -1,4 +1,4 @@
-// jpegdec_restart_pin: the restart-interval path of csrc/jpeg_dec_plan.h -- plan_chunks and jpeg_decode_restart_parallel_host -- built with g++ alone, with
+// jpegdec_restart_pin: the restart-interval path of csrc/jpeg_dec_plan.h -- plan_chunks and decode_planned_host with restart_wgs = W -- built with g++ alone, with
 // -fsanitize=address,undefined (tests/test_jpegdec_restart_cpu.py, tests/jpegdec_restart_cases.py), over the fixtures and the mutated files.
 //   jpegdec_restart_pin <in> <out>
 // in:  int32 n; per case int32 {size, S, W, max_sub} + the file
@@ -64,17 +64,17 @@ int main(int argc, char** argv) {
         int w = d.w, h = d.h;
         const int stride = w + 3;
         std::vector<uint8_t> buf((size_t)stride * (h + 1) + 8, 0xA5);
-        RestartStats rs;
+        PlannedStats rs;
         int st = cls;
         const bool pixels = cls != OMNI_JPEGDEC_UNSUPPORTED && w > 0 && h > 0;
         if (pixels) {
-            st = jpeg_decode_restart_parallel_host(file.data(), (int64_t)file.size(), S, W, max_sub, buf.data(), stride, w, h, &w, &h, &rs);
+            st = decode_planned_host(file.data(), (int64_t)file.size(), S, W, 0u, max_sub, buf.data(), stride, w, h, &w, &h, &rs);
             if (st < 0) return 4;
             for (int y = 0; y <= h; ++y)
                 for (int x = y < h ? w : 0; x < stride; ++x)
                     if (buf[(size_t)y * stride + x] != 0xA5) return 5;
         }
-        const int32_t r[9] = {st, w, h, (int32_t)rs.n_sub, (int32_t)rs.subseq_bits, (int32_t)rs.n_chunks, (int32_t)rs.rounds, plan, pixels ? 1 : 0};
+        const int32_t r[9] = {st, w, h, (int32_t)rs.n_sub, (int32_t)rs.subseq_bits, (int32_t)rs.n_chunks, (int32_t)rs.chunk_rounds, plan, pixels ? 1 : 0};
         fwrite(r, 4, 9, out);
         if (pixels)
             for (int y = 0; y < h; ++y) fwrite(buf.data() + (size_t)y * stride, 1, (size_t)w, out);

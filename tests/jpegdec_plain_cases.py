@@ -1,5 +1,5 @@
 """The cases of the JPEG decoder's path that spreads a file WITHOUT a restart interval over several workgroups (OMNI_JPEGDEC_PLAIN_WGS; csrc/jpeg_dec_plan.h
-plain_chunks / jpeg_decode_plain_parallel_host, csrc/jpeg_dec.hip chunk, seam and write kernels), shared by the CPU and the GPU tier.  The files and Pillow's
+plain_chunks / decode_planned_host, csrc/jpeg_dec.hip chunk, seam and write kernels), shared by the CPU and the GPU tier.  The files and Pillow's
 pixels are the committed fixture of tests/jpegdec_cases.py; the one picture made here is written by the library's own host encoder.  The g++ pin program around
 the header is tests/cpp/jpegdec_plain_pin.cpp."""
 import os

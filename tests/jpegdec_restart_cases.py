@@ -1,4 +1,4 @@
-"""The cases of the JPEG decoder's restart-interval path (OMNI_JPEGDEC_RESTART_WGS; csrc/jpeg_dec_plan.h plan_chunks / jpeg_decode_restart_parallel_host,
+"""The cases of the JPEG decoder's restart-interval path (OMNI_JPEGDEC_RESTART_WGS; csrc/jpeg_dec_plan.h plan_chunks / decode_planned_host,
 csrc/jpeg_dec.hip), shared by the CPU and the GPU tier: files with restart markers as Pillow writes them and Pillow's pixels for them, from the committed fixture
 tests/golden/jpegdec_restart_cases.npz (written by tools/gen_jpegdec_restart_golden.py; the tests never import Pillow), the mutations derived from one of them,
 and the g++ pin program around the header (tests/cpp/jpegdec_restart_pin.cpp).

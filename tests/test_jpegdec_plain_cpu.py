@@ -1,7 +1,7 @@
 """Files without a restart interval over several workgroups, without a GPU: the partition, the S rule and the CPU stand-in for the kernels of a handle whose
-OMNI_JPEGDEC_PLAIN_WGS is W >= 2 (csrc/jpeg_dec_plan.h plain_chunks / plain_subseq_bits / jpeg_decode_plain_parallel_host; inside the library through
+OMNI_JPEGDEC_PLAIN_WGS is W >= 2 (csrc/jpeg_dec_plan.h plain_chunks / plain_subseq_bits / decode_planned_host with plain_wgs = W; inside the library through
 omni_jpeg_decode_plain_parallel_host, and as a g++ program of its own under -fsanitize=address,undefined) against the committed Pillow pixels
-(tests/golden/jpegdec_cases.npz), the sequential host decoder and the unchanged one-chunk stand-in, for every OK fixture, S in {default, 128} and W in {2, 3, 8};
+(tests/golden/jpegdec_cases.npz), the sequential host decoder and the same stand-in with the switch off (one chunk), for every OK fixture, S in {default, 128} and W in {2, 3, 8};
 the three ends of the relaxation; the chunk cap; the 40 mutations; the config entry and the bindings."""
 import ctypes as C
 import os
@@ -25,7 +25,7 @@ def test_stand_in_equals_pillow_the_sequential_decoder_and_the_one_chunk_stand_i
     st_h, pix_h = c.jpeg_decode_host(data)
     assert st_h == P.OK and np.array_equal(pix_h, want)
     for S in (default_S(c), 128):
-        st_1, pix_1, one = c.jpeg_decode_parallel_host(data, S)                                # the one-chunk stand-in, as it was
+        st_1, pix_1, one = c.jpeg_decode_parallel_host(data, S)                                # the stand-in with the switch off: one chunk
         assert st_1 == P.OK and np.array_equal(pix_1, want)
         for W in P.WGS:
             st, pix, stats = c.jpeg_decode_plain_parallel_host(data, S, W)
@@ -62,7 +62,7 @@ def test_a_small_workgroup_doubles_the_subsequence_length_only_until_the_chunks_
 
 
 def test_the_mutations_equal_the_one_chunk_stand_in(omni):
-    """the unchanged one-chunk stand-in is the yardstick for corrupt input: same status, same pixels"""
+    """the stand-in with the switch off (one chunk) is the yardstick for corrupt input: same status, same pixels under either switch value"""
     c = omni.capi
     seen = set()
     for what, data in J.mutations():

@@ -1,7 +1,7 @@
 """CPU gate of the JPEG decoder's arithmetic (csrc/jpeg_dec_plan.h, what csrc/jpeg_dec.hip runs lane-wise): built with g++ into tests/cpp/jpegdec_plan_pin.cpp and
 held to Pillow (libjpeg-turbo, JDCT_ISLOW; Image.draft('L') for colour files = libjpeg's JCS_GRAYSCALE, the first component alone) on EVERY PIXEL of the
 fixtures of tests/jpegdec_cases.py: gray 8 x 8, 17 x 13, 96 x 64 at q 5 / 75 / 100, noise at q 100, an optimised DHT, 160 x 120, colour 4:2:0 / 4:2:2 / 4:4:4,
-640 x 480, two files with restart intervals (HOST), one progressive file (UNSUPPORTED).  The parallel scheme (jpeg_decode_parallel_host, the CPU stand-in for the
+640 x 480, two files with restart intervals (HOST), one progressive file (UNSUPPORTED).  The parallel scheme (decode_planned_host with both switches off, the CPU stand-in for the
 kernels) equals the sequential decoder at S = 128, 256, 1024, 4096 and really crosses the relaxation; both agree on truncated and byte-flipped scans, and the same
 program runs clean under -fsanitize=address,undefined.  cv::imdecode itself is not pinned here (no OpenCV)."""
 import io

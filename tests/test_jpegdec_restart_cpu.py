@@ -1,5 +1,5 @@
 """The restart-interval path of the JPEG decoder without a GPU: the chunk plan and the CPU stand-in for the kernels of a handle whose OMNI_JPEGDEC_RESTART_WGS is
-on (csrc/jpeg_dec_plan.h plan_chunks / jpeg_decode_restart_parallel_host; inside the library through omni_jpeg_decode_restart_parallel_host, and as a g++ program
+on (csrc/jpeg_dec_plan.h plan_chunks / decode_planned_host with restart_wgs = W; inside the library through omni_jpeg_decode_restart_parallel_host, and as a g++ program
 of its own under -fsanitize=address,undefined) against the committed Pillow pixels (tests/golden/jpegdec_restart_cases.npz) and the sequential host decoder, for
 every fixture, S in {default, 128} and W in {1, 3, 8}; the mutations and the one documented divergence (tests/jpegdec_restart_cases.py); the config entry."""
 import ctypes as C
