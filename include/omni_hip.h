@@ -425,7 +425,8 @@ omni_cam* omni_cam_create(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, omn
 /* CameraConfig::PINHOLE_DEPTH (loop_cam.cpp:190-194; generate_gray_depth_image_descriptor :231-339; launch/realsense.launch): ONE camera per
  * image -- SuperPoint and MobileNetVLAD on each of the n_images images, no up/down match (n_matches = 0, the match arrays unused), the arrays
  * of omni_cam_result sized [n_images].  sp with max_batch >= n_images, vlad with max_batch >= n_images.  The landmarks come from the depth
- * image on the host (host/loop_geometry.hpp fill_depth_landmarks); pass fisheye_mask = 0 to the enqueue calls (:536 masks STEREO_FISHEYE only). */
+ * image: inside the unit for the model set with omni_cam_set_depth_model (below: csrc/depth_landmarks.hip), on the host otherwise (host/loop_geometry.hpp
+ * fill_depth_landmarks); pass fisheye_mask = 0 to the enqueue calls (:536 masks STEREO_FISHEYE only). */
 omni_cam* omni_cam_create_mono(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, omni_vlad* vlad, int n_images, int max_num, int global_dim);
 void      omni_cam_destroy(omni_cam* cam);
 int       omni_cam_enqueue_dev(omni_cam* cam, const uint8_t* gray_dev, int stride, int fisheye_mask);   /* no host sync */
@@ -510,13 +511,13 @@ int omni_cam_set_stereo_model(omni_cam* cam, const omni_stereo_model* model);
  * refuses, before anything is enqueued, a unit whose active size is not n_keyframes * dirs_per_keyframe -- also one whose poses were not set since the last unit. */
 int omni_cam_set_poses(omni_cam* cam, const double* poses7, int n_keyframes);
 typedef struct omni_cam_landmarks_result {      /* pointers into the handle's pinned host block; valid after omni_cam_wait until the handle's next enqueue */
-    int n_images, n_dirs, max_num;              /* of that unit: n_images = 2 * n_dirs */
+    int n_images, n_dirs, max_num;              /* of that unit: n_images = 2 * n_dirs (a mono unit with a depth model: n_images = n_dirs) */
     const float*   norm2d;                      /* [n_images][max_num][2]  the message's landmarks_2d_norm */
     const float*   landmarks_3d;                /* [n_images][max_num][3] */
     const uint8_t* landmarks_flag;              /* [n_images][max_num] */
-    const int*     count_3d;                    /* [n_dirs] */
+    const int*     count_3d;                    /* [n_dirs] (a mono unit with a depth model: one per image) */
 } omni_cam_landmarks_result;
-/* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran without a model */
+/* OMNI_ERR_INVALID while a unit is pending, and when the last unit ran without a model (a stereo model, or a mono handle's depth model: omni_cam_set_depth_model) */
 int omni_cam_landmarks(omni_cam* cam, omni_cam_landmarks_result* out);
 
 /* ---- the lens model of the lift: what the reference's camodocal camera (camera_config_path, loop_cam.cpp:31-33) does in cam->liftProjective before the division by z
@@ -541,6 +542,47 @@ int omni_cam_set_camera_model(omni_cam* cam, const omni_camera_model* camera);
  * intrinsics4 = fx fy cx cy (gamma1 gamma2 u0 v0).  _project_host is the forward model (tests, synthetic data): xyz [n][3] double -> pixels [n][2] double. */
 int omni_camera_lift_host(const omni_camera_model* camera, const double* intrinsics4, const float* xy, int n, double* out_xy_f64);
 int omni_camera_project_host(const omni_camera_model* camera, const double* intrinsics4, const double* xyz, int n, double* out_xy_f64);
+
+/* ---- depth landmarks: what generate_gray_depth_image_descriptor does between the networks and the frame message (CameraConfig::PINHOLE_DEPTH, loop_cam.cpp:260-304; the
+ * lifted key points of :558-566).  The arithmetic is stated once, in csrc/depth_plan.h (the lens: csrc/camera_plan.h; the pose algebra: csrc/landmark_plan.h): f64, every
+ * product and sum rounded on its own, the same operations in the same order as host/loop_geometry.hpp's fill_image_descriptor + fill_depth_landmarks -- including the
+ * latter's recorded deviation: a key point the reference's 640 x 480 gate lets through but which lies outside THIS depth image gets no landmark.  Per image: no landmarks at
+ * all unless it has MORE than accept_min_3d_pts key points and a depth frame; a key point gets one when its depth (u16 millimetres under the pixel rounded half to
+ * even, / 1000.0) lies strictly between depth_near and depth_far: pose_drone * extrinsic * (lifted pixel * depth), as floats, flag 1. */
+typedef struct omni_depth_model {
+    double fx, fy, cx, cy;            /* of the network-size image, as omni_stereo_model's (MEI: gamma1, gamma2, u0, v0) */
+    double depth_near, depth_far;     /* metres (DEPTH_NEAR_THRES / DEPTH_FAR_THRES) */
+    int accept_min_3d_pts;            /* no landmarks at all unless the image has MORE key points than this (loop_cam.cpp:266-270) */
+    int depth_width, depth_height;    /* of every depth image */
+    double extrinsic[7];              /* body -> camera, xyz + quaternion wxyz (normalised on the way in) */
+} omni_depth_model;
+/* The stage on HBM-resident arrays: kps_xy_dev [n_images][max_num][2], n_kps_dev [n_images], poses7_dev [n_images][7] (pose_drone of each image's key frame),
+ * depth_dev: image i at depth_dev + i * depth_stride_elems * depth_height (u16, stride in ELEMENTS), have_dev [n_images] u8 (0: the image has no depth frame and gets
+ * no landmarks; NULL: every image has one).  Outputs (device): norm2d_out [n_images][max_num][2] float (zeros behind an image's last key point), l3d_out
+ * [n_images][max_num][3] float, flag_out [n_images][max_num] u8, count_out [n_images] (count_3d).  camera == NULL: the ideal pinhole.  Refused before anything is
+ * launched: a null argument, max_num outside 1..1024, a zero or NaN focal length, what omni_landmarks_enqueue_dev_camera refuses of a lens, depth_width / depth_height
+ * below 1, a stride below the width, a NaN depth_near or depth_far.  Asynchronous on the context's stream. */
+int omni_depth_landmarks_enqueue_dev(omni_ctx* ctx, const omni_depth_model* model, const omni_camera_model* camera, const double* poses7_dev, int n_images, int max_num,
+                                     const float* kps_xy_dev, const int* n_kps_dev, const uint16_t* depth_dev, int depth_stride_elems, const uint8_t* have_dev,
+                                     float* norm2d_out, float* l3d_out, uint8_t* flag_out, int* count_out);
+/* the same arguments in HOST memory, csrc/depth_plan.h compiled by g++: no GPU, no context.  The same refusals. */
+int omni_depth_landmarks_host(const omni_depth_model* model, const omni_camera_model* camera, const double* poses7, int n_images, int max_num, const float* kps_xy,
+                              const int* n_kps, const uint16_t* depth, int depth_stride_elems, const uint8_t* have, float* norm2d_out, float* l3d_out, uint8_t* flag_out,
+                              int* count_out);
+/* The same stage inside a MONO key-frame unit (omni_cam_create_mono): with a model set, every unit runs the kernel on its SuperPoint stream behind the key points and
+ * copies the four arrays into the handle's pinned block in front of the unit's event; omni_cam_landmarks then serves the unit with n_images == n_dirs and count_3d
+ * [n_images].  The lens travels in this call (camera == NULL: the ideal pinhole): omni_cam_set_camera_model keeps refusing mono handles.  model == NULL switches the
+ * stage off again.  Refused: a stereo handle, a unit in flight, what omni_depth_landmarks_enqueue_dev refuses of a model and a lens.
+ * With a depth model omni_cam_set_poses is accepted on the mono handle: one key frame per image, n_keyframes = the unit's active size. */
+int omni_cam_set_depth_model(omni_cam* cam, const omni_depth_model* model, const omni_camera_model* camera);
+/* The depth frames of the NEXT unit, in host memory: frames[i] = image i's depth_height rows of stride_elems u16 elements, or NULL -- this key frame has no depth
+ * image and gets no landmarks.  Copied into the handle's pinned block before the call returns; uploaded on the SuperPoint stream at enqueue, next to the poses.
+ * _dev: the frames are in HBM already (image i at depth_dev + i * stride_elems * depth_height), BORROWED until omni_cam_wait; have_host [n_images] u8 or NULL (all).
+ * Refused: no depth model, a unit in flight, n_images outside 1 .. the handle's size, a stride below depth_width.  While a depth model is set every enqueue entry a
+ * mono handle accepts (_dev, _host, _host_parts, _jpeg_host with right_files = NULL) refuses, before anything is enqueued, a unit whose poses or depth frames were
+ * not set since the last unit, or were set for another size than the unit's active size. */
+int omni_cam_set_depth_host(omni_cam* cam, const uint16_t* const* frames, int stride_elems, int n_images);
+int omni_cam_set_depth_dev(omni_cam* cam, const uint16_t* depth_dev, int stride_elems, const uint8_t* have_host, int n_images);
 
 /* ---- loop verification: the homography RANSAC of compute_correspond_features (loop_detector.cpp:574-598: the 3-D-flag filter, then
  * cv::findHomography(old_2d, new_2d, RANSAC, 3, mask)) on the GPU, f64 (csrc/homography.hip; the arithmetic: csrc/ransac_plan.h, operation for operation

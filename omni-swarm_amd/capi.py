@@ -44,6 +44,7 @@ SYMBOLS = [
     "omni_resize_create", "omni_resize_destroy", "omni_resize_mode", "omni_resize_enqueue_dev", "omni_cam_enqueue_raw_dev", "omni_cam_enqueue_raw_host", "omni_cam_enqueue_raw_host_parts",
     "omni_landmarks_enqueue_dev", "omni_cam_set_stereo_model", "omni_cam_set_poses", "omni_cam_landmarks",
     "omni_landmarks_enqueue_dev_camera", "omni_cam_set_camera_model", "omni_camera_lift_host", "omni_camera_project_host",
+    "omni_depth_landmarks_enqueue_dev", "omni_depth_landmarks_host", "omni_cam_set_depth_model", "omni_cam_set_depth_host", "omni_cam_set_depth_dev",
     "omni_homography_ransac_multi", "omni_bf_match_homography_multi", "omni_pnp_ransac_multi",
     "omni_jpeg_create", "omni_jpeg_destroy", "omni_jpeg_enqueue_dev", "omni_jpeg_header", "omni_jpeg_encode_host", "omni_cam_set_jpeg", "omni_cam_jpeg",
     "omni_jpegdec_create", "omni_jpegdec_destroy", "omni_jpegdec_enqueue_host", "omni_jpegdec_last_stats", "omni_jpegdec_last_ms", "omni_jpegdec_debug_buffers", "omni_jpegdec_classify",
@@ -136,6 +137,38 @@ def camera_project_host(camera, intrinsics4, xyz) -> np.ndarray:
     out = np.zeros((len(xyz), 2), np.float64)
     _check(lib().omni_camera_project_host(C.byref(camera) if camera is not None else None, k.ctypes.data, xyz.ctypes.data, len(xyz), out.ctypes.data))
     return out
+
+
+class DepthModel(C.Structure):
+    """omni_depth_model: the intrinsics, the depth window, the accept rule, the depth images' size and the extrinsic (xyz + quaternion wxyz) of the depth-landmark stage"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("depth_near", C.c_double), ("depth_far", C.c_double),
+                ("accept_min_3d_pts", C.c_int), ("depth_width", C.c_int), ("depth_height", C.c_int), ("extrinsic", C.c_double * 7)]
+
+
+def depth_model(fx, fy, cx, cy, depth_near, depth_far, accept_min_3d_pts, depth_width, depth_height, extrinsic=(0, 0, 0, 1, 0, 0, 0)) -> DepthModel:
+    e = np.asarray(extrinsic, np.float64).reshape(-1)
+    if e.shape != (7,):
+        raise ValueError(f"depth_model: an extrinsic of {e.size} numbers, xyz + quaternion wxyz")
+    m = DepthModel()
+    m.fx, m.fy, m.cx, m.cy, m.depth_near, m.depth_far = float(fx), float(fy), float(cx), float(cy), float(depth_near), float(depth_far)
+    m.accept_min_3d_pts, m.depth_width, m.depth_height = int(accept_min_3d_pts), int(depth_width), int(depth_height)
+    m.extrinsic[:] = [float(v) for v in e]
+    return m
+
+
+def depth_landmarks_host(model: DepthModel, poses7, kps_xy, n_kps, depth, have=None, camera=None, depth_stride: int = 0) -> dict:
+    """omni_depth_landmarks_host: csrc/depth_plan.h on the host, no GPU.  kps_xy [N][M][2], n_kps [N], poses7 [N][7], depth [N][depth_height][stride] u16
+    (depth_stride 0: the array's last dimension), have [N] or None (all)"""
+    kps_xy, n_kps = _f32(kps_xy), np.ascontiguousarray(n_kps, np.int32)
+    N, M = n_kps.shape[0], kps_xy.shape[1]
+    p = np.ascontiguousarray(poses7, np.float64).reshape(-1, 7)
+    d = np.ascontiguousarray(depth, np.uint16)
+    hv = np.ascontiguousarray(have, np.uint8) if have is not None else None
+    assert p.shape == (N, 7) and kps_xy.shape == (N, M, 2) and (hv is None or hv.shape == (N,))
+    outs = np.zeros((N, M, 2), np.float32), np.zeros((N, M, 3), np.float32), np.zeros((N, M), np.uint8), np.zeros(N, np.int32)
+    _check(lib().omni_depth_landmarks_host(C.byref(model), C.byref(camera) if camera is not None else None, p.ctypes.data, N, M, kps_xy.ctypes.data, n_kps.ctypes.data,
+                                           d.ctypes.data, depth_stride or d.shape[-1], hv.ctypes.data if hv is not None else None, *[o.ctypes.data for o in outs]))
+    return dict(zip(("norm2d", "landmarks_3d", "landmarks_flag", "count_3d"), outs))
 
 
 class _CamLandmarks(C.Structure):
@@ -277,6 +310,11 @@ def lib():
     sig("omni_cam_set_camera_model", C.c_int, [_vp, C.POINTER(CameraModel)])
     sig("omni_camera_lift_host", C.c_int, [C.POINTER(CameraModel), _vp, _vp, C.c_int, _vp])
     sig("omni_camera_project_host", C.c_int, [C.POINTER(CameraModel), _vp, _vp, C.c_int, _vp])
+    sig("omni_depth_landmarks_enqueue_dev", C.c_int, [_vp, C.POINTER(DepthModel), C.POINTER(CameraModel), _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp])
+    sig("omni_depth_landmarks_host", C.c_int, [C.POINTER(DepthModel), C.POINTER(CameraModel), _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp])
+    sig("omni_cam_set_depth_model", C.c_int, [_vp, C.POINTER(DepthModel), C.POINTER(CameraModel)])
+    sig("omni_cam_set_depth_host", C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_int])
+    sig("omni_cam_set_depth_dev", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int])
     sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
     sig("omni_cam_landmarks", C.c_int, [_vp, C.POINTER(_CamLandmarks)])
     sig("omni_jpeg_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64])
@@ -1408,6 +1446,38 @@ def landmarks(ctx: Context, model: StereoModel, poses7, kps_xy, n_kps, match_up,
     return dict(zip(("norm2d", "landmarks_3d", "landmarks_flag", "count_3d"), res))
 
 
+def depth_landmarks_dev(ctx: Context, model: DepthModel, poses7_dev, n_images, max_num, kps_xy_dev, n_kps_dev, depth_dev, depth_stride, have_dev, norm2d_out, l3d_out,
+                        flag_out, count_out, camera=None):
+    """omni_depth_landmarks_enqueue_dev: the depth landmarks of n_images images on HBM-resident arrays; asynchronous on ctx.  camera None: the ideal pinhole"""
+    _check(lib().omni_depth_landmarks_enqueue_dev(ctx.h, C.byref(model), C.byref(camera) if camera is not None else None, poses7_dev, n_images, max_num, kps_xy_dev,
+                                                  n_kps_dev, depth_dev, depth_stride, have_dev, norm2d_out, l3d_out, flag_out, count_out))
+
+
+def depth_landmarks(ctx: Context, model: DepthModel, poses7, kps_xy, n_kps, depth, have=None, camera=None, depth_stride: int = 0) -> dict:
+    """host convenience around depth_landmarks_dev (upload, run, download): the arguments of depth_landmarks_host"""
+    kps_xy, n_kps = _f32(kps_xy), np.ascontiguousarray(n_kps, np.int32)
+    N, M = n_kps.shape[0], kps_xy.shape[1]
+    d = np.ascontiguousarray(depth, np.uint16)
+    ins = [np.ascontiguousarray(poses7, np.float64).reshape(-1, 7), kps_xy, n_kps, d]
+    if have is not None:
+        ins.append(np.ascontiguousarray(have, np.uint8))
+    assert ins[0].shape == (N, 7) and kps_xy.shape == (N, M, 2)
+    outs = [((N, M, 2), np.float32), ((N, M, 3), np.float32), ((N, M), np.uint8), ((N,), np.int32)]
+    dev, odev = [], []
+    try:
+        for a in ins:
+            dev.append(ctx.to_device(a))
+        for shape, dt in outs:
+            odev.append(ctx.alloc(int(np.prod(shape)) * np.dtype(dt).itemsize))
+        depth_landmarks_dev(ctx, model, dev[0], N, M, dev[1], dev[2], dev[3], depth_stride or d.shape[-1], dev[4] if have is not None else None, *odev, camera=camera)
+        ctx.sync()
+        res = [ctx.from_device(o, shape, dt) for o, (shape, dt) in zip(odev, outs)]
+    finally:
+        for x in dev + odev:
+            ctx.free(x)
+    return dict(zip(("norm2d", "landmarks_3d", "landmarks_flag", "count_3d"), res))
+
+
 class Cam:
     """omni_cam: one key frame's CNN + matching work as a single asynchronous unit (LoopCam::on_flattened_images,
     loop_cam.cpp:178-229).  wait() returns numpy VIEWS of the handle's pinned host block (valid until the next enqueue)."""
@@ -1534,6 +1604,23 @@ class Cam:
         """a CameraModel: the lens of the stage's lifts (csrc/camera_plan.h); None: the ideal pinhole again.  Kept over set_stereo_model."""
         _check(lib().omni_cam_set_camera_model(self.h, C.byref(camera) if camera is not None else None))
 
+    def set_depth_model(self, model, camera=None):
+        """a DepthModel (mono handles): every following unit lifts its key points and reads its depth landmarks on the GPU (landmarks() after wait()); the lens
+        (a CameraModel; None: the ideal pinhole) travels with it.  model None switches the stage off.  set_poses and set_depth_host / _dev before every enqueue."""
+        _check(lib().omni_cam_set_depth_model(self.h, C.byref(model) if model is not None else None, C.byref(camera) if camera is not None else None))
+
+    def set_depth_host(self, frames, stride: int = 0):
+        """the depth frames of the NEXT unit: a list of [H][stride] u16 arrays, None for a key frame without a depth image; copied before the call returns"""
+        arrs = [np.ascontiguousarray(f, np.uint16) if f is not None else None for f in frames]
+        ptrs = (_vp * len(arrs))(*[a.ctypes.data if a is not None else None for a in arrs])
+        st = stride or next((a.shape[-1] for a in arrs if a is not None), 0)
+        _check(lib().omni_cam_set_depth_host(self.h, ptrs, st, len(arrs)))
+
+    def set_depth_dev(self, depth_dev: int, stride: int, n_images: int, have=None):
+        """the same for frames already in HBM ([n_images][H][stride] u16), borrowed until wait(); have [n_images] or None (all)"""
+        hv = np.ascontiguousarray(have, np.uint8) if have is not None else None
+        _check(lib().omni_cam_set_depth_dev(self.h, depth_dev, stride, hv.ctypes.data if hv is not None else None, n_images))
+
     def landmarks(self) -> dict:
         """after wait(): numpy VIEWS of the unit's lifted key points, 3-D landmarks, flags and count_3d (valid until the next enqueue)"""
         r = _CamLandmarks()
@@ -1541,7 +1628,7 @@ class Cam:
         A = np.ctypeslib.as_array
         ni, n, m = r.n_images, r.n_dirs, r.max_num
         return {"norm2d": A(r.norm2d, (ni, m, 2)), "landmarks_3d": A(r.landmarks_3d, (ni, m, 3)), "landmarks_flag": A(r.landmarks_flag, (ni, m)),
-                "count_3d": A(r.count_3d, (n,))}
+                "count_3d": A(r.count_3d, (n,))}          # (a mono unit with a depth model: n_images == n_dirs, one count per image)
 
     def set_jpeg(self, quality: int, capacity_per_image: int = 0):
         """send_img: every following unit also encodes its main images as JPEG files (jpeg() after wait()); quality 0 switches it off.

@@ -10,6 +10,7 @@
 // (each with its own SuperPoint / MobileNetVLAD instance) keep several key frames in flight.
 #include "common.h"
 #include "camera_plan.h"
+#include <string.h>
 
 struct omni_cam {
     omni_sp* sp = nullptr;
@@ -42,6 +43,17 @@ struct omni_cam {
     double* d_poses = nullptr;
     char* d_lm = nullptr;                     // ONE block laid out as host + off_norm .. off_lm_end: norm2d | landmarks_3d | flags | count_3d (one copy down)
     size_t off_poses = 0, off_norm = 0, off_l3d = 0, off_flag = 0, off_cnt = 0, off_lm_end = 0;
+    // depth landmarks inside a MONO unit (omni_cam_set_depth_model; depth_landmarks.hip): the same poses staging, the same block of four arrays (one image per
+    // direction, count_3d per image), plus the NEXT unit's depth frames -- h_depth (pinned): [n_cap] frames of depth_width x depth_height u16, rows packed, then
+    // (at depth_have) have [n_cap] u8; d_depth: the same layout in HBM.  omni_cam_set_depth_dev borrows the frames instead (depth_ext) and sets have only
+    bool dp_on = false;
+    omni_depth_model dmodel;
+    omni_camera_model dcamera = omni::cam::ideal();
+    int n_depth = 0;                          // images omni_cam_set_depth_host / _dev set since the last unit (0: none)
+    const uint16_t* depth_ext = nullptr;      // != nullptr: the next unit reads these frames (HBM, borrowed until omni_cam_wait) with depth_ext_stride
+    int depth_ext_stride = 0;
+    uint8_t *h_depth = nullptr, *d_depth = nullptr;
+    size_t depth_have = 0, depth_bytes = 0;
     // send_img inside the unit (omni_cam_set_jpeg; jpeg.hip): the unit's main images [0, n) as JPEG files, on the MobileNetVLAD stream.  d_jpeg / h_jpeg: the
     // images' bytes [n_cap][jpeg_cap], then (at jpeg_meta) sizes [n_cap] and statuses [n_cap] -- a block of its own, pinned on the host side
     omni_jpeg* jpeg = nullptr;
@@ -70,7 +82,8 @@ omni_cam* omni_cam_create(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, omn
 }
 
 // CameraConfig::PINHOLE_DEPTH (loop_cam.cpp:190-194, generate_gray_depth_image_descriptor :231-339): ONE camera per image, both networks on every
-// image, no up/down match; the landmarks come from the depth image on the host (loop_geometry.hpp fill_depth_landmarks)
+// image, no up/down match; the landmarks come from the depth image: inside the unit with a depth model (omni_cam_set_depth_model, depth_landmarks.hip), else on
+// the host (loop_geometry.hpp fill_depth_landmarks)
 omni_cam* omni_cam_create_mono(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, omni_vlad* vlad, int n_images, int max_num, int global_dim) {
     return cam_create(sp_ctx, sp, vlad_ctx, vlad, n_images, 1, max_num, global_dim, 0);
 }
@@ -97,7 +110,7 @@ static omni_cam* cam_create(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, o
     c->off_t = o;   o += al(n * M * 4);
     c->off_d = o;   o += al(n * M * 4);
     c->off_nm = o;  o += al(n * 4);
-    if (cams == 2) {                                                          // the landmark stage's part of the block (a few kilobytes per image)
+    {                                                                         // the landmark stage's part of the block (a few kilobytes per image; mono: the depth landmarks')
         c->off_poses = o; o += al(n * 7 * 8);
         c->off_norm = o;  o += al(ni * M * 2 * 4);
         c->off_l3d = o;   o += al(ni * M * 3 * 4);
@@ -109,7 +122,7 @@ static omni_cam* cam_create(omni_ctx* sp_ctx, omni_sp* sp, omni_ctx* vlad_ctx, o
     bool ok = hipHostMalloc((void**)&c->host, o, hipHostMallocDefault) == hipSuccess &&
               hipMalloc((void**)&c->d_qidx, n * M * 4) == hipSuccess && hipMalloc((void**)&c->d_tidx, n * M * 4) == hipSuccess &&
               hipMalloc((void**)&c->d_dist, n * M * 4) == hipSuccess && hipMalloc((void**)&c->d_nm, n * 4) == hipSuccess &&
-              (cams != 2 || (hipMalloc((void**)&c->d_poses, n * 7 * 8) == hipSuccess && hipMalloc((void**)&c->d_lm, c->off_lm_end - c->off_norm) == hipSuccess)) &&
+              hipMalloc((void**)&c->d_poses, n * 7 * 8) == hipSuccess && hipMalloc((void**)&c->d_lm, c->off_lm_end - c->off_norm) == hipSuccess &&
               hipEventCreateWithFlags(&c->e1, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->e2, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->e_up, hipEventDisableTiming) == hipSuccess &&
@@ -125,7 +138,7 @@ void omni_cam_destroy(omni_cam* c) {
     (void)hipSetDevice(c->c1->device);
     (void)hipStreamSynchronize(c->c1->stream);
     (void)hipStreamSynchronize(c->c2->stream);
-    void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw, c->d_poses, c->d_lm};
+    void* ptrs[] = {c->d_qidx, c->d_tidx, c->d_dist, c->d_nm, c->d_gray, c->d_raw, c->d_poses, c->d_lm, c->d_depth};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->jpeg) omni_jpeg_destroy(c->jpeg);
     if (c->jdec) omni_jpegdec_destroy(c->jdec);
@@ -133,6 +146,7 @@ void omni_cam_destroy(omni_cam* c) {
     if (c->h_jdec_status) (void)hipHostFree(c->h_jdec_status);
     if (c->d_jpeg) (void)hipFree(c->d_jpeg);
     if (c->h_jpeg) (void)hipHostFree(c->h_jpeg);
+    if (c->h_depth) (void)hipHostFree(c->h_depth);
     if (c->host) (void)hipHostFree(c->host);
     if (c->e1) (void)hipEventDestroy(c->e1);
     if (c->e2) (void)hipEventDestroy(c->e2);
@@ -156,6 +170,13 @@ static int cam_staging(omni_cam* c, uint8_t*& buf, size_t& have, size_t need) {
 
 // with a stereo model set, a unit needs the poses of ITS key frames: checked by every enqueue entry before anything is enqueued (c->mu held)
 static int cam_poses_check(omni_cam* c) {
+    if (c->dp_on) {                                                           // a mono unit with a depth model: the poses AND the depth frames of its images, one key frame per image
+        OMNI_REQUIRE(c->n_poses > 0, OMNI_ERR_INVALID, "a depth model is set but the unit's poses are not (omni_cam_set_poses before every enqueue)");
+        OMNI_REQUIRE(c->n_poses == c->n, OMNI_ERR_INVALID, "poses of %d key frames for a unit of %d images (omni_cam_set_poses, omni_cam_set_active)", c->n_poses, c->n);
+        OMNI_REQUIRE(c->n_depth > 0, OMNI_ERR_INVALID, "a depth model is set but the unit's depth frames are not (omni_cam_set_depth_host / _dev before every enqueue)");
+        OMNI_REQUIRE(c->n_depth == c->n, OMNI_ERR_INVALID, "depth frames of %d images for a unit of %d images (omni_cam_set_depth_host / _dev, omni_cam_set_active)", c->n_depth, c->n);
+        return OMNI_OK;
+    }
     if (!c->lm_on) return OMNI_OK;
     OMNI_REQUIRE(c->n_poses > 0, OMNI_ERR_INVALID, "a stereo model is set but the unit's poses are not (omni_cam_set_poses before every enqueue)");
     OMNI_REQUIRE(c->n_poses * c->model.dirs_per_keyframe == c->n, OMNI_ERR_INVALID, "poses of %d key frames x %d directions for a unit of %d (omni_cam_set_poses, omni_cam_set_active)",
@@ -539,6 +560,25 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
         c->lm_unit = true; c->lm_n = n;
         c->n_poses = 0;                                                       // (consumed: the next unit needs its own)
     }
+    if (c->dp_on) {
+        // generate_gray_depth_image_descriptor's landmarks (loop_cam.cpp:260-304) behind the key points they read: the unit's poses, have flags and (unless they
+        // are in HBM already) depth frames go up on this stream, the kernel follows, its four arrays go down in front of the unit's event
+        const omni_depth_model& dm = c->dmodel;
+        const size_t frame = (size_t)dm.depth_width * dm.depth_height * sizeof(uint16_t);
+        float *d_norm = reinterpret_cast<float*>(c->d_lm), *d_l3d = reinterpret_cast<float*>(c->d_lm + (c->off_l3d - c->off_norm));
+        uint8_t* d_flag = reinterpret_cast<uint8_t*>(c->d_lm + (c->off_flag - c->off_norm));
+        int* d_cnt = reinterpret_cast<int*>(c->d_lm + (c->off_cnt - c->off_norm));
+        OMNI_HIP_TRY(hipMemcpyAsync(c->d_poses, h + c->off_poses, (size_t)n * 7 * 8, hipMemcpyHostToDevice, s1));
+        OMNI_HIP_TRY(hipMemcpyAsync(c->d_depth + c->depth_have, c->h_depth + c->depth_have, (size_t)n, hipMemcpyHostToDevice, s1));
+        if (!c->depth_ext) OMNI_HIP_TRY(hipMemcpyAsync(c->d_depth, c->h_depth, (size_t)n * frame, hipMemcpyHostToDevice, s1));
+        const uint16_t* depth = c->depth_ext ? c->depth_ext : reinterpret_cast<const uint16_t*>(c->d_depth);
+        if ((rc = omni::depth_landmarks_launch(s1, dm, c->dcamera, c->d_poses, n, M, c->kps_dev, c->n_dev, depth, c->depth_ext ? c->depth_ext_stride : dm.depth_width,
+                                               c->d_depth + c->depth_have, d_norm, d_l3d, d_flag, d_cnt)))
+            return rc;
+        OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_norm, c->d_lm, c->off_lm_end - c->off_norm, hipMemcpyDeviceToHost, s1));
+        c->lm_unit = true; c->lm_n = n;
+        c->n_poses = 0; c->n_depth = 0; c->depth_ext = nullptr;              // (consumed: the next unit needs its own)
+    }
     OMNI_HIP_TRY(hipEventRecord(c->e1, s1));
     OMNI_HIP_TRY(hipMemcpyAsync(h + c->off_g, c->g_dev, (size_t)n * c->out_dim * 4, hipMemcpyDeviceToHost, s2));
     c->jpeg_unit = false;
@@ -617,9 +657,10 @@ int omni_cam_set_poses(omni_cam* c, const double* poses7, int n_keyframes) {
     OMNI_REQUIRE(c && poses7, OMNI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_poses with a unit in flight (omni_cam_wait first)");
-    OMNI_REQUIRE(c->lm_on, OMNI_ERR_INVALID, "omni_cam_set_poses without a stereo model (omni_cam_set_stereo_model)");
-    OMNI_REQUIRE(n_keyframes >= 1 && (int64_t)n_keyframes * c->model.dirs_per_keyframe <= c->n_cap, OMNI_ERR_INVALID,
-                 "omni_cam_set_poses: %d key frames x %d directions, the handle holds %d directions", n_keyframes, c->model.dirs_per_keyframe, c->n_cap);
+    OMNI_REQUIRE(c->lm_on || c->dp_on, OMNI_ERR_INVALID, "omni_cam_set_poses without a stereo model (omni_cam_set_stereo_model)");
+    const int dirs = c->dp_on ? 1 : c->model.dirs_per_keyframe;              // (a mono unit with a depth model: one key frame per image)
+    OMNI_REQUIRE(n_keyframes >= 1 && (int64_t)n_keyframes * dirs <= c->n_cap, OMNI_ERR_INVALID,
+                 "omni_cam_set_poses: %d key frames x %d directions, the handle holds %d directions", n_keyframes, dirs, c->n_cap);
     memcpy(c->host + c->off_poses, poses7, (size_t)n_keyframes * 7 * sizeof(double));
     c->n_poses = n_keyframes;
     return OMNI_OK;
@@ -631,11 +672,78 @@ int omni_cam_landmarks(omni_cam* c, omni_cam_landmarks_result* out) {
     OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_landmarks with a unit in flight (omni_cam_wait first)");
     OMNI_REQUIRE(c->lm_unit, OMNI_ERR_INVALID, "omni_cam_landmarks: the last unit ran without a stereo model (omni_cam_set_stereo_model)");
     const char* h = c->host;
-    out->n_images = 2 * c->lm_n; out->n_dirs = c->lm_n; out->max_num = c->M;
+    out->n_images = c->cams * c->lm_n; out->n_dirs = c->lm_n; out->max_num = c->M;      // (a mono unit: the depth landmarks, count_3d per image)
     out->norm2d = reinterpret_cast<const float*>(h + c->off_norm);
     out->landmarks_3d = reinterpret_cast<const float*>(h + c->off_l3d);
     out->landmarks_flag = reinterpret_cast<const uint8_t*>(h + c->off_flag);
     out->count_3d = reinterpret_cast<const int*>(h + c->off_cnt);
+    return OMNI_OK;
+}
+
+// ---- depth landmarks inside a mono unit ----------------------------------------------------------------------------------------------------------------
+int omni_cam_set_depth_model(omni_cam* c, const omni_depth_model* model, const omni_camera_model* camera) {
+    OMNI_REQUIRE(c, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_depth_model with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->cams == 1, OMNI_ERR_INVALID, "omni_cam_set_depth_model: a stereo handle triangulates its landmarks (omni_cam_set_stereo_model), it reads no depth image");
+    if (!model) { c->dp_on = false; c->n_poses = 0; c->n_depth = 0; c->depth_ext = nullptr; return OMNI_OK; }
+    int rc;
+    if ((rc = omni::depth_check_model(model))) return rc;
+    const omni_camera_model cm = camera ? *camera : omni::cam::ideal();
+    if ((rc = omni::landmarks_check_camera(&cm))) return rc;
+    (void)hipSetDevice(c->c1->device);
+    const size_t have_at = ((size_t)c->n_cap * model->depth_width * model->depth_height * sizeof(uint16_t) + 255) & ~(size_t)255, bytes = have_at + (size_t)c->n_cap;
+    if (bytes != c->depth_bytes || have_at != c->depth_have) {                // (set-up time: no unit is in flight, the frees below wait for nothing of this handle)
+        c->dp_on = false;
+        if (c->d_depth) (void)hipFree(c->d_depth);
+        if (c->h_depth) (void)hipHostFree(c->h_depth);
+        c->d_depth = c->h_depth = nullptr; c->depth_bytes = 0;
+        OMNI_HIP_TRY(hipMalloc((void**)&c->d_depth, bytes));
+        OMNI_HIP_TRY(hipHostMalloc((void**)&c->h_depth, bytes, hipHostMallocDefault));
+        memset(c->h_depth, 0, bytes);
+        c->depth_bytes = bytes; c->depth_have = have_at;
+    }
+    c->dmodel = *model; c->dcamera = cm;
+    c->dp_on = true;
+    c->n_poses = 0; c->n_depth = 0; c->depth_ext = nullptr;
+    return OMNI_OK;
+}
+
+static int cam_depth_check(omni_cam* c, const char* who, int stride_elems, int n_images) {
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "%s with a unit in flight (omni_cam_wait first)", who);
+    OMNI_REQUIRE(c->dp_on, OMNI_ERR_INVALID, "%s without a depth model (omni_cam_set_depth_model)", who);
+    OMNI_REQUIRE(n_images >= 1 && n_images <= c->n_cap, OMNI_ERR_INVALID, "%s: %d images, the handle holds 1..%d", who, n_images, c->n_cap);
+    OMNI_REQUIRE(stride_elems >= c->dmodel.depth_width, OMNI_ERR_INVALID, "%s: a stride of %d elements for depth images %d wide", who, stride_elems, c->dmodel.depth_width);
+    return OMNI_OK;
+}
+
+int omni_cam_set_depth_host(omni_cam* c, const uint16_t* const* frames, int stride_elems, int n_images) {
+    OMNI_REQUIRE(c && frames, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc;
+    if ((rc = cam_depth_check(c, "omni_cam_set_depth_host", stride_elems, n_images))) return rc;
+    const int w = c->dmodel.depth_width, hgt = c->dmodel.depth_height;
+    uint16_t* dst = reinterpret_cast<uint16_t*>(c->h_depth);
+    uint8_t* have = c->h_depth + c->depth_have;
+    for (int i = 0; i < n_images; ++i) {
+        have[i] = frames[i] != nullptr;
+        if (!frames[i]) continue;                                             // (the kernel does not read the frame of an image without one)
+        uint16_t* d = dst + (size_t)i * w * hgt;
+        if (stride_elems == w) memcpy(d, frames[i], (size_t)w * hgt * sizeof(uint16_t));
+        else for (int y = 0; y < hgt; ++y) memcpy(d + (size_t)y * w, frames[i] + (size_t)y * stride_elems, (size_t)w * sizeof(uint16_t));
+    }
+    c->n_depth = n_images; c->depth_ext = nullptr;
+    return OMNI_OK;
+}
+
+int omni_cam_set_depth_dev(omni_cam* c, const uint16_t* depth_dev, int stride_elems, const uint8_t* have_host, int n_images) {
+    OMNI_REQUIRE(c && depth_dev, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc;
+    if ((rc = cam_depth_check(c, "omni_cam_set_depth_dev", stride_elems, n_images))) return rc;
+    uint8_t* have = c->h_depth + c->depth_have;
+    for (int i = 0; i < n_images; ++i) have[i] = have_host ? have_host[i] != 0 : 1;
+    c->n_depth = n_images; c->depth_ext = depth_dev; c->depth_ext_stride = stride_elems;
     return OMNI_OK;
 }
 

@@ -203,6 +203,11 @@ int landmarks_launch(hipStream_t stream, const omni_stereo_model& m, const omni_
                      float* l3d_up, float* l3d_down, uint8_t* flag_up, uint8_t* flag_down, int* count);
 int landmarks_check_model(const omni_stereo_model* m);
 int landmarks_check_camera(const omni_camera_model* cm);      // csrc/camera_plan.h's cam::check as an error code
+// depth_landmarks.hip: the depth landmarks of n_images images of ONE camera each (csrc/depth_plan.h); image i reads pose i of poses7_dev, depth image i of `depth`
+// (stride in elements) and have[i] (nullptr: all).  Asynchronous on `stream`; the caller has checked the model (depth_check_model), the lens and the sizes.
+int depth_landmarks_launch(hipStream_t stream, const omni_depth_model& m, const omni_camera_model& cm, const double* poses7_dev, int n_images, int max_num, const float* kps_xy,
+                           const int* n_kps, const uint16_t* depth, int stride, const uint8_t* have, float* norm2d, float* l3d, uint8_t* flag, int* count);
+int depth_check_model(const omni_depth_model* m);
 }  // namespace omni
 
 struct omni_jpeg;

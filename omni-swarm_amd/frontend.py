@@ -14,6 +14,9 @@ Camera geometry (liftProjective, SVD triangulation, loop_cam.cpp:73-106,405-454,
 (camera_model=: camodocal's PINHOLE with distortion or MEI; the ideal pinhole without one), the key frame's
 pose_drone set with set_poses() before every key frame; without a model it is left to the caller, for whom the 2-D key
 points, descriptors, global descriptors and the up/down match lists are everything those steps consume.
+CameraConfig::PINHOLE_DEPTH (generate_gray_depth_image_descriptor, :231-339): a capi.DepthModel (depth_model=) makes the
+object a MONO unit -- n_dirs images of one camera each, no down camera, no rows blanked -- whose lifted key points and
+depth landmarks (:260-304) come out of the unit too (csrc/depth_landmarks.hip); set_poses() and set_depth() before every unit.
 """
 from __future__ import annotations
 
@@ -26,10 +29,16 @@ class LoopCam:
     def __init__(self, ctx: capi.Context, sp_weights: dict, pca_comp, pca_mean, vlad_weights: dict, vlad_specs,
                  vlad_shape=(32, 112, 4096), width: int = 600, height: int = 480, thres: float = 0.015,
                  max_num: int = 200, precision: int = capi.PREC_F16, n_dirs: int = 4, fisheye: bool = True,
-                 accept_min_3d_pts: int = 0, stereo_model: capi.StereoModel = None, camera_model: capi.CameraModel = None):
+                 accept_min_3d_pts: int = 0, stereo_model: capi.StereoModel = None, camera_model: capi.CameraModel = None,
+                 depth_model: capi.DepthModel = None):
+        if depth_model is not None and stereo_model is not None:
+            raise ValueError("LoopCam: depth_model (PINHOLE_DEPTH, one camera per image) and stereo_model (an up / down pair per direction) are two camera configurations")
+        self.mono = depth_model is not None
+        if self.mono:
+            fisheye = False                        # loop_cam.cpp:536 blanks rows for STEREO_FISHEYE only
         self.ctx, self.W, self.H, self.n_dirs, self.max_num, self.fisheye = ctx, width, height, n_dirs, max_num, fisheye
         self.accept_min_3d_pts = accept_min_3d_pts
-        self.sp = capi.SuperPoint(ctx, sp_weights, pca_comp, pca_mean, width, height, thres, max_num, precision, 2 * n_dirs)
+        self.sp = capi.SuperPoint(ctx, sp_weights, pca_comp, pca_mean, width, height, thres, max_num, precision, (1 if self.mono else 2) * n_dirs)
         k, d, o = vlad_shape
         # MobileNetVLAD is ~50 small launches: on its own HIP stream they overlap SuperPoint's large convolutions
         import os
@@ -39,17 +48,24 @@ class LoopCam:
         self.out_dim = o
         self.dim = self.sp.desc_dim
         # the whole key frame as one asynchronous unit with a single pinned result block (csrc/cam.hip)
-        self.cam = capi.Cam(self.sp, self.vlad, n_dirs, o, capi.BF_OPENCV)
+        self.cam = capi.Cam(self.sp, self.vlad, n_dirs, o, capi.BF_OPENCV, mono=self.mono)
         self.stereo_model = stereo_model
         if stereo_model is not None:
             self.cam.set_stereo_model(stereo_model)
         self.camera_model = camera_model
-        if camera_model is not None:
+        self.depth_model = depth_model
+        if depth_model is not None:
+            self.cam.set_depth_model(depth_model, camera_model)      # (the lens travels with the depth model: a mono handle takes no set_camera_model)
+        elif camera_model is not None:
             self.cam.set_camera_model(camera_model)
 
     def set_poses(self, poses7):
         """pose_drone (xyz + quaternion wxyz) of the key frames of the NEXT unit, [n_keyframes][7]: needed before every key frame when a stereo_model is set"""
         self.cam.set_poses(poses7)
+
+    def set_depth(self, frames, stride: int = 0):
+        """depth_model: the depth frames ([H][W] u16 millimetres; None: no depth image, no landmarks) of the NEXT unit's images, copied before the call returns"""
+        self.cam.set_depth_host(frames, stride)
 
     def close(self):
         self.cam.close()
@@ -76,6 +92,14 @@ class LoopCam:
         n = r["global_desc"].shape[0]          # the unit's directions: n_dirs, or fewer after Cam.set_active
         nk = r["n_kps"]
         images = []
+        if self.mono:                            # one camera per image; the lifted key points and the depth landmarks computed inside the unit
+            lm = self.cam.landmarks()
+            for d in range(n):
+                nu = int(nk[d])
+                images.append({"landmarks_2d": r["kps_xy"][d, :nu].copy(), "feature_descriptor": r["desc"][d, :nu].copy(), "scores": r["scores"][d, :nu].copy(),
+                               "landmark_num": nu, "image_desc": r["global_desc"][d].copy(), "direction": 0, "landmarks_2d_norm": lm["norm2d"][d, :nu].copy(),
+                               "landmarks_3d": lm["landmarks_3d"][d, :nu].copy(), "landmarks_flag": lm["landmarks_flag"][d, :nu].copy(), "count_3d": int(lm["count_3d"][d])})
+            return {"images": images, "landmark_num": int(sum(i["landmark_num"] for i in images))}
         for d in range(n):
             nu, nd = int(nk[d]), int(nk[n + d])
             k = int(r["n_matches"][d]) if nu > self.accept_min_3d_pts else 0    # :388 `if (pts_up.size() > ACCEPT_MIN_3D_PTS)`

@@ -83,8 +83,14 @@ public:
         // STEREO_FISHEYE / STEREO_PINHOLE with `geometry`: the lifting and the up/down triangulation of generate_stereo_image_descriptor (loop_cam.cpp:397-444) run
         // inside the key-frame unit, f64 on the GPU (csrc/landmarks.hip: bit-identical to the host functions, tests/test_gpu_landmarks.py), and finish() copies the
         // landmarks out of the unit's result block instead of submitting one triangulation task per direction.  Off: the host path (fill_stereo_landmarks on the
-        // geometry pool).  PINHOLE_DEPTH reads its landmarks from the depth image on the host either way.  (set_device_landmarks: before the first key frame.)
+        // geometry pool).  PINHOLE_DEPTH has a switch of its own, below.  (set_device_landmarks: before the first key frame.)
         bool device_landmarks = true;
+        // PINHOLE_DEPTH with `geometry`: the lift of every key point and the depth landmarks of generate_gray_depth_image_descriptor (loop_cam.cpp:260-304) run inside
+        // the key-frame unit, f64 on the GPU (csrc/depth_landmarks.hip: bit-identical to fill_image_descriptor + fill_depth_landmarks, tests/test_gpu_depth_landmarks.py);
+        // the unit's depth frames are COPIED at push_keyframe / taken out of set_depth's range at enqueue and go up with the unit, and finish() copies the landmarks
+        // out of the unit's result block.  Off (the default: DESIGN.md section 0.2k has the measurements): the host path, both functions inline on the calling thread,
+        // the depth frames borrowed until the unit is finished.  (set_device_depth_landmarks: before the first key frame.)
+        bool device_depth_landmarks = false;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -462,6 +468,28 @@ public:
             }
         return m;
     }
+    // ---- PINHOLE_DEPTH's depth landmarks inside the key-frame unit (Config::device_depth_landmarks) ---------------------------------------------------------------
+    bool device_depth_landmarks() const { return cfg_.device_depth_landmarks && cfg_.geometry && cfg_.camera_configuration == 2 && !shard_; }      // (the sharded database builds no messages)
+    // what every lane's unit is given: the intrinsics, the depth window, the accept rule and the extrinsic finish() stamps on the messages (view 0's, as a PoseMsg);
+    // the depth images have the networks' size (the reference reads them at network-size key-point coordinates)
+    omni_depth_model depth_model() const {
+        omni_depth_model m{};
+        m.fx = cfg_.fx; m.fy = cfg_.fy; m.cx = cfg_.cx; m.cy = cfg_.cy; m.depth_near = cfg_.depth_near; m.depth_far = cfg_.depth_far; m.accept_min_3d_pts = cfg_.accept_min_3d_pts;
+        m.depth_width = cfg_.width; m.depth_height = cfg_.height;
+        const PoseMsg e = to_msg(view_extrinsic(0, true));
+        std::copy(e.position, e.position + 3, m.extrinsic); std::copy(e.quat_wxyz, e.quat_wxyz + 4, m.extrinsic + 3);
+        return m;
+    }
+    // before the first key frame: switches the stage on or off on every lane (what the C entry point omni_pipeline_set_device_depth_landmarks sets).  Refused for a
+    // stereo camera configuration, which reads no depth image
+    void set_device_depth_landmarks(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (cfg_.camera_configuration != 2) throw std::runtime_error("set_device_depth_landmarks: camera_configuration is not 2 (PINHOLE_DEPTH)");
+        if (any_keyframe_seen_) throw std::runtime_error("set_device_depth_landmarks after the first key frame");
+        cfg_.device_depth_landmarks = on;
+        apply_stereo_model();
+    }
+    bool device_depth_landmarks_config() const { return cfg_.device_depth_landmarks; }      // the switch as set, whatever the mode makes of it
     // ---- the homography RANSAC of the loop candidates on the GPU (Config::device_homography) --------------------------------------------------------------
     bool device_homography() const { return cfg_.device_homography && cfg_.geometry && !shard_; }      // (the sharded database builds no messages)
     bool device_homography_config() const { return cfg_.device_homography; }      // the switch as set, whatever the mode makes of it
@@ -536,8 +564,12 @@ private:
     }
     void apply_stereo_model(Lane& l) {
         const omni_stereo_model m = stereo_model();
-        if (cfg_.stereo()) l.cam.set_camera_model(&cfg_.camera_model);      // (a mono unit runs no landmark stage: PINHOLE_DEPTH lifts on the host)
+        if (cfg_.stereo()) l.cam.set_camera_model(&cfg_.camera_model);      // (a mono unit's lens travels with its depth model)
         l.cam.set_stereo_model(device_landmarks() ? &m : nullptr);
+        if (!cfg_.stereo()) {
+            const omni_depth_model d = depth_model();
+            l.cam.set_depth_model(device_depth_landmarks() ? &d : nullptr, &cfg_.camera_model);
+        }
     }
     void apply_stereo_model() {
         for (auto& l : lanes_) apply_stereo_model(*l);
@@ -545,13 +577,22 @@ private:
     }
     // pose_drone of the m key frames of the unit about to be enqueued on `lane` -- the PoseMsgs finish() stamps on its messages
     void unit_poses(Lane* lane, int m, int64_t first_id) {
-        if (!device_landmarks()) return;
+        if (!device_landmarks() && !device_depth_landmarks()) return;
         pose_stage_.resize((size_t)7 * m);
         for (int k = 0; k < m; ++k) {
             const PoseMsg p = lane->meta.empty() ? pose_of(first_id + k) : lane->meta[(size_t)k].pose;
             std::copy(p.position, p.position + 3, pose_stage_.data() + 7 * k); std::copy(p.quat_wxyz, p.quat_wxyz + 4, pose_stage_.data() + 7 * k + 3);
         }
         lane->cam.set_poses(pose_stage_.data(), m);
+        if (!device_depth_landmarks()) return;
+        // ... and its depth frames: the streaming intake's copies (push_keyframe), or run()'s key frames taken out of set_depth's range; nullptr: no depth image
+        depth_frames_.resize((size_t)m);
+        for (int k = 0; k < m; ++k) {
+            const int64_t kf_id = first_id + k;
+            depth_frames_[(size_t)k] = !lane->meta.empty() ? lane->meta[(size_t)k].depth
+                                       : (depth_ && kf_id >= depth_base_ && kf_id < depth_base_ + depth_n_) ? depth_ + (size_t)(kf_id - depth_base_) * cfg_.width * cfg_.height : nullptr;
+        }
+        lane->cam.set_depth_host(depth_frames_.data(), cfg_.width, m);
     }
 public:
 
@@ -588,8 +629,8 @@ public:
     template <class Params> void apply_params(const Params& p) { p.to_detector(det_); p.to_geometry(geo_); }
 
     // PINHOLE_DEPTH: the depth images (u16 millimetres, height x width, rows packed) of key frames msg_id = first_msg_id .. first_msg_id + n - 1,
-    // image i at depth + i * width * height.  Borrowed: they must stay valid until the run() that consumes them returns.  A key frame without
-    // one gets no landmarks.
+    // image i at depth + i * width * height.  Borrowed: they must stay valid until the run() that consumes them returns (with device_depth_landmarks a
+    // unit's frames are read when it is enqueued, inside that run()).  A key frame without one gets no landmarks.
     void set_depth(int64_t first_msg_id, const uint16_t* depth, int64_t n) { depth_base_ = first_msg_id; depth_ = depth; depth_n_ = n; }
 
     // N > 1 GPUs, one process per GPU: the database becomes one row-sharded index over all ranks (omni_shard_*, RCCL inside libomni_hip.so).
@@ -744,7 +785,8 @@ public:
     // = down cameras (PINHOLE_DEPTH: the one gray image; STEREO_PINHOLE: images[0] = the left frame, images[1] = the right frame, of the camera's size when
     // Config::src_width is set; the raw-fisheye mode: images[0] = the up frame, images[1] = the down frame of the fisheye camera's size), each Config::in_height() rows of `stride` bytes -- the key-frame id and stamp (StereoFrame::keyframe_id,
     // ::stamp), VIO's pose, and prevent_adding_db (:156: a non-key frame that moved less than min_movement_keyframe is matched but not added);
-    // depth: PINHOLE_DEPTH's 16-bit depth image (rows packed), borrowed until the key frame's unit is finished
+    // depth: PINHOLE_DEPTH's 16-bit depth image (rows packed), borrowed until the key frame's unit is finished -- with device_depth_landmarks it is copied before
+    // push_keyframe returns, like the images
     struct KeyframeIn {
         const uint8_t* const* images = nullptr; int stride = 0;
         int64_t msg_id = 0; double stamp = 0; PoseMsg pose_drone; bool prevent_adding_db = false;
@@ -799,6 +841,12 @@ public:
                 for (int y = 0; y < cfg_.in_height(); ++y) std::memcpy(dst + (size_t)y * cfg_.in_width(), src + (size_t)y * k.stride, (size_t)cfg_.in_width());
             }
         SlotMeta sm; sm.msg_id = k.msg_id; sm.stamp = k.stamp; sm.pose = k.pose_drone; sm.prevent_adding_db = k.prevent_adding_db; sm.depth = k.depth;
+        if (k.depth && device_depth_landmarks()) {                // the unit reads the frame when it leaves for the GPU: the lane's own copy, not the caller's buffer
+            const size_t dimg = (size_t)cfg_.width * cfg_.height;
+            if (open_->depth_stage.size() < dimg * MB) open_->depth_stage.resize(dimg * MB);
+            std::memcpy(open_->depth_stage.data() + dimg * m, k.depth, dimg * sizeof(uint16_t));
+            sm.depth = open_->depth_stage.data() + dimg * m;
+        }
         open_->meta.push_back(sm);
         const bool full = (int)open_->meta.size() == MB;
         const bool idle = cfg_.dispatch_when_idle && stream_pending_.empty();
@@ -870,6 +918,7 @@ private:
         std::vector<std::vector<uint8_t>> jfiles[2];   // streaming intake with compressed_images: the unit's JPEG files, left then right camera, copied at the push
         int jpeg_frames = 0;                           // > 0: the unit in flight came as that many JPEG files (their statuses are read when it is finished)
         uint8_t* stage = nullptr;                      // pinned block the streaming intake packs the unit's images into
+        std::vector<uint16_t> depth_stage;             // streaming intake with device_depth_landmarks: the unit's depth frames [mb][height][width], copied at the push
         size_t stage_bytes = 0;
         ~Lane() { if (stage) omni_host_free(stage); }
         Context sp_ctx, vlad_ctx;
@@ -1008,7 +1057,8 @@ private:
         // can change landmark_num (generate_gray_depth_image_descriptor drops an image below ACCEPT_MIN_3D_PTS): everything is built first, as before.
         const bool defer_heavy = !cfg_.geometry;
         // the unit's own landmarks (Config::device_landmarks): lifted floats, 3-D points and flags of every image, already in the pinned block
-        const bool dev_lm = device_landmarks();
+        const bool dev_dp = device_depth_landmarks();
+        const bool dev_lm = device_landmarks() || dev_dp;
         const omni_cam_landmarks_result lmr = dev_lm ? lane.cam.landmarks() : omni_cam_landmarks_result{};
         // the unit's own JPEG files of its main images (Config::send_img), already in the lane's pinned block
         const bool jpg = send_img();
@@ -1037,7 +1087,9 @@ private:
                 }
                 stamp_image_descriptor(im, stamp, cfg_.self_id, to_msg(view_extrinsic(d, true)), pose, kf_id);
                 if (cfg_.geometry && !cfg_.stereo()) {
-                    // generate_gray_depth_image_descriptor's landmarks (loop_cam.cpp:260-304): read from the depth image under each key point
+                    // generate_gray_depth_image_descriptor's landmarks (loop_cam.cpp:260-304): read from the depth image under each key point -- by the unit
+                    // itself with device_depth_landmarks (the message is complete as it comes out of the block), else here
+                    if (dev_dp) continue;
                     const bool have = streamed ? lane.meta[m].depth != nullptr : (depth_ && kf_id >= depth_base_ && kf_id < depth_base_ + depth_n_);
                     if (have) fill_depth_landmarks(im, streamed ? lane.meta[m].depth : depth_ + (size_t)(kf_id - depth_base_) * cfg_.width * cfg_.height, cfg_.width, cfg_.width, cfg_.height, cfg_.depth_near,
                                                    cfg_.depth_far, cfg_.accept_min_3d_pts, lift64_);
@@ -1177,6 +1229,7 @@ private:
     std::atomic<int64_t> jpeg_corrupt_{0};
     bool any_keyframe_seen_ = false;            // set_device_landmarks is refused from the first key frame on
     std::vector<double> pose_stage_;            // unit_poses: the unit's poses on their way into the handle's pinned staging
+    std::vector<const uint16_t*> depth_frames_; // ... and its depth frames' addresses
     std::vector<FisheyeFrameDescriptor> frames_;
     std::unique_ptr<IndexFlatIP> shard_index_;
     omni_shard* shard_ = nullptr;

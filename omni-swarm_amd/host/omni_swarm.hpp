@@ -409,6 +409,14 @@ public:
         check(omni_cam_landmarks(h_, &r), "omni_cam_landmarks");
         return r;
     }
+    // the depth landmarks inside a MONO unit (csrc/depth_landmarks.hip; loop_cam.cpp:260-304): set_depth_model once (nullptr: off again; the lens travels with
+    // it), then set_poses (one key frame per image) and set_depth_host / set_depth_dev (the next unit's depth frames; a null frame: no landmarks for that image)
+    // before every enqueue, landmarks() after wait().  set_depth_host copies the frames before it returns; set_depth_dev borrows them until wait()
+    void set_depth_model(const omni_depth_model* model, const omni_camera_model* camera = nullptr) { check(omni_cam_set_depth_model(h_, model, camera), "omni_cam_set_depth_model"); }
+    void set_depth_host(const uint16_t* const* frames, int stride_elems, int n_images) { check(omni_cam_set_depth_host(h_, frames, stride_elems, n_images), "omni_cam_set_depth_host"); }
+    void set_depth_dev(const uint16_t* depth_dev, int stride_elems, const uint8_t* have_host, int n_images) {
+        check(omni_cam_set_depth_dev(h_, depth_dev, stride_elems, have_host, n_images), "omni_cam_set_depth_dev");
+    }
     // send_img inside the unit (csrc/jpeg.hip; encode_image, loop_cam.cpp:56-71): set_jpeg once (quality 0: off again), jpeg() after wait() -- the unit's MAIN
     // images (up / left cameras; every image of a mono handle) as baseline JPEG files, libjpeg's defaults (csrc/jpeg_plan.h; cv::imencode's parity unpinned)
     void set_jpeg(int quality, int64_t capacity_per_image) { check(omni_cam_set_jpeg(h_, quality, capacity_per_image), "omni_cam_set_jpeg"); }

@@ -52,6 +52,10 @@ CAMERA_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_camera.so")
 CAMERA_SYMBOLS = ["omni_camera_last_error", "omni_pipeline_set_camera_model", "omni_pipeline_get_camera_model", "omni_camera_from_yaml",
                   "omni_pipeline_create_from_launch_camera", "omni_pipeline_frame_landmarks"]
 _camera_lib = None
+# where the pipeline reads PINHOLE_DEPTH's depth landmarks: include/omni_host_depth.h, lib/libomni_host_depth.so (the same handle)
+DEPTH_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_depth.so")
+DEPTH_SYMBOLS = ["omni_depth_last_error", "omni_pipeline_set_device_depth_landmarks", "omni_pipeline_get_device_depth_landmarks"]
+_depth_lib = None
 
 
 def lib():
@@ -177,6 +181,20 @@ def landmarks_lib():
     return _landmarks_lib
 
 
+def depth_lib():
+    global _depth_lib
+    if _depth_lib is None:
+        lib()                                   # (libomni_hip.so / OMNI_LIB first, as for the other host libraries)
+        if not os.path.exists(DEPTH_LIB_PATH):
+            raise OSError(f"{DEPTH_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(DEPTH_LIB_PATH)
+        L.omni_depth_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_device_depth_landmarks.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_device_depth_landmarks.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        _depth_lib = L
+    return _depth_lib
+
+
 def camera_lib():
     """libomni_host_camera.so (include/omni_host_camera.h): the lens model of the key-frame pipeline, the camodocal file reader"""
     global _camera_lib
@@ -294,7 +312,8 @@ class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
-                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None):
+                 stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
+                 device_depth_landmarks=None):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -315,6 +334,9 @@ class KeyframePipeline:
         camera_model: a dict(type="PINHOLE" | "MEI", k1=, k2=, p1=, p2=, xi=) (what camera_from_yaml returns; its "intrinsics", when present, replace fx fy cx cy)
         or a capi.CameraModel = the lens behind the intrinsics, as the reference's camodocal file describes it: every lift -- landmarks_2d_norm, the triangulation on
         either path, PINHOLE_DEPTH's depth landmarks -- undoes it (csrc/camera_plan.h).  None: the ideal pinhole.  Refused in the raw_fisheye mode.
+        device_depth_landmarks: True / False = PINHOLE_DEPTH's lifted key points and depth landmarks of a `geometry` pipeline inside the key-frame unit on the GPU
+        (every depth image is then copied at push_keyframe / read when run() enqueues its unit) / on the calling thread (the same bits either way); None: the
+        library's default, which is off.  Refused for the stereo configurations.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -351,6 +373,8 @@ class KeyframePipeline:
             self.set_device_landmarks(device_landmarks)
         if device_homography is not None:
             self.set_device_homography(device_homography)
+        if device_depth_landmarks is not None:
+            self.set_device_depth_landmarks(device_depth_landmarks)
         if device_pnp is not None:
             self.set_device_pnp(device_pnp)
         if send_img:
@@ -391,6 +415,18 @@ class KeyframePipeline:
         """before the first key frame: stereo landmarks inside the key-frame unit (GPU) or on the host's geometry threads"""
         if landmarks_lib().omni_pipeline_set_device_landmarks(self.h, int(bool(on))):
             raise capi.OmniError(f"omni_pipeline_set_device_landmarks: {landmarks_lib().omni_landmarks_last_error().decode()}")
+
+    def set_device_depth_landmarks(self, on: bool):
+        """before the first key frame, PINHOLE_DEPTH only: the depth landmarks inside the key-frame unit (GPU) or on the calling thread"""
+        if depth_lib().omni_pipeline_set_device_depth_landmarks(self.h, int(bool(on))):
+            raise capi.OmniError(f"omni_pipeline_set_device_depth_landmarks: {depth_lib().omni_depth_last_error().decode()}")
+
+    def device_depth_landmarks(self) -> bool:
+        """the switch as it was set"""
+        on = C.c_int(0)
+        if depth_lib().omni_pipeline_get_device_depth_landmarks(self.h, C.byref(on)):
+            raise capi.OmniError(f"omni_pipeline_get_device_depth_landmarks: {depth_lib().omni_depth_last_error().decode()}")
+        return bool(on.value)
 
     def _jpegdec(self, rc, what):
         if rc:
