@@ -128,7 +128,7 @@ def test_the_arithmetic_is_stated_once():
     assert '#include "landmark_plan.h"' in plan and "#pragma clang fp contract(off)" in open(os.path.join(PKG, "csrc", "landmark_plan.h")).read()
     mk = open(os.path.join(PKG, "Makefile")).read()
     assert "build/depth_landmarks.o: HIPFLAGS += -ffp-contract=off" in mk and "lib/libomni_host_depth.so" in mk
-    for f in ("depth_landmarks.hip", "depth_host.cpp", "cam.hip"):
+    for f in ("depth_landmarks.hip", "depth_host.cpp", "cam.hip", "cam_input.h"):
         text = re.sub(r"//.*", "", open(os.path.join(PKG, "csrc", f)).read())
         assert not re.search(r"\brint\(", text) and "/ 1000" not in text and "> 640" not in text, f
     kernel = re.sub(r"//.*", "", open(os.path.join(PKG, "csrc", "depth_landmarks.hip")).read())

@@ -55,7 +55,7 @@ def test_the_arithmetic_is_stated_once():
     code = re.sub(r"//.*", "", plan)
     for word in ("hip/", "common.h", "std::vector", "<vector>", "<algorithm>", "float", "double"):
         assert word not in code, word
-    for f in ("jpeg.hip", "cam.hip", "jpeg_host.cpp"):
+    for f in ("jpeg.hip", "cam.hip", "cam_input.h", "jpeg_host.cpp"):
         text = re.sub(r"//.*", "", open(os.path.join(PKG, "csrc", f)).read())
         for word in ("4433", "15137", "0x7d", "5000 /"):                     # the DCT's constants, the Huffman table, the quality rule
             assert word not in text, (f, word)

@@ -60,7 +60,7 @@ def test_the_camera_configuration_is_asked_one_question_at_a_time():
     # no HIP in the plan's header, and no second place that makes a coefficient
     plan = open(os.path.join(PKG, "csrc", "resize_plan.h")).read()
     assert "hip/" not in plan and "__device__" not in plan and "common.h" not in plan
-    for f in ("resize.hip", "cam.hip"):
+    for f in ("resize.hip", "cam.hip", "cam_input.h"):
         text = open(os.path.join(PKG, "csrc", f)).read()
         assert "nearbyint" not in text and "rint(" not in text and "floor" not in text, f
     assert "resize_plan(src_width, src_height, dst_width, dst_height)" in open(os.path.join(PKG, "csrc", "resize.hip")).read()
