@@ -807,6 +807,48 @@ int        omni_cam_jpegdec_status(omni_cam* cam, int* status, int n_frames);
 int        omni_cam_enqueue_fisheye_jpeg_host(omni_cam* cam, omni_flatten* up, omni_flatten* down, const uint8_t* const* up_files, const int64_t* up_sizes,
                                               const uint8_t* const* down_files, const int64_t* down_sizes, int n_keyframes, int first_view, int fisheye_mask);
 
+/* ---- PCA fit: components_.csv / mean_.csv from the key-frame stream (csrc/pca_plan.h) ------------------------------------------------------------------------
+ * The reference dumps every key point's 256-d descriptor to a text file (OUTPUT_RAW_SUPERPOINT_DESC, loop_cam.cpp:51-53, 577-582) and fits
+ * sklearn.decomposition.PCA(64) on the dump in a notebook.  Here the fit's moments -- the count n, the sum s [256] and the second-moment matrix S [256][256], f64
+ * -- are accumulated in HBM from what every SuperPoint pass leaves there, and only they cross PCIe.  A row is the descriptor a handle WITHOUT PCA returns
+ * (raw / the channel's norm across the image's key points, f32, widened to f64); rows with a non-finite element (a channel that is zero at every key point of
+ * an image: 0/0, in the reference too) are left out and counted in `skipped`.  Per kept row, in stream order: n += 1, s[c] += x[c], S[i][j] = fma(x[i], x[j],
+ * S[i][j]) -- one chain per entry, so the moments depend on the row sequence alone, not on batch sizes or on how the stream was cut into calls, and equal
+ * omni_pca_moments_host bit for bit. */
+typedef struct omni_pcafit omni_pcafit;
+omni_pcafit* omni_pcafit_create(omni_ctx* ctx);            /* an empty accumulator in HBM on ctx's device */
+void         omni_pcafit_destroy(omni_pcafit* fit);        /* waits for its work; a handle it is still attached to lets go of it first */
+int          omni_pcafit_reset(omni_pcafit* fit);          /* waits for what is enqueued, then n = skipped = 0, s = S = 0 */
+/* the rows of one pass: raw_desc [batch][max_num][256] f32, norm_partial [batch][8][256] f32 (per-channel sums of squares over eight key-point segments),
+ * n_kps [batch] (clamped to 0 .. max_num).  Asynchronous on the fit's context; batch >= 1, 1 <= max_num <= 1024 */
+int          omni_pcafit_enqueue_rows_dev(omni_pcafit* fit, const float* raw_desc_dev, const float* norm_partial_dev, const int* n_kps_dev, int batch, int max_num);
+/* With a fit attached every forward pass of the handle (omni_sp_infer, omni_sp_enqueue_dev, a key-frame unit that runs on the handle) enqueues the accumulation
+ * on the pass's own stream behind the channel norms; results of the pass are unchanged.  NULL detaches: the pass then launches what it launched before, and so
+ * does destroying either of the two.  The fit must have been created on the handle's own context (one stream: nothing to order between the pass, other enqueues
+ * and the fit's readers), and one fit serves one handle at a time.  OMNI_ERR_INVALID when the fit's context is on another device, is another context of the
+ * same device, or the fit is attached to another handle.  (omni_sp_postprocess_dense, a test hook, never accumulates.) */
+int          omni_sp_set_pcafit(omni_sp* sp, omni_pcafit* fit_or_null);
+/* both wait for the fit's work.  S_full [256][256] is handed out mirrored to a full symmetric matrix */
+int          omni_pcafit_stats(omni_pcafit* fit, int64_t* n, int64_t* skipped);
+int          omni_pcafit_moments(omni_pcafit* fit, double* s256, double* S_full);
+/* two accumulators on the host (as omni_pcafit_moments hands them out): *n += n_right, s += s_right, S += S_right element-wise */
+int          omni_pcafit_merge_host(int64_t* n, double* s256, double* S_full, int64_t n_right, const double* s256_right, const double* S_full_right);
+/* C = (S - s s^T / n) / (n - 1), mean = s / n, cyclic Jacobi in f64 on the host; eigenvalues descending (ties to the lower index), the first pca_dim eigenvectors
+ * are the rows of components [pca_dim][256], each with its entry of largest magnitude positive (ties to the lowest column).  Any output may be NULL:
+ * components / mean in f64 and f32, explained_variance [pca_dim], *total_variance = trace(C).  OMNI_ERR_INVALID with a message for n < 2, pca_dim outside
+ * 1 .. 256, n <= pca_dim */
+int          omni_pca_solve_host(int64_t n, const double* s256, const double* S_full, int pca_dim, double* components, float* components_f32, double* mean,
+                                 float* mean_f32, double* explained_variance, double* total_variance);
+int          omni_pcafit_solve(omni_pcafit* fit, int pca_dim, double* components, float* components_f32, double* mean, float* mean_f32,
+                               double* explained_variance, double* total_variance);      /* = omni_pcafit_stats + omni_pcafit_moments + omni_pca_solve_host */
+/* csrc/pca_plan.h compiled by g++ into the library: omni_pcafit_enqueue_rows_dev on host arrays, without a GPU.  *n, *skipped, s256 and S_full are read and
+ * updated (zeros for a new accumulator; of S_full the upper triangle is read, and it is mirrored on return) */
+int          omni_pca_moments_host(const float* raw_desc, const float* norm_partial, const int* n_kps, int batch, int max_num, int64_t* n, int64_t* skipped,
+                                   double* s256, double* S_full);
+/* components_.csv (one component per line, comma separated) and mean_.csv (one value per line), "%.9g": what every SuperPoint handle here loads, read back to
+ * the same f32 (a denormal value is written as 0: the handles' reader refuses denormals) */
+int          omni_pca_write_csv(const char* comp_path, const char* mean_path, const float* components_f32, const float* mean_f32, int pca_dim);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ SYMBOLS = [
     "omni_jpeg_decode_host", "omni_jpeg_decode_parallel_host", "omni_jpeg_decode_restart_parallel_host", "omni_jpegdec_last_chunks", "omni_jpeg_decode_plain_parallel_host", "omni_jpegdec_last_seam", "omni_jpegdec_debug_state_buffer",
     "omni_jpegdec_last_unstuff", "omni_jpegdec_debug_in_buffer", "omni_jpegdec_unstuff_dev", "omni_jpeg_unstuff_tile_bytes", "omni_jpeg_unstuff_host", "omni_jpeg_unstuff_tiled_host", "omni_jpeg_scan_end",
     "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
+    "omni_pcafit_create", "omni_pcafit_destroy", "omni_pcafit_reset", "omni_pcafit_enqueue_rows_dev", "omni_sp_set_pcafit", "omni_pcafit_stats", "omni_pcafit_moments",
+    "omni_pcafit_merge_host", "omni_pca_solve_host", "omni_pcafit_solve", "omni_pca_moments_host", "omni_pca_write_csv",
 ]
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
@@ -374,6 +376,19 @@ def lib():
     sig("omni_shard_step_wait", C.c_int, [_vp, _fp, _i64p])
     sig("omni_shard_last_exchange_us", C.c_int, [_vp, _fp, _fp])
     sig("omni_shard_search", C.c_int, [_vp, C.c_int, _fp, C.c_int, _fp, _i64p])
+    _dp = C.POINTER(C.c_double)
+    sig("omni_pcafit_create", _vp, [_vp])
+    sig("omni_pcafit_destroy", None, [_vp])
+    sig("omni_pcafit_reset", C.c_int, [_vp])
+    sig("omni_pcafit_enqueue_rows_dev", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int])
+    sig("omni_sp_set_pcafit", C.c_int, [_vp, _vp])
+    sig("omni_pcafit_stats", C.c_int, [_vp, _i64p, _i64p])
+    sig("omni_pcafit_moments", C.c_int, [_vp, _dp, _dp])
+    sig("omni_pcafit_merge_host", C.c_int, [_i64p, _dp, _dp, C.c_int64, _dp, _dp])
+    sig("omni_pca_solve_host", C.c_int, [C.c_int64, _dp, _dp, C.c_int, _dp, _fp, _dp, _fp, _dp, _dp])
+    sig("omni_pcafit_solve", C.c_int, [_vp, C.c_int, _dp, _fp, _dp, _fp, _dp, _dp])
+    sig("omni_pca_moments_host", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _i64p, _i64p, _dp, _dp])
+    sig("omni_pca_write_csv", C.c_int, [C.c_char_p, C.c_char_p, _fp, _fp, C.c_int])
     if L.omni_abi_version() != ABI_VERSION:
         raise OmniError("libomni_hip.so ABI version mismatch")
     _lib = L
@@ -577,6 +592,12 @@ class SuperPoint:
         _check(lib().omni_sp_debug_layer(self.h, name.encode(), batch, _pf(out), C.byref(c), C.byref(h), C.byref(w)))
         return out
 
+    def set_pcafit(self, fit: "PcaFit | None"):
+        """omni_sp_set_pcafit: every pass of this handle adds its rows to `fit` (None: detach).  `fit` must have been made on this handle's Context and serves one
+        handle at a time; closing either of the two detaches"""
+        _check(lib().omni_sp_set_pcafit(self.h, fit.h if fit is not None else None))
+        self._pcafit = fit
+
     def last_plan(self) -> int:
         """The kernel forms of the last pass as bits (include/omni_hip.h omni_sp_last_plan)."""
         return lib().omni_sp_last_plan(self.h)
@@ -591,6 +612,126 @@ class SuperPoint:
                 out.append({"stage": name, "ms": float(ms[i]), "flops_per_image": lib().omni_sp_stage_flops(self.h, i),
                             "tiles_left_out": lib().omni_sp_stage_tiles_left_out(self.h, i)})
         return out
+
+
+PCA_DIM_IN = 256      # csrc/pca_plan.h kDim
+
+
+class PcaMoments:
+    """The accumulator of a PCA fit on the host (csrc/pca_plan.h): n, skipped, s [256], S [256][256] (symmetric), float64"""
+
+    def __init__(self, n=0, skipped=0, s=None, S=None):
+        self.n, self.skipped = int(n), int(skipped)
+        self.s = np.zeros(PCA_DIM_IN, np.float64) if s is None else np.ascontiguousarray(s, np.float64).reshape(PCA_DIM_IN).copy()
+        self.S = np.zeros((PCA_DIM_IN, PCA_DIM_IN), np.float64) if S is None else np.ascontiguousarray(S, np.float64).reshape(PCA_DIM_IN, PCA_DIM_IN).copy()
+
+    def add_rows(self, raw_desc, norm_partial, n_kps) -> "PcaMoments":
+        """omni_pca_moments_host (no GPU): the stand-in of PcaFit.enqueue_rows_dev.  raw_desc [B][M][256], norm_partial [B][8][256] float32, n_kps [B] int32"""
+        raw, part, n_kps = _f32(raw_desc), _f32(norm_partial), np.ascontiguousarray(n_kps, np.int32)
+        if raw.ndim != 3 or raw.shape[2] != PCA_DIM_IN or part.shape != (raw.shape[0], 8, PCA_DIM_IN) or n_kps.shape != (raw.shape[0],):
+            raise ValueError(f"PcaMoments.add_rows: raw_desc {raw.shape}, norm_partial {part.shape}, n_kps {n_kps.shape}")
+        n, sk = C.c_int64(self.n), C.c_int64(self.skipped)
+        _check(lib().omni_pca_moments_host(raw.ctypes.data, part.ctypes.data, n_kps.ctypes.data, raw.shape[0], raw.shape[1], C.byref(n), C.byref(sk),
+                                           self.s.ctypes.data_as(C.POINTER(C.c_double)), self.S.ctypes.data_as(C.POINTER(C.c_double))))
+        self.n, self.skipped = n.value, sk.value
+        return self
+
+    def add_descriptors(self, descs) -> "PcaMoments":
+        """rows given as the 256-d descriptors of one image each (what a handle without PCA returns, [n][256] float32): raw = the descriptor, norm = 1"""
+        for d in descs:
+            d = _f32(d).reshape(-1, PCA_DIM_IN)
+            if len(d) == 0:
+                continue
+            part = np.zeros((1, 8, PCA_DIM_IN), np.float32)
+            part[0, 0] = 1.0
+            self.add_rows(d[None], part, np.array([len(d)], np.int32))
+        return self
+
+    def merge(self, right: "PcaMoments") -> "PcaMoments":
+        """omni_pcafit_merge_host: n, s, S += right's (skipped too)"""
+        n = C.c_int64(self.n)
+        dp = C.POINTER(C.c_double)
+        _check(lib().omni_pcafit_merge_host(C.byref(n), self.s.ctypes.data_as(dp), self.S.ctypes.data_as(dp), right.n, right.s.ctypes.data_as(dp), right.S.ctypes.data_as(dp)))
+        self.n, self.skipped = n.value, self.skipped + right.skipped
+        return self
+
+    def solve(self, pca_dim: int = 64) -> dict:
+        return pca_solve_host(self.n, self.s, self.S, pca_dim)
+
+
+def _pca_outputs(pca_dim: int):
+    k = max(1, min(int(pca_dim), PCA_DIM_IN))
+    return {"components": np.zeros((k, PCA_DIM_IN), np.float64), "components_f32": np.zeros((k, PCA_DIM_IN), np.float32), "mean": np.zeros(PCA_DIM_IN, np.float64),
+            "mean_f32": np.zeros(PCA_DIM_IN, np.float32), "explained_variance": np.zeros(k, np.float64)}
+
+
+def _pca_out_args(o, tv):
+    dp = C.POINTER(C.c_double)
+    return (o["components"].ctypes.data_as(dp), _pf(o["components_f32"]), o["mean"].ctypes.data_as(dp), _pf(o["mean_f32"]), o["explained_variance"].ctypes.data_as(dp), C.byref(tv))
+
+
+def pca_solve_host(n: int, s, S, pca_dim: int = 64) -> dict:
+    """omni_pca_solve_host (no GPU): components [pca_dim][256] and mean [256] in float64 and float32, explained_variance [pca_dim], total_variance"""
+    s, S = np.ascontiguousarray(s, np.float64).reshape(PCA_DIM_IN), np.ascontiguousarray(S, np.float64).reshape(PCA_DIM_IN, PCA_DIM_IN)
+    o, tv = _pca_outputs(pca_dim), C.c_double()
+    dp = C.POINTER(C.c_double)
+    _check(lib().omni_pca_solve_host(int(n), s.ctypes.data_as(dp), S.ctypes.data_as(dp), int(pca_dim), *_pca_out_args(o, tv)))
+    o["total_variance"] = tv.value
+    return o
+
+
+def pca_write_csv(comp_path: str, mean_path: str, components_f32, mean_f32):
+    """omni_pca_write_csv: components_.csv / mean_.csv as every SuperPoint handle here loads them"""
+    comp, mean = _f32(components_f32), _f32(mean_f32).reshape(-1)
+    if comp.ndim != 2 or comp.shape[1] != PCA_DIM_IN or mean.shape != (PCA_DIM_IN,):
+        raise ValueError(f"pca_write_csv: components {comp.shape}, mean {mean.shape}")
+    _check(lib().omni_pca_write_csv(os.fsencode(comp_path), os.fsencode(mean_path), _pf(comp), _pf(mean), comp.shape[0]))
+
+
+class PcaFit:
+    """omni_pcafit: the moments of a PCA fit accumulated in HBM (csrc/pca_fit.hip); attach with SuperPoint.set_pcafit or feed rows with enqueue_rows_dev"""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.h = lib().omni_pcafit_create(ctx.h)
+        if not self.h:
+            raise OmniError(f"omni_pcafit_create failed: {lib().omni_last_error().decode()}")
+        ctx._adopt(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().omni_pcafit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(lib().omni_pcafit_reset(self.h))
+
+    def enqueue_rows_dev(self, raw_desc_dev: int, norm_partial_dev: int, n_kps_dev: int, batch: int, max_num: int):
+        _check(lib().omni_pcafit_enqueue_rows_dev(self.h, raw_desc_dev, norm_partial_dev, n_kps_dev, batch, max_num))
+
+    def stats(self):
+        n, sk = C.c_int64(), C.c_int64()
+        _check(lib().omni_pcafit_stats(self.h, C.byref(n), C.byref(sk)))
+        return n.value, sk.value
+
+    def moments(self) -> PcaMoments:
+        m = PcaMoments()
+        dp = C.POINTER(C.c_double)
+        m.n, m.skipped = self.stats()
+        _check(lib().omni_pcafit_moments(self.h, m.s.ctypes.data_as(dp), m.S.ctypes.data_as(dp)))
+        return m
+
+    def solve(self, pca_dim: int = 64) -> dict:
+        o, tv = _pca_outputs(pca_dim), C.c_double()
+        _check(lib().omni_pcafit_solve(self.h, int(pca_dim), *_pca_out_args(o, tv)))
+        o["total_variance"] = tv.value
+        return o
 
 
 class MobileNetVLAD:

@@ -227,6 +227,15 @@ int jpegdec_enqueue_on(omni_jpegdec* d, hipStream_t stream, const uint8_t* const
                        int* status_dev);
 }  // namespace omni
 
+namespace omni {
+// pca_fit.hip: the rows of one SuperPoint pass (csrc/pca_plan.h) added to the fit's accumulator on `stream`, which must be the fit's own context's (a fit is
+// attached only to a handle of its own context: omni_sp_set_pcafit)
+int pcafit_enqueue_on(omni_pcafit* f, hipStream_t stream, const float* raw_desc, const float* norm_partial, const int* n_kps, int batch, int max_num);
+const omni_ctx* pcafit_ctx(const omni_pcafit* f);
+int pcafit_set_owner(omni_pcafit* f, omni_sp* sp_or_null);      // the handle that holds the fit (nullptr: none); refused while another handle holds it
+void sp_drop_pcafit(omni_sp* sp, omni_pcafit* f);               // superpoint.hip: sp stops feeding f, if it does (omni_pcafit_destroy of an attached fit)
+}  // namespace omni
+
 // ---- 64-bit sortable keys -------------------------------------------------------------------------------------
 // key = (orderable(score) << 32) | (0xFFFFFFFF - id): descending key order == (score desc, id asc).
 __host__ __device__ static inline uint32_t omni_f32_orderable(float f) {

@@ -59,6 +59,8 @@ struct SpSparseDesc {
     // a heat map that did not come from the head (omni_sp_postprocess_dense): the same two steps as separate kernels -- sp_thresh_kernel makes the bitmap,
     // sp_mask_kernel lists and masks -- so that every edge case of the post-processing tests runs through the kernel the pipeline uses
     bool cand_from_list = false;
+    // omni_sp_set_pcafit: the pass's rows go into this accumulator behind sp_chan_sumsq_kernel (pca_fit.hip); null: nothing is launched
+    omni_pcafit* pcafit = nullptr;
 };
 
 // semi: [B][H][W] f32 probability map; desc_nhwc: [B][H/8][W/8][256] f32 (channel-normalised coarse descriptors; read by the two dense modes only)

@@ -694,6 +694,7 @@ int sp_postprocess(hipStream_t stream, const SpPostParams& p, const SpPostBuffer
     }
     hipLaunchKernelGGL(sp_chan_sumsq_kernel, dim3(NORM_SEGS, batch), dim3(256), 0, stream, p.max_num, b.n_kps, b.raw_desc, b.norm_partial);
     OMNI_LAUNCH_CHECK();
+    if (sparse.pcafit && (rc = pcafit_enqueue_on(sparse.pcafit, stream, b.raw_desc, b.norm_partial, b.n_kps, batch, p.max_num))) return rc;
     if (p.pca_dim > 0) {
         hipLaunchKernelGGL(sp_pca_kernel, dim3(cdiv(p.max_num, 4), batch), dim3(256), 0, stream, b.raw_desc, b.norm_partial, p.max_num, b.n_kps,
                            p.pca_dim, b.pca_compT, b.pca_mean, b.desc_out);

@@ -110,6 +110,7 @@ struct omni_sp {
     bool mask_band = false;                  // layers 1..5 leave out their band (false: their rectangle -- OMNI_SP_MASK_RECT=1, or H % 4 != 0)
     uint8_t* zero_gray = nullptr;            // the calibration's all-zero image (grows with the largest stride seen)
     size_t zero_gray_bytes = 0;
+    omni_pcafit* pcafit = nullptr;           // omni_sp_set_pcafit: every pass adds its rows to this accumulator (borrowed; null: none)
     std::mutex mu;
 };
 
@@ -425,6 +426,7 @@ static SpSparseDesc sp_sparse_desc(const omni_sp* s, const SpPassPlan& p) {
     sd.wfrag = s->wDbFrag; sd.wdb_hi = s->wDbFragHi; sd.wdb_lo = s->wDbFragLo; sd.wdb_f32 = s->wpk[LDB];
     sd.a4b = s->a4b; sd.da_w = s->wpk[LPA]; sd.da_bias = s->bias_heads; sd.da_g32_first = 8; sd.da_inv = s->winv[LPA]; sd.da_compact = s->da_compact;
     sd.cx = s->cx32; sd.cy = s->cy32; sd.n_cu = s->ctx->prop.multiProcessorCount; sd.zero_page = s->ctx->zero_page;
+    sd.pcafit = s->pcafit;
     return sd;
 }
 
@@ -580,6 +582,11 @@ static int sp_fetch_locked(omni_sp* s, int batch, float* kps_xy, int* n_kps, flo
     return OMNI_OK;
 }
 
+void sp_drop_pcafit(omni_sp* s, omni_pcafit* f) {
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->pcafit == f) { s->pcafit = nullptr; (void)pcafit_set_owner(f, nullptr); }
+}
+
 static int upload_gray(omni_sp* s, const uint8_t* gray_host, int stride, int batch) {
     // pack rows to a dense [batch][H][W] device image (stride = W)
     const size_t n = (size_t)batch * s->H * s->W;
@@ -631,6 +638,7 @@ omni_sp* omni_sp_create(omni_ctx* ctx, const omni_sp_weights* w, const float* pc
 
 void omni_sp_destroy(omni_sp* s) {
     if (!s) return;
+    if (s->pcafit) { (void)omni::pcafit_set_owner(s->pcafit, nullptr); s->pcafit = nullptr; }
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     s->mem.release_all();
@@ -681,6 +689,20 @@ int omni_sp_infer(omni_sp* s, const uint8_t* gray_host, int stride, int batch, i
     s->perf_valid = s->perf;
     if ((rc = omni::sp_forward(s, s->gray_stage, s->W, batch, fisheye_mask, s->perf, true))) return rc;
     return omni::sp_fetch_locked(s, batch, kps_xy, n_kps, desc, scores);
+}
+
+int omni_sp_set_pcafit(omni_sp* s, omni_pcafit* fit) {
+    OMNI_REQUIRE(s, OMNI_ERR_INVALID, "null handle");
+    OMNI_REQUIRE(!fit || omni::pcafit_ctx(fit)->device == s->ctx->device, OMNI_ERR_INVALID, "the fit's context is on device %d, the handle's on device %d",
+                 fit ? omni::pcafit_ctx(fit)->device : -1, s->ctx->device);
+    // the accumulation runs on the pass's stream and the fit's readers wait for the fit's: one context, so one stream, and nothing to order
+    OMNI_REQUIRE(!fit || omni::pcafit_ctx(fit) == s->ctx, OMNI_ERR_INVALID, "the fit belongs to another context than the handle: create it on the handle's context");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (fit == s->pcafit) return OMNI_OK;
+    if (fit) { if (int rc = omni::pcafit_set_owner(fit, s)) return rc; }
+    if (s->pcafit) (void)omni::pcafit_set_owner(s->pcafit, nullptr);
+    s->pcafit = fit;
+    return OMNI_OK;
 }
 
 int omni_sp_dev_outputs(omni_sp* s, const float** kps_xy_dev, const int** n_kps_dev, const float** desc_dev, const float** scores_dev) {

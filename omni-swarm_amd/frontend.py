@@ -30,7 +30,7 @@ class LoopCam:
                  vlad_shape=(32, 112, 4096), width: int = 600, height: int = 480, thres: float = 0.015,
                  max_num: int = 200, precision: int = capi.PREC_F16, n_dirs: int = 4, fisheye: bool = True,
                  accept_min_3d_pts: int = 0, stereo_model: capi.StereoModel = None, camera_model: capi.CameraModel = None,
-                 depth_model: capi.DepthModel = None):
+                 depth_model: capi.DepthModel = None, pca_fit: capi.PcaFit = None):
         if depth_model is not None and stereo_model is not None:
             raise ValueError("LoopCam: depth_model (PINHOLE_DEPTH, one camera per image) and stereo_model (an up / down pair per direction) are two camera configurations")
         self.mono = depth_model is not None
@@ -47,6 +47,10 @@ class LoopCam:
         self.vlad = capi.MobileNetVLAD(self.vctx, vlad_weights, vlad_specs, k, d, o, width, height, n_dirs)
         self.out_dim = o
         self.dim = self.sp.desc_dim
+        # OUTPUT_RAW_SUPERPOINT_DESC (loop_cam.cpp:51-53, 577-582) without the dump: every unit adds its key points' 256-d descriptors to the fit's moments on the GPU
+        self.pca_fit = pca_fit
+        if pca_fit is not None:
+            self.sp.set_pcafit(pca_fit)
         # the whole key frame as one asynchronous unit with a single pinned result block (csrc/cam.hip)
         self.cam = capi.Cam(self.sp, self.vlad, n_dirs, o, capi.BF_OPENCV, mono=self.mono)
         self.stereo_model = stereo_model

@@ -91,6 +91,11 @@ public:
         // out of the unit's result block.  Off (the default: DESIGN.md section 0.2k has the measurements): the host path, both functions inline on the calling thread,
         // the depth frames borrowed until the unit is finished.  (set_device_depth_landmarks: before the first key frame.)
         bool device_depth_landmarks = false;
+        // OUTPUT_RAW_SUPERPOINT_DESC (loop_cam.cpp:51-53, 577-582) as a calibration mode: every lane owns a PCA-fit accumulator in HBM attached to its SuperPoint
+        // handle (omni_sp_set_pcafit, csrc/pca_fit.hip), so the 256-d descriptors of every key point of the stream enter the fit's moments without leaving the GPU;
+        // pca_fit_moments / pca_fit / pca_fit_write read them, and components_.csv / mean_.csv come out of the library instead of a notebook.  Results of the
+        // pipeline are the same with the switch on or off.  Off by default.  The sharded database refuses it.  (set_fit_pca: before the first key frame.)
+        bool fit_pca = false;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -212,6 +217,7 @@ private:
         det_.stereo_fisheye = c.masked();
         geo_.MAX_DIRS = c.dirs();
         for (int p = 0; p < c.pipelines; ++p) lanes_.push_back(std::make_unique<Lane>(c, c.microbatch));
+        apply_fit_pca();
         if (c.fisheye_raw()) {
             // ONE pair of flatten objects serves every lane: omni_cam_enqueue_fisheye_* launches the remap on the UNIT's stream and only reads the maps and the
             // view table (flatten_unit_launch, csrc/flatten.hip: neither the object's own stream nor its lock), which nothing writes after omni_flatten_create
@@ -490,6 +496,34 @@ public:
         apply_stereo_model();
     }
     bool device_depth_landmarks_config() const { return cfg_.device_depth_landmarks; }      // the switch as set, whatever the mode makes of it
+    // ---- the PCA fit of the stream's 256-d descriptors (Config::fit_pca) ------------------------------------------------------------------------------------------
+    bool fit_pca() const { return cfg_.fit_pca; }
+    // before the first key frame (what the C entry point omni_pipeline_set_fit_pca sets): every lane gets, or gives up, an accumulator of its own -- lanes run on
+    // different streams.  Refused on the sharded database, which builds no descriptors of its own
+    void set_fit_pca(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (on && shard_) throw std::runtime_error("set_fit_pca: the sharded database builds no descriptors of its own");
+        if (any_keyframe_seen_) throw std::runtime_error("set_fit_pca after the first key frame");
+        cfg_.fit_pca = on;
+        apply_fit_pca();
+    }
+    // waits for every lane, then merges the lanes' accumulators: lanes_ in order, then the tail lanes in key order
+    PcaMoments pca_fit_moments() {
+        if (!cfg_.fit_pca) throw std::runtime_error("pca_fit_moments: the pipeline was made without fit_pca");
+        sync();
+        PcaMoments m;
+        for (auto& l : lanes_) if (l->fit) m.merge(l->fit->moments());
+        for (auto& t : tail_lanes_) if (t.second->fit) m.merge(t.second->fit->moments());
+        return m;
+    }
+    PcaSolution pca_fit(int pca_dim = 64) { return pca_solve(pca_fit_moments(), pca_dim); }
+    void pca_fit_write(const std::string& comp_path, const std::string& mean_path, int pca_dim = 64) { pca_fit(pca_dim).write(comp_path, mean_path); }
+    void pca_fit_reset() {
+        if (!cfg_.fit_pca) throw std::runtime_error("pca_fit_reset: the pipeline was made without fit_pca");
+        sync();
+        for (auto& l : lanes_) if (l->fit) l->fit->reset();
+        for (auto& t : tail_lanes_) if (t.second->fit) t.second->fit->reset();
+    }
     // ---- the homography RANSAC of the loop candidates on the GPU (Config::device_homography) --------------------------------------------------------------
     bool device_homography() const { return cfg_.device_homography && cfg_.geometry && !shard_; }      // (the sharded database builds no messages)
     bool device_homography_config() const { return cfg_.device_homography; }      // the switch as set, whatever the mode makes of it
@@ -557,6 +591,14 @@ public:
     }
 private:
     struct Lane;
+    void apply_fit_pca(Lane& l) {
+        if (cfg_.fit_pca && !l.fit) { l.fit = std::make_unique<PcaFitX>(l.sp_ctx); l.sp.set_pcafit(l.fit.get()); }
+        else if (!cfg_.fit_pca && l.fit) { l.sp.set_pcafit(nullptr); l.fit.reset(); }
+    }
+    void apply_fit_pca() {
+        for (auto& l : lanes_) apply_fit_pca(*l);
+        for (auto& t : tail_lanes_) apply_fit_pca(*t.second);
+    }
     void apply_jpeg(Lane& l) { l.cam.set_jpeg(send_img() ? cfg_.jpg_quality : 0, jpeg_capacity()); }
     void apply_jpeg() {
         for (auto& l : lanes_) apply_jpeg(*l);
@@ -638,6 +680,7 @@ public:
     // frame's candidate is decided on GLOBAL ids with the reference's rule (loop_detector.cpp:232: recency + threshold); the id maps of
     // LoopDetectorCore describe one drone's own database and are not used in this mode.
     void attach_shard(int rank, int world, const char* unique_id) {
+        if (cfg_.fit_pca) throw std::runtime_error("attach_shard: fit_pca does not run on the sharded database, which builds no descriptors of its own");
         if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
@@ -894,7 +937,7 @@ public:
         const int rem = n_keyframes % cfg_.microbatch;
         if (!rem) return nullptr;
         auto it = tail_lanes_.find(rem);
-        if (it == tail_lanes_.end()) { it = tail_lanes_.emplace(rem, std::make_unique<Lane>(cfg_, rem)).first; apply_stereo_model(*it->second); apply_jpeg(*it->second); }
+        if (it == tail_lanes_.end()) { it = tail_lanes_.emplace(rem, std::make_unique<Lane>(cfg_, rem)).first; apply_stereo_model(*it->second); apply_jpeg(*it->second); apply_fit_pca(*it->second); }
         return it->second.get();
     }
 
@@ -920,7 +963,7 @@ private:
         uint8_t* stage = nullptr;                      // pinned block the streaming intake packs the unit's images into
         std::vector<uint16_t> depth_stage;             // streaming intake with device_depth_landmarks: the unit's depth frames [mb][height][width], copied at the push
         size_t stage_bytes = 0;
-        ~Lane() { if (stage) omni_host_free(stage); }
+        ~Lane() { if (fit) (void)omni_sp_set_pcafit(sp.handle(), nullptr); if (stage) omni_host_free(stage); }
         Context sp_ctx, vlad_ctx;
         Swarm::SuperPointHIP sp;
         bool one_stream;                               // MobileNetVLAD behind SuperPoint on ONE stream (OMNI_PIPELINE_ONE_STREAM) instead of next to it on its own
@@ -929,6 +972,7 @@ private:
         LoopCamHIP cam;
         std::unique_ptr<ResizeHIP> resize;             // STEREO_PINHOLE with camera-size frames: the tables of the resize that runs inside the unit
         const float* rows_dev = nullptr;
+        std::unique_ptr<PcaFitX> fit;                  // Config::fit_pca: the lane's own accumulator, attached to sp (declared last: it goes before the handle and its context do)
     };
 
     // The open unit of the streaming intake leaves for the GPU, full or not (a partial one: the down cameras' block moves up behind the up cameras' and the

@@ -13,6 +13,7 @@
 // Errors: the reference aborts (assert / NV_CUDA_CHECK); these adapters throw std::runtime_error carrying
 // omni_last_error() from constructors and return empty results + set last_status from inference calls.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <chrono>
 #include <cstdio>
@@ -57,6 +58,56 @@ public:
     omni_ctx* get() const { return h_; }
 private:
     omni_ctx* h_;
+};
+
+// ---- the fit half of the reference's PCA workflow (OUTPUT_RAW_SUPERPOINT_DESC + pca.ipynb): an accumulator in HBM (omni_pcafit, csrc/pca_plan.h), fed by every
+// pass of the SuperPoint handle it is attached to (Swarm::SuperPointHIP::set_pcafit) ----
+struct PcaMoments {
+    int64_t n = 0, skipped = 0;
+    std::vector<double> s = std::vector<double>(256, 0.0), S = std::vector<double>(256 * 256, 0.0);      // S: full symmetric [256][256]
+    void merge(const PcaMoments& right) {
+        check(omni_pcafit_merge_host(&n, s.data(), S.data(), right.n, right.s.data(), right.S.data()), "omni_pcafit_merge_host");
+        skipped += right.skipped;
+    }
+};
+struct PcaSolution {
+    int pca_dim = 0;
+    std::vector<double> components, mean, explained_variance;      // [pca_dim][256], [256], [pca_dim]
+    std::vector<float> components_f32, mean_f32;
+    double total_variance = 0;
+    void write(const std::string& comp_path, const std::string& mean_path) const {
+        check(omni_pca_write_csv(comp_path.c_str(), mean_path.c_str(), components_f32.data(), mean_f32.data(), pca_dim), "omni_pca_write_csv");
+    }
+};
+inline PcaSolution pca_solve(const PcaMoments& m, int pca_dim) {
+    PcaSolution o;
+    const size_t k = (size_t)std::max(1, std::min(pca_dim, 256));
+    o.pca_dim = pca_dim;
+    o.components.resize(k * 256); o.components_f32.resize(k * 256); o.mean.resize(256); o.mean_f32.resize(256); o.explained_variance.resize(k);
+    check(omni_pca_solve_host(m.n, m.s.data(), m.S.data(), pca_dim, o.components.data(), o.components_f32.data(), o.mean.data(), o.mean_f32.data(),
+                              o.explained_variance.data(), &o.total_variance), "omni_pca_solve_host");
+    return o;
+}
+class PcaFitX {
+public:
+    explicit PcaFitX(Context& ctx) : h_(omni_pcafit_create(ctx.get())) { if (!h_) throw std::runtime_error(std::string("omni_pcafit_create: ") + omni_last_error()); }
+    ~PcaFitX() { omni_pcafit_destroy(h_); }
+    PcaFitX(const PcaFitX&) = delete;
+    PcaFitX& operator=(const PcaFitX&) = delete;
+    omni_pcafit* get() const { return h_; }
+    void reset() { check(omni_pcafit_reset(h_), "omni_pcafit_reset"); }
+    void enqueue_rows_dev(const float* raw_desc_dev, const float* norm_partial_dev, const int* n_kps_dev, int batch, int max_num) {
+        check(omni_pcafit_enqueue_rows_dev(h_, raw_desc_dev, norm_partial_dev, n_kps_dev, batch, max_num), "omni_pcafit_enqueue_rows_dev");
+    }
+    PcaMoments moments() {          // waits for the fit's work
+        PcaMoments m;
+        check(omni_pcafit_stats(h_, &m.n, &m.skipped), "omni_pcafit_stats");
+        check(omni_pcafit_moments(h_, m.s.data(), m.S.data()), "omni_pcafit_moments");
+        return m;
+    }
+    PcaSolution solve(int pca_dim = 64) { return pca_solve(moments(), pca_dim); }
+private:
+    omni_pcafit* h_;
 };
 
 // ---- weight container: "OMNW1" file = named float32 tensors (written by tools/export_weights.py from a state_dict) ----
@@ -192,6 +243,9 @@ public:
 #endif
     int desc_dim() const { return dim_; }
     omni_sp* handle() const { return h_; }
+    // every pass from now on adds its 256-d descriptors to `fit` on the GPU (nullptr: detach).  The fit must be made on this handle's Context; one fit serves one
+    // handle at a time; whichever of the two is destroyed first, the other lets go
+    void set_pcafit(omni::PcaFitX* fit) { omni::check(omni_sp_set_pcafit(h_, fit ? fit->get() : nullptr), "omni_sp_set_pcafit"); }
     int last_status = OMNI_OK;
 private:
     omni_sp* h_ = nullptr;

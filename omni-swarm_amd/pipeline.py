@@ -195,6 +195,33 @@ def depth_lib():
     return _depth_lib
 
 
+PCA_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libomni_host_pca.so")
+PCA_SYMBOLS = ["omni_pca_host_last_error", "omni_pipeline_set_fit_pca", "omni_pipeline_get_fit_pca", "omni_pipeline_pca_fit_stats", "omni_pipeline_pca_fit_moments",
+               "omni_pipeline_pca_fit_solve", "omni_pipeline_pca_fit_write", "omni_pipeline_pca_fit_reset"]
+_pca_lib = None
+
+
+def pca_lib():
+    """libomni_host_pca.so (include/omni_host_pca.h): the PCA fit of the key-frame pipeline's descriptor stream"""
+    global _pca_lib
+    if _pca_lib is None:
+        lib()
+        if not os.path.exists(PCA_LIB_PATH):
+            raise OSError(f"{PCA_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(PCA_LIB_PATH)
+        dp, fp, ip64 = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        L.omni_pca_host_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_fit_pca.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_fit_pca.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.omni_pipeline_pca_fit_stats.argtypes = [C.c_void_p, ip64, ip64]
+        L.omni_pipeline_pca_fit_moments.argtypes = [C.c_void_p, ip64, ip64, dp, dp]
+        L.omni_pipeline_pca_fit_solve.argtypes = [C.c_void_p, C.c_int, dp, fp, dp, fp, dp, dp]
+        L.omni_pipeline_pca_fit_write.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int]
+        L.omni_pipeline_pca_fit_reset.argtypes = [C.c_void_p]
+        _pca_lib = L
+    return _pca_lib
+
+
 def camera_lib():
     """libomni_host_camera.so (include/omni_host_camera.h): the lens model of the key-frame pipeline, the camodocal file reader"""
     global _camera_lib
@@ -313,7 +340,7 @@ class KeyframePipeline:
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
-                 device_depth_landmarks=None):
+                 device_depth_landmarks=None, fit_pca=False):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -337,6 +364,8 @@ class KeyframePipeline:
         device_depth_landmarks: True / False = PINHOLE_DEPTH's lifted key points and depth landmarks of a `geometry` pipeline inside the key-frame unit on the GPU
         (every depth image is then copied at push_keyframe / read when run() enqueues its unit) / on the calling thread (the same bits either way); None: the
         library's default, which is off.  Refused for the stereo configurations.
+        fit_pca: the reference's OUTPUT_RAW_SUPERPOINT_DESC as a calibration mode: the 256-d descriptors of every key point of the stream enter the moments of
+        a PCA fit on the GPU (csrc/pca_fit.hip); pca_fit / pca_fit_write make components_.csv / mean_.csv of them.  Results do not depend on it.  Default off.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -381,6 +410,43 @@ class KeyframePipeline:
             self.set_send_img(True, jpg_quality)
         if compressed_images:
             self.set_compressed_images(True)
+        if fit_pca:
+            self.set_fit_pca(True)
+
+    def _pca(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {pca_lib().omni_pca_host_last_error().decode()}")
+
+    def set_fit_pca(self, on: bool):
+        """before the first key frame: every lane accumulates the moments of a PCA fit of the stream's 256-d descriptors (refused on the sharded database)"""
+        self._pca(pca_lib().omni_pipeline_set_fit_pca(self.h, int(bool(on))), "omni_pipeline_set_fit_pca")
+
+    def fit_pca(self) -> bool:
+        on = C.c_int(0)
+        self._pca(pca_lib().omni_pipeline_get_fit_pca(self.h, C.byref(on)), "omni_pipeline_get_fit_pca")
+        return bool(on.value)
+
+    def pca_fit_moments(self) -> "capi.PcaMoments":
+        """waits for the units in flight; the lanes' accumulators merged in a fixed order"""
+        m, n, sk = capi.PcaMoments(), C.c_int64(), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._pca(pca_lib().omni_pipeline_pca_fit_moments(self.h, C.byref(n), C.byref(sk), m.s.ctypes.data_as(dp), m.S.ctypes.data_as(dp)), "omni_pipeline_pca_fit_moments")
+        m.n, m.skipped = n.value, sk.value
+        return m
+
+    def pca_fit(self, pca_dim: int = 64) -> dict:
+        """components [pca_dim][256] and mean [256] (float64 and float32), explained_variance, total_variance of the stream so far"""
+        o, tv = capi._pca_outputs(pca_dim), C.c_double()
+        self._pca(pca_lib().omni_pipeline_pca_fit_solve(self.h, int(pca_dim), *capi._pca_out_args(o, tv)), "omni_pipeline_pca_fit_solve")
+        o["total_variance"] = tv.value
+        return o
+
+    def pca_fit_write(self, comp_path: str, mean_path: str, pca_dim: int = 64):
+        """components_.csv / mean_.csv of the stream so far: the files a pipeline is created with"""
+        self._pca(pca_lib().omni_pipeline_pca_fit_write(self.h, os.fsencode(comp_path), os.fsencode(mean_path), int(pca_dim)), "omni_pipeline_pca_fit_write")
+
+    def pca_fit_reset(self):
+        self._pca(pca_lib().omni_pipeline_pca_fit_reset(self.h), "omni_pipeline_pca_fit_reset")
 
     def set_camera_model(self, camera_model, intrinsics=None):
         """before the first key frame: the lens of every lift (see __init__); None: the ideal pinhole.  intrinsics [fx, fy, cx, cy] of the network-size image
