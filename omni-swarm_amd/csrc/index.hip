@@ -15,31 +15,102 @@
 #include "config.h"
 #include "common.h"
 #include "topk.h"
+#include "index_plan.h"
 #include <sys/stat.h>
 #include <climits>
+
+namespace omni {
+
+// The rows of an index in HBM and their only owner: nothing else allocates or frees db, db16 or norm_max.
+// INVARIANT (the certificate of the batched search trusts it): the fp16 mirror db16 of an fp32 shard holds fp16(row) for EVERY row, or does not exist.
+// norm_max says that the shard wants a mirror (OMNI_INDEX_MIRROR, not sharded): growth allocates one only then, and whoever cannot give the rows held a
+// mirror gives up norm_max with it -- so no later growth allocates an EMPTY mirror for rows already held ("The plan of a search").
+struct IndexRows {
+    void* db = nullptr;                    // fp32: row-major [capacity][dim]; fp16: T16 blocks
+    void* db16 = nullptr;                  // fp32 shards: the mirror, T16 blocks
+    uint32_t* norm_max = nullptr;          // device: bits of the largest squared row norm seen (atomicMax on the bit pattern of a float >= 0)
+    int64_t capacity = 0;
+    size_t row_bytes = 0, mirror_row_bytes = 0;
+    static size_t elem(int storage) { return storage == OMNI_STORE_F16 ? 2 : 4; }
+    void init(int dim, int storage) { row_bytes = (size_t)dim * elem(storage); mirror_row_bytes = (size_t)dim * 2; }
+    int want_mirror(hipStream_t st) {
+        if (hipMalloc((void**)&norm_max, 4) != hipSuccess || hipMemsetAsync(norm_max, 0, 4, st) != hipSuccess) { set_error("hipMalloc failed"); return OMNI_ERR_NOMEM; }
+        return OMNI_OK;
+    }
+    // room for `cap` rows in an owner that holds none (a snapshot is loaded into a fresh owner and adopted on success)
+    bool reserve(int64_t cap) {
+        if (hipMalloc(&db, (size_t)cap * row_bytes) != hipSuccess) { db = nullptr; return false; }
+        capacity = cap;
+        return true;
+    }
+    // Room for `rows` rows, keeping the `ntotal` held: new buffers first, then the copies, a stream sync, commit, free the old buffers.  Every failure frees
+    // what this call allocated: the index keeps its old buffers.  *rebuild_mirror: the rows held had no mirror, the caller converts them from row 0.
+    int grow(int64_t rows, int64_t ntotal, hipStream_t st, bool* rebuild_mirror) {
+        *rebuild_mirror = false;
+        if (rows <= capacity) return OMNI_OK;
+        const int64_t cap = index_grown_capacity(capacity, rows);
+        void* nd = nullptr;
+        void* nm = nullptr;
+        OMNI_HIP_TRY(hipMalloc(&nd, (size_t)cap * row_bytes));
+        auto fail = [&](int code, const char* what) { if (nd) (void)hipFree(nd); if (nm) (void)hipFree(nm); set_error("index growth to %lld rows: %s failed", (long long)cap, what); return code; };
+        const size_t old_blocks = (size_t)((ntotal + 15) & ~(int64_t)15);
+        if (db && ntotal > 0 && hipMemcpyAsync(nd, db, old_blocks * row_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(OMNI_ERR_HIP, "the copy of the rows");
+        if (norm_max) {
+            if (hipMalloc(&nm, (size_t)cap * mirror_row_bytes) != hipSuccess) { nm = nullptr; return fail(OMNI_ERR_NOMEM, "hipMalloc of the fp16 mirror"); }
+            if (db16 && ntotal > 0) {
+                if (hipMemcpyAsync(nm, db16, old_blocks * mirror_row_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(OMNI_ERR_HIP, "the copy of the mirror");
+            } else if (ntotal > 0) {
+                *rebuild_mirror = true;
+            }
+        }
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(OMNI_ERR_HIP, "the stream");
+        if (db) (void)hipFree(db);
+        if (db16) (void)hipFree(db16);
+        db = nd;
+        db16 = nm;
+        capacity = cap;
+        return OMNI_OK;
+    }
+    // The rows of `fresh` (reserve + filled on st) replace the ones held.  A shard that wants a mirror gets an EMPTY one for the caller to fill from row 0; with
+    // no room for it the rows are adopted all the same and norm_max goes: the index works, every batch goes through the exact scan from now on.
+    void adopt(IndexRows& fresh, hipStream_t st) {
+        (void)hipStreamSynchronize(st);
+        if (db) (void)hipFree(db);
+        if (db16) { (void)hipFree(db16); db16 = nullptr; }
+        db = fresh.db; capacity = fresh.capacity;
+        fresh.db = nullptr; fresh.capacity = 0;
+        if (norm_max && hipMalloc(&db16, (size_t)capacity * mirror_row_bytes) != hipSuccess) {
+            db16 = nullptr;
+            (void)hipGetLastError();
+            (void)hipFree(norm_max); norm_max = nullptr;
+        }
+    }
+    void drop_mirror() {
+        if (db16) { (void)hipFree(db16); db16 = nullptr; }
+        if (norm_max) { (void)hipFree(norm_max); norm_max = nullptr; }
+    }
+    void release() {
+        if (db) (void)hipFree(db);
+        db = nullptr; capacity = 0;
+        drop_mirror();
+    }
+};
+
+}  // namespace omni
 
 struct omni_index {
     omni_ctx* ctx = nullptr;
     int dim = 0;
     int storage = OMNI_STORE_F32;
-    int64_t capacity = 0;
     int64_t ntotal = 0;
     int rank = 0, world = 1;
-    void* db = nullptr;
-    // fp32 shards keep an fp16 MIRROR of the rows in the T16 layout (+50 % memory): a batch of queries is first scored against the mirror in ONE
-    // pass on the matrix cores (8 KB per row instead of 16, every query of the batch at once), the best K' candidates per query are re-scored
-    // EXACTLY against the fp32 rows, and a per-query certificate (the K'-th mirror score plus the fp16 rounding bound is below the k-th exact
-    // score) proves that the result is the exact fp32 top-k -- scores bit-identical to the single-query kernel; a query whose certificate
-    // fails is searched again by the exact multi-pass scan.  OMNI_INDEX_MIRROR=0 switches the mirror off.
-    void* db16 = nullptr;
-    uint32_t* norm_max = nullptr;          // device: bits of the largest squared row norm seen (atomicMax on the bit pattern of a float >= 0)
+    omni::IndexRows rows;
     omni::DevBuf qbuf, keys_a, keys_b, out_d, out_i, stage, mq_q, mq_inv, cert_keys, cert_flags;
     omni::HostBuf hq, hout, hflags;
     int64_t cert_searches = 0, cert_fallbacks = 0;      // statistics: queries answered through the mirror / of those, re-run exactly
     hipEvent_t scan0 = nullptr, scan1 = nullptr;
     bool scan_timed = false;
     std::mutex mu;
-    size_t elem() const { return storage == OMNI_STORE_F16 ? 2 : 4; }
 };
 
 namespace omni {
@@ -49,9 +120,7 @@ namespace omni {
 #else
 #define NT_LOAD(p) __builtin_nontemporal_load(p)
 #endif
-#define SCAN_THREADS 256
-#define SCAN_WAVES (SCAN_THREADS / 64)
-#define SCAN_MAX_QB 8
+// (SCAN_*, MQ_* sizes: index_plan.h)
 // per-query row limits of a batched prefix search (omni_index_search_batch_prefix_dev): query q only sees rows [0, v[q]); rows beyond
 // get the empty key.  Passed by value (kernel argument segment) so that back-to-back enqueues need no staging buffer.
 template <int N> struct ScanLimits { int64_t v[N]; };
@@ -180,13 +249,6 @@ ip_scan_rows_kernel(const float* __restrict__ db, int64_t n_rows, int dim, const
 // (16 rows x 64 queries) across the 16 k-slices of a pass, then writes 64-bit keys for topk.h.
 //   algorithmic bytes: rows x dim x 2 (read once) + rows x nq x 8 (keys);  MFMA work 2 x 2 x 64 x dim flop per row ~ 28 % of the
 //   matrix peak at 5.3 TB/s, so the bound is HBM.
-#define MQ_THREADS 512
-#define MQ_WAVES 8
-#define MQ_RT 4
-#define MQ_NQ 64
-#define MQ_KS 256
-#define MQ_SLICE_BYTES (2 * MQ_NQ * MQ_KS * 2)
-#define MQ_SMEM (2 * MQ_SLICE_BYTES)
 #define MQ_RING 4
 #define MQ_SLICE_STRIDE (MQ_KS * 2 * 16)     // bytes between consecutive k-slices of a 16-row block (T16 layout): 8 KiB, 1 KiB per k-step
 typedef _Float16 mq_half8 __attribute__((ext_vector_type(8)));
@@ -624,154 +686,167 @@ cert_select_kernel(const uint64_t* __restrict__ exact /*[nq][kp]*/, const uint64
     }
 }
 
-// form (omni_index_debug_scan): -1 = the choice below, 0 = the one-row-per-wave kernel, 1 = ip_scan_rows_kernel
-static int launch_scan(hipStream_t st, const omni_index* ix, int64_t n, int qb, const float* q_dev, uint64_t* keys, int64_t key_stride,
-                       const int64_t* limits, int form = -1) {
+// what the plan of a search reads of a handle (index_plan.h)
+static IndexFacts index_facts(const omni_index* ix) {
+    static const int rows_min_qb = config_process()[CFG_SCAN_ROWS_MIN];
+    static const int64_t mirror_min_rows = config_process()[CFG_INDEX_MIRROR_MIN_ROWS];
+    IndexFacts f;
+    f.dim = ix->dim; f.storage = ix->storage; f.has_mirror = ix->rows.db16 != nullptr;
+    f.n_cu = index_n_cu(ix->ctx->prop.multiProcessorCount);
+    Config c;                                         // (OMNI_MQ_MIN is read per call: tests switch it between searches of one process)
+    f.mq_min = index_mq_min(config_resolve(&c) == OMNI_OK ? c[CFG_MQ_MIN] : kCfgOptions[CFG_MQ_MIN].def);
+    f.rows_min_qb = rows_min_qb; f.mirror_min_rows = mirror_min_rows;
+    return f;
+}
+
+// one pass of a VALU scan kernel (form) over rows [0, n) of the shard: qb queries at q_dev -> keys[q][row]
+static int launch_scan(hipStream_t st, const omni_index* ix, const IndexFacts& f, IndexScanForm form, int64_t n, int qb, const float* q_dev, uint64_t* keys,
+                       int64_t key_stride, const int64_t* limits) {
     ScanLimits<SCAN_MAX_QB> lim;
     for (int q = 0; q < SCAN_MAX_QB; ++q) lim.v[q] = limits && q < qb ? limits[q] : INT64_MAX;
-    const bool f16 = ix->storage == OMNI_STORE_F16;
-    int cus = ix->ctx->prop.multiProcessorCount > 0 ? ix->ctx->prop.multiProcessorCount : 256;
-    int64_t want = cdiv64(f16 ? cdiv64(n, 16) : n, SCAN_WAVES);      // a wave walks rows (fp32) or 16-row blocks (fp16)
-    int grid = (int)(want < (int64_t)cus * 8 ? want : (int64_t)cus * 8);
-    if (grid < 1) grid = 1;
-    size_t smem = (size_t)qb * ix->dim * sizeof(float);
-    static const int rows_min_qb = config_process()[CFG_SCAN_ROWS_MIN];
-    if (!f16 && qb >= 4 && (form < 0 ? qb >= rows_min_qb : form == 1)) {
-        constexpr int R = 4;
-        int64_t want_g = cdiv64(cdiv64(n, R), SCAN_WAVES);
-        int grid_g = (int)(want_g < (int64_t)cus * 8 ? want_g : (int64_t)cus * 8);
-        if (grid_g < 1) grid_g = 1;
+    const IndexScanLaunch l = index_scan_launch(f, form, n, qb);
+#define OMNI_SCAN_LAUNCH(T, ...)                                                                                        \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3(l.grid), dim3(l.threads), l.smem_bytes, st, reinterpret_cast<const T*>(ix->rows.db), n, ix->dim, q_dev, keys, key_stride, lim)
+#define OMNI_F32_CASE(QB) case QB: OMNI_SCAN_LAUNCH(float, ip_scan_kernel<float, QB>); break;
+#define OMNI_T16_CASE(QB) case QB: OMNI_SCAN_LAUNCH(__half, ip_scan_t16_kernel<QB>); break;
 #define OMNI_ROWS_CASE(QB)                                                                                              \
     case QB: {                                                                                                          \
-        auto kf = ip_scan_rows_kernel<QB, R>;                                                                           \
         static DynSmemState attr;                                                                                       \
-        OMNI_HIP_TRY(ensure_dyn_smem(attr, (const void*)kf, smem));                                                     \
-        hipLaunchKernelGGL(kf, dim3(grid_g), dim3(SCAN_THREADS), smem, st, reinterpret_cast<const float*>(ix->db), n, ix->dim, q_dev, keys,  \
-                           key_stride, lim);                                                                            \
+        OMNI_HIP_TRY(ensure_dyn_smem(attr, (const void*)ip_scan_rows_kernel<QB, SCAN_ROWS_R>, l.smem_bytes));           \
+        OMNI_SCAN_LAUNCH(float, ip_scan_rows_kernel<QB, SCAN_ROWS_R>);                                                  \
         break; }
-        switch (qb) {
-            OMNI_ROWS_CASE(4) OMNI_ROWS_CASE(5) OMNI_ROWS_CASE(6) OMNI_ROWS_CASE(7) OMNI_ROWS_CASE(8)
-            default: set_error("internal: bad query block %d", qb); return OMNI_ERR_INVALID;
-        }
+#define OMNI_CASES_1_3(C) C(1) C(2) C(3)
+#define OMNI_CASES_4_8(C) C(4) C(5) C(6) C(7) C(8)
+    bool known = true;
+    switch (form) {
+        case INDEX_SCAN_F32_ROWS: switch (qb) { OMNI_CASES_4_8(OMNI_ROWS_CASE) default: known = false; } break;
+        case INDEX_SCAN_F32_ONE:  switch (qb) { OMNI_CASES_1_3(OMNI_F32_CASE) OMNI_CASES_4_8(OMNI_F32_CASE) default: known = false; } break;
+        case INDEX_SCAN_T16:      switch (qb) { OMNI_CASES_1_3(OMNI_T16_CASE) OMNI_CASES_4_8(OMNI_T16_CASE) default: known = false; } break;
+        default: known = false;
+    }
+#undef OMNI_CASES_4_8
+#undef OMNI_CASES_1_3
 #undef OMNI_ROWS_CASE
-        OMNI_LAUNCH_CHECK();
-        return OMNI_OK;
-    }
-#define OMNI_SCAN_CASE(QB)                                                                                              \
-    case QB:                                                                                                            \
-        if (f16)                                                                                                        \
-            hipLaunchKernelGGL((ip_scan_t16_kernel<QB>), dim3(grid), dim3(SCAN_THREADS), smem, st,                      \
-                               reinterpret_cast<const __half*>(ix->db), n, ix->dim, q_dev, keys, key_stride, lim);      \
-        else                                                                                                            \
-            hipLaunchKernelGGL((ip_scan_kernel<float, QB>), dim3(grid), dim3(SCAN_THREADS), smem, st,                   \
-                               reinterpret_cast<const float*>(ix->db), n, ix->dim, q_dev, keys, key_stride, lim);       \
-        break;
-    switch (qb) {
-        OMNI_SCAN_CASE(1) OMNI_SCAN_CASE(2) OMNI_SCAN_CASE(3) OMNI_SCAN_CASE(4)
-        OMNI_SCAN_CASE(5) OMNI_SCAN_CASE(6) OMNI_SCAN_CASE(7) OMNI_SCAN_CASE(8)
-        default: set_error("internal: bad query block %d", qb); return OMNI_ERR_INVALID;
-    }
-#undef OMNI_SCAN_CASE
+#undef OMNI_T16_CASE
+#undef OMNI_F32_CASE
+#undef OMNI_SCAN_LAUNCH
+    if (!known) { set_error("internal: bad query block %d", qb); return OMNI_ERR_INVALID; }
     OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 
-// up to MQ_NQ queries in one pass over an fp16 shard (ip_scan_mq_kernel); rotate_arg (omni_index_debug_scan): -1 = OMNI_MQ_ROT, else 0 / 1
-static int launch_scan_mq(hipStream_t st, omni_index* ix, int64_t n, int nq, const float* q_dev, uint64_t* keys, int64_t key_stride,
-                          const int64_t* limits, const void* db_t16 = nullptr, int rotate_arg = -1) {
+// up to MQ_NQ queries in one pass on the matrix cores (ip_scan_mq_kernel) over the T16 rows at db_t16: an fp16 shard's own or an fp32 shard's mirror
+static int launch_scan_mq(hipStream_t st, omni_index* ix, const IndexFacts& f, int64_t n, int nq, const float* q_dev, uint64_t* keys, int64_t key_stride,
+                          const int64_t* limits, const void* db_t16, int rotate) {
     ScanLimits<MQ_NQ> lim;
     for (int q = 0; q < MQ_NQ; ++q) lim.v[q] = limits && q < nq ? limits[q] : INT64_MAX;
+    const IndexScanLaunch l = index_scan_launch(f, INDEX_SCAN_MQ, n, nq);
     auto kfn = ip_scan_mq_kernel;
     static DynSmemState attr;
-    OMNI_HIP_TRY(ensure_dyn_smem(attr, (const void*)kfn, MQ_SMEM));
-    const int slices = ix->dim / MQ_KS;
+    OMNI_HIP_TRY(ensure_dyn_smem(attr, (const void*)kfn, l.smem_bytes));
     int rc;
-    if ((rc = ix->mq_q.ensure((size_t)slices * MQ_SLICE_BYTES))) return rc;
+    if ((rc = ix->mq_q.ensure(index_mq_query_bytes(ix->dim)))) return rc;
     if ((rc = ix->mq_inv.ensure(MQ_NQ * sizeof(float)))) return rc;
     hipLaunchKernelGGL(mq_prep_kernel, dim3(MQ_NQ), dim3(256), 0, st, q_dev, nq, ix->dim, ix->mq_q.as<uint4>(), ix->mq_inv.as<float>());
     OMNI_LAUNCH_CHECK();
-    const int64_t tiles = cdiv64(n, 16);
-    const int cus = ix->ctx->prop.multiProcessorCount > 0 ? ix->ctx->prop.multiProcessorCount : 256;
-    // one workgroup per CU (128 KB of LDS each) walking 512-row blocks b, b + grid, ...
-    const int64_t blocks = cdiv64(tiles, MQ_WAVES * MQ_RT);
-    const int64_t grid = blocks < cus ? blocks : cus;
-    static const int rotate_cfg = config_process()[CFG_MQ_ROT];
-    const int rotate = rotate_arg < 0 ? rotate_cfg : rotate_arg;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(MQ_THREADS), MQ_SMEM, st, reinterpret_cast<const _Float16*>(db_t16 ? db_t16 : ix->db),
-                       n, ix->dim, ix->mq_q.as<char>(), ix->mq_inv.as<float>(), nq, keys, key_stride, rotate, lim);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)l.grid), dim3(l.threads), l.smem_bytes, st, reinterpret_cast<const _Float16*>(db_t16), n, ix->dim, ix->mq_q.as<char>(),
+                       ix->mq_inv.as<float>(), nq, keys, key_stride, rotate, lim);
     OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 
-// number of queries from which an fp16 shard is searched on the matrix cores (OMNI_MQ_MIN overrides: 1 = always, 0 = never)
-static int mq_min_queries() {
-    Config c;                                         // (read per call: tests switch it between searches of one process)
-    const int v = config_resolve(&c) == OMNI_OK ? c[CFG_MQ_MIN] : kCfgOptions[CFG_MQ_MIN].def;
-    return v <= 0 ? (1 << 30) : v;
-}
-
-static int mirror_rows(omni_index* ix, int64_t row0, int64_t n);
-static int ensure_capacity(omni_index* ix, int64_t rows) {
-    if (rows <= ix->capacity) return OMNI_OK;
-    int64_t cap = ix->capacity > 0 ? ix->capacity : 1024;
-    while (cap < rows) cap *= 2;
-    cap = (cap + 15) & ~(int64_t)15;                             // whole 16-row blocks (fp16 T16 layout)
-    void* nd = nullptr;
-    void* nm = nullptr;
-    OMNI_HIP_TRY(hipMalloc(&nd, (size_t)cap * ix->dim * ix->elem()));
-    // (every failure below frees what this call allocated: the index keeps its old buffers)
-    auto fail = [&](int code, const char* what) { if (nd) (void)hipFree(nd); if (nm) (void)hipFree(nm); set_error("index growth to %lld rows: %s failed", (long long)cap, what); return code; };
-    const size_t old_blocks = (size_t)((ix->ntotal + 15) & ~(int64_t)15);
-    if (ix->db && ix->ntotal > 0 &&
-        hipMemcpyAsync(nd, ix->db, old_blocks * ix->dim * ix->elem(), hipMemcpyDeviceToDevice, ix->ctx->stream) != hipSuccess) return fail(OMNI_ERR_HIP, "the copy of the rows");
-    bool rebuild_mirror = false;
-    if (ix->norm_max) {                                              // fp32 shard with an fp16 mirror
-        if (hipMalloc(&nm, (size_t)cap * ix->dim * 2) != hipSuccess) { nm = nullptr; return fail(OMNI_ERR_NOMEM, "hipMalloc of the fp16 mirror"); }
-        if (ix->db16 && ix->ntotal > 0) {
-            if (hipMemcpyAsync(nm, ix->db16, old_blocks * ix->dim * 2, hipMemcpyDeviceToDevice, ix->ctx->stream) != hipSuccess) return fail(OMNI_ERR_HIP, "the copy of the mirror");
-        } else if (ix->ntotal > 0) {
-            rebuild_mirror = true;                                   // rows without a mirror (it could not be allocated when they were loaded): convert them now
-        }
+// the scan passes of a plan in launch order: keys[q][row] (stride n) for the passes' queries, q_dev their rows back to back; db_t16: what a matrix-core pass reads
+static int run_scan_passes(hipStream_t st, omni_index* ix, const IndexScanPasses& passes, int64_t n, const float* q_dev, uint64_t* keys, const int64_t* limits,
+                           const void* db_t16) {
+    static const int rotate = config_process()[CFG_MQ_ROT];
+    for (int i = 0; i < passes.count(); ++i) {
+        const IndexScanPass p = passes.pass(i);
+        const float* q = q_dev + (int64_t)p.q0 * ix->dim;
+        uint64_t* kq = keys + (int64_t)p.q0 * n;
+        const int64_t* lim = limits ? limits + p.q0 : nullptr;
+        const int rc = p.form == INDEX_SCAN_MQ ? launch_scan_mq(st, ix, passes.facts, n, p.qb, q, kq, n, lim, db_t16, rotate)
+                                               : launch_scan(st, ix, passes.facts, p.form, n, p.qb, q, kq, n, lim);
+        if (rc) return rc;
     }
-    if (hipStreamSynchronize(ix->ctx->stream) != hipSuccess) return fail(OMNI_ERR_HIP, "the stream");
-    if (ix->db) (void)hipFree(ix->db);
-    if (ix->db16) (void)hipFree(ix->db16);
-    ix->db = nd;
-    ix->db16 = nm;
-    ix->capacity = cap;
-    if (rebuild_mirror) return mirror_rows(ix, 0, ix->ntotal);       // the certificate of the batched search assumes mirror == fp16(row) for EVERY row
     return OMNI_OK;
 }
 
 // rows [row0, row0 + n) of an fp32 shard were just written (stream order): bring the fp16 mirror and the norm bound up to date
 static int mirror_rows(omni_index* ix, int64_t row0, int64_t n) {
-    if (!ix->db16 || n <= 0) return OMNI_OK;
+    if (!ix->rows.db16 || n <= 0) return OMNI_OK;
     hipStream_t st = ix->ctx->stream;
-    const float* rows = (const float*)ix->db + row0 * ix->dim;
-    hipLaunchKernelGGL(f32_to_t16_kernel, dim3((unsigned)cdiv64(n * ix->dim / 8, 256)), dim3(256), 0, st, rows, (__half*)ix->db16, row0, n, ix->dim);
+    const float* rows = (const float*)ix->rows.db + row0 * ix->dim;
+    hipLaunchKernelGGL(f32_to_t16_kernel, dim3((unsigned)cdiv64(n * ix->dim / 8, 256)), dim3(256), 0, st, rows, (__half*)ix->rows.db16, row0, n, ix->dim);
     OMNI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(row_norm_max_kernel, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, st, rows, n, ix->dim, ix->norm_max);
+    hipLaunchKernelGGL(row_norm_max_kernel, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, st, rows, n, ix->dim, ix->rows.norm_max);
     OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 
-// x_dev: n x dim fp32 in HBM -> appended (converted when storage is fp16)
-static int append_dev(omni_index* ix, int64_t n, const float* x_dev) {
+static int ensure_capacity(omni_index* ix, int64_t rows) {
+    bool rebuild_mirror;
+    const int rc = ix->rows.grow(rows, ix->ntotal, ix->ctx->stream, &rebuild_mirror);
+    return rc == OMNI_OK && rebuild_mirror ? mirror_rows(ix, 0, ix->ntotal) : rc;
+}
+
+// x: n x dim fp32, read by a copy of `kind` -> appended.  An fp16 shard converts on the device: its x is in HBM
+static int append_rows(omni_index* ix, int64_t n, const float* x, hipMemcpyKind kind) {
     OMNI_REQUIRE(ix->ntotal + n < 0xFFFFFFFFll, OMNI_ERR_CAPACITY, "index full: row ids are packed into 32 bits (omni_make_key)");
     int rc = ensure_capacity(ix, ix->ntotal + n);
     if (rc) return rc;
     hipStream_t st = ix->ctx->stream;
     const int64_t cnt = n * ix->dim;
     if (ix->storage == OMNI_STORE_F32) {
-        OMNI_HIP_TRY(hipMemcpyAsync((float*)ix->db + ix->ntotal * ix->dim, x_dev, (size_t)cnt * 4,
-                                    hipMemcpyDeviceToDevice, st));
+        OMNI_HIP_TRY(hipMemcpyAsync((float*)ix->rows.db + ix->ntotal * ix->dim, x, (size_t)cnt * 4, kind, st));
         if ((rc = mirror_rows(ix, ix->ntotal, n))) return rc;
     } else {
-        hipLaunchKernelGGL(f32_to_t16_kernel, dim3((unsigned)cdiv64(cnt / 8, 256)), dim3(256), 0, st, x_dev, (__half*)ix->db, ix->ntotal, n,
+        hipLaunchKernelGGL(f32_to_t16_kernel, dim3((unsigned)cdiv64(cnt / 8, 256)), dim3(256), 0, st, x, (__half*)ix->rows.db, ix->ntotal, n,
                            ix->dim);
         OMNI_LAUNCH_CHECK();
     }
     ix->ntotal += n;
+    return OMNI_OK;
+}
+
+// INDEX_PATH_MIRROR_CERT behind the mirror pass (its keys in keys_a): the best kp candidates per query re-scored EXACTLY against the fp32 rows, and per query the
+// results plus a certificate (cert_select_kernel) that they are the exact fp32 top-k -- scores bit-identical to the single-query kernel's.  The certificate is
+// checked on the host: one small copy + a wait for this search (its callers fetch the results right afterwards); the queries that are not certified go,
+// together, through the exact passes (what every batch cost before the mirror existed) -- results identical either way
+static int certify_or_rescan(omni_index* ix, const IndexSearchPlan& plan, int nq, const float* q_dev, int k, float* D_dev, int64_t* I_dev, int64_t n, const int64_t* limits) {
+    hipStream_t st = ix->ctx->stream;
+    uint64_t* ka = ix->keys_a.as<uint64_t>();
+    uint64_t* kb = ix->keys_b.as<uint64_t>();
+    const int kp = plan.kp;
+    int rc;
+    uint64_t* cand = nullptr;
+    if ((rc = topk_keys(st, ka, kb, nq, n, kp, &cand))) return rc;
+    hipLaunchKernelGGL(cert_refine_kernel, dim3((unsigned)cdiv64((int64_t)nq * kp, 4)), dim3(256), 0, st, reinterpret_cast<const float*>(ix->rows.db), ix->dim, q_dev,
+                       cand, nq, kp, ix->cert_keys.as<uint64_t>());
+    OMNI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cert_select_kernel, dim3(nq), dim3(64), 0, st, ix->cert_keys.as<uint64_t>(), cand, kp, k, q_dev, ix->dim, ix->rows.norm_max, ix->rank, ix->world,
+                       D_dev, I_dev, ix->cert_flags.as<int>());
+    OMNI_LAUNCH_CHECK();
+    OMNI_HIP_TRY(hipMemcpyAsync(ix->hflags.p, ix->cert_flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    OMNI_HIP_TRY(hipStreamSynchronize(st));
+    ix->cert_searches += nq;
+    const int* fl = ix->hflags.as<int>();
+    static const bool force_fallback = config_process()[CFG_INDEX_CERT_FAIL] != 0;      // test hook
+    GatherIdx gi;
+    int64_t lim_f[MQ_NQ];
+    int nfl = 0;
+    for (int q = 0; q < nq; ++q)
+        if (fl[q] || force_fallback) { gi.v[nfl] = q; lim_f[nfl] = limits ? limits[q] : INT64_MAX; ++nfl; }
+    if (nfl == 0) return OMNI_OK;
+    ix->cert_fallbacks += nfl;
+    for (int i = nfl; i < MQ_NQ; ++i) gi.v[i] = 0;
+    if ((rc = ix->stage.ensure((size_t)nfl * ix->dim * 4))) return rc;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(nfl), dim3(256), 0, st, q_dev, gi, ix->dim, ix->stage.as<float>());
+    OMNI_LAUNCH_CHECK();
+    if ((rc = run_scan_passes(st, ix, plan.fallback_passes(nfl), n, ix->stage.as<float>(), ka, lim_f, nullptr))) return rc;
+    uint64_t* r1 = nullptr;
+    if ((rc = topk_keys(st, ka, kb, nfl, n, k, &r1))) return rc;
+    hipLaunchKernelGGL(decode_topk_scatter_kernel, dim3(cdiv(nfl * k, 256)), dim3(256), 0, st, r1, nfl, k, ix->rank, ix->world, gi, D_dev, I_dev);
+    OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 
@@ -780,94 +855,45 @@ static int search_dev(omni_index* ix, int nq, const float* q_dev, int k, float* 
                       const int64_t* limits = nullptr) {
     hipStream_t st = ix->ctx->stream;
     const int64_t n = n_limit >= 0 && n_limit < ix->ntotal ? n_limit : ix->ntotal;      // rows [0, n) take part
-    const int64_t chunks = cdiv64(n > 0 ? n : 1, TOPK_CHUNK);
-    const int64_t per_q = (n > chunks * k ? n : chunks * k);
+    const IndexSearchPlan plan = index_search_plan(index_facts(ix), nq, k, n);
     int rc;
-    if ((rc = ix->keys_a.ensure((size_t)nq * per_q * 8))) return rc;
-    if ((rc = ix->keys_b.ensure((size_t)nq * per_q * 8))) return rc;
+    if ((rc = ix->keys_a.ensure(plan.keys_bytes))) return rc;
+    if ((rc = ix->keys_b.ensure(plan.keys_bytes))) return rc;
+    if ((rc = ix->cert_keys.ensure(plan.cert_keys_bytes))) return rc;
+    if ((rc = ix->cert_flags.ensure(plan.cert_flags_bytes))) return rc;
+    if ((rc = ix->hflags.ensure(plan.hflags_bytes))) return rc;
     uint64_t* ka = ix->keys_a.as<uint64_t>();
-    uint64_t* kb = ix->keys_b.as<uint64_t>();
-    // fp32 shard, a batch of queries: mirror pass + exact refinement + certificate (see omni_index::db16)
-    const int kp = k + 24 > 2 * k ? k + 24 : 2 * k;                 // candidates per query
-    // (small databases stay on the exact kernels: their scans are launch-bound, the mirror's extra launches and its host check would cost more
-    // than the halved HBM traffic saves -- OMNI_INDEX_MIRROR_MIN_ROWS, default 32768)
-    static const int64_t mirror_min_rows = config_process()[CFG_INDEX_MIRROR_MIN_ROWS];
-    if (n >= mirror_min_rows && n > 0 && ix->storage == OMNI_STORE_F32 && ix->db16 && nq >= mq_min_queries() && nq <= MQ_NQ && kp <= TOPK_SEL_MAX_K) {
-        if ((rc = ix->cert_keys.ensure((size_t)nq * kp * 8))) return rc;
-        if ((rc = ix->cert_flags.ensure((size_t)MQ_NQ * 4))) return rc;
-        if ((rc = ix->hflags.ensure((size_t)MQ_NQ * 4))) return rc;
+    if (plan.passes.count() > 0) {                                  // scan0 .. scan1: the mirror pass alone, or every pass of an exact search
         OMNI_HIP_TRY(hipEventRecord(ix->scan0, st));
-        if ((rc = launch_scan_mq(st, ix, n, nq, q_dev, ka, n, limits, ix->db16))) return rc;
+        if ((rc = run_scan_passes(st, ix, plan.passes, n, q_dev, ka, limits, plan.path == INDEX_PATH_MIRROR_CERT ? ix->rows.db16 : ix->rows.db))) return rc;
         OMNI_HIP_TRY(hipEventRecord(ix->scan1, st));
         ix->scan_timed = true;
-        uint64_t* cand = nullptr;
-        if ((rc = topk_keys(st, ka, kb, nq, n, kp, &cand))) return rc;
-        hipLaunchKernelGGL(cert_refine_kernel, dim3((unsigned)cdiv64((int64_t)nq * kp, 4)), dim3(256), 0, st, reinterpret_cast<const float*>(ix->db), ix->dim, q_dev,
-                           cand, nq, kp, ix->cert_keys.as<uint64_t>());
-        OMNI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(cert_select_kernel, dim3(nq), dim3(64), 0, st, ix->cert_keys.as<uint64_t>(), cand, kp, k, q_dev, ix->dim, ix->norm_max, ix->rank, ix->world,
-                           D_dev, I_dev, ix->cert_flags.as<int>());
-        OMNI_LAUNCH_CHECK();
-        // the certificate is checked on the host: one small copy + a wait for this search (its callers fetch the results right afterwards);
-        // a query that is not certified is searched again with the exact scan -- results identical either way
-        OMNI_HIP_TRY(hipMemcpyAsync(ix->hflags.p, ix->cert_flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-        OMNI_HIP_TRY(hipStreamSynchronize(st));
-        ix->cert_searches += nq;
-        const int* fl = ix->hflags.as<int>();
-        static const bool force_fallback = config_process()[CFG_INDEX_CERT_FAIL] != 0;      // test hook
-        // the uncertified queries, together, through the exact scan (blocks of <= 8 queries per pass over the fp32 rows: what every batch
-        // cost before the mirror existed)
-        GatherIdx gi;
-        int64_t lim_f[MQ_NQ];
-        int nfl = 0;
-        for (int q = 0; q < nq; ++q)
-            if (fl[q] || force_fallback) { gi.v[nfl] = q; lim_f[nfl] = limits ? limits[q] : INT64_MAX; ++nfl; }
-        if (nfl == 0) return OMNI_OK;
-        ix->cert_fallbacks += nfl;
-        for (int i = nfl; i < MQ_NQ; ++i) gi.v[i] = 0;
-        if ((rc = ix->stage.ensure((size_t)nfl * ix->dim * 4))) return rc;
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(nfl), dim3(256), 0, st, q_dev, gi, ix->dim, ix->stage.as<float>());
-        OMNI_LAUNCH_CHECK();
-        int max_qb = (int)(131072 / ((size_t)ix->dim * 4));
-        max_qb = max_qb > SCAN_MAX_QB ? SCAN_MAX_QB : (max_qb < 1 ? 1 : max_qb);
-        for (int q0 = 0; q0 < nfl; q0 += max_qb) {
-            const int qb = nfl - q0 < max_qb ? nfl - q0 : max_qb;
-            if ((rc = launch_scan(st, ix, n, qb, ix->stage.as<float>() + (int64_t)q0 * ix->dim, ka + (int64_t)q0 * n, n, lim_f + q0))) return rc;
-        }
-        uint64_t* r1 = nullptr;
-        if ((rc = topk_keys(st, ka, kb, nfl, n, k, &r1))) return rc;
-        hipLaunchKernelGGL(decode_topk_scatter_kernel, dim3(cdiv(nfl * k, 256)), dim3(256), 0, st, r1, nfl, k, ix->rank, ix->world, gi, D_dev, I_dev);
-        OMNI_LAUNCH_CHECK();
-        return OMNI_OK;
     }
-    if (n > 0) {
-        OMNI_HIP_TRY(hipEventRecord(ix->scan0, st));
-        const bool mq = ix->storage == OMNI_STORE_F16 && nq >= mq_min_queries();
-        for (int q0 = 0; mq && q0 < nq; q0 += MQ_NQ) {
-            const int qb = nq - q0 < MQ_NQ ? nq - q0 : MQ_NQ;
-            if ((rc = launch_scan_mq(st, ix, n, qb, q_dev + (int64_t)q0 * ix->dim, ka + (int64_t)q0 * n, n, limits ? limits + q0 : nullptr))) return rc;
-        }
-        int max_qb = (int)(131072 / ((size_t)ix->dim * 4));       // the query block lives in LDS: <= 128 KB of it
-        max_qb = max_qb > SCAN_MAX_QB ? SCAN_MAX_QB : (max_qb < 1 ? 1 : max_qb);
-        for (int q0 = 0; !mq && q0 < nq; q0 += max_qb) {
-            int qb = nq - q0 < max_qb ? nq - q0 : max_qb;
-            rc = launch_scan(st, ix, n, qb, q_dev + (int64_t)q0 * ix->dim, ka + (int64_t)q0 * n, n, limits ? limits + q0 : nullptr);
-            if (rc) return rc;
-        }
-        OMNI_HIP_TRY(hipEventRecord(ix->scan1, st));
-        ix->scan_timed = true;
+    switch (plan.path) {
+        case INDEX_PATH_MIRROR_CERT: return certify_or_rescan(ix, plan, nq, q_dev, k, D_dev, I_dev, n, limits);
+        case INDEX_PATH_MQ_F16:
+        case INDEX_PATH_EXACT_SCAN: break;                          // the keys of every (query, row) are in keys_a
     }
     uint64_t* res = nullptr;
-    if ((rc = topk_keys(st, ka, kb, nq, n, k, &res))) return rc;
+    if ((rc = topk_keys(st, ka, ix->keys_b.as<uint64_t>(), nq, n, k, &res))) return rc;
     hipLaunchKernelGGL(decode_topk_kernel, dim3(cdiv(nq * k, 256)), dim3(256), 0, st, res, nq, k, ix->rank, ix->world,
                        D_dev, I_dev);
     OMNI_LAUNCH_CHECK();
     return OMNI_OK;
 }
 
+// what every search entry checks first (pointers: the entry's own were all non-null)
+static int check_search_args(bool pointers, int nq, int nq_max, int k) {
+    OMNI_REQUIRE(pointers, OMNI_ERR_INVALID, "null argument");
+    OMNI_REQUIRE(nq >= 1 && nq <= nq_max, OMNI_ERR_CAPACITY, "nq=%d outside [1,%d]", nq, nq_max);
+    OMNI_REQUIRE(k >= 1 && k <= TOPK_MAX_K, OMNI_ERR_CAPACITY, "k=%d outside [1,%d]", k, TOPK_MAX_K);
+    return OMNI_OK;
+}
+
 }  // namespace omni
 
 extern "C" {
+using omni::MQ_NQ;
 
 omni_index* omni_index_create(omni_ctx* ctx, int dim, int storage, int64_t initial_capacity_rows) {
     if (!ctx) { omni::set_error("null ctx"); return nullptr; }
@@ -879,15 +905,12 @@ omni_index* omni_index_create(omni_ctx* ctx, int dim, int storage, int64_t initi
     (void)hipSetDevice(ctx->device);
     omni_index* ix = new omni_index();
     ix->ctx = ctx; ix->dim = dim; ix->storage = storage;
+    ix->rows.init(dim, storage);
     if (hipEventCreate(&ix->scan0) != hipSuccess || hipEventCreate(&ix->scan1) != hipSuccess) {
         omni::set_error("hipEventCreate failed"); delete ix; return nullptr;
     }
     static const bool mirror_on = omni::config_process()[omni::CFG_INDEX_MIRROR] != 0;
-    if (storage == OMNI_STORE_F32 && mirror_on) {
-        if (hipMalloc((void**)&ix->norm_max, 4) != hipSuccess || hipMemsetAsync(ix->norm_max, 0, 4, ctx->stream) != hipSuccess) {
-            omni::set_error("hipMalloc failed"); omni_index_destroy(ix); return nullptr;
-        }
-    }
+    if (storage == OMNI_STORE_F32 && mirror_on && ix->rows.want_mirror(ctx->stream) != OMNI_OK) { omni_index_destroy(ix); return nullptr; }
     if (initial_capacity_rows > 0 && omni::ensure_capacity(ix, initial_capacity_rows) != OMNI_OK) { omni_index_destroy(ix); return nullptr; }
     return ix;
 }
@@ -896,9 +919,7 @@ void omni_index_destroy(omni_index* ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->ctx->device);
     (void)hipStreamSynchronize(ix->ctx->stream);
-    if (ix->db) (void)hipFree(ix->db);
-    if (ix->db16) (void)hipFree(ix->db16);
-    if (ix->norm_max) (void)hipFree(ix->norm_max);
+    ix->rows.release();
     ix->cert_keys.release(); ix->cert_flags.release(); ix->hflags.release();
     ix->qbuf.release(); ix->keys_a.release(); ix->keys_b.release(); ix->out_d.release(); ix->out_i.release();
     ix->stage.release(); ix->mq_q.release(); ix->mq_inv.release(); ix->hq.release(); ix->hout.release();
@@ -932,8 +953,7 @@ int omni_index_set_shard(omni_index* ix, int rank, int world) {
     // A shard's searches are ENQUEUED (omni_shard_step_enqueue: no host synchronisation between its collectives, the scan and the copy of the lists).  The
     // mirror path of the batched search checks its exactness certificate on the host -- a wait in the middle of that unit -- so a sharded index searches
     // its fp32 rows with the exact many-query scan (no certificate, nothing to check) and drops the mirror: +0 % HBM instead of +50 %.
-    if (ix->db16) { (void)hipFree(ix->db16); ix->db16 = nullptr; }
-    if (ix->norm_max) { (void)hipFree(ix->norm_max); ix->norm_max = nullptr; }
+    ix->rows.drop_mirror();
     return OMNI_OK;
 }
 
@@ -943,7 +963,7 @@ int omni_index_add_dev(omni_index* ix, int64_t n, const float* x_dev) {
     std::lock_guard<std::mutex> lk(ix->mu);
     (void)hipSetDevice(ix->ctx->device);
     if (n == 0) return OMNI_OK;
-    return omni::append_dev(ix, n, x_dev);
+    return omni::append_rows(ix, n, x_dev, hipMemcpyDeviceToDevice);
 }
 
 int omni_index_add(omni_index* ix, int64_t n, const float* x_host) {
@@ -959,16 +979,11 @@ int omni_index_add(omni_index* ix, int64_t n, const float* x_host) {
         int64_t m = n - s < slab ? n - s : slab;
         size_t bytes = (size_t)m * ix->dim * 4;
         if (ix->storage == OMNI_STORE_F32) {
-            OMNI_REQUIRE(ix->ntotal + m < 0xFFFFFFFFll, OMNI_ERR_CAPACITY, "index full: row ids are packed into 32 bits (omni_make_key)");
-            if ((rc = omni::ensure_capacity(ix, ix->ntotal + m))) return rc;
-            OMNI_HIP_TRY(hipMemcpyAsync((float*)ix->db + ix->ntotal * ix->dim, x_host + s * ix->dim, bytes,
-                                        hipMemcpyHostToDevice, ix->ctx->stream));
-            if ((rc = omni::mirror_rows(ix, ix->ntotal, m))) return rc;
-            ix->ntotal += m;
+            if ((rc = omni::append_rows(ix, m, x_host + s * ix->dim, hipMemcpyHostToDevice))) return rc;
         } else {
             if ((rc = ix->stage.ensure(bytes))) return rc;
             OMNI_HIP_TRY(hipMemcpyAsync(ix->stage.p, x_host + s * ix->dim, bytes, hipMemcpyHostToDevice, ix->ctx->stream));
-            if ((rc = omni::append_dev(ix, m, ix->stage.as<float>()))) return rc;
+            if ((rc = omni::append_rows(ix, m, ix->stage.as<float>(), hipMemcpyDeviceToDevice))) return rc;
         }
         OMNI_HIP_TRY(hipStreamSynchronize(ix->ctx->stream));   // x_host may be pageable / reused by the caller
     }
@@ -977,9 +992,7 @@ int omni_index_add(omni_index* ix, int64_t n, const float* x_host) {
 
 int omni_index_search_dev(omni_index* ix, int nq, const float* q_dev, int k, float* D_dev, int64_t* I_dev) {
     omni::TraceRange trace_range("index search");
-    OMNI_REQUIRE(ix && q_dev && D_dev && I_dev, OMNI_ERR_INVALID, "null argument");
-    OMNI_REQUIRE(nq >= 1 && nq <= 4096, OMNI_ERR_CAPACITY, "nq=%d outside [1,4096]", nq);
-    OMNI_REQUIRE(k >= 1 && k <= TOPK_MAX_K, OMNI_ERR_CAPACITY, "k=%d outside [1,%d]", k, TOPK_MAX_K);
+    if (int rc = omni::check_search_args(ix && q_dev && D_dev && I_dev, nq, 4096, k)) return rc;
     std::lock_guard<std::mutex> lk(ix->mu);
     (void)hipSetDevice(ix->ctx->device);
     return omni::search_dev(ix, nq, q_dev, k, D_dev, I_dev);
@@ -987,9 +1000,7 @@ int omni_index_search_dev(omni_index* ix, int nq, const float* q_dev, int k, flo
 
 int omni_index_search_prefix_dev(omni_index* ix, int nq, const float* q_dev, int k, int64_t n_limit, float* D_dev, int64_t* I_dev) {
     omni::TraceRange trace_range("index search (prefix)");
-    OMNI_REQUIRE(ix && q_dev && D_dev && I_dev, OMNI_ERR_INVALID, "null argument");
-    OMNI_REQUIRE(nq >= 1 && nq <= 4096, OMNI_ERR_CAPACITY, "nq=%d outside [1,4096]", nq);
-    OMNI_REQUIRE(k >= 1 && k <= TOPK_MAX_K, OMNI_ERR_CAPACITY, "k=%d outside [1,%d]", k, TOPK_MAX_K);
+    if (int rc = omni::check_search_args(ix && q_dev && D_dev && I_dev, nq, 4096, k)) return rc;
     OMNI_REQUIRE(n_limit >= 0, OMNI_ERR_INVALID, "n_limit=%lld < 0", (long long)n_limit);
     std::lock_guard<std::mutex> lk(ix->mu);
     (void)hipSetDevice(ix->ctx->device);
@@ -999,9 +1010,7 @@ int omni_index_search_prefix_dev(omni_index* ix, int nq, const float* q_dev, int
 int omni_index_search_batch_prefix_dev(omni_index* ix, int nq, const float* rows_dev, const int64_t* row_idx, int k,
                                        const int64_t* n_limits, float* D_dev, int64_t* I_dev) {
     omni::TraceRange trace_range("index search (batch, prefix)");
-    OMNI_REQUIRE(ix && rows_dev && n_limits && D_dev && I_dev, OMNI_ERR_INVALID, "null argument");
-    OMNI_REQUIRE(nq >= 1 && nq <= MQ_NQ, OMNI_ERR_CAPACITY, "nq=%d outside [1,%d]", nq, MQ_NQ);
-    OMNI_REQUIRE(k >= 1 && k <= TOPK_MAX_K, OMNI_ERR_CAPACITY, "k=%d outside [1,%d]", k, TOPK_MAX_K);
+    if (int rc = omni::check_search_args(ix && rows_dev && n_limits && D_dev && I_dev, nq, MQ_NQ, k)) return rc;
     std::lock_guard<std::mutex> lk(ix->mu);
     (void)hipSetDevice(ix->ctx->device);
     int64_t lim[MQ_NQ], nmax = 0;
@@ -1025,9 +1034,7 @@ int omni_index_search_batch_prefix_dev(omni_index* ix, int nq, const float* rows
 
 int omni_index_search(omni_index* ix, int nq, const float* q_host, int k, float* D, int64_t* I) {
     omni::TraceRange trace_range("index search (host queries)");
-    OMNI_REQUIRE(ix && q_host && D && I, OMNI_ERR_INVALID, "null argument");
-    OMNI_REQUIRE(nq >= 1 && nq <= 4096, OMNI_ERR_CAPACITY, "nq=%d outside [1,4096]", nq);
-    OMNI_REQUIRE(k >= 1 && k <= TOPK_MAX_K, OMNI_ERR_CAPACITY, "k=%d outside [1,%d]", k, TOPK_MAX_K);
+    if (int rc = omni::check_search_args(ix && q_host && D && I, nq, 4096, k)) return rc;
     std::lock_guard<std::mutex> lk(ix->mu);
     if (ix->ntotal == 0) {      // faiss pads an empty index's result with -1 labels; nothing to launch
         for (size_t i = 0; i < (size_t)nq * k; ++i) { D[i] = -3.402823466e+38f; I[i] = -1; }
@@ -1067,7 +1074,7 @@ int omni_index_save(omni_index* ix, const char* path) {
     OmnxHeader h{};
     memcpy(h.magic, "OMNX1\0\0", 8); h.dim = ix->dim; h.storage = ix->storage; h.ntotal = ix->ntotal;
     bool ok = fwrite(&h, sizeof(h), 1, f) == 1;
-    const size_t row = (size_t)ix->dim * ix->elem(), slab_rows = 4096;
+    const size_t row = ix->rows.row_bytes, slab_rows = 4096;
     int rc = ix->hout.ensure(slab_rows * row);
     const bool f16 = ix->storage == OMNI_STORE_F16;              // snapshots hold plain row-major rows: de-block the T16 layout per slab
     if (!rc && f16) rc = ix->stage.ensure(slab_rows * row);
@@ -1075,8 +1082,8 @@ int omni_index_save(omni_index* ix, const char* path) {
         const size_t m = (size_t)(ix->ntotal - s < (int64_t)slab_rows ? ix->ntotal - s : slab_rows);
         if (f16)
             hipLaunchKernelGGL((omni::t16_rows_kernel<true>), dim3((unsigned)omni::cdiv64((int64_t)m * (ix->dim / 8), 256)), dim3(256), 0,
-                               ix->ctx->stream, (__half*)ix->db, ix->stage.as<__half>(), s, (int64_t)m, ix->dim);
-        if (hipMemcpyAsync(ix->hout.p, f16 ? (const char*)ix->stage.p : (const char*)ix->db + (size_t)s * row, m * row, hipMemcpyDeviceToHost,
+                               ix->ctx->stream, (__half*)ix->rows.db, ix->stage.as<__half>(), s, (int64_t)m, ix->dim);
+        if (hipMemcpyAsync(ix->hout.p, f16 ? (const char*)ix->stage.p : (const char*)ix->rows.db + (size_t)s * row, m * row, hipMemcpyDeviceToHost,
                            ix->ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ix->ctx->stream) != hipSuccess) { omni::set_error("device read failed while saving"); rc = OMNI_ERR_HIP; break; }
         ok = fwrite(ix->hout.p, row, m, f) == m;
@@ -1095,7 +1102,7 @@ int omni_index_load(omni_index* ix, const char* path) {
     OMNI_REQUIRE(f, OMNI_ERR_INVALID, "cannot open %s", path);
     OmnxHeader h{};
     int rc = OMNI_OK;
-    const size_t row = (size_t)ix->dim * ix->elem(), slab_rows = 4096;
+    const size_t row = ix->rows.row_bytes, slab_rows = 4096;
     if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "OMNX1\0\0", 8) != 0) { omni::set_error("%s is not an OMNX1 snapshot", path); rc = OMNI_ERR_INVALID; }
     else if (h.dim != ix->dim || h.storage != ix->storage || h.ntotal < 0 || h.ntotal >= 0xFFFFFFFFll) {
         omni::set_error("snapshot %s is dim=%d storage=%d ntotal=%lld, the handle is dim=%d storage=%d", path, h.dim, h.storage, (long long)h.ntotal,
@@ -1110,12 +1117,13 @@ int omni_index_load(omni_index* ix, const char* path) {
         }
     }
     // load into a FRESH buffer and swap on success: a failed load leaves the handle as it was
-    void* nd = nullptr;
-    int64_t cap = 0;
+    omni::IndexRows fresh;
+    fresh.init(ix->dim, ix->storage);
     if (!rc) {
-        cap = ((h.ntotal > 0 ? h.ntotal : 1) + 15) & ~(int64_t)15;
-        if (hipMalloc(&nd, (size_t)cap * row) != hipSuccess) { omni::set_error("hipMalloc(%zu) failed while loading", (size_t)cap * row); nd = nullptr; rc = OMNI_ERR_NOMEM; }
+        const int64_t cap = omni::index_loaded_capacity(h.ntotal);
+        if (!fresh.reserve(cap)) { omni::set_error("hipMalloc(%zu) failed while loading", (size_t)cap * row); rc = OMNI_ERR_NOMEM; }
     }
+    void* const nd = fresh.db;
     if (!rc) rc = ix->hout.ensure(slab_rows * row);
     const bool f16 = ix->storage == OMNI_STORE_F16;
     if (!rc && f16) rc = ix->stage.ensure(slab_rows * row);
@@ -1130,21 +1138,11 @@ int omni_index_load(omni_index* ix, const char* path) {
         if (!okc || hipStreamSynchronize(ix->ctx->stream) != hipSuccess) { omni::set_error("device write failed while loading"); rc = OMNI_ERR_HIP; }
     }
     fclose(f);
-    if (rc) { if (nd) (void)hipFree(nd); return rc; }
-    (void)hipStreamSynchronize(ix->ctx->stream);
-    if (ix->db) (void)hipFree(ix->db);
-    if (ix->db16) { (void)hipFree(ix->db16); ix->db16 = nullptr; }
-    ix->db = nd; ix->capacity = cap; ix->ntotal = h.ntotal;
-    if (ix->norm_max) {                                              // rebuild the fp16 mirror of the loaded rows
-        if (hipMalloc(&ix->db16, (size_t)cap * ix->dim * 2) != hipSuccess) {
-            // no room for the mirror: the rows are loaded, the index works -- every batch goes through the exact scan from now on.  (Leaving norm_max set with
-            // no mirror made the next growth allocate an EMPTY mirror for the rows already held: the certificate would have trusted garbage.)
-            ix->db16 = nullptr;
-            (void)hipGetLastError();
-            (void)hipFree(ix->norm_max); ix->norm_max = nullptr;
-            return OMNI_OK;
-        }
-        OMNI_HIP_TRY(hipMemsetAsync(ix->norm_max, 0, 4, ix->ctx->stream));
+    if (rc) { fresh.release(); return rc; }
+    ix->rows.adopt(fresh, ix->ctx->stream);
+    ix->ntotal = h.ntotal;
+    if (ix->rows.db16) {                                             // rebuild the fp16 mirror of the loaded rows
+        OMNI_HIP_TRY(hipMemsetAsync(ix->rows.norm_max, 0, 4, ix->ctx->stream));
         if ((rc = omni::mirror_rows(ix, 0, h.ntotal))) return rc;
         OMNI_HIP_TRY(hipStreamSynchronize(ix->ctx->stream));
     }
@@ -1164,13 +1162,13 @@ int omni_index_debug_scan(omni_index* ix, int which, int nq, const float* q_host
     std::lock_guard<std::mutex> lk(ix->mu);
     OMNI_REQUIRE(n >= 1 && n <= ix->ntotal, OMNI_ERR_INVALID, "n=%lld outside [1, ntotal=%lld]", (long long)n, (long long)ix->ntotal);
     const bool f16 = ix->storage == OMNI_STORE_F16;
-    const int max_qb = (int)(131072 / ((size_t)ix->dim * 4)) < SCAN_MAX_QB ? (int)(131072 / ((size_t)ix->dim * 4)) : SCAN_MAX_QB;      // search_dev's query block
+    const int max_qb = omni::index_query_block(ix->dim);
     switch (which) {
         case OMNI_SCAN_F32:       OMNI_REQUIRE(!f16 && nq >= 1 && nq <= max_qb, OMNI_ERR_INVALID, "ip_scan_kernel: fp32 rows, 1 <= nq <= %d", max_qb); break;
         case OMNI_SCAN_F32_ROWS:  OMNI_REQUIRE(!f16 && nq >= 4 && nq <= max_qb, OMNI_ERR_INVALID, "ip_scan_rows_kernel: fp32 rows, 4 <= nq <= %d", max_qb); break;
         case OMNI_SCAN_T16:       OMNI_REQUIRE(f16 && nq >= 1 && nq <= max_qb, OMNI_ERR_INVALID, "ip_scan_t16_kernel: fp16 rows, 1 <= nq <= %d", max_qb); break;
         case OMNI_SCAN_MQ:        OMNI_REQUIRE(f16 && nq >= 1 && nq <= MQ_NQ, OMNI_ERR_INVALID, "ip_scan_mq_kernel: fp16 rows, 1 <= nq <= %d", MQ_NQ); break;
-        case OMNI_SCAN_MQ_MIRROR: OMNI_REQUIRE(!f16 && ix->db16 && nq >= 1 && nq <= MQ_NQ, OMNI_ERR_INVALID, "ip_scan_mq_kernel on the mirror: fp32 rows with a mirror, 1 <= nq <= %d", MQ_NQ); break;
+        case OMNI_SCAN_MQ_MIRROR: OMNI_REQUIRE(!f16 && ix->rows.db16 && nq >= 1 && nq <= MQ_NQ, OMNI_ERR_INVALID, "ip_scan_mq_kernel on the mirror: fp32 rows with a mirror, 1 <= nq <= %d", MQ_NQ); break;
         default: omni::set_error("omni_index_debug_scan: unknown kernel %d", which); return OMNI_ERR_INVALID;
     }
     (void)hipSetDevice(ix->ctx->device);
@@ -1183,10 +1181,12 @@ int omni_index_debug_scan(omni_index* ix, int which, int nq, const float* q_host
     auto done = [&](int code) { (void)hipStreamSynchronize(st); q_dev.release(); keys.release(); return code; };
     if (hipMemcpyAsync(q_dev.p, q_host, qbytes, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemsetAsync(keys.p, 0xFF, kbytes, st) != hipSuccess) { omni::set_error("omni_index_debug_scan: upload failed"); return done(OMNI_ERR_HIP); }
+    const omni::IndexFacts facts = omni::index_facts(ix);
     if (which == OMNI_SCAN_MQ || which == OMNI_SCAN_MQ_MIRROR)
-        rc = omni::launch_scan_mq(st, ix, n, nq, q_dev.as<float>(), keys.as<uint64_t>(), n, limits, which == OMNI_SCAN_MQ_MIRROR ? ix->db16 : nullptr, rotate ? 1 : 0);
+        rc = omni::launch_scan_mq(st, ix, facts, n, nq, q_dev.as<float>(), keys.as<uint64_t>(), n, limits, which == OMNI_SCAN_MQ_MIRROR ? ix->rows.db16 : ix->rows.db, rotate ? 1 : 0);
     else
-        rc = omni::launch_scan(st, ix, n, nq, q_dev.as<float>(), keys.as<uint64_t>(), n, limits, which == OMNI_SCAN_F32_ROWS ? 1 : 0);
+        rc = omni::launch_scan(st, ix, facts, which == OMNI_SCAN_F32_ROWS ? omni::INDEX_SCAN_F32_ROWS : which == OMNI_SCAN_T16 ? omni::INDEX_SCAN_T16 : omni::INDEX_SCAN_F32_ONE, n, nq,
+                               q_dev.as<float>(), keys.as<uint64_t>(), n, limits);
     if (rc) return done(rc);
     if (hipMemcpyAsync(keys_host, keys.p, kbytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         omni::set_error("omni_index_debug_scan: read-back failed"); return done(OMNI_ERR_HIP);

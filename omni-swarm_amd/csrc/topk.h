@@ -6,10 +6,9 @@
 // first k; levels repeat until one chunk is left.  Exact for any n, k <= TOPK_MAX_K.
 #pragma once
 #include "common.h"
+#include "topk_sizes.h"
 
-#define TOPK_CHUNK 2048
 #define TOPK_THREADS 1024
-#define TOPK_MAX_K 1024
 
 namespace omni {
 
@@ -53,7 +52,6 @@ topk_chunk_kernel(const uint64_t* __restrict__ keys_in, int64_t n_in, int64_t in
 // 8 bits over the keys' high words, 256-bin LDS histograms), gather the keys at or above it (k plus ties) and rank those by
 // counting.  Exact: ties at the cut-off are resolved on the full 64-bit key (lower id first); if more than TOPK_SEL_CAP keys tie
 // the chunk falls back to the bitonic sort in place.  ~4x less work than the full sort for the k = 5 + max_index of the reference.
-#define TOPK_SEL_MAX_K 64
 #define TOPK_SEL_CAP 512
 #define TOPK_SEL_THREADS 256
 static __global__ void __launch_bounds__(TOPK_SEL_THREADS)

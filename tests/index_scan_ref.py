@@ -7,18 +7,18 @@ below +0), low word = 0xFFFFFFFF - row, 0 = OMNI_KEY_EMPTY for a row at or beyon
 
 A score's reference is the IDEAL VALUE OF THE KERNEL'S OWN ALGEBRA in float64, from the operands AS STORED:
   ip_scan_kernel<float, QB>, ip_scan_rows_kernel<QB, 4>, cert_refine_kernel.  fp32 rows, fp32 queries:  y = sum_k q_k row_k.
-      A lane adds its dim / 64 products with one fmaf each (index.hip:88-99 / 140-155 / 563-567: columns 4 lane + 256 j + e, j outer, e inner), wave_sum adds
-      the 64 lanes in a butterfly of 6 additions (index.hip:59-63, offsets 32, 16, .. 1):  K = dim / 64 + 6.
+      A lane adds its dim / 64 products with one fmaf each (index.hip:157-168 / 209-224 / 625-629: columns 4 lane + 256 j + e, j outer, e inner), wave_sum adds
+      the 64 lanes in a butterfly of 6 additions (index.hip:128-132, offsets 32, 16, .. 1):  K = dim / 64 + 6.
   ip_scan_t16_kernel<QB>.  Rows are fp16(row) (f32_to_t16_kernel, round to nearest even), converted back exactly:  y = sum_k q_k fp16(row_k).  Lane (r, c) of
-      a 16-row block adds the 8 halfs of chunk 4 st + c for st = 0 .. dim / 32 - 1 (index.hip:501-518): a chain of dim / 4 fmaf; two shuffles (xor 16, xor 32,
-      index.hip:523-524) add the 4 chunk lanes of a row:  K = dim / 4 + 2.
-  ip_scan_mq_kernel (on an fp16 shard, or on the fp16 mirror of an fp32 shard).  ``mq_prep`` restates mq_prep_kernel (index.hip:196-230): per query
+      a 16-row block adds the 8 halfs of chunk 4 st + c for st = 0 .. dim / 32 - 1 (index.hip:563-580): a chain of dim / 4 fmaf; two shuffles (xor 16, xor 32,
+      index.hip:585-586) add the 4 chunk lanes of a row:  K = dim / 4 + 2.
+  ip_scan_mq_kernel (on an fp16 shard, or on the fp16 mirror of an fp32 shard).  ``mq_prep`` restates mq_prep_kernel (index.hip:258-292): per query
       m = max |q|, sh = 13 - ilogb(m) clamped to +-100 (0 for m = 0 and for the padding slots nq .. 63, whose operands are zero), v = fl32(q 2^sh),
       hi = half(v), lo = half(v - hi), inv = 2^-sh.  The kernel adds hi_k row_k and lo_k row_k (both exact in fp32) and multiplies by inv once
-      (index.hip:399):  y = inv sum_k (hi_k + lo_k) fp16(row_k).  The dropped residue v - hi - lo is no error of the scan: it is an allowance of its own,
+      (index.hip:461):  y = inv sum_k (hi_k + lo_k) fp16(row_k).  The dropped residue v - hi - lo is no error of the scan: it is an allowance of its own,
       R = inv sum_k max(2^-22 |v_k|, 2^-25) |fp16(row_k)|  (half an fp16 step of lo, |lo| <= ulp16(v) / 2; 2^-25 absolute where lo is an fp16 subnormal),
       which the certificate's budget has to cover as well (``cert_eps``).
-      K.  Per k-step one v_mfma_f32_16x16x32_f16 against hi, one against lo, each adding 32 exact products to the fp32 accumulator (index.hip:269-274).
+      K.  Per k-step one v_mfma_f32_16x16x32_f16 against hi, one against lo, each adding 32 exact products to the fp32 accumulator (index.hip:331-336).
       ASSUMED of one MFMA: nothing but that every addition inside it rounds no worse than an fp32 addition, in any order (the hardware's order and its
       intermediate width are not documented).  Any such summation of the 2 dim products stays within gamma_(2 dim) T:  K = 2 dim, the full-gamma
       convention of split_layer_ref for tier 1.  The final multiplication by a power of two is exact (scores in the normal range).
@@ -28,7 +28,7 @@ Two tiers per score.
       query): the score is exactly 0.
   Tier 2 (sensitivity): the same summation emulated in float32 on the CPU (``valu_emul``, ``t16_emul``, ``mq_emul``: the lane's fmaf chain and the shuffles in
       the kernel's order; for the matrix cores one MFMA = one exact 32-term dot added to the accumulator with one rounding, hi then lo per k-step, the k-slices
-      in the order the rotation gives the row's 512-row block (index.hip:302-305: block index mod dim / 256), times inv once).  Per class (``tier2``), with
+      in the order the rotation gives the row's 512-row block (index.hip:364-367: block index mod dim / 256), times inv once).  Per class (``tier2``), with
       z = error / tier-1 allowance:  RMS(z_got) <= c RMS(z_emul).  Classes hold >= 1 000 scores (smaller ones are not judged alone; a case with fewer than
       1 000 scores in all is left to tier 1): for the VALU kernels the query slot and the row mod 4 (fp32: the rows kernel's place in its group) or mod 16
       (fp16: the row of the block); for the matrix cores the query slot (64), the (wave, row tile) place of the row's 16-row tile in its 512-row block (32),
@@ -48,7 +48,7 @@ U = 2.0 ** -24
 TIER2_C = {"f32": 2.0, "t16": 2.0, "mq": 8.57}
 MIN_CLASS = 1000
 KEY_EMPTY = np.uint64(0)
-# cert_select_kernel's constants (index.hip:615-620), as the float32 literals they are
+# cert_select_kernel's constants (index.hip:677-682), as the float32 literals they are
 CERT_RND = np.float32(4.8829e-4) * np.float32(1.0001)
 CERT_SUB = np.float32(6.0e-8)
 CERT_ARITH = np.float32(4.0e-6)
