@@ -4,7 +4,7 @@
 //     not a number fails the creation loudly instead of silently selecting something;
 //   * launch-site hooks (traces, timing ablations, A/B forcing of a tile orientation, the index thresholds) are process-wide: config_process(), resolved
 //     at FIRST USE -- the first launch or index search that looks at one of them -- and frozen from then on (loading the library freezes nothing: its
-//     initializer reads OMNI_HW_QUEUES alone, config_option_now); omni_config_value reports the frozen value of such an option once it is frozen;
+//     initializer reads OMNI_HW_QUEUES and the runtime's GPU_MAX_HW_QUEUES alone, config_option_now); omni_config_value reports the frozen value of such an option once it is frozen;
 //   * include/omni_hip.h: omni_config_count / omni_config_describe / omni_config_value list the table and what a handle created now would see
 //     (tests/test_config_cpu.py asserts the default variant set -- the production path -- from it).
 #pragma once
@@ -51,5 +51,7 @@ int config_resolve(Config* out);
 const Config& config_process();
 // ONE option parsed from the environment as it is now, nothing cached (the library's load-time initializer)
 int config_option_now(CfgId i);
+// GPU_MAX_HW_QUEUES as the process has it now (nullptr: unset): the preset the initializer weighs against OMNI_HW_QUEUES (stream_plan.h hw_queues_to_set)
+const char* config_runtime_hw_queues();
 
 }  // namespace omni

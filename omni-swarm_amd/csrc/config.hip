@@ -1,5 +1,6 @@
 // config.hip -- the table behind config.h and its C entry points (include/omni_hip.h: omni_config_*)
 #include "config.h"
+#include "stream_plan.h"
 
 #include <atomic>
 #include <cerrno>
@@ -88,8 +89,10 @@ const CfgOption kCfgOptions[CFG_COUNT] = {
                                                       "1 = it only surveys the 0xFF bytes (csrc/jpeg_dec_plan.h survey), uploads the scans as they are, and one kernel in front of "
                                                       "the others compacts them by tiles of 4096 bytes.  Same pixels, same statistics"},
     // ---- runtime ---------------------------------------------------------------------------------------------------------------------------------------
-    {"OMNI_HW_QUEUES", 8, 0, 64, CFG_TUNING, "hardware queues asked of the HIP runtime when the library is loaded (GPU_MAX_HW_QUEUES, unless already set): the pipeline's five "
-                                            "streams must not share one; 0 = the runtime's default of 4"},
+    {"OMNI_HW_QUEUES", HW_QUEUES_DEFAULT, 0, HW_QUEUES_MAX, CFG_TUNING, "hardware queues asked of the HIP runtime when the library is loaded: GPU_MAX_HW_QUEUES is set to this number unless "
+                                            "it already holds one as high or higher (a lower one is overwritten, stream_plan.h hw_queues_to_set).  The default covers the streams of a "
+                                            "default pipeline (four lanes and a tail lane of two each, the detector, PnP, the caller's, the null stream) in whole fours: two streams on "
+                                            "one queue run one after the other.  N = exactly N for a process that has set no more; 0 = the variable is left as it is"},
     // ---- strings ---------------------------------------------------------------------------------------------------------------------------------------
     {"OMNI_RCCL_LIB", 0, 0, 0, CFG_STRING, "path of the RCCL library omni_shard dlopens (default: librccl.so next to torch, then the loader's search path)"},
 };
@@ -137,6 +140,8 @@ int config_option_now(CfgId i) {
     parse_one(kCfgOptions[i], &v, &bad);
     return v;                                   // (an invalid value: the default)
 }
+
+const char* config_runtime_hw_queues() { return getenv("GPU_MAX_HW_QUEUES"); }
 
 const Config& config_process() {
     static const Config c = [] {

@@ -3,6 +3,7 @@
 // TensorRTInferenceGeneric (swarm_loop/src/tensorrt_generic.cpp:14-36,99-120).
 #include "config.h"
 #include "common.h"
+#include "stream_plan.h"
 
 #include <cstdlib>
 #include <dlfcn.h>
@@ -17,16 +18,18 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace omni
 
-// The key-frame pipeline keeps five streams busy (two units in flight x (SuperPoint, MobileNetVLAD) + the detector's); the HIP runtime multiplexes
-// streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default, and two streams on one queue run strictly one after the other: the detector's search
-// of micro-batch k then sits behind the MobileNetVLAD kernels of micro-batch k + 1, the host waits for it, and the GPU idles 15 % of the time
-// (rocprofv3 kernel trace of round 4).  The runtime reads the variable when it initialises: ask for 8 queues when this library is loaded,
-// unless the process already chose (OMNI_HW_QUEUES=0 leaves the runtime's default).
+// The key-frame pipeline keeps nine streams busy (four units in flight x (SuperPoint, MobileNetVLAD) + the detector's) and creates five more
+// (stream_plan.h); the HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default, idle streams included, and two streams on
+// one queue run strictly one after the other: a unit's SuperPoint kernels then sit behind another unit's MobileNetVLAD kernels, and the detector's search
+// of micro-batch k behind the kernels of micro-batch k + 1 while the host waits for it (15 % idle with five streams on four queues in round 4, DESIGN.md;
+// with nine on five the four units in flight start two behind two and each takes 1.3 ms longer, profiles/r11_queues.md).  The runtime reads the variable when it initialises: when this library is loaded it asks for the
+// plan's number, over a lower value the process came with and never below a higher one (hw_queues_to_set; OMNI_HW_QUEUES=0 leaves the variable alone).
 namespace {
 struct HwQueues {
     HwQueues() {
-        const int n = omni::config_option_now(omni::CFG_HW_QUEUES);      // this option only: the process-wide table stays unresolved until something uses it
-        if (n > 0) { char v[16]; snprintf(v, sizeof(v), "%d", n); setenv("GPU_MAX_HW_QUEUES", v, 0); }
+        // this option only: the process-wide table stays unresolved until something uses it
+        const int n = omni::hw_queues_to_set(omni::config_option_now(omni::CFG_HW_QUEUES), omni::config_runtime_hw_queues());
+        if (n > 0) { char v[16]; snprintf(v, sizeof(v), "%d", n); setenv("GPU_MAX_HW_QUEUES", v, 1); }
     }
 } g_hw_queues;
 }  // namespace

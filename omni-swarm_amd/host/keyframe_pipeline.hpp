@@ -14,6 +14,7 @@
 #include <memory>
 #include <thread>
 
+#include "../csrc/stream_plan.h"
 #include "camera_model.hpp"
 #include "fisheye_flatten.hpp"
 #include "loop_geometry.hpp"
@@ -173,7 +174,7 @@ public:
 
     // units in flight when the caller does not say: fp16's small-grid tails (NMS, sampling, matcher, MobileNetVLAD's last blocks) are filled by the next
     // units' kernels, so four pay; the fp32-class modes are CU-filling convolutions end to end and gain nothing beyond two
-    static int default_pipelines(int precision) { return precision == OMNI_PREC_F16 ? 4 : 2; }
+    static int default_pipelines(int precision) { return precision == OMNI_PREC_F16 ? omni::STREAM_PLAN_DEFAULT_PIPELINES : 2; }
     static Config resolved(Config c) {
         if (c.camera_configuration < 0 || c.camera_configuration > 2)
             throw std::runtime_error("KeyframePipeline: camera_configuration must be 0 (STEREO_PINHOLE), 1 (STEREO_FISHEYE) or 2 (PINHOLE_DEPTH)");
@@ -944,16 +945,15 @@ public:
 private:
     struct Lane {                                      // one micro-batch in flight: its own streams, networks and result block
         Lane(const Config& c, int mb_)
-            : mb(mb_), sp_ctx(c.device), vlad_ctx(c.device),
+            : mb(mb_), one_stream(cfg_int("OMNI_PIPELINE_ONE_STREAM") != 0), sp_ctx(c.device), vlad_ctx(one_stream ? nullptr : std::make_unique<Context>(c.device)),
               sp(sp_ctx, c.sp_weights, c.pca_comp, c.pca_mean, c.width, c.height, c.thres, c.max_num, false, c.precision, (c.stereo() ? 2 : 1) * c.dirs() * mb_),
-              one_stream(cfg_int("OMNI_PIPELINE_ONE_STREAM") != 0),
-              vlad(one_stream ? sp_ctx : vlad_ctx, c.vlad_weights, c.width, c.height, false, c.dirs() * mb_),
-              cam(sp_ctx, sp, one_stream ? sp_ctx : vlad_ctx, vlad, c.dirs() * mb_, c.max_num, c.width, c.height, !c.stereo()) {
+              vlad(vlad_stream_ctx(), c.vlad_weights, c.width, c.height, false, c.dirs() * mb_),
+              cam(sp_ctx, sp, vlad_stream_ctx(), vlad, c.dirs() * mb_, c.max_num, c.width, c.height, !c.stereo()) {
             check(omni_vlad_dev_output(vlad.handle(), &rows_dev), "omni_vlad_dev_output");
             if (c.resized()) resize = std::make_unique<ResizeHIP>(sp_ctx, c.src_width, c.src_height, c.width, c.height);
             cur = mb_;
         }
-        void sync() { check(omni_ctx_sync(sp_ctx.get()), "sync"); check(omni_ctx_sync(vlad_ctx.get()), "sync"); }
+        void sync() { check(omni_ctx_sync(sp_ctx.get()), "sync"); if (vlad_ctx) check(omni_ctx_sync(vlad_ctx->get()), "sync"); }
         std::chrono::steady_clock::time_point t_enqueue;
         int mb;                                        // key frames the unit was created for
         int cur = 0;                                   // ... and of the unit in flight (a partly filled micro-batch of the streaming intake: omni_cam_set_active)
@@ -964,10 +964,11 @@ private:
         std::vector<uint16_t> depth_stage;             // streaming intake with device_depth_landmarks: the unit's depth frames [mb][height][width], copied at the push
         size_t stage_bytes = 0;
         ~Lane() { if (fit) (void)omni_sp_set_pcafit(sp.handle(), nullptr); if (stage) omni_host_free(stage); }
-        Context sp_ctx, vlad_ctx;
-        Swarm::SuperPointHIP sp;
         bool one_stream;                               // MobileNetVLAD behind SuperPoint on ONE stream (OMNI_PIPELINE_ONE_STREAM) instead of next to it on its own
-        Context& vlad_stream_ctx() { return one_stream ? sp_ctx : vlad_ctx; }
+        Context sp_ctx;
+        std::unique_ptr<Context> vlad_ctx;             // MobileNetVLAD's own stream: made only when it is used (an idle stream takes a hardware-queue slot too, csrc/stream_plan.h)
+        Swarm::SuperPointHIP sp;
+        Context& vlad_stream_ctx() { return one_stream ? sp_ctx : *vlad_ctx; }
         Swarm::MobileNetVLADHIP vlad;
         LoopCamHIP cam;
         std::unique_ptr<ResizeHIP> resize;             // STEREO_PINHOLE with camera-size frames: the tables of the resize that runs inside the unit
