@@ -849,6 +849,53 @@ int          omni_pca_moments_host(const float* raw_desc, const float* norm_part
  * the same f32 (a denormal value is written as 0: the handles' reader refuses denormals) */
 int          omni_pca_write_csv(const char* comp_path, const char* mean_path, const float* components_f32, const float* mean_f32, int pca_dim);
 
+/* ---- LoopNet wire: a key frame's images as the packets of LoopNet::broadcast_fisheye_desc (swarm_loop/src/loop_net.cpp:19-101), packed on the GPU -----------------
+ * The byte layout is csrc/wire_plan.h's, which restates host/loop_net_wire.hpp's wire::encode: per image one VIOKF_HEADER packet of OMNI_WIRE_HEADER_BYTES and one
+ * VIOKF_LANDMARKS packet of OMNI_WIRE_LANDMARK_BYTES per sent landmark (landmark i < n_kps is sent when flag[i] > 0 || send_all_features, in index order; the
+ * header's feature_num counts the flagged ones either way; an image without key points gets no packets).  msg_id of every packet and header_id of the landmark
+ * packets are left ZERO: the host numbers a frame's packets when it takes them.  Every other scalar field comes from one record per image: */
+#define OMNI_WIRE_HEADER_BYTES 16545         /* 161 + 4 * 4096 */
+#define OMNI_WIRE_LANDMARK_BYTES 324         /* 36 + 28 + 4 + 4 * 64 */
+#define OMNI_WIRE_HEADER_OFFSET 3            /* where an image's header packet starts in its buffer: its float area then starts on a 4-byte boundary */
+typedef struct omni_wire_image_meta {
+    double  timestamp;
+    int64_t frame_id;
+    int32_t drone_id, direction, prevent_adding_db, reserved;
+    double  pose_drone[7];                   /* xyz + quaternion wxyz, as sent */
+    double  camera_extrinsic[7];
+} omni_wire_image_meta;
+/* An image's buffer: omni_wire_packet_capacity(max_num) = 3 + 16545 + 324 * max_num bytes (0 for max_num outside 1..1024); the header packet at byte 3, landmark
+ * packet k at 16548 + 324 * k; bytes behind the last packet are not written.  An image's table: omni_wire_table_ints(max_num) = 2 + 2 * (1 + max_num) ints:
+ * [0] packets, [1] bytes used, then (offset, size) per packet, the header first; unused entries are written as zero. */
+int64_t omni_wire_packet_capacity(int max_num);
+int     omni_wire_table_ints(int max_num);
+/* Inputs (device), laid out as a key-frame unit's arrays: kps_xy [n_images][max_num][2] f32, n_kps [n_images] (clamped to 0..max_num), desc [n_images][max_num][64],
+ * norm2d [n_images][max_num][2], l3d [n_images][max_num][3], flag [n_images][max_num] u8, global [n_images][4096], meta [n_images].  Outputs (device): packets_out
+ * [n_images][capacity] (4-byte aligned), table_out [n_images][table_ints].  One workgroup per image, asynchronous on ctx's stream.  Refused before anything is
+ * launched: a null argument, n_images outside 1..65535, max_num outside 1..1024, desc_dim != 64, global_dim != 4096, a misaligned packets_out. */
+int     omni_wire_pack_enqueue_dev(omni_ctx* ctx, int n_images, int max_num, int desc_dim, int global_dim, int send_all_features, const float* kps_xy_dev,
+                                   const int* n_kps_dev, const float* desc_dev, const float* norm2d_dev, const float* l3d_dev, const uint8_t* flag_dev,
+                                   const float* global_dev, const omni_wire_image_meta* meta_dev, uint8_t* packets_out_dev, int* table_out_dev);
+/* csrc/wire_plan.h compiled by g++ into the library: the same arguments in host memory, the same bytes and tables, without a GPU (no alignment asked) */
+int     omni_wire_pack_host(int n_images, int max_num, int desc_dim, int global_dim, int send_all_features, const float* kps_xy, const int* n_kps, const float* desc,
+                            const float* norm2d, const float* l3d, const uint8_t* flag, const float* global, const omni_wire_image_meta* meta, uint8_t* packets_out,
+                            int* table_out);
+/* The same stage inside a key-frame unit.  omni_cam_set_wire(cam, 1, send_all_features): every following unit runs the kernel on its SuperPoint stream behind the
+ * landmark stage (stereo model or depth model) and behind MobileNetVLAD's rows, and copies the buffers and tables of its MAIN images -- [0, n_dirs) on a stereo
+ * handle, all images on a mono handle -- into a pinned block of the handle in front of the unit's event; on = 0 switches it off again, and a unit then launches
+ * exactly what it launched before.  omni_cam_set_wire_meta hands over the records of the NEXT unit's main images (copied before the call returns, as
+ * omni_cam_set_poses' poses); omni_cam_wire serves the unit after omni_cam_wait.  Refused: a handle without a landmark model (the stage packs landmarks the device
+ * made), descriptors other than 64 or global descriptors other than 4096 floats, a unit in flight; at enqueue, records that were not set or were set for another size. */
+int     omni_cam_set_wire(omni_cam* cam, int on, int send_all_features);
+int     omni_cam_set_wire_meta(omni_cam* cam, const omni_wire_image_meta* records, int n_images);
+typedef struct omni_cam_wire_result {           /* pointers into the handle's pinned host block; valid after omni_cam_wait until the handle's next enqueue */
+    int n_images, max_num, table_ints;
+    int64_t capacity;                           /* omni_wire_packet_capacity(max_num) */
+    const uint8_t* packets;                     /* [n_images][capacity] */
+    const int*     table;                       /* [n_images][table_ints] */
+} omni_cam_wire_result;
+int     omni_cam_wire(omni_cam* cam, omni_cam_wire_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,7 +53,10 @@ SYMBOLS = [
     "omni_cam_enqueue_jpeg_host", "omni_cam_jpegdec_status", "omni_cam_enqueue_fisheye_jpeg_host",
     "omni_pcafit_create", "omni_pcafit_destroy", "omni_pcafit_reset", "omni_pcafit_enqueue_rows_dev", "omni_sp_set_pcafit", "omni_pcafit_stats", "omni_pcafit_moments",
     "omni_pcafit_merge_host", "omni_pca_solve_host", "omni_pcafit_solve", "omni_pca_moments_host", "omni_pca_write_csv",
+    "omni_wire_packet_capacity", "omni_wire_table_ints", "omni_wire_pack_enqueue_dev", "omni_wire_pack_host", "omni_cam_set_wire", "omni_cam_set_wire_meta", "omni_cam_wire",
 ]
+WIRE_HEADER_BYTES, WIRE_LANDMARK_BYTES, WIRE_HEADER_OFFSET = 16545, 324, 3      # include/omni_hip.h OMNI_WIRE_*
+WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")                            # packet 0 of an image / every other packet
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
 JPEG_OK, JPEG_TRUNCATED, JPEG_HEADER_BYTES = 0, 1, 328      # include/omni_hip.h OMNI_JPEG_*
@@ -173,6 +176,48 @@ def depth_landmarks_host(model: DepthModel, poses7, kps_xy, n_kps, depth, have=N
     return dict(zip(("norm2d", "landmarks_3d", "landmarks_flag", "count_3d"), outs))
 
 
+class WireImageMeta(C.Structure):
+    """omni_wire_image_meta: what a key frame's image sends besides the unit's arrays (stamp, ids, direction, the two poses as xyz + quaternion wxyz)"""
+    _fields_ = [("timestamp", C.c_double), ("frame_id", C.c_int64), ("drone_id", C.c_int32), ("direction", C.c_int32), ("prevent_adding_db", C.c_int32),
+                ("reserved", C.c_int32), ("pose_drone", C.c_double * 7), ("camera_extrinsic", C.c_double * 7)]
+
+
+WIRE_META_DTYPE = np.dtype([("timestamp", "<f8"), ("frame_id", "<i8"), ("drone_id", "<i4"), ("direction", "<i4"), ("prevent_adding_db", "<i4"), ("reserved", "<i4"),
+                            ("pose_drone", "<f8", (7,)), ("camera_extrinsic", "<f8", (7,))])      # the same 144 bytes as a numpy record
+
+
+def wire_packet_capacity(max_num: int) -> int:
+    return int(lib().omni_wire_packet_capacity(max_num))
+
+
+def wire_table_ints(max_num: int) -> int:
+    return int(lib().omni_wire_table_ints(max_num))
+
+
+def _wire_inputs(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta):
+    kps_xy, n_kps = _f32(kps_xy), np.ascontiguousarray(n_kps, np.int32)
+    N, M = n_kps.shape[0], kps_xy.shape[1]
+    ins = [kps_xy, n_kps, _f32(desc), _f32(norm2d), _f32(l3d), np.ascontiguousarray(flag, np.uint8), _f32(global_desc), np.ascontiguousarray(meta, WIRE_META_DTYPE)]
+    assert kps_xy.shape == (N, M, 2) and ins[2].shape[:2] == (N, M) and ins[3].shape == (N, M, 2) and ins[4].shape == (N, M, 3) and ins[5].shape == (N, M)
+    assert ins[6].shape[0] == N and ins[7].shape == (N,)
+    return N, M, ins
+
+
+def wire_pack_host(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, send_all_features: bool = False, fill: int = 0):
+    """omni_wire_pack_host: csrc/wire_plan.h on the host, no GPU.  kps_xy [N][M][2], n_kps [N], desc [N][M][64], norm2d [N][M][2], l3d [N][M][3], flag [N][M] u8,
+    global_desc [N][4096], meta [N] records of WIRE_META_DTYPE -> (packets [N][capacity] u8 pre-filled with `fill`, table [N][table_ints] i32)"""
+    N, M, ins = _wire_inputs(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta)
+    out = np.full((N, wire_packet_capacity(M)), fill, np.uint8)
+    table = np.zeros((N, wire_table_ints(M)), np.int32)
+    _check(lib().omni_wire_pack_host(N, M, ins[2].shape[2], ins[6].shape[1], int(bool(send_all_features)), *[a.ctypes.data for a in ins], out.ctypes.data, table.ctypes.data))
+    return out, table
+
+
+def wire_packets(packets_row: np.ndarray, table_row: np.ndarray):
+    """one image's packets as (channel, bytes) in sending order, cut out of its buffer through its table"""
+    return [(WIRE_CHANNELS[min(k, 1)], packets_row[table_row[2 + 2 * k]:table_row[2 + 2 * k] + table_row[3 + 2 * k]].tobytes()) for k in range(int(table_row[0]))]
+
+
 class _CamLandmarks(C.Structure):
     _fields_ = [("n_images", C.c_int), ("n_dirs", C.c_int), ("max_num", C.c_int), ("norm2d", C.POINTER(C.c_float)), ("landmarks_3d", C.POINTER(C.c_float)),
                 ("landmarks_flag", C.POINTER(C.c_uint8)), ("count_3d", C.POINTER(C.c_int))]
@@ -180,6 +225,10 @@ class _CamLandmarks(C.Structure):
 
 class _CamJpeg(C.Structure):
     _fields_ = [("n_images", C.c_int), ("capacity", C.c_int64), ("bytes", C.POINTER(C.c_uint8)), ("sizes", C.POINTER(C.c_int)), ("status", C.POINTER(C.c_int))]
+
+
+class _CamWire(C.Structure):
+    _fields_ = [("n_images", C.c_int), ("max_num", C.c_int), ("table_ints", C.c_int), ("capacity", C.c_int64), ("packets", C.POINTER(C.c_uint8)), ("table", C.POINTER(C.c_int))]
 
 
 class _VladWeights(C.Structure):
@@ -319,6 +368,10 @@ def lib():
     sig("omni_cam_set_depth_dev", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int])
     sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
     sig("omni_cam_landmarks", C.c_int, [_vp, C.POINTER(_CamLandmarks)])
+    sig("omni_wire_packet_capacity", C.c_int64, [C.c_int])
+    sig("omni_wire_table_ints", C.c_int, [C.c_int])
+    sig("omni_wire_pack_enqueue_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+    sig("omni_wire_pack_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
     sig("omni_jpeg_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64])
     sig("omni_jpeg_destroy", None, [_vp])
     sig("omni_jpeg_enqueue_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp])
@@ -326,6 +379,9 @@ def lib():
     sig("omni_jpeg_encode_host", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _i64p, _ip])
     sig("omni_cam_set_jpeg", C.c_int, [_vp, C.c_int, C.c_int64])
     sig("omni_cam_jpeg", C.c_int, [_vp, C.POINTER(_CamJpeg)])
+    sig("omni_cam_set_wire", C.c_int, [_vp, C.c_int, C.c_int])
+    sig("omni_cam_set_wire_meta", C.c_int, [_vp, _vp, C.c_int])
+    sig("omni_cam_wire", C.c_int, [_vp, C.POINTER(_CamWire)])
     sig("omni_jpegdec_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int64])
     sig("omni_jpegdec_destroy", None, [_vp])
     sig("omni_jpegdec_enqueue_host", C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _vp, C.c_int, _vp])
@@ -1619,6 +1675,30 @@ def depth_landmarks(ctx: Context, model: DepthModel, poses7, kps_xy, n_kps, dept
     return dict(zip(("norm2d", "landmarks_3d", "landmarks_flag", "count_3d"), res))
 
 
+def wire_pack_dev(ctx: Context, n_images, max_num, kps_xy_dev, n_kps_dev, desc_dev, norm2d_dev, l3d_dev, flag_dev, global_dev, meta_dev, packets_out, table_out,
+                  send_all_features: bool = False, desc_dim: int = 64, global_dim: int = 4096):
+    """omni_wire_pack_enqueue_dev: a unit's HBM-resident arrays -> LoopNet packet buffers and tables (csrc/wire_pack.hip); asynchronous on ctx"""
+    _check(lib().omni_wire_pack_enqueue_dev(ctx.h, n_images, max_num, desc_dim, global_dim, int(bool(send_all_features)), kps_xy_dev, n_kps_dev, desc_dev, norm2d_dev,
+                                            l3d_dev, flag_dev, global_dev, meta_dev, packets_out, table_out))
+
+
+def wire_pack(ctx: Context, kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, send_all_features: bool = False, fill: int = 0):
+    """host convenience around wire_pack_dev (upload, run, download): the arguments and results of wire_pack_host"""
+    N, M, ins = _wire_inputs(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta)
+    outs = [np.full((N, wire_packet_capacity(M)), fill, np.uint8), np.full((N, wire_table_ints(M)), -1, np.int32)]
+    dev = []
+    try:
+        for a in ins + outs:
+            dev.append(ctx.to_device(a.view(np.uint8) if a.dtype == WIRE_META_DTYPE else a))
+        wire_pack_dev(ctx, N, M, *dev, send_all_features=send_all_features, desc_dim=ins[2].shape[2], global_dim=ins[6].shape[1])
+        ctx.sync()
+        res = [ctx.from_device(d, o.shape, o.dtype) for d, o in zip(dev[-2:], outs)]
+    finally:
+        for x in dev:
+            ctx.free(x)
+    return res[0], res[1]
+
+
 class Cam:
     """omni_cam: one key frame's CNN + matching work as a single asynchronous unit (LoopCam::on_flattened_images,
     loop_cam.cpp:178-229).  wait() returns numpy VIEWS of the handle's pinned host block (valid until the next enqueue)."""
@@ -1783,6 +1863,23 @@ class Cam:
         A = np.ctypeslib.as_array
         raw, sizes, status = A(r.bytes, (r.n_images, r.capacity)), A(r.sizes, (r.n_images,)), A(r.status, (r.n_images,))
         return [(int(status[i]), raw[i, :sizes[i]].tobytes()) for i in range(r.n_images)]
+
+    def set_wire(self, on: bool, send_all_features: bool = False):
+        """the LoopNet wire: every following unit also packs its main images as LoopNet packets (wire() after wait()); needs a landmark model on the handle"""
+        _check(lib().omni_cam_set_wire(self.h, int(bool(on)), int(bool(send_all_features))))
+
+    def set_wire_meta(self, records):
+        """the records (WIRE_META_DTYPE) of the NEXT unit's main images; copied before the call returns"""
+        m = np.ascontiguousarray(records, WIRE_META_DTYPE).reshape(-1)
+        _check(lib().omni_cam_set_wire_meta(self.h, m.ctypes.data, len(m)))
+
+    def wire(self):
+        """after wait(): numpy VIEWS (packets [n][capacity] u8, table [n][table_ints] i32) of the unit's main images (valid until the next enqueue); wire_packets cuts
+        an image's packets out"""
+        r = _CamWire()
+        _check(lib().omni_cam_wire(self.h, C.byref(r)))
+        A = np.ctypeslib.as_array
+        return A(r.packets, (r.n_images, r.capacity)), A(r.table, (r.n_images, r.table_ints))
 
     def ready(self) -> bool:
         r = C.c_int(0)

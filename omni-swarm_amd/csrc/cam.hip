@@ -13,6 +13,7 @@
 #include "common.h"
 #include "camera_plan.h"
 #include "cam_input.h"
+#include "wire_plan.h"
 #include <string.h>
 
 namespace ci = omni::ci;
@@ -86,6 +87,21 @@ struct CamJpegDec {
     void release() { if (h) omni_jpegdec_destroy(h); h = nullptr; mem.release_all(); if (h_status) (void)hipHostFree(h_status); }
 };
 
+// the LoopNet wire inside the unit (omni_cam_set_wire; wire_pack.hip): the unit's MAIN images [0, n) as packets, on the SuperPoint stream behind the landmark stage.
+// dev / host (pinned): the images' buffers [n_cap][cap], then (at table_at) their tables [n_cap][te], then (at meta_at) the NEXT unit's records [n_cap], which the
+// host side stages (omni_cam_set_wire_meta) and the enqueue uploads
+struct CamWire {
+    bool on = false, unit = false;            // the stage is on; the unit enqueued last ran it (omni_cam_wire)
+    int send_all = 0, n = 0, n_meta = 0;      // n: main images of the unit enqueued last; n_meta: records set since the last unit (0: none)
+    int64_t cap = 0;
+    int te = 0;
+    size_t table_at = 0, meta_at = 0;
+    omni::DevBuf dev;
+    omni::HostBuf host;
+    hipEvent_t e_g = nullptr;                 // MobileNetVLAD's rows, for the SuperPoint stream to wait on
+    void release() { dev.release(); host.release(); if (e_g) (void)hipEventDestroy(e_g); e_g = nullptr; }
+};
+
 struct omni_cam {
     omni_sp* sp = nullptr; omni_vlad* vlad = nullptr;
     omni_ctx *c1 = nullptr, *c2 = nullptr;    // the SuperPoint stream's context, the MobileNetVLAD stream's
@@ -93,7 +109,7 @@ struct omni_cam {
       // n: directions of the NEXT enqueue (omni_cam_set_active), n_cap: what the handle and its networks were created for
       // W x H: the size the SuperPoint handle (and MobileNetVLAD) was created for
     bool pending = false;
-    CamCore core; CamLandmarks lm; CamDepth depth; CamJpegEnc enc; CamJpegDec dec;      // the stages: omni_cam_destroy releases each
+    CamCore core; CamLandmarks lm; CamDepth depth; CamJpegEnc enc; CamJpegDec dec; CamWire wire;      // the stages: omni_cam_destroy releases each
     std::mutex mu;
 };
 
@@ -152,15 +168,14 @@ void omni_cam_destroy(omni_cam* c) {
     if (!c) return;
     (void)hipSetDevice(c->c1->device);
     (void)hipStreamSynchronize(c->c1->stream); (void)hipStreamSynchronize(c->c2->stream);
-    c->dec.release(); c->enc.release(); c->depth.release(); c->lm.release(); c->core.release();
+    c->wire.release(); c->dec.release(); c->enc.release(); c->depth.release(); c->lm.release(); c->core.release();
     delete c;
 }
 
 static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, int fisheye_mask);
 
-// with a stereo model set, a unit needs the poses of ITS key frames; with a depth model, the depth frames of its images too: checked by every enqueue entry before
-// anything is enqueued (c->mu held)
-static int cam_poses_depth_check(omni_cam* c) {
+// with a stereo model set, a unit needs the poses of ITS key frames; with a depth model, the depth frames of its images too
+static int cam_landmark_inputs_check(omni_cam* c) {
     const int n_poses = c->lm.n_poses, n_depth = c->depth.n;
     if (c->depth.on) {                                                        // a mono unit with a depth model: the poses AND the depth frames of its images, one key frame per image
         OMNI_REQUIRE(n_poses > 0, OMNI_ERR_INVALID, "a depth model is set but the unit's poses are not (omni_cam_set_poses before every enqueue)");
@@ -173,6 +188,18 @@ static int cam_poses_depth_check(omni_cam* c) {
     OMNI_REQUIRE(n_poses > 0, OMNI_ERR_INVALID, "a stereo model is set but the unit's poses are not (omni_cam_set_poses before every enqueue)");
     OMNI_REQUIRE(n_poses * c->lm.model.dirs_per_keyframe == c->n, OMNI_ERR_INVALID, "poses of %d key frames x %d directions for a unit of %d (omni_cam_set_poses, omni_cam_set_active)",
                  n_poses, c->lm.model.dirs_per_keyframe, c->n);
+    return OMNI_OK;
+}
+
+// what a unit needs besides its frames: the above, and with the wire stage on the records of its main images and a landmark stage to pack the landmarks of.
+// Checked by every enqueue entry before anything is enqueued (c->mu held)
+static int cam_poses_depth_check(omni_cam* c) {
+    int rc;
+    if ((rc = cam_landmark_inputs_check(c))) return rc;
+    if (!c->wire.on) return OMNI_OK;
+    OMNI_REQUIRE(c->lm.on || c->depth.on, OMNI_ERR_INVALID, "the wire stage is on but the handle has no landmark model (omni_cam_set_stereo_model / omni_cam_set_depth_model)");
+    OMNI_REQUIRE(c->wire.n_meta > 0, OMNI_ERR_INVALID, "the wire stage is on but the unit's records are not set (omni_cam_set_wire_meta before every enqueue)");
+    OMNI_REQUIRE(c->wire.n_meta == c->n, OMNI_ERR_INVALID, "records of %d images for a unit of %d main images (omni_cam_set_wire_meta, omni_cam_set_active)", c->wire.n_meta, c->n);
     return OMNI_OK;
 }
 
@@ -516,6 +543,23 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
         OMNI_HIP_TRY(hipMemcpyAsync(h + l.off_norm, l.d_lm, l.off_end - l.off_norm, hipMemcpyDeviceToHost, s1));
         l.unit = true; l.n = n; l.n_poses = 0;                                // (the poses are consumed: the next unit needs its own)
     }
+    c->wire.unit = false;
+    if (c->wire.on) {
+        // LoopNet::broadcast_fisheye_desc's packets of the unit's main images (loop_net.cpp:19-101; csrc/wire_plan.h) behind the landmark stage whose arrays they
+        // carry -- the first n images of every array, on a stereo handle the up cameras' -- and behind MobileNetVLAD's rows, which come from the other stream.  The
+        // records go up, the buffers and tables of the n images go down in front of the unit's event
+        CamWire& w = c->wire;
+        uint8_t *d_w = w.dev.as<uint8_t>(), *h_w = w.host.as<uint8_t>();
+        OMNI_HIP_TRY(hipEventRecord(w.e_g, s2));
+        OMNI_HIP_TRY(hipStreamWaitEvent(s1, w.e_g, 0));
+        OMNI_HIP_TRY(hipMemcpyAsync(d_w + w.meta_at, h_w + w.meta_at, (size_t)n * sizeof(omni_wire_image_meta), hipMemcpyHostToDevice, s1));
+        if ((rc = omni::wire_pack_launch(s1, n, M, w.send_all, k.kps_dev, k.n_dev, k.desc_dev, v.norm2d, v.l3d, v.flag, k.g_dev,
+                                         reinterpret_cast<const omni_wire_image_meta*>(d_w + w.meta_at), d_w, reinterpret_cast<int*>(d_w + w.table_at))))
+            return rc;
+        OMNI_HIP_TRY(hipMemcpyAsync(h_w, d_w, (size_t)n * w.cap, hipMemcpyDeviceToHost, s1));
+        OMNI_HIP_TRY(hipMemcpyAsync(h_w + w.table_at, d_w + w.table_at, (size_t)n * w.te * sizeof(int), hipMemcpyDeviceToHost, s1));
+        w.unit = true; w.n = n; w.n_meta = 0;                                 // (the records are consumed: the next unit needs its own)
+    }
     OMNI_HIP_TRY(hipEventRecord(k.e1, s1));
     OMNI_HIP_TRY(hipMemcpyAsync(h + k.off_g, k.g_dev, (size_t)n * c->out_dim * 4, hipMemcpyDeviceToHost, s2));
     c->enc.unit = false;
@@ -714,6 +758,54 @@ int omni_cam_jpeg(omni_cam* c, omni_cam_jpeg_result* out) {
     OMNI_REQUIRE(c->enc.unit, OMNI_ERR_INVALID, "omni_cam_jpeg: the last unit ran with the stage off (omni_cam_set_jpeg)");
     out->n_images = c->enc.n; out->capacity = c->enc.cap; out->bytes = c->enc.host.as<uint8_t>();
     out->sizes = reinterpret_cast<const int*>(out->bytes + c->enc.meta); out->status = out->sizes + c->n_cap;
+    return OMNI_OK;
+}
+
+// ---- the LoopNet wire inside the unit --------------------------------------------------------------------------------------------------------------------
+int omni_cam_set_wire(omni_cam* c, int on, int send_all_features) {
+    OMNI_REQUIRE(c, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_wire with a unit in flight (omni_cam_wait first)");
+    CamWire& w = c->wire;
+    if (!on) { w.on = false; w.n_meta = 0; return OMNI_OK; }
+    OMNI_REQUIRE(c->lm.on || c->depth.on, OMNI_ERR_INVALID,
+                 "omni_cam_set_wire: the handle has no landmark model (omni_cam_set_stereo_model / omni_cam_set_depth_model): the stage packs landmarks the device made");
+    OMNI_REQUIRE(c->D == WP_DESC_DIM && c->out_dim == WP_GLOBAL_DIM, OMNI_ERR_INVALID, "omni_cam_set_wire: descriptors of %d and global descriptors of %d floats, the wire carries %d and %d",
+                 c->D, c->out_dim, WP_DESC_DIM, WP_GLOBAL_DIM);
+    (void)hipSetDevice(c->c1->device);
+    if (!w.cap) {                                    // (set-up time: no unit is in flight)
+        int rc;
+        const int64_t cap = omni::wp::capacity(c->M);
+        const int te = omni::wp::table_ints(c->M);
+        const size_t table_at = ((size_t)c->n_cap * cap + 255) & ~(size_t)255, meta_at = (table_at + (size_t)c->n_cap * te * sizeof(int) + 255) & ~(size_t)255;
+        const size_t bytes = meta_at + (size_t)c->n_cap * sizeof(omni_wire_image_meta);
+        if ((rc = w.dev.ensure(bytes)) || (rc = w.host.ensure(bytes))) return rc;
+        if (!w.e_g) OMNI_HIP_TRY(hipEventCreateWithFlags(&w.e_g, hipEventDisableTiming));
+        memset(w.host.p, 0, bytes);
+        w.cap = cap; w.te = te; w.table_at = table_at; w.meta_at = meta_at;
+    }
+    w.on = true; w.send_all = send_all_features != 0; w.n_meta = 0;
+    return OMNI_OK;
+}
+
+int omni_cam_set_wire_meta(omni_cam* c, const omni_wire_image_meta* records, int n_images) {
+    OMNI_REQUIRE(c && records, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_wire_meta with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->wire.on, OMNI_ERR_INVALID, "omni_cam_set_wire_meta with the wire stage off (omni_cam_set_wire)");
+    OMNI_REQUIRE(n_images >= 1 && n_images <= c->n_cap, OMNI_ERR_INVALID, "omni_cam_set_wire_meta: %d images, the handle holds 1..%d main images", n_images, c->n_cap);
+    memcpy(c->wire.host.as<uint8_t>() + c->wire.meta_at, records, (size_t)n_images * sizeof(omni_wire_image_meta));
+    c->wire.n_meta = n_images;
+    return OMNI_OK;
+}
+
+int omni_cam_wire(omni_cam* c, omni_cam_wire_result* out) {
+    OMNI_REQUIRE(c && out, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_wire with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->wire.unit, OMNI_ERR_INVALID, "omni_cam_wire: the last unit ran with the stage off (omni_cam_set_wire)");
+    out->n_images = c->wire.n; out->max_num = c->M; out->table_ints = c->wire.te; out->capacity = c->wire.cap;
+    out->packets = c->wire.host.as<uint8_t>(); out->table = reinterpret_cast<const int*>(out->packets + c->wire.table_at);
     return OMNI_OK;
 }
 

@@ -208,6 +208,9 @@ int landmarks_check_camera(const omni_camera_model* cm);      // csrc/camera_pla
 int depth_landmarks_launch(hipStream_t stream, const omni_depth_model& m, const omni_camera_model& cm, const double* poses7_dev, int n_images, int max_num, const float* kps_xy,
                            const int* n_kps, const uint16_t* depth, int stride, const uint8_t* have, float* norm2d, float* l3d, uint8_t* flag, int* count);
 int depth_check_model(const omni_depth_model* m);
+// wire_pack.hip: LoopNet's packets of n_images images out of a unit's arrays (csrc/wire_plan.h); the caller has checked what omni_wire_pack_enqueue_dev refuses
+int wire_pack_launch(hipStream_t stream, int n_images, int max_num, int send_all_features, const float* kps_xy, const int* n_kps, const float* desc, const float* norm2d,
+                     const float* l3d, const uint8_t* flag, const float* global, const omni_wire_image_meta* meta, uint8_t* out, int* table);
 }  // namespace omni
 
 struct omni_jpeg;

@@ -15,9 +15,11 @@
 #include <thread>
 
 #include "../csrc/stream_plan.h"
+#include "../csrc/wire_plan.h"
 #include "camera_model.hpp"
 #include "fisheye_flatten.hpp"
 #include "loop_geometry.hpp"
+#include "loop_net_wire.hpp"
 #include "omni_swarm.hpp"
 
 namespace omni {
@@ -97,6 +99,14 @@ public:
         // pca_fit_moments / pca_fit / pca_fit_write read them, and components_.csv / mean_.csv come out of the library instead of a notebook.  Results of the
         // pipeline are the same with the switch on or off.  Off by default.  The sharded database refuses it.  (set_fit_pca: before the first key frame.)
         bool fit_pca = false;
+        // The LoopNet wire (host/loop_net_wire.hpp; swarm_loop/src/loop_net.cpp).  `wire`: the pipeline owns a LoopNetWire; every finished local key frame's
+        // packets -- LoopNet::broadcast_fisheye_desc of its message -- are kept in order until take_packets hands them out, and packets of other drones enter
+        // through recv_packet / scan_recv: every frame the wire completes goes through flush() + on_remote_frame.  `device_wire`: the packets are packed inside
+        // the key-frame unit on the GPU (csrc/wire_pack.hip) and finish() copies them and numbers them in the wire's own id sequence, instead of running
+        // broadcast_fisheye_desc on the calling thread; the same bytes either way.  It packs the landmarks the device made: it needs device_landmarks or
+        // device_depth_landmarks in effect and is refused otherwise, as on the sharded database, which builds no messages.  send_all_features: LoopNet's
+        // SEND_ALL_FEATURES.  All off by default.  (set_wire: before the first key frame.)
+        bool wire = false, device_wire = false, send_all_features = false;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -235,6 +245,7 @@ private:
         }
         apply_stereo_model();
         apply_jpeg();
+        if (c.wire) { const bool dw = c.device_wire; cfg_.wire = cfg_.device_wire = false; set_wire(true, dw, c.send_all_features); }
         if (c.device_pnp) ensure_pnp_context();
         if (c.geometry) {
             geo_.self_id = c.self_id; geo_.MIN_LOOP_NUM = c.min_loop_num; geo_.MIN_DIRECTION_LOOP = c.min_direction_loop;
@@ -493,6 +504,7 @@ public:
         std::lock_guard<std::mutex> lk(intake_mu_);
         if (cfg_.camera_configuration != 2) throw std::runtime_error("set_device_depth_landmarks: camera_configuration is not 2 (PINHOLE_DEPTH)");
         if (any_keyframe_seen_) throw std::runtime_error("set_device_depth_landmarks after the first key frame");
+        if (!on && cfg_.wire && cfg_.device_wire) throw std::runtime_error("set_device_depth_landmarks(false): device_wire packs the landmarks the device made (set_wire first)");
         cfg_.device_depth_landmarks = on;
         apply_stereo_model();
     }
@@ -559,6 +571,7 @@ public:
     void set_device_landmarks(bool on) {
         std::lock_guard<std::mutex> lk(intake_mu_);
         if (any_keyframe_seen_) throw std::runtime_error("set_device_landmarks after the first key frame");
+        if (!on && cfg_.wire && cfg_.device_wire && cfg_.stereo()) throw std::runtime_error("set_device_landmarks(false): device_wire packs the landmarks the device made (set_wire first)");
         cfg_.device_landmarks = on;
         apply_stereo_model();
     }
@@ -613,6 +626,7 @@ private:
             const omni_depth_model d = depth_model();
             l.cam.set_depth_model(device_depth_landmarks() ? &d : nullptr, &cfg_.camera_model);
         }
+        l.cam.set_wire(device_wire(), cfg_.send_all_features);      // (behind the models: the stage is refused on a handle without one)
     }
     void apply_stereo_model() {
         for (auto& l : lanes_) apply_stereo_model(*l);
@@ -627,6 +641,24 @@ private:
             std::copy(p.position, p.position + 3, pose_stage_.data() + 7 * k); std::copy(p.quat_wxyz, p.quat_wxyz + 4, pose_stage_.data() + 7 * k + 3);
         }
         lane->cam.set_poses(pose_stage_.data(), m);
+        if (device_wire()) {
+            // ... and what its main images send besides the unit's arrays: the fields finish() stamps on their messages (stamp_image_descriptor, finish_frame_descriptor)
+            const int nd = cfg_.dirs();
+            wire_meta_.assign((size_t)m * nd, omni_wire_image_meta{});
+            for (int k = 0; k < m; ++k) {
+                const bool streamed = !lane->meta.empty();
+                const int64_t kf_id = streamed ? lane->meta[(size_t)k].msg_id : first_id + k;
+                for (int d = 0; d < nd; ++d) {
+                    omni_wire_image_meta& w = wire_meta_[(size_t)k * nd + d];
+                    w.timestamp = streamed ? lane->meta[(size_t)k].stamp : (double)kf_id; w.frame_id = kf_id; w.drone_id = cfg_.self_id; w.direction = d;
+                    w.prevent_adding_db = 0;                       // (the frame's flag stays on the frame: no local image carries one)
+                    std::copy(pose_stage_.data() + 7 * k, pose_stage_.data() + 7 * k + 7, w.pose_drone);
+                    const PoseMsg e = to_msg(view_extrinsic(d, true));
+                    std::copy(e.position, e.position + 3, w.camera_extrinsic); std::copy(e.quat_wxyz, e.quat_wxyz + 4, w.camera_extrinsic + 3);
+                }
+            }
+            lane->cam.set_wire_meta(wire_meta_.data(), m * nd);
+        }
         if (!device_depth_landmarks()) return;
         // ... and its depth frames: the streaming intake's copies (push_keyframe), or run()'s key frames taken out of set_depth's range; nullptr: no depth image
         depth_frames_.resize((size_t)m);
@@ -650,6 +682,127 @@ public:
         cfg_.have_stereo_extrinsics = true;
         apply_stereo_model();                                  // (the units triangulate from the same extrinsics the messages carry)
     }
+
+    // ---- the LoopNet wire (Config::wire, Config::device_wire) -----------------------------------------------------------------------------------------------
+    bool wire() const { return net_ != nullptr; }
+    bool device_wire() const { return net_ && cfg_.device_wire && (device_landmarks() || device_depth_landmarks()); }
+    bool send_all_features() const { return cfg_.send_all_features; }
+    // before the first key frame (what the C entry point omni_pipeline_set_wire sets)
+    void set_wire(bool on, bool device, bool send_all_features) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_wire after the first key frame");
+        if (on && shard_) throw std::runtime_error("set_wire: the sharded database builds no messages");
+        if (device && !on) throw std::runtime_error("set_wire: device_wire without wire");
+        if (device && !(device_landmarks() || device_depth_landmarks()))
+            throw std::runtime_error("set_wire: device_wire packs the landmarks the key-frame unit made: it needs device_landmarks (the stereo configurations) or "
+                                     "device_depth_landmarks (PINHOLE_DEPTH) in effect, with the geometry stage on");
+        cfg_.wire = on; cfg_.device_wire = on && device; cfg_.send_all_features = send_all_features;
+        if (!on) { net_.reset(); outbox_.clear(); inbox_.clear(); }
+        else if (!net_) {
+            net_ = std::make_unique<LoopNetWire>(cfg_.self_id);
+            net_->publish = [this](const char* ch, const std::vector<uint8_t>& b) {
+                if (!publishing_) return;
+                publishing_->off.push_back((int64_t)publishing_->bytes.size()); publishing_->size.push_back((int)b.size());
+                publishing_->channel.push_back(std::strcmp(ch, wire::CH_HEADER) == 0 ? 0 : 1);
+                publishing_->bytes.insert(publishing_->bytes.end(), b.begin(), b.end());
+            };
+            net_->frame_desc_callback = [this](const FisheyeFrameDescriptor& f) { inbox_.push_back(f); };
+            net_->MIN_DIRECTION_LOOP = cfg_.min_direction_loop;
+        }
+        if (net_) net_->SEND_ALL_FEATURES = send_all_features;
+        apply_stereo_model();
+    }
+    // the receiving side's settings (loop_net.h:33, swarm_loop.cpp:232; group_by_frame_id false: the reference's frame key)
+    void set_wire_recv(double recv_period, int min_direction_loop, bool group_by_frame_id) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (!net_) throw std::runtime_error("set_wire_recv: the wire is off (set_wire)");
+        if (!(recv_period >= 0) || min_direction_loop < 1) throw std::invalid_argument("set_wire_recv: recv_period < 0 or MIN_DIRECTION_LOOP < 1");
+        net_->recv_period = recv_period; net_->MIN_DIRECTION_LOOP = min_direction_loop; net_->group_by_frame_id = group_by_frame_id;
+    }
+    // one finished local key frame's packets, in sending order: channel 0 = VIOKF_HEADER, 1 = VIOKF_LANDMARKS
+    struct SentFrame { int64_t msg_id = 0; std::vector<uint8_t> bytes; std::vector<int64_t> off; std::vector<int> size; std::vector<uint8_t> channel; };
+    size_t wire_pending() const { return outbox_.size(); }
+    const SentFrame* oldest_packets() const { return outbox_.empty() ? nullptr : &outbox_.front(); }
+    SentFrame take_packets() {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (outbox_.empty()) throw std::runtime_error("take_packets: no key frame's packets are pending");
+        SentFrame s = std::move(outbox_.front());
+        outbox_.pop_front();
+        return s;
+    }
+    // A packet of the transport (LoopNet's two lcm.subscribe handlers, loop_net.cpp:9-13) / the periodic scan (:231-298), between two calls of run / push_keyframe /
+    // poll / flush.  Every frame the wire completes goes through the serial flow: flush(), then on_remote_frame -- its candidate lands in candidates(), an accepted
+    // loop in edges().  This pipeline's own packets are ignored (sent_message).  false: the packet did not parse or has another shape.
+    bool recv_packet(const char* channel, const uint8_t* data, size_t n, double now) {
+        if (!net_) throw std::runtime_error("recv_packet: the wire is off (set_wire)");
+        if (!channel || (!data && n)) throw std::invalid_argument("recv_packet: null argument");
+        const bool ok = net_->on_packet(channel, data, n, now);
+        drain_inbox();
+        return ok;
+    }
+    void scan_recv(double now) {
+        if (!net_) throw std::runtime_error("scan_recv: the wire is off (set_wire)");
+        net_->scan_recv_packets(now);
+        drain_inbox();
+    }
+    int64_t remote_frames() const { return remote_frames_; }
+    // the calling thread's milliseconds inside finish() spent on the wire so far: broadcast_fisheye_desc, or the copy and the id patch of device_wire
+    double wire_host_ms(bool reset) { const double v = wire_ms_; if (reset) wire_ms_ = 0; return v; }
+private:
+    void drain_inbox() {
+        while (!inbox_.empty()) {
+            const FisheyeFrameDescriptor f = std::move(inbox_.front());
+            inbox_.pop_front();
+            ++remote_frames_;
+            flush();
+            on_remote_frame(f);
+        }
+    }
+    // finish(): the unit's key frames leave as packets -- broadcast_fisheye_desc on the calling thread, or the unit's own packed bytes with the ids patched in
+    void wire_out(Lane& lane) {
+        const bool dev = device_wire();
+        const omni_cam_wire_result wr = dev ? lane.cam.wire() : omni_cam_wire_result{};
+        const int nd = cfg_.dirs();
+        for (int m = 0; m < lane.cur; ++m) {
+            FisheyeFrameDescriptor& f = frames_[(size_t)m];
+            outbox_.emplace_back();
+            SentFrame& s = outbox_.back();
+            s.msg_id = f.msg_id;
+            if (!dev) {
+                publishing_ = &s;
+                try { net_->broadcast_fisheye_desc(f); } catch (...) { publishing_ = nullptr; throw; }
+                publishing_ = nullptr;
+                continue;
+            }
+            size_t total = 0;
+            for (int d = 0; d < nd; ++d) {
+                const int* tb = wr.table + ((size_t)nd * m + d) * wr.table_ints;
+                if (tb[0] < 0 || tb[0] > 1 + wr.max_num || tb[1] < 0 || tb[1] > wr.capacity || (tb[0] > 0 && tb[1] < WP_LANDMARKS_AT)) throw std::runtime_error("wire_out: a packet table out of range");
+                if (tb[0]) total += (size_t)tb[1] - WP_HEADER_OFFSET;
+            }
+            s.bytes.reserve(total);
+            for (int d = 0; d < nd; ++d) {
+                const size_t i = (size_t)nd * m + d;
+                const int* tb = wr.table + i * wr.table_ints;
+                const uint8_t* buf = wr.packets + i * (size_t)wr.capacity;
+                if (!tb[0]) continue;
+                // an image's packets lie back to back behind the buffer's padding: one copy, then the ids
+                const size_t base = s.bytes.size();
+                s.bytes.insert(s.bytes.end(), buf + WP_HEADER_OFFSET, buf + tb[1]);
+                int64_t header_id = 0;
+                for (int k = 0; k < tb[0]; ++k) {
+                    const int off = tb[WP_TABLE_HEAD + 2 * k], size = tb[WP_TABLE_HEAD + 2 * k + 1];
+                    if (off != (k ? wp::landmark_offset(k - 1) : WP_HEADER_OFFSET) || size != (k ? WP_LANDMARK_BYTES : WP_HEADER_BYTES) || (int64_t)off + size > tb[1])
+                        throw std::runtime_error("wire_out: a packet out of place");
+                    uint8_t* at = s.bytes.data() + base + (size_t)(off - WP_HEADER_OFFSET);
+                    if (k == 0) { header_id = net_->reserve_id(true); wp::patch_header_id(at, header_id); f.images[(size_t)d].msg_id = header_id; }
+                    else wp::patch_landmark_ids(at, net_->reserve_id(false), header_id);
+                    s.off.push_back((int64_t)(base + (size_t)(off - WP_HEADER_OFFSET))); s.size.push_back(size); s.channel.push_back(k ? 1 : 0);
+                }
+            }
+        }
+    }
+public:
 
     // A key frame that arrived from ANOTHER drone (LoopNet's reassembled message; LoopDetector::on_image_recv, loop_detector.cpp:11-137), handed to the detector on
     // the calling thread between two calls of run / push_keyframe / poll / flush, after a flush().  Everything deferred earlier is verified first; the frame's own
@@ -682,6 +835,7 @@ public:
     // LoopDetectorCore describe one drone's own database and are not used in this mode.
     void attach_shard(int rank, int world, const char* unique_id) {
         if (cfg_.fit_pca) throw std::runtime_error("attach_shard: fit_pca does not run on the sharded database, which builds no descriptors of its own");
+        if (cfg_.wire) throw std::runtime_error("attach_shard: the wire does not run on the sharded database, which builds no messages");
         if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
@@ -1100,7 +1254,7 @@ private:
         // the messages are first built LIGHT (landmark_num, stamps), the detector step is enqueued, and the heavy part -- 75 KB of key points, descriptors and
         // lifted points per image -- is copied into the frames the detector now holds while its searches run on the GPU.  With the geometry stage the landmarks
         // can change landmark_num (generate_gray_depth_image_descriptor drops an image below ACCEPT_MIN_3D_PTS): everything is built first, as before.
-        const bool defer_heavy = !cfg_.geometry;
+        const bool defer_heavy = !cfg_.geometry && !net_;                      // (the wire sends whole messages: they are built first)
         // the unit's own landmarks (Config::device_landmarks): lifted floats, 3-D points and flags of every image, already in the pinned block
         const bool dev_dp = device_depth_landmarks();
         const bool dev_lm = device_landmarks() || dev_dp;
@@ -1173,6 +1327,11 @@ private:
             if (first) std::rethrow_exception(first);
         }
         host_ms_[2] += since(t_a);
+        if (net_) {
+            t_a = std::chrono::steady_clock::now();
+            wire_out(lane);
+            wire_ms_ += since(t_a);
+        }
         t_a = std::chrono::steady_clock::now();
         int hits = collect_detector();                                          // the unit before this one
         t_a = std::chrono::steady_clock::now();
@@ -1276,6 +1435,14 @@ private:
     std::vector<double> pose_stage_;            // unit_poses: the unit's poses on their way into the handle's pinned staging
     std::vector<const uint16_t*> depth_frames_; // ... and its depth frames' addresses
     std::vector<FisheyeFrameDescriptor> frames_;
+    // the LoopNet wire: the object, the finished key frames' packets not yet taken, the frames it completed and that are not yet through the detector
+    std::unique_ptr<LoopNetWire> net_;
+    std::deque<SentFrame> outbox_;
+    std::deque<FisheyeFrameDescriptor> inbox_;
+    SentFrame* publishing_ = nullptr;           // where broadcast_fisheye_desc's packets go while finish() runs it
+    std::vector<omni_wire_image_meta> wire_meta_;
+    int64_t remote_frames_ = 0;
+    double wire_ms_ = 0;                        // the calling thread's milliseconds in wire_out so far (wire_host_ms)
     std::unique_ptr<IndexFlatIP> shard_index_;
     omni_shard* shard_ = nullptr;
     int world_ = 1;

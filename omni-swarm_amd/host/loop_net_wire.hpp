@@ -224,6 +224,9 @@ public:
         }
     }
 
+    // ids for packets that were encoded elsewhere (the key-frame unit's pack stage, csrc/wire_plan.h, leaves them zero): the next id of this object's sequence,
+    // a header's entered into sent_message as broadcast_img_desc does
+    int64_t reserve_id(bool header) { const int64_t id = next_id(); if (header) sent_message.insert(id); return id; }
     bool msg_blocked(int64_t id) const { return blacklist.count(id) || sent_message.count(id); }     // loop_net.h:85-87
     int pending_images() const { return (int)received_images.size(); }
 

@@ -479,6 +479,15 @@ public:
         check(omni_cam_jpeg(h_, &r), "omni_cam_jpeg");
         return r;
     }
+    // the LoopNet wire inside the unit (csrc/wire_pack.hip; LoopNet::broadcast_fisheye_desc, loop_net.cpp:19-101): set_wire once (needs a landmark model),
+    // set_wire_meta before every enqueue, wire() after wait() -- the unit's MAIN images as packet buffers and tables (csrc/wire_plan.h), the ids left zero for the host
+    void set_wire(bool on, bool send_all_features) { check(omni_cam_set_wire(h_, on ? 1 : 0, send_all_features ? 1 : 0), "omni_cam_set_wire"); }
+    void set_wire_meta(const omni_wire_image_meta* records, int n_images) { check(omni_cam_set_wire_meta(h_, records, n_images), "omni_cam_set_wire_meta"); }
+    omni_cam_wire_result wire() {
+        omni_cam_wire_result r{};
+        check(omni_cam_wire(h_, &r), "omni_cam_wire");
+        return r;
+    }
     // non-blocking: would wait() return at once?
     bool ready() { int r = 0; check(omni_cam_ready(h_, &r), "omni_cam_ready"); return r != 0; }
     // blocks until the key frame is done; pointers stay valid until the next enqueue on this object

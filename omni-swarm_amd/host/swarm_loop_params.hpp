@@ -243,6 +243,7 @@ struct SwarmLoopParams {
         c.send_img = send_img; c.jpg_quality = jpg_quality;                 // swarm_loop.cpp:224-225 -> LoopCam (encode_image, loop_cam.cpp:56-71)
         c.compressed_images = is_compressed_images;                         // the VINS settings file (read_vins_settings): CompressedImage topics
         c.fit_pca = output_raw_superpoint_desc;                             // loop_cam.cpp:51-53, 577-582: the descriptor dump behind pca.ipynb -> the fit's moments in HBM
+        c.send_all_features = send_all_features;                            // swarm_loop.cpp:235 -> LoopNet (loop_net.cpp:66): taken up when the pipeline's wire is switched on
         if (have_camera_config) {
             // the camodocal file (read_camera_config): lens and intrinsics, the latter scaled to the networks' image size when the file was calibrated at another
             // one.  DEVIATION: the reference does not scale (CameraModel::scaled has the reason)

@@ -39,6 +39,11 @@ _pnp_lib = None
 JPEG_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpeg.so")
 JPEG_SYMBOLS = ["omni_jpeg_host_last_error", "omni_pipeline_set_send_img", "omni_pipeline_get_send_img", "omni_pipeline_jpeg_truncated", "omni_pipeline_frame_image"]
 _jpeg_lib = None
+WIRE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_wire.so")
+WIRE_SYMBOLS = ["omni_wire_host_last_error", "omni_pipeline_set_wire", "omni_pipeline_get_wire", "omni_pipeline_wire_pending", "omni_pipeline_take_packets",
+                "omni_pipeline_set_wire_recv", "omni_pipeline_recv_packet", "omni_pipeline_scan_recv", "omni_pipeline_remote_frames", "omni_pipeline_wire_host_ms"]
+WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")      # include/omni_host_wire.h OMNI_WIRE_CHANNEL_*
+_wire_lib = None
 JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
 JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
                    "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
@@ -335,12 +340,36 @@ def jpeg_lib():
     return _jpeg_lib
 
 
+def wire_lib():
+    global _wire_lib
+    if _wire_lib is None:
+        lib()
+        if not os.path.exists(WIRE_LIB_PATH):
+            raise OSError(f"{WIRE_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(WIRE_LIB_PATH)
+        L.omni_wire_host_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_wire.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.omni_pipeline_get_wire.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.omni_pipeline_wire_pending.argtypes = [C.c_void_p]
+        L.omni_pipeline_wire_pending.restype = C.c_int64
+        L.omni_pipeline_take_packets.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.POINTER(C.c_int)]
+        L.omni_pipeline_set_wire_recv.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
+        L.omni_pipeline_recv_packet.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_double, C.POINTER(C.c_int)]
+        L.omni_pipeline_scan_recv.argtypes = [C.c_void_p, C.c_double]
+        L.omni_pipeline_remote_frames.argtypes = [C.c_void_p]
+        L.omni_pipeline_remote_frames.restype = C.c_int64
+        L.omni_pipeline_wire_host_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+        _wire_lib = L
+    return _wire_lib
+
+
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
-                 device_depth_landmarks=None, fit_pca=False):
+                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -366,6 +395,8 @@ class KeyframePipeline:
         library's default, which is off.  Refused for the stereo configurations.
         fit_pca: the reference's OUTPUT_RAW_SUPERPOINT_DESC as a calibration mode: the 256-d descriptors of every key point of the stream enter the moments of
         a PCA fit on the GPU (csrc/pca_fit.hip); pca_fit / pca_fit_write make components_.csv / mean_.csv of them.  Results do not depend on it.  Default off.
+        wire / device_wire / send_all_features: the LoopNet wire (set_wire): every finished key frame leaves as LoopNet's packets (take_packets) and packets of
+        other drones enter through recv_packet / scan_recv; device_wire packs the packets inside the key-frame unit on the GPU (the same bytes).  Default off.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -412,6 +443,8 @@ class KeyframePipeline:
             self.set_compressed_images(True)
         if fit_pca:
             self.set_fit_pca(True)
+        if wire or device_wire:
+            self.set_wire(wire, device_wire, send_all_features)
 
     def _pca(self, rc, what):
         if rc:
@@ -556,6 +589,58 @@ class KeyframePipeline:
         hits = C.c_int(0)
         self._jpegdec(jpegdec_lib().omni_pipeline_run_jpeg(self.h, len(keyframes), first_msg_id, fp, fs, C.byref(hits)), "omni_pipeline_run_jpeg")
         return hits.value
+
+    def _wire(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {wire_lib().omni_wire_host_last_error().decode()}")
+
+    def set_wire(self, wire: bool, device_wire: bool = False, send_all_features: bool = False):
+        """the LoopNet wire (host/loop_net_wire.hpp): on, every finished key frame's packets are kept until take_packets; device_wire: packed on the GPU inside the
+        key-frame unit (csrc/wire_pack.hip) instead of on the calling thread, the same bytes.  Before the first key frame; device_wire needs the landmarks made on
+        the device (device_landmarks / device_depth_landmarks with geometry)"""
+        self._wire(wire_lib().omni_pipeline_set_wire(self.h, int(bool(wire)), int(bool(device_wire)), int(bool(send_all_features))), "omni_pipeline_set_wire")
+
+    def wire(self):
+        """(wire, device_wire as in effect, send_all_features)"""
+        v = [C.c_int(0) for _ in range(3)]
+        self._wire(wire_lib().omni_pipeline_get_wire(self.h, *[C.byref(x) for x in v]), "omni_pipeline_get_wire")
+        return tuple(bool(x.value) for x in v)
+
+    @property
+    def wire_pending(self) -> int:
+        return int(wire_lib().omni_pipeline_wire_pending(self.h))
+
+    def take_packets(self):
+        """pops the oldest finished key frame's packets: (msg_id, [(channel name, bytes), ...]) in sending order"""
+        L = wire_lib()
+        nb, npk, mid = C.c_int64(0), C.c_int(0), C.c_int64(0)
+        self._wire(L.omni_pipeline_take_packets(self.h, None, None, 0, C.byref(nb), None, None, None, 0, C.byref(npk)), "omni_pipeline_take_packets")
+        buf = np.empty(max(nb.value, 1), np.uint8)
+        off, size, ch = np.empty(max(npk.value, 1), np.int64), np.empty(max(npk.value, 1), np.int32), np.empty(max(npk.value, 1), np.int32)
+        self._wire(L.omni_pipeline_take_packets(self.h, C.byref(mid), buf.ctypes.data, buf.size, C.byref(nb), off.ctypes.data, size.ctypes.data, ch.ctypes.data, len(off),
+                                                C.byref(npk)), "omni_pipeline_take_packets")
+        return int(mid.value), [(WIRE_CHANNELS[ch[k]], buf[off[k]:off[k] + size[k]].tobytes()) for k in range(npk.value)]
+
+    def set_wire_recv(self, recv_period: float = 0.5, min_direction_loop: int = 3, group_by_frame_id: bool = False):
+        self._wire(wire_lib().omni_pipeline_set_wire_recv(self.h, recv_period, min_direction_loop, int(bool(group_by_frame_id))), "omni_pipeline_set_wire_recv")
+
+    def recv_packet(self, channel: str, data: bytes, now: float) -> bool:
+        """one packet of another drone; frames it completes go through the detector (candidates(), edges()) before the call returns.  False: it did not parse"""
+        ok = C.c_int(0)
+        self._wire(wire_lib().omni_pipeline_recv_packet(self.h, channel.encode(), data, len(data), now, C.byref(ok)), "omni_pipeline_recv_packet")
+        return bool(ok.value)
+
+    def scan_recv(self, now: float):
+        self._wire(wire_lib().omni_pipeline_scan_recv(self.h, now), "omni_pipeline_scan_recv")
+
+    @property
+    def remote_frames(self) -> int:
+        return int(wire_lib().omni_pipeline_remote_frames(self.h))
+
+    def wire_host_ms(self, reset: bool = False) -> float:
+        ms = C.c_double(0)
+        self._wire(wire_lib().omni_pipeline_wire_host_ms(self.h, C.byref(ms), int(reset)), "omni_pipeline_wire_host_ms")
+        return ms.value
 
     def _jpeg(self, rc, what):
         if rc:
