@@ -896,6 +896,28 @@ typedef struct omni_cam_wire_result {           /* pointers into the handle's pi
 } omni_cam_wire_result;
 int     omni_cam_wire(omni_cam* cam, omni_cam_wire_result* out);
 
+/* ---- rows of a mixed detector batch: one contiguous [n_rows][dim] fp32 block in frame order out of rows that lie in three places ------------------------------
+ * The plan is csrc/rows_plan.h's: output row r is row table[r].index of the block table[r].source names -- a key-frame unit's rows already in HBM (e.g.
+ * MobileNetVLAD's output buffer), rows staged on the host and uploaded next to the table (the global descriptors of frames other drones sent), or zeros.  A bitwise
+ * copy: NaN payloads survive.  Source rows may repeat. */
+#define OMNI_ROW_UNIT 0
+#define OMNI_ROW_STAGED 1
+#define OMNI_ROW_ZERO 2
+typedef struct omni_row_source { int32_t source; int32_t index; } omni_row_source;
+/* One launch per batch, one workgroup of 256 lanes per output row, asynchronous on ctx's stream; table_dev [n_rows], unit_rows_dev [n_unit_rows][dim], staged_rows_dev
+ * [n_staged_rows][dim] and out_dev [n_rows][dim] are device memory (a block of no rows may be NULL; out_dev overlaps neither input).  dim % 4 == 0 with all three
+ * bases 16-byte aligned moves 16 bytes per lane and step, everything else dwords.  Refused before anything is launched: a null ctx, table or output, a missing
+ * block with rows, n_rows < 1, dim < 1, a negative row count, a base that is not 4-byte aligned.  The table is in device memory: whoever made it has checked its
+ * entries (omni_rows_assemble_host refuses the same table; csrc/rows_plan.h refusal); an entry out of range reads nothing and its row comes out zero. */
+int     omni_rows_assemble_enqueue_dev(omni_ctx* ctx, int64_t n_rows, int dim, const omni_row_source* table_dev, const float* unit_rows_dev, int64_t n_unit_rows,
+                                       const float* staged_rows_dev, int64_t n_staged_rows, float* out_dev);
+/* csrc/rows_plan.h compiled by g++ into the library: the same arguments in host memory, the same bits, without a GPU and without a context.  Refuses besides: an
+ * unknown source, an index outside its block. */
+int     omni_rows_assemble_host(int64_t n_rows, int dim, const omni_row_source* table, const float* unit_rows, int64_t n_unit_rows, const float* staged_rows,
+                                int64_t n_staged_rows, float* out);
+/* PINNED host memory -> device on the context's stream, without waiting (omni_memcpy_d2h_async's twin): src_pinned stays untouched until the copy has run */
+int     omni_memcpy_h2d_async(omni_ctx* ctx, void* dst_dev, const void* src_pinned, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

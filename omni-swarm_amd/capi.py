@@ -54,7 +54,9 @@ SYMBOLS = [
     "omni_pcafit_create", "omni_pcafit_destroy", "omni_pcafit_reset", "omni_pcafit_enqueue_rows_dev", "omni_sp_set_pcafit", "omni_pcafit_stats", "omni_pcafit_moments",
     "omni_pcafit_merge_host", "omni_pca_solve_host", "omni_pcafit_solve", "omni_pca_moments_host", "omni_pca_write_csv",
     "omni_wire_packet_capacity", "omni_wire_table_ints", "omni_wire_pack_enqueue_dev", "omni_wire_pack_host", "omni_cam_set_wire", "omni_cam_set_wire_meta", "omni_cam_wire",
+    "omni_rows_assemble_enqueue_dev", "omni_rows_assemble_host", "omni_memcpy_h2d_async",
 ]
+ROW_UNIT, ROW_STAGED, ROW_ZERO = 0, 1, 2      # include/omni_hip.h OMNI_ROW_*: where a row of a mixed detector batch comes from
 WIRE_HEADER_BYTES, WIRE_LANDMARK_BYTES, WIRE_HEADER_OFFSET = 16545, 324, 3      # include/omni_hip.h OMNI_WIRE_*
 WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")                            # packet 0 of an image / every other packet
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
@@ -213,6 +215,23 @@ def wire_pack_host(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, se
     return out, table
 
 
+def _rows_inputs(table, unit_rows, staged_rows, dim):
+    table = np.ascontiguousarray(table, np.int32).reshape(-1, 2)      # omni_row_source: (source, index) per output row
+    unit_rows, staged_rows = _f32(unit_rows).reshape(-1, dim if dim > 0 else 1), _f32(staged_rows).reshape(-1, dim if dim > 0 else 1)
+    return table, unit_rows, staged_rows
+
+
+def rows_assemble_host(table, unit_rows, staged_rows, dim: int, n_rows: int = None) -> np.ndarray:
+    """omni_rows_assemble_host: csrc/rows_plan.h on the host, no GPU.  table [n_rows][2] i32 = (ROW_*, index), unit_rows [U][dim], staged_rows [S][dim]
+    -> [n_rows][dim] f32, bit for bit"""
+    table, unit_rows, staged_rows = _rows_inputs(table, unit_rows, staged_rows, dim)
+    n_rows = len(table) if n_rows is None else n_rows
+    out = np.empty((max(n_rows, 0), max(dim, 0)), np.float32)
+    _check(lib().omni_rows_assemble_host(n_rows, dim, table.ctypes.data, unit_rows.ctypes.data if len(unit_rows) else None, len(unit_rows),
+                                         staged_rows.ctypes.data if len(staged_rows) else None, len(staged_rows), out.ctypes.data))
+    return out
+
+
 def wire_packets(packets_row: np.ndarray, table_row: np.ndarray):
     """one image's packets as (channel, bytes) in sending order, cut out of its buffer through its table"""
     return [(WIRE_CHANNELS[min(k, 1)], packets_row[table_row[2 + 2 * k]:table_row[2 + 2 * k] + table_row[3 + 2 * k]].tobytes()) for k in range(int(table_row[0]))]
@@ -368,6 +387,9 @@ def lib():
     sig("omni_cam_set_depth_dev", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int])
     sig("omni_cam_set_poses", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int])
     sig("omni_cam_landmarks", C.c_int, [_vp, C.POINTER(_CamLandmarks)])
+    sig("omni_rows_assemble_enqueue_dev", C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp])
+    sig("omni_rows_assemble_host", C.c_int, [C.c_int64, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp])
+    sig("omni_memcpy_h2d_async", C.c_int, [_vp, _vp, _vp, C.c_size_t])
     sig("omni_wire_packet_capacity", C.c_int64, [C.c_int])
     sig("omni_wire_table_ints", C.c_int, [C.c_int])
     sig("omni_wire_pack_enqueue_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -1680,6 +1702,37 @@ def wire_pack_dev(ctx: Context, n_images, max_num, kps_xy_dev, n_kps_dev, desc_d
     """omni_wire_pack_enqueue_dev: a unit's HBM-resident arrays -> LoopNet packet buffers and tables (csrc/wire_pack.hip); asynchronous on ctx"""
     _check(lib().omni_wire_pack_enqueue_dev(ctx.h, n_images, max_num, desc_dim, global_dim, int(bool(send_all_features)), kps_xy_dev, n_kps_dev, desc_dev, norm2d_dev,
                                             l3d_dev, flag_dev, global_dev, meta_dev, packets_out, table_out))
+
+
+def rows_assemble_dev(ctx: Context, n_rows: int, dim: int, table_dev, unit_rows_dev, n_unit_rows: int, staged_rows_dev, n_staged_rows: int, out_dev):
+    """omni_rows_assemble_enqueue_dev: the rows of a mixed detector batch gathered into one block (csrc/rows_assemble.hip); asynchronous on ctx"""
+    _check(lib().omni_rows_assemble_enqueue_dev(ctx.h, n_rows, dim, table_dev, unit_rows_dev, n_unit_rows, staged_rows_dev, n_staged_rows, out_dev))
+
+
+def rows_assemble(ctx: Context, table, unit_rows, staged_rows, dim: int, unit_offset_floats: int = 0) -> np.ndarray:
+    """host convenience around rows_assemble_dev (upload, run, download): the arguments and result of rows_assemble_host.  The table and the staged rows go up
+    through omni_memcpy_h2d_async out of one pinned block, as the detector sends them.  unit_offset_floats: the unit block starts that many floats into its
+    allocation (an address off the 16-byte grid takes the dword path)."""
+    table, unit_rows, staged_rows = _rows_inputs(table, unit_rows, staged_rows, dim)
+    n_rows, tb = len(table), (table.nbytes + 255) // 256 * 256
+    pinned = ctx.host_alloc((tb + max(staged_rows.nbytes, 1),), np.uint8)
+    dev = []
+    try:
+        pinned[:table.nbytes] = table.view(np.uint8).reshape(-1)
+        pinned[tb:tb + staged_rows.nbytes] = staged_rows.view(np.uint8).reshape(-1)
+        dev.append(ctx.alloc(pinned.nbytes))
+        _check(lib().omni_memcpy_h2d_async(ctx.h, dev[0], pinned.ctypes.data, pinned.nbytes))
+        dev.append(ctx.to_device(np.concatenate([np.zeros(unit_offset_floats, np.float32), unit_rows.reshape(-1)])))
+        dev.append(ctx.to_device(np.full((n_rows, dim), np.float32(-7.0))))
+        rows_assemble_dev(ctx, n_rows, dim, dev[0], dev[1] + 4 * unit_offset_floats if len(unit_rows) else None, len(unit_rows),
+                          dev[0] + tb if len(staged_rows) else None, len(staged_rows), dev[2])
+        ctx.sync()
+        return ctx.from_device(dev[2], (n_rows, dim), np.float32)
+    finally:
+        ctx.sync()
+        for x in dev:
+            ctx.free(x)
+        ctx.host_free(pinned)
 
 
 def wire_pack(ctx: Context, kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, send_all_features: bool = False, fill: int = 0):

@@ -240,6 +240,12 @@ int omni_memcpy_d2h_async(omni_ctx* c, void* dst_pinned, const void* src, size_t
     return OMNI_OK;
 }
 
+int omni_memcpy_h2d_async(omni_ctx* c, void* dst_dev, const void* src_pinned, size_t bytes) {
+    OMNI_REQUIRE(c && dst_dev && src_pinned, OMNI_ERR_INVALID, "null argument");
+    OMNI_HIP_TRY(hipMemcpyAsync(dst_dev, src_pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    return OMNI_OK;
+}
+
 int omni_ctx_order_after(omni_ctx* later, omni_ctx* earlier) {
     OMNI_REQUIRE(later && earlier && later->device == earlier->device, OMNI_ERR_INVALID, "omni_ctx_order_after: two contexts of one device");
     if (later == earlier) return OMNI_OK;

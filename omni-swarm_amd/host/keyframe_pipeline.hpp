@@ -21,6 +21,7 @@
 #include "loop_geometry.hpp"
 #include "loop_net_wire.hpp"
 #include "omni_swarm.hpp"
+#include "remote_queue.hpp"
 
 namespace omni {
 
@@ -107,6 +108,14 @@ public:
         // device_depth_landmarks in effect and is refused otherwise, as on the sharded database, which builds no messages.  send_all_features: LoopNet's
         // SEND_ALL_FEATURES.  All off by default.  (set_wire: before the first key frame.)
         bool wire = false, device_wire = false, send_all_features = false;
+        // Remote key frames join the unit stream.  Off (the default): every frame the wire completes goes through flush() + on_remote_frame -- the units in flight
+        // are waited for, the frame's four global descriptors go up in four blocking copies and its search is waited for.  On: the frame is QUEUED
+        // (queue_remote_frame; drain_inbox does it for the wire's frames) with p, the number of local key frames handed over before it, and the next key-frame
+        // unit's detector batch takes it at its place in the serial order (host/remote_queue.hpp): its rows are gathered with the unit's on the GPU
+        // (csrc/rows_assemble.hip; LoopDetectorCore's mixed batch) and its verdict is replayed with the unit's.  With no local key frame around, queue_remote_frame,
+        // poll() and flush() begin a batch of remote frames alone.  Candidates, edges, counters and rows are the serial flow's.  The sharded database, which builds
+        // no messages, refuses it.  (set_remote_in_stream: before the first key frame.)
+        bool remote_in_stream = false;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -751,10 +760,13 @@ public:
 private:
     void drain_inbox() {
         while (!inbox_.empty()) {
-            const FisheyeFrameDescriptor f = std::move(inbox_.front());
+            FisheyeFrameDescriptor f = std::move(inbox_.front());
             inbox_.pop_front();
             ++remote_frames_;
-            flush();
+            if (cfg_.remote_in_stream) { queue_remote_frame(std::move(f)); continue; }
+            ++remote_stats_[3];
+            const int hits = flush();                          // (the local candidates this flush found are returned by the next push_keyframe / poll / flush)
+            { std::lock_guard<std::mutex> lk(intake_mu_); carried_hits_ += hits; }
             on_remote_frame(f);
         }
     }
@@ -812,12 +824,41 @@ public:
         std::lock_guard<std::mutex> lk(intake_mu_);
         if (shard_) throw std::runtime_error("on_remote_frame: the sharded database builds no messages");
         if (f.drone_id == cfg_.self_id) throw std::invalid_argument("on_remote_frame: the frame carries this drone's own id");
+        // remote_in_stream: frames queued earlier (and the batch that holds some) come first, so the order is kept
+        if (cfg_.remote_in_stream && (!remote_queue_.empty() || det_pending_.active)) carried_hits_ += flush_locked();
         collect_geometry();
         const LoopCandidate r = det_.on_image_recv(f);
         collect_geometry();
         if (r.found) candidates_.push_back({f.msg_id, r.old_msg_id, r.direction_new, r.direction_old});
         return r;
     }
+    // ---- remote key frames in the unit stream (Config::remote_in_stream) -------------------------------------------------------------------------------------
+    bool remote_in_stream() const { return cfg_.remote_in_stream; }
+    // before the first key frame (what the C entry point omni_pipeline_set_remote_in_stream sets)
+    void set_remote_in_stream(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_remote_in_stream after the first key frame");
+        if (on && shard_) throw std::runtime_error("set_remote_in_stream: the sharded database builds no messages");
+        if (!on && remote_pending() > 0) throw std::runtime_error("set_remote_in_stream(false): remote frames are queued (flush first)");
+        cfg_.remote_in_stream = on;
+    }
+    // A key frame of ANOTHER drone joins the stream: it is queued behind the local key frames handed over so far and leaves with the next unit's detector batch --
+    // or, when every local key frame in front of it has its batch begun and no batch is pending, at once in a batch of remote frames alone (collected by poll(),
+    // the next unit or flush()).  Its candidate goes into candidates(), an accepted loop into edges(), as with on_remote_frame.
+    void queue_remote_frame(FisheyeFrameDescriptor&& f) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (shard_) throw std::runtime_error("queue_remote_frame: the sharded database builds no messages");
+        if (!cfg_.remote_in_stream) throw std::runtime_error("queue_remote_frame: remote_in_stream is off (set_remote_in_stream)");
+        if (f.drone_id == cfg_.self_id) throw std::invalid_argument("queue_remote_frame: the frame carries this drone's own id");
+        remote_queue_.push_back({std::move(f), next_seq_});
+        ++remote_stats_[0];
+        begin_remote_batch();
+    }
+    // remote frames queued or in a detector batch that has not been collected yet
+    int64_t remote_pending() const { return (int64_t)remote_queue_.size() + remote_in_batch_; }
+    // [0] frames queued so far, [1] of them, frames that joined a key-frame unit's batch, [2] batches of remote frames alone, [3] flushes a remote frame forced
+    // (the frames of the wire that took the switch-off path)
+    void remote_stats(int64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = remote_stats_[i]; }
     LoopDetectorCore& detector() { return det_; }
     LoopGeometry& geometry() { return geo_; }
     // the reference's launch parameters (host/swarm_loop_params.hpp) that reach the detector and the geometry stage AFTER construction (the constructor took
@@ -836,6 +877,7 @@ public:
     void attach_shard(int rank, int world, const char* unique_id) {
         if (cfg_.fit_pca) throw std::runtime_error("attach_shard: fit_pca does not run on the sharded database, which builds no descriptors of its own");
         if (cfg_.wire) throw std::runtime_error("attach_shard: the wire does not run on the sharded database, which builds no messages");
+        if (cfg_.remote_in_stream) throw std::runtime_error("attach_shard: remote_in_stream does not run on the sharded database, which builds no messages");
         if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
@@ -908,6 +950,7 @@ public:
             const int want = recut ? m : lane->mb;
             if (lane->cur != want) { lane->cam.set_active(nd * want); lane->cur = want; }     // (the streaming intake or a recut run may have left another size)
             chain(lane, fifo);
+            lane->seq_first = next_seq_; next_seq_ += m;            // (run()'s key frames are handed over in id order)
             unit_poses(lane, want, first_msg_id + f0);
             if (compressed()) {
                 // pool[e] / tail: JpegFile[2 * cnt] (PINHOLE_DEPTH: [cnt]) -- the block's left (raw fisheye: up) files, then its right (down) files; a unit takes
@@ -1027,6 +1070,7 @@ public:
                 if (!l->stage) throw std::runtime_error(std::string("omni_host_alloc: ") + omni_last_error());
             }
             l->t_enqueue = std::chrono::steady_clock::now();
+            l->seq_first = next_seq_;
             open_ = l;
         }
         const int m = (int)open_->meta.size();
@@ -1046,6 +1090,7 @@ public:
             sm.depth = open_->depth_stage.data() + dimg * m;
         }
         open_->meta.push_back(sm);
+        ++next_seq_;                                            // handed over: a remote frame queued from now on comes behind this key frame
         const bool full = (int)open_->meta.size() == MB;
         const bool idle = cfg_.dispatch_when_idle && stream_pending_.empty();
         const bool aged = cfg_.max_wait_ms >= 0 && since(open_->t_enqueue) >= cfg_.max_wait_ms;
@@ -1066,11 +1111,16 @@ public:
         int hits = carried_hits_; carried_hits_ = 0;
         hits += reap_ready();
         if (open_ && !open_->meta.empty() && cfg_.max_wait_ms >= 0 && since(open_->t_enqueue) >= cfg_.max_wait_ms) dispatch_open();
+        begin_remote_batch();                                   // queued remote frames with no local key frame in front of them do not wait for one
         return hits;
     }
     // everything pushed so far through the detector (and the geometry stage): a partial micro-batch runs as its own, smaller unit
     int flush() {
         std::lock_guard<std::mutex> lk(intake_mu_);
+        return flush_locked();
+    }
+private:
+    int flush_locked() {
         int hits = carried_hits_; carried_hits_ = 0;
         std::exception_ptr first;
         try { if (open_ && !open_->meta.empty()) dispatch_open(); } catch (...) { first = std::current_exception(); }
@@ -1080,9 +1130,15 @@ public:
             try { hits += finish_timed(*l, 0); } catch (...) { if (!first) first = std::current_exception(); }      // the other units are still finished
         }
         try { hits += collect_detector(); drain_geometry(); } catch (...) { if (!first) first = std::current_exception(); }
+        // the queue is drained completely: every local key frame is through (or was dropped with a failed unit), what is left goes as batches of remote frames
+        begun_seq_ = next_seq_;
+        try {
+            while (!remote_queue_.empty()) { begin_remote_batch(); if (!det_pending_.active) break; hits += collect_detector(); drain_geometry(); }
+        } catch (...) { if (!first) first = std::current_exception(); }
         if (first) std::rethrow_exception(first);
         return hits;
     }
+public:
     // the streaming intake's settings after construction (what the C entry point omni_pipeline_set_latency sets)
     void set_latency(double max_wait_ms, bool dispatch_when_idle) { std::lock_guard<std::mutex> lk(intake_mu_); cfg_.max_wait_ms = max_wait_ms; cfg_.dispatch_when_idle = dispatch_when_idle; }
 
@@ -1110,6 +1166,7 @@ private:
         void sync() { check(omni_ctx_sync(sp_ctx.get()), "sync"); if (vlad_ctx) check(omni_ctx_sync(vlad_ctx->get()), "sync"); }
         std::chrono::steady_clock::time_point t_enqueue;
         int mb;                                        // key frames the unit was created for
+        int64_t seq_first = 0;                         // hand-over number of the unit's first key frame (remote_in_stream: the unit covers [seq_first, seq_first + cur))
         int cur = 0;                                   // ... and of the unit in flight (a partly filled micro-batch of the streaming intake: omni_cam_set_active)
         std::vector<SlotMeta> meta;                    // streaming intake (push_keyframe): what each key frame of the unit came with; empty = run()'s numbering
         std::vector<std::vector<uint8_t>> jfiles[2];   // streaming intake with compressed_images: the unit's JPEG files, left then right camera, copied at the push
@@ -1209,8 +1266,10 @@ private:
         struct Pop { ~Pop() { omni_trace_pop(); } } pop_at_exit;
         int hits = 0, fi = 0;
         det_pending_.active = false;                     // first: if end_images_batch() throws (its rollback has dropped the batch), the next unit starts clean
+        remote_in_batch_ = 0;
         for (auto& c : det_.end_images_batch()) {
-            if (c.found) { ++hits; candidates_.push_back({det_pending_.ids[(size_t)fi], c.old_msg_id, c.direction_new, c.direction_old}); }
+            // (the returned count stays that of LOCAL key frames; a remote frame's candidate is in candidates(), as with on_remote_frame)
+            if (c.found) { if (det_pending_.remote.empty() || !det_pending_.remote[(size_t)fi]) ++hits; candidates_.push_back({det_pending_.ids[(size_t)fi], c.old_msg_id, c.direction_new, c.direction_old}); }
             ++fi;
         }
         host_ms_[3] += since(t_a);
@@ -1218,10 +1277,10 @@ private:
         // the previous micro-batch's tasks ran meanwhile; this one's run until the next is collected.  The tasks reference this micro-batch's frames:
         // those moved into the database live there (std::map: stable), the others are handed over
         drain_geometry();
-        const bool left = start_geometry(&det_.held_frames(), &det_pending_.t_enqueue);
+        const bool left = start_geometry(&det_.held_frames(), det_pending_.timed ? &det_pending_.t_enqueue : nullptr);
         if (!async_geometry_) drain_geometry();
         det_.held_frames().clear();
-        if (!left) latencies_ms_.push_back(since(det_pending_.t_enqueue));        // (otherwise drain_geometry() records it, when the micro-batch's last edge is in)
+        if (!left && det_pending_.timed) latencies_ms_.push_back(since(det_pending_.t_enqueue));        // (otherwise drain_geometry() records it, when the micro-batch's last edge is in)
         host_ms_[4] += since(t_a);
         return hits;
     }
@@ -1337,8 +1396,12 @@ private:
         t_a = std::chrono::steady_clock::now();
         det_pending_.ids.resize((size_t)lane.cur);
         for (int m = 0; m < lane.cur; ++m) det_pending_.ids[(size_t)m] = lane.meta.empty() ? first_id + m : lane.meta[(size_t)m].msg_id;
-        det_pending_.t_enqueue = lane.t_enqueue;
-        det_.begin_images_batch(std::move(frames_), lane.rows_dev);             // appends + searches + the copy of the lists: enqueued, not waited for
+        det_pending_.t_enqueue = lane.t_enqueue; det_pending_.timed = true;
+        det_pending_.remote.clear();
+        unit_pos_.clear();
+        begun_seq_ = lane.seq_first + lane.cur;                                  // (whatever throws below: these key frames will not come again)
+        if (!join_remote(lane))
+            det_.begin_images_batch(std::move(frames_), lane.rows_dev);         // appends + searches + the copy of the lists: enqueued, not waited for
         det_pending_.active = true;
         frames_.clear();
         // the appends and the query gather read MobileNetVLAD's output buffer: the lane's next unit must not overwrite it before they have
@@ -1350,9 +1413,12 @@ private:
             // key frames in stripes over the helper threads and this one (OMNI_MESSAGE_THREADS): each message is written by one thread, the result block is
             // only read; what the stripes share is the allocator.  Matters where this is exposed: behind the LAST unit of a run() call
             const int n_kf = std::min(lane.cur, (int)held.size()), parts = msg_pool_ ? std::min(n_kf, msg_pool_->size() + 1) : 1;
+            // unit slot m is batch frame unit_pos_[m] when remote frames have joined the batch (join_remote), frame m otherwise
             auto stripe = [&, n_kf, parts](int p) {
-                for (int m = p; m < n_kf; m += parts)
-                    for (int d = 0; d < nd && d < (int)held[(size_t)m].images.size(); ++d) heavy(held[(size_t)m].images[(size_t)d], nd * m + d);
+                for (int m = p; m < n_kf; m += parts) {
+                    FisheyeFrameDescriptor& f = held[unit_pos_.empty() ? (size_t)m : unit_pos_[(size_t)m]];
+                    for (int d = 0; d < nd && d < (int)f.images.size(); ++d) heavy(f.images[(size_t)d], nd * m + d);
+                }
             };
             std::vector<std::future<void>> helpers;
             for (int p = 1; p < parts; ++p) helpers.push_back(msg_pool_->submit([&stripe, p] { stripe(p); }));
@@ -1364,6 +1430,54 @@ private:
         }
         if (!async_detector_) hits += collect_detector();                       // OMNI_DETECTOR_ASYNC=0: wait for it here, as before (A/B)
         return hits;
+    }
+
+    // finish(): the queued remote frames that belong in front of, between or right behind the key frames of `lane`'s unit join its batch (host/remote_queue.hpp).
+    // false: none do -- the caller begins the unit's batch as it always did.  frames_ and det_pending_.ids hold the unit's key frames on entry
+    bool join_remote(Lane& lane) {
+        if (!cfg_.remote_in_stream || remote_queue_.empty()) return false;
+        std::vector<int64_t> ps;
+        for (const QueuedRemote& q : remote_queue_) ps.push_back(q.p);
+        int64_t taken = 0;
+        const std::vector<RemoteMergeSlot> plan = remote_merge_plan(lane.seq_first, lane.seq_first + lane.cur, ps.data(), (int64_t)ps.size(), &taken);
+        if (taken == 0) return false;
+        const int nd = cfg_.dirs();
+        std::vector<FisheyeFrameDescriptor> batch;
+        std::vector<int64_t> first_row, ids;
+        batch.reserve(plan.size());
+        unit_pos_.assign((size_t)lane.cur, 0);
+        for (const RemoteMergeSlot& s : plan) {
+            det_pending_.remote.push_back(s.remote ? 1 : 0);
+            if (s.remote) { FisheyeFrameDescriptor& f = remote_queue_[(size_t)s.index].f; ids.push_back(f.msg_id); first_row.push_back(-1); batch.push_back(std::move(f)); }
+            else { unit_pos_[(size_t)s.index] = batch.size(); ids.push_back(det_pending_.ids[(size_t)s.index]); first_row.push_back((int64_t)nd * s.index); batch.push_back(std::move(frames_[(size_t)s.index])); }
+        }
+        remote_queue_.erase(remote_queue_.begin(), remote_queue_.begin() + taken);
+        det_pending_.ids = std::move(ids);
+        remote_stats_[1] += taken;
+        det_.begin_images_batch(std::move(batch), lane.rows_dev, (int64_t)nd * lane.cur, first_row);
+        remote_in_batch_ = taken;
+        return true;
+    }
+    // A batch of remote frames alone, for those that wait for no local key frame: every local key frame handed over before the oldest queued frame has its batch
+    // begun (no open unit and no unit in flight in front of it), and no detector batch is pending.  Collected like a unit's: collect_detector
+    void begin_remote_batch() {
+        if (!cfg_.remote_in_stream || remote_queue_.empty() || det_pending_.active || remote_queue_.front().p > begun_seq_) return;
+        std::vector<int64_t> ps;
+        for (const QueuedRemote& q : remote_queue_) ps.push_back(q.p);
+        int64_t taken = 0;
+        remote_merge_plan(begun_seq_, begun_seq_, ps.data(), (int64_t)ps.size(), &taken);
+        std::vector<FisheyeFrameDescriptor> batch;
+        det_pending_.ids.clear();
+        for (int64_t q = 0; q < taken; ++q) { det_pending_.ids.push_back(remote_queue_[(size_t)q].f.msg_id); batch.push_back(std::move(remote_queue_[(size_t)q].f)); }
+        remote_queue_.erase(remote_queue_.begin(), remote_queue_.begin() + taken);
+        det_pending_.remote.assign((size_t)taken, 1);
+        det_pending_.timed = false;
+        unit_pos_.clear();
+        ++remote_stats_[2];
+        // (nothing is deferred while no batch is pending, and the replay verifies a remote candidate behind everything started earlier: no wait for the geometry here)
+        det_.begin_images_batch(std::move(batch), nullptr, 0, std::vector<int64_t>((size_t)taken, -1));
+        det_pending_.active = true;
+        remote_in_batch_ = taken;
     }
 
     Config cfg_;
@@ -1383,7 +1497,8 @@ private:
         bool timed = false;
     };
     std::deque<GeoBatch> geo_inflight_;         // (declared before the pool: outlives its threads)
-    struct DetPending { bool active = false; std::vector<int64_t> ids; std::chrono::steady_clock::time_point t_enqueue; } det_pending_;
+    // ids: one per frame of the batch (a remote frame's own msg_id); remote: per frame, empty = a unit's key frames alone; timed: a unit's batch (its latency is recorded)
+    struct DetPending { bool active = false, timed = true; std::vector<int64_t> ids; std::vector<char> remote; std::chrono::steady_clock::time_point t_enqueue; } det_pending_;
     bool async_detector_ = [] { int v = 1; check(omni_config_value("OMNI_DETECTOR_ASYNC", &v), "omni_config_value"); return v != 0; }();
     bool async_geometry_ = [] { int v = 1; check(omni_config_value("OMNI_GEOMETRY_ASYNC", &v), "omni_config_value"); return v != 0; }();
     std::atomic<int> homography_pairs_device_{0}, homography_pairs_host_{0};      // (counted by the geometry tasks; declared before the pool: outlive its threads)
@@ -1442,6 +1557,13 @@ private:
     SentFrame* publishing_ = nullptr;           // where broadcast_fisheye_desc's packets go while finish() runs it
     std::vector<omni_wire_image_meta> wire_meta_;
     int64_t remote_frames_ = 0;
+    // remote_in_stream: the queue in arrival order, each frame with p = the local key frames handed over before it; next_seq_: local key frames handed over so far;
+    // begun_seq_: every local key frame below it has its detector batch begun; remote_in_batch_: remote frames in the batch that is pending
+    struct QueuedRemote { FisheyeFrameDescriptor f; int64_t p; };
+    std::deque<QueuedRemote> remote_queue_;
+    int64_t next_seq_ = 0, begun_seq_ = 0, remote_in_batch_ = 0;
+    int64_t remote_stats_[4] = {0, 0, 0, 0};
+    std::vector<size_t> unit_pos_;               // finish(): unit slot -> position in the batch, when remote frames have joined it
     double wire_ms_ = 0;                        // the calling thread's milliseconds in wire_out so far (wire_host_ms)
     std::unique_ptr<IndexFlatIP> shard_index_;
     omni_shard* shard_ = nullptr;

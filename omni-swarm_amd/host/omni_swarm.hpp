@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/omni_hip.h"
+#include "../csrc/rows_plan.h"
 #ifdef OMNI_WITH_OPENCV
 #include <opencv2/opencv.hpp>
 #endif
@@ -685,7 +686,12 @@ public:
 
     LoopDetectorCore(Context& ctx, int self_id, int storage = OMNI_STORE_F32)
         : self_id(self_id), local_index(ctx, 4096, storage), remote_index(ctx, 4096, storage), ctx_(ctx) {}
-    ~LoopDetectorCore() { if (batch_buf_) omni_dev_free(ctx_.get(), batch_buf_); if (raw_pinned_) omni_host_free(raw_pinned_); }
+    ~LoopDetectorCore() {
+        if (batch_buf_) omni_dev_free(ctx_.get(), batch_buf_);
+        if (mixed_dev_) omni_dev_free(ctx_.get(), mixed_dev_);
+        if (raw_pinned_) omni_host_free(raw_pinned_);
+        if (mixed_pinned_) omni_host_free(mixed_pinned_);
+    }
 
     int database_size() const { return replaying_ ? (int)(sim_local_ + sim_remote_) : (int)(local_index.ntotal + remote_index.ntotal); }
 
@@ -715,10 +721,31 @@ public:
         pb_.owned = std::move(frames);
         begin_batch(&pb_.owned, true, rows_dev);
     }
+    // A batch whose rows come from BOTH places (a key-frame unit's batch that remote frames have joined): unit_first_row[f] >= 0 -- frame f's images are rows
+    // first .. first + images - 1 of unit_rows_dev ([n_unit_rows][4096] in HBM, e.g. MobileNetVLAD's output buffer); -1 -- its rows are its own image_desc on the
+    // host (malformed / sanitise apply to these frames, as in a batch without rows_dev; an image without a 4096-float descriptor gets a row of zeros).  The rows
+    // are gathered into ONE block in frame order on the GPU (omni_rows_assemble_enqueue_dev, csrc/rows_plan.h): the table and the host rows go into a pinned block
+    // of this object and up in one asynchronous copy, one kernel writes the block, and the appends and prefix searches read it as they read rows_dev above.
+    // Nothing here waits for the GPU.  unit_rows_dev == nullptr with every entry -1: a batch of remote frames alone.
+    void begin_images_batch(std::vector<FisheyeFrameDescriptor>&& frames, const float* unit_rows_dev, int64_t n_unit_rows, const std::vector<int64_t>& unit_first_row) {
+        if (pb_.active) throw std::logic_error("begin_images_batch: the previous batch was not ended");
+        if (unit_first_row.size() != frames.size()) throw std::invalid_argument("begin_images_batch: one unit_first_row entry per frame");
+        pb_.owned = std::move(frames);
+        // (in place: the frames are this object's now, and the unit's own frames -- light messages whose descriptors are in HBM only -- are left alone)
+        for (size_t fi = 0; fi < pb_.owned.size(); ++fi) if (unit_first_row[fi] < 0 && malformed(pb_.owned[fi])) sanitise(pb_.owned[fi]);
+        const MixedRows mixed{unit_rows_dev, n_unit_rows, &unit_first_row};
+        begin_batch(&pb_.owned, true, nullptr, &mixed);
+    }
+    std::vector<LoopCandidate> on_images_recv_batch(std::vector<FisheyeFrameDescriptor>&& frames, const float* unit_rows_dev, int64_t n_unit_rows,
+                                                    const std::vector<int64_t>& unit_first_row) {
+        begin_images_batch(std::move(frames), unit_rows_dev, n_unit_rows, unit_first_row);
+        return end_images_batch();
+    }
     bool batch_pending() const { return pb_.active; }
     std::vector<FisheyeFrameDescriptor>& held_frames() { return pb_.owned; }
 
 private:
+    struct MixedRows { const float* unit_rows_dev; int64_t n_unit_rows; const std::vector<int64_t>* unit_first_row; };
     struct BatchSearch { IndexFlatIP* index; size_t row; int max_index; int64_t n_limit; };
     struct PendingBatch {
         bool active = false, movable = false;
@@ -728,11 +755,63 @@ private:
         std::vector<std::pair<size_t, size_t>> where;            // byte offsets of I and D per search
         size_t need = 0;
         bool any_add = false;
+        bool mixed_upload = false;                               // the batch's rows were gathered by assemble_mixed: its upload reads mixed_pinned_
         int64_t start_local = 0, start_remote = 0;
         float* own_rows = nullptr;
     } pb_;
     char* raw_pinned_ = nullptr;
     size_t raw_pinned_bytes_ = 0;
+    // The rows of a mixed batch, [total_rows][4096] in frame order, gathered on the GPU: table + host rows into the pinned block, ONE asynchronous upload, ONE
+    // kernel (csrc/rows_assemble.hip) into the device block behind them.  No host synchronisation.  The pinned block must not be rewritten before the upload of
+    // the previous batch has run, and the device block not before its appends and searches have read it: one batch is open at a time, and end_images_batch synchronises
+    // with the stream whenever a batch uploaded anything (PendingBatch::mixed_upload), so both hold.  Only behind a batch that FAILED after its upload was
+    // enqueued (mixed_in_flight_ still set) the next one waits here first.
+    char* mixed_pinned_ = nullptr;
+    char* mixed_dev_ = nullptr;
+    size_t mixed_pinned_bytes_ = 0, mixed_dev_bytes_ = 0;
+    bool mixed_in_flight_ = false;
+    const float* assemble_mixed(const std::vector<FisheyeFrameDescriptor>& frames, const MixedRows& mixed, size_t total_rows) {
+        std::vector<omni_row_source> table;
+        std::vector<const float*> staged;
+        table.reserve(total_rows);
+        for (size_t fi = 0; fi < frames.size(); ++fi) {
+            const int64_t first = (*mixed.unit_first_row)[fi];
+            for (size_t i = 0; i < frames[fi].images.size(); ++i) {
+                const std::vector<float>& g = frames[fi].images[i].image_desc;
+                if (first >= 0) table.push_back({OMNI_ROW_UNIT, (int32_t)(first + (int64_t)i)});
+                else if (g.size() == 4096) { table.push_back({OMNI_ROW_STAGED, (int32_t)staged.size()}); staged.push_back(g.data()); }
+                else table.push_back({OMNI_ROW_ZERO, 0});
+            }
+        }
+        const int64_t n_rows = (int64_t)total_rows, n_staged = (int64_t)staged.size();
+        if (const char* why = rows::refusal(table.data(), n_rows, 4096, mixed.n_unit_rows, n_staged)) throw std::invalid_argument(std::string("begin_images_batch: ") + why);
+        const size_t up = rows::upload_bytes(n_rows, 4096, n_staged), dev = rows::device_bytes(n_rows, 4096, n_staged);
+        if (mixed_in_flight_) { check(omni_ctx_sync(ctx_.get()), "omni_ctx_sync"); mixed_in_flight_ = false; }
+        if (mixed_pinned_bytes_ < up) {
+            if (mixed_pinned_) omni_host_free(mixed_pinned_);
+            mixed_pinned_bytes_ = 0;
+            mixed_pinned_ = static_cast<char*>(omni_host_alloc(up));
+            if (!mixed_pinned_) throw std::runtime_error(std::string("omni_host_alloc: ") + omni_last_error());
+            mixed_pinned_bytes_ = up;
+        }
+        if (mixed_dev_bytes_ < dev) {
+            if (mixed_dev_) omni_dev_free(ctx_.get(), mixed_dev_);
+            mixed_dev_bytes_ = 0;
+            mixed_dev_ = static_cast<char*>(omni_dev_alloc(ctx_.get(), dev));
+            if (!mixed_dev_) throw std::runtime_error(std::string("omni_dev_alloc: ") + omni_last_error());
+            mixed_dev_bytes_ = dev;
+        }
+        std::memcpy(mixed_pinned_, table.data(), table.size() * sizeof(omni_row_source));
+        float* staged_host = reinterpret_cast<float*>(mixed_pinned_ + rows::table_bytes(n_rows));
+        for (size_t s = 0; s < staged.size(); ++s) std::memcpy(staged_host + s * 4096, staged[s], 4096 * 4);
+        float* out = reinterpret_cast<float*>(mixed_dev_ + rows::out_offset(n_rows, 4096, n_staged));
+        check(omni_memcpy_h2d_async(ctx_.get(), mixed_dev_, mixed_pinned_, up), "begin_images_batch upload");
+        mixed_in_flight_ = true;
+        check(omni_rows_assemble_enqueue_dev(ctx_.get(), n_rows, 4096, reinterpret_cast<const omni_row_source*>(mixed_dev_), mixed.unit_rows_dev, mixed.n_unit_rows,
+                                             reinterpret_cast<const float*>(mixed_dev_ + rows::table_bytes(n_rows)), n_staged, out),
+              "omni_rows_assemble_enqueue_dev");
+        return out;
+    }
     void rollback_batch() {
         // a failed append / search / copy: take the rows of this batch out again so that row ids, the id maps and the recency rule of every
         // later frame stay what they were (the Python twin's _rollback)
@@ -744,13 +823,20 @@ private:
         row_ids_.clear(); deferred_.clear();
         pb_.active = false;
     }
-    void begin_batch(const std::vector<FisheyeFrameDescriptor>* frames_in, bool movable, const float* rows_dev) {
+    void begin_batch(const std::vector<FisheyeFrameDescriptor>* frames_in, bool movable, const float* rows_dev, const MixedRows* mixed = nullptr) {
         if (pb_.active) throw std::logic_error("on_images_recv_batch: a batch begun with begin_images_batch is still open");
+        if (mixed) {
+            for (size_t fi = 0; fi < frames_in->size(); ++fi) {
+                const int64_t first = (*mixed->unit_first_row)[fi];
+                if (first >= 0 && (!mixed->unit_rows_dev || first + (int64_t)(*frames_in)[fi].images.size() > mixed->n_unit_rows))
+                    throw std::invalid_argument("begin_images_batch: a frame's rows lie outside unit_rows_dev");
+            }
+        }
         // host rows are read as 4096 floats each: an image whose global descriptor has another length (a malformed or other-version packet
         // that got past LoopNet) counts as an image without landmarks -- the reference would read past the vector (loop_detector.cpp:166-170)
         pb_.cleaned.clear();
         pb_.movable = movable;
-        if (!rows_dev) {
+        if (!rows_dev && !mixed) {                               // (a mixed batch owns its frames: its host-row frames were sanitised in place)
             bool bad = false;
             for (auto& f : *frames_in) bad = bad || malformed(f);
             if (bad) { pb_.cleaned = *frames_in; for (auto& f : pb_.cleaned) sanitise(f); pb_.movable = false; }
@@ -794,7 +880,11 @@ private:
         }
         // enqueue: rows to HBM unless they are there already, appends, prefix searches, one result copy
         pb_.own_rows = nullptr;
-        if (!rows_dev && (!adds.empty() || !searches.empty())) {
+        pb_.mixed_upload = false;
+        if (mixed && (!adds.empty() || !searches.empty())) {
+            rows_dev = assemble_mixed(frames, *mixed, total_rows);
+            pb_.mixed_upload = true;
+        } else if (!rows_dev && (!adds.empty() || !searches.empty())) {
             std::vector<float> stage(total_rows * 4096, 0.f);
             size_t r = 0;
             for (auto& f : frames) for (auto& img : f.images) { if (img.image_desc.size() == 4096) std::memcpy(&stage[r * 4096], img.image_desc.data(), 4096 * 4); ++r; }
@@ -865,7 +955,7 @@ public:
         if (!pb_.active) throw std::logic_error("end_images_batch without a batch");
         const std::vector<FisheyeFrameDescriptor>& frames = *pb_.frames;
         try {
-            if (pb_.need || pb_.any_add || pb_.own_rows) check(omni_ctx_sync(ctx_.get()), "omni_ctx_sync");      // the only synchronisation
+            if (pb_.need || pb_.any_add || pb_.own_rows || pb_.mixed_upload) { check(omni_ctx_sync(ctx_.get()), "omni_ctx_sync"); mixed_in_flight_ = false; }      // the only synchronisation
         } catch (...) { rollback_batch(); throw; }
         deferred_.clear();
         for (size_t j = 0; j < pb_.searches.size(); ++j) {

@@ -44,6 +44,11 @@ WIRE_SYMBOLS = ["omni_wire_host_last_error", "omni_pipeline_set_wire", "omni_pip
                 "omni_pipeline_set_wire_recv", "omni_pipeline_recv_packet", "omni_pipeline_scan_recv", "omni_pipeline_remote_frames", "omni_pipeline_wire_host_ms"]
 WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")      # include/omni_host_wire.h OMNI_WIRE_CHANNEL_*
 _wire_lib = None
+# remote key frames joining the unit stream: include/omni_host_remote.h, lib/libomni_host_remote.so (the same handle)
+REMOTE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_remote.so")
+REMOTE_SYMBOLS = ["omni_remote_last_error", "omni_pipeline_set_remote_in_stream", "omni_pipeline_get_remote_in_stream", "omni_pipeline_remote_pending",
+                  "omni_pipeline_remote_stats", "omni_pipeline_queue_copy_as_remote", "omni_remote_merge_plan"]
+_remote_lib = None
 JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
 JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
                    "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
@@ -364,12 +369,42 @@ def wire_lib():
     return _wire_lib
 
 
+def remote_lib():
+    global _remote_lib
+    if _remote_lib is None:
+        if not os.path.exists(REMOTE_LIB_PATH):
+            raise OSError(f"{REMOTE_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(REMOTE_LIB_PATH)
+        L.omni_remote_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_remote_in_stream.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_remote_in_stream.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.omni_pipeline_remote_pending.argtypes = [C.c_void_p]
+        L.omni_pipeline_remote_pending.restype = C.c_int64
+        L.omni_pipeline_remote_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_pipeline_queue_copy_as_remote.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64]
+        L.omni_remote_merge_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        _remote_lib = L
+    return _remote_lib
+
+
+def remote_merge_plan(a: int, b: int, queue_p):
+    """host/remote_queue.hpp's order rule, no pipeline and no GPU: the detector batch of a unit that covers the local hand-over numbers [a, b), given p of the queued
+    remote frames in arrival order -> ([(is_remote, index), ...] in detector order, queue entries taken from the front)"""
+    p = np.ascontiguousarray(queue_p, np.int64)
+    cap = max(b - a, 0) + len(p)
+    rem, idx = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int64)
+    n, taken = C.c_int64(0), C.c_int64(0)
+    if remote_lib().omni_remote_merge_plan(a, b, p.ctypes.data if len(p) else None, len(p), rem.ctypes.data, idx.ctypes.data, cap, C.byref(n), C.byref(taken)):
+        raise capi.OmniError(f"omni_remote_merge_plan: {remote_lib().omni_remote_last_error().decode()}")
+    return [(bool(rem[s]), int(idx[s])) for s in range(n.value)], taken.value
+
+
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
-                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False):
+                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -397,6 +432,9 @@ class KeyframePipeline:
         a PCA fit on the GPU (csrc/pca_fit.hip); pca_fit / pca_fit_write make components_.csv / mean_.csv of them.  Results do not depend on it.  Default off.
         wire / device_wire / send_all_features: the LoopNet wire (set_wire): every finished key frame leaves as LoopNet's packets (take_packets) and packets of
         other drones enter through recv_packet / scan_recv; device_wire packs the packets inside the key-frame unit on the GPU (the same bytes).  Default off.
+        remote_in_stream: key frames of other drones (the wire's, or queue_copy_as_remote's) are queued and join the next key-frame unit's detector batch at
+        their place in the serial order, their rows gathered with the unit's on the GPU (csrc/rows_assemble.hip), instead of stopping the pipeline with a flush
+        each; the same candidates, edges and rows (set_remote_in_stream).  Default off.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -445,6 +483,8 @@ class KeyframePipeline:
             self.set_fit_pca(True)
         if wire or device_wire:
             self.set_wire(wire, device_wire, send_all_features)
+        if remote_in_stream:
+            self.set_remote_in_stream(True)
 
     def _pca(self, rc, what):
         if rc:
@@ -641,6 +681,34 @@ class KeyframePipeline:
         ms = C.c_double(0)
         self._wire(wire_lib().omni_pipeline_wire_host_ms(self.h, C.byref(ms), int(reset)), "omni_pipeline_wire_host_ms")
         return ms.value
+
+    def _remote(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {remote_lib().omni_remote_last_error().decode()}")
+
+    def set_remote_in_stream(self, on: bool):
+        """remote key frames join the unit stream instead of flushing it (host/remote_queue.hpp).  Before the first key frame; refused on a sharded database"""
+        self._remote(remote_lib().omni_pipeline_set_remote_in_stream(self.h, int(bool(on))), "omni_pipeline_set_remote_in_stream")
+
+    def remote_in_stream(self) -> bool:
+        on = C.c_int(0)
+        self._remote(remote_lib().omni_pipeline_get_remote_in_stream(self.h, C.byref(on)), "omni_pipeline_get_remote_in_stream")
+        return bool(on.value)
+
+    @property
+    def remote_pending(self) -> int:
+        """remote frames queued, or in a detector batch that poll() / the next unit / flush() has not collected yet"""
+        return int(remote_lib().omni_pipeline_remote_pending(self.h))
+
+    def remote_stats(self):
+        """(frames queued, frames that joined a unit's batch, batches of remote frames alone, flushes a remote frame forced: the switch-off path)"""
+        out = (C.c_int64 * 4)()
+        self._remote(remote_lib().omni_pipeline_remote_stats(self.h, out), "omni_pipeline_remote_stats")
+        return tuple(int(v) for v in out)
+
+    def queue_copy_as_remote(self, src_msg_id: int, drone_id: int, new_msg_id: int):
+        """recv_copy_as_remote's twin: the copy of the stored key frame is queued (remote_in_stream) instead of handed to on_remote_frame"""
+        self._remote(remote_lib().omni_pipeline_queue_copy_as_remote(self.h, src_msg_id, drone_id, new_msg_id), "omni_pipeline_queue_copy_as_remote")
 
     def _jpeg(self, rc, what):
         if rc:
