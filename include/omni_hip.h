@@ -612,6 +612,57 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
                                    int mode, int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags,
                                    int* q_idx, int* t_idx, float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status);
 
+/* ---- loop verification: the correspondences of a candidate, assembled behind the homography kernels in the same round trip (csrc/corr_assemble.hip; the
+ * arithmetic: csrc/corr_plan.h, operation for operation that of the two compute_correspond_features of host/loop_geometry.hpp, loop_detector.cpp:431-624).
+ * A candidate owns pair_count <= 4 consecutive pairs of the call, in the order of the direction pairing.  Per pair: the flag filter, then the compaction by the
+ * homography mask (a pair with fewer than 4 flagged matches keeps them all); per candidate the concatenation over its pairs of X = landmarks_3d of the new
+ * image and u = landmarks_2d_norm of the old image rotated by the pair's dq_old and cast to float -- the layout omni_pnp_ransac_multi takes.  gate:
+ *   OMNI_CORR_OK      compute_correspond_features' `true` and compute_loop_core's size gate (:291) passed: compute_relative_pose is next;
+ *   OMNI_CORR_REJECT  one of the two failed: not a loop;
+ *   OMNI_CORR_HOST    one of the candidate's pairs came back OMNI_HG_HOST: run the host functions for this candidate. */
+#define OMNI_CORR_OK 0
+#define OMNI_CORR_REJECT 1
+#define OMNI_CORR_HOST 2
+typedef struct omni_corr_cand {
+    int32_t pair_first, pair_count;                         /* its pairs: pair_first .. pair_first + pair_count - 1 of the call */
+    int32_t min_match_pre_dir, min_direction_loop;          /* MIN_MATCH_PRE_DIR, MIN_DIRECTION_LOOP */
+    int32_t min_loop_num, init_mode_min_loop_num, init_mode; /* MIN_LOOP_NUM, INIT_MODE_MIN_LOOP_NUM, and whether the candidate runs in init_mode */
+    int32_t reserved;
+} omni_corr_cand;
+/* Everything the stage reads and writes, all in host memory (omni_corr_assemble_host) or all in device memory (the kernel).  Per pair p, rows of max_n: q_idx /
+ * t_idx [n_pairs][max_n] and n_matches = the matcher's list; q_flags [n_pairs][max_n] and n_flags = landmarks_flag of the new image; nq / nt = the two images' key
+ * points; mask [n_pairs][max_n] over the FLAGGED matches and hg_status = the homography stage's; q_3d [n_pairs][max_n][3] = landmarks_3d of the new image; t_norm
+ * [n_pairs][max_n][2] = landmarks_2d_norm of the old one; dq_old [n_pairs][4] = (w, x, y, z).  Out: X [n_cands][cap][3], u [n_cands][cap][2] (cap >= pair_count *
+ * max_n), n_corr, matched_dir_count, gate [n_cands]; new_idx / old_idx [n_pairs][max_n] and n_pair_corr [n_pairs] = the key-point indices of every pair's
+ * correspondences. */
+typedef struct omni_corr_io {
+    int32_t n_cands, n_pairs, max_n, cap;
+    const omni_corr_cand* cands;
+    const int32_t *q_idx, *t_idx, *n_matches;
+    const uint8_t* q_flags;
+    const int32_t *n_flags, *nq, *nt;
+    const uint8_t* mask;
+    const int32_t* hg_status;
+    const float *q_3d, *t_norm;
+    const double* dq_old;
+    float *X, *u;
+    int32_t *n_corr, *matched_dir_count, *gate, *new_idx, *old_idx, *n_pair_corr;
+} omni_corr_io;
+/* csrc/corr_plan.h compiled by g++ into the library: the stage on the host, the same bits, without a GPU and without a context.  1 <= n_cands <= 64,
+ * 0 <= n_pairs <= 64, 1 <= max_n <= 1024, 1 <= cap <= 4096.  Refused: a null argument, a candidate with more than 4 pairs or pairs outside the call's, cap below
+ * pair_count * max_n. */
+int omni_corr_assemble_host(const omni_corr_io* io);
+/* The kernel alone on arrays from the host (omni_homography_ransac_multi's counterpart): io as above, every pointer in host memory; one upload, one launch, one
+ * download.  The same refusals (OMNI_ERR_CAPACITY for the sizes).  *kernel_us, when not NULL: the launch's device time between two events.  Blocking. */
+int omni_corr_assemble_multi(omni_ctx* ctx, const omni_corr_io* io, float* kernel_us);
+/* omni_bf_match_homography_multi followed, in the same round trip (one more upload, one more launch, the same download), by the stage above: besides its
+ * arguments the candidates (n_cands, cands, cap), per pair q_3d[p] [nq[p]][3], t_norm[p] [nt[p]][2] and dq_old [n_pairs][4], and the stage's outputs (host). */
+int omni_bf_match_homography_corr_multi(omni_ctx* ctx, int n_pairs, const float* const* q_host, const int* nq, const float* const* t_host, const int* nt, int dim,
+                                        int mode, int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags,
+                                        int n_cands, const omni_corr_cand* cands, int cap, const float* const* q_3d, const float* const* t_norm, const double* dq_old,
+                                        int* q_idx, int* t_idx, float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status,
+                                        float* X, float* u, int* n_corr, int* matched_dir_count, int* gate, int* new_idx, int* old_idx, int* n_pair_corr);
+
 /* ---- loop verification: the RANSAC half of compute_relative_pose (loop_detector.cpp:355-413: cv::solvePnPRansac over EPnP models of 5 points, reprojection
  * error 3, confidence 0.99) on the GPU, f64 (csrc/pnp.hip; the arithmetic: csrc/pnp_plan.h, operation for operation that of host/geometry.hpp's
  * ransac_run<PnPModel> -- the same mask, the same best model).  The refit on the inliers (geom::pnp_refit) stays with the caller.  Per candidate:

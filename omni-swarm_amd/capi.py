@@ -55,6 +55,7 @@ SYMBOLS = [
     "omni_pcafit_merge_host", "omni_pca_solve_host", "omni_pcafit_solve", "omni_pca_moments_host", "omni_pca_write_csv",
     "omni_wire_packet_capacity", "omni_wire_table_ints", "omni_wire_pack_enqueue_dev", "omni_wire_pack_host", "omni_cam_set_wire", "omni_cam_set_wire_meta", "omni_cam_wire",
     "omni_rows_assemble_enqueue_dev", "omni_rows_assemble_host", "omni_memcpy_h2d_async",
+    "omni_corr_assemble_host", "omni_corr_assemble_multi", "omni_bf_match_homography_corr_multi",
 ]
 ROW_UNIT, ROW_STAGED, ROW_ZERO = 0, 1, 2      # include/omni_hip.h OMNI_ROW_*: where a row of a mixed detector batch comes from
 WIRE_HEADER_BYTES, WIRE_LANDMARK_BYTES, WIRE_HEADER_OFFSET = 16545, 324, 3      # include/omni_hip.h OMNI_WIRE_*
@@ -78,6 +79,16 @@ class _SpWeights(C.Structure):
 class _VladLayer(C.Structure):
     _fields_ = [("kind", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("stride", C.c_int),
                 ("weight", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float))]
+
+
+class CorrCand(C.Structure):      # include/omni_hip.h omni_corr_cand
+    _fields_ = [(n, C.c_int32) for n in ("pair_first", "pair_count", "min_match_pre_dir", "min_direction_loop", "min_loop_num", "init_mode_min_loop_num", "init_mode", "reserved")]
+
+
+class CorrIO(C.Structure):        # include/omni_hip.h omni_corr_io
+    _fields_ = [(n, C.c_int32) for n in ("n_cands", "n_pairs", "max_n", "cap")] + \
+               [(n, C.c_void_p) for n in ("cands", "q_idx", "t_idx", "n_matches", "q_flags", "n_flags", "nq", "nt", "mask", "hg_status", "q_3d", "t_norm", "dq_old", "X", "u",
+                                          "n_corr", "matched_dir_count", "gate", "new_idx", "old_idx", "n_pair_corr")]
 
 
 class _CamResult(C.Structure):
@@ -390,6 +401,11 @@ def lib():
     sig("omni_rows_assemble_enqueue_dev", C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp])
     sig("omni_rows_assemble_host", C.c_int, [C.c_int64, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp])
     sig("omni_memcpy_h2d_async", C.c_int, [_vp, _vp, _vp, C.c_size_t])
+    sig("omni_corr_assemble_host", C.c_int, [C.POINTER(CorrIO)])
+    sig("omni_corr_assemble_multi", C.c_int, [_vp, C.POINTER(CorrIO), _fp])
+    sig("omni_bf_match_homography_corr_multi", C.c_int, [_vp, C.c_int, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
+                                                       C.POINTER(_vp), _ip, C.c_int, _vp, C.c_int, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(C.c_double),
+                                                       _ip, _ip, _fp, _ip, _ip, _ip, _vp, C.POINTER(C.c_double), _ip, _ip, _fp, _fp, _ip, _ip, _ip, _ip, _ip, _ip])
     sig("omni_wire_packet_capacity", C.c_int64, [C.c_int])
     sig("omni_wire_table_ints", C.c_int, [C.c_int])
     sig("omni_wire_pack_enqueue_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -1621,6 +1637,110 @@ def bf_match_homography_multi(ctx: Context, pairs, mode: int = BF_OPENCV) -> lis
                                                 ip(kept), ip(nk), mask.ctypes.data, H.ctypes.data_as(C.POINTER(C.c_double)), ip(info), ip(status)))
     return [{"q_idx": qi[p, :n[p]].copy(), "t_idx": ti[p, :n[p]].copy(), "dist": dd[p, :n[p]].copy(), "kept": kept[p, :nk[p]].copy(), "mask": mask[p, :nk[p]].copy(),
              "H": H[p].copy(), "info": info[p].copy(), "status": int(status[p])} for p in range(P)]
+
+
+CORR_OK, CORR_REJECT, CORR_HOST = 0, 1, 2      # include/omni_hip.h OMNI_CORR_*
+HG_UNFILTERED, HG_OK, HG_NO_MODEL, HG_HOST = 0, 1, 2, 3
+
+
+def _corr_cands(cands):
+    """[(pair_first, pair_count, min_match_pre_dir, min_direction_loop, min_loop_num, init_mode_min_loop_num, init_mode), ...] -> omni_corr_cand[]"""
+    out = (CorrCand * max(len(cands), 1))()
+    for c, v in enumerate(cands):
+        (out[c].pair_first, out[c].pair_count, out[c].min_match_pre_dir, out[c].min_direction_loop, out[c].min_loop_num, out[c].init_mode_min_loop_num,
+         out[c].init_mode) = (int(x) for x in v)
+    return out
+
+
+def _corr_result(cands, P, n_corr, mdc, gate, X, u, new_idx, old_idx, npc):
+    per_cand = [{"n_corr": int(n_corr[c]), "matched_dir_count": int(mdc[c]), "gate": int(gate[c]), "X": X[c, :max(0, n_corr[c])].copy(), "u": u[c, :max(0, n_corr[c])].copy()}
+                for c in range(len(cands))]
+    per_pair = [{"new_idx": new_idx[p, :max(0, npc[p])].copy(), "old_idx": old_idx[p, :max(0, npc[p])].copy()} for p in range(P)]
+    return per_cand, per_pair
+
+
+class CorrArrays:
+    """omni_corr_io in host memory, built from per-pair dicts: q_idx, t_idx (the matcher's list), q_flags, nq, nt, mask (over the flagged matches), hg_status, q_3d
+    [nq][3], t_norm [nt][2], dq_old (w, x, y, z); cands: see _corr_cands.  .io is the struct (the arrays live as long as this object)"""
+
+    def __init__(self, cands, pairs, max_n: int | None = None, cap: int | None = None):
+        P, Cn = len(pairs), len(cands)
+        if max_n is None:
+            max_n = int(max([1] + [max(len(p["q_idx"]), len(p["q_flags"]), p["nq"], p["nt"], len(p["mask"])) for p in pairs]))
+        if cap is None:
+            cap = max(1, max([c[1] for c in cands] + [0]) * max_n)
+        Pn, Cc = max(P, 1), max(Cn, 1)
+        self.cands, self.P, self.max_n, self.cap = cands, P, max_n, cap
+        self.qi, self.ti = np.zeros((Pn, max_n), np.int32), np.zeros((Pn, max_n), np.int32)
+        self.fl, self.mk = np.zeros((Pn, max_n), np.uint8), np.zeros((Pn, max_n), np.uint8)
+        self.nm, self.nf, self.nq, self.nt, self.st = (np.zeros(Pn, np.int32) for _ in range(5))
+        self.q3, self.tn, self.dq = np.zeros((Pn, max_n, 3), np.float32), np.zeros((Pn, max_n, 2), np.float32), np.zeros((Pn, 4), np.float64)
+        for p, d in enumerate(pairs):
+            n = len(d["q_idx"])
+            self.qi[p, :n], self.ti[p, :n], self.nm[p] = d["q_idx"], d["t_idx"], d.get("n_matches", n)
+            self.fl[p, :len(d["q_flags"])], self.nf[p] = d["q_flags"], len(d["q_flags"])
+            self.mk[p, :len(d["mask"])] = d["mask"]
+            self.nq[p], self.nt[p], self.st[p] = d["nq"], d["nt"], d["hg_status"]
+            a, b = _f32(d["q_3d"]).reshape(-1, 3), _f32(d["t_norm"]).reshape(-1, 2)
+            self.q3[p, :len(a)], self.tn[p, :len(b)], self.dq[p] = a, b, d["dq_old"]
+        self.X, self.u = np.zeros((Cc, cap, 3), np.float32), np.zeros((Cc, cap, 2), np.float32)
+        self.n_corr, self.mdc, self.gate = (np.full(Cc, -1, np.int32) for _ in range(3))
+        self.new_idx, self.old_idx, self.npc = np.zeros((Pn, max_n), np.int32), np.zeros((Pn, max_n), np.int32), np.zeros(Pn, np.int32)
+        self.cd = _corr_cands(cands)
+        self.io = CorrIO(Cn, P, max_n, cap, C.cast(self.cd, _vp), *(a.ctypes.data for a in (
+            self.qi, self.ti, self.nm, self.fl, self.nf, self.nq, self.nt, self.mk, self.st, self.q3, self.tn, self.dq, self.X, self.u, self.n_corr, self.mdc, self.gate,
+            self.new_idx, self.old_idx, self.npc)))
+
+    def result(self):
+        return _corr_result(self.cands, self.P, self.n_corr, self.mdc, self.gate, self.X, self.u, self.new_idx, self.old_idx, self.npc)
+
+
+def corr_assemble(cands, pairs, ctx: Context | None = None, max_n: int | None = None, cap: int | None = None, time_kernel: bool = False):
+    """The correspondences of loop candidates (csrc/corr_plan.h): ctx None -> omni_corr_assemble_host, no GPU; a Context -> the kernel alone
+    (omni_corr_assemble_multi).  cands, pairs: see CorrArrays.  -> (per candidate {n_corr, matched_dir_count, gate, X [n][3], u [n][2]}, per pair {new_idx,
+    old_idx})[, the kernel's microseconds]"""
+    a = CorrArrays(cands, pairs, max_n, cap)
+    us = C.c_float(-1.0)
+    if ctx is None:
+        _check(lib().omni_corr_assemble_host(C.byref(a.io)))
+    else:
+        _check(lib().omni_corr_assemble_multi(ctx.h, C.byref(a.io), C.byref(us) if time_kernel else None))
+    return a.result() + (float(us.value),) if time_kernel else a.result()
+
+
+def bf_match_homography_corr_multi(ctx: Context, pairs, cands, mode: int = BF_OPENCV):
+    """bf_match_homography_multi with the correspondence stage behind it in the same round trip (omni_bf_match_homography_corr_multi).  pairs:
+    [(q_desc, t_desc, q_xy, t_xy, q_flags, q_3d [nq][3], t_norm [nt][2], dq_old (w, x, y, z)), ...]; cands: see _corr_cands.  -> (bf_match_homography_multi's
+    list, per candidate {n_corr, matched_dir_count, gate, X, u}, per pair {new_idx, old_idx})"""
+    P = len(pairs)
+    qs, ts = [_f32(x[0]) for x in pairs], [_f32(x[1]) for x in pairs]
+    qx, tx = [_f32(x[2]).reshape(-1, 2) for x in pairs], [_f32(x[3]).reshape(-1, 2) for x in pairs]
+    fl = [np.ascontiguousarray(x[4], np.uint8) for x in pairs]
+    q3, tn = [_f32(x[5]).reshape(-1, 3) for x in pairs], [_f32(x[6]).reshape(-1, 2) for x in pairs]
+    dq = np.ascontiguousarray([x[7] for x in pairs], np.float64).reshape(P, 4)
+    dim = next((a.shape[1] for a in qs + ts if a.ndim == 2 and a.shape[0]), 64)
+    nq, nt = np.array([q.shape[0] for q in qs], np.int32), np.array([t.shape[0] for t in ts], np.int32)
+    nf = np.array([f.shape[0] for f in fl], np.int32)
+    max_n = int(max(1, nq.max(), nt.max(), nf.max()))
+    cap = max(1, max(c[1] for c in cands) * max_n)
+    ptrs = lambda arrs: (_fp * P)(*[_pf(a) if a.shape[0] else None for a in arrs])
+    fp = (_vp * P)(*[f.ctypes.data if f.shape[0] else None for f in fl])
+    qi, ti, dd, n = np.zeros((P, max_n), np.int32), np.zeros((P, max_n), np.int32), np.zeros((P, max_n), np.float32), np.zeros(P, np.int32)
+    kept, nk, mask = np.zeros((P, max_n), np.int32), np.zeros(P, np.int32), np.zeros((P, max_n), np.uint8)
+    H, info, status = np.zeros((P, 9), np.float64), np.zeros((P, 4), np.int32), np.zeros(P, np.int32)
+    Cn = len(cands)
+    X, u = np.zeros((Cn, cap, 3), np.float32), np.zeros((Cn, cap, 2), np.float32)
+    n_corr, mdc, gate = (np.full(Cn, -1, np.int32) for _ in range(3))
+    new_idx, old_idx, npc = np.zeros((P, max_n), np.int32), np.zeros((P, max_n), np.int32), np.zeros(P, np.int32)
+    ip = lambda a: a.ctypes.data_as(_ip)
+    cd = _corr_cands(cands)
+    _check(lib().omni_bf_match_homography_corr_multi(ctx.h, P, ptrs(qs), ip(nq), ptrs(ts), ip(nt), dim, mode, max_n, ptrs(qx), ptrs(tx), fp, ip(nf), Cn, C.cast(cd, _vp), cap,
+                                                     ptrs(q3), ptrs(tn), dq.ctypes.data_as(C.POINTER(C.c_double)), ip(qi), ip(ti), _pf(dd), ip(n), ip(kept), ip(nk),
+                                                     mask.ctypes.data, H.ctypes.data_as(C.POINTER(C.c_double)), ip(info), ip(status), _pf(X), _pf(u), ip(n_corr), ip(mdc),
+                                                     ip(gate), ip(new_idx), ip(old_idx), ip(npc)))
+    hg = [{"q_idx": qi[p, :n[p]].copy(), "t_idx": ti[p, :n[p]].copy(), "dist": dd[p, :n[p]].copy(), "kept": kept[p, :nk[p]].copy(), "mask": mask[p, :nk[p]].copy(),
+           "H": H[p].copy(), "info": info[p].copy(), "status": int(status[p])} for p in range(P)]
+    return (hg,) + _corr_result(cands, P, n_corr, mdc, gate, X, u, new_idx, old_idx, npc)
 
 
 def bf_match_batched_dev(ctx: Context, n_pairs, max_n, dim, mode, q_dev, q_stride, nq_dev, t_dev, t_stride, nt_dev,

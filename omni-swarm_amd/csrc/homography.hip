@@ -13,11 +13,14 @@
 // Built with contraction off (Makefile; the header's pragma says the same): products and sums round one by one, as the host's.
 #include "common.h"
 #include "ransac_plan.h"
+#include "corr_plan.h"
 
 namespace omni {
 
 int bf_launch(omni_ctx* ctx, int n_pairs, int max_n, int dim, int mode, const float* q, int64_t qs, const int* nq, const float* t, int64_t ts, const int* nt, int* oq,
               int* ot, float* od, int* on);                  // bfmatch.hip
+
+int corr_launch(hipStream_t stream, const omni_corr_io& io);      // corr_assemble.hip
 
 #define HG_THREADS 256
 static_assert(rs::kRound <= HG_THREADS && rs::kRawChunk == HG_THREADS && rs::kRoundFirst <= rs::kRound, "one lane per hypothesis and per drawn number");
@@ -183,6 +186,12 @@ static int ransac_launch(omni_ctx* ctx, int n_pairs, int max_n, const float* src
 }
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// what omni_bf_match_homography_corr_multi adds to the round trip: the candidates, the gathers' sources and where the stage's outputs go (all host memory)
+struct CorrHost {
+    int n_cands; const omni_corr_cand* cands; int cap; const float* const* q_3d; const float* const* t_norm; const double* dq_old;
+    float *X, *u; int *n_corr, *matched_dir_count, *gate, *new_idx, *old_idx, *n_pair_corr;
+};
+
 }  // namespace omni
 
 extern "C" {
@@ -222,9 +231,12 @@ int omni_homography_ransac_multi(omni_ctx* ctx, int n_pairs, int max_n, const fl
     return OMNI_OK;
 }
 
-int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* const* q_host, const int* nq, const float* const* t_host, const int* nt, int dim, int mode,
+}  // extern "C"
+
+// the round trip of both entries; corr == nullptr: omni_bf_match_homography_multi's, to the byte
+static int bf_match_homography_run(omni_ctx* ctx, int n_pairs, const float* const* q_host, const int* nq, const float* const* t_host, const int* nt, int dim, int mode,
                                    int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags, int* q_idx, int* t_idx,
-                                   float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status) {
+                                   float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status, const omni::CorrHost* corr) {
     using namespace omni;
     OMNI_REQUIRE(ctx && q_host && t_host && nq && nt && q_xy && t_xy && q_flags && n_flags && q_idx && t_idx && dist && n_matches && kept && n_kept && mask && H && info && status,
                  OMNI_ERR_INVALID, "null argument");
@@ -244,12 +256,27 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
     const size_t P = (size_t)n_pairs, slab = (size_t)max_n * dim * 4, fq = up256(P * slab), f_xy = up256(P * max_n * 8), f_fl = up256(P * max_n), fo = up256(P * max_n * 4);
     const size_t off_t = fq, off_qxy = 2 * fq, off_txy = off_qxy + f_xy, off_fl = off_txy + f_xy, off_n = off_fl + f_fl, off_src = off_n + 768, off_dst = off_src + f_xy;
     const size_t off_oq = off_dst + f_xy, off_ot = off_oq + fo, off_od = off_ot + fo, off_kept = off_od + fo, off_on = off_kept + fo, off_nk = off_on + 256;
-    const size_t off_st = off_nk + 256, off_info = off_st + 256, off_H = off_info + 1024, off_mask = off_H + 64 * 72, total = off_mask + f_fl;
+    const size_t off_st = off_nk + 256, off_info = off_st + 256, off_H = off_info + 1024, off_mask = off_H + 64 * 72, hg_total = off_mask + f_fl;
+    // the correspondence stage behind it.  Down (behind mask, so that the one download takes it along): new_idx | old_idx [P][max_n] | n_corr | matched | gate |
+    // n_pair_corr [64] | X [C][cap][3] | u [C][cap][2].  Up (a second copy): cands [64] | dq_old [64][4] | q_3d [P][max_n][3] | t_norm [P][max_n][2]
+    const size_t C = corr ? (size_t)corr->n_cands : 0, cap = corr ? (size_t)corr->cap : 0, f_X = up256(C * cap * 12), f_u = up256(C * cap * 8), f_3d = up256(P * max_n * 12);
+    const size_t off_ni = hg_total, off_oi = off_ni + fo, off_nc = off_oi + fo, off_X = off_nc + 1024, off_u = off_X + f_X, down_end = corr ? off_u + f_u : hg_total;
+    const size_t off_cd = down_end, off_dq = off_cd + 64 * sizeof(omni_corr_cand), off_3d = off_dq + 64 * 32, off_tn = off_3d + f_3d;
+    const size_t total = corr ? off_tn + f_xy : hg_total;
     int rc;
     if ((rc = ensure_T(ctx, max_n))) return rc;
     if ((rc = ctx->scratch.ensure(total))) return rc;
     if ((rc = ctx->hstage.ensure(total))) return rc;
     char *d = ctx->scratch.as<char>(), *h = ctx->hstage.as<char>();
+    if (corr) {
+        memcpy(h + off_cd, corr->cands, C * sizeof(omni_corr_cand));
+        memcpy(h + off_dq, corr->dq_old, P * 32);
+        for (int p = 0; p < n_pairs; ++p) {
+            if (nq[p]) memcpy(h + off_3d + (size_t)p * max_n * 12, corr->q_3d[p], (size_t)nq[p] * 12);
+            if (nt[p]) memcpy(h + off_tn + (size_t)p * max_n * 8, corr->t_norm[p], (size_t)nt[p] * 8);
+        }
+        OMNI_HIP_TRY(hipMemcpyAsync(d + off_cd, h + off_cd, total - off_cd, hipMemcpyHostToDevice, ctx->stream));
+    }
     for (int p = 0; p < n_pairs; ++p) {
         if (nq[p]) { memcpy(h + (size_t)p * slab, q_host[p], (size_t)nq[p] * dim * 4); memcpy(h + off_qxy + (size_t)p * max_n * 8, q_xy[p], (size_t)nq[p] * 8); }
         if (nt[p]) { memcpy(h + off_t + (size_t)p * slab, t_host[p], (size_t)nt[p] * dim * 4); memcpy(h + off_txy + (size_t)p * max_n * 8, t_xy[p], (size_t)nt[p] * 8); }
@@ -257,7 +284,7 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
         ((int*)(h + off_n))[p] = nq[p]; ((int*)(h + off_n))[64 + p] = nt[p]; ((int*)(h + off_n))[128 + p] = n_flags[p];
     }
     OMNI_HIP_TRY(hipMemcpyAsync(d, h, off_src, hipMemcpyHostToDevice, ctx->stream));
-    OMNI_HIP_TRY(hipMemsetAsync(d + off_st, 0, total - off_st, ctx->stream));
+    OMNI_HIP_TRY(hipMemsetAsync(d + off_st, 0, down_end - off_st, ctx->stream));
     const int *nq_d = (const int*)(d + off_n), *nt_d = nq_d + 64, *nf_d = nq_d + 128;
     if ((rc = bf_launch(ctx, n_pairs, max_n, dim, mode, (const float*)d, (int64_t)max_n * dim, nq_d, (const float*)(d + off_t), (int64_t)max_n * dim, nt_d, (int*)(d + off_oq),
                         (int*)(d + off_ot), (float*)(d + off_od), (int*)(d + off_on))))
@@ -269,8 +296,35 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
     if ((rc = ransac_launch(ctx, n_pairs, max_n, (const float*)(d + off_src), (const float*)(d + off_dst), (const int*)(d + off_nk), (int*)(d + off_st), (uint8_t*)(d + off_mask),
                             (double*)(d + off_H), (int*)(d + off_info))))
         return rc;
-    OMNI_HIP_TRY(hipMemcpyAsync(h + off_oq, d + off_oq, total - off_oq, hipMemcpyDeviceToHost, ctx->stream));
+    if (corr) {
+        omni_corr_io io{};
+        io.n_cands = corr->n_cands; io.n_pairs = n_pairs; io.max_n = max_n; io.cap = corr->cap;
+        io.cands = (const omni_corr_cand*)(d + off_cd);
+        io.q_idx = (const int*)(d + off_oq); io.t_idx = (const int*)(d + off_ot); io.n_matches = (const int*)(d + off_on);
+        io.q_flags = (const uint8_t*)(d + off_fl); io.n_flags = nf_d; io.nq = nq_d; io.nt = nt_d;
+        io.mask = (const uint8_t*)(d + off_mask); io.hg_status = (const int*)(d + off_st);
+        io.q_3d = (const float*)(d + off_3d); io.t_norm = (const float*)(d + off_tn); io.dq_old = (const double*)(d + off_dq);
+        io.X = (float*)(d + off_X); io.u = (float*)(d + off_u);
+        io.n_corr = (int*)(d + off_nc); io.matched_dir_count = io.n_corr + 64; io.gate = io.n_corr + 128; io.n_pair_corr = io.n_corr + 192;
+        io.new_idx = (int*)(d + off_ni); io.old_idx = (int*)(d + off_oi);
+        if ((rc = corr_launch(ctx->stream, io))) return rc;
+    }
+    OMNI_HIP_TRY(hipMemcpyAsync(h + off_oq, d + off_oq, down_end - off_oq, hipMemcpyDeviceToHost, ctx->stream));
     OMNI_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (corr) {
+        const int* nc = (const int*)(h + off_nc);
+        memcpy(corr->n_corr, nc, C * 4); memcpy(corr->matched_dir_count, nc + 64, C * 4); memcpy(corr->gate, nc + 128, C * 4); memcpy(corr->n_pair_corr, nc + 192, P * 4);
+        for (size_t c = 0; c < C; ++c) {
+            const size_t n = (size_t)(nc[c] < 0 ? 0 : ((size_t)nc[c] > cap ? (int)cap : nc[c]));
+            memcpy(corr->X + c * cap * 3, h + off_X + c * cap * 12, n * 12);
+            memcpy(corr->u + c * cap * 2, h + off_u + c * cap * 8, n * 8);
+        }
+        for (int p = 0; p < n_pairs; ++p) {
+            const int k = nc[192 + p] < 0 ? 0 : (nc[192 + p] > max_n ? max_n : nc[192 + p]);
+            memcpy(corr->new_idx + (size_t)p * max_n, h + off_ni + (size_t)p * max_n * 4, (size_t)k * 4);
+            memcpy(corr->old_idx + (size_t)p * max_n, h + off_oi + (size_t)p * max_n * 4, (size_t)k * 4);
+        }
+    }
     memset(mask, 0, P * max_n);
     for (int p = 0; p < n_pairs; ++p) {
         const size_t row = (size_t)p * max_n;
@@ -286,6 +340,32 @@ int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* cons
     memcpy(info, h + off_info, P * 16);
     memcpy(H, h + off_H, P * 72);
     return OMNI_OK;
+}
+
+extern "C" {
+
+int omni_bf_match_homography_multi(omni_ctx* ctx, int n_pairs, const float* const* q_host, const int* nq, const float* const* t_host, const int* nt, int dim, int mode,
+                                   int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags, int* q_idx, int* t_idx,
+                                   float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status) {
+    return bf_match_homography_run(ctx, n_pairs, q_host, nq, t_host, nt, dim, mode, max_n, q_xy, t_xy, q_flags, n_flags, q_idx, t_idx, dist, n_matches, kept, n_kept, mask, H,
+                                   info, status, nullptr);
+}
+
+int omni_bf_match_homography_corr_multi(omni_ctx* ctx, int n_pairs, const float* const* q_host, const int* nq, const float* const* t_host, const int* nt, int dim,
+                                        int mode, int max_n, const float* const* q_xy, const float* const* t_xy, const uint8_t* const* q_flags, const int* n_flags,
+                                        int n_cands, const omni_corr_cand* cands, int cap, const float* const* q_3d, const float* const* t_norm, const double* dq_old,
+                                        int* q_idx, int* t_idx, float* dist, int* n_matches, int* kept, int* n_kept, uint8_t* mask, double* H, int* info, int* status,
+                                        float* X, float* u, int* n_corr, int* matched_dir_count, int* gate, int* new_idx, int* old_idx, int* n_pair_corr) {
+    using namespace omni;
+    OMNI_REQUIRE(cands && q_3d && t_norm && dq_old && X && u && n_corr && matched_dir_count && gate && new_idx && old_idx && n_pair_corr && nq && nt, OMNI_ERR_INVALID,
+                 "omni_bf_match_homography_corr_multi: null argument");
+    const char* why = n_pairs < 1 ? "n_pairs < 1" : corr::refusal(n_cands, n_pairs, max_n, cap, cands);
+    OMNI_REQUIRE(!why, OMNI_ERR_CAPACITY, "omni_bf_match_homography_corr_multi: %s (n_cands %d, n_pairs %d, max_n %d, cap %d)", why, n_cands, n_pairs, max_n, cap);
+    for (int p = 0; p < n_pairs && p < 64; ++p)
+        OMNI_REQUIRE((nq[p] <= 0 || q_3d[p]) && (nt[p] <= 0 || t_norm[p]), OMNI_ERR_INVALID, "omni_bf_match_homography_corr_multi: pair %d: null landmarks", p);
+    const CorrHost corr{n_cands, cands, cap, q_3d, t_norm, dq_old, X, u, n_corr, matched_dir_count, gate, new_idx, old_idx, n_pair_corr};
+    return bf_match_homography_run(ctx, n_pairs, q_host, nq, t_host, nt, dim, mode, max_n, q_xy, t_xy, q_flags, n_flags, q_idx, t_idx, dist, n_matches, kept, n_kept, mask, H,
+                                   info, status, &corr);
 }
 
 }  // extern "C"

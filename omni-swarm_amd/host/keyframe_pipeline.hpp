@@ -14,6 +14,7 @@
 #include <memory>
 #include <thread>
 
+#include "../csrc/corr_plan.h"
 #include "../csrc/stream_plan.h"
 #include "../csrc/wire_plan.h"
 #include "camera_model.hpp"
@@ -116,6 +117,13 @@ public:
         // poll() and flush() begin a batch of remote frames alone.  Candidates, edges, counters and rows are the serial flow's.  The sharded database, which builds
         // no messages, refuses it.  (set_remote_in_stream: before the first key frame.)
         bool remote_in_stream = false;
+        // `geometry`: inter-drone loop candidates are verified with their batch.  Off (the default): a candidate between a frame of another drone and a frame of
+        // this one is verified on the spot -- its own matcher + homography round trip, its own PnP on one pool thread -- because the detector reads the verdict for
+        // the init-mode counters.  On: such a candidate is deferred like one between two frames of this drone, and everything deferred is verified in ONE round trip
+        // when the detector's batch ends -- or earlier, in front of a remote frame whose mode depends on a pending verdict (host/verify_plan.hpp; only around the
+        // crossing of inter_drone_init_frames).  Candidates, edges and their ids, counters and rows are the switch-off flow's.  Independent of remote_in_stream; the
+        // sharded database, which builds no messages, refuses it.  (set_batch_verify: between two calls, while no detector batch is pending.)
+        bool batch_verify = false;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -287,9 +295,44 @@ private:
                 collect_geometry();
                 return edges_.size() > before;
             };
+            if (c.batch_verify) apply_batch_verify(true);
         }
     }
+    // Config::batch_verify: the detector's late-verdict hooks.  A ticket is a place in deferred_; a resolve is one start_geometry + drain_geometry over everything
+    // deferred so far -- the candidates between two frames of this drone that came before included, so the edge order is the candidate order
+    void apply_batch_verify(bool on) {
+        if (!on) { det_.defer_loop = nullptr; det_.resolve_loops = nullptr; return; }
+        det_.defer_loop = [this](const FisheyeFrameDescriptor& a, const FisheyeFrameDescriptor& b, int da, int db, bool im) {
+            ++geometry_calls_;
+            deferred_.push_back({&a, &b, da, db, im, true});
+            return verify_deferred_++;
+        };
+        det_.resolve_loops = [this] {
+            drain_geometry();                                       // what earlier batches left running comes first
+            verdicts_.clear();
+            const int64_t before = matcher_round_trips_;
+            start_geometry(nullptr);
+            drain_geometry();
+            verify_round_trips_ += matcher_round_trips_ - before;
+            return std::move(verdicts_);
+        };
+    }
 public:
+    bool batch_verify() const { return cfg_.batch_verify; }
+    // between two calls, while no detector batch is pending (what the C entry point omni_pipeline_set_batch_verify sets)
+    void set_batch_verify(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (on && shard_) throw std::runtime_error("set_batch_verify: the sharded database builds no messages");
+        if (on && !cfg_.geometry) throw std::runtime_error("set_batch_verify: the pipeline has no geometry stage");
+        if (det_pending_.active || !deferred_.empty()) throw std::runtime_error("set_batch_verify: a detector batch is pending (flush first)");
+        cfg_.batch_verify = on;
+        apply_batch_verify(on);
+    }
+    // [0] inter-drone candidates deferred, [1] resolves at the end of a detector batch (a frame outside a batch is a batch of one), [2] early resolves forced by
+    // the rule, [3] matcher round trips spent on [1] and [2]
+    // candidates whose correspondences the round trip assembled so far, and candidates it handed back to the host functions
+    void corr_stats(int64_t out[2]) const { out[0] = corr_candidates_device_; out[1] = corr_candidates_host_; }
+    void verify_stats(int64_t out[4]) const { out[0] = verify_deferred_; out[1] = det_.end_resolves; out[2] = det_.early_resolves; out[3] = verify_round_trips_; }
     // The geometry of every deferred candidate: (1) ONE GPU round trip matches the direction pairs of all of them (compute_correspond_features
     // pairs up to four directions per candidate, loop_detector.cpp:431-537; the matcher is a pure function of its two descriptor sets);
     // (2) one task per candidate on the pool: flag filter, homography-RANSAC masks, PnP-RANSAC + refit, verification (f64), its match() calls
@@ -307,6 +350,7 @@ public:
                     geo_.number_edge(r.second); edges_.push_back(r.second);
                     if (fi < gb.self_self.size() && gb.self_self[fi]) det_.inter_drone_loop_count[{cfg_.self_id, cfg_.self_id}] += 2;      // what the detector would have counted (:826-827, both orders)
                 }
+                if (fi < gb.verdict.size() && gb.verdict[fi]) verdicts_.push_back(r.first ? 1 : 0);      // batch_verify: the detector's ticket, in candidate order
             }
             if (gb.timed) latencies_ms_.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - gb.t_enqueue).count());
             geo_inflight_.pop_front();
@@ -324,6 +368,13 @@ public:
         std::vector<int> pair_dim;                                   // descriptor length of every pair (one match_multi call per distinct length)
         std::vector<Prepared> prep(deferred_.size());
         const int nd = geo_.MAX_DIRS;
+        // batch_verify with device_homography: the correspondences of every candidate the entry takes are assembled behind the homography masks in the same round
+        // trip (BFMatcherL2X::match_homography_corr_multi, csrc/corr_assemble.hip), and its task starts at compute_relative_pose.  A candidate with a pair that was
+        // not listed (malformed descriptors, an image without key points), with pairs of different descriptor lengths, with more points than the entry takes or
+        // with landmark arrays shorter than its key points goes through the path above
+        const bool corr_on = cfg_.batch_verify && dev_hg;
+        std::vector<char> corr_ok(deferred_.size(), 0);
+        std::vector<BFMatcherL2X::PairC> pairs_c;                    // corr_on: pairs_h with the gathers' sources (same positions)
         for (size_t ci = 0; ci < deferred_.size(); ++ci) {
             const FisheyeFrameDescriptor &a = *deferred_[ci].a, &b = *deferred_[ci].b;
             const int da = deferred_[ci].da, db = deferred_[ci].db;
@@ -344,22 +395,76 @@ public:
                 }
             }
             prep[ci].count = pairs.size() - prep[ci].first;
+            if (corr_on) {
+                int wanted = 0;
+                bool ok = da >= 0 && db >= 0 && da < (int)a.images.size() && db < (int)b.images.size();
+                const geom::Quat main_quat_old = ok ? to_pose(b.images[db].camera_extrinsic).att : geom::Quat{};
+                size_t at = prep[ci].first;
+                for (int s = 0; s < nd; ++s) {
+                    int dn, dold;
+                    corr::pair_dirs(da, db, nd, s, &dn, &dold);
+                    if (!(dn < (int)a.images.size() && dold < (int)b.images.size() && b.images[dold].landmark_num > 0 && a.images[dn].landmark_num > 0)) continue;
+                    ++wanted;
+                    const ImageDescriptor &x = a.images[dn], &y = b.images[dold];
+                    // (the pairs were listed above in this order: the pair at `at` is this one, or one is missing and the candidate is not served)
+                    if (!ok || at >= prep[ci].first + prep[ci].count || pairs[at].query != x.feature_descriptor.data() || pairs[at].train != y.feature_descriptor.data() ||
+                        pair_dim[at] != pair_dim[prep[ci].first] || pairs[at].nq > BFMatcherL2X::kMaxPoints || pairs[at].nt > BFMatcherL2X::kMaxPoints ||
+                        (int)x.landmarks_3d.size() < pairs[at].nq || (int)x.landmarks_2d_norm.size() < pairs[at].nq || (int)y.landmarks_2d_norm.size() < pairs[at].nt) { ok = false; continue; }
+                    const geom::Quat dq = main_quat_old.inverse() * to_pose(y.camera_extrinsic).att;
+                    pairs_c.resize(pairs.size());
+                    pairs_c[at] = {pairs_h[at], &x.landmarks_3d[0].x, &y.landmarks_2d_norm[0].x, {dq.w, dq.x, dq.y, dq.z}};
+                    ++at;
+                }
+                corr_ok[ci] = ok && wanted >= 1 && wanted <= corr::kMaxPairs && (size_t)wanted == prep[ci].count;
+            }
         }
+        pairs_c.resize(pairs.size());
         std::vector<std::vector<DMatch>> outs(pairs.size());
         std::vector<BFMatcherL2X::Homography> hgs(dev_hg ? pairs.size() : 0);
+        std::vector<std::shared_ptr<BFMatcherL2X::Corr>> corrs(deferred_.size());
         {
             std::vector<char> done(pairs.size(), 0);
+            for (size_t c0 = 0; corr_on && c0 < deferred_.size();) {          // whole candidates, one descriptor length, at most 64 pairs and 64 candidates per round trip
+                if (!corr_ok[c0]) { ++c0; continue; }
+                const int dim = pair_dim[prep[c0].first];
+                std::vector<BFMatcherL2X::PairC> sub;
+                std::vector<BFMatcherL2X::CandC> cands;
+                std::vector<size_t> which;
+                size_t c1 = c0;
+                for (; c1 < deferred_.size() && cands.size() < (size_t)corr::kMaxCall; ++c1) {
+                    if (!corr_ok[c1] || pair_dim[prep[c1].first] != dim) continue;
+                    if (sub.size() + prep[c1].count > (size_t)corr::kMaxCall) break;
+                    cands.push_back({(int)sub.size(), (int)prep[c1].count, geo_.MIN_MATCH_PRE_DIR, geo_.MIN_DIRECTION_LOOP, geo_.MIN_LOOP_NUM, geo_.INIT_MODE_MIN_LOOP_NUM, deferred_[c1].im});
+                    for (size_t j = 0; j < prep[c1].count; ++j) sub.push_back(pairs_c[prep[c1].first + j]);
+                    which.push_back(c1);
+                    corr_ok[c1] = 0;                                          // (taken)
+                }
+                std::vector<std::vector<DMatch>> so;
+                std::vector<BFMatcherL2X::Homography> sh;
+                std::vector<BFMatcherL2X::Corr> sc;
+                bf_.match_homography_corr_multi(sub, cands, dim, so, sh, sc);
+                ++matcher_round_trips_;
+                for (size_t k = 0; k < which.size(); ++k) {
+                    const size_t ci = which[k];
+                    for (size_t j = 0; j < prep[ci].count; ++j) {
+                        const size_t p = prep[ci].first + j;
+                        outs[p] = std::move(so[(size_t)cands[k].pair_first + j]); hgs[p] = std::move(sh[(size_t)cands[k].pair_first + j]); done[p] = 1;
+                    }
+                    corrs[ci] = std::make_shared<BFMatcherL2X::Corr>(std::move(sc[k]));
+                }
+            }
             for (size_t p0 = 0; p0 < pairs.size(); ++p0) {
                 if (done[p0]) continue;
                 std::vector<BFMatcherL2X::Pair> sub;
                 std::vector<BFMatcherL2X::PairH> sub_h;
                 std::vector<size_t> where;
                 for (size_t p = p0; p < pairs.size(); ++p)
-                    if (!done[p] && pair_dim[p] == pair_dim[p0]) { sub.push_back(pairs[p]); if (dev_hg) sub_h.push_back(pairs_h[p]); where.push_back(p); done[p] = 1; }
+                    if (!done[p] && pair_dim[p] == pair_dim[p0] && sub.size() < 64) { sub.push_back(pairs[p]); if (dev_hg) sub_h.push_back(pairs_h[p]); where.push_back(p); done[p] = 1; }
                 std::vector<std::vector<DMatch>> so;
                 std::vector<BFMatcherL2X::Homography> sh;
                 if (dev_hg) bf_.match_homography_multi(sub_h, pair_dim[p0], so, sh);
                 else bf_.match_multi(sub, pair_dim[p0], so);
+                ++matcher_round_trips_;
                 for (size_t j = 0; j < where.size(); ++j) { outs[where[j]] = std::move(so[j]); if (dev_hg) hgs[where[j]] = std::move(sh[j]); }
             }
         }
@@ -376,8 +481,30 @@ public:
             auto mine_h = std::make_shared<std::vector<BFMatcherL2X::Homography>>();
             for (size_t j = 0; j < prep[ci].count; ++j) { mine_o->push_back(std::move(outs[prep[ci].first + j])); if (dev_hg) mine_h->push_back(std::move(hgs[prep[ci].first + j])); }
             const Deferred c = deferred_[ci];
-            auto work = [this, g0 = geo_, mine_p, mine_o, mine_d, mine_h, c, dev_pnp]() -> Result {    // g0: the parameters, copied on this thread
+            const std::shared_ptr<BFMatcherL2X::Corr> mine_c = corrs[ci] && corrs[ci]->gate != OMNI_CORR_HOST ? corrs[ci] : nullptr;
+            if (corrs[ci]) ++(mine_c ? corr_candidates_device_ : corr_candidates_host_);
+            auto work = [this, g0 = geo_, mine_p, mine_o, mine_d, mine_h, mine_c, c, dev_pnp]() -> Result {    // g0: the parameters, copied on this thread
                 LoopGeometry g = g0;
+                if (mine_c)                                            // the candidate's correspondences from the round trip above: the task starts at compute_relative_pose
+                    g.correspondences = [&](const FisheyeFrameDescriptor& nw, const FisheyeFrameDescriptor& old, int main_dir_new, int main_dir_old,
+                                            LoopGeometry::Correspondence& cr) {
+                        for (int s = 0; s < g.MAX_DIRS; ++s) {
+                            int dn, dold;
+                            corr::pair_dirs(main_dir_new, main_dir_old, g.MAX_DIRS, s, &dn, &dold);
+                            if (dn < (int)nw.images.size() && dold < (int)old.images.size() && old.images[dold].landmark_num > 0 && nw.images[dn].landmark_num > 0) {
+                                cr.dirs_new.push_back(dn); cr.dirs_old.push_back(dold);
+                            }
+                        }
+                        if (cr.dirs_new.size() != mine_c->new_idx.size()) return -1;
+                        cr.new_idx = mine_c->new_idx; cr.old_idx = mine_c->old_idx;
+                        for (int i = 0; i < mine_c->n_corr; ++i) {
+                            cr.new_3d.push_back({mine_c->X[3 * i], mine_c->X[3 * i + 1], mine_c->X[3 * i + 2]});
+                            cr.old_norm_2d.push_back({mine_c->u[2 * i], mine_c->u[2 * i + 1]});
+                        }
+                        for (const BFMatcherL2X::Homography& h : *mine_h)      // what homography_mask would have counted, pair by pair
+                            if (h.status == OMNI_HG_OK || h.status == OMNI_HG_NO_MODEL) ++homography_pairs_device_;
+                        return mine_c->gate == OMNI_CORR_OK ? 1 : 0;
+                    };
                 if (dev_pnp)                                           // the candidate's PnP RANSAC on the device, from this thread; what it hands back runs on the host
                     g.pnp_ransac = [this, dev_pnp](const std::vector<geom::Vec3>& X, const std::vector<geom::Vec2>& u, int iterations, std::vector<uint8_t>& mask, geom::Rt& best) {
                         const size_t n = X.size();
@@ -421,6 +548,7 @@ public:
                 return r;
             };
             gb.self_self.push_back(c.a->drone_id == cfg_.self_id && c.b->drone_id == cfg_.self_id);
+            gb.verdict.push_back(c.verdict);
             if (pool_) futs.push_back(pool_->submit(work));
             else { std::promise<Result> pr; pr.set_value(work()); futs.push_back(pr.get_future()); }
         }
@@ -878,6 +1006,7 @@ public:
         if (cfg_.fit_pca) throw std::runtime_error("attach_shard: fit_pca does not run on the sharded database, which builds no descriptors of its own");
         if (cfg_.wire) throw std::runtime_error("attach_shard: the wire does not run on the sharded database, which builds no messages");
         if (cfg_.remote_in_stream) throw std::runtime_error("attach_shard: remote_in_stream does not run on the sharded database, which builds no messages");
+        if (cfg_.batch_verify) throw std::runtime_error("attach_shard: batch_verify does not run on the sharded database, which builds no messages");
         if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
@@ -1492,6 +1621,7 @@ private:
     struct GeoBatch {                           // the geometry tasks of one micro-batch, in candidate order
         std::vector<std::future<std::pair<bool, LoopEdge>>> futs;
         std::vector<char> self_self;            // per task: a candidate between two frames of the self drone (the detector did not get its verdict)
+        std::vector<char> verdict;              // per task: batch_verify's inter-drone candidate, whose verdict the detector's ticket waits for
         std::vector<FisheyeFrameDescriptor> held;
         std::chrono::steady_clock::time_point t_enqueue;
         bool timed = false;
@@ -1503,6 +1633,7 @@ private:
     bool async_geometry_ = [] { int v = 1; check(omni_config_value("OMNI_GEOMETRY_ASYNC", &v), "omni_config_value"); return v != 0; }();
     std::atomic<int> homography_pairs_device_{0}, homography_pairs_host_{0};      // (counted by the geometry tasks; declared before the pool: outlive its threads)
     std::atomic<int> pnp_candidates_device_{0}, pnp_candidates_host_{0};
+    int corr_candidates_device_ = 0, corr_candidates_host_ = 0;      // batch_verify: candidates whose correspondences came from the GPU / that the device handed back
     // device_pnp: a context (stream, staging, mutex) of its own -- the geometry tasks block on it for the length of a candidate's RANSAC, and neither the unit
     // enqueues, the detector step nor the matcher round trip of the host thread (the lanes' contexts, index_ctx_) ever wait for that mutex.  Made when the
     // switch is first on, kept until the pipeline goes (declared before the pool: outlives its threads)
@@ -1513,7 +1644,9 @@ private:
     std::unique_ptr<TaskPool> msg_pool_ = [] { const int n = cfg_int("OMNI_MESSAGE_THREADS"); return n > 0 ? std::make_unique<TaskPool>(n) : nullptr; }();
     std::vector<ImageDescriptor> downs_;        // the down-camera halves of the micro-batch being finished
     std::vector<std::future<void>> stereo_tasks_;
-    struct Deferred { const FisheyeFrameDescriptor *a, *b; int da, db; bool im; };
+    struct Deferred { const FisheyeFrameDescriptor *a, *b; int da, db; bool im; bool verdict = false; };
+    std::vector<char> verdicts_;                // batch_verify: the verdicts drain_geometry() collected for the resolve that is running
+    int64_t verify_deferred_ = 0, verify_round_trips_ = 0, matcher_round_trips_ = 0;
     std::vector<Deferred> deferred_;            // candidates waiting for collect_geometry(): references into the database / the current micro-batch
     std::vector<LoopEdge> edges_;
     std::vector<Candidate> candidates_;

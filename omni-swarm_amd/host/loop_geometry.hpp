@@ -177,6 +177,13 @@ public:
         std::vector<int> dirs_new, dirs_old;
     };
 
+    // optional: the whole of the frame pair's compute_correspond_features computed elsewhere (the GPU, behind the homography masks in the matcher's round trip:
+    // BFMatcherL2X::match_homography_corr_multi, csrc/corr_assemble.hip -- the same numbers, bit for bit).  It fills what compute_relative_pose reads -- c.new_3d,
+    // c.old_norm_2d -- and c.new_idx, c.old_idx, c.dirs_new, c.dirs_old, and returns 1 (the function's `true`), 0 (its `false`) or -1: a candidate it cannot serve,
+    // which runs the host functions here, like an unset hook.  c.new_norm_2d and c.old_3d, which nothing behind the size gate reads, stay empty: the gate takes
+    // c.new_3d's size, which is theirs.
+    std::function<int(const FisheyeFrameDescriptor& nw, const FisheyeFrameDescriptor& old, int main_dir_new, int main_dir_old, Correspondence& c)> correspondences;
+
     // :539-624 (the USE_FUNDMENTAL branch, loop_detector.cpp:8).  Returns false when fewer than 4 flagged matches exist -- the vectors then
     // keep the unfiltered matches, and the caller (like the reference's) uses them regardless of the return value.
     bool compute_correspond_features(const ImageDescriptor& nw, const ImageDescriptor& old, std::vector<geom::Vec2>& new_norm_2d, std::vector<geom::Vec3>& new_3d,
@@ -284,11 +291,14 @@ public:
                            Correspondence* out_corr = nullptr) const {
         if (nw.landmark_num < MIN_LOOP_NUM) return false;
         Correspondence c;
-        bool success = compute_correspond_features(nw, old, main_dir_new, main_dir_old, c);
+        const int served = correspondences ? correspondences(nw, old, main_dir_new, main_dir_old, c) : -1;
+        if (served < 0) c = Correspondence();
+        bool success = served >= 0 ? served != 0 : compute_correspond_features(nw, old, main_dir_new, main_dir_old, c);
         geom::Pose DP_old_to_new;
         int inlier_num = 0;
         if (success) {
-            if ((int)c.new_norm_2d.size() > MIN_LOOP_NUM || (init_mode && (int)c.new_norm_2d.size() > INIT_MODE_MIN_LOOP_NUM))
+            const int n_corr = (int)(served >= 0 ? c.new_3d.size() : c.new_norm_2d.size());
+            if (n_corr > MIN_LOOP_NUM || (init_mode && n_corr > INIT_MODE_MIN_LOOP_NUM))
                 success = compute_relative_pose(c.new_3d, c.old_norm_2d, to_pose(old.images[main_dir_old].camera_extrinsic), to_pose(nw.pose_drone),
                                                 to_pose(old.pose_drone), DP_old_to_new, init_mode, inlier_num) != 0;
             else success = false;

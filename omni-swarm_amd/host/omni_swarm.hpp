@@ -29,6 +29,7 @@
 
 #include "../../include/omni_hip.h"
 #include "../csrc/rows_plan.h"
+#include "verify_plan.hpp"
 #ifdef OMNI_WITH_OPENCV
 #include <opencv2/opencv.hpp>
 #endif
@@ -595,6 +596,67 @@ public:
             std::copy(H.begin() + p * 9, H.begin() + p * 9 + 9, hg[p].H); std::copy(info.begin() + p * 4, info.begin() + p * 4 + 4, hg[p].info);
         }
     }
+    // match_homography_multi followed, in the same GPU round trip, by the correspondences of the candidates the pairs belong to (omni_bf_match_homography_corr_multi,
+    // csrc/corr_assemble.hip; the arithmetic: csrc/corr_plan.h): per pair also the new image's landmarks_3d ([nq][3] floats), the old image's landmarks_2d_norm
+    // ([nt][2]) and dq_old (w, x, y, z); per candidate its consecutive pairs, in pairing order, and the gates' parameters.  corr[c]: the gate (OMNI_CORR_*), X [n][3]
+    // and u [n][2] as omni_pnp_ransac_multi takes them, and the key-point indices of every pair's correspondences.  At most 64 pairs and 64 candidates per call,
+    // at most 4 pairs per candidate, at most kMaxPoints key points per image.
+    static constexpr int kMaxPoints = 1024;
+    struct PairC { PairH h; const float* q_3d; const float* t_norm; double dq_old[4]; };
+    struct CandC { int pair_first, pair_count, min_match_pre_dir, min_direction_loop, min_loop_num, init_mode_min_loop_num; bool init_mode; };
+    struct Corr { int gate = OMNI_CORR_HOST, n_corr = 0, matched_dir_count = 0; std::vector<float> X, u; std::vector<std::vector<int>> new_idx, old_idx; };
+    void match_homography_corr_multi(const std::vector<PairC>& pairs, const std::vector<CandC>& cands, int dim, std::vector<std::vector<DMatch>>& out,
+                                     std::vector<Homography>& hg, std::vector<Corr>& corr) {
+        out.assign(pairs.size(), {}); hg.assign(pairs.size(), {}); corr.assign(cands.size(), {});
+        if (pairs.empty() || cands.empty()) return;
+        const size_t P = pairs.size(), C = cands.size();
+        int max_n = 1, max_pairs = 1;
+        std::vector<const float*> q(P), t(P), qx(P), tx(P), q3(P), tn(P);
+        std::vector<const uint8_t*> fl(P);
+        std::vector<int> nq(P), nt(P), nf(P), n(P), nk(P), status(P), info(P * 4), npc(P);
+        std::vector<double> dq(P * 4);
+        for (size_t p = 0; p < P; ++p) {
+            const PairH& h = pairs[p].h;
+            q[p] = h.query; t[p] = h.train; nq[p] = h.nq; nt[p] = h.nt; qx[p] = h.q_xy; tx[p] = h.t_xy; fl[p] = h.q_flags; nf[p] = h.n_flags;
+            q3[p] = pairs[p].q_3d; tn[p] = pairs[p].t_norm;
+            std::copy(pairs[p].dq_old, pairs[p].dq_old + 4, dq.begin() + p * 4);
+            max_n = std::max(max_n, std::max(std::max(nq[p], nt[p]), nf[p]));
+        }
+        std::vector<omni_corr_cand> cd(C);
+        for (size_t c = 0; c < C; ++c) {
+            cd[c] = {cands[c].pair_first, cands[c].pair_count, cands[c].min_match_pre_dir, cands[c].min_direction_loop, cands[c].min_loop_num, cands[c].init_mode_min_loop_num,
+                     cands[c].init_mode ? 1 : 0, 0};
+            max_pairs = std::max(max_pairs, cands[c].pair_count);
+        }
+        const size_t cap = (size_t)max_pairs * max_n;
+        std::vector<int> qi(P * max_n), ti(P * max_n), kept(P * max_n), ni(P * max_n), oi(P * max_n), n_corr(C), mdc(C), gate(C);
+        std::vector<float> dd(P * max_n), X(C * cap * 3), u(C * cap * 2);
+        std::vector<uint8_t> mask(P * max_n);
+        std::vector<double> H(P * 9);
+        check(omni_bf_match_homography_corr_multi(ctx_.get(), (int)P, q.data(), nq.data(), t.data(), nt.data(), dim, mode_, max_n, qx.data(), tx.data(), fl.data(), nf.data(),
+                                                  (int)C, cd.data(), (int)cap, q3.data(), tn.data(), dq.data(), qi.data(), ti.data(), dd.data(), n.data(), kept.data(), nk.data(),
+                                                  mask.data(), H.data(), info.data(), status.data(), X.data(), u.data(), n_corr.data(), mdc.data(), gate.data(), ni.data(),
+                                                  oi.data(), npc.data()),
+              "BFMatcherL2X::match_homography_corr_multi");
+        for (size_t p = 0; p < P; ++p) {
+            for (int i = 0; i < n[p]; ++i) out[p].push_back({qi[p * max_n + i], ti[p * max_n + i], dd[p * max_n + i]});
+            hg[p].status = status[p];
+            hg[p].kept.assign(kept.begin() + p * max_n, kept.begin() + p * max_n + nk[p]);
+            hg[p].mask.assign(mask.begin() + p * max_n, mask.begin() + p * max_n + nk[p]);
+            std::copy(H.begin() + p * 9, H.begin() + p * 9 + 9, hg[p].H); std::copy(info.begin() + p * 4, info.begin() + p * 4 + 4, hg[p].info);
+        }
+        for (size_t c = 0; c < C; ++c) {
+            Corr& r = corr[c];
+            r.gate = gate[c]; r.n_corr = n_corr[c]; r.matched_dir_count = mdc[c];
+            r.X.assign(X.begin() + c * cap * 3, X.begin() + c * cap * 3 + (size_t)n_corr[c] * 3);
+            r.u.assign(u.begin() + c * cap * 2, u.begin() + c * cap * 2 + (size_t)n_corr[c] * 2);
+            for (int j = 0; j < cands[c].pair_count; ++j) {
+                const size_t p = (size_t)(cands[c].pair_first + j);
+                r.new_idx.emplace_back(ni.begin() + p * max_n, ni.begin() + p * max_n + npc[p]);
+                r.old_idx.emplace_back(oi.begin() + p * max_n, oi.begin() + p * max_n + npc[p]);
+            }
+        }
+    }
 #ifdef OMNI_WITH_OPENCV
     void match(const cv::Mat& query, const cv::Mat& train, std::vector<cv::DMatch>& matches) {
         std::vector<DMatch> m;
@@ -683,6 +745,15 @@ public:
     bool stereo_fisheye = true;
     // geometry stage (compute_loop, :627-836) stays on the host: (new, old, dir_new, dir_old, init_mode) -> success
     std::function<bool(const FisheyeFrameDescriptor&, const FisheyeFrameDescriptor&, int, int, bool)> compute_loop;
+    // Late verdicts (host/verify_plan.hpp).  With BOTH hooks set a candidate between a frame of another drone and a frame of the self drone is not verified on the
+    // spot: defer_loop takes compute_loop's arguments and returns a ticket; resolve_loops verifies everything deferred since the last call and returns one verdict
+    // per ticket, in ticket order.  The detector resolves when the mode of a remote frame depends on a pending verdict (verify_rule), and before end_images_batch /
+    // on_image_recv return, and applies the verdicts in candidate order: LoopCandidate::loop and the counters are the serial flow's.  A candidate between two
+    // frames of the self drone still goes to compute_loop.  Unset (the default): compute_loop for every candidate, as before.
+    std::function<int64_t(const FisheyeFrameDescriptor&, const FisheyeFrameDescriptor&, int, int, bool)> defer_loop;
+    std::function<std::vector<char>()> resolve_loops;
+    // resolves forced in front of a remote frame by verify_rule / resolves when a batch (or a single frame) ended with tickets pending
+    int64_t early_resolves = 0, end_resolves = 0;
 
     LoopDetectorCore(Context& ctx, int self_id, int storage = OMNI_STORE_F32)
         : self_id(self_id), local_index(ctx, 4096, storage), remote_index(ctx, 4096, storage), ctx_(ctx) {}
@@ -974,11 +1045,17 @@ public:
         // replay the decision rules frame by frame on the fetched results
         replaying_ = true; sim_local_ = pb_.start_local; sim_remote_ = pb_.start_remote; next_deferred_ = next_row_id_ = 0;
         std::vector<LoopCandidate> out;
+        out.reserve(frames.size());                              // (tickets point at the candidates they will decide)
         std::vector<FisheyeFrameDescriptor>* movable = pb_.movable ? &pb_.owned : nullptr;
         try {
-            for (size_t fi = 0; fi < frames.size(); ++fi) { move_src_ = movable ? &(*movable)[fi] : nullptr; out.push_back(on_image_recv(frames[fi])); }
+            for (size_t fi = 0; fi < frames.size(); ++fi) {
+                move_src_ = movable ? &(*movable)[fi] : nullptr;
+                out.emplace_back();
+                on_image_recv_into(frames[fi], out.back());
+            }
             move_src_ = nullptr;
-        } catch (...) { replaying_ = false; move_src_ = nullptr; throw; }
+            if (!tickets_.empty()) { ++end_resolves; resolve_tickets(); }
+        } catch (...) { replaying_ = false; move_src_ = nullptr; tickets_.clear(); verify_pending_.resolved(); throw; }
         replaying_ = false;
         if (next_deferred_ != deferred_.size() || next_row_id_ != row_ids_.size()) throw std::logic_error("on_images_recv_batch: plan and replay diverged");
         return out;
@@ -987,17 +1064,35 @@ public:
     LoopCandidate on_image_recv(const FisheyeFrameDescriptor& f_in) {            // :11-137
         if (!replaying_ && malformed(f_in)) { FisheyeFrameDescriptor c = f_in; sanitise(c); return on_image_recv(c); }
         LoopCandidate r;
-        if (f_in.images.empty()) return r;
+        if (replaying_ || !late_verdicts()) { on_image_recv_into(f_in, r); return r; }
+        // a batch of one: what the frame deferred is resolved before it returns
+        try {
+            on_image_recv_into(f_in, r);
+            if (!tickets_.empty()) { ++end_resolves; resolve_tickets(); }
+        } catch (...) { tickets_.clear(); verify_pending_.resolved(); throw; }
+        return r;
+    }
+    bool late_verdicts() const { return defer_loop && resolve_loops; }
+
+private:
+    void on_image_recv_into(const FisheyeFrameDescriptor& f_in, LoopCandidate& r) {
+        if (f_in.images.empty()) return;
         const int drone_id = f_in.drone_id;
-        if (drone_id != self_id && database_size() == 0) return r;                // :36-38
+        if (drone_id != self_id && database_size() == 0) return;                  // :36-38
         const bool new_node = all_nodes.find(drone_id) == all_nodes.end();
         all_nodes.insert(drone_id);
         int dir_count = 0;
         for (auto& img : f_in.images) if (img.landmark_num > 0) ++dir_count;
-        if (dir_count < MIN_DIRECTION_LOOP) return r;                             // :60-63
-        if (f_in.landmark_num < MIN_LOOP_NUM) return r;                           // :65
+        if (dir_count < MIN_DIRECTION_LOOP) return;                               // :60-63
+        if (f_in.landmark_num < MIN_LOOP_NUM) return;                             // :65
         bool init_mode = false;
-        if (drone_id != self_id) init_mode = inter_drone_loop_count[{drone_id, self_id}] < inter_drone_init_frames;   // :67-72
+        if (drone_id != self_id) {
+            if (late_verdicts() && verify_rule(inter_drone_loop_count[{drone_id, self_id}], verify_pending_.of(drone_id), inter_drone_init_frames) == VerifyRule::RESOLVE) {
+                ++early_resolves;                                                 // the mode depends on a pending verdict: resolve, then read the counter
+                resolve_tickets();
+            }
+            init_mode = inter_drone_loop_count[{drone_id, self_id}] < inter_drone_init_frames;   // :67-72
+        }
         const bool nonkeyframe = f_in.prevent_adding_db;
         const FisheyeFrameDescriptor* fp = &f_in;          // re-pointed to the database's copy: the frame may have been MOVED into it
         if (!nonkeyframe || new_node) { fp = add_to_database(f_in); r.added = true; }                               // :89-94
@@ -1010,6 +1105,14 @@ public:
             if (direction_old >= 0 && old) {
                 r.found = true; r.old_msg_id = old->msg_id; r.image_id = image_id; r.direction_new = direction_new; r.direction_old = direction_old; r.distance = distance;
                 bool success = false;
+                if (late_verdicts() && f.drone_id != old->drone_id && (f.drone_id == self_id || old->drone_id == self_id)) {
+                    // an inter-drone candidate: the verdict comes with resolve_tickets(), which counts it and sets r.loop
+                    const bool swap = old->drone_id != self_id;
+                    const int64_t ticket = swap ? defer_loop(*old, f, direction_old, direction_new, init_mode) : defer_loop(f, *old, direction_new, direction_old, init_mode);
+                    tickets_.push_back({ticket, f.drone_id, old->drone_id, &r});
+                    verify_pending_.defer(swap ? old->drone_id : f.drone_id);
+                    return;
+                }
                 if (old->drone_id == self_id) success = compute_loop && compute_loop(f, *old, direction_new, direction_old, init_mode);       // :110-111
                 else if (f.drone_id == self_id) success = compute_loop && compute_loop(*old, f, direction_old, direction_new, init_mode);    // :114-115
                 if (success) {                                                                                                                // :826-827
@@ -1019,8 +1122,24 @@ public:
                 }
             }
         }
-        return r;
     }
+    // the verdicts of everything deferred, applied in candidate order (:826-827)
+    struct Ticket { int64_t id; int drone_new, drone_old; LoopCandidate* cand; };
+    std::vector<Ticket> tickets_;
+    VerifyPending verify_pending_;
+    void resolve_tickets() {
+        const std::vector<char> verdicts = resolve_loops();
+        if (verdicts.size() != tickets_.size()) throw std::logic_error("resolve_loops: " + std::to_string(verdicts.size()) + " verdicts for " + std::to_string(tickets_.size()) + " tickets");
+        for (size_t t = 0; t < tickets_.size(); ++t)
+            if (verdicts[t]) {
+                ++inter_drone_loop_count[{tickets_[t].drone_new, tickets_[t].drone_old}];
+                ++inter_drone_loop_count[{tickets_[t].drone_old, tickets_[t].drone_new}];
+                tickets_[t].cand->loop = true;
+            }
+        tickets_.clear();
+        verify_pending_.resolved();
+    }
+public:
 
     // an image that claims landmarks but whose global descriptor is not 4096 floats long
     static bool malformed(const FisheyeFrameDescriptor& f) {

@@ -49,6 +49,10 @@ REMOTE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_remote.so")
 REMOTE_SYMBOLS = ["omni_remote_last_error", "omni_pipeline_set_remote_in_stream", "omni_pipeline_get_remote_in_stream", "omni_pipeline_remote_pending",
                   "omni_pipeline_remote_stats", "omni_pipeline_queue_copy_as_remote", "omni_remote_merge_plan"]
 _remote_lib = None
+# inter-drone loop candidates verified with their batch: include/omni_host_verify.h, lib/libomni_host_verify.so (the same handle)
+VERIFY_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_verify.so")
+VERIFY_SYMBOLS = ["omni_verify_last_error", "omni_pipeline_set_batch_verify", "omni_pipeline_get_batch_verify", "omni_pipeline_verify_stats", "omni_pipeline_edge_ids", "omni_pipeline_corr_stats", "omni_verify_correspond_host", "omni_verify_plan"]
+_verify_lib = None
 JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
 JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
                    "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
@@ -399,12 +403,63 @@ def remote_merge_plan(a: int, b: int, queue_p):
     return [(bool(rem[s]), int(idx[s])) for s in range(n.value)], taken.value
 
 
+def verify_lib():
+    global _verify_lib
+    if _verify_lib is None:
+        if not os.path.exists(VERIFY_LIB_PATH):
+            raise OSError(f"{VERIFY_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(VERIFY_LIB_PATH)
+        L.omni_verify_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_batch_verify.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_batch_verify.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.omni_pipeline_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_pipeline_edge_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.omni_pipeline_edge_ids.restype = C.c_int64
+        L.omni_pipeline_corr_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_verify_correspond_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11
+        L.omni_verify_plan.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int]
+        _verify_lib = L
+    return _verify_lib
+
+
+def verify_plan(self_id: int, T: int, drone, partner, partner_init, verdict, batch_len, n_drones: int):
+    """host/verify_plan.hpp's certainty rule over a stream of frames cut into detector batches, no pipeline and no GPU (include/omni_host_verify.h has the
+    arguments) -> (init_mode per frame, resolved_before per frame, end_resolve per batch, inter_drone_loop_count[{x, self_id}] per drone x)"""
+    dr, pa, pi = (np.ascontiguousarray(v, np.int32) for v in (drone, partner, partner_init))
+    ve, bl = np.ascontiguousarray(verdict, np.uint8), np.ascontiguousarray(batch_len, np.int64)
+    n, nb = len(dr), len(bl)
+    if not (len(pa) == len(pi) == len(ve) == n):
+        raise ValueError("verify_plan: one partner, partner_init and verdict per frame")
+    im, rb, er, cnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(nb, 1), np.int32), np.zeros(max(n_drones, 1), np.int64)
+    if verify_lib().omni_verify_plan(self_id, T, n, dr.ctypes.data, pa.ctypes.data, pi.ctypes.data, ve.ctypes.data, bl.ctypes.data, nb, im.ctypes.data, rb.ctypes.data,
+                                     er.ctypes.data, cnt.ctypes.data, n_drones):
+        raise capi.OmniError(f"omni_verify_plan: {verify_lib().omni_verify_last_error().decode()}")
+    return [bool(v) for v in im[:n]], [bool(v) for v in rb[:n]], [bool(v) for v in er[:nb]], [int(v) for v in cnt[:n_drones]]
+
+
+def verify_correspond_host(cands, pairs, cand: int, max_dirs: int, main_dir_new: int, main_dir_old: int, step_present, old_quat):
+    """LoopGeometry::compute_correspond_features on two frames built from candidate `cand` (omni_verify_correspond_host; cands and pairs as capi.CorrArrays takes
+    them, the pairs' dq_old ignored) -> {dq_old [pair_count][4], n_corr, result, size_gate, X [n][3], u [n][2], new_idx, old_idx (per pair)}"""
+    a = capi.CorrArrays(cands, pairs)
+    pc = cands[cand][1]
+    sp, oq = np.ascontiguousarray(step_present, np.uint8), np.ascontiguousarray(old_quat, np.float64).reshape(max_dirs, 4)
+    dq, X, u = np.zeros((max(pc, 1), 4), np.float64), np.zeros((a.cap, 3), np.float32), np.zeros((a.cap, 2), np.float32)
+    n, res, gate = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    ni, oi, npc = np.zeros((max(pc, 1), a.max_n), np.int32), np.zeros((max(pc, 1), a.max_n), np.int32), np.zeros(max(pc, 1), np.int32)
+    if verify_lib().omni_verify_correspond_host(C.addressof(a.io), cand, max_dirs, main_dir_new, main_dir_old, sp.ctypes.data, oq.ctypes.data, dq.ctypes.data, X.ctypes.data,
+                                                u.ctypes.data, C.addressof(n), C.addressof(res), C.addressof(gate), ni.ctypes.data, oi.ctypes.data, npc.ctypes.data):
+        raise capi.OmniError(f"omni_verify_correspond_host: {verify_lib().omni_verify_last_error().decode()}")
+    return {"dq_old": dq[:pc], "n_corr": n.value, "result": bool(res.value), "size_gate": bool(gate.value), "X": X[:n.value].copy(), "u": u[:n.value].copy(),
+            "new_idx": [ni[j, :npc[j]].copy() for j in range(pc)], "old_idx": [oi[j, :npc[j]].copy() for j in range(pc)]}
+
+
 class KeyframePipeline:
     def __init__(self, device: int, sp_weights_path: str, pca_comp_csv: str, pca_mean_csv: str, vlad_weights_path: str, width=600, height=480,
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
-                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False):
+                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False, batch_verify=False):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -435,6 +490,9 @@ class KeyframePipeline:
         remote_in_stream: key frames of other drones (the wire's, or queue_copy_as_remote's) are queued and join the next key-frame unit's detector batch at
         their place in the serial order, their rows gathered with the unit's on the GPU (csrc/rows_assemble.hip), instead of stopping the pipeline with a flush
         each; the same candidates, edges and rows (set_remote_in_stream).  Default off.
+        batch_verify: loop candidates between a frame of another drone and a frame of this one are verified with their detector batch, in one GPU round trip,
+        instead of one by one on the spot; earlier only where a remote frame's init mode depends on a pending verdict (host/verify_plan.hpp).  The same
+        candidates, edges and counters (set_batch_verify, verify_stats).  Independent of remote_in_stream.  Default off.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -485,6 +543,8 @@ class KeyframePipeline:
             self.set_wire(wire, device_wire, send_all_features)
         if remote_in_stream:
             self.set_remote_in_stream(True)
+        if batch_verify:
+            self.set_batch_verify(True)
 
     def _pca(self, rc, what):
         if rc:
@@ -705,6 +765,39 @@ class KeyframePipeline:
         out = (C.c_int64 * 4)()
         self._remote(remote_lib().omni_pipeline_remote_stats(self.h, out), "omni_pipeline_remote_stats")
         return tuple(int(v) for v in out)
+
+    def _verify(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {verify_lib().omni_verify_last_error().decode()}")
+
+    def set_batch_verify(self, on: bool):
+        """inter-drone loop candidates are verified with their detector batch (host/verify_plan.hpp).  While no detector batch is pending; refused without a
+        geometry stage and on a sharded database"""
+        self._verify(verify_lib().omni_pipeline_set_batch_verify(self.h, int(bool(on))), "omni_pipeline_set_batch_verify")
+
+    def batch_verify(self) -> bool:
+        on = C.c_int(0)
+        self._verify(verify_lib().omni_pipeline_get_batch_verify(self.h, C.byref(on)), "omni_pipeline_get_batch_verify")
+        return bool(on.value)
+
+    def verify_stats(self):
+        """(inter-drone candidates deferred, resolves at the end of a detector batch, early resolves forced by the rule, matcher round trips spent on both)"""
+        out = (C.c_int64 * 4)()
+        self._verify(verify_lib().omni_pipeline_verify_stats(self.h, out), "omni_pipeline_verify_stats")
+        return tuple(int(v) for v in out)
+
+    def corr_stats(self):
+        """(candidates whose correspondences the matcher's round trip assembled on the GPU, candidates it handed back to the host functions)"""
+        out = (C.c_int64 * 2)()
+        self._verify(verify_lib().omni_pipeline_corr_stats(self.h, out), "omni_pipeline_corr_stats")
+        return tuple(int(v) for v in out)
+
+    def edge_ids(self) -> np.ndarray:
+        """LoopEdge::id of every accepted edge, in the order of edges(): numbered in candidate order"""
+        n = int(verify_lib().omni_pipeline_edge_ids(self.h, None, 0))
+        out = np.zeros(max(n, 1), np.int64)
+        verify_lib().omni_pipeline_edge_ids(self.h, out.ctypes.data, n)
+        return out[:n]
 
     def queue_copy_as_remote(self, src_msg_id: int, drone_id: int, new_msg_id: int):
         """recv_copy_as_remote's twin: the copy of the stored key frame is queued (remote_in_stream) instead of handed to on_remote_frame"""
