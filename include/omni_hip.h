@@ -931,6 +931,27 @@ int     omni_wire_pack_enqueue_dev(omni_ctx* ctx, int n_images, int max_num, int
 int     omni_wire_pack_host(int n_images, int max_num, int desc_dim, int global_dim, int send_all_features, const float* kps_xy, const int* n_kps, const float* desc,
                             const float* norm2d, const float* l3d, const uint8_t* flag, const float* global, const omni_wire_image_meta* meta, uint8_t* packets_out,
                             int* table_out);
+/* The third packet of an image, the whole ImageDescriptor_t (channel SWARM_LOOP_IMG_DES, loop_net.cpp:37-41, 103-116; wire::encode(ImageDescriptor, with_features) of
+ * host/loop_net_wire.hpp, restated in csrc/wire_plan.h): a head of 177 bytes with every scalar and every length member, then image_desc, feature_descriptor (with
+ * with_features; otherwise its length member is 0), landmarks_2d_norm, landmarks_2d, landmarks_3d of ALL n_kps landmarks, then the flag bytes and the JPEG file.
+ * On top of the inputs above: jpeg [n_images][jpeg_capacity] u8, jpeg_sizes [n_images], jpeg_status [n_images] as omni_jpeg_enqueue_dev leaves them (image_size is the
+ * size clamped to 0..jpeg_capacity for a file of status OMNI_JPEG_OK, 0 otherwise, and 0 for every image when with_image is 0), and the images' width and height.
+ * Outputs: packets_out [n_images][omni_wire_image_capacity(max_num, jpeg_capacity)] -- the packet at byte 3, so that its float area starts on a 4-byte boundary;
+ * written are the packet and zeros up to the next 4-byte boundary, nothing behind that -- and sizes_out [n_images][2] = (offset, size), (0, 0) for an image without
+ * key points, which is not sent.  msg_id is left ZERO (the host writes the image's id, its header packet's).  omni_wire_image_capacity = 180 + 4 * (4096 + 71 *
+ * max_num) + (max_num + jpeg_capacity rounded up to 4); 0 for max_num outside 1..1024 or a jpeg_capacity that is negative, above 2^30 or no multiple of 4.
+ * Refused before anything is launched: what omni_wire_pack_enqueue_dev refuses, such a jpeg_capacity, JPEG pointers that are not all null with with_image == 0 or
+ * not all set with with_image != 0, a misaligned packets_out or jpeg. */
+int64_t omni_wire_image_capacity(int max_num, int64_t jpeg_capacity);
+int     omni_wire_pack_image_enqueue_dev(omni_ctx* ctx, int n_images, int max_num, int desc_dim, int global_dim, int with_features, int with_image,
+                                         const float* kps_xy_dev, const int* n_kps_dev, const float* desc_dev, const float* norm2d_dev, const float* l3d_dev,
+                                         const uint8_t* flag_dev, const float* global_dev, const omni_wire_image_meta* meta_dev, const uint8_t* jpeg_dev,
+                                         const int* jpeg_sizes_dev, const int* jpeg_status_dev, int64_t jpeg_capacity, int image_width, int image_height,
+                                         uint8_t* packets_out_dev, int* sizes_out_dev);
+int     omni_wire_pack_image_host(int n_images, int max_num, int desc_dim, int global_dim, int with_features, int with_image, const float* kps_xy, const int* n_kps,
+                                  const float* desc, const float* norm2d, const float* l3d, const uint8_t* flag, const float* global, const omni_wire_image_meta* meta,
+                                  const uint8_t* jpeg, const int* jpeg_sizes, const int* jpeg_status, int64_t jpeg_capacity, int image_width, int image_height,
+                                  uint8_t* packets_out, int* sizes_out);
 /* The same stage inside a key-frame unit.  omni_cam_set_wire(cam, 1, send_all_features): every following unit runs the kernel on its SuperPoint stream behind the
  * landmark stage (stereo model or depth model) and behind MobileNetVLAD's rows, and copies the buffers and tables of its MAIN images -- [0, n_dirs) on a stereo
  * handle, all images on a mono handle -- into a pinned block of the handle in front of the unit's event; on = 0 switches it off again, and a unit then launches
@@ -946,6 +967,21 @@ typedef struct omni_cam_wire_result {           /* pointers into the handle's pi
     const int*     table;                       /* [n_images][table_ints] */
 } omni_cam_wire_result;
 int     omni_cam_wire(omni_cam* cam, omni_cam_wire_result* out);
+/* The whole descriptor inside the unit, behind the stage above.  omni_cam_set_wire_image(cam, with_features, with_image): every following unit runs
+ * wire_pack_image_kernel on its SuperPoint stream behind wire_pack_kernel -- with_image: also behind an event the MobileNetVLAD stream records after the JPEG stage
+ * (omni_cam_set_jpeg), whose files it reads where that stage left them in HBM -- on the same main images, arrays and records, with the handle's image size as
+ * image_width / image_height when the file travels (0 x 0 otherwise: encode_image sets them, loop_cam.cpp:67-70), and copies buffers and sizes into a pinned block of the handle in front of the unit's event.  Both flags 0 switch it off again (the
+ * default), and a unit then launches exactly what it launched before; omni_cam_set_wire(cam, 0, ..) switches it off too.  Refused: with the wire stage off,
+ * with_image on a handle that encodes no JPEG files or whose JPEG capacity per image is no multiple of 4, a unit in flight; at enqueue, with_image when the JPEG
+ * stage was switched off or given another capacity since. */
+int     omni_cam_set_wire_image(omni_cam* cam, int with_features, int with_image);
+typedef struct omni_cam_wire_image_result {     /* pointers into the handle's pinned host block; valid after omni_cam_wait until the handle's next enqueue */
+    int n_images, with_features, with_image;
+    int64_t capacity;                           /* omni_wire_image_capacity(max_num, the JPEG stage's capacity or 0) */
+    const uint8_t* packets;                     /* [n_images][capacity] */
+    const int*     sizes;                       /* [n_images][2] = (offset, size); (0, 0): not sent */
+} omni_cam_wire_image_result;
+int     omni_cam_wire_image(omni_cam* cam, omni_cam_wire_image_result* out);
 
 /* ---- rows of a mixed detector batch: one contiguous [n_rows][dim] fp32 block in frame order out of rows that lie in three places ------------------------------
  * The plan is csrc/rows_plan.h's: output row r is row table[r].index of the block table[r].source names -- a key-frame unit's rows already in HBM (e.g.

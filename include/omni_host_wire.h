@@ -19,6 +19,7 @@ const char* omni_wire_host_last_error(void);
 
 #define OMNI_WIRE_CHANNEL_HEADER 0        /* "VIOKF_HEADER" */
 #define OMNI_WIRE_CHANNEL_LANDMARKS 1     /* "VIOKF_LANDMARKS" */
+/* (channels 2 and 3, SWARM_LOOP_IMG_DES and SWARM_LOOP_CONN, are off by default and belong to omni_host_wire_messages.h) */
 
 /* wire != 0: the pipeline owns a LoopNetWire and keeps every finished key frame's packets.  device_wire != 0: the packets are packed inside the key-frame unit on the
  * GPU (csrc/wire_pack.hip) and only copied and numbered on the calling thread; 0: LoopNetWire::broadcast_fisheye_desc runs there.  The same bytes either way.

@@ -54,12 +54,14 @@ SYMBOLS = [
     "omni_pcafit_create", "omni_pcafit_destroy", "omni_pcafit_reset", "omni_pcafit_enqueue_rows_dev", "omni_sp_set_pcafit", "omni_pcafit_stats", "omni_pcafit_moments",
     "omni_pcafit_merge_host", "omni_pca_solve_host", "omni_pcafit_solve", "omni_pca_moments_host", "omni_pca_write_csv",
     "omni_wire_packet_capacity", "omni_wire_table_ints", "omni_wire_pack_enqueue_dev", "omni_wire_pack_host", "omni_cam_set_wire", "omni_cam_set_wire_meta", "omni_cam_wire",
+    "omni_wire_image_capacity", "omni_wire_pack_image_enqueue_dev", "omni_wire_pack_image_host", "omni_cam_set_wire_image", "omni_cam_wire_image",
     "omni_rows_assemble_enqueue_dev", "omni_rows_assemble_host", "omni_memcpy_h2d_async",
     "omni_corr_assemble_host", "omni_corr_assemble_multi", "omni_bf_match_homography_corr_multi",
 ]
 ROW_UNIT, ROW_STAGED, ROW_ZERO = 0, 1, 2      # include/omni_hip.h OMNI_ROW_*: where a row of a mixed detector batch comes from
 WIRE_HEADER_BYTES, WIRE_LANDMARK_BYTES, WIRE_HEADER_OFFSET = 16545, 324, 3      # include/omni_hip.h OMNI_WIRE_*
 WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")                            # packet 0 of an image / every other packet
+WIRE_IMAGE_CHANNEL, WIRE_IMAGE_HEAD_BYTES, WIRE_IMAGE_OFFSET = "SWARM_LOOP_IMG_DES", 177, 3      # the whole descriptor (csrc/wire_plan.h whole_*)
 JPEGDEC_OK, JPEGDEC_HOST, JPEGDEC_UNSUPPORTED, JPEGDEC_CORRUPT = 0, 1, 2, 3      # include/omni_hip.h OMNI_JPEGDEC_*
 JPEGDEC_GUARD_BYTES = 256
 JPEG_OK, JPEG_TRUNCATED, JPEG_HEADER_BYTES = 0, 1, 328      # include/omni_hip.h OMNI_JPEG_*
@@ -226,6 +228,34 @@ def wire_pack_host(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, se
     return out, table
 
 
+def wire_image_capacity(max_num: int, jpeg_capacity: int = 0) -> int:
+    return int(lib().omni_wire_image_capacity(max_num, jpeg_capacity))
+
+
+def _wire_jpeg_inputs(N, jpeg, jpeg_sizes, jpeg_status):
+    """the JPEG rows of a whole descriptor: (with_image, [jpeg [N][capacity] u8, sizes [N] i32, status [N] i32] or [], capacity)"""
+    if jpeg is None:
+        assert jpeg_sizes is None and jpeg_status is None
+        return 0, [], 0
+    jp = np.ascontiguousarray(jpeg, np.uint8)
+    js, jt = np.ascontiguousarray(jpeg_sizes, np.int32), np.ascontiguousarray(jpeg_status, np.int32)
+    assert jp.ndim == 2 and jp.shape[0] == N and js.shape == (N,) and jt.shape == (N,)
+    return 1, [jp, js, jt], jp.shape[1]
+
+
+def wire_pack_image_host(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, jpeg=None, jpeg_sizes=None, jpeg_status=None, width: int = 0, height: int = 0,
+                         with_features: bool = True, fill: int = 0):
+    """omni_wire_pack_image_host: the whole descriptor of csrc/wire_plan.h on the host, no GPU.  The arrays of wire_pack_host plus jpeg [N][capacity] u8, jpeg_sizes [N],
+    jpeg_status [N] (all three None: with_image 0) -> (packets [N][wire_image_capacity] u8 pre-filled with `fill`, sizes [N][2] i32 = (offset, size))"""
+    N, M, ins = _wire_inputs(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta)
+    with_image, jp, cap = _wire_jpeg_inputs(N, jpeg, jpeg_sizes, jpeg_status)
+    out = np.full((N, wire_image_capacity(M, cap)), fill, np.uint8)
+    sizes = np.full((N, 2), -1, np.int32)
+    _check(lib().omni_wire_pack_image_host(N, M, ins[2].shape[2], ins[6].shape[1], int(bool(with_features)), with_image, *[a.ctypes.data for a in ins],
+                                           *([a.ctypes.data for a in jp] or [None] * 3), cap, width, height, out.ctypes.data, sizes.ctypes.data))
+    return out, sizes
+
+
 def _rows_inputs(table, unit_rows, staged_rows, dim):
     table = np.ascontiguousarray(table, np.int32).reshape(-1, 2)      # omni_row_source: (source, index) per output row
     unit_rows, staged_rows = _f32(unit_rows).reshape(-1, dim if dim > 0 else 1), _f32(staged_rows).reshape(-1, dim if dim > 0 else 1)
@@ -259,6 +289,10 @@ class _CamJpeg(C.Structure):
 
 class _CamWire(C.Structure):
     _fields_ = [("n_images", C.c_int), ("max_num", C.c_int), ("table_ints", C.c_int), ("capacity", C.c_int64), ("packets", C.POINTER(C.c_uint8)), ("table", C.POINTER(C.c_int))]
+
+
+class _CamWireImage(C.Structure):
+    _fields_ = [("n_images", C.c_int), ("with_features", C.c_int), ("with_image", C.c_int), ("capacity", C.c_int64), ("packets", C.POINTER(C.c_uint8)), ("sizes", C.POINTER(C.c_int))]
 
 
 class _VladWeights(C.Structure):
@@ -410,6 +444,9 @@ def lib():
     sig("omni_wire_table_ints", C.c_int, [C.c_int])
     sig("omni_wire_pack_enqueue_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
     sig("omni_wire_pack_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+    sig("omni_wire_image_capacity", C.c_int64, [C.c_int, C.c_int64])
+    sig("omni_wire_pack_image_enqueue_dev", C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 11 + [C.c_int64, C.c_int, C.c_int, _vp, _vp])
+    sig("omni_wire_pack_image_host", C.c_int, [C.c_int] * 6 + [_vp] * 11 + [C.c_int64, C.c_int, C.c_int, _vp, _vp])
     sig("omni_jpeg_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64])
     sig("omni_jpeg_destroy", None, [_vp])
     sig("omni_jpeg_enqueue_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp])
@@ -420,6 +457,8 @@ def lib():
     sig("omni_cam_set_wire", C.c_int, [_vp, C.c_int, C.c_int])
     sig("omni_cam_set_wire_meta", C.c_int, [_vp, _vp, C.c_int])
     sig("omni_cam_wire", C.c_int, [_vp, C.POINTER(_CamWire)])
+    sig("omni_cam_set_wire_image", C.c_int, [_vp, C.c_int, C.c_int])
+    sig("omni_cam_wire_image", C.c_int, [_vp, C.POINTER(_CamWireImage)])
     sig("omni_jpegdec_create", _vp, [_vp, C.c_int, C.c_int, C.c_int, C.c_int64])
     sig("omni_jpegdec_destroy", None, [_vp])
     sig("omni_jpegdec_enqueue_host", C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _vp, C.c_int, _vp])
@@ -1824,6 +1863,35 @@ def wire_pack_dev(ctx: Context, n_images, max_num, kps_xy_dev, n_kps_dev, desc_d
                                             l3d_dev, flag_dev, global_dev, meta_dev, packets_out, table_out))
 
 
+def wire_pack_image_dev(ctx: Context, n_images, max_num, kps_xy_dev, n_kps_dev, desc_dev, norm2d_dev, l3d_dev, flag_dev, global_dev, meta_dev, jpeg_dev, jpeg_sizes_dev,
+                        jpeg_status_dev, jpeg_capacity, width, height, packets_out, sizes_out, with_features: bool = True, with_image: bool = True, desc_dim: int = 64,
+                        global_dim: int = 4096):
+    """omni_wire_pack_image_enqueue_dev: a unit's HBM-resident arrays and JPEG files -> whole-descriptor packets (csrc/wire_pack.hip); asynchronous on ctx"""
+    _check(lib().omni_wire_pack_image_enqueue_dev(ctx.h, n_images, max_num, desc_dim, global_dim, int(bool(with_features)), int(bool(with_image)), kps_xy_dev, n_kps_dev,
+                                                  desc_dev, norm2d_dev, l3d_dev, flag_dev, global_dev, meta_dev, jpeg_dev, jpeg_sizes_dev, jpeg_status_dev, jpeg_capacity,
+                                                  width, height, packets_out, sizes_out))
+
+
+def wire_pack_image(ctx: Context, kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta, jpeg=None, jpeg_sizes=None, jpeg_status=None, width: int = 0, height: int = 0,
+                    with_features: bool = True, fill: int = 0):
+    """host convenience around wire_pack_image_dev (upload, run, download): the arguments and results of wire_pack_image_host"""
+    N, M, ins = _wire_inputs(kps_xy, n_kps, desc, norm2d, l3d, flag, global_desc, meta)
+    with_image, jp, cap = _wire_jpeg_inputs(N, jpeg, jpeg_sizes, jpeg_status)
+    outs = [np.full((N, wire_image_capacity(M, cap)), fill, np.uint8), np.full((N, 2), -1, np.int32)]
+    dev = []
+    try:
+        for a in ins + jp + outs:
+            dev.append(ctx.to_device(a.view(np.uint8) if a.dtype == WIRE_META_DTYPE else a))
+        wire_pack_image_dev(ctx, N, M, *dev[:8], *(dev[8:11] if with_image else [None] * 3), cap, width, height, *dev[-2:], with_features=with_features,
+                            with_image=bool(with_image), desc_dim=ins[2].shape[2], global_dim=ins[6].shape[1])
+        ctx.sync()
+        res = [ctx.from_device(d, o.shape, o.dtype) for d, o in zip(dev[-2:], outs)]
+    finally:
+        for x in dev:
+            ctx.free(x)
+    return res[0], res[1]
+
+
 def rows_assemble_dev(ctx: Context, n_rows: int, dim: int, table_dev, unit_rows_dev, n_unit_rows: int, staged_rows_dev, n_staged_rows: int, out_dev):
     """omni_rows_assemble_enqueue_dev: the rows of a mixed detector batch gathered into one block (csrc/rows_assemble.hip); asynchronous on ctx"""
     _check(lib().omni_rows_assemble_enqueue_dev(ctx.h, n_rows, dim, table_dev, unit_rows_dev, n_unit_rows, staged_rows_dev, n_staged_rows, out_dev))
@@ -2053,6 +2121,25 @@ class Cam:
         _check(lib().omni_cam_wire(self.h, C.byref(r)))
         A = np.ctypeslib.as_array
         return A(r.packets, (r.n_images, r.capacity)), A(r.table, (r.n_images, r.table_ints))
+
+    def jpeg_arrays(self):
+        """after wait(): numpy VIEWS (bytes [n][capacity] u8, sizes [n] i32, status [n] i32) of the unit's JPEG stage, as omni_cam_jpeg serves them"""
+        r = _CamJpeg()
+        _check(lib().omni_cam_jpeg(self.h, C.byref(r)))
+        A = np.ctypeslib.as_array
+        return A(r.bytes, (r.n_images, r.capacity)), A(r.sizes, (r.n_images,)), A(r.status, (r.n_images,))
+
+    def set_wire_image(self, with_features: bool, with_image: bool):
+        """the whole descriptor behind the LoopNet packets of set_wire (wire_image() after wait()): with the 64-d descriptors, with the JPEG file of set_jpeg; both
+        False switch it off"""
+        _check(lib().omni_cam_set_wire_image(self.h, int(bool(with_features)), int(bool(with_image))))
+
+    def wire_image(self):
+        """after wait(): numpy VIEWS (packets [n][capacity] u8, sizes [n][2] i32 = (offset, size)) of the unit's main images (valid until the next enqueue)"""
+        r = _CamWireImage()
+        _check(lib().omni_cam_wire_image(self.h, C.byref(r)))
+        A = np.ctypeslib.as_array
+        return A(r.packets, (r.n_images, r.capacity)), A(r.sizes, (r.n_images, 2))
 
     def ready(self) -> bool:
         r = C.c_int(0)

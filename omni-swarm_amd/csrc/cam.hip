@@ -99,7 +99,19 @@ struct CamWire {
     omni::DevBuf dev;
     omni::HostBuf host;
     hipEvent_t e_g = nullptr;                 // MobileNetVLAD's rows, for the SuperPoint stream to wait on
-    void release() { dev.release(); host.release(); if (e_g) (void)hipEventDestroy(e_g); e_g = nullptr; }
+    // the whole descriptor of the same images (omni_cam_set_wire_image; wire_pack_image_kernel) behind the packets above and, with the file, behind the JPEG stage of
+    // the other stream.  img_dev / img_host (pinned): the images' buffers [n_cap][img_cap], then (at img_sizes_at) their (offset, size) pairs [n_cap][2]
+    bool img_on = false, img_unit = false;    // the stage is on; the unit enqueued last ran it (omni_cam_wire_image)
+    int img_features = 0, img_file = 0;       // with_features, with_image
+    int64_t img_cap = 0, img_jcap = 0;        // img_jcap: the JPEG stage's capacity the buffers were sized for (0 without the file)
+    size_t img_sizes_at = 0;
+    omni::DevBuf img_dev;
+    omni::HostBuf img_host;
+    hipEvent_t e_j = nullptr;                 // the JPEG stage's files, for the SuperPoint stream to wait on
+    void release() {
+        dev.release(); host.release(); img_dev.release(); img_host.release();
+        for (hipEvent_t* e : {&e_g, &e_j}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    }
 };
 
 struct omni_cam {
@@ -200,6 +212,9 @@ static int cam_poses_depth_check(omni_cam* c) {
     OMNI_REQUIRE(c->lm.on || c->depth.on, OMNI_ERR_INVALID, "the wire stage is on but the handle has no landmark model (omni_cam_set_stereo_model / omni_cam_set_depth_model)");
     OMNI_REQUIRE(c->wire.n_meta > 0, OMNI_ERR_INVALID, "the wire stage is on but the unit's records are not set (omni_cam_set_wire_meta before every enqueue)");
     OMNI_REQUIRE(c->wire.n_meta == c->n, OMNI_ERR_INVALID, "records of %d images for a unit of %d main images (omni_cam_set_wire_meta, omni_cam_set_active)", c->wire.n_meta, c->n);
+    if (c->wire.img_on && c->wire.img_file)
+        OMNI_REQUIRE(c->enc.quality && c->enc.cap == c->wire.img_jcap, OMNI_ERR_INVALID,
+                     "the whole descriptor carries the image but the JPEG stage is off or has another capacity (omni_cam_set_jpeg, then omni_cam_set_wire_image again)");
     return OMNI_OK;
 }
 
@@ -560,7 +575,10 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
         OMNI_HIP_TRY(hipMemcpyAsync(h_w + w.table_at, d_w + w.table_at, (size_t)n * w.te * sizeof(int), hipMemcpyDeviceToHost, s1));
         w.unit = true; w.n = n; w.n_meta = 0;                                 // (the records are consumed: the next unit needs its own)
     }
-    OMNI_HIP_TRY(hipEventRecord(k.e1, s1));
+    // (with the whole descriptor on, the SuperPoint stream has one more kernel to run, behind the JPEG stage enqueued below: its event is recorded there)
+    const bool wire_image = c->wire.on && c->wire.img_on;
+    c->wire.img_unit = false;
+    if (!wire_image) OMNI_HIP_TRY(hipEventRecord(k.e1, s1));
     OMNI_HIP_TRY(hipMemcpyAsync(h + k.off_g, k.g_dev, (size_t)n * c->out_dim * 4, hipMemcpyDeviceToHost, s2));
     c->enc.unit = false;
     if (c->enc.quality) {
@@ -574,9 +592,30 @@ static int cam_enqueue_locked(omni_cam* c, const uint8_t* gray_dev, int stride, 
         int* d_meta = reinterpret_cast<int*>(d_jpeg + e.meta);
         if ((rc = omni::jpeg_check_enqueue(e.h, stride, n, row0))) return rc;
         if ((rc = omni::jpeg_launch(e.h, s2, gray_dev, stride, n, row0, d_jpeg, d_meta, d_meta + c->n_cap))) return rc;
+        if (wire_image && c->wire.img_file) OMNI_HIP_TRY(hipEventRecord(c->wire.e_j, s2));
         OMNI_HIP_TRY(hipMemcpyAsync(h_jpeg, d_jpeg, (size_t)n * e.cap, hipMemcpyDeviceToHost, s2));
         OMNI_HIP_TRY(hipMemcpyAsync(h_jpeg + e.meta, d_meta, (size_t)2 * c->n_cap * 4, hipMemcpyDeviceToHost, s2));
         e.unit = true; e.n = n;
+    }
+    if (wire_image) {
+        // the third packet of the same images, the whole ImageDescriptor_t (loop_net.cpp:103-116; csrc/wire_plan.h whole_*), on the SuperPoint stream behind
+        // wire_pack_kernel: the same arrays and records, and with the file the JPEG stage's output where it lies in HBM, behind that stage's event.  Buffers and
+        // sizes of the n images go down in front of the unit's event
+        CamWire& w = c->wire;
+        const CamJpegEnc& e = c->enc;
+        uint8_t *d_w = w.dev.as<uint8_t>(), *d_i = w.img_dev.as<uint8_t>(), *h_i = w.img_host.as<uint8_t>();
+        const uint8_t* d_jpeg = w.img_file ? e.dev.as<uint8_t>() : nullptr;
+        const int* d_meta = w.img_file ? reinterpret_cast<const int*>(d_jpeg + e.meta) : nullptr;
+        if (w.img_file) OMNI_HIP_TRY(hipStreamWaitEvent(s1, w.e_j, 0));
+        if ((rc = omni::wire_pack_image_launch(s1, n, M, w.img_features, w.img_file, k.kps_dev, k.n_dev, k.desc_dev, v.norm2d, v.l3d, v.flag, k.g_dev,
+                                               reinterpret_cast<const omni_wire_image_meta*>(d_w + w.meta_at), d_jpeg, d_meta, w.img_file ? d_meta + c->n_cap : nullptr,
+                                               w.img_jcap, w.img_file ? c->W : 0, w.img_file ? c->H : 0,      // (encode_image sets the size with the file, loop_cam.cpp:67-70)
+                                               d_i, reinterpret_cast<int*>(d_i + w.img_sizes_at))))
+            return rc;
+        OMNI_HIP_TRY(hipMemcpyAsync(h_i, d_i, (size_t)n * w.img_cap, hipMemcpyDeviceToHost, s1));
+        OMNI_HIP_TRY(hipMemcpyAsync(h_i + w.img_sizes_at, d_i + w.img_sizes_at, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, s1));
+        OMNI_HIP_TRY(hipEventRecord(k.e1, s1));
+        w.img_unit = true;
     }
     OMNI_HIP_TRY(hipEventRecord(k.e2, s2));
     c->pending = true;
@@ -767,7 +806,7 @@ int omni_cam_set_wire(omni_cam* c, int on, int send_all_features) {
     std::lock_guard<std::mutex> lk(c->mu);
     OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_wire with a unit in flight (omni_cam_wait first)");
     CamWire& w = c->wire;
-    if (!on) { w.on = false; w.n_meta = 0; return OMNI_OK; }
+    if (!on) { w.on = false; w.img_on = false; w.n_meta = 0; return OMNI_OK; }
     OMNI_REQUIRE(c->lm.on || c->depth.on, OMNI_ERR_INVALID,
                  "omni_cam_set_wire: the handle has no landmark model (omni_cam_set_stereo_model / omni_cam_set_depth_model): the stage packs landmarks the device made");
     OMNI_REQUIRE(c->D == WP_DESC_DIM && c->out_dim == WP_GLOBAL_DIM, OMNI_ERR_INVALID, "omni_cam_set_wire: descriptors of %d and global descriptors of %d floats, the wire carries %d and %d",
@@ -806,6 +845,44 @@ int omni_cam_wire(omni_cam* c, omni_cam_wire_result* out) {
     OMNI_REQUIRE(c->wire.unit, OMNI_ERR_INVALID, "omni_cam_wire: the last unit ran with the stage off (omni_cam_set_wire)");
     out->n_images = c->wire.n; out->max_num = c->M; out->table_ints = c->wire.te; out->capacity = c->wire.cap;
     out->packets = c->wire.host.as<uint8_t>(); out->table = reinterpret_cast<const int*>(out->packets + c->wire.table_at);
+    return OMNI_OK;
+}
+
+// the whole descriptor behind the packets above: with_features and with_image both 0 switch it off again
+int omni_cam_set_wire_image(omni_cam* c, int with_features, int with_image) {
+    OMNI_REQUIRE(c, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_set_wire_image with a unit in flight (omni_cam_wait first)");
+    CamWire& w = c->wire;
+    if (!with_features && !with_image) { w.img_on = false; return OMNI_OK; }
+    OMNI_REQUIRE(w.on, OMNI_ERR_INVALID, "omni_cam_set_wire_image with the wire stage off (omni_cam_set_wire): the whole descriptor follows an image's packets");
+    OMNI_REQUIRE(!with_image || c->enc.quality, OMNI_ERR_INVALID, "omni_cam_set_wire_image: with_image, but the unit encodes no JPEG files (omni_cam_set_jpeg)");
+    const int64_t jcap = with_image ? c->enc.cap : 0;
+    OMNI_REQUIRE(jcap % 4 == 0 && jcap <= WP_MAX_JPEG_CAPACITY, OMNI_ERR_INVALID,
+                 "omni_cam_set_wire_image: the JPEG stage's capacity of %lld bytes per image is above 2^30 or no multiple of 4: a file's row would not be 4-byte aligned",
+                 (long long)jcap);
+    (void)hipSetDevice(c->c1->device);
+    const int64_t cap = omni::wp::whole_capacity(c->M, jcap);
+    if (cap != w.img_cap) {                          // (set-up time: no unit is in flight)
+        int rc;
+        w.img_on = false; w.img_cap = 0;
+        const size_t sizes_at = ((size_t)c->n_cap * cap + 255) & ~(size_t)255, bytes = sizes_at + (size_t)c->n_cap * 2 * sizeof(int);
+        if ((rc = w.img_dev.ensure(bytes)) || (rc = w.img_host.ensure(bytes))) return rc;
+        memset(w.img_host.p, 0, bytes);
+        w.img_cap = cap; w.img_sizes_at = sizes_at;
+    }
+    if (!w.e_j) OMNI_HIP_TRY(hipEventCreateWithFlags(&w.e_j, hipEventDisableTiming));
+    w.img_jcap = jcap; w.img_features = with_features != 0; w.img_file = with_image != 0; w.img_on = true;
+    return OMNI_OK;
+}
+
+int omni_cam_wire_image(omni_cam* c, omni_cam_wire_image_result* out) {
+    OMNI_REQUIRE(c && out, OMNI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    OMNI_REQUIRE(!c->pending, OMNI_ERR_INVALID, "omni_cam_wire_image with a unit in flight (omni_cam_wait first)");
+    OMNI_REQUIRE(c->wire.img_unit, OMNI_ERR_INVALID, "omni_cam_wire_image: the last unit ran with the stage off (omni_cam_set_wire_image)");
+    out->n_images = c->wire.n; out->capacity = c->wire.img_cap; out->with_features = c->wire.img_features; out->with_image = c->wire.img_file;
+    out->packets = c->wire.img_host.as<uint8_t>(); out->sizes = reinterpret_cast<const int*>(out->packets + c->wire.img_sizes_at);
     return OMNI_OK;
 }
 

@@ -211,6 +211,11 @@ int depth_check_model(const omni_depth_model* m);
 // wire_pack.hip: LoopNet's packets of n_images images out of a unit's arrays (csrc/wire_plan.h); the caller has checked what omni_wire_pack_enqueue_dev refuses
 int wire_pack_launch(hipStream_t stream, int n_images, int max_num, int send_all_features, const float* kps_xy, const int* n_kps, const float* desc, const float* norm2d,
                      const float* l3d, const uint8_t* flag, const float* global, const omni_wire_image_meta* meta, uint8_t* out, int* table);
+// ... and their whole descriptors (wire_plan.h whole_*), with the JPEG files jpeg [n_images][jpeg_capacity] (null without with_image); the caller has checked what
+// omni_wire_pack_image_enqueue_dev refuses
+int wire_pack_image_launch(hipStream_t stream, int n_images, int max_num, int with_features, int with_image, const float* kps_xy, const int* n_kps, const float* desc,
+                           const float* norm2d, const float* l3d, const uint8_t* flag, const float* global, const omni_wire_image_meta* meta, const uint8_t* jpeg,
+                           const int* jpeg_sizes, const int* jpeg_status, int64_t jpeg_capacity, int width, int height, uint8_t* out, int* sizes_out);
 }  // namespace omni
 
 struct omni_jpeg;

@@ -27,6 +27,9 @@
 //              stage stores whole dwords only (the first dword's three leading bytes are zero padding).  Bytes behind the last packet are not written.
 //   table      per image table_ints(max_num) = 2 + 2 * (1 + max_num) ints: [0] packets, [1] bytes used (the end of the last packet; 0 without packets), then
 //              (offset, size) per packet, packet 0 the header (channel VIOKF_HEADER), the others landmarks (VIOKF_LANDMARKS); the unused entries are zero.
+//
+// The third packet of an image, the whole descriptor (wire::encode(ImageDescriptor, with_features), channel SWARM_LOOP_IMG_DES), has a buffer and a size table of its
+// own, stated further down (whole_*): wire_pack_image_kernel / pack_whole_image_host, pinned by tests/cpp/wire_image_plan_pin.cpp in the same way.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -120,8 +123,121 @@ WP_HD int table_entry(int e, int n_sent) {
     return second ? WP_LANDMARK_BYTES : landmark_offset(k - 1);
 }
 
+// ---- the whole descriptor (wire::encode(ImageDescriptor, with_features); channel SWARM_LOOP_IMG_DES) ------------------------------------------------------------
+//   head      WP_IMAGE_HEAD_BYTES = 177: every scalar and EVERY length member
+//       0  i64 fingerprint "OMNIIMG1"      8  f64 timestamp      16  i32 drone_id      20  i64 msg_id (ZERO here)      28  i64 frame_id
+//      36  i32 landmark_num               40  i32 direction      44  u8  prevent_adding_db
+//      45  7 x f64 pose_drone            101  7 x f64 camera_extrinsic                157  i32 image_width            161  i32 image_height
+//     165  i32 image_desc_size = 4096    169  i32 feature_descriptor_size = 64 * landmark_num, or 0 without with_features     173  i32 image_size
+//   floats    image_desc, feature_descriptor, landmarks_2d_norm (2 per landmark), landmarks_2d (2), landmarks_3d (3): big-endian dwords, ALL landmark_num
+//             landmarks (not only the flagged ones: the reference sends the message as it is, loop_net.cpp:105-114)
+//   bytes     landmarks_flag (landmark_num bytes), then image (image_size bytes: the JPEG file of the unit's encode stage)
+//   image     image_size = the file's size clamped to [0, jpeg_capacity] when with_image is set and the file's status is OMNI_JPEG_OK; 0 otherwise
+//   buffer    per image whole_capacity(max_num, jpeg_capacity) bytes, a multiple of 4.  The packet starts at byte WP_IMAGE_OFFSET = 3, so the float area starts at byte
+//             180 and the byte tail on a 4-byte boundary behind it.  Written: the three bytes of padding (zero), the packet, zeros up to the next 4-byte boundary
+//             behind it; nothing behind that.  The JPEG file's rows are read as dwords: jpeg_capacity is a multiple of 4 and the host's rows are read bytewise.
+//   sizes     per image 2 ints: (offset, size) of the packet, (0, 0) for an image that is not sent (landmark_num == 0, as broadcast_fisheye_desc)
+//   id        msg_id is the image's, i.e. its header packet's: patch_whole_image_id
+#define WP_IMAGE_HEAD_BYTES 177
+#define WP_IMAGE_OFFSET 3
+#define WP_IMAGE_HEAD_PADDED (WP_IMAGE_OFFSET + WP_IMAGE_HEAD_BYTES)     // 180 bytes = 45 dwords
+#define WP_IMAGE_HEAD_DWORDS (WP_IMAGE_HEAD_PADDED / 4)
+#define WP_LANDMARK_FLOATS 7                                             // 2 + 2 + 3 per landmark besides its descriptor
+#define WP_MAX_JPEG_CAPACITY (1 << 30)
+static_assert(WP_IMAGE_HEAD_PADDED % 4 == 0, "dword placement of the whole descriptor");
+
+constexpr uint64_t kFpImage = 0x4f4d4e49494d4731ull;          // "OMNIIMG1" (wire::FP_IMAGE)
+
+WP_HD int whole_feature_floats(int landmark_num, int with_features) { return with_features ? WP_DESC_DIM * landmark_num : 0; }
+WP_HD int whole_float_dwords(int landmark_num, int with_features) { return WP_GLOBAL_DIM + whole_feature_floats(landmark_num, with_features) + WP_LANDMARK_FLOATS * landmark_num; }
+WP_HD int64_t whole_capacity(int max_num, int64_t jpeg_capacity) {
+    return (int64_t)WP_IMAGE_HEAD_PADDED + 4 * (int64_t)whole_float_dwords(max_num, 1) + (((int64_t)max_num + jpeg_capacity + 3) & ~(int64_t)3);
+}
+WP_HD int whole_image_size(int with_image, int status, int size, int64_t jpeg_capacity) {
+    if (!with_image || status != OMNI_JPEG_OK || size < 0) return 0;
+    return (int64_t)size > jpeg_capacity ? (int)jpeg_capacity : size;
+}
+WP_HD int whole_packet_bytes(int landmark_num, int with_features, int image_size) {
+    return WP_IMAGE_HEAD_BYTES + 4 * whole_float_dwords(landmark_num, with_features) + landmark_num + image_size;
+}
+
+// byte b of the first WP_IMAGE_HEAD_PADDED bytes of an image's whole-descriptor buffer
+WP_HD uint8_t whole_head_byte(int b, const omni_wire_image_meta& m, int landmark_num, int width, int height, int feature_floats, int image_size) {
+    const int o = b - WP_IMAGE_OFFSET;
+    if (o < 0) return 0;
+    if (o < 8) return be_byte64(kFpImage, o);
+    if (o < 16) return be_byte64(f64_bits(m.timestamp), o - 8);
+    if (o < 20) return be_byte32((uint32_t)m.drone_id, o - 16);
+    if (o < 28) return 0;                                                                    // msg_id: the host's
+    if (o < 36) return be_byte64((uint64_t)m.frame_id, o - 28);
+    if (o < 40) return be_byte32((uint32_t)landmark_num, o - 36);
+    if (o < 44) return be_byte32((uint32_t)m.direction, o - 40);
+    if (o < 45) return m.prevent_adding_db ? 1 : 0;
+    if (o < 101) return be_byte64(f64_bits(m.pose_drone[(o - 45) >> 3]), (o - 45) & 7);
+    if (o < 157) return be_byte64(f64_bits(m.camera_extrinsic[(o - 101) >> 3]), (o - 101) & 7);
+    if (o < 161) return be_byte32((uint32_t)width, o - 157);
+    if (o < 165) return be_byte32((uint32_t)height, o - 161);
+    if (o < 169) return be_byte32((uint32_t)WP_GLOBAL_DIM, o - 165);
+    if (o < 173) return be_byte32((uint32_t)feature_floats, o - 169);
+    return be_byte32((uint32_t)image_size, o - 173);
+}
+
+// dword j of the float area, as the little-endian machine stores it; every array is the image's own rows, of which the first landmark_num are contiguous
+WP_HD uint32_t whole_float_dword(int j, int landmark_num, int feature_floats, const float* global, const float* desc, const float* norm2d, const float* kps_xy,
+                                 const float* l3d) {
+    const float* p;
+    if (j < WP_GLOBAL_DIM) p = global + j;
+    else if ((j -= WP_GLOBAL_DIM) < feature_floats) p = desc + j;
+    else if ((j -= feature_floats) < 2 * landmark_num) p = norm2d + j;
+    else if ((j -= 2 * landmark_num) < 2 * landmark_num) p = kps_xy + j;
+    else p = l3d + (j - 2 * landmark_num);
+    return __builtin_bswap32(f32_bits(p));
+}
+
+// dword q of a JPEG file's row; only a dword with a byte of the file in it is ever asked for (4 * q < image_size <= jpeg_capacity, a multiple of 4)
+WP_HD uint32_t jpeg_dword(const uint8_t* row, int q) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return reinterpret_cast<const uint32_t*>(row)[q];                                        // (the row starts on a 4-byte boundary: refused otherwise)
+#else
+    uint32_t v; __builtin_memcpy(&v, row + 4 * (size_t)q, 4); return v;
+#endif
+}
+
+// dword d of the byte tail (landmark_num flag bytes, then image_size bytes of the file, then zeros up to the 4-byte boundary), as the machine stores it.  The file's
+// destination starts at byte landmark_num of the tail, its source on a dword of its own: an output dword is put together from two neighbouring source dwords.
+WP_HD uint32_t whole_tail_dword(int d, int landmark_num, int image_size, const uint8_t* flag, const uint8_t* jpeg_row) {
+    const int base = 4 * d, s = base - landmark_num;         // s: the file's byte that output byte 0 holds (negative: flag bytes come first)
+    uint32_t v = 0;
+    if (s < 0) {
+        const int k = -s < 4 ? -s : 4;                        // flag bytes in this dword
+        for (int j = 0; j < k; ++j) v |= (uint32_t)flag[base + j] << (8 * j);
+        if (k < 4 && image_size > 0) v |= jpeg_dword(jpeg_row, 0) << (8 * k);
+    } else if (s < image_size) {
+        const int q = s >> 2, sh = 8 * (s & 3);
+        const uint32_t lo = jpeg_dword(jpeg_row, q), hi = sh != 0 && 4 * (q + 1) < image_size ? jpeg_dword(jpeg_row, q + 1) : 0u;
+        v = sh != 0 ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    }
+    const int valid = landmark_num + image_size - base;       // bytes of this dword that belong to the packet
+    return valid >= 4 ? v : valid <= 0 ? 0u : v & ((1u << (8 * valid)) - 1u);
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 inline void put_dword(uint8_t* at, uint32_t v) { __builtin_memcpy(at, &v, 4); }
+
+// one image's whole descriptor on one thread, the dwords the kernel's lanes store.  out: whole_capacity(max_num, jpeg_capacity) bytes, sizes: 2 ints.  jpeg_row,
+// jpeg_size and jpeg_status are read only with with_image set.
+inline void pack_whole_image_host(int max_num, int with_features, int with_image, const float* kps_xy, int n_kps, const float* desc, const float* norm2d, const float* l3d,
+                                  const uint8_t* flag, const float* global, const omni_wire_image_meta& m, const uint8_t* jpeg_row, int jpeg_size, int jpeg_status,
+                                  int64_t jpeg_capacity, int width, int height, uint8_t* out, int* sizes) {
+    const int n = clamp_count(n_kps, max_num);
+    if (!image_sent(n)) { sizes[0] = sizes[1] = 0; return; }
+    const int isz = whole_image_size(with_image, jpeg_status, jpeg_size, jpeg_capacity), ff = whole_feature_floats(n, with_features), fd = whole_float_dwords(n, with_features);
+    for (int b = 0; b < WP_IMAGE_HEAD_PADDED; ++b) out[b] = whole_head_byte(b, m, n, width, height, ff, isz);
+    for (int j = 0; j < fd; ++j) put_dword(out + WP_IMAGE_HEAD_PADDED + 4 * (size_t)j, whole_float_dword(j, n, ff, global, desc, norm2d, kps_xy, l3d));
+    uint8_t* tail = out + WP_IMAGE_HEAD_PADDED + 4 * (size_t)fd;
+    for (int d = 0; 4 * d < n + isz; ++d) put_dword(tail + 4 * (size_t)d, whole_tail_dword(d, n, isz, flag, jpeg_row));
+    sizes[0] = WP_IMAGE_OFFSET; sizes[1] = whole_packet_bytes(n, with_features, isz);
+}
 
 // one image on one thread: the order the kernel's lanes produce, sequentially.  out: capacity(max_num) bytes, table: table_ints(max_num) ints
 inline void pack_image_host(int max_num, int send_all_features, const float* kps_xy, int n_kps, const float* desc, const float* norm2d, const float* l3d,
@@ -144,6 +260,7 @@ inline void pack_image_host(int max_num, int send_all_features, const float* kps
 inline void put_be64(uint8_t* at, int64_t v) { for (int j = 0; j < 8; ++j) at[j] = be_byte64((uint64_t)v, j); }
 inline void patch_header_id(uint8_t* header_packet, int64_t msg_id) { put_be64(header_packet + 20, msg_id); }
 inline void patch_landmark_ids(uint8_t* landmark_packet, int64_t msg_id, int64_t header_id) { put_be64(landmark_packet + 8, msg_id); put_be64(landmark_packet + 16, header_id); }
+inline void patch_whole_image_id(uint8_t* whole_packet, int64_t msg_id) { put_be64(whole_packet + 20, msg_id); }      // the image's id: its header packet's
 #endif
 
 }  // namespace wp

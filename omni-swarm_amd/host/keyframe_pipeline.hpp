@@ -68,6 +68,9 @@ private:
 
 class KeyframePipeline {
 public:
+    // Config::wire_img_desc (include/omni_host_wire_messages.h OMNI_WIRE_IMG_*)
+    enum { WIRE_IMG_OFF = 0, WIRE_IMG_IMAGE = 1, WIRE_IMG_WHOLE = 2, WIRE_IMG_PC_REPLAY = 3 };
+    static constexpr size_t REMOTE_IMAGES_MAX = 64;       // received images kept for take_remote_image; beyond it the oldest is dropped and counted
     struct Config {
         int device = 0, width = 600, height = 480, max_num = 200, precision = OMNI_PREC_F16;
         float thres = 0.02f;
@@ -109,6 +112,15 @@ public:
         // device_depth_landmarks in effect and is refused otherwise, as on the sharded database, which builds no messages.  send_all_features: LoopNet's
         // SEND_ALL_FEATURES.  All off by default.  (set_wire: before the first key frame.)
         bool wire = false, device_wire = false, send_all_features = false;
+        // LoopNet's other two message kinds on the same wire (loop_net.cpp:9-10).  `wire_img_desc`: which images also leave as a whole ImageDescriptor_t
+        // (SWARM_LOOP_IMG_DES, loop_net.cpp:37-41, 103-116) -- WIRE_IMG_IMAGE: behind an image's landmark packets, without the 64-d descriptors, with the JPEG file
+        // (LoopNet's send_img; refused unless send_img is in effect); WIRE_IMG_WHOLE: with the descriptors (send_whole_img_desc), and with the file exactly when
+        // send_img is in effect; WIRE_IMG_PC_REPLAY: the whole descriptor ALONE, no header and landmark packets (is_pc_replay).  With device_wire the packet is
+        // packed inside the unit (wire_pack_image_kernel), out of its arrays and the file its JPEG stage left in HBM; the same bytes either way.
+        // `wire_loop_conn`: every edge that enters edges() leaves as a SWARM_LOOP_CONN packet (loop_net.cpp:122-127), an outbox entry of its own; edges of other
+        // drones arrive in remote_edges().  Both off by default.  (set_wire_messages: before the first key frame, with the wire on; not on the sharded database.)
+        int wire_img_desc = 0;
+        bool wire_loop_conn = false;
         // Remote key frames join the unit stream.  Off (the default): every frame the wire completes goes through flush() + on_remote_frame -- the units in flight
         // are waited for, the frame's four global descriptors go up in four blocking copies and its search is waited for.  On: the frame is QUEUED
         // (queue_remote_frame; drain_inbox does it for the wire's frames) with p, the number of local key frames handed over before it, and the next key-frame
@@ -263,6 +275,8 @@ private:
         apply_stereo_model();
         apply_jpeg();
         if (c.wire) { const bool dw = c.device_wire; cfg_.wire = cfg_.device_wire = false; set_wire(true, dw, c.send_all_features); }
+        cfg_.wire_img_desc = 0; cfg_.wire_loop_conn = false;
+        if (c.wire_img_desc || c.wire_loop_conn) set_wire_messages(c.wire_img_desc, c.wire_loop_conn);
         if (c.device_pnp) ensure_pnp_context();
         if (c.geometry) {
             geo_.self_id = c.self_id; geo_.MIN_LOOP_NUM = c.min_loop_num; geo_.MIN_DIRECTION_LOOP = c.min_direction_loop;
@@ -348,6 +362,7 @@ public:
                 std::pair<bool, LoopEdge> r = gb.futs[fi].get();
                 if (r.first) {
                     geo_.number_edge(r.second); edges_.push_back(r.second);
+                    if (cfg_.wire_loop_conn && net_) queue_loop_conn(edges_.back());
                     if (fi < gb.self_self.size() && gb.self_self[fi]) det_.inter_drone_loop_count[{cfg_.self_id, cfg_.self_id}] += 2;      // what the detector would have counted (:826-827, both orders)
                 }
                 if (fi < gb.verdict.size() && gb.verdict[fi]) verdicts_.push_back(r.first ? 1 : 0);      // batch_verify: the detector's ticket, in candidate order
@@ -736,6 +751,7 @@ public:
         std::lock_guard<std::mutex> lk(intake_mu_);
         if (any_keyframe_seen_) throw std::runtime_error("set_send_img after the first key frame");
         if (on && (quality < 1 || quality > 100)) throw std::invalid_argument("set_send_img: jpg_quality outside 1..100");
+        if (!on && cfg_.wire_img_desc == WIRE_IMG_IMAGE) throw std::runtime_error("set_send_img(false): wire_img_desc IMAGE sends the file (set_wire_messages first)");
         cfg_.send_img = on;
         if (on) cfg_.jpg_quality = quality;
         apply_jpeg();
@@ -750,7 +766,12 @@ private:
         for (auto& l : lanes_) apply_fit_pca(*l);
         for (auto& t : tail_lanes_) apply_fit_pca(*t.second);
     }
-    void apply_jpeg(Lane& l) { l.cam.set_jpeg(send_img() ? cfg_.jpg_quality : 0, jpeg_capacity()); }
+    // (the whole descriptor's stage reads the JPEG stage's files and follows the wire stage: it is set behind either)
+    void apply_jpeg(Lane& l) {
+        l.cam.set_jpeg(send_img() ? cfg_.jpg_quality : 0, jpeg_capacity());
+        const int mode = device_wire() ? cfg_.wire_img_desc : WIRE_IMG_OFF;
+        l.cam.set_wire_image(mode >= WIRE_IMG_WHOLE, mode == WIRE_IMG_IMAGE || (mode >= WIRE_IMG_WHOLE && send_img()));
+    }
     void apply_jpeg() {
         for (auto& l : lanes_) apply_jpeg(*l);
         for (auto& t : tail_lanes_) apply_jpeg(*t.second);
@@ -764,6 +785,7 @@ private:
             l.cam.set_depth_model(device_depth_landmarks() ? &d : nullptr, &cfg_.camera_model);
         }
         l.cam.set_wire(device_wire(), cfg_.send_all_features);      // (behind the models: the stage is refused on a handle without one)
+        apply_jpeg(l);
     }
     void apply_stereo_model() {
         for (auto& l : lanes_) apply_stereo_model(*l);
@@ -834,16 +856,22 @@ public:
             throw std::runtime_error("set_wire: device_wire packs the landmarks the key-frame unit made: it needs device_landmarks (the stereo configurations) or "
                                      "device_depth_landmarks (PINHOLE_DEPTH) in effect, with the geometry stage on");
         cfg_.wire = on; cfg_.device_wire = on && device; cfg_.send_all_features = send_all_features;
-        if (!on) { net_.reset(); outbox_.clear(); inbox_.clear(); }
+        if (!on) { net_.reset(); outbox_.clear(); inbox_.clear(); cfg_.wire_img_desc = WIRE_IMG_OFF; cfg_.wire_loop_conn = false; }
         else if (!net_) {
             net_ = std::make_unique<LoopNetWire>(cfg_.self_id);
             net_->publish = [this](const char* ch, const std::vector<uint8_t>& b) {
                 if (!publishing_) return;
                 publishing_->off.push_back((int64_t)publishing_->bytes.size()); publishing_->size.push_back((int)b.size());
-                publishing_->channel.push_back(std::strcmp(ch, wire::CH_HEADER) == 0 ? 0 : 1);
+                publishing_->channel.push_back(std::strcmp(ch, wire::CH_HEADER) == 0 ? 0 : std::strcmp(ch, wire::CH_LANDMARKS) == 0 ? 1 : std::strcmp(ch, wire::CH_IMG_DES) == 0 ? 2 : 3);
                 publishing_->bytes.insert(publishing_->bytes.end(), b.begin(), b.end());
             };
             net_->frame_desc_callback = [this](const FisheyeFrameDescriptor& f) { inbox_.push_back(f); };
+            net_->loopconn_callback = [this](const LoopEdge& e) { remote_edges_.push_back(e); };
+            net_->image_callback = [this](const ImageDescriptor& d) {
+                if (d.image.empty()) return;                       // (a descriptor without its file: nothing to show)
+                if (remote_images_.size() >= REMOTE_IMAGES_MAX) { remote_images_.pop_front(); ++remote_images_dropped_; }
+                remote_images_.push_back({d.drone_id, d.frame_id, d.direction, d.image_width, d.image_height, d.image});
+            };
             net_->MIN_DIRECTION_LOOP = cfg_.min_direction_loop;
         }
         if (net_) net_->SEND_ALL_FEATURES = send_all_features;
@@ -856,7 +884,47 @@ public:
         if (!(recv_period >= 0) || min_direction_loop < 1) throw std::invalid_argument("set_wire_recv: recv_period < 0 or MIN_DIRECTION_LOOP < 1");
         net_->recv_period = recv_period; net_->MIN_DIRECTION_LOOP = min_direction_loop; net_->group_by_frame_id = group_by_frame_id;
     }
-    // one finished local key frame's packets, in sending order: channel 0 = VIOKF_HEADER, 1 = VIOKF_LANDMARKS
+    // ---- the wire's other two message kinds (Config::wire_img_desc, Config::wire_loop_conn) -----------------------------------------------------------------
+    int wire_img_desc() const { return net_ ? cfg_.wire_img_desc : WIRE_IMG_OFF; }
+    bool wire_loop_conn() const { return net_ && cfg_.wire_loop_conn; }
+    // before the first key frame (what the C entry point omni_pipeline_set_wire_messages sets)
+    void set_wire_messages(int img_desc, bool loop_conn) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_wire_messages after the first key frame");
+        if (shard_) throw std::runtime_error("set_wire_messages: the sharded database builds no messages");
+        if (!net_) throw std::runtime_error("set_wire_messages: the wire is off (set_wire)");
+        if (img_desc < WIRE_IMG_OFF || img_desc > WIRE_IMG_PC_REPLAY) throw std::invalid_argument("set_wire_messages: wire_img_desc outside 0..3 (OFF, IMAGE, WHOLE, PC_REPLAY)");
+        if (img_desc == WIRE_IMG_IMAGE && !send_img()) throw std::runtime_error("set_wire_messages: wire_img_desc IMAGE sends the JPEG file: send_img is not in effect (set_send_img)");
+        const int before = cfg_.wire_img_desc;
+        cfg_.wire_img_desc = img_desc;
+        try { apply_jpeg(); } catch (...) { cfg_.wire_img_desc = before; apply_jpeg(); throw; }       // (the unit refuses a JPEG capacity that is no multiple of 4)
+        cfg_.wire_loop_conn = loop_conn;
+        // LoopNet(_lcm_uri, send_img, send_whole_img_desc, ..) and IS_PC_REPLAY, as LoopNetWire::broadcast_img_desc reads them
+        net_->send_img = img_desc == WIRE_IMG_IMAGE; net_->send_whole_img_desc = img_desc == WIRE_IMG_WHOLE; net_->is_pc_replay = img_desc == WIRE_IMG_PC_REPLAY;
+    }
+    // received whole descriptors that carry their 64-d descriptors enter the frame flow (LoopNetWire::accept_img_desc: what a replay ground station sets)
+    void set_wire_accept_img_desc(bool on) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (!net_) throw std::runtime_error("set_wire_accept_img_desc: the wire is off (set_wire)");
+        net_->accept_img_desc = on;
+    }
+    bool wire_accept_img_desc() const { return net_ && net_->accept_img_desc; }
+    // the edges other drones sent (SWARM_LOOP_CONN), in arrival order; this pipeline's own edges are never listed
+    const std::vector<LoopEdge>& remote_edges() const { return remote_edges_; }
+    // the JPEG files other drones sent inside whole descriptors, oldest first; at most REMOTE_IMAGES_MAX are kept
+    struct RemoteImage { int drone_id = 0; int64_t frame_id = 0; int direction = 0, width = 0, height = 0; std::vector<uint8_t> bytes; };
+    size_t remote_images_pending() const { return remote_images_.size(); }
+    int64_t remote_images_dropped() const { return remote_images_dropped_; }
+    const RemoteImage* oldest_remote_image() const { return remote_images_.empty() ? nullptr : &remote_images_.front(); }
+    RemoteImage take_remote_image() {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (remote_images_.empty()) throw std::runtime_error("take_remote_image: no image is pending");
+        RemoteImage r = std::move(remote_images_.front());
+        remote_images_.pop_front();
+        return r;
+    }
+    // one finished local key frame's packets, in sending order: channel 0 = VIOKF_HEADER, 1 = VIOKF_LANDMARKS, 2 = SWARM_LOOP_IMG_DES; or one accepted edge's one
+    // packet, channel 3 = SWARM_LOOP_CONN, msg_id the edge's id
     struct SentFrame { int64_t msg_id = 0; std::vector<uint8_t> bytes; std::vector<int64_t> off; std::vector<int> size; std::vector<uint8_t> channel; };
     size_t wire_pending() const { return outbox_.size(); }
     const SentFrame* oldest_packets() const { return outbox_.empty() ? nullptr : &outbox_.front(); }
@@ -902,7 +970,17 @@ private:
     void wire_out(Lane& lane) {
         const bool dev = device_wire();
         const omni_cam_wire_result wr = dev ? lane.cam.wire() : omni_cam_wire_result{};
-        const int nd = cfg_.dirs();
+        const int nd = cfg_.dirs(), mode = cfg_.wire_img_desc;
+        // the whole descriptors of the same images, packed by the unit behind their packets; under PC_REPLAY they leave alone (loop_net.cpp:37-41)
+        const omni_cam_wire_image_result wi = dev && mode != WIRE_IMG_OFF ? lane.cam.wire_image() : omni_cam_wire_image_result{};
+        const bool alone = mode == WIRE_IMG_PC_REPLAY;
+        auto whole_size = [&](size_t i) {
+            if (mode == WIRE_IMG_OFF) return 0;
+            const int off = wi.sizes[2 * i], size = wi.sizes[2 * i + 1];
+            if (size == 0 && off == 0) return 0;
+            if (off != WP_IMAGE_OFFSET || size < WP_IMAGE_HEAD_BYTES || (int64_t)off + size > wi.capacity) throw std::runtime_error("wire_out: a whole descriptor out of place");
+            return size;
+        };
         for (int m = 0; m < lane.cur; ++m) {
             FisheyeFrameDescriptor& f = frames_[(size_t)m];
             outbox_.emplace_back();
@@ -918,7 +996,8 @@ private:
             for (int d = 0; d < nd; ++d) {
                 const int* tb = wr.table + ((size_t)nd * m + d) * wr.table_ints;
                 if (tb[0] < 0 || tb[0] > 1 + wr.max_num || tb[1] < 0 || tb[1] > wr.capacity || (tb[0] > 0 && tb[1] < WP_LANDMARKS_AT)) throw std::runtime_error("wire_out: a packet table out of range");
-                if (tb[0]) total += (size_t)tb[1] - WP_HEADER_OFFSET;
+                if (tb[0] && !alone) total += (size_t)tb[1] - WP_HEADER_OFFSET;
+                if (tb[0]) total += (size_t)whole_size((size_t)nd * m + d);
             }
             s.bytes.reserve(total);
             for (int d = 0; d < nd; ++d) {
@@ -926,10 +1005,21 @@ private:
                 const int* tb = wr.table + i * wr.table_ints;
                 const uint8_t* buf = wr.packets + i * (size_t)wr.capacity;
                 if (!tb[0]) continue;
+                const int ws = whole_size(i);
+                // the image's id (LoopNetWire's sequence: the header's, or under PC_REPLAY the image's one id), then its whole descriptor behind its packets
+                int64_t header_id = 0;
+                auto whole = [&] {
+                    if (!ws) return;
+                    const size_t at = s.bytes.size();
+                    const uint8_t* src = wi.packets + i * (size_t)wi.capacity + WP_IMAGE_OFFSET;
+                    s.bytes.insert(s.bytes.end(), src, src + ws);
+                    wp::patch_whole_image_id(s.bytes.data() + at, header_id);
+                    s.off.push_back((int64_t)at); s.size.push_back(ws); s.channel.push_back(2);
+                };
+                if (alone) { header_id = net_->reserve_id(true); f.images[(size_t)d].msg_id = header_id; whole(); continue; }
                 // an image's packets lie back to back behind the buffer's padding: one copy, then the ids
                 const size_t base = s.bytes.size();
                 s.bytes.insert(s.bytes.end(), buf + WP_HEADER_OFFSET, buf + tb[1]);
-                int64_t header_id = 0;
                 for (int k = 0; k < tb[0]; ++k) {
                     const int off = tb[WP_TABLE_HEAD + 2 * k], size = tb[WP_TABLE_HEAD + 2 * k + 1];
                     if (off != (k ? wp::landmark_offset(k - 1) : WP_HEADER_OFFSET) || size != (k ? WP_LANDMARK_BYTES : WP_HEADER_BYTES) || (int64_t)off + size > tb[1])
@@ -939,8 +1029,18 @@ private:
                     else wp::patch_landmark_ids(at, net_->reserve_id(false), header_id);
                     s.off.push_back((int64_t)(base + (size_t)(off - WP_HEADER_OFFSET))); s.size.push_back(size); s.channel.push_back(k ? 1 : 0);
                 }
+                whole();
             }
         }
+    }
+    // an accepted edge as it enters edges(): LoopNet::broadcast_loop_connection (loop_net.cpp:122-127), an outbox entry of its own
+    void queue_loop_conn(const LoopEdge& e) {
+        outbox_.emplace_back();
+        SentFrame& s = outbox_.back();
+        s.msg_id = e.id;
+        publishing_ = &s;
+        try { net_->broadcast_loop_connection(e); } catch (...) { publishing_ = nullptr; throw; }
+        publishing_ = nullptr;
     }
 public:
 
@@ -1468,7 +1568,8 @@ private:
                 ImageDescriptor& im = f.images[d];
                 // extractor_img_desc_deepnet (loop_cam.cpp:525-585) + the stamps of generate_stereo_image_descriptor (:362-374)
                 if (defer_heavy) im.landmark_num = r.n_kps[i]; else heavy(im, i);
-                if (jpg) {                                                          // encode_image (loop_cam.cpp:306-308, 463-469)
+                if (jpg) {                                                          // encode_image (loop_cam.cpp:306-308, 463-469; width and height: :67-70)
+                    im.image_width = cfg_.width; im.image_height = cfg_.height;
                     if (jr.status[i] == OMNI_JPEG_OK) im.image.assign(jr.bytes + (size_t)i * jr.capacity, jr.bytes + (size_t)i * jr.capacity + jr.sizes[i]);
                     else { im.image.clear(); ++jpeg_truncated_; }
                 }
@@ -1690,6 +1791,9 @@ private:
     SentFrame* publishing_ = nullptr;           // where broadcast_fisheye_desc's packets go while finish() runs it
     std::vector<omni_wire_image_meta> wire_meta_;
     int64_t remote_frames_ = 0;
+    std::vector<LoopEdge> remote_edges_;        // SWARM_LOOP_CONN of other drones, in arrival order
+    std::deque<RemoteImage> remote_images_;     // the files of their whole descriptors, at most REMOTE_IMAGES_MAX
+    int64_t remote_images_dropped_ = 0;
     // remote_in_stream: the queue in arrival order, each frame with p = the local key frames handed over before it; next_seq_: local key frames handed over so far;
     // begun_seq_: every local key frame below it has its detector batch begun; remote_in_batch_: remote frames in the batch that is pending
     struct QueuedRemote { FisheyeFrameDescriptor f; int64_t p; };

@@ -18,6 +18,17 @@
 // under complete, lossy and shuffled delivery.
 // Deviations (both asserted by that test): message ids come from a per-object counter mixed with the drone id instead of rand() + nsec
 // (loop_net.cpp:28,81): deterministic; a header always activates its image, also when a landmark packet overtook it (see on_header).
+//
+// The other two message kinds of loop_net.cpp:9-10, under the same rules and with the same caveat (fingerprints of our own, "OMNIIMG1" and "OMNILCN1": byte-level
+// interoperation with a reference drone is UNPINNED, the .lcm files are not vendored):
+//   SWARM_LOOP_IMG_DES   the whole ImageDescriptor_t: behind an image's landmark packets under send_img (without the 64-d descriptors) or send_whole_img_desc
+//                        (with them), alone and whole under is_pc_replay (loop_net.cpp:37-41, 103-116).  ALL landmark_num landmarks, as the reference sends them.
+//                        A fixed head with every scalar and every length member, then the float arrays, then the two byte arrays (csrc/wire_plan.h restates it for
+//                        the GPU, which stores whole dwords).
+//   SWARM_LOOP_CONN      every accepted LoopEdge (loop_net.cpp:122-127, 174-184), a packet of fixed size; doubles travel as their 64 bits.
+// One more deviation: the reference hands every received SWARM_LOOP_IMG_DES to image_desc_callback (:129-140), so the receiver of a send_img drone gets each
+// image twice, the second time without descriptors.  Here a received whole-descriptor packet always reaches image_callback; it enters the frame flow only with
+// accept_img_desc set (what a replay ground station sets) AND when it carries its descriptors.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -25,6 +36,7 @@
 #include <map>
 #include <set>
 
+#include "loop_geometry.hpp"
 #include "omni_swarm.hpp"
 
 namespace omni {
@@ -108,6 +120,77 @@ inline bool decode(const uint8_t* p, size_t n, LandmarkDescriptor& l) {
     return r.ok && r.o == n;
 }
 
+constexpr int64_t FP_IMAGE = 0x4f4d4e49494d4731ll;       // "OMNIIMG1"
+constexpr int64_t FP_LOOP_CONN = 0x4f4d4e494c434e31ll;   // "OMNILCN1"
+constexpr const char* CH_IMG_DES = "SWARM_LOOP_IMG_DES"; // loop_net.cpp:9
+constexpr const char* CH_LOOP_CONN = "SWARM_LOOP_CONN";  // loop_net.cpp:10
+constexpr size_t IMAGE_HEAD_BYTES = 177;                 // the whole descriptor's fixed head: every scalar and every length member
+constexpr size_t LOOP_CONN_BYTES = 276;                  // 8 + 3 x 8 + 3 x 4 + 2 x 8 + 3 x 56 + 6 x 8
+
+// The whole ImageDescriptor.  Head: fingerprint, timestamp, drone_id, msg_id, frame_id, landmark_num, direction, prevent_adding_db, pose_drone, camera_extrinsic,
+// image_width, image_height, image_desc_size, feature_descriptor_size, image_size; then image_desc, feature_descriptor, landmarks_2d_norm, landmarks_2d,
+// landmarks_3d (the three of landmark_num entries each); then landmarks_flag and image.  with_features false: feature_descriptor_size 0 (loop_net.cpp:105-107).
+// An array shorter than landmark_num announces is completed with zeros (as broadcast_img_desc reads flags and 3-D points).
+inline std::vector<uint8_t> encode(const ImageDescriptor& m, bool with_features) {
+    Writer w;
+    const int n = m.landmark_num < 0 ? 0 : m.landmark_num;
+    const size_t fds = with_features ? (size_t)n * 64 : 0;
+    w.i64(FP_IMAGE); w.f64(m.timestamp); w.i32(m.drone_id); w.i64(m.msg_id); w.i64(m.frame_id); w.i32(n); w.i32(m.direction);
+    w.u8(m.prevent_adding_db ? 1 : 0); w.pose(m.pose_drone); w.pose(m.camera_extrinsic);
+    w.i32(m.image_width); w.i32(m.image_height); w.i32((int32_t)m.image_desc.size()); w.i32((int32_t)fds); w.i32((int32_t)m.image.size());
+    for (float v : m.image_desc) w.f32(v);
+    for (size_t i = 0; i < fds; ++i) w.f32(i < m.feature_descriptor.size() ? m.feature_descriptor[i] : 0.f);
+    for (int i = 0; i < n; ++i) { const Point2f p = i < (int)m.landmarks_2d_norm.size() ? m.landmarks_2d_norm[i] : Point2f{0, 0}; w.f32(p.x); w.f32(p.y); }
+    for (int i = 0; i < n; ++i) { const Point2f p = i < (int)m.landmarks_2d.size() ? m.landmarks_2d[i] : Point2f{0, 0}; w.f32(p.x); w.f32(p.y); }
+    for (int i = 0; i < n; ++i) { const Point3f p = i < (int)m.landmarks_3d.size() ? m.landmarks_3d[i] : Point3f{}; w.f32(p.x); w.f32(p.y); w.f32(p.z); }
+    for (int i = 0; i < n; ++i) w.u8(i < (int)m.landmarks_flag.size() ? m.landmarks_flag[i] : 0);
+    w.b.insert(w.b.end(), m.image.begin(), m.image.end());
+    return std::move(w.b);
+}
+// The four length members must account for the packet's size exactly; that is checked before anything is resized.
+inline bool decode(const uint8_t* p, size_t n, ImageDescriptor& m) {
+    Reader r(p, n);
+    if (r.i64() != FP_IMAGE) return false;
+    m.timestamp = r.f64(); m.drone_id = r.i32(); m.msg_id = r.i64(); m.frame_id = r.i64(); m.landmark_num = r.i32(); m.direction = r.i32();
+    m.prevent_adding_db = r.u8() != 0; m.pose_drone = r.pose(); m.camera_extrinsic = r.pose();
+    m.image_width = r.i32(); m.image_height = r.i32();
+    const int32_t ids = r.i32(), fds = r.i32(), isz = r.i32(), k = m.landmark_num;
+    if (!r.ok || k < 0 || ids < 0 || fds < 0 || isz < 0) return false;
+    if ((uint64_t)IMAGE_HEAD_BYTES + 4ull * ((uint64_t)ids + (uint64_t)fds + 7ull * (uint64_t)k) + (uint64_t)k + (uint64_t)isz != (uint64_t)n) return false;
+    m.image_desc.resize(ids); m.feature_descriptor.resize(fds); m.landmarks_2d_norm.resize(k); m.landmarks_2d.resize(k); m.landmarks_3d.resize(k);
+    for (auto& v : m.image_desc) v = r.f32();
+    for (auto& v : m.feature_descriptor) v = r.f32();
+    for (auto& v : m.landmarks_2d_norm) { v.x = r.f32(); v.y = r.f32(); }
+    for (auto& v : m.landmarks_2d) { v.x = r.f32(); v.y = r.f32(); }
+    for (auto& v : m.landmarks_3d) { v.x = r.f32(); v.y = r.f32(); v.z = r.f32(); }
+    if (!r.need((size_t)k + (size_t)isz)) return false;
+    m.landmarks_flag.assign(p + r.o, p + r.o + k); r.o += k;
+    m.image.assign(p + r.o, p + r.o + isz); r.o += isz;
+    return r.ok && r.o == n;
+}
+
+inline void put_pose(Writer& w, const geom::Pose& q) { w.f64(q.pos.x); w.f64(q.pos.y); w.f64(q.pos.z); w.f64(q.att.w); w.f64(q.att.x); w.f64(q.att.y); w.f64(q.att.z); }
+inline void get_pose(Reader& r, geom::Pose& q) { q.pos.x = r.f64(); q.pos.y = r.f64(); q.pos.z = r.f64(); q.att.w = r.f64(); q.att.x = r.f64(); q.att.y = r.f64(); q.att.z = r.f64(); }
+// every field of omni::LoopEdge (loop_geometry.hpp), LOOP_CONN_BYTES in all
+inline std::vector<uint8_t> encode(const LoopEdge& e) {
+    Writer w;
+    w.i64(FP_LOOP_CONN); w.i64(e.id); w.i64(e.keyframe_id_a); w.i64(e.keyframe_id_b); w.i32(e.drone_id_a); w.i32(e.drone_id_b); w.i32(e.pnp_inlier_num);
+    w.f64(e.ts_a); w.f64(e.ts_b); put_pose(w, e.relative_pose); put_pose(w, e.self_pose_a); put_pose(w, e.self_pose_b);
+    for (double v : e.pos_cov) w.f64(v);
+    for (double v : e.ang_cov) w.f64(v);
+    return std::move(w.b);
+}
+inline bool decode(const uint8_t* p, size_t n, LoopEdge& e) {
+    if (n != LOOP_CONN_BYTES) return false;
+    Reader r(p, n);
+    if (r.i64() != FP_LOOP_CONN) return false;
+    e.id = r.i64(); e.keyframe_id_a = r.i64(); e.keyframe_id_b = r.i64(); e.drone_id_a = r.i32(); e.drone_id_b = r.i32(); e.pnp_inlier_num = r.i32();
+    e.ts_a = r.f64(); e.ts_b = r.f64(); get_pose(r, e.relative_pose); get_pose(r, e.self_pose_a); get_pose(r, e.self_pose_b);
+    for (double& v : e.pos_cov) v = r.f64();
+    for (double& v : e.ang_cov) v = r.f64();
+    return r.ok && r.o == n;
+}
+
 }  // namespace wire
 
 class LoopNetWire {
@@ -115,6 +198,7 @@ public:
     static constexpr int FEATURE_DESC_SIZE = 64;         // loop_defines.h:67
     static constexpr size_t IMAGE_DESC_SIZE = 4096;      // MobileNetVLAD's output (loop_defines.h)
     static constexpr int MAX_FEATURES = 4096;            // sanity bound on a header's feature_num (the reference sends <= 200)
+    static constexpr int MAX_IMAGE_BYTES = 1 << 22;      // sanity bound on a whole descriptor's image_size (a q 75 JPEG of a 640 x 480 view is ~60 kB)
     double orphan_timeout = 10.0;                        // landmarks whose header never arrives are forgotten after this many seconds
     double recv_period = 0.5;                            // loop_net.h:33
     int MIN_DIRECTION_LOOP = 3;
@@ -122,19 +206,25 @@ public:
     // false = the reference's key (frame_hash = image.msg_id, loop_net.cpp:144: every image opens a frame of its own, so a received fisheye
     // frame never holds more than one direction); true = key by (drone, frame_id) so that the 4 directions of a key frame meet again
     bool group_by_frame_id = false;
+    // LoopNet(_lcm_uri, send_img, send_whole_img_desc, recv_msg_duration) and IS_PC_REPLAY (loop_net.h, loop_net.cpp:37,103): which images also leave as a whole
+    // descriptor.  accept_img_desc: received whole descriptors that carry their 64-d descriptors enter the frame flow (see the deviation above); off by default
+    bool send_img = false, send_whole_img_desc = false, is_pc_replay = false, accept_img_desc = false;
     // transport: publish(channel, bytes) is called for every outgoing packet; feed incoming packets to on_packet()
     std::function<void(const char* channel, const std::vector<uint8_t>& bytes)> publish;
     std::function<void(const FisheyeFrameDescriptor&)> frame_desc_callback;      // -> LoopDetector::on_image_recv
     std::function<void(int drone_id, float rate)> msg_recv_rate_callback = [](int, float) {};
+    std::function<void(const LoopEdge&)> loopconn_callback;                      // every received edge that is not our own (loop_net.cpp:174-184)
+    std::function<void(const ImageDescriptor&)> image_callback;                  // every received whole descriptor that is not our own (:129-140)
     explicit LoopNetWire(int self_id) : self_id_(self_id) {}
 
     // :19-26
     void broadcast_fisheye_desc(FisheyeFrameDescriptor& f) { for (auto& img : f.images) if (img.landmark_num > 0) broadcast_img_desc(img); }
 
-    // :28-101 (the header + landmark path; the optional whole-ImageDescriptor_t publish of :103-118 is debug transport and left out)
+    // :28-118: the replay early return, the header + landmark packets, then the whole descriptor behind them under send_img / send_whole_img_desc
     int broadcast_img_desc(ImageDescriptor& img) {
         img.msg_id = next_id();
         sent_message.insert(img.msg_id);
+        if (is_pc_replay) { const auto b = wire::encode(img, true); publish(wire::CH_IMG_DES, b); return (int)b.size(); }      // :37-41
         int feature_num = 0;
         for (int i = 0; i < img.landmark_num; ++i) if (i < (int)img.landmarks_flag.size() && img.landmarks_flag[i] > 0) ++feature_num;
         wire::ImageDescriptorHeader h;
@@ -155,8 +245,12 @@ public:
             lm.msg_id = next_id(); lm.header_id = img.msg_id;
             auto b = wire::encode(lm); bytes += b.size(); publish(wire::CH_LANDMARKS, b);
         }
+        if (send_img || send_whole_img_desc) { const auto b = wire::encode(img, send_whole_img_desc); bytes += b.size(); publish(wire::CH_IMG_DES, b); }   // :103-116
         return (int)bytes;
     }
+
+    // :122-127
+    void broadcast_loop_connection(const LoopEdge& e) { sent_message.insert(e.id); publish(wire::CH_LOOP_CONN, wire::encode(e)); }
 
     // lcm.subscribe handlers (:9-13): returns false for packets that do not parse
     // Array lengths come from the network: a landmark must carry exactly FEATURE_DESC_SIZE floats and a header a 4096-float global descriptor
@@ -175,6 +269,22 @@ public:
             if (!wire::decode(data, n, l)) return false;
             if (l.feature_descriptor.size() != (size_t)FEATURE_DESC_SIZE) return false;
             on_landmark(l, now);
+            return true;
+        }
+        // the whole descriptor: LoopDetector reads 4096 / 64 floats per image / landmark here too, so the two float arrays are of those sizes or absent
+        if (std::strcmp(channel, wire::CH_IMG_DES) == 0) {
+            ImageDescriptor m;
+            if (!wire::decode(data, n, m)) return false;
+            if (!(m.image_desc.size() == IMAGE_DESC_SIZE || m.image_desc.empty()) || m.landmark_num > MAX_FEATURES || m.direction < 0 || m.direction >= 4 ||
+                !(m.feature_descriptor.empty() || m.feature_descriptor.size() == (size_t)FEATURE_DESC_SIZE * m.landmark_num) || m.image.size() > (size_t)MAX_IMAGE_BYTES)
+                return false;
+            on_whole_image(m, now);
+            return true;
+        }
+        if (std::strcmp(channel, wire::CH_LOOP_CONN) == 0) {
+            LoopEdge e;
+            if (!wire::decode(data, n, e)) return false;
+            if (!sent_message.count(e.id) && loopconn_callback) loopconn_callback(e);                 // :178-183
             return true;
         }
         return false;
@@ -241,6 +351,19 @@ private:
         ImageDescriptor& t = received_images[m.msg_id];
         t.timestamp = m.timestamp; t.drone_id = m.drone_id; t.image_desc = m.image_desc; t.pose_drone = m.pose_drone; t.camera_extrinsic = m.camera_extrinsic;
         t.landmark_num = m.feature_num; t.frame_id = m.frame_id; t.msg_id = m.msg_id; t.prevent_adding_db = m.prevent_adding_db; t.direction = m.direction;
+    }
+    // :129-140, with the deviation stated at the top.  A whole descriptor that enters the frame flow supersedes what the header + landmark packets of the same
+    // image have assembled so far, and an image those packets already delivered is not delivered again (its id is black-listed).
+    void on_whole_image(const ImageDescriptor& m, double now) {
+        if (sent_message.count(m.msg_id)) return;
+        if (image_callback) image_callback(m);
+        if (!accept_img_desc || m.landmark_num <= 0 || m.feature_descriptor.empty() || blacklist.count(m.msg_id)) return;
+        active_receving_msg.erase(m.msg_id); received_images.erase(m.msg_id); orphan_first_seen.erase(m.msg_id);
+        blacklist.insert(m.msg_id);
+        msg_header_recv_time[m.msg_id] = now;
+        image_desc_callback(m);
+        msg_header_recv_time.erase(m.msg_id);
+        scan_recv_packets(now);
     }
     // :300-324
     void on_landmark(const wire::LandmarkDescriptor& m, double now) {

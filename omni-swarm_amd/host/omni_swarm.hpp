@@ -490,6 +490,13 @@ public:
         check(omni_cam_wire(h_, &r), "omni_cam_wire");
         return r;
     }
+    // the whole descriptor behind those packets (wire_pack_image_kernel): both flags false switch it off; wire_image() after wait()
+    void set_wire_image(bool with_features, bool with_image) { check(omni_cam_set_wire_image(h_, with_features ? 1 : 0, with_image ? 1 : 0), "omni_cam_set_wire_image"); }
+    omni_cam_wire_image_result wire_image() {
+        omni_cam_wire_image_result r{};
+        check(omni_cam_wire_image(h_, &r), "omni_cam_wire_image");
+        return r;
+    }
     // non-blocking: would wait() return at once?
     bool ready() { int r = 0; check(omni_cam_ready(h_, &r), "omni_cam_ready"); return r != 0; }
     // blocks until the key frame is done; pointers stay valid until the next enqueue on this object

@@ -266,6 +266,7 @@ struct SwarmLoopParams {
     }
     template <class Wire> void to_wire(Wire& w) const {                    // LoopNet(_lcm_uri, send_img, send_whole_img_desc, recv_msg_duration), swarm_loop.cpp:309
         w.recv_period = recv_msg_duration; w.MIN_DIRECTION_LOOP = min_direction_loop; w.SEND_ALL_FEATURES = send_all_features;
+        w.send_img = send_img; w.send_whole_img_desc = send_whole_img_desc; w.is_pc_replay = is_pc_replay;      // loop_net.cpp:37, 103 (IS_PC_REPLAY: loop_params.cpp)
     }
 
     std::vector<std::string> type_mismatches;      // parameters a launch file set with a type param<T> refuses: they kept their defaults

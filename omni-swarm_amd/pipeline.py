@@ -42,8 +42,18 @@ _jpeg_lib = None
 WIRE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_wire.so")
 WIRE_SYMBOLS = ["omni_wire_host_last_error", "omni_pipeline_set_wire", "omni_pipeline_get_wire", "omni_pipeline_wire_pending", "omni_pipeline_take_packets",
                 "omni_pipeline_set_wire_recv", "omni_pipeline_recv_packet", "omni_pipeline_scan_recv", "omni_pipeline_remote_frames", "omni_pipeline_wire_host_ms"]
-WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")      # include/omni_host_wire.h OMNI_WIRE_CHANNEL_*
+WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS", "SWARM_LOOP_IMG_DES", "SWARM_LOOP_CONN")      # include/omni_host_wire.h, omni_host_wire_messages.h OMNI_WIRE_CHANNEL_*
 _wire_lib = None
+WIREMSG_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_wiremsg.so")
+WIREMSG_SYMBOLS = ["omni_wiremsg_last_error", "omni_pipeline_set_wire_messages", "omni_pipeline_get_wire_messages", "omni_pipeline_set_wire_accept_img_desc",
+                   "omni_pipeline_get_remote_edges", "omni_pipeline_remote_image_pending", "omni_pipeline_take_remote_image"]
+WIRE_IMG_OFF, WIRE_IMG_IMAGE, WIRE_IMG_WHOLE, WIRE_IMG_PC_REPLAY = range(4)      # include/omni_host_wire_messages.h OMNI_WIRE_IMG_*
+WIRE_IMG_MODES = {"off": 0, "image": 1, "whole": 2, "pc_replay": 3}
+WIRE_REMOTE_IMAGES_MAX = 64
+REMOTE_EDGE_DTYPE = np.dtype([("id", "<i8"), ("keyframe_id_a", "<i8"), ("keyframe_id_b", "<i8"), ("drone_id_a", "<i4"), ("drone_id_b", "<i4"), ("pnp_inlier_num", "<i4"),
+                              ("reserved", "<i4"), ("ts_a", "<f8"), ("ts_b", "<f8"), ("relative_pose", "<f8", (7,)), ("self_pose_a", "<f8", (7,)), ("self_pose_b", "<f8", (7,)),
+                              ("pos_cov", "<f8", (3,)), ("ang_cov", "<f8", (3,))])      # omni_remote_edge
+_wiremsg_lib = None
 # remote key frames joining the unit stream: include/omni_host_remote.h, lib/libomni_host_remote.so (the same handle)
 REMOTE_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_remote.so")
 REMOTE_SYMBOLS = ["omni_remote_last_error", "omni_pipeline_set_remote_in_stream", "omni_pipeline_get_remote_in_stream", "omni_pipeline_remote_pending",
@@ -373,6 +383,26 @@ def wire_lib():
     return _wire_lib
 
 
+def wiremsg_lib():
+    global _wiremsg_lib
+    if _wiremsg_lib is None:
+        lib()
+        if not os.path.exists(WIREMSG_LIB_PATH):
+            raise OSError(f"{WIREMSG_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(WIREMSG_LIB_PATH)
+        L.omni_wiremsg_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_wire_messages.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.omni_pipeline_get_wire_messages.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.omni_pipeline_set_wire_accept_img_desc.argtypes = [C.c_void_p, C.c_int]
+        L.omni_pipeline_get_remote_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.omni_pipeline_remote_image_pending.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_pipeline_remote_image_pending.restype = C.c_int64
+        L.omni_pipeline_take_remote_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _wiremsg_lib = L
+    return _wiremsg_lib
+
+
 def remote_lib():
     global _remote_lib
     if _remote_lib is None:
@@ -459,7 +489,8 @@ class KeyframePipeline:
                  thres=0.02, max_num=200, precision=capi.PREC_F16, microbatch=8, pipelines=0, storage=capi.STORE_F32, self_id=1,
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
-                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False, batch_verify=False):
+                 device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False, batch_verify=False,
+                 wire_img_desc="off", wire_loop_conn=False):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -487,6 +518,10 @@ class KeyframePipeline:
         a PCA fit on the GPU (csrc/pca_fit.hip); pca_fit / pca_fit_write make components_.csv / mean_.csv of them.  Results do not depend on it.  Default off.
         wire / device_wire / send_all_features: the LoopNet wire (set_wire): every finished key frame leaves as LoopNet's packets (take_packets) and packets of
         other drones enter through recv_packet / scan_recv; device_wire packs the packets inside the key-frame unit on the GPU (the same bytes).  Default off.
+        wire_img_desc / wire_loop_conn: LoopNet's other two message kinds on that wire (set_wire_messages).  "image" / "whole" / "pc_replay": an image's whole
+        descriptor leaves behind its landmark packets without its 64-d descriptors and with its JPEG file (needs send_img) / with the descriptors, and with the
+        file when send_img is on / alone; with device_wire it is packed inside the unit too.  wire_loop_conn: every accepted edge leaves as a packet of its own,
+        and edges of other drones arrive in remote_edges().  Default off.
         remote_in_stream: key frames of other drones (the wire's, or queue_copy_as_remote's) are queued and join the next key-frame unit's detector batch at
         their place in the serial order, their rows gathered with the unit's on the GPU (csrc/rows_assemble.hip), instead of stopping the pipeline with a flush
         each; the same candidates, edges and rows (set_remote_in_stream).  Default off.
@@ -541,6 +576,8 @@ class KeyframePipeline:
             self.set_fit_pca(True)
         if wire or device_wire:
             self.set_wire(wire, device_wire, send_all_features)
+        if WIRE_IMG_MODES.get(wire_img_desc, wire_img_desc) or wire_loop_conn:
+            self.set_wire_messages(wire_img_desc, wire_loop_conn)
         if remote_in_stream:
             self.set_remote_in_stream(True)
         if batch_verify:
@@ -741,6 +778,53 @@ class KeyframePipeline:
         ms = C.c_double(0)
         self._wire(wire_lib().omni_pipeline_wire_host_ms(self.h, C.byref(ms), int(reset)), "omni_pipeline_wire_host_ms")
         return ms.value
+
+    def _wiremsg(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {wiremsg_lib().omni_wiremsg_last_error().decode()}")
+
+    def set_wire_messages(self, wire_img_desc="off", wire_loop_conn: bool = False):
+        """LoopNet's other two message kinds (include/omni_host_wire_messages.h).  wire_img_desc: "off" / "image" / "whole" / "pc_replay" (or WIRE_IMG_*).  Before the
+        first key frame, with the wire on; "image" needs send_img"""
+        mode = WIRE_IMG_MODES[wire_img_desc] if isinstance(wire_img_desc, str) else int(wire_img_desc)
+        self._wiremsg(wiremsg_lib().omni_pipeline_set_wire_messages(self.h, mode, int(bool(wire_loop_conn))), "omni_pipeline_set_wire_messages")
+
+    def wire_messages(self):
+        """(wire_img_desc as WIRE_IMG_*, wire_loop_conn, accept_img_desc)"""
+        v = [C.c_int(0) for _ in range(3)]
+        self._wiremsg(wiremsg_lib().omni_pipeline_get_wire_messages(self.h, *[C.byref(x) for x in v]), "omni_pipeline_get_wire_messages")
+        return v[0].value, bool(v[1].value), bool(v[2].value)
+
+    def set_wire_accept_img_desc(self, on: bool):
+        """received whole descriptors that carry their 64-d descriptors enter the frame flow (what a replay ground station sets); default off"""
+        self._wiremsg(wiremsg_lib().omni_pipeline_set_wire_accept_img_desc(self.h, int(bool(on))), "omni_pipeline_set_wire_accept_img_desc")
+
+    def remote_edges(self) -> np.ndarray:
+        """the edges other drones sent so far (REMOTE_EDGE_DTYPE records, every field of a LoopEdge, the doubles bit for bit), in arrival order"""
+        n = C.c_int(0)
+        self._wiremsg(wiremsg_lib().omni_pipeline_get_remote_edges(self.h, None, 0, C.byref(n)), "omni_pipeline_get_remote_edges")
+        out = np.zeros(n.value, REMOTE_EDGE_DTYPE)
+        if n.value:
+            self._wiremsg(wiremsg_lib().omni_pipeline_get_remote_edges(self.h, out.ctypes.data, len(out), C.byref(n)), "omni_pipeline_get_remote_edges")
+        return out
+
+    def remote_images_pending(self):
+        """(images waiting for take_remote_image, images dropped so far because more than WIRE_REMOTE_IMAGES_MAX waited)"""
+        dropped = C.c_int64(0)
+        return int(wiremsg_lib().omni_pipeline_remote_image_pending(self.h, C.byref(dropped))), int(dropped.value)
+
+    def take_remote_image(self):
+        """pops the oldest JPEG file another drone sent inside a whole descriptor: dict(drone_id, frame_id, direction, width, height, bytes); None when none waits"""
+        L = wiremsg_lib()
+        if L.omni_pipeline_remote_image_pending(self.h, None) <= 0:
+            return None
+        nb = C.c_int64(0)
+        self._wiremsg(L.omni_pipeline_take_remote_image(self.h, None, 0, C.byref(nb), None, None, None, None, None), "omni_pipeline_take_remote_image")
+        buf = np.empty(max(nb.value, 1), np.uint8)
+        drone, direction, w, h, frame = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._wiremsg(L.omni_pipeline_take_remote_image(self.h, buf.ctypes.data, buf.size, C.byref(nb), C.byref(drone), C.byref(frame), C.byref(direction), C.byref(w),
+                                                        C.byref(h)), "omni_pipeline_take_remote_image")
+        return {"drone_id": drone.value, "frame_id": frame.value, "direction": direction.value, "width": w.value, "height": h.value, "bytes": buf[:nb.value].tobytes()}
 
     def _remote(self, rc, what):
         if rc:
