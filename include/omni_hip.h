@@ -1005,6 +1005,54 @@ int     omni_rows_assemble_host(int64_t n_rows, int dim, const omni_row_source* 
 /* PINNED host memory -> device on the context's stream, without waiting (omni_memcpy_d2h_async's twin): src_pinned stays untouched until the copy has run */
 int     omni_memcpy_h2d_async(omni_ctx* ctx, void* dst_dev, const void* src_pinned, size_t bytes);
 
+/* ---- pairwise consistency of loop edges (PCM): SwarmLocalOutlierRejection::OutlierRejectionLoopEdgesPCM, swarm_localization/src/swarm_outlier_rejection/
+ * swarm_outlier_rejection.cpp:173-298, the consistency rows on the GPU and the clique heuristic on the host -----------------------------------------------------------
+ * The arithmetic is csrc/pcm_plan.h's and nothing else restates it: per pair of edges four pose compositions in f64, the log map of
+ * LoopGeometry::check_loop_odometry_consistency with the header's OWN arctangent, and the squared Mahalanobis distance under summed diagonal covariances.  swarm_msgs
+ * (Swarm::Pose, DroneTrajectory) is not vendored: parity with the reference is unpinned and the header is the specification.  An edge: */
+typedef struct omni_pcm_edge {
+    int64_t id;
+    int32_t drone_a, drone_b;
+    double  relative_pose[7];                /* xyz + quaternion wxyz (unit): b's frame in a's, as LoopEdge::relative_pose */
+    double  self_pose_a[7], self_pose_b[7];  /* each drone's own odometry pose at the edge's frame */
+    double  arc_a, arc_b;                    /* cumulative path length of drone a / b at the edge's frame (metres) */
+    double  pos_cov[3], ang_cov[3];          /* the edge's covariance diagonal */
+} omni_pcm_edge;
+typedef struct omni_pcm_params {
+    double pcm_thres;                        /* a pair is consistent iff smd < pcm_thres (0.6: swarm_localization_node.cpp:475) */
+    double pos_covariance_per_meter;         /* cov(odom) = |arc difference| * (pos x3, yaw x3)   (0.01 / 0.003: swarm_loop.cpp:247-248) */
+    double yaw_covariance_per_meter;
+} omni_pcm_params;
+#define OMNI_PCM_FULL 100                    /* omni_pcm_add: the handle cannot take n more edges; nothing was changed (a status, not an error: no message is set) */
+#define OMNI_PCM_MAX_ADD 64
+#define OMNI_PCM_MIN_CAPACITY 64
+#define OMNI_PCM_MAX_CAPACITY 32768
+#define OMNI_PCM_DEFAULT_CAPACITY 4096
+typedef struct omni_pcm omni_pcm;
+/* A handle owns one graph in HBM: the edges as structure-of-arrays and a square bit matrix of `capacity` rows of capacity / 64 words (bit j & 63 of word j >> 6 of row
+ * i: edges i and j are consistent; the diagonal is 0).  capacity: a multiple of 64 in 64 .. 32768. */
+int          omni_pcm_create(omni_ctx* ctx, int capacity, const omni_pcm_params* params, omni_pcm** out);
+void         omni_pcm_destroy(omni_pcm* pcm);
+int          omni_pcm_size(const omni_pcm* pcm);
+int          omni_pcm_capacity(const omni_pcm* pcm);
+/* Appends n edges (1 .. 64) as vertices size .. size + n - 1 and compares each with EVERY earlier one, those of this call included: one upload, four launches (the
+ * records into the arrays; one lane per pair and a ballot per row word; the mirrored bits; the block that travels back), one download.  Blocking.  degrees_out [size + n]: every vertex's degree
+ * after the call.  rows_out [n][capacity / 64]: the new vertices' rows after the call, both triangles.  *kernel_us (may be NULL): the launches' time between two events.
+ * Returns OMNI_PCM_FULL when size + n > capacity.  Refused: a null argument, n outside 1..64. */
+int          omni_pcm_add(omni_pcm* pcm, const omni_pcm_edge* edges, int n, int32_t* degrees_out, uint64_t* rows_out, float* kernel_us);
+/* rows [first, first + n_rows) of the bit matrix and the degrees of the first size vertices (either output may be NULL), for tests */
+int          omni_pcm_adjacency(omni_pcm* pcm, int first, int n_rows, uint64_t* rows_out, int32_t* degrees_out);
+/* csrc/pcm_plan.h compiled by g++ into the library: edges [n_total] in host memory, vertices [first, n_total) are the new ones.  rows_out [n_total - first][stride_words]
+ * (stride_words * 64 >= n_total): their rows, both triangles; degree_add [n_total]: the consistent pairs this call found at each vertex (first == 0: the degrees).
+ * smd_out (may be NULL) [n_total - first][n_total]: the distance of every pair (i, j < i), NaN bits included, 0 where same_robot_pair is 0 or j >= i.  No GPU, no context. */
+int          omni_pcm_rows_host(const omni_pcm_edge* edges, int n_total, int first, const omni_pcm_params* params, int stride_words, uint64_t* rows_out,
+                                int32_t* degree_add, double* smd_out);
+/* The clique heuristic of csrc/pcm_plan.h on the rows of n vertices (row v at rows + v * stride_words; bits at or above n must be 0): clique_out [n] receives the
+ * vertices of the clique found, the start vertex first, *size_out their number. */
+int          omni_pcm_max_clique_host(const uint64_t* rows, int n, int stride_words, int32_t* clique_out, int* size_out);
+/* the header's arctangent (tests): atan2(y, x) */
+double       omni_pcm_atan2(double y, double x);
+
 #ifdef __cplusplus
 }
 #endif

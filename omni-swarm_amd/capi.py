@@ -57,7 +57,12 @@ SYMBOLS = [
     "omni_wire_image_capacity", "omni_wire_pack_image_enqueue_dev", "omni_wire_pack_image_host", "omni_cam_set_wire_image", "omni_cam_wire_image",
     "omni_rows_assemble_enqueue_dev", "omni_rows_assemble_host", "omni_memcpy_h2d_async",
     "omni_corr_assemble_host", "omni_corr_assemble_multi", "omni_bf_match_homography_corr_multi",
+    "omni_pcm_create", "omni_pcm_destroy", "omni_pcm_size", "omni_pcm_capacity", "omni_pcm_add", "omni_pcm_adjacency", "omni_pcm_rows_host", "omni_pcm_max_clique_host", "omni_pcm_atan2",
 ]
+PCM_FULL, PCM_MAX_ADD, PCM_DEFAULT_CAPACITY = 100, 64, 4096      # include/omni_hip.h OMNI_PCM_*
+# include/omni_hip.h omni_pcm_edge as a numpy record: poses are xyz + quaternion wxyz
+PCM_EDGE_DTYPE = np.dtype([("id", "<i8"), ("drone_a", "<i4"), ("drone_b", "<i4"), ("relative_pose", "<f8", (7,)), ("self_pose_a", "<f8", (7,)), ("self_pose_b", "<f8", (7,)),
+                           ("arc_a", "<f8"), ("arc_b", "<f8"), ("pos_cov", "<f8", (3,)), ("ang_cov", "<f8", (3,))])
 ROW_UNIT, ROW_STAGED, ROW_ZERO = 0, 1, 2      # include/omni_hip.h OMNI_ROW_*: where a row of a mixed detector batch comes from
 WIRE_HEADER_BYTES, WIRE_LANDMARK_BYTES, WIRE_HEADER_OFFSET = 16545, 324, 3      # include/omni_hip.h OMNI_WIRE_*
 WIRE_CHANNELS = ("VIOKF_HEADER", "VIOKF_LANDMARKS")                            # packet 0 of an image / every other packet
@@ -81,6 +86,10 @@ class _SpWeights(C.Structure):
 class _VladLayer(C.Structure):
     _fields_ = [("kind", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("stride", C.c_int),
                 ("weight", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float))]
+
+
+class PcmParams(C.Structure):     # include/omni_hip.h omni_pcm_params
+    _fields_ = [("pcm_thres", C.c_double), ("pos_covariance_per_meter", C.c_double), ("yaw_covariance_per_meter", C.c_double)]
 
 
 class CorrCand(C.Structure):      # include/omni_hip.h omni_corr_cand
@@ -522,6 +531,15 @@ def lib():
     sig("omni_pcafit_solve", C.c_int, [_vp, C.c_int, _dp, _fp, _dp, _fp, _dp, _dp])
     sig("omni_pca_moments_host", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _i64p, _i64p, _dp, _dp])
     sig("omni_pca_write_csv", C.c_int, [C.c_char_p, C.c_char_p, _fp, _fp, C.c_int])
+    sig("omni_pcm_create", C.c_int, [_vp, C.c_int, C.POINTER(PcmParams), C.POINTER(_vp)])
+    sig("omni_pcm_destroy", None, [_vp])
+    sig("omni_pcm_size", C.c_int, [_vp])
+    sig("omni_pcm_capacity", C.c_int, [_vp])
+    sig("omni_pcm_add", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _fp])
+    sig("omni_pcm_adjacency", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp])
+    sig("omni_pcm_rows_host", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(PcmParams), C.c_int, _vp, _vp, _vp])
+    sig("omni_pcm_max_clique_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _ip])
+    sig("omni_pcm_atan2", C.c_double, [C.c_double, C.c_double])
     if L.omni_abi_version() != ABI_VERSION:
         raise OmniError("libomni_hip.so ABI version mismatch")
     _lib = L
@@ -1202,6 +1220,93 @@ class Resize:
 
 
 RESIZE_COPY, RESIZE_AREA2, RESIZE_LINEAR = 0, 1, 2
+
+
+def pcm_params(pcm_thres: float = 0.6, pos_covariance_per_meter: float = 0.01, yaw_covariance_per_meter: float = 0.003) -> PcmParams:
+    return PcmParams(pcm_thres, pos_covariance_per_meter, yaw_covariance_per_meter)
+
+
+def _pcm_edges(edges) -> np.ndarray:
+    e = np.ascontiguousarray(edges, dtype=PCM_EDGE_DTYPE).reshape(-1)
+    assert PCM_EDGE_DTYPE.itemsize == 248
+    return e
+
+
+def pcm_rows_host(edges, first: int = 0, params: PcmParams | None = None, stride_words: int = 0, with_smd: bool = False):
+    """csrc/pcm_plan.h under g++ (omni_pcm_rows_host): edges[first:] are the new vertices.  Returns (rows [n - first][stride_words] u64, degree_add [n] i32) and, with
+    with_smd, the distance of every pair (i, j < i) as a third array [n - first][n]."""
+    e = _pcm_edges(edges)
+    n = len(e)
+    stride = stride_words or max(1, (n + 63) // 64)
+    pr = params or pcm_params()
+    rows = np.zeros((max(n - first, 0), stride), np.uint64)
+    deg = np.zeros(max(n, 1), np.int32)
+    smd = np.zeros((max(n - first, 0), max(n, 1)), np.float64) if with_smd else None
+    _check(lib().omni_pcm_rows_host(e.ctypes.data, n, first, C.byref(pr), stride, rows.ctypes.data, deg.ctypes.data, smd.ctypes.data if with_smd else None))
+    return (rows, deg[:n], smd) if with_smd else (rows, deg[:n])
+
+
+def pcm_max_clique_host(rows: np.ndarray, n: int | None = None) -> np.ndarray:
+    """The clique heuristic of csrc/pcm_plan.h on bitset rows [>= n][stride_words] u64: the vertices of the clique found, the start vertex first."""
+    r = np.ascontiguousarray(rows, np.uint64)
+    n = r.shape[0] if n is None else n
+    out = np.zeros(max(n, 1), np.int32)
+    size = C.c_int(0)
+    _check(lib().omni_pcm_max_clique_host(r.ctypes.data, n, r.shape[1] if r.ndim == 2 and r.shape[1] else 1, out.ctypes.data, C.byref(size)))
+    return out[:size.value].copy()
+
+
+def pcm_atan2(y: float, x: float) -> float:
+    return lib().omni_pcm_atan2(y, x)
+
+
+class Pcm:
+    """omni_pcm: the pairwise-consistency graph of one drone pair's loop edges in HBM (csrc/pcm.hip; the arithmetic is csrc/pcm_plan.h's).  add() appends 1..64 edges
+    and returns the degrees of all vertices and the new vertices' rows, or None when the handle is full (OMNI_PCM_FULL: nothing changed)."""
+
+    def __init__(self, ctx: Context, capacity: int = PCM_DEFAULT_CAPACITY, params: PcmParams | None = None):
+        self.ctx, self.capacity, self.params = ctx, capacity, params or pcm_params()
+        h = _vp()
+        _check(lib().omni_pcm_create(ctx.h, capacity, C.byref(self.params), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        self.last_kernel_us = 0.0
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().omni_pcm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self) -> int:
+        return lib().omni_pcm_size(self.h)
+
+    def add(self, edges, time_kernel: bool = False):
+        e = _pcm_edges(edges)
+        n, held, words = len(e), self.size, self.capacity // 64
+        deg = np.zeros(held + max(n, 1), np.int32)
+        rows = np.zeros((max(n, 1), words), np.uint64)
+        us = C.c_float(0)
+        rc = lib().omni_pcm_add(self.h, e.ctypes.data, n, deg.ctypes.data, rows.ctypes.data, C.byref(us) if time_kernel else None)
+        if rc == PCM_FULL:
+            return None
+        _check(rc)
+        self.last_kernel_us = us.value
+        return deg[:held + n], rows[:n]
+
+    def adjacency(self, first: int = 0, n_rows: int | None = None):
+        """(rows [n_rows][capacity / 64] u64 as they lie in HBM, degrees [size] i32)"""
+        n_rows = self.size - first if n_rows is None else n_rows
+        rows = np.zeros((max(n_rows, 1), self.capacity // 64), np.uint64)
+        deg = np.zeros(max(self.size, 1), np.int32)
+        _check(lib().omni_pcm_adjacency(self.h, first, n_rows, rows.ctypes.data, deg.ctypes.data))
+        return rows[:n_rows], deg[:self.size]
 
 
 def jpeg_header(width: int, height: int, quality: int) -> bytes:

@@ -21,6 +21,7 @@
 #include "fisheye_flatten.hpp"
 #include "loop_geometry.hpp"
 #include "loop_net_wire.hpp"
+#include "loop_outlier_rejection.hpp"
 #include "omni_swarm.hpp"
 #include "remote_queue.hpp"
 
@@ -136,6 +137,16 @@ public:
         // crossing of inter_drone_init_frames).  Candidates, edges and their ids, counters and rows are the switch-off flow's.  Independent of remote_in_stream; the
         // sharded database, which builds no messages, refuses it.  (set_batch_verify: between two calls, while no detector batch is pending.)
         bool batch_verify = false;
+        // `geometry`: pairwise-consistency outlier rejection of the loop edges (SwarmLocalOutlierRejection::OutlierRejectionLoopEdges, swarm_localization/src/
+        // swarm_outlier_rejection/swarm_outlier_rejection.cpp:98-298; host/loop_outlier_rejection.hpp).  Every edge that enters edges() or remote_edges() is compared
+        // with every earlier edge of its drone pair on the GPU (csrc/pcm.hip; the arithmetic is csrc/pcm_plan.h's), the clique heuristic runs on the host, and
+        // good_edges() lists the edges that agree with each other.  The stage only ADDS an output: edges(), candidates, counters and rows are what they are without
+        // it.  pcm_thres: the reference's default (swarm_localization_node.cpp:475); pcm_redundant: every drone pair is evaluated, not only those with this drone at
+        // one end (:122-139); pcm_capacity: edges per drone pair (a multiple of 64 in 64..32768).  The odometry covariance per metre of path is the reference's
+        // swarm_loop.cpp:247-248.  Off by default.  The sharded database, which builds no messages, refuses it.  (set_pcm: before the first key frame.)
+        bool pcm = false, pcm_redundant = false;
+        double pcm_thres = 0.6, pcm_pos_covariance_per_meter = 0.01, pcm_yaw_covariance_per_meter = 0.003;
+        int pcm_capacity = OMNI_PCM_DEFAULT_CAPACITY;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -311,6 +322,7 @@ private:
             };
             if (c.batch_verify) apply_batch_verify(true);
         }
+        if (c.pcm) { cfg_.pcm = false; set_pcm(true, c.pcm_thres, c.pcm_redundant, c.pcm_capacity); }
     }
     // Config::batch_verify: the detector's late-verdict hooks.  A ticket is a place in deferred_; a resolve is one start_geometry + drain_geometry over everything
     // deferred so far -- the candidates between two frames of this drone that came before included, so the edge order is the candidate order
@@ -342,6 +354,82 @@ public:
         cfg_.batch_verify = on;
         apply_batch_verify(on);
     }
+    // ---- pairwise-consistency outlier rejection of the loop edges (Config::pcm) ---------------------------------------------------------------------------------
+    bool pcm() const { return cfg_.pcm; }
+    double pcm_thres() const { return cfg_.pcm_thres; }
+    bool pcm_redundant() const { return cfg_.pcm_redundant; }
+    int pcm_capacity() const { return cfg_.pcm_capacity; }
+    // before the first key frame (what the C entry point omni_pipeline_set_pcm sets)
+    void set_pcm(bool on, double thres, bool redundant, int capacity) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_pcm after the first key frame");
+        if (on && shard_) throw std::runtime_error("set_pcm: the sharded database builds no messages");
+        if (on && !cfg_.geometry) throw std::runtime_error("set_pcm: the pipeline has no geometry stage");
+        if (on && !(thres > 0)) throw std::invalid_argument("set_pcm: pcm_thres must be positive");
+        if (!on) { pcm_.reset(); pcm_ctx_.reset(); cfg_.pcm = false; return; }
+        LoopOutlierRejection::Params p;
+        p.self_id = cfg_.self_id; p.redundant = redundant; p.capacity = capacity;
+        p.pcm = omni_pcm_params{thres, cfg_.pcm_pos_covariance_per_meter, cfg_.pcm_yaw_covariance_per_meter};
+        // omni_pcm_add is blocking: a stream of its own, not the detector's, and a high-priority one -- short work the host waits on next to units that fill the GPU
+        if (!pcm_ctx_) pcm_ctx_ = std::make_unique<Context>(cfg_.device, true);
+        pcm_ = std::make_unique<LoopOutlierRejection>(pcm_ctx_->get(), p);       // (refuses the capacity)
+        cfg_.pcm = true; cfg_.pcm_thres = thres; cfg_.pcm_redundant = redundant; cfg_.pcm_capacity = capacity;
+    }
+    // edges() and remote_edges(), in that order, without those the stage rejected.  An edge one of whose frames this pipeline never saw is outside the graph and
+    // passes.  Without the stage: all of them.
+    std::vector<LoopEdge> good_edges() {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        pcm_feed();
+        std::vector<LoopEdge> out;
+        for (const std::vector<LoopEdge>* v : {&edges_, &remote_edges_})
+            for (const LoopEdge& e : *v)
+                if (!pcm_ || pcm_outside_.count(e.id) || pcm_->good(e.id, e.drone_id_a, e.drone_id_b)) out.push_back(e);
+        return out;
+    }
+    // [0] edges entered, [1] pairs evaluated, [2] consistent pairs, [3] clique runs, [4] edges left out because the pipeline never saw one of their frames, [5] edges
+    // that met a full handle
+    void pcm_stats(int64_t out[6]) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        pcm_feed();
+        for (int i = 0; i < 6; ++i) out[i] = pcm_ ? pcm_->stats().v[i] : 0;
+        out[4] = pcm_unknown_;
+    }
+    // the records the stage entered so far, in the order they entered (what a host recomputation takes: tests)
+    const std::vector<omni_pcm_edge>& pcm_records() { std::lock_guard<std::mutex> lk(intake_mu_); pcm_feed(); return pcm_records_; }
+private:
+    // the cumulative path length of a drone at the key frames this pipeline saw, local and remote, from their pose_drone in the order they came
+    void pcm_note_frame(int drone, int64_t kf_id, const PoseMsg& pose) {
+        if (!pcm_) return;
+        PcmPath& t = pcm_path_[drone];
+        if (t.any) { const double dx = pose.position[0] - t.last[0], dy = pose.position[1] - t.last[1], dz = pose.position[2] - t.last[2]; t.length += std::sqrt(dx * dx + dy * dy + dz * dz); }
+        t.any = true; t.last[0] = pose.position[0]; t.last[1] = pose.position[1]; t.last[2] = pose.position[2];
+        pcm_arc_[{drone, kf_id}] = t.length;
+    }
+    // the new edges of edges() and remote_edges() enter the stage: after every detector batch and every drained inbox, and before the stage's outputs are read
+    void pcm_feed() {
+        if (!pcm_ || (pcm_fed_local_ == edges_.size() && pcm_fed_remote_ == remote_edges_.size())) return;
+        std::vector<omni_pcm_edge> batch;
+        auto put = [](double* o, const geom::Pose& q) { o[0] = q.pos.x; o[1] = q.pos.y; o[2] = q.pos.z; o[3] = q.att.w; o[4] = q.att.x; o[5] = q.att.y; o[6] = q.att.z; };
+        auto take = [&](const std::vector<LoopEdge>& v, size_t& fed) {
+            for (; fed < v.size(); ++fed) {
+                const LoopEdge& e = v[fed];
+                const auto a = pcm_arc_.find({e.drone_id_a, e.keyframe_id_a}), b = pcm_arc_.find({e.drone_id_b, e.keyframe_id_b});
+                if (a == pcm_arc_.end() || b == pcm_arc_.end()) { ++pcm_unknown_; pcm_outside_.insert(e.id); continue; }
+                omni_pcm_edge r;
+                r.id = e.id; r.drone_a = e.drone_id_a; r.drone_b = e.drone_id_b;
+                put(r.relative_pose, e.relative_pose); put(r.self_pose_a, e.self_pose_a); put(r.self_pose_b, e.self_pose_b);
+                r.arc_a = a->second; r.arc_b = b->second;
+                for (int k = 0; k < 3; ++k) { r.pos_cov[k] = e.pos_cov[k]; r.ang_cov[k] = e.ang_cov[k]; }
+                batch.push_back(r);
+            }
+        };
+        take(edges_, pcm_fed_local_);
+        take(remote_edges_, pcm_fed_remote_);
+        if (batch.empty()) return;
+        pcm_records_.insert(pcm_records_.end(), batch.begin(), batch.end());
+        pcm_->add(batch);
+    }
+public:
     // [0] inter-drone candidates deferred, [1] resolves at the end of a detector batch (a frame outside a batch is a batch of one), [2] early resolves forced by
     // the rule, [3] matcher round trips spent on [1] and [2]
     // candidates whose correspondences the round trip assembled so far, and candidates it handed back to the host functions
@@ -965,6 +1053,7 @@ private:
             { std::lock_guard<std::mutex> lk(intake_mu_); carried_hits_ += hits; }
             on_remote_frame(f);
         }
+        pcm_feed();
     }
     // finish(): the unit's key frames leave as packets -- broadcast_fisheye_desc on the calling thread, or the unit's own packed bytes with the ids patched in
     void wire_out(Lane& lane) {
@@ -1055,8 +1144,10 @@ public:
         // remote_in_stream: frames queued earlier (and the batch that holds some) come first, so the order is kept
         if (cfg_.remote_in_stream && (!remote_queue_.empty() || det_pending_.active)) carried_hits_ += flush_locked();
         collect_geometry();
+        pcm_note_frame(f.drone_id, f.msg_id, f.pose_drone);
         const LoopCandidate r = det_.on_image_recv(f);
         collect_geometry();
+        pcm_feed();
         if (r.found) candidates_.push_back({f.msg_id, r.old_msg_id, r.direction_new, r.direction_old});
         return r;
     }
@@ -1078,6 +1169,7 @@ public:
         if (shard_) throw std::runtime_error("queue_remote_frame: the sharded database builds no messages");
         if (!cfg_.remote_in_stream) throw std::runtime_error("queue_remote_frame: remote_in_stream is off (set_remote_in_stream)");
         if (f.drone_id == cfg_.self_id) throw std::invalid_argument("queue_remote_frame: the frame carries this drone's own id");
+        pcm_note_frame(f.drone_id, f.msg_id, f.pose_drone);
         remote_queue_.push_back({std::move(f), next_seq_});
         ++remote_stats_[0];
         begin_remote_batch();
@@ -1107,6 +1199,7 @@ public:
         if (cfg_.wire) throw std::runtime_error("attach_shard: the wire does not run on the sharded database, which builds no messages");
         if (cfg_.remote_in_stream) throw std::runtime_error("attach_shard: remote_in_stream does not run on the sharded database, which builds no messages");
         if (cfg_.batch_verify) throw std::runtime_error("attach_shard: batch_verify does not run on the sharded database, which builds no messages");
+        if (cfg_.pcm) throw std::runtime_error("attach_shard: pcm does not run on the sharded database, which builds no messages");
         if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
@@ -1511,6 +1604,7 @@ private:
         det_.held_frames().clear();
         if (!left && det_pending_.timed) latencies_ms_.push_back(since(det_pending_.t_enqueue));        // (otherwise drain_geometry() records it, when the micro-batch's last edge is in)
         host_ms_[4] += since(t_a);
+        pcm_feed();                                      // Config::pcm: the edges drained so far enter the stage
         return hits;
     }
     // the micro-batch's key frames reach the detector in order, as one batch; rows and queries are taken from MobileNetVLAD's output
@@ -1605,6 +1699,7 @@ private:
                 }
             }
             finish_frame_descriptor(f, stamp, kf_id, pose, cfg_.self_id);             // on_flattened_images (loop_cam.cpp:178-217)
+            pcm_note_frame(cfg_.self_id, kf_id, pose);
         }
         {   // join the triangulation tasks; if one throws, the others are still joined (they reference this micro-batch's frames) and the list is
             // emptied before the exception leaves: the next finish() must not meet futures that were already consumed
@@ -1794,6 +1889,16 @@ private:
     std::vector<LoopEdge> remote_edges_;        // SWARM_LOOP_CONN of other drones, in arrival order
     std::deque<RemoteImage> remote_images_;     // the files of their whole descriptors, at most REMOTE_IMAGES_MAX
     int64_t remote_images_dropped_ = 0;
+    // Config::pcm: the stage on a context of its own, the path lengths it reads, how far edges_ / remote_edges_ have entered it, the edges left outside it
+    std::unique_ptr<Context> pcm_ctx_;
+    std::unique_ptr<LoopOutlierRejection> pcm_;
+    struct PcmPath { bool any = false; double last[3] = {0, 0, 0}, length = 0; };
+    std::map<int, PcmPath> pcm_path_;
+    std::map<std::pair<int, int64_t>, double> pcm_arc_;
+    size_t pcm_fed_local_ = 0, pcm_fed_remote_ = 0;
+    std::set<int64_t> pcm_outside_;
+    int64_t pcm_unknown_ = 0;
+    std::vector<omni_pcm_edge> pcm_records_;
     // remote_in_stream: the queue in arrival order, each frame with p = the local key frames handed over before it; next_seq_: local key frames handed over so far;
     // begun_seq_: every local key frame below it has its detector batch begun; remote_in_batch_: remote frames in the batch that is pending
     struct QueuedRemote { FisheyeFrameDescriptor f; int64_t p; };

@@ -63,6 +63,12 @@ _remote_lib = None
 VERIFY_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_verify.so")
 VERIFY_SYMBOLS = ["omni_verify_last_error", "omni_pipeline_set_batch_verify", "omni_pipeline_get_batch_verify", "omni_pipeline_verify_stats", "omni_pipeline_edge_ids", "omni_pipeline_corr_stats", "omni_verify_correspond_host", "omni_verify_plan"]
 _verify_lib = None
+# pairwise-consistency outlier rejection of the loop edges: include/omni_host_pcm.h, lib/libomni_host_pcm.so (the same handle)
+PCM_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_pcm.so")
+PCM_SYMBOLS = ["omni_pcm_host_last_error", "omni_pipeline_set_pcm", "omni_pipeline_get_pcm", "omni_pipeline_good_edges", "omni_pipeline_pcm_stats", "omni_pipeline_pcm_records",
+               "omni_pcm_filter_host"]
+PCM_STATS = ("edges_entered", "pairs_evaluated", "consistent_pairs", "clique_runs", "unknown_frames", "full_handles")
+_pcm_lib = None
 JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
 JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
                    "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
@@ -383,6 +389,38 @@ def wire_lib():
     return _wire_lib
 
 
+def pcm_lib():
+    global _pcm_lib
+    if _pcm_lib is None:
+        lib()
+        if not os.path.exists(PCM_LIB_PATH):
+            raise OSError(f"{PCM_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(PCM_LIB_PATH)
+        L.omni_pcm_host_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_pcm.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]
+        L.omni_pipeline_get_pcm.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.omni_pipeline_good_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.omni_pipeline_pcm_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.omni_pipeline_pcm_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.omni_pcm_filter_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(capi.PcmParams), C.c_void_p, C.POINTER(C.c_int64)]
+        _pcm_lib = L
+    return _pcm_lib
+
+
+def pcm_filter_host(edges, self_id: int, batches=None, redundant: bool = False, capacity: int = capi.PCM_DEFAULT_CAPACITY, params=None):
+    """host/loop_outlier_rejection.hpp with its rows from omni_pcm_rows_host (no GPU): capi.PCM_EDGE_DTYPE records enter in calls of batches[0], batches[1], ..
+    edges (None: one call).  Returns (good [n] bool: whether edge k passes afterwards, stats dict)."""
+    e = np.ascontiguousarray(edges, dtype=capi.PCM_EDGE_DTYPE).reshape(-1)
+    good = np.zeros(max(len(e), 1), np.uint8)
+    st = (C.c_int64 * 6)()
+    b = None if batches is None else np.ascontiguousarray(batches, np.int32)
+    pr = params or capi.pcm_params()
+    if pcm_lib().omni_pcm_filter_host(e.ctypes.data, len(e), None if b is None else b.ctypes.data, 0 if b is None else len(b), self_id, int(bool(redundant)), capacity,
+                                      C.byref(pr), good.ctypes.data, st):
+        raise capi.OmniError(f"omni_pcm_filter_host: {pcm_lib().omni_pcm_host_last_error().decode()}")
+    return good[:len(e)].astype(bool), dict(zip(PCM_STATS, (int(v) for v in st)))
+
+
 def wiremsg_lib():
     global _wiremsg_lib
     if _wiremsg_lib is None:
@@ -490,7 +528,7 @@ class KeyframePipeline:
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
                  device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False, batch_verify=False,
-                 wire_img_desc="off", wire_loop_conn=False):
+                 wire_img_desc="off", wire_loop_conn=False, pcm=False, pcm_thres=0.6, pcm_redundant=False, pcm_capacity=capi.PCM_DEFAULT_CAPACITY):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -528,6 +566,9 @@ class KeyframePipeline:
         batch_verify: loop candidates between a frame of another drone and a frame of this one are verified with their detector batch, in one GPU round trip,
         instead of one by one on the spot; earlier only where a remote frame's init mode depends on a pending verdict (host/verify_plan.hpp).  The same
         candidates, edges and counters (set_batch_verify, verify_stats).  Independent of remote_in_stream.  Default off.
+        pcm / pcm_thres / pcm_redundant / pcm_capacity: pairwise-consistency outlier rejection of the loop edges of a `geometry` pipeline (set_pcm): every edge
+        that enters edges() or remote_edges() is compared with every earlier edge of its drone pair on the GPU (csrc/pcm.hip), a clique heuristic picks each
+        pair's inlier set, and good_edges() lists what is left; edges(), candidates, counters and rows are unchanged.  Default off.
         pipelines <= 0: the library's default number of units in flight for the precision (4 for fp16, 2 otherwise)"""
         self.microbatch = microbatch
         common = (device, sp_weights_path.encode(), pca_comp_csv.encode(), pca_mean_csv.encode(), vlad_weights_path.encode(), width, height, thres, max_num,
@@ -582,6 +623,44 @@ class KeyframePipeline:
             self.set_remote_in_stream(True)
         if batch_verify:
             self.set_batch_verify(True)
+        if pcm:
+            self.set_pcm(True, pcm_thres, pcm_redundant, pcm_capacity)
+
+    def _pcm(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {pcm_lib().omni_pcm_host_last_error().decode()}")
+
+    def set_pcm(self, on: bool, pcm_thres: float = 0.6, redundant: bool = False, capacity: int = capi.PCM_DEFAULT_CAPACITY):
+        """before the first key frame: pairwise-consistency outlier rejection of the loop edges (refused on the sharded database and without a geometry stage)"""
+        self._pcm(pcm_lib().omni_pipeline_set_pcm(self.h, int(bool(on)), float(pcm_thres), int(bool(redundant)), int(capacity)), "omni_pipeline_set_pcm")
+
+    def pcm(self) -> dict:
+        on, thres, red, cap = C.c_int(0), C.c_double(0), C.c_int(0), C.c_int(0)
+        self._pcm(pcm_lib().omni_pipeline_get_pcm(self.h, C.byref(on), C.byref(thres), C.byref(red), C.byref(cap)), "omni_pipeline_get_pcm")
+        return dict(on=bool(on.value), pcm_thres=thres.value, redundant=bool(red.value), capacity=cap.value)
+
+    def good_edges(self) -> np.ndarray:
+        """edges() then remote_edges() without those the stage rejected (REMOTE_EDGE_DTYPE records); with the stage off: all of them"""
+        n = C.c_int(0)
+        self._pcm(pcm_lib().omni_pipeline_good_edges(self.h, None, 0, C.byref(n)), "omni_pipeline_good_edges")
+        out = np.zeros(n.value, REMOTE_EDGE_DTYPE)
+        if len(out):
+            self._pcm(pcm_lib().omni_pipeline_good_edges(self.h, out.ctypes.data, len(out), C.byref(n)), "omni_pipeline_good_edges")
+        return out
+
+    def pcm_stats(self) -> dict:
+        st = (C.c_int64 * 6)()
+        self._pcm(pcm_lib().omni_pipeline_pcm_stats(self.h, st), "omni_pipeline_pcm_stats")
+        return dict(zip(PCM_STATS, (int(v) for v in st)))
+
+    def pcm_records(self) -> np.ndarray:
+        """the records the stage entered so far, in the order they entered (capi.PCM_EDGE_DTYPE, path lengths included)"""
+        n = C.c_int(0)
+        self._pcm(pcm_lib().omni_pipeline_pcm_records(self.h, None, 0, C.byref(n)), "omni_pipeline_pcm_records")
+        out = np.zeros(n.value, capi.PCM_EDGE_DTYPE)
+        if len(out):
+            self._pcm(pcm_lib().omni_pipeline_pcm_records(self.h, out.ctypes.data, len(out), C.byref(n)), "omni_pipeline_pcm_records")
+        return out
 
     def _pca(self, rc, what):
         if rc:
