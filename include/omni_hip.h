@@ -1053,6 +1053,69 @@ int          omni_pcm_max_clique_host(const uint64_t* rows, int n, int stride_wo
 /* the header's arctangent (tests): atan2(y, x) */
 double       omni_pcm_atan2(double y, double x);
 
+/* ---- 4-DoF pose graph over odometry and loop edges: the loop + ego-motion part of swarm_localization's sliding-window problem (swarm_localization_solver.cpp
+ * :1064-1100, :1156-1213, :1668-1712; RelativePoseFactor4d of swarm_localization_factors.hpp) ---------------------------------------------------------------------------
+ * The arithmetic is csrc/pgo_plan.h's and nothing else restates it: residual r = sqrt_inf o (z - DeltaPose(p_i, p_j)) with the header's OWN sine and cosine, analytic
+ * Jacobians, Huber(1) as Ceres corrects a block, and Levenberg-Marquardt over block-Jacobi conjugate gradients with every sum in a fixed order.  Ceres, Eigen and
+ * swarm_msgs are not vendored: parity with the reference is unpinned and the header is the specification.  A pose is double[4]: x y z yaw. */
+typedef struct omni_pgo_edge {
+    int32_t i, j;                            /* the two poses: z measures DeltaPose(pose i, pose j) */
+    double  z[4];                            /* x y z yaw of pose j in pose i's yaw frame */
+    double  sqrt_inf[4];                     /* the diagonal of the square-root information: 1 / sqrt(cov) over (pos_cov xyz, ang_cov[2]) */
+    int32_t robust;                          /* != 0: HuberLoss(1.0) (loop edges); 0: no loss (ego motion) */
+    int32_t reserved;
+} omni_pgo_edge;
+typedef struct omni_pgo_params {
+    int32_t max_iterations;                  /* outer Levenberg-Marquardt iterations (50) */
+    int32_t max_cg_iterations;               /* conjugate-gradient steps per linear solve; 0: 4 x the number of free poses */
+    int32_t max_lambda_retries;              /* enlargements of lambda after a rejected step before the solve gives up (16) */
+    int32_t reserved;
+    double  initial_lambda;                  /* 1e-4 */
+    double  function_tolerance;              /* CONVERGED when an accepted step lowers the cost by no more than this x the cost (1e-6) */
+    double  parameter_tolerance;             /* CONVERGED when |step| <= this x (|free poses| + this) (1e-8) */
+    double  cg_tolerance;                    /* a linear solve ends when r.z <= this^2 x its first value (1e-6) */
+} omni_pgo_params;
+typedef struct omni_pgo_stats {
+    double  initial_cost, final_cost;        /* the sum over edges of rho(|r|^2) / 2 at the start and at the poses returned */
+    int32_t iterations, cg_iterations;       /* outer iterations begun; conjugate-gradient steps over all linear solves */
+    int32_t status;                          /* OMNI_PGO_* */
+    int32_t reserved;
+} omni_pgo_stats;
+#define OMNI_PGO_CONVERGED 0
+#define OMNI_PGO_MAX_ITERATIONS 1            /* a cap was reached: max_iterations, or max_lambda_retries without an accepted step */
+#define OMNI_PGO_NONFINITE 2                 /* a NaN or inf in a cost or a step: the poses are returned as they came */
+#define OMNI_PGO_EMPTY 3                     /* no free pose with an edge, or no edge: the poses are returned as they came, both costs are 0 */
+#define OMNI_PGO_MAX_POSES 4096
+#define OMNI_PGO_MAX_EDGES 16384
+#define OMNI_PGO_MAX_STARTS 64
+typedef struct omni_pgo omni_pgo;
+int          omni_pgo_default_params(omni_pgo_params* out);
+int          omni_pgo_create(omni_ctx* ctx, omni_pgo** out);
+void         omni_pgo_destroy(omni_pgo* pgo);
+/* Solves n_starts (1 .. 64) initial pose sets of ONE graph, one workgroup per start, in one launch between one upload and one download (solve_with_multiple_init,
+ * swarm_localization_solver.cpp:781-846).  poses_in / poses_out [n_starts][n_poses][4]; fixed [n_poses] bytes (!= 0: the pose is constant); edges [n_edges];
+ * stats_out [n_starts]; *best: the start with the lowest final cost among those that ended CONVERGED or MAX_ITERATIONS, the lower index on a tie, -1 when there is
+ * none; *kernel_us (may be NULL): the launch's time between two events.  Blocking.  Refused before any launch: a null argument, n_poses outside 1..4096, n_edges
+ * outside 0..16384, n_starts outside 1..64, an edge whose i or j is outside 0..n_poses-1 or whose i equals j, a parameter that is negative or not finite. */
+int          omni_pgo_solve_multi(omni_pgo* pgo, const omni_pgo_params* params, const double* poses_in, const uint8_t* fixed, const omni_pgo_edge* edges, int n_poses,
+                                  int n_edges, int n_starts, double* poses_out, omni_pgo_stats* stats_out, int* best, float* kernel_us);
+/* csrc/pgo_plan.h compiled by g++ into the library: the same arguments, the same refusals, the same bits, one start after the other on the calling thread.  No GPU,
+ * no context. */
+int          omni_pgo_solve_host(const omni_pgo_params* params, const double* poses_in, const uint8_t* fixed, const omni_pgo_edge* edges, int n_poses, int n_edges,
+                                 int n_starts, double* poses_out, omni_pgo_stats* stats_out, int* best);
+/* For tests: per edge the residual after the loss's correction res_out [n_edges][4], the corrected Jacobians jac_i_out / jac_j_out [n_edges][4][4] (row = residual,
+ * column = x y z yaw of pose i / j) and the cost cost_out [n_edges]; any output may be NULL.  The refusals of the graph are those above. */
+int          omni_pgo_residuals_host(const double* poses, const omni_pgo_edge* edges, int n_poses, int n_edges, double* res_out, double* jac_i_out, double* jac_j_out,
+                                     double* cost_out);
+/* For tests: the incidence lists of pgo::plan_graph.  offsets_out [n_poses + 1], incident_out [2 n_edges] (2 x edge + side, side 1: the pose is the edge's j),
+ * active_out [n_poses] bytes (free and with an edge), *n_active_out their number. */
+int          omni_pgo_plan_graph_host(const uint8_t* fixed, const omni_pgo_edge* edges, int n_poses, int n_edges, int32_t* offsets_out, int32_t* incident_out,
+                                      uint8_t* active_out, int* n_active_out);
+/* the header's sine and cosine, NormalizeAngle and the fixed-shape sum (tests) */
+void         omni_pgo_sincos(double yaw, double* sin_out, double* cos_out);
+double       omni_pgo_normalize_angle(double a);
+double       omni_pgo_sum_host(const double* v, int n);
+
 #ifdef __cplusplus
 }
 #endif

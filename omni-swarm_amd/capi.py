@@ -58,7 +58,14 @@ SYMBOLS = [
     "omni_rows_assemble_enqueue_dev", "omni_rows_assemble_host", "omni_memcpy_h2d_async",
     "omni_corr_assemble_host", "omni_corr_assemble_multi", "omni_bf_match_homography_corr_multi",
     "omni_pcm_create", "omni_pcm_destroy", "omni_pcm_size", "omni_pcm_capacity", "omni_pcm_add", "omni_pcm_adjacency", "omni_pcm_rows_host", "omni_pcm_max_clique_host", "omni_pcm_atan2",
+    "omni_pgo_default_params", "omni_pgo_create", "omni_pgo_destroy", "omni_pgo_solve_multi", "omni_pgo_solve_host", "omni_pgo_residuals_host", "omni_pgo_plan_graph_host",
+    "omni_pgo_sincos", "omni_pgo_normalize_angle", "omni_pgo_sum_host",
 ]
+PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_NONFINITE, PGO_EMPTY = 0, 1, 2, 3      # include/omni_hip.h OMNI_PGO_*
+PGO_MAX_POSES, PGO_MAX_EDGES, PGO_MAX_STARTS = 4096, 16384, 64
+# include/omni_hip.h omni_pgo_edge and omni_pgo_stats as numpy records: a pose is x y z yaw
+PGO_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("z", "<f8", (4,)), ("sqrt_inf", "<f8", (4,)), ("robust", "<i4"), ("reserved", "<i4")])
+PGO_STATS_DTYPE = np.dtype([("initial_cost", "<f8"), ("final_cost", "<f8"), ("iterations", "<i4"), ("cg_iterations", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
 PCM_FULL, PCM_MAX_ADD, PCM_DEFAULT_CAPACITY = 100, 64, 4096      # include/omni_hip.h OMNI_PCM_*
 # include/omni_hip.h omni_pcm_edge as a numpy record: poses are xyz + quaternion wxyz
 PCM_EDGE_DTYPE = np.dtype([("id", "<i8"), ("drone_a", "<i4"), ("drone_b", "<i4"), ("relative_pose", "<f8", (7,)), ("self_pose_a", "<f8", (7,)), ("self_pose_b", "<f8", (7,)),
@@ -90,6 +97,11 @@ class _VladLayer(C.Structure):
 
 class PcmParams(C.Structure):     # include/omni_hip.h omni_pcm_params
     _fields_ = [("pcm_thres", C.c_double), ("pos_covariance_per_meter", C.c_double), ("yaw_covariance_per_meter", C.c_double)]
+
+
+class PgoParams(C.Structure):     # include/omni_hip.h omni_pgo_params
+    _fields_ = [("max_iterations", C.c_int32), ("max_cg_iterations", C.c_int32), ("max_lambda_retries", C.c_int32), ("reserved", C.c_int32),
+                ("initial_lambda", C.c_double), ("function_tolerance", C.c_double), ("parameter_tolerance", C.c_double), ("cg_tolerance", C.c_double)]
 
 
 class CorrCand(C.Structure):      # include/omni_hip.h omni_corr_cand
@@ -540,6 +552,16 @@ def lib():
     sig("omni_pcm_rows_host", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(PcmParams), C.c_int, _vp, _vp, _vp])
     sig("omni_pcm_max_clique_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _ip])
     sig("omni_pcm_atan2", C.c_double, [C.c_double, C.c_double])
+    sig("omni_pgo_default_params", C.c_int, [C.POINTER(PgoParams)])
+    sig("omni_pgo_create", C.c_int, [_vp, C.POINTER(_vp)])
+    sig("omni_pgo_destroy", None, [_vp])
+    sig("omni_pgo_solve_multi", C.c_int, [_vp, C.POINTER(PgoParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _fp])
+    sig("omni_pgo_solve_host", C.c_int, [C.POINTER(PgoParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip])
+    sig("omni_pgo_residuals_host", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp])
+    sig("omni_pgo_plan_graph_host", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _ip])
+    sig("omni_pgo_sincos", None, [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)])
+    sig("omni_pgo_normalize_angle", C.c_double, [C.c_double])
+    sig("omni_pgo_sum_host", C.c_double, [_vp, C.c_int])
     if L.omni_abi_version() != ABI_VERSION:
         raise OmniError("libomni_hip.so ABI version mismatch")
     _lib = L
@@ -1307,6 +1329,113 @@ class Pcm:
         deg = np.zeros(max(self.size, 1), np.int32)
         _check(lib().omni_pcm_adjacency(self.h, first, n_rows, rows.ctypes.data, deg.ctypes.data))
         return rows[:n_rows], deg[:self.size]
+
+
+def pgo_params(**kw) -> PgoParams:
+    """omni_pgo_default_params with the given fields replaced (max_iterations, max_cg_iterations, max_lambda_retries, initial_lambda, function_tolerance,
+    parameter_tolerance, cg_tolerance)"""
+    pr = PgoParams()
+    _check(lib().omni_pgo_default_params(C.byref(pr)))
+    for k, v in kw.items():
+        assert k in dict(PgoParams._fields_) and k != "reserved", k
+        setattr(pr, k, v)
+    return pr
+
+
+def pgo_edges(edges) -> np.ndarray:
+    e = np.ascontiguousarray(edges, dtype=PGO_EDGE_DTYPE).reshape(-1)
+    assert PGO_EDGE_DTYPE.itemsize == 80 and PGO_STATS_DTYPE.itemsize == 32
+    return e
+
+
+def pgo_sqrt_inf(pos_cov, yaw_cov) -> np.ndarray:
+    """the diagonal square-root information of csrc/pgo_plan.h: 1 / sqrt(cov) over (pos_cov xyz, yaw_cov); a zero covariance gives inf, as IEEE does"""
+    with np.errstate(divide="ignore"):
+        return 1.0 / np.sqrt(np.concatenate([np.broadcast_to(np.asarray(pos_cov, np.float64), (3,)), [float(yaw_cov)]]))
+
+
+def _pgo_args(poses, fixed, edges):
+    x = np.ascontiguousarray(poses, np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise OmniError("pose graph: poses must be [n][4] or [starts][n][4]")
+    f = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    if len(f) != x.shape[1]:
+        raise OmniError("pose graph: fixed must have one byte per pose")
+    return x, f, pgo_edges(edges)
+
+
+def pgo_solve_host(poses, fixed, edges, params: PgoParams | None = None):
+    """csrc/pgo_plan.h under g++ (omni_pgo_solve_host): poses [starts][n][4] (or [n][4]: one start).  Returns (poses_out [starts][n][4], stats [starts]
+    PGO_STATS_DTYPE, best)."""
+    x, f, e = _pgo_args(poses, fixed, edges)
+    pr = params or pgo_params()
+    out, st, best = np.zeros_like(x), np.zeros(max(x.shape[0], 1), PGO_STATS_DTYPE), C.c_int(-2)
+    _check(lib().omni_pgo_solve_host(C.byref(pr), x.ctypes.data, f.ctypes.data, e.ctypes.data, x.shape[1], len(e), x.shape[0], out.ctypes.data, st.ctypes.data, C.byref(best)))
+    return out, st[:x.shape[0]], best.value
+
+
+def pgo_residuals_host(poses, edges):
+    """(residuals [m][4], jac_i [m][4][4], jac_j [m][4][4], costs [m]) of csrc/pgo_plan.h at poses [n][4], the loss's correction applied"""
+    x, e = np.ascontiguousarray(poses, np.float64), pgo_edges(edges)
+    m = len(e)
+    r, ji, jj, c = np.zeros((max(m, 1), 4)), np.zeros((max(m, 1), 4, 4)), np.zeros((max(m, 1), 4, 4)), np.zeros(max(m, 1))
+    _check(lib().omni_pgo_residuals_host(x.ctypes.data, e.ctypes.data, x.shape[0], m, r.ctypes.data, ji.ctypes.data, jj.ctypes.data, c.ctypes.data))
+    return r[:m], ji[:m], jj[:m], c[:m]
+
+
+def pgo_plan_graph_host(fixed, edges):
+    """(offsets [n + 1], incident [2 m] = 2 x edge + side, active [n], n_active) of pgo::plan_graph"""
+    f, e = np.ascontiguousarray(fixed, np.uint8).reshape(-1), pgo_edges(edges)
+    n, m = len(f), len(e)
+    off, inc, act, na = np.zeros(n + 1, np.int32), np.zeros(max(2 * m, 1), np.int32), np.zeros(max(n, 1), np.uint8), C.c_int(0)
+    _check(lib().omni_pgo_plan_graph_host(f.ctypes.data, e.ctypes.data, n, m, off.ctypes.data, inc.ctypes.data, act.ctypes.data, C.byref(na)))
+    return off, inc[:2 * m], act[:n], na.value
+
+
+def pgo_sincos(yaw: float):
+    s, c = C.c_double(0), C.c_double(0)
+    lib().omni_pgo_sincos(yaw, C.byref(s), C.byref(c))
+    return s.value, c.value
+
+
+def pgo_sum_host(v) -> float:
+    a = np.ascontiguousarray(v, np.float64).reshape(-1)
+    return lib().omni_pgo_sum_host(a.ctypes.data, len(a))
+
+
+class Pgo:
+    """omni_pgo: the 4-DoF pose graph solver on the GPU (csrc/pgo.hip; the arithmetic is csrc/pgo_plan.h's).  solve() takes one graph and 1..64 initial pose sets,
+    one workgroup each, and returns what pgo_solve_host returns, bit for bit."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        h = _vp()
+        _check(lib().omni_pgo_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        self.last_kernel_us = 0.0
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().omni_pgo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, poses, fixed, edges, params: PgoParams | None = None, time_kernel: bool = False):
+        x, f, e = _pgo_args(poses, fixed, edges)
+        pr = params or pgo_params()
+        out, st, best, us = np.zeros_like(x), np.zeros(max(x.shape[0], 1), PGO_STATS_DTYPE), C.c_int(-2), C.c_float(0)
+        _check(lib().omni_pgo_solve_multi(self.h, C.byref(pr), x.ctypes.data, f.ctypes.data, e.ctypes.data, x.shape[1], len(e), x.shape[0], out.ctypes.data, st.ctypes.data,
+                                          C.byref(best), C.byref(us) if time_kernel else None))
+        self.last_kernel_us = us.value
+        return out, st[:x.shape[0]], best.value
 
 
 def jpeg_header(width: int, height: int, quality: int) -> bytes:

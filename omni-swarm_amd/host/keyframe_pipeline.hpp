@@ -23,6 +23,7 @@
 #include "loop_net_wire.hpp"
 #include "loop_outlier_rejection.hpp"
 #include "omni_swarm.hpp"
+#include "pose_graph.hpp"
 #include "remote_queue.hpp"
 
 namespace omni {
@@ -147,6 +148,12 @@ public:
         bool pcm = false, pcm_redundant = false;
         double pcm_thres = 0.6, pcm_pos_covariance_per_meter = 0.01, pcm_yaw_covariance_per_meter = 0.003;
         int pcm_capacity = OMNI_PCM_DEFAULT_CAPACITY;
+        // The 4-DoF pose graph over the window's ego motion and loop edges (host/pose_graph.hpp builds it, csrc/pgo.hip solves it; the loop + ego-motion part of
+        // swarm_localization_solver.cpp:1064-1213, :1668-1712): optimize() solves the last pose_graph_window key frames per drone (the reference's max_keyframe_num
+        // is 50, swarm_localization_node.cpp:465; 2..256) with the edges good_edges() returns, from pose_graph_starts initial pose sets (1..64).  The stage only adds
+        // outputs -- estimated_poses(), drift(), pose_graph_stats().  Off by default; refused on the sharded database and without a geometry stage, like pcm.
+        bool pose_graph = false;
+        int pose_graph_window = 50, pose_graph_starts = 1;
         // `geometry`: the homography RANSAC of every direction pair of a loop candidate (compute_correspond_features, loop_detector.cpp:589-598) runs on the GPU, in
         // the round trip that matches the pairs anyway (omni_bf_match_homography_multi, csrc/homography.hip: the same mask bit for bit, tests/test_gpu_homography.py);
         // the candidate's host task takes the masks instead of running geom::find_homography_ransac -- 2 000 f64 9 x 9 eigen-solves per pair of a candidate
@@ -323,6 +330,7 @@ private:
             if (c.batch_verify) apply_batch_verify(true);
         }
         if (c.pcm) { cfg_.pcm = false; set_pcm(true, c.pcm_thres, c.pcm_redundant, c.pcm_capacity); }
+        if (c.pose_graph) { cfg_.pose_graph = false; set_pose_graph(true, c.pose_graph_window, c.pose_graph_starts); }
     }
     // Config::batch_verify: the detector's late-verdict hooks.  A ticket is a place in deferred_; a resolve is one start_geometry + drain_geometry over everything
     // deferred so far -- the candidates between two frames of this drone that came before included, so the edge order is the candidate order
@@ -396,9 +404,108 @@ public:
     }
     // the records the stage entered so far, in the order they entered (what a host recomputation takes: tests)
     const std::vector<omni_pcm_edge>& pcm_records() { std::lock_guard<std::mutex> lk(intake_mu_); pcm_feed(); return pcm_records_; }
+
+    // ---- the 4-DoF pose graph of the window (Config::pose_graph) -------------------------------------------------------------------------------------------------
+    struct EstimatedPose { int drone = 0, pose_index = -1; int64_t keyframe_id = 0; double pose[4] = {0, 0, 0, 0}, odom[4] = {0, 0, 0, 0}, init[4] = {0, 0, 0, 0}; };
+    // [0] optimize() calls, [1] poses, [2] ego-motion edges, [3] loop edges, [4] loop edges outside the window, [5] drones no edge reaches, [6] key frames merged
+    // into their predecessor's pose, [7] the best start (-1: none), [8] its status (OMNI_PGO_*), [9] its outer iterations, [10] its conjugate-gradient steps -- all
+    // of the last call; cost: its initial and final cost
+    struct PoseGraphStats { int64_t v[11] = {0, 0, 0, 0, 0, 0, 0, -1, OMNI_PGO_EMPTY, 0, 0}; double cost[2] = {0, 0}; };
+    bool pose_graph() const { return cfg_.pose_graph; }
+    int pose_graph_window() const { return cfg_.pose_graph_window; }
+    int pose_graph_starts() const { return cfg_.pose_graph_starts; }
+    // before the first key frame (what the C entry point omni_pipeline_set_pose_graph sets)
+    void set_pose_graph(bool on, int window, int starts) {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        if (any_keyframe_seen_) throw std::runtime_error("set_pose_graph after the first key frame");
+        if (on && shard_) throw std::runtime_error("set_pose_graph: the sharded database builds no messages");
+        if (on && !cfg_.geometry) throw std::runtime_error("set_pose_graph: the pipeline has no geometry stage");
+        if (on && (window < SwarmPoseGraph::kMinWindow || window > SwarmPoseGraph::kMaxWindow)) throw std::invalid_argument("set_pose_graph: pose_graph_window outside 2..256");
+        if (on && (starts < 1 || starts > OMNI_PGO_MAX_STARTS)) throw std::invalid_argument("set_pose_graph: pose_graph_starts outside 1..64");
+        if (pg_handle_) { omni_pgo_destroy(pg_handle_); pg_handle_ = nullptr; }
+        pg_.reset();
+        if (!on) { pg_ctx_.reset(); cfg_.pose_graph = false; return; }
+        SwarmPoseGraph::Params p;
+        p.self_id = cfg_.self_id; p.window = window; p.starts = starts;
+        p.pos_covariance_per_meter = cfg_.pcm_pos_covariance_per_meter; p.yaw_covariance_per_meter = cfg_.pcm_yaw_covariance_per_meter;
+        // omni_pgo_solve_multi is blocking: a context of its own, as for pcm
+        if (!pg_ctx_) pg_ctx_ = std::make_unique<Context>(cfg_.device, true);
+        if (omni_pgo_create(pg_ctx_->get(), &pg_handle_) != OMNI_OK) throw std::runtime_error(std::string("omni_pgo_create: ") + omni_last_error());
+        pg_ = std::make_unique<SwarmPoseGraph>(p);
+        cfg_.pose_graph = true; cfg_.pose_graph_window = window; cfg_.pose_graph_starts = starts;
+    }
+    // Solves the current window (blocking): the problem host/pose_graph.hpp builds from the key frames seen so far and good_edges(), on the GPU, every start a
+    // workgroup; the cheapest start's poses are what estimated_poses() returns.  Returns that start's status (OMNI_PGO_*).
+    int optimize() {
+        if (!cfg_.pose_graph) throw std::runtime_error("optimize: the pose graph is off");
+        const std::vector<LoopEdge> good = good_edges();
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        std::vector<SwarmPoseGraph::Loop> loops;
+        for (const LoopEdge& e : good) {
+            SwarmPoseGraph::Loop l;
+            l.id = e.id; l.drone_a = e.drone_id_a; l.drone_b = e.drone_id_b; l.keyframe_a = e.keyframe_id_a; l.keyframe_b = e.keyframe_id_b;
+            l.rel[0] = e.relative_pose.pos.x; l.rel[1] = e.relative_pose.pos.y; l.rel[2] = e.relative_pose.pos.z;
+            l.rel[3] = e.relative_pose.att.w; l.rel[4] = e.relative_pose.att.x; l.rel[5] = e.relative_pose.att.y; l.rel[6] = e.relative_pose.att.z;
+            for (int k = 0; k < 3; ++k) { l.pos_cov[k] = e.pos_cov[k]; l.ang_cov[k] = e.ang_cov[k]; }
+            loops.push_back(l);
+        }
+        pg_problem_ = pg_->build(loops);
+        const SwarmPoseGraph::Problem& P = pg_problem_;
+        PoseGraphStats st;
+        st.v[0] = pg_stats_.v[0] + 1;
+        st.v[1] = P.n_poses; st.v[2] = P.ego_edges; st.v[3] = P.loop_edges; st.v[4] = P.loops_outside; st.v[5] = P.unreachable_drones; st.v[6] = P.merged;
+        pg_solution_.assign(P.poses.begin(), P.poses.begin() + (long)(4 * (size_t)P.n_poses));
+        if (P.n_poses > 0) {
+            std::vector<double> out(P.poses.size());
+            std::vector<omni_pgo_stats> ss((size_t)P.n_starts);
+            const omni_pgo_params pr = pg_params_;
+            int best = -1;
+            if (omni_pgo_solve_multi(pg_handle_, &pr, P.poses.data(), P.fixed.data(), P.edges.data(), P.n_poses, (int)P.edges.size(), P.n_starts, out.data(), ss.data(), &best,
+                                     nullptr) != OMNI_OK)
+                throw std::runtime_error(std::string("omni_pgo_solve_multi: ") + omni_last_error());
+            const int use = best >= 0 ? best : 0;
+            st.v[7] = best; st.v[8] = ss[(size_t)use].status; st.v[9] = ss[(size_t)use].iterations; st.v[10] = ss[(size_t)use].cg_iterations;
+            st.cost[0] = ss[(size_t)use].initial_cost; st.cost[1] = ss[(size_t)use].final_cost;
+            pg_solution_.assign(out.begin() + (long)(4 * (size_t)P.n_poses * (size_t)use), out.begin() + (long)(4 * (size_t)P.n_poses * (size_t)(use + 1)));
+        }
+        pg_stats_ = st;
+        return (int)st.v[8];
+    }
+    // every window key frame of the last optimize(), drones ascending, oldest first: the estimate, the odometry pose and the initial value (start 0), x y z yaw, and
+    // the pose of the problem the frame maps to -- one locked call, so that a reader never sees two optimize() calls mixed
+    std::vector<EstimatedPose> estimated_poses() {
+        std::lock_guard<std::mutex> lk(intake_mu_);
+        std::vector<EstimatedPose> out;
+        for (const SwarmPoseGraph::Frame& f : pg_problem_.frames) {
+            EstimatedPose e;
+            e.drone = f.drone; e.pose_index = f.pose_index; e.keyframe_id = f.keyframe_id;
+            for (int k = 0; k < 4; ++k) { e.pose[k] = pg_solution_[4 * (size_t)f.pose_index + (size_t)k]; e.odom[k] = f.odom[k]; e.init[k] = f.init[k]; }
+            out.push_back(e);
+        }
+        return out;
+    }
+    // this drone's newest estimated pose . inverse(its odometry pose), x y z yaw; false when the last optimize() held no frame of this drone
+    bool drift(double out[4]) {
+        const std::vector<EstimatedPose> est = estimated_poses();
+        const EstimatedPose* last = nullptr;
+        for (const EstimatedPose& e : est) if (e.drone == cfg_.self_id) last = &e;
+        if (!last) return false;
+        double inv[4];
+        pgo::pose_inverse(last->odom, inv);
+        pgo::pose_mul(last->pose, inv, out);
+        return true;
+    }
+    PoseGraphStats pose_graph_stats() { std::lock_guard<std::mutex> lk(intake_mu_); return pg_stats_; }
+    // the exact problem the last optimize() solved (what a host recomputation takes: tests), and the solver's parameters
+    SwarmPoseGraph::Problem pose_graph_problem() { std::lock_guard<std::mutex> lk(intake_mu_); return pg_problem_; }
+    omni_pgo_params pose_graph_params() { std::lock_guard<std::mutex> lk(intake_mu_); return pg_params_; }
 private:
     // the cumulative path length of a drone at the key frames this pipeline saw, local and remote, from their pose_drone in the order they came
     void pcm_note_frame(int drone, int64_t kf_id, const PoseMsg& pose) {
+        if (pg_) {                                                   // Config::pose_graph reads the same key frames
+            const double p7[7] = {pose.position[0], pose.position[1], pose.position[2], pose.quat_wxyz[0], pose.quat_wxyz[1], pose.quat_wxyz[2], pose.quat_wxyz[3]};
+            pg_->note_frame(drone, kf_id, p7);
+        }
         if (!pcm_) return;
         PcmPath& t = pcm_path_[drone];
         if (t.any) { const double dx = pose.position[0] - t.last[0], dy = pose.position[1] - t.last[1], dz = pose.position[2] - t.last[2]; t.length += std::sqrt(dx * dx + dy * dy + dz * dz); }
@@ -1200,6 +1307,7 @@ public:
         if (cfg_.remote_in_stream) throw std::runtime_error("attach_shard: remote_in_stream does not run on the sharded database, which builds no messages");
         if (cfg_.batch_verify) throw std::runtime_error("attach_shard: batch_verify does not run on the sharded database, which builds no messages");
         if (cfg_.pcm) throw std::runtime_error("attach_shard: pcm does not run on the sharded database, which builds no messages");
+        if (cfg_.pose_graph) throw std::runtime_error("attach_shard: the pose graph does not run on the sharded database, which builds no messages");
         if (cfg_.fisheye_raw()) throw std::runtime_error("attach_shard: the raw-fisheye mode (fisheye_src_width x fisheye_src_height) does not run on the sharded database");
         shard_index_ = std::make_unique<IndexFlatIP>(index_ctx_, 4096, cfg_.storage);
         shard_ = omni_shard_create(index_ctx_.get(), shard_index_->handle(), 4096, rank, world, unique_id);
@@ -1208,7 +1316,7 @@ public:
         apply_stereo_model();                                  // (off: this mode builds no messages)
         apply_jpeg();
     }
-    ~KeyframePipeline() { if (shard_) omni_shard_destroy(shard_); }
+    ~KeyframePipeline() { if (pg_handle_) omni_pgo_destroy(pg_handle_); if (shard_) omni_shard_destroy(shard_); }
     int64_t db_rows() const { return shard_ ? omni_shard_ntotal(shard_) : det_.local_index.ntotal + det_.remote_index.ntotal; }
 
     // bulk pre-load of the key-frame database: rows [n][4096], dirs() consecutive rows = the directions of one earlier key frame
@@ -1899,6 +2007,14 @@ private:
     std::set<int64_t> pcm_outside_;
     int64_t pcm_unknown_ = 0;
     std::vector<omni_pcm_edge> pcm_records_;
+    // Config::pose_graph: the window's builder, the solver's handle on a context of its own, and what the last optimize() built and found
+    std::unique_ptr<Context> pg_ctx_;
+    std::unique_ptr<SwarmPoseGraph> pg_;
+    omni_pgo* pg_handle_ = nullptr;
+    omni_pgo_params pg_params_ = pgo::default_params();
+    SwarmPoseGraph::Problem pg_problem_;
+    std::vector<double> pg_solution_;
+    PoseGraphStats pg_stats_;
     // remote_in_stream: the queue in arrival order, each frame with p = the local key frames handed over before it; next_seq_: local key frames handed over so far;
     // begun_seq_: every local key frame below it has its detector batch begun; remote_in_batch_: remote frames in the batch that is pending
     struct QueuedRemote { FisheyeFrameDescriptor f; int64_t p; };

@@ -69,6 +69,17 @@ PCM_SYMBOLS = ["omni_pcm_host_last_error", "omni_pipeline_set_pcm", "omni_pipeli
                "omni_pcm_filter_host"]
 PCM_STATS = ("edges_entered", "pairs_evaluated", "consistent_pairs", "clique_runs", "unknown_frames", "full_handles")
 _pcm_lib = None
+# the 4-DoF pose graph of the window: include/omni_host_posegraph.h, lib/libomni_host_posegraph.so (the same handle)
+POSEGRAPH_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_posegraph.so")
+POSEGRAPH_SYMBOLS = ["omni_posegraph_host_last_error", "omni_pipeline_set_pose_graph", "omni_pipeline_get_pose_graph", "omni_pipeline_optimize",
+                     "omni_pipeline_estimated_poses", "omni_pipeline_pose_graph_drift", "omni_pipeline_pose_graph_stats", "omni_pipeline_pose_graph_problem",
+                     "omni_pose_graph_build_host"]
+POSEGRAPH_STATS = ("optimize_calls", "poses", "ego_edges", "loop_edges", "loops_outside", "unreachable_drones", "merged", "best", "status", "iterations", "cg_iterations")
+POSEGRAPH_COUNTS = ("ego_edges", "loop_edges", "loops_outside", "unreachable_drones", "merged")
+# include/omni_host_posegraph.h omni_pose_graph_frame / omni_pose_graph_keyframe as numpy records
+POSE_GRAPH_FRAME_DTYPE = np.dtype([("drone", "<i4"), ("pose_index", "<i4"), ("keyframe_id", "<i8"), ("odom", "<f8", (4,)), ("init", "<f8", (4,)), ("pose", "<f8", (4,))])
+POSE_GRAPH_KEYFRAME_DTYPE = np.dtype([("drone", "<i4"), ("reserved", "<i4"), ("keyframe_id", "<i8"), ("pose", "<f8", (7,))])
+_posegraph_lib = None
 JPEGDEC_LIB_PATH = os.path.join(_HERE, "lib", "libomni_host_jpegdec.so")
 JPEGDEC_SYMBOLS = ["omni_jpegdec_host_last_error", "omni_pipeline_set_compressed_images", "omni_pipeline_get_compressed_images", "omni_pipeline_jpeg_corrupt",
                    "omni_pipeline_push_keyframe_jpeg", "omni_pipeline_run_jpeg", "omni_swarm_vins_is_compressed_images", "omni_pipeline_apply_vins_settings"]
@@ -407,6 +418,52 @@ def pcm_lib():
     return _pcm_lib
 
 
+def posegraph_lib():
+    global _posegraph_lib
+    if _posegraph_lib is None:
+        lib()
+        if not os.path.exists(POSEGRAPH_LIB_PATH):
+            raise OSError(f"{POSEGRAPH_LIB_PATH} is missing: run `make -C omni-swarm_amd`")
+        L = C.CDLL(POSEGRAPH_LIB_PATH)
+        ip = C.POINTER(C.c_int)
+        L.omni_posegraph_host_last_error.restype = C.c_char_p
+        L.omni_pipeline_set_pose_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.omni_pipeline_get_pose_graph.argtypes = [C.c_void_p, ip, ip, ip]
+        L.omni_pipeline_optimize.argtypes = [C.c_void_p, ip]
+        L.omni_pipeline_estimated_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip]
+        L.omni_pipeline_pose_graph_drift.argtypes = [C.c_void_p, C.POINTER(C.c_double), ip]
+        L.omni_pipeline_pose_graph_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        L.omni_pipeline_pose_graph_problem.argtypes = [C.c_void_p, ip, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(capi.PgoParams)]
+        L.omni_pose_graph_build_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, ip,
+                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip]
+        _posegraph_lib = L
+    return _posegraph_lib
+
+
+def pose_graph_build_host(keyframes, loops, self_id: int, window: int = 50, starts: int = 1, pos_covariance_per_meter: float = 0.01, yaw_covariance_per_meter: float = 0.003):
+    """host/pose_graph.hpp without a pipeline and without a GPU: keyframes (POSE_GRAPH_KEYFRAME_DTYPE, in the order seen) and loops (REMOTE_EDGE_DTYPE, in order) ->
+    dict(frames POSE_GRAPH_FRAME_DTYPE, poses [starts][n][4], fixed [n], edges capi.PGO_EDGE_DTYPE, and the counts of POSEGRAPH_COUNTS)"""
+    kf = np.ascontiguousarray(keyframes, dtype=POSE_GRAPH_KEYFRAME_DTYPE).reshape(-1)
+    lp = np.ascontiguousarray(loops, dtype=REMOTE_EDGE_DTYPE).reshape(-1)
+    L = posegraph_lib()
+    n_frames, sizes, counts = C.c_int(0), (C.c_int * 3)(), (C.c_int * 5)()
+
+    def call(frames, poses, fixed, edges):
+        rc = L.omni_pose_graph_build_host(self_id, window, starts, pos_covariance_per_meter, yaw_covariance_per_meter, kf.ctypes.data if len(kf) else None, len(kf),
+                                          lp.ctypes.data if len(lp) else None, len(lp), frames.ctypes.data if frames is not None and len(frames) else None,
+                                          0 if frames is None else len(frames), C.byref(n_frames), sizes, None if poses is None else poses.ctypes.data,
+                                          None if fixed is None else fixed.ctypes.data, 0 if fixed is None else len(fixed), None if edges is None else edges.ctypes.data,
+                                          0 if edges is None else len(edges), counts)
+        if rc:
+            raise capi.OmniError(f"omni_pose_graph_build_host: {L.omni_posegraph_host_last_error().decode()}")
+
+    call(None, None, None, None)
+    frames = np.zeros(n_frames.value, POSE_GRAPH_FRAME_DTYPE)
+    poses, fixed, edges = np.zeros((sizes[2], sizes[0], 4)), np.zeros(max(sizes[0], 1), np.uint8), np.zeros(max(sizes[1], 1), capi.PGO_EDGE_DTYPE)
+    call(frames, poses, fixed, edges)
+    return dict(frames=frames, poses=poses, fixed=fixed[:sizes[0]], edges=edges[:sizes[1]], **dict(zip(POSEGRAPH_COUNTS, (int(v) for v in counts))))
+
+
 def pcm_filter_host(edges, self_id: int, batches=None, redundant: bool = False, capacity: int = capi.PCM_DEFAULT_CAPACITY, params=None):
     """host/loop_outlier_rejection.hpp with its rows from omni_pcm_rows_host (no GPU): capi.PCM_EDGE_DTYPE records enter in calls of batches[0], batches[1], ..
     edges (None: one call).  Returns (good [n] bool: whether edge k passes afterwards, stats dict)."""
@@ -528,7 +585,8 @@ class KeyframePipeline:
                  inner_product_thres=0.3, init_mode_product_thres=0.2, match_index_dist=5, min_loop_num=30, min_direction_loop=3, geometry=False, pinhole_depth=None,
                  stereo_pinhole=None, device_landmarks=None, device_homography=None, send_img=False, jpg_quality=50, device_pnp=None, compressed_images=False, raw_fisheye=None, camera_model=None,
                  device_depth_landmarks=None, fit_pca=False, wire=False, device_wire=False, send_all_features=False, remote_in_stream=False, batch_verify=False,
-                 wire_img_desc="off", wire_loop_conn=False, pcm=False, pcm_thres=0.6, pcm_redundant=False, pcm_capacity=capi.PCM_DEFAULT_CAPACITY):
+                 wire_img_desc="off", wire_loop_conn=False, pcm=False, pcm_thres=0.6, pcm_redundant=False, pcm_capacity=capi.PCM_DEFAULT_CAPACITY,
+                 pose_graph=False, pose_graph_window=50, pose_graph_starts=1):
         """pinhole_depth: None = CameraConfig::STEREO_FISHEYE (4 directions x up/down views per key frame); a dict(fx, fy, cx, cy, depth_near, depth_far,
         accept_min_3d_pts) = CameraConfig::PINHOLE_DEPTH (launch/realsense.launch): one gray image + one depth image (set_depth) per key frame.
         stereo_pinhole: a dict(fx, fy, cx, cy[, src_width, src_height, triangle_thres, accept_min_3d_pts]) = CameraConfig::STEREO_PINHOLE: a left and a right
@@ -625,6 +683,57 @@ class KeyframePipeline:
             self.set_batch_verify(True)
         if pcm:
             self.set_pcm(True, pcm_thres, pcm_redundant, pcm_capacity)
+        if pose_graph:
+            self.set_pose_graph(True, pose_graph_window, pose_graph_starts)
+
+    def _pg(self, rc, what):
+        if rc:
+            raise capi.OmniError(f"{what}: {posegraph_lib().omni_posegraph_host_last_error().decode()}")
+
+    def set_pose_graph(self, on: bool, window: int = 50, starts: int = 1):
+        """before the first key frame: the 4-DoF pose graph of the last `window` key frames per drone (2..256) over ego motion and good_edges(), solved by optimize()
+        from `starts` initial pose sets (1..64); refused on the sharded database and without a geometry stage"""
+        self._pg(posegraph_lib().omni_pipeline_set_pose_graph(self.h, int(bool(on)), int(window), int(starts)), "omni_pipeline_set_pose_graph")
+
+    def pose_graph(self) -> dict:
+        on, window, starts = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._pg(posegraph_lib().omni_pipeline_get_pose_graph(self.h, C.byref(on), C.byref(window), C.byref(starts)), "omni_pipeline_get_pose_graph")
+        return dict(on=bool(on.value), window=window.value, starts=starts.value)
+
+    def optimize(self) -> int:
+        """solves the current window on the GPU (blocking); returns the kept start's status (capi.PGO_*)"""
+        st = C.c_int(0)
+        self._pg(posegraph_lib().omni_pipeline_optimize(self.h, C.byref(st)), "omni_pipeline_optimize")
+        return st.value
+
+    def estimated_poses(self) -> np.ndarray:
+        """every window key frame of the last optimize() (POSE_GRAPH_FRAME_DTYPE): drone, key frame id, pose = the estimate x y z yaw, odom = the odometry pose"""
+        n = C.c_int(0)
+        self._pg(posegraph_lib().omni_pipeline_estimated_poses(self.h, None, 0, C.byref(n)), "omni_pipeline_estimated_poses")
+        out = np.zeros(n.value, POSE_GRAPH_FRAME_DTYPE)
+        if len(out):
+            self._pg(posegraph_lib().omni_pipeline_estimated_poses(self.h, out.ctypes.data, len(out), C.byref(n)), "omni_pipeline_estimated_poses")
+        return out
+
+    def drift(self):
+        """this drone's newest estimated pose . inverse(its odometry pose) as x y z yaw, or None when the last optimize() held no key frame of this drone"""
+        out, valid = (C.c_double * 4)(), C.c_int(0)
+        self._pg(posegraph_lib().omni_pipeline_pose_graph_drift(self.h, out, C.byref(valid)), "omni_pipeline_pose_graph_drift")
+        return np.array(out[:]) if valid.value else None
+
+    def pose_graph_stats(self) -> dict:
+        st, cost = (C.c_int64 * 11)(), (C.c_double * 2)()
+        self._pg(posegraph_lib().omni_pipeline_pose_graph_stats(self.h, st, cost), "omni_pipeline_pose_graph_stats")
+        return dict(zip(POSEGRAPH_STATS, (int(v) for v in st)), initial_cost=cost[0], final_cost=cost[1])
+
+    def pose_graph_problem(self) -> dict:
+        """the exact problem the last optimize() solved: dict(poses [starts][n][4], fixed [n], edges capi.PGO_EDGE_DTYPE, params capi.PgoParams)"""
+        sizes, pr = (C.c_int * 3)(), capi.PgoParams()
+        self._pg(posegraph_lib().omni_pipeline_pose_graph_problem(self.h, sizes, None, None, 0, None, 0, None), "omni_pipeline_pose_graph_problem")
+        poses, fixed, edges = np.zeros((sizes[2], sizes[0], 4)), np.zeros(max(sizes[0], 1), np.uint8), np.zeros(max(sizes[1], 1), capi.PGO_EDGE_DTYPE)
+        self._pg(posegraph_lib().omni_pipeline_pose_graph_problem(self.h, sizes, poses.ctypes.data, fixed.ctypes.data, sizes[0], edges.ctypes.data, len(edges), C.byref(pr)),
+                 "omni_pipeline_pose_graph_problem")
+        return dict(poses=poses, fixed=fixed[:sizes[0]], edges=edges[:sizes[1]], params=pr)
 
     def _pcm(self, rc, what):
         if rc:
