@@ -172,7 +172,10 @@ int omni_sp_postprocess_dense(omni_sp* sp, const float* semi_host, const float* 
 /* test hook: one intermediate activation of the last forward pass as NCHW float32 (name in {"conv1a","conv1b",...,
  * "conv4b","heads","desc"}; post-ReLU, post-pool where the layer pools).  out may be NULL to query the shape only.
  * "desc_rows_in" / "desc_rows_out" (fp32-class paths behind a pass that sampled its descriptors sparsely): the compact cDa rows around the key points and
- * their convDb + norm, as they lie: [batch][4 max_num][256] (C = 4 max_num, H = 256, W = 1); rows of key points that do not exist are not meaningful. */
+ * their convDb + norm, as they lie: [batch][4 max_num][256] (C = 4 max_num, H = 256, W = 1); rows of key points that do not exist are not meaningful.
+ * "desc_raw" / "desc_norm_partial" (after any pass that ran the post-processing -- infer, enqueue + fetch, postprocess_dense --, batch <= that pass's): the sampled
+ * descriptors before the channel normalisation, [batch][max_num][256] (C = max_num, H = 256, W = 1; rows beyond an image's n_kps are not meaningful), and the
+ * per-channel sums of their squares over the 8 key-point segments, [batch][8][256] (C = 8, H = 256, W = 1), as they lie.  Plain copies: nothing is launched or changed. */
 int omni_sp_debug_layer(omni_sp* sp, const char* name, int batch, float* out_nchw_host, int* C, int* H, int* W);
 /* test hook: the kernel forms of the last forward pass (csrc/sp_plan.h), as bits: 1, 2, 4, 8 = conv1b, conv2a, conv2b, conv3a ran the Winograd kernel; 16 = conv1a
  * was fused into conv1b; 32 = the split detector head (detector_head_mfma16 over fp32 input); 64 = the sparse descriptor tail ran convdb_l2norm_split; 128 = the

@@ -759,6 +759,10 @@ class SuperPoint:
         return self._split(kps, n, d, sc)
 
     def debug_layer(self, name: str, batch: int = 1) -> np.ndarray:
+        """omni_sp_debug_layer: [batch, C, H, W] float32.  name: "conv1a" .. "conv4b", "heads", "desc" (an activation of the last forward pass, NCHW); "desc_rows_in" /
+        "desc_rows_out" (the sparse fp32 descriptor tail's compact rows, C = 4 max_num, H = 256, W = 1); "desc_raw" (the sampled descriptors before the channel
+        normalisation, C = max_num, H = 256, W = 1; rows beyond n_kps are not meaningful) / "desc_norm_partial" (their per-channel sums of squares in 8 key-point
+        segments, C = 8, H = 256, W = 1): after any pass that ran the post-processing (inference, fetch, postprocess_dense), batch <= that pass's"""
         c, h, w = C.c_int(), C.c_int(), C.c_int()
         _check(lib().omni_sp_debug_layer(self.h, name.encode(), batch, None, C.byref(c), C.byref(h), C.byref(w)))
         out = np.empty((batch, c.value, h.value, w.value), np.float32)

@@ -124,6 +124,16 @@ __device__ __forceinline__ int xcd_block_id(int enable) {
     const int n = (int)gridDim.x, b = (int)blockIdx.x;
     return (enable && (n & 7) == 0) ? (b & 7) * (n >> 3) + (b >> 3) : b;
 }
+// The descriptor sampler's coordinate of key-point coordinate k (superpoint_tensorrt.cpp:204-205 + grid_sampler's align_corners = false): g = 2 k / size - 1,
+// ((g + 1) size_c - 1) / 2, in IEEE single OPERATION BY OPERATION.  sp_sample_kernel and every restatement of it (sample_corner, the sparse descriptor heads of
+// conv.hip and conv_split.hip) take the cell (floor) and the weights from THIS function: they must agree to the bit.  The __f*_rn intrinsics do not give that: they are
+// plain operators in the HIP headers, and under hipcc's default -ffp-contract=fast-honor-pragmas (g + 1) size_c - 1 became one v_fma_f32 (no rounding of the
+// product; tests/test_gpu_sp_desc.py found it at the widths whose cell count is no power of two).  The pragma takes the contract flag off these operations.
+__device__ __forceinline__ float sp_sample_coord(float k, float size, float size_c) {
+#pragma clang fp contract(off)
+    const float g = (2.0f * k) / size - 1.0f;
+    return ((g + 1.0f) * size_c - 1.0f) / 2.0f;
+}
 #endif
 
 // getKeyPoints' threshold fused into the head's epilogue (superpoint_tensorrt.cpp:167-173: mask = prob > thres): with bits set, a lane stores the 32

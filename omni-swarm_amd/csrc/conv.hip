@@ -1523,10 +1523,7 @@ conv3x3_c128_sparse_kernel(const _Float16* __restrict__ in /*[B][Hc][Wc][128]*/,
         cx = cy = -4;
         if (kp >= n_kps[b]) return false;
         const float kx = kps_xy[((int64_t)b * max_num + kp) * 2 + 0], ky = kps_xy[((int64_t)b * max_num + kp) * 2 + 1];
-        const float gx = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, kx), fW), 1.0f);
-        const float gy = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, ky), fH), 1.0f);
-        const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.0f), fWc), 1.0f), 2.0f);
-        const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.0f), fHc), 1.0f), 2.0f);
+        const float ix = sp_sample_coord(kx, fW, fWc), iy = sp_sample_coord(ky, fH, fHc);
         cx = (int)floorf(ix) + (slot & 1); cy = (int)floorf(iy) + ((slot >> 1) & 1);
         return cx >= 0 && cx < Wc && cy >= 0 && cy < Hc;
     };
@@ -2480,10 +2477,7 @@ convdb_sparse_kernel(const _Float16* __restrict__ in, int in_cstride, const _Flo
         wgt = 0.f;
         if (kp >= n_kps[b]) return -1;
         const float kx = kps_xy[((int64_t)b * max_num + kp) * 2 + 0], ky = kps_xy[((int64_t)b * max_num + kp) * 2 + 1];
-        const float gx = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, kx), fW), 1.0f);
-        const float gy = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, ky), fH), 1.0f);
-        const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.0f), fWc), 1.0f), 2.0f);
-        const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.0f), fHc), 1.0f), 2.0f);
+        const float ix = sp_sample_coord(kx, fW, fWc), iy = sp_sample_coord(ky, fH, fHc);
         const float fx0 = floorf(ix), fy0 = floorf(iy);
         const int cx = (int)fx0 + (slot & 1), cy = (int)fy0 + ((slot >> 1) & 1);
         const float wx = (slot & 1) ? ix - fx0 : (fx0 + 1.f) - ix, wy = (slot & 2) ? iy - fy0 : (fy0 + 1.f) - iy;

@@ -443,10 +443,7 @@ sp_sample_kernel(const float* __restrict__ desc_nhwc, int W, int H, int max_num,
         const float kx = kps_xy[((int64_t)b * max_num + i) * 2 + 0];
         const float ky = kps_xy[((int64_t)b * max_num + i) * 2 + 1];
         // grid = 2*k/size - 1 (:204-205); unnormalise with align_corners=false: ((g+1)*size_c - 1)/2
-        const float gx = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, kx), fW), 1.0f);
-        const float gy = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, ky), fH), 1.0f);
-        const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.0f), fWc), 1.0f), 2.0f);
-        const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.0f), fHc), 1.0f), 2.0f);
+        const float ix = sp_sample_coord(kx, fW, fWc), iy = sp_sample_coord(ky, fH, fHc);
         const float fx0 = floorf(ix), fy0 = floorf(iy);
         const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
         const float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = (fx0 + 1.f) - ix, wy0 = (fy0 + 1.f) - iy;
@@ -467,10 +464,7 @@ sp_sample_kernel(const float* __restrict__ desc_nhwc, int W, int H, int max_num,
 __device__ __forceinline__ void sample_corner(float kx, float ky, int W, int H, int j, int& cx, int& cy, float& wgt) {
     const int Wc = W >> 3, Hc = H >> 3;
     const float fW = (float)W, fH = (float)H, fWc = (float)Wc, fHc = (float)Hc;
-    const float gx = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, kx), fW), 1.0f);
-    const float gy = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, ky), fH), 1.0f);
-    const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.0f), fWc), 1.0f), 2.0f);
-    const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.0f), fHc), 1.0f), 2.0f);
+    const float ix = sp_sample_coord(kx, fW, fWc), iy = sp_sample_coord(ky, fH, fHc);
     const float fx0 = floorf(ix), fy0 = floorf(iy);
     const float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = (fx0 + 1.f) - ix, wy0 = (fy0 + 1.f) - iy;
     cx = (int)fx0 + (j & 1); cy = (int)fy0 + (j >> 1);

@@ -57,6 +57,7 @@ struct omni_sp {
     void* da_compact = nullptr;              // [B][max_num][4][256] fp16: cDa at the corner cells of the key points
     float *cx32 = nullptr, *cy32 = nullptr;  // fp32 paths: the gathered cDa rows / their convDb + norm, [ceil8(B * max_num * 4)][256] each
     int last_batch = 0;                      // images of the last forward pass (0: none yet -- nothing to make a dense map from)
+    int post_batch = 0;                      // images of the last pass that ran sp_postprocess (0: none yet -- pb.raw_desc / pb.norm_partial hold nothing)
     void* wDbFrag = nullptr;                    // convDb as register-resident fp16 A fragments (fused convDb + L2 norm, fp16 path)
     void* wDbFragHi = nullptr; void* wDbFragLo = nullptr;      // OMNI_PREC_SPLIT: the same as (hi, lo) pairs (convdb_l2norm_split); OMNI_SP_SPLIT_DB=0: exact-f32 convDb
     float* bias_heads = nullptr;             // [512]
@@ -544,7 +545,10 @@ static int sp_forward(omni_sp* s, const uint8_t* gray_dev, int stride, int batch
     else if (p.desc == SP_DESC_DENSE_GENERIC) rc = sp_desc_dense_generic(s, p, batch);
     // (every other tail: convDb runs inside the post-processing, at the key points only)
     if (rc || (rc = mark())) return rc;
-    if (p.run_post && (rc = sp_postprocess(st, post_params(s), s->pb, s->semi, s->draw, batch, sp_sparse_desc(s, p)))) return rc;
+    if (p.run_post) {
+        if ((rc = sp_postprocess(st, post_params(s), s->pb, s->semi, s->draw, batch, sp_sparse_desc(s, p)))) return rc;
+        s->post_batch = batch;
+    }
     return mark();
 }
 
@@ -754,6 +758,7 @@ int omni_sp_postprocess_dense(omni_sp* s, const float* semi_host, const float* d
     omni::SpSparseDesc sd;
     sd.cand_from_list = s->facts.fused_cand;       // threshold + window masks as the pipeline makes them (OMNI_SP_FUSED_CAND=0: sp_cand_kernel)
     if ((rc = omni::sp_postprocess(st, omni::post_params(s), s->pb, s->semi, s->draw, batch, sd))) return rc;
+    s->post_batch = batch;
     return omni::sp_fetch_locked(s, batch, kps_xy, n_kps, desc, scores);
 }
 
@@ -772,6 +777,20 @@ int omni_sp_debug_layer(omni_sp* s, const char* name, int batch, float* out_nchw
         std::lock_guard<std::mutex> lk(s->mu);
         (void)hipSetDevice(s->ctx->device);
         OMNI_HIP_TRY(hipMemcpyAsync(out_nchw_host, rows_in ? s->cx32 : s->cy32, (size_t)batch * s->max_num * 4 * 256 * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+        OMNI_HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+        return OMNI_OK;
+    }
+    const bool d_raw = strcmp(name, "desc_raw") == 0;
+    if (d_raw || strcmp(name, "desc_norm_partial") == 0) {     // the descriptor tail's stage outputs as they lie: raw_desc [batch][max_num][256], norm_partial [batch][8][256] fp32
+        std::lock_guard<std::mutex> lk(s->mu);
+        OMNI_REQUIRE(batch <= s->post_batch, OMNI_ERR_INVALID, "layer %s: no post-processing pass of >= %d images to take it from", name, batch);
+        const int rows = d_raw ? s->max_num : 8;
+        if (C) *C = rows;
+        if (Hl) *Hl = 256;
+        if (Wl) *Wl = 1;
+        if (!out_nchw_host) return OMNI_OK;
+        (void)hipSetDevice(s->ctx->device);
+        OMNI_HIP_TRY(hipMemcpyAsync(out_nchw_host, d_raw ? s->pb.raw_desc : s->pb.norm_partial, (size_t)batch * rows * 256 * 4, hipMemcpyDeviceToHost, s->ctx->stream));
         OMNI_HIP_TRY(hipStreamSynchronize(s->ctx->stream));
         return OMNI_OK;
     }
